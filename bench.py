@@ -2,7 +2,7 @@
 """bench.py -- megapixels/sec of tile + blend + QA on a synthetic 720p -> 200 MP job (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 200MP|150MP|100MP|4MP|200MP-kd ...]
-                    [--mode strips|batch] [--no-pcie]
+                    [--mode strips|batch] [--dump-outputs DIR] [--full [--no-pcie] [--no-cpu-baseline] [--no-prof] [--sweep ...]]
 
 One process per GPU (N > 1: launched by torch.distributed.run, RCCL over xGMI).  A "step" is one
 pass of the hot path over one synthetic image: overlap-tile extract of the 5x5 tile grid from the
@@ -14,9 +14,16 @@ BASELINE metric).  --mode batch is BASELINE config 4: every rank runs the whole 
 communication on the data path (weak scaling).  "-kd" workloads use the non-uniform k-d tiling of config 5.
 
 Prints ONE JSON line (rank 0).  ``value`` = canvas megapixels / max-over-ranks wall time per step,
-inputs already resident in HBM.  ``roofline`` describes the dominant kernel (HIP-event time measured
-here, on the stream the kernels run on); ``cpu_baseline`` is the CPU oracle (oracle/sr_oracle.c,
-OpenMP) timed on this node's host cores on a bounded sample of the same workload.
+inputs already resident in HBM; ``ms_per_step`` = milliseconds of one timed step (--steps of them).
+A plain run only sets up, warms up, times the steps and prints the line.  ``--full`` adds everything
+else: ``roofline`` describes the dominant kernel (HIP-event time measured here, on the stream the
+kernels run on), the per-kernel table, the PCIe and single-image figures, the ``sweep`` of further
+workloads, ``cpu_baseline`` -- the CPU oracle
+(oracle/sr_oracle.c, OpenMP) timed on this node's host cores on a bounded sample of the same workload
+-- and ``parity``, that sample through the HIP pipeline compared with the oracle.
+
+``--dump-outputs DIR`` writes what the timed path computed in its last step (the canvas, sampled, and
+the scores) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -236,6 +243,29 @@ def parity_vs_oracle(sample: dict, geo_full, device_index: int) -> dict:
             "oracle": "restated reference CPU path; its OpenCV-defined semantics are parity-unpinned (DESIGN.md 2)"}
 
 
+DUMP_SAMPLE = 1 << 21        # canvas bytes kept by --dump-outputs: 8 MB of values + 16 MB of their indices
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir: str, canvas: np.ndarray, quality: dict) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the blended u8 canvas [H, W*cn] and
+    the scores -- as out_dir/<name>.npy in float32 / float64.  A 200 MP canvas is 600 MB of bytes, so it is kept as a fixed,
+    seeded sample of its bytes (with their flat indices) plus its exact row and column sums (~25 MB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = canvas.reshape(-1)
+    k = min(flat.size, DUMP_SAMPLE)
+    idx = np.arange(flat.size) if k == flat.size else \
+        np.sort(np.random.default_rng(DUMP_SEED).choice(flat.size, k, replace=False))
+    arrays = {"canvas_sample": flat[idx].astype(np.float32),
+              "canvas_sample_index": idx.astype(np.float64),
+              "canvas_row_sums": canvas.sum(axis=1, dtype=np.int64).astype(np.float64),
+              "canvas_col_sums": canvas.sum(axis=0, dtype=np.int64).astype(np.float64)}
+    for name, v in quality.items():
+        arrays[name] = np.array([v], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 _STAGE_FILE = os.environ.get("SR_BENCH_STAGE_FILE")
 
 
@@ -257,8 +287,10 @@ def _launch_ranks(n: int, argv, deadline_s: float) -> int:
     return _launch.launch_ranks(n, os.path.abspath(__file__), argv, deadline_s, who="bench.py")
 
 
-def run_workload(args, workload: str, steps: int, warmup: int, detailed: bool, dist_state) -> dict:
-    """One measurement of `workload` on the ranks of `dist_state`; returns the result record on rank 0 (None elsewhere)."""
+def run_workload(args, workload: str, steps: int, warmup: int, detailed: bool, dist_state, dump_dir=None) -> dict:
+    """One measurement of `workload` on the ranks of `dist_state`; returns the result record on rank 0 (None elsewhere).
+    `detailed` (--full) adds the per-kernel, PCIe, single-image and CPU-baseline figures; `dump_dir` receives the outputs
+    of the last timed step (dump_outputs)."""
     import torch
     import torch.distributed as dist
     import device_pipeline as dp
@@ -381,6 +413,16 @@ def run_workload(args, workload: str, steps: int, warmup: int, detailed: bool, d
     _stage(f"{workload}: timed region ({steps} steps) done")
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(steps))
     prof_timed = {} if no_prof else prof_ctl.get()               # the dominant kernel, inside the timed region
+    if dump_dir:
+        # before anything else runs on the pipeline: the strips of N > 1 are gathered on rank 0 (batch: rank 0's own image)
+        canvas = pipe.gather_canvas(0) if (world > 1 and not batch) else pipe.canvas
+        quality = pipe.metrics()
+        if rank == 0:
+            if lp_model is not None:
+                quality[f"lpips_{args.lpips}_synthetic_weights"] = lp_value
+            dump_outputs(dump_dir, canvas.cpu().numpy(), quality)
+        del canvas
+        _stage(f"{workload}: outputs written")
     prof, prof_steps = {}, max(1, min(steps, 5))
     # one image at a time, nothing overlapped, no per-kernel events: what an isolated image costs (the image stream above
     # hides the assessment of image i under the pyramids of image i+1)
@@ -632,18 +674,27 @@ def main() -> int:
     ap.add_argument("--mode", default="strips", choices=["strips", "batch"],
                     help="strips: one image over all ranks (strong scaling, the BASELINE metric); "
                          "batch: one image per rank, no data-path communication (config 4, weak scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, ~25 MB): "
+                         "a fixed, seeded sample of the canvas bytes with their indices, the canvas's row and column sums, "
+                         "and the scores")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel table and roofline (kernel timing in the warm-up "
+                         "and around the dominant kernel in the timed region), PCIe copies, single-image latency, the "
+                         "--sweep workloads, the CPU baseline and the parity check against the oracle")
     ap.add_argument("--sweep", default="100MP,150MP",
-                    help="comma list of further workloads measured briefly after the main one and reported in the "
+                    help="with --full: comma list of further workloads measured briefly after the main one and reported in the "
                          "`sweep` object of the same JSON line (north_star: 100 / 150 / 200 MP); '' or 'none' to skip")
     ap.add_argument("--sweep-steps", type=int, default=8)
     ap.add_argument("--no-pcie", action="store_true",
-                    help="skip the host->device (inputs) / device->host (canvas) timing that N=1 runs report beside the resident rate")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: skip the host->device (inputs) / device->host (canvas) timing that N=1 runs report "
+                         "beside the resident rate")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
     ap.add_argument("--lpips", default="none", choices=["none", "alex", "vgg"],
                     help="BASELINE config 5 whole: add LPIPS(canvas, reference) of this backbone to every timed image (seeded "
                          "synthetic weights -- the pretrained ones are not available offline; timing does not depend on their "
                          "values); one GPU or batch mode only.  Not part of the default line.")
-    ap.add_argument("--no-prof", action="store_true", help="skip the per-kernel HIP-event timing")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: skip the per-kernel HIP-event timing")
     ap.add_argument("--deadline-s", type=float, default=900.0,
                     help="self-launched N > 1 runs: after this many seconds the launcher terminates the ranks still running, "
                          "prints every rank's last completed stage and exits 124")
@@ -651,6 +702,9 @@ def main() -> int:
 
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return _launch_ranks(args.gpus, sys.argv[1:], args.deadline_s)   # children only; this process never touches the GPU
@@ -687,8 +741,8 @@ def main() -> int:
     _stage(f"process group ({backend}, world {world}) initialised")
     state = (world, rank, local_rank, backend, dev)
 
-    out = run_workload(args, args.workload, args.steps, args.warmup, True, state)
-    sweep = [w for w in args.sweep.split(",") if w and w != "none" and w != args.workload]
+    out = run_workload(args, args.workload, args.steps, args.warmup, args.full, state, args.dump_outputs)
+    sweep = [w for w in args.sweep.split(",") if w and w != "none" and w != args.workload] if args.full else []
     sweep_out = {}
     for wl in sweep:
         if wl not in WORKLOAD_CHOICES:
@@ -699,7 +753,8 @@ def main() -> int:
             sweep_out[wl] = {k: r[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "step_ms", "quality")}
             sweep_out[wl]["workload"] = r["config"]["workload"]
     if rank == 0:
-        out["sweep"] = sweep_out
+        if args.full:
+            out["sweep"] = sweep_out
         print(json.dumps(out), flush=True)
     _stage("JSON line printed")
     if world > 1:

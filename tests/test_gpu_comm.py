@@ -196,10 +196,11 @@ def test_one_rccl_and_one_rocm_smi_mapped(ctx):
         comm.close()
 
 
-def test_bench_two_rank_rehearsal_matches_one_rank():
+def test_bench_two_rank_rehearsal_matches_one_rank(tmp_path):
     """The driver's scale command has a tested twin: `SR_DIST_BACKEND=gloo python bench.py --gpus 2 --workload 4MP` -- the
     self-launcher plus two ranks sharing this GPU (3 processes; rows staged through the host, flagged as a rehearsal) --
-    prints ONE JSON line with n_gpus 2 / strips2, per-rank exchange records, and exactly the scores of the 1-rank run."""
+    prints ONE JSON line with n_gpus 2 / strips2, per-rank exchange records, and exactly the scores of the 1-rank run;
+    its --dump-outputs (the strips gathered on rank 0) equal the 1-rank run's."""
     import json
     import os
     import subprocess
@@ -217,8 +218,19 @@ def test_bench_two_rank_rehearsal_matches_one_rank():
         assert len(lines) == 1, r.stdout[-2000:]
         return json.loads(lines[0])
 
-    two = run({"SR_DIST_BACKEND": "gloo"}, ["--gpus", "2", "--deadline-s", "500"])
-    one = run({}, ["--gpus", "1"])
+    d2, d1 = str(tmp_path / "two"), str(tmp_path / "one")
+    two = run({"SR_DIST_BACKEND": "gloo"}, ["--gpus", "2", "--deadline-s", "500", "--dump-outputs", d2])
+    one = run({}, ["--gpus", "1", "--dump-outputs", d1])
+    names = sorted(os.listdir(d1))
+    assert names == sorted(os.listdir(d2)) and "canvas_sample.npy" in names and "psnr.npy" in names
+    for n in names:
+        a, b = np.load(os.path.join(d2, n)), np.load(os.path.join(d1, n))
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype
+        if n.startswith("canvas") or n == "psnr.npy":
+            assert np.array_equal(a, b), n
+        else:
+            np.testing.assert_allclose(a, b, rtol=1e-12, err_msg=n)
+    assert np.load(os.path.join(d1, "psnr.npy"))[0] == one["quality"]["psnr"]
     assert two["n_gpus"] == 2 and two["config"]["parallelism"] == "strips2" and two["scaling"] == "strong"
     assert "REHEARSAL" in two["data"] and one["data"] == "synthetic"
     assert two["quality"]["psnr"] == one["quality"]["psnr"]

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run(split):
     env = dict(os.environ)
     env["SR_ASSESS_SPLIT"] = "1" if split else "0"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--sweep", "none",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "3", "--sweep", "none",
                         "--no-cpu-baseline", "--no-pcie"], env=env, capture_output=True, text=True, timeout=900)
     if r.returncode != 0:
         raise SystemExit(r.stderr[-3000:])

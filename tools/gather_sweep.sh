@@ -4,13 +4,14 @@ set -u
 REPS=${1:-2}
 OUT=gpurun_out/gather_sweep.txt
 : > $OUT
+TMP=${OUT%.txt}_tmp
 run() {   # name, env assignments...
   local name=$1; shift
-  env "$@" python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-pcie --sweep none > gpurun_out/gs_tmp.json 2> gpurun_out/gs_tmp.err || echo "$name failed" >> $OUT
-  python - "$name" >> $OUT <<'P'
+  env "$@" python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-pcie --sweep none > $TMP.json 2> $TMP.err || echo "$name failed" >> $OUT
+  python - "$name" "$TMP.json" >> $OUT <<'P'
 import json, sys
 try:
-    d = json.loads(open("gpurun_out/gs_tmp.json").read().strip().splitlines()[-1])
+    d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
     fg = d["kernels"]["final_gather"]
     print(f"{sys.argv[1]:34s} step {d['ms_per_step']:.4f} median {d['step_ms']['median']:.4f} gather {fg['ms_per_step']:.4f} parts {fg.get('parts_ms')}")
 except Exception as e:

@@ -7,7 +7,7 @@ OUT=gpurun_out/pmc_$TAG
 export TMPDIR=/tmp
 rm -rf "$OUT"; mkdir -p "$OUT"
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/$C" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prof --no-pcie --sweep none "$@" \
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/$C" -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prof --no-pcie --sweep none "$@" \
       > /dev/null 2> "$OUT/$C.err" || echo "$C failed"
 done
 python3 - "$OUT" <<'PY'
