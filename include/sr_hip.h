@@ -306,6 +306,30 @@ SR_API int sr_feather_merge_dt(sr_ctx *ctx, int dtype, const sr_merge_tile *h_ti
                                const int64_t *h_strides, int blending, uint8_t *d_canvas, int64_t canvas_stride,
                                int canvas_h, int canvas_w);
 
+/* BlendingModule.gradient_domain_fusion (blending_module.py:1377-1489 with _reconstruct_from_gradients :1491-1523): n tiles
+ * of dtype SR_U8 or SR_F32 (the reference's astype(float32) of any other type is the caller's), h x w x cn (cn 1..4) with
+ * their canvas rectangles (x, y = the reference's position (y, x); 0 <= x < canvas_w, 0 <= y < canvas_h, min side >= 8).
+ * Per channel the float32 Sobel of each tile (reflect-101 at the TILE's borders) times its cosine weight map
+ * (feather width min(h, w) // 8) is accumulated in list order, divided by max(sum of weights, 1e-6f), summed along rows
+ * (np.cumsum, axis=1) and along columns (axis=0) as sequential fp32 chains, halved, clipped to [0, 255] and truncated into
+ * the u8 canvas.  d_work: canvas_h * canvas_w * cn floats of device workspace (the row sums).  Asynchronous. */
+SR_API int sr_gradient_fusion(sr_ctx *ctx, int dtype, void *const *h_d_tiles, const int64_t *h_strides,
+                              const sr_tile_rect *h_rects, int n, int cn, int canvas_h, int canvas_w, uint8_t *d_canvas,
+                              int64_t canvas_stride, float *d_work);
+/* compute_blend_quality's gradient fields (blending_module.py:1600-1606): over every element of the u8 image (cn 1..4) the
+ * float32 Sobel gx, gy (reflect-101 at the image border, exact integers here); *h_sum_sq receives the exact sum of
+ * gx^2 + gy^2, *h_sum_mag the fp64 sum of sqrt(gx^2 + gy^2).  mean = sum_mag / N, std = sqrt(sum_sq / N - mean^2). */
+SR_API int sr_gradient_stats_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, int cn,
+                                uint64_t *h_sum_sq, double *h_sum_mag);
+/* compute_blend_quality's per-tile SSIM (blending_module.py:1584-1596 with _compute_ssim :855-903): for tile i (rectangle
+ * h_rects[i], u8, cn 1, 3 or 4 like the canvas) the ROI canvas[y:y+h, x:x+w] clipped by the canvas; when the clip changes
+ * its size the tile is first resized to the ROI like cv2.resize(INTER_LINEAR).  Gray = cv2.COLOR_BGR2GRAY applied to the
+ * RGB data (channel 0 takes the blue weight; cn 1: the value itself).  h_sums[5 i .. 5 i + 4] receive the exact sums of
+ * a, b, a^2, b^2, a b over the ROI (a: canvas gray, b: tile gray); the float64 SSIM formula is the caller's. */
+SR_API int sr_tile_ssim_sums_u8(sr_ctx *ctx, const uint8_t *d_canvas, int64_t canvas_stride, int canvas_h, int canvas_w,
+                                int cn, const sr_tile_rect *h_rects, void *const *h_d_tiles, const int64_t *h_strides, int n,
+                                int gray_shift, uint64_t *h_sums);
+
 /* ---- quality metrics (quality_assessment_module.py:277-417) ---------------------------- */
 /* Sum of squared differences over h rows of rowlen u8 elements -> *h_sse (exact integer).
  * PSNR = 10 log10(data_range^2 / (sse / (h*rowlen))) is finished on the host (and partial sums

@@ -126,6 +126,10 @@ SIGNATURES = {
     "sr_weighted_fusion_host": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(TileRect), _i, _i, _i, _i, _i, _vp, _vp]),
     "sr_feather_merge": (_i, [_vp, C.POINTER(MergeTile), _i, C.POINTER(_vp), C.POINTER(_i64), _i, _vp, _i64, _i, _i]),
     "sr_feather_merge_dt": (_i, [_vp, _i, C.POINTER(MergeTile), _i, C.POINTER(_vp), C.POINTER(_i64), _i, _vp, _i64, _i, _i]),
+    "sr_gradient_fusion": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(TileRect), _i, _i, _i, _i, _vp, _i64, _vp]),
+    "sr_gradient_stats_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(C.c_uint64), C.POINTER(_dbl)]),
+    "sr_tile_ssim_sums_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(TileRect), C.POINTER(_vp), C.POINTER(_i64), _i, _i,
+                                  C.POINTER(C.c_uint64)]),
     "sr_sse_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i64, C.POINTER(C.c_uint64)]),
     "sr_sse_u8_async": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i64, _vp]),
     "sr_psnr_from_sse": (_dbl, [C.c_uint64, C.c_uint64, _dbl]),
@@ -619,6 +623,37 @@ class Context:
     def resize_cubic_window_u8(self, d_src, src_stride, h, w, cn, dh, dw, x0, y0, ww, wh, d_dst, dst_stride):
         check(self.lib.sr_resize_cubic_window_u8(self.handle, C.c_void_p(d_src), src_stride, h, w, cn, dh, dw, x0, y0,
                                                  ww, wh, C.c_void_p(d_dst), dst_stride))
+
+    def gradient_fusion(self, dtype: int, d_tiles: Sequence[int], strides: Sequence[int], rects_xywh, cn: int, h: int, w: int,
+                        d_canvas: int, canvas_stride: int, d_work: int):
+        """sr_gradient_fusion: tiles in HBM (SR_U8 / SR_F32), canvas rectangles (x, y, w, h) -> u8 canvas; d_work holds
+        h * w * cn floats.  Asynchronous."""
+        n = len(rects_xywh)
+        rects = (TileRect * n)(*[TileRect(int(x), int(y), int(tw), int(th)) for (x, y, tw, th) in rects_xywh])
+        ptrs = (C.c_void_p * n)(*[C.c_void_p(p) for p in d_tiles])
+        st = (C.c_int64 * n)(*[int(v) for v in strides])
+        check(self.lib.sr_gradient_fusion(self.handle, int(dtype), ptrs, st, rects, n, int(cn), int(h), int(w),
+                                          C.c_void_p(d_canvas), int(canvas_stride), C.c_void_p(d_work)))
+
+    def gradient_stats_u8(self, d_img: int, stride: int, h: int, w: int, cn: int) -> Tuple[int, float]:
+        """-> (exact sum of gx^2 + gy^2, fp64 sum of sqrt(gx^2 + gy^2)) of the u8 image's float32 Sobel."""
+        sq, mag = C.c_uint64(0), C.c_double(0.0)
+        check(self.lib.sr_gradient_stats_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w), int(cn),
+                                            C.byref(sq), C.byref(mag)))
+        return sq.value, mag.value
+
+    def tile_ssim_sums_u8(self, d_canvas: int, canvas_stride: int, h: int, w: int, cn: int, rects_xywh,
+                          d_tiles: Sequence[int], strides: Sequence[int], gray_shift: int = 15) -> np.ndarray:
+        """-> (n, 5) exact sums of a, b, a^2, b^2, a b (a: gray canvas ROI, b: gray tile, resized to a clipped ROI)."""
+        n = len(rects_xywh)
+        out = np.zeros((max(n, 1), 5), dtype=np.uint64)
+        rects = (TileRect * max(n, 1))(*[TileRect(int(x), int(y), int(tw), int(th)) for (x, y, tw, th) in rects_xywh])
+        ptrs = (C.c_void_p * max(n, 1))(*[C.c_void_p(p) for p in d_tiles])
+        st = (C.c_int64 * max(n, 1))(*[int(v) for v in strides])
+        check(self.lib.sr_tile_ssim_sums_u8(self.handle, C.c_void_p(d_canvas), int(canvas_stride), int(h), int(w), int(cn),
+                                            rects, ptrs, st, n, int(gray_shift),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out[:n]
 
     # numpy-in / numpy-out conveniences (stage through HBM) ----------------------------------
     def pyr_down_np(self, img: np.ndarray) -> np.ndarray:

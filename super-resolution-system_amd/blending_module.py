@@ -6,9 +6,10 @@ blend hot path (reference blending_module.py:38-56,96-136,164-363,369-561,661-76
 (include/sr_hip.h) -- there is no NumPy/OpenCV compute path here and no CPU fallback: without
 libsrhip.so or a GPU the compute methods raise.
 
-Out of scope for this path: Poisson / gradient-domain fusion and seam repair -- those methods exist
-so callers get a clear NotImplementedError instead of an AttributeError.  Built from SURVEY 8(f): detect_seams (rank 1),
-multi_band_fusion, feather_blend and color_correction (rank 4).
+Out of scope for this path: Poisson fusion and seam repair -- those methods exist so callers get a clear
+NotImplementedError instead of an AttributeError.  Built from SURVEY 8(f): detect_seams (rank 1), multi_band_fusion,
+feather_blend and color_correction (rank 4); since then gradient_domain_fusion and the module-level compute_blend_quality
+(blending_module.py:1377-1489, 1563-1608).
 
 Reference quirks kept: bare arrays without output_shape fail like the
 reference (ValueError: max() of an empty sequence); the canvas perimeter, where every tile's cosine
@@ -367,8 +368,43 @@ class BlendingModule:
         images, positions, shape = self._collect(tiles, output_shape, guess_without_shape=True)
         return self._fuse(images, positions, shape, "ones", laplacian=False)
 
-    def gradient_domain_fusion(self, *a, **k):
-        self._out_of_scope("gradient_domain_fusion")
+    def gradient_domain_fusion(self, tiles: List[np.ndarray], positions: List[Tuple[int, int]],
+                               output_shape: Tuple[int, int]) -> np.ndarray:
+        """blending_module.py:1377-1489 (+ _reconstruct_from_gradients :1491-1523): the float32 Sobel of every tile
+        (reflect-101 at the tile's own borders, computed on the whole tile and then cropped to the canvas) weighted by its
+        cosine map, accumulated in list order, normalised by max(sum of weights, 1e-6), integrated as cumsum along x plus
+        cumsum along y, halved, clipped and truncated to uint8 -- in two HIP passes (sr_gradient_fusion), each cumsum a
+        sequential fp32 chain as NumPy's.  Positions are (y, x) and must lie in [0, H) x [0, W): the reference slices a tile
+        at a negative or outside position inconsistently (negative starts wrap, its crop goes empty), so those raise
+        ValueError here, as do mixed ndim, channel counts unlike tiles[0] and tiles whose smaller side is below 8 (a zero
+        feather width: the reference's weights are NaN).  Tiles other than uint8 go through astype(float32) like the
+        reference's; integer-valued data gives the reference's canvas byte for byte."""
+        images, pos, shape, cn = _check_tile_list(tiles, positions, output_shape, "gradient_domain_fusion")
+        if cn > 4:
+            raise NotImplementedError(f"gradient_domain_fusion: {cn} channels (1-4 on the HIP path)")
+        for im in images:
+            if min(im.shape[:2]) < 8:
+                raise ValueError(f"gradient_domain_fusion: tile of {im.shape[0]}x{im.shape[1]}; a side below 8 gives the "
+                                 f"reference a zero feather width (NaN weights)")
+        is_u8 = all(im.dtype == np.uint8 for im in images)
+        arrs = [np.ascontiguousarray(im if is_u8 or im.dtype == np.float32 else im.astype(np.float32)) for im in images]
+        es = 1 if is_u8 else 4
+        H, W = shape
+        ctx = self._ctx()
+        bufs = [ctx.upload(a) for a in arrs]
+        work = canvas = None
+        try:
+            work = ctx.alloc(H * W * cn * 4)
+            canvas = ctx.alloc(H * W * cn)
+            ctx.gradient_fusion(_native.SR_U8 if is_u8 else _native.SR_F32, [b.ptr for b in bufs],
+                                [a.shape[1] * cn * es for a in arrs], [(x, y, a.shape[1], a.shape[0]) for a, (y, x) in
+                                                                       zip(arrs, pos)], cn, H, W, canvas.ptr, W * cn, work.ptr)
+            return ctx.download(canvas.ptr, (H, W) if images[0].ndim == 2 else (H, W, cn), np.uint8)
+        finally:
+            ctx.sync()
+            for b in bufs + [work, canvas]:
+                if b is not None:
+                    b.free()
 
     def detect_seams(self, result: np.ndarray, tiles: List[Union[np.ndarray, TileInfo]], window_size: int = 16,
                      stride: int = 8) -> List[Seam]:
@@ -517,6 +553,88 @@ class BlendingModule:
             ctx.sync()
             for b in (d_img, d_ref, out):
                 b.free()
+
+
+def _check_tile_list(tiles, positions, output_shape, what: str):
+    """Argument checks shared by gradient_domain_fusion and compute_blend_quality, before any device call: the (tile,
+    position) pairs as the reference's zip() forms them, tiles all HxW or all HxWxC with tiles[0]'s channel count, and every
+    position inside the canvas.  -> (arrays, [(y, x)], (H, W), channels)."""
+    H, W = int(output_shape[0]), int(output_shape[1])
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: output shape {H}x{W}")
+    images = [np.asarray(t) for t in tiles]
+    if not images:
+        raise ValueError(f"{what}: no tiles")
+    nd, chans = images[0].ndim, images[0].shape[2:]
+    for im in images:
+        if im.ndim not in (2, 3) or im.ndim != nd:
+            raise ValueError(f"{what}: tiles must all be HxW or all HxWxC arrays")
+        if im.shape[2:] != chans:
+            raise ValueError(f"{what}: tiles have different channel counts ({im.shape[2:]} vs {chans})")
+        if im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError(f"{what}: empty tile")
+    pairs = list(zip(images, positions))
+    pos = []
+    for im, p in pairs:
+        y, x = int(p[0]), int(p[1])
+        if not (0 <= y < H and 0 <= x < W):
+            raise ValueError(f"{what}: position (y={y}, x={x}) outside the {H}x{W} canvas")
+        pos.append((y, x))
+    return [im for im, _ in pairs], pos, (H, W), (chans[0] if chans else 1)
+
+
+def compute_blend_quality(result: np.ndarray, tiles: List[np.ndarray], positions: List[Tuple[int, int]]) -> Dict[str, float]:
+    """blending_module.py:1563-1608 for uint8 data.  Per tile the global SSIM (_compute_ssim, :855-903) of the canvas ROI
+    result[y:y+h, x:x+w] against the tile -- resized to the ROI like cv2.resize(INTER_LINEAR) when the canvas clips it --
+    both as cv2.COLOR_BGR2GRAY of the RGB data: exact integer sums on the GPU, the float64 formula here, so the SSIM fields
+    are the reference's to rounding.  mean_gradient / gradient_discontinuity: mean and population std of
+    sqrt(gx^2 + gy^2) of the float32 Sobel of the whole canvas per channel, from an exact sum of squares and an fp64 sum of
+    roots (the reference's float32 np.mean / np.std carry ~1e-6 relative error; these agree with a float64 evaluation to
+    ~1e-12).  Positions are (y, x) inside the canvas (ValueError otherwise, as for gradient_domain_fusion); canvas and tiles
+    must be uint8 (NotImplementedError otherwise) with the canvas's channel count (1, 3 or 4)."""
+    result = np.asarray(result)
+    if result.dtype != np.uint8:
+        raise NotImplementedError(f"compute_blend_quality: uint8 canvas only on the HIP path (got {result.dtype})")
+    if result.ndim not in (2, 3):
+        raise ValueError(f"compute_blend_quality: canvas must be HxW or HxWxC (got shape {result.shape})")
+    images, pos, (H, W), cn = _check_tile_list(tiles, positions, result.shape[:2], "compute_blend_quality")
+    for im in images:
+        if im.dtype != np.uint8:
+            raise NotImplementedError(f"compute_blend_quality: uint8 tiles only on the HIP path (got {im.dtype})")
+    rcn = result.shape[2] if result.ndim == 3 else 1
+    if images[0].ndim != result.ndim or cn != rcn:
+        raise ValueError(f"compute_blend_quality: tiles of shape {images[0].shape[2:]} against a canvas of {result.shape}")
+    if result.ndim == 3 and cn not in (3, 4):
+        raise ValueError(f"compute_blend_quality: cv2.cvtColor(BGR2GRAY) needs 3 or 4 channels (got {cn})")
+    result = np.ascontiguousarray(result)
+    arrs = [np.ascontiguousarray(im) for im in images]
+    ctx = _native.default_context(0)
+    d_res = ctx.upload(result)
+    bufs = [ctx.upload(a) for a in arrs]
+    try:
+        sums = ctx.tile_ssim_sums_u8(d_res.ptr, W * cn, H, W, cn, [(x, y, a.shape[1], a.shape[0]) for a, (y, x) in
+                                                                    zip(arrs, pos)],
+                                     [b.ptr for b in bufs], [a.shape[1] * cn for a in arrs])
+        sum_sq, sum_mag = ctx.gradient_stats_u8(d_res.ptr, W * cn, H, W, cn)
+    finally:
+        ctx.sync()
+        for b in [d_res] + bufs:
+            b.free()
+    c1, c2 = (0.01 * 255.0) ** 2, (0.03 * 255.0) ** 2
+    scores = []
+    for a, (y, x), row in zip(arrs, pos, sums):
+        n = min(a.shape[0], H - y) * min(a.shape[1], W - x)
+        s_a, s_b, s_aa, s_bb, s_ab = (int(v) for v in row)
+        mu1, mu2 = s_a / n, s_b / n
+        var1 = (n * s_aa - s_a * s_a) / (n * n)         # exact integer numerators, one rounding each
+        var2 = (n * s_bb - s_b * s_b) / (n * n)
+        cov = (n * s_ab - s_a * s_b) / (n * n)
+        scores.append(float(((2 * mu1 * mu2 + c1) * (2 * cov + c2)) / ((mu1 ** 2 + mu2 ** 2 + c1) * (var1 + var2 + c2))))
+    count = H * W * cn
+    mean = sum_mag / count
+    var = max(sum_sq / count - mean * mean, 0.0)
+    return {"mean_ssim": np.mean(scores), "min_ssim": np.min(scores), "std_ssim": np.std(scores),
+            "mean_gradient": float(mean), "gradient_discontinuity": float(np.sqrt(var))}
 
 
 def create_tile_grid(images: List[np.ndarray], grid_shape: Tuple[int, int],

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "sr_ctx.h"
+#include "sr_linear.h"
 
 // Wave priority of the chain's kernels beside the assessment (A/B builds: -DSR_CHAIN_PRIO=1..3 for the small launches --
 // pyramid levels 2..5 down and up, the level-2 border columns -- -DSR_CHAIN_PRIO_BIG for tile extract and the level-1 + 2 march).
@@ -2956,12 +2957,6 @@ static void cubic_table(int n_src, int n_dst, std::vector<CubicTab> &tab)
 // ---------------------------------------------------------------------------------------------
 // TilingModule.merge_tiles feather path (tiling_module.py:1074-1175), canvas-centric
 // ---------------------------------------------------------------------------------------------
-struct LinTab {
-    int ofs;       // left / top source index (clamped)
-    short a0, a1;  // 11-bit coefficients of cv::resize INTER_LINEAR (u8 data)
-    float f;       // the fraction itself (float data: coefficients 1 - f and f)
-};
-
 struct MergeDev {
     int x, y, src_w, src_h, out_w, out_h;
     int ov_t, ov_b, ov_l, ov_r;
@@ -3104,9 +3099,7 @@ __global__ __launch_bounds__(256) void k_feather_merge(const MergeDev *__restric
                 const unsigned char *r0 = base + (size_t)Y.ofs * st, *r1 = base + (size_t)y1 * st;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const int s0 = (int)r0[X.ofs * 3 + c] * X.a0 + (int)r0[x1 * 3 + c] * X.a1;
-                    const int s1 = (int)r1[X.ofs * 3 + c] * X.a0 + (int)r1[x1 * 3 + c] * X.a1;
-                    const int v = (((Y.a0 * (s0 >> 4)) >> 16) + ((Y.a1 * (s1 >> 4)) >> 16) + 2) >> 2;
+                    const int v = lin_u8(r0, r1, X.ofs * 3 + c, x1 * 3 + c, X, Y);
                     acc[k][c] += (float)(unsigned char)v * w;
                 }
             } else if (whole) {
@@ -3138,25 +3131,6 @@ __global__ __launch_bounds__(256) void k_feather_merge(const MergeDev *__restric
         for (int k = 0; k < nx; ++k)
 #pragma unroll
             for (int c = 0; c < 3; ++c) o[3 * k + c] = (unsigned char)ob[3 * k + c];
-    }
-}
-
-static void linear_table(int n_src, int n_dst, std::vector<LinTab> &tab)
-{
-    const size_t base = tab.size();
-    tab.resize(base + n_dst);
-    const double scale = 1.0 / ((double)n_dst / (double)n_src);
-    for (int d = 0; d < n_dst; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)floorf(f);
-        f -= (float)s;
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= n_src - 1) { f = 0.f; s = n_src - 1; }
-        LinTab &t = tab[base + d];
-        t.ofs = s;
-        t.a0 = (short)rintf((1.0f - f) * 2048.0f);
-        t.a1 = (short)rintf(f * 2048.0f);
-        t.f = f;
     }
 }
 
