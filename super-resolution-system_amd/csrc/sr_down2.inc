@@ -107,11 +107,7 @@ __device__ __forceinline__ void d2_request(march_rsrc px, unsigned plo, unsigned
     R.m = (plo + off - 6u) & 3u;
     const unsigned soff = off + 6u - R.m;                           // the resource's base is the tile's first byte - 12
     R.lo = march_ld3(px, voff_lo, soff);
-#ifdef D2_PROBE_NOHI             /* timing probes only (wrong values) */
-    R.hi = R.lo;
-#else
     R.hi = march_ld3(px, voff_hi, soff);
-#endif
 }
 
 __device__ __forceinline__ void d2_hpass(const D2Raw &R, D2Row &H)
@@ -208,9 +204,6 @@ __device__ __forceinline__ f2_t d2_pair(float v)
 __device__ __forceinline__ void d2_store2(const D2Out &O, int Y, const f2_t (&v)[3])
 {
     if (!O.st2) return;
-#ifdef D2_PROBE_NOST2
-    if (v[0].x != 12345.0f) return;
-#endif
     const f2_t sc = d2_pair(1.0f / 256.0f);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -236,11 +229,7 @@ __device__ __forceinline__ void d2_step(int r, int rn, const D2Row &e0, const D2
     d2_request(px, plo, stride, d2_row(2 * rn + 2, hs, z0, z1), voff_lo, voff_hi, cur[1]);
     f2_t f[3][2];
     d2_vpass(e0, o0, e1, n1, n2, f);
-#ifdef D2_PROBE_NOST1
-    if (O.st1 && r >= own_lo && r < own_hi && f[0][0].x == 12345.0f) {
-#else
     if (O.st1 && r >= own_lo && r < own_hi) {
-#endif
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             u4_t o;
@@ -295,7 +284,6 @@ __global__ __launch_bounds__(64, D2_WAVES) void k_down2_march(const TileDev *__r
                                                     float *__restrict__ arena_w, const float *__restrict__ luts)
 {
     static_assert(CN == 3, "the fused level 0 -> 2 march is written for interleaved RGB");
-    SR_CHAIN_SETPRIO_BIG();
     const TileDev &T = tiles[blockIdx.z];
     if (!down2_takes(T)) return;
     const int ws = T.W[0], hs = T.H[0], w1 = T.W[1], h1 = T.H[1], h2 = T.H[2];
@@ -403,7 +391,6 @@ __host__ __device__ __forceinline__ int down2_cols_count(const TileDev &T)
 
 __global__ __launch_bounds__(256, 4) void k_down2_cols(const TileDev *__restrict__ tiles, float *__restrict__ arena)
 {
-    SR_CHAIN_SETPRIO();
     const TileDev &T = tiles[blockIdx.z];
     if (!down2_takes(T)) return;
     const int ncg = down_ncg(T.W[0], T.W[1]), w2 = T.W[2], h2 = T.H[2], h1 = T.H[1], w1 = T.W[1], p1 = T.P[1], p2 = T.P[2];

@@ -29,22 +29,6 @@
 #include "sr_ctx.h"
 #include "sr_linear.h"
 
-// Wave priority of the chain's kernels beside the assessment (A/B builds: -DSR_CHAIN_PRIO=1..3 for the small launches --
-// pyramid levels 2..5 down and up, the level-2 border columns -- -DSR_CHAIN_PRIO_BIG for tile extract and the level-1 + 2 march).
-// Measured and rejected (profiles/r04_e_chain_prio.txt): the step is 3.15-3.23 ms at every setting -- the small launches are
-// slow beside the assessment because ONE of their waves fits a SIMD next to its three (104 free registers), not because
-// they lose the issue arbitration.
-#ifdef SR_CHAIN_PRIO
-#define SR_CHAIN_SETPRIO() __builtin_amdgcn_s_setprio(SR_CHAIN_PRIO)
-#else
-#define SR_CHAIN_SETPRIO() ((void)0)
-#endif
-#ifdef SR_CHAIN_PRIO_BIG
-#define SR_CHAIN_SETPRIO_BIG() __builtin_amdgcn_s_setprio(SR_CHAIN_PRIO_BIG)
-#else
-#define SR_CHAIN_SETPRIO_BIG() ((void)0)
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // context (struct, Guard, ProfScope: sr_ctx.h)
 // ---------------------------------------------------------------------------------------------
@@ -224,7 +208,7 @@ struct FinalDesc {
     int x, y, w, h;
     int fw, lut_off, nl, pad0;
     int H1, W1, P1, pad1;
-    long long g1, r1;      // float offsets of plane 0 of G_1 / R_1 in the arena
+    long long g1, r1;      // float offsets of plane 0 of G_1 / R_1 in the arena (r1: read by no kernel since the unfused gather went)
     const void *src;       // level-0 tile data (row 0, possibly virtual) and its row stride in bytes
     long long stride;
     int H2, W2, P2, pad2;  // level 2 (the fused gather builds R_1 from it on the fly)
@@ -422,7 +406,6 @@ __global__ __launch_bounds__(256) void k_down_march(const TileDev *__restrict__ 
                                                     int lvl, int seg_rows, int march_blocks, float *__restrict__ arena,
                                                     const float *__restrict__ luts, int skip_down2)
 {
-    SR_CHAIN_SETPRIO();
     const TileDev &T = tiles[blockIdx.z];
     if (lvl + 1 >= T.nl) return;
     if (skip_down2 && down2_takes(T)) return;                       // levels 1 and 2 of this tile come from k_down2_march
@@ -617,12 +600,10 @@ __global__ __launch_bounds__(256) void k_final(const TileDev *__restrict__ tiles
 }
 
 // ---------------------------------------------------------------------------------------------
-// Final gather, register-blocked: one thread = 4 x 2 canvas pixels.  For every covering tile the
-// thread loads ONE 3-row x 4-column neighbourhood of G_1 and R_1 per plane and evaluates the same
-// per-pixel expressions as k_final from registers (12 loads per 8 pixels per plane per array
-// instead of 6-9 per pixel).  x0 is a multiple of 4 and y0 - row_begin a multiple of 2, so the
-// parity of the tile-local origin -- which selects the even/odd pyrUp phase of every pixel in the
-// thread -- is uniform per tile across the launch (template XO / YO).
+// pyrUp of a thread's 4 x 2 pixels from ONE 3-row x 4-column neighbourhood of a level (the same per-pixel expressions as
+// up_sample, 12 loads per 8 pixels instead of 6-9 per pixel).  x0 is a multiple of 4 and y0 - row_begin a multiple of 2,
+// so the parity of the tile-local origin -- which selects the even/odd pyrUp phase of every pixel in the thread -- is
+// uniform per tile across a launch (template XO / YO).
 // ---------------------------------------------------------------------------------------------
 template <int POS, bool ODD>
 __device__ __forceinline__ float up_h_reg(const float (&v)[4], int ws, int sx)
@@ -705,7 +686,7 @@ __device__ __forceinline__ void up_block_interior(const float *__restrict__ plan
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         const f4_t q = ld_f4_a4(plane + (size_t)(r0 + r) * ps + c0);
-        // power-of-two factors of the odd phases are folded into the final constants (exact; see up_regs)
+        // power-of-two factors of the odd phases are folded into the final constants (exact; see up_pairs)
         if (!XO) {
             h[r][0] = (q.x + q.y * 6.0f) + q.z;
             h[r][1] = q.y + q.z;
@@ -771,44 +752,6 @@ __device__ __forceinline__ void tile_weights(const FinalDesc &D, const float *__
         }
 }
 
-// pyrUp of one 3 x 4 register neighbourhood (rows q[0..2]) -> the thread's 2 x 4 pixels (interior form)
-template <bool XO, bool YO>
-__device__ __forceinline__ void up_regs(const f4_t (&q)[3], float (&u)[2][4])
-{
-    // Scaling by a power of two commutes with fp32 rounding, so the x4 of the odd phases ((a + b) * 4) is not
-    // applied where the reference applies it but folded into the final constant: 1/64 (even,even), 1/16 (one odd
-    // phase), 1/4 (odd,odd).  Bit-identical to the reference order, 10 multiplies fewer per plane.
-    float h[3][4];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        if (!XO) {
-            h[r][0] = (q[r].x + q[r].y * 6.0f) + q[r].z;
-            h[r][1] = q[r].y + q[r].z;
-            h[r][2] = (q[r].y + q[r].z * 6.0f) + q[r].w;
-            h[r][3] = q[r].z + q[r].w;
-        } else {
-            h[r][0] = q[r].x + q[r].y;
-            h[r][1] = (q[r].x + q[r].y * 6.0f) + q[r].z;
-            h[r][2] = q[r].y + q[r].z;
-            h[r][3] = (q[r].y + q[r].z * 6.0f) + q[r].w;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const bool kodd = XO ? ((k & 1) == 0) : ((k & 1) == 1);          // pixel k is an odd pyrUp column phase
-        const float ce = kodd ? (1.0f / 16.0f) : (1.0f / 64.0f);          // even row phase
-        const float co = kodd ? (1.0f / 4.0f) : (1.0f / 16.0f);           // odd row phase
-        const float ev = ((h[0][k] + h[1][k] * 6.0f) + h[2][k]) * ce;
-        if (!YO) {
-            u[0][k] = ev;
-            u[1][k] = (h[1][k] + h[2][k]) * co;
-        } else {
-            u[0][k] = (h[0][k] + h[1][k]) * co;
-            u[1][k] = ev;
-        }
-    }
-}
-
 // weights of an interior visit (all eight pixels inside the tile).  The LUT is monotone in the edge distance, so
 // lut[min(dy, dx)] == min(lut[dy], lut[dx]) exactly: 2 + 4 LUT reads and 8 v_min_f32 instead of 8 reads behind
 // 8 three-way integer minima.
@@ -836,14 +779,12 @@ __device__ __forceinline__ void tile_weights_interior(const FinalDesc &D, const 
         for (int k = 0; k < 4; ++k) w0[j][k] = __builtin_fminf(fy[j], fx[k]);
 }
 
-// interior visit: every global load of the visit is issued before the first use, then straight-line arithmetic.
-// Plane bases are wave-uniform (SGPR pair); the per-lane part of an address is one 32-bit byte offset.
-template <int DT, bool LAP, int CN, bool XO, bool YO>
-__device__ __forceinline__ void gather_tile_fast(const FinalDesc &D, const float *__restrict__ arena,
-                                                 const float *__restrict__ luts, int lx0, int ly0,
+// interior visit of the weighted average: every global load of the visit is issued before the first use, then
+// straight-line arithmetic
+template <int DT, int CN>
+__device__ __forceinline__ void gather_tile_fast(const FinalDesc &D, const float *__restrict__ luts, int lx0, int ly0,
                                                  float (&acc)[2][4][CN], float (&wacc)[2][4])
 {
-    const bool pyr = LAP && D.nl > 1;
     // ---- loads of the level-0 pixels and the weights ------------------------------------------------------
     float g0[2][4][CN];
     u3_t qs[2];
@@ -871,101 +812,32 @@ __device__ __forceinline__ void gather_tile_fast(const FinalDesc &D, const float
         if (LAZY) {
             const int b = 3 * k + c;
             unsigned wd = (b >> 2) == 0 ? qs[j].x : ((b >> 2) == 1 ? qs[j].y : qs[j].z);
-            asm volatile("" : "+v"(wd));      // keeps the conversion at its use: hoisted above the branch it would cost 24 live registers
+            asm volatile("" : "+v"(wd));      // keeps the conversion at its use
             return (float)((wd >> (8 * (b & 3))) & 0xFFu);
         }
         return g0[j][k][c];
     };
-    if (pyr) {                               // tile-uniform: a real branch, not a select per value
-        // plane by plane: the six 16-byte loads of a plane are in flight together, the next plane's are issued
-        // before this plane's arithmetic (two planes of level-1 data live at a time, not three)
-        const int r0 = (ly0 - 1) >> 1, c0 = (lx0 - 1) >> 1;
-        const size_t splane = (size_t)D.H1 * D.P1;
-        const unsigned rowb = (unsigned)D.P1 * 4u;
-        const unsigned o = (unsigned)r0 * rowb + (unsigned)c0 * 4u;      // byte offset inside a plane (planes < 4 GB)
-        f4_t qg[3], qr[3], ng[3], nr[3];
-        {
-            const char *gb = (const char *)(arena + D.g1), *rb = (const char *)(arena + D.r1);
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                qg[r] = ld_f4_a4((const float *)(gb + (o + r * rowb)));
-                qr[r] = ld_f4_a4((const float *)(rb + (o + r * rowb)));
-            }
-        }
+    for (int c = 0; c < CN; ++c)
 #pragma unroll
-        for (int c = 0; c < CN; ++c) {
-#ifndef SR_FINAL_NOPREF
-            if (c + 1 < CN) {
-                const char *gb = (const char *)(arena + D.g1 + (c + 1) * splane);
-                const char *rb = (const char *)(arena + D.r1 + (c + 1) * splane);
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    ng[r] = ld_f4_a4((const float *)(gb + (o + r * rowb)));
-                    nr[r] = ld_f4_a4((const float *)(rb + (o + r * rowb)));
-                }
-            }
-#else
-            if (c > 0) {
-                const char *gb = (const char *)(arena + D.g1 + c * splane);
-                const char *rb = (const char *)(arena + D.r1 + c * splane);
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    qg[r] = ld_f4_a4((const float *)(gb + (o + r * rowb)));
-                    qr[r] = ld_f4_a4((const float *)(rb + (o + r * rowb)));
-                }
-            }
-#endif
-            float ug[2][4], ur[2][4];
-            up_regs<XO, YO>(qg, ug);
-            up_regs<XO, YO>(qr, ur);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float lap = px(j, k, c) - ug[j][k];
-                    const float wl = lap * w0[j][k];
-                    acc[j][k][c] += ur[j][k] + wl;
-                }
-#ifndef SR_FINAL_NOPREF
-            if (c + 1 < CN) {
-#pragma unroll
-                for (int r = 0; r < 3; ++r) { qg[r] = ng[r]; qr[r] = nr[r]; }
-            }
-#endif
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < CN; ++c)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[j][k][c] += px(j, k, c) * w0[j][k];
-    }
+            for (int k = 0; k < 4; ++k) acc[j][k][c] += px(j, k, c) * w0[j][k];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int k = 0; k < 4; ++k) wacc[j][k] += w0[j][k];
 }
 
-// any visit: clamped taps, border selects, per-pixel validity (tile / level borders, ragged canvas edges)
-template <int DT, bool LAP, int CN, bool XO, bool YO>
-__device__ __forceinline__ void gather_tile_generic(const FinalDesc &D, const float *__restrict__ arena,
-                                                    const float *__restrict__ luts, int lx0, int ly0, unsigned valid,
-                                                    float (&acc)[2][4][CN], float (&wacc)[2][4])
+// any visit of the weighted average: per-pixel validity (tile borders, ragged canvas edges)
+template <int DT, int CN>
+__device__ __forceinline__ void gather_tile_generic(const FinalDesc &D, const float *__restrict__ luts, int lx0, int ly0,
+                                                    unsigned valid, float (&acc)[2][4][CN], float (&wacc)[2][4])
 {
     float w0[2][4];
     tile_weights(D, luts, lx0, ly0, w0);
-    const int r0 = (ly0 - 1) >> 1, c0 = (lx0 - 1) >> 1;
-    const bool pyr = LAP && D.nl > 1;
-    const int hs = D.H1, ws = D.W1, ps = D.P1;
-    const size_t splane = (size_t)hs * ps;
 #pragma unroll
-    for (int c = 0; c < CN; ++c) {
-        float ug[2][4], ur[2][4];
-        if (pyr) {
-            up_block<XO, YO>(arena + D.g1 + c * splane, hs, ws, ps, r0, c0, ug);
-            up_block<XO, YO>(arena + D.r1 + c * splane, hs, ws, ps, r0, c0, ur);
-        }
+    for (int c = 0; c < CN; ++c)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -975,17 +847,8 @@ __device__ __forceinline__ void gather_tile_generic(const FinalDesc &D, const fl
                 float g0;
                 if (DT == SRC_U8) g0 = (float)((const unsigned char *)srow)[(lx0 + k) * CN + c];
                 else g0 = ((const float *)srow)[(lx0 + k) * CN + c];
-                float r;
-                if (pyr) {
-                    const float lap = g0 - ug[j][k];
-                    const float wl = lap * w0[j][k];
-                    r = ur[j][k] + wl;
-                } else {
-                    r = g0 * w0[j][k];
-                }
-                acc[j][k][c] += r;
+                acc[j][k][c] += g0 * w0[j][k];
             }
-    }
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -1073,7 +936,6 @@ __device__ __forceinline__ void up_level_thread(const TileDev &T, int lvl, float
 template <int CN>
 __global__ __launch_bounds__(256) void k_up_level_blk(const TileDev *__restrict__ tiles, int lvl, float *__restrict__ arena)
 {
-    SR_CHAIN_SETPRIO();
     const TileDev &T = tiles[blockIdx.z];
     if (lvl >= T.nl) return;
     const int w = T.W[lvl], h = T.H[lvl], p = T.P[lvl];
@@ -1182,16 +1044,15 @@ __device__ __forceinline__ void store_pixels(float (&acc)[NR][4][CN], const floa
 // id, list entries and the 80-byte descriptors are wave-uniform, so they travel through the scalar cache into
 // SGPRs: no LDS staging and no barrier before the first vector load.
 
-// Final gather, border part: the cells the interior part leaves out (a border visit).  Runs over the blocks of the
+// Weighted average, border part: the cells the interior part leaves out (a border visit).  Runs over the blocks of the
 // edge work list built on the host when the plan is made: 256 x 8 pixel blocks along horizontal tile edges (shape 0),
 // 16 x 128 pixel blocks along vertical ones (shape 1).  These are the leading blocks of k_final_fast's launch (the
 // slow, divergent ones are scheduled first, the kernel's tail is made of regular blocks).
-template <int DT, bool LAP, int CN>
+template <int DT, int CN>
 __device__ __forceinline__ void final_edge_block(const FinalDesc *__restrict__ descs, const int4 *__restrict__ edge_blocks,
-                                                 int ebi, const int *__restrict__ cand_idx,
-                                                 const float *__restrict__ arena, const float *__restrict__ luts,
+                                                 int ebi, const int *__restrict__ cand_idx, const float *__restrict__ luts,
                                                  unsigned char *__restrict__ canvas, long long cstride,
-                                                 float *__restrict__ canvas_f32, int cw, int row_begin, int row_end)
+                                                 float *__restrict__ canvas_f32, int cw, int row_end)
 {
     const int4 eb = edge_blocks[ebi];
     const int c_begin = eb.w, c_end = edge_blocks[ebi + 1].w;
@@ -1205,7 +1066,7 @@ __device__ __forceinline__ void final_edge_block(const FinalDesc *__restrict__ d
         const FinalDesc &D = descs[cand_idx[i]];
         const int lx0 = x0 - D.x, ly0 = y0 - D.y;
         if (lx0 + nx <= 0 || ly0 + ny <= 0 || lx0 >= D.w || ly0 >= D.h) continue;
-        if (!visit_is_interior<LAP>(D, lx0, ly0, nx, ny)) edge = true;
+        if (!visit_is_interior<false>(D, lx0, ly0, nx, ny)) edge = true;
     }
     if (!edge) return;
     float acc[2][4][CN], wacc[2][4];
@@ -1228,19 +1089,15 @@ __device__ __forceinline__ void final_edge_block(const FinalDesc *__restrict__ d
             for (int k = 0; k < 4; ++k)
                 if (j < ny && k < nx && lx0 + k >= 0 && lx0 + k < D.w && ly0 + j >= 0 && ly0 + j < D.h)
                     valid |= 1u << (j * 4 + k);
-        const bool xo = (D.x & 1) != 0;
-        const bool yo = ((row_begin - D.y) & 1) != 0;
-        if (!xo && !yo) gather_tile_generic<DT, LAP, CN, false, false>(D, arena, luts, lx0, ly0, valid, acc, wacc);
-        else if (xo && !yo) gather_tile_generic<DT, LAP, CN, true, false>(D, arena, luts, lx0, ly0, valid, acc, wacc);
-        else if (!xo && yo) gather_tile_generic<DT, LAP, CN, false, true>(D, arena, luts, lx0, ly0, valid, acc, wacc);
-        else gather_tile_generic<DT, LAP, CN, true, true>(D, arena, luts, lx0, ly0, valid, acc, wacc);
+        gather_tile_generic<DT, CN>(D, luts, lx0, ly0, valid, acc, wacc);
     }
     store_pixels<CN>(acc, wacc, canvas, cstride, canvas_f32, cw, x0, y0, nx, ny);
 }
 
-// Final gather.  The first n_edge blocks of the (one-dimensional) grid work through the edge list (above); the others
-// are the regular FIN_BW x FIN_BH pixel blocks: threads all of whose tile visits are interior compute here, threads with
-// any border visit leave their pixels to the edge blocks.
+// Weighted average (weighted_average_fusion; the Laplacian blend of 1- and 3-channel tiles is the fused gather below).
+// The first n_edge blocks of the (one-dimensional) grid work through the edge list (above); the others are the regular
+// FIN_BW x FIN_BH pixel blocks: threads all of whose tile visits are interior compute here, threads with any border
+// visit leave their pixels to the edge blocks.
 #ifndef SR_FINAL_WAVES
 #define SR_FINAL_WAVES 3
 #endif
@@ -1250,22 +1107,20 @@ __device__ __forceinline__ void final_edge_block(const FinalDesc *__restrict__ d
 #define FIN_TY (256 / FIN_TX)
 #define FIN_BW (4 * FIN_TX)       /* canvas pixels per regular block */
 #define FIN_BH (2 * FIN_TY)
-template <int DT, bool LAP, int CN>
+template <int DT, int CN>
 __global__ __launch_bounds__(256, SR_FINAL_WAVES) void k_final_fast(const FinalDesc *__restrict__ descs,
                                                        const int *__restrict__ cand_off, const int *__restrict__ cand_idx,
                                                        const int4 *__restrict__ edge_blocks, const int *__restrict__ edge_cand,
-                                                       int n_edge, int nbx_r,
-                                                       const float *__restrict__ arena, const float *__restrict__ luts,
+                                                       int n_edge, int nbx_r, const float *__restrict__ luts,
                                                        unsigned char *__restrict__ canvas, long long cstride,
                                                        float *__restrict__ canvas_f32, int cw, int row_begin, int row_end)
 {
     if ((int)blockIdx.x < n_edge) {
-        final_edge_block<DT, LAP, CN>(descs, edge_blocks, (int)blockIdx.x, edge_cand, arena, luts, canvas, cstride, canvas_f32, cw,
-                                      row_begin, row_end);
+        final_edge_block<DT, CN>(descs, edge_blocks, (int)blockIdx.x, edge_cand, luts, canvas, cstride, canvas_f32, cw, row_end);
         return;
     }
     // regular blocks: FIN_BW x FIN_BH canvas pixels, FIN_TX x FIN_TY threads of 4 x 2 pixels (a wave covers
-    // 64 / FIN_TX thread rows).  Squarer blocks re-read fewer level-1 halo rows: a block needs FIN_BH / 2 + 2 of them.
+    // 64 / FIN_TX thread rows)
     const int blk = (int)blockIdx.x - n_edge;
     const int by = blk / nbx_r, bx = blk - by * nbx_r;
     const int c_begin = cand_off[blk], c_end = cand_off[blk + 1];
@@ -1288,13 +1143,8 @@ __global__ __launch_bounds__(256, SR_FINAL_WAVES) void k_final_fast(const FinalD
         const int lx0 = x0 - D.x, ly0 = y0 - D.y;
         if (lx0 + nx <= 0 || ly0 + ny <= 0 || lx0 >= D.w || ly0 >= D.h) continue;
         // one border visit sends the whole thread to the edge pass (which recomputes every visit)
-        if (!visit_is_interior<LAP>(D, lx0, ly0, nx, ny)) return;
-        const bool xo = (D.x & 1) != 0;                      // x0 is a multiple of 4
-        const bool yo = ((row_begin - D.y) & 1) != 0;        // y0 - row_begin is a multiple of 2
-        if (!xo && !yo) gather_tile_fast<DT, LAP, CN, false, false>(D, arena, luts, lx0, ly0, acc, wacc);
-        else if (xo && !yo) gather_tile_fast<DT, LAP, CN, true, false>(D, arena, luts, lx0, ly0, acc, wacc);
-        else if (!xo && yo) gather_tile_fast<DT, LAP, CN, false, true>(D, arena, luts, lx0, ly0, acc, wacc);
-        else gather_tile_fast<DT, LAP, CN, true, true>(D, arena, luts, lx0, ly0, acc, wacc);
+        if (!visit_is_interior<false>(D, lx0, ly0, nx, ny)) return;
+        gather_tile_fast<DT, CN>(D, luts, lx0, ly0, acc, wacc);
     }
     store_pixels<CN>(acc, wacc, canvas, cstride, canvas_f32, cw, x0, y0, nx, ny);
 }
@@ -1326,10 +1176,6 @@ __global__ __launch_bounds__(256, SR_FINAL_WAVES) void k_final_fast(const FinalD
 #define FU_E1W 16                           /* edge shape 1: FU_E1W x FU_E1H pixels (4 cells across: a vertical tile edge
                                                makes 1 - 3 of them border cells) */
 #define FU_E1H (FU_THREADS / 2)
-#ifndef FU_DB
-#define FU_DB 0                /* 1: two LDS windows per block taken in turn (one barrier per tile instead of two): measured
-                                  and rejected, 0.21 -> 0.26 ms for the 200 MP grid's remainder -- three blocks per CU instead of four */
-#endif
 #define FU_LP 72              /* LDS pitch (floats) of a regular block's window: 18 patches of 4 columns */
 /* pixels per plane window (two floats each): rows = block rows / 2 + 3, rounded up to even; 72 (regular), 136 (shape 0) or
    24 (shape 1) columns */
@@ -1416,7 +1262,9 @@ __device__ __forceinline__ void fused_stage1(const FinalDesc &D, const float *__
 }
 
 // pyrUp of a 3-row x 4-column neighbourhood of (g, r) PAIRS -> the thread's 4 x 2 pixels, both arrays at once in packed
-// fp32 (interior form; up_regs with pairs).  q[r][i] is the pair at row r0 + r, column c0 + i.
+// fp32 (interior form).  q[r][i] is the pair at row r0 + r, column c0 + i.  Scaling by a power of two commutes with fp32
+// rounding, so the x4 of the odd phases ((a + b) * 4) is not applied where the reference applies it but folded into the
+// final constant: 1/64 (even,even), 1/16 (one odd phase), 1/4 (odd,odd).  Bit-identical to the reference order.
 template <bool XO, bool YO>
 __device__ __forceinline__ void up_pairs(const f2_t (&q)[3][4], f2_t (&u)[2][4])
 {
@@ -1650,10 +1498,8 @@ __device__ __forceinline__ void fused_edge_block(const FinalDesc *__restrict__ d
 #pragma unroll
             for (int c = 0; c < CN; ++c) acc[j][k][c] = 0.f;
         }
-    float *const lds_all = lds;
     for (int i = c_begin; i < c_end; ++i) {
         const FinalDesc &D = descs[cand_idx[i]];
-        if (FU_DB) lds = lds_all + ((i - c_begin) & 1) * (2 * CN * FU_PLANE);
         int R0 = 0, C0 = 0, npr = 0, npc = 0;
         const bool win = D.nl > 1 && fused_window(D, eb.x - D.x, eb.y - D.y, bw, bh, R0, C0, npr, npc);
         if (win) fused_stage1<CN>(D, arena, lds, R0, C0, npr, npc, LP, tid);
@@ -1700,7 +1546,7 @@ __device__ __forceinline__ void fused_edge_block(const FinalDesc *__restrict__ d
             else if (!xo && yo) fused_gather_generic<DT, CN, false, true>(D, luts, lds, LP, R0, C0, lx0, ly0, valid, acc, wacc);
             else fused_gather_generic<DT, CN, true, true>(D, luts, lds, LP, R0, C0, lx0, ly0, valid, acc, wacc);
         }
-        if (!FU_DB) __syncthreads();                       // the next tile's stage 1 overwrites the window
+        __syncthreads();                                   // the next tile's stage 1 overwrites the window
     }
     if (edge) store_pixels<CN>(acc, wacc, canvas, cstride, canvas_f32, cw, x0, y0, nx, ny);
 }
@@ -1709,15 +1555,11 @@ template <int DT, int CN>
 __global__ __launch_bounds__(FU_THREADS, FU_WAVES) void k_final_fused(const FinalDesc *__restrict__ descs, const int *__restrict__ cand_off,
                                                         const int *__restrict__ cand_idx, const int4 *__restrict__ edge_blocks,
                                                         const int *__restrict__ edge_cand, int n_edge, int nbx_r,
-                                                        const int *__restrict__ reg_list,
                                                         const float *__restrict__ arena, const float *__restrict__ luts,
                                                         unsigned char *__restrict__ canvas, long long cstride,
                                                         float *__restrict__ canvas_f32, int cw, int row_begin, int row_end)
 {
-    // FU_DB: two windows, taken in turn by the tiles of a block -- the barrier that kept a tile's stage 1 from overwriting the window
-    // the previous tile's gather still reads is not needed then (one barrier per tile instead of two, 52 instead of 26 KB of LDS)
-    __shared__ __attribute__((aligned(16))) float lds_all[(FU_DB ? 2 : 1) * 2 * CN * FU_PLANE];
-    float *lds = lds_all;
+    __shared__ __attribute__((aligned(16))) float lds[2 * CN * FU_PLANE];
     if ((int)blockIdx.x < n_edge) {
         fused_edge_block<DT, CN>(descs, edge_blocks, (int)blockIdx.x, edge_cand, arena, luts, lds, canvas, cstride, canvas_f32, cw,
                                  row_begin, row_end);
@@ -1726,48 +1568,22 @@ __global__ __launch_bounds__(FU_THREADS, FU_WAVES) void k_final_fused(const Fina
     // (Measured and rejected: a workgroup marching down several blocks of a column -- one dispatch, halo rows still in
     // the CU's caches -- is slower, 1.37 -> 1.52 ms at 16 blocks: the blocks of a march run strictly one after the other
     // and each is a chain of dependent memory round trips; independent blocks overlap them.)
-    // the regular blocks that are left once the marched zones (sr_march.inc) are taken out: block id and, per cell row of
-    // the block, the mask of the cell columns a march item covers
-    const int *rl = reg_list + 9 * ((int)blockIdx.x - n_edge);
-    const int blk = rl[0];
+    const int blk = (int)blockIdx.x - n_edge;
     const int by = blk / nbx_r, bx = blk - by * nbx_r;
     const int c_begin = cand_off[blk], c_end = cand_off[blk + 1];
     const int tid = threadIdx.x;
-    const int bx0 = bx * FU_BW, by0 = row_begin + by * FU_BH;
-    // the cells that are left span a sub-rectangle of the block (thin bands along the marched zones, mostly): the level-1
-    // window is built for that rectangle only, and the threads are dealt over ITS cells (a band of 3 x 8 cells is one
-    // wave's work, not a few lanes of each of the four) -- block-uniform: scalar arithmetic on the mask words
-    int sbx = bx0, sby = by0, sbw = FU_BW, sbh = FU_BH;
-    {
-        const int ncol = min(32, (cw - bx0 + 3) >> 2), nrow = min(FU_BH / 2, (row_end - by0 + 1) >> 1);
-        const unsigned colmask = ncol >= 32 ? 0xFFFFFFFFu : ((1u << ncol) - 1u);
-        unsigned any = 0u;
-        int cy0 = FU_BH / 2, cy1 = -1;
-#pragma unroll
-        for (int cy = 0; cy < FU_BH / 2; ++cy) {
-            const unsigned a = cy < nrow ? (~(unsigned)rl[1 + cy] & colmask) : 0u;
-            if (a) {
-                any |= a;
-                cy0 = min(cy0, cy);
-                cy1 = cy;
-            }
-        }
-        if (any) {
-            const int cx0 = __builtin_ctz(any), cx1 = 31 - __builtin_clz(any);
-            sbx = bx0 + 4 * cx0;
-            sby = by0 + 2 * cy0;
-            sbw = 4 * (cx1 - cx0 + 1);
-            sbh = 2 * (cy1 - cy0 + 1);
-        }
-    }
-    const int scw = sbw >> 2;                                        // cells across the sub-rectangle
+    // (the block origin through readfirstlane: without it the float RGB instance spills a VGPR)
+    const int sbx = __builtin_amdgcn_readfirstlane(bx * FU_BW), sby = __builtin_amdgcn_readfirstlane(row_begin + by * FU_BH);
+    // the block's cells stop at the canvas width and at row_end: the level-1 window is built for the cells in use only,
+    // and the threads are dealt over them (the cells of a ragged block fill the first waves) -- block-uniform
+    const int scw = min(FU_BW / 4, (cw - sbx + 3) >> 2), sch = min(FU_BH / 2, (row_end - sby + 1) >> 1);
+    const int sbw = 4 * scw, sbh = 2 * sch;
     const int scy = tid / scw, scx = tid - scy * scw;
     const int x0 = sbx + scx * 4, y0 = sby + scy * 2;
     const int nx = min(4, cw - x0), ny = min(2, row_end - y0);
-    const int mrow = (y0 - by0) >> 1, mcol = (x0 - bx0) >> 2;         // the cell's place in the block's mask
     // a cell with any border visit belongs to the edge blocks (which recompute every visit of it): it stops
     // accumulating at its first border visit and stores nothing
-    bool alive = scy < (sbh >> 1) && x0 < cw && y0 < row_end && !(((unsigned)rl[1 + min(mrow, FU_BH / 2 - 1)] >> mcol) & 1u);
+    bool alive = scy < sch;
     float acc[2][4][CN], wacc[2][4];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -1779,7 +1595,6 @@ __global__ __launch_bounds__(FU_THREADS, FU_WAVES) void k_final_fused(const Fina
         }
     for (int i = c_begin; i < c_end; ++i) {
         const FinalDesc &D = descs[cand_idx[i]];
-        if (FU_DB) lds = lds_all + ((i - c_begin) & 1) * (2 * CN * FU_PLANE);
         const int lxa = sbx - D.x, lya = sby - D.y;
         int R0 = 0, C0 = 0, npr = 0, npc = 0;
         const bool win = D.nl > 1 && fused_window(D, lxa, lya, sbw, sbh, R0, C0, npr, npc);        // block-uniform
@@ -1808,7 +1623,7 @@ __global__ __launch_bounds__(FU_THREADS, FU_WAVES) void k_final_fused(const Fina
             }
 #undef FU_CALL
         }
-        if (!FU_DB) __syncthreads();                           // the next tile's stage 1 overwrites the window
+        __syncthreads();                                       // the next tile's stage 1 overwrites the window
     }
     if (alive) store_pixels<CN>(acc, wacc, canvas, cstride, canvas_f32, cw, x0, y0, nx, ny);   // ragged cells without a visit: zeros
 }
@@ -2007,7 +1822,6 @@ struct ExtractDesc {
 __global__ __launch_bounds__(256) void k_tile_extract(const unsigned char *__restrict__ img, long long istride,
                                                       int cn, const ExtractDesc *__restrict__ descs, int pad_mode)
 {
-    SR_CHAIN_SETPRIO_BIG();
     const ExtractDesc D = descs[blockIdx.z];
     const int r = blockIdx.y * 4 + threadIdx.y;
     const long long b0 = ((long long)blockIdx.x * 64 + threadIdx.x) * 16;
@@ -3162,14 +2976,12 @@ struct sr_blend_plan {
     int *d_fcand_off = nullptr, *d_fcand_idx = nullptr, *d_fedge_cand = nullptr;
     int4 *d_fedge_blocks = nullptr;
     int n_fedge_blocks = 0;
-    // marched zones (k_final_march): work items per tile count, and the regular blocks of k_final_fused that remain
+    // marched zones (k_final_march): work items per tile count
     bool march = false;
     bool down2 = true;               // levels 1 and 2 of full-window u8 RGB tiles in one march (sr_down2.inc); SR_DOWN2=0: two launches
     MarchItem *d_march_items[MARCH_NT + 1] = {nullptr};
     int n_march_items[MARCH_NT + 1] = {0};
     long long n_march_total = 0;
-    int *d_freg_list = nullptr, *d_freg_all = nullptr;      // without the marched zones / every regular block (float tiles): 9 ints each
-    long long n_freg = 0, n_freg_all = 0;
     RectItem *d_rects = nullptr;                            // what the marched zones leave, as rectangles of cells (k_final_rect)
     int *d_rect_cand = nullptr;
     long long n_rects = 0;
@@ -3191,12 +3003,11 @@ static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // changes of any tile the classes are constant, so the canvas falls into rectangles with a fixed list of visiting tiles;
 // a rectangle is marched when every tile that touches it is marchable in both directions.  Rectangles lose one cell
 // column per side to the halo lanes and are cut into strips of <= MARCH_CELLS cells and segments of <= MARCH_SEG steps
-// (an even number: an odd last cell row stays with the block kernel).
-// reg_list: the regular blocks that still hold unmarched cells, 9 ints each: block id and, per cell row of the block,
-// the mask of its marched cell columns.
+// (an even number: an odd last cell row is left to the rectangles).
+// cover: [cell row][word of 32 cell columns] bits of the marched cells (row pitch nbx_r words).
 // ---------------------------------------------------------------------------------------------
 static void plan_march(const sr_blend_plan *P, int nbx_r, int nby_r, std::vector<MarchItem> (&items)[MARCH_NT + 1],
-                       std::vector<int> &reg_list, std::vector<unsigned> &cover)
+                       std::vector<unsigned> &cover)
 {
     const int rows = P->row_end - P->row_begin, cw = P->canvas_w, n = P->n;
     const int ncx = cw / 4, ncy = rows / 2;                    // whole cells only: ragged ends are border visits
@@ -3208,11 +3019,9 @@ static void plan_march(const sr_blend_plan *P, int nbx_r, int nby_r, std::vector
     // The march is four launches of long work items: it wins on a big canvas (200 MP: 1.12 against 1.22 ms for the block kernel
     // alone) and loses on a small one, where every launch is a few short items deep -- a rank's strip of a world of 4 / 8:
     // 0.39 / 0.27 ms against 0.33 / 0.18 (tools/virtual_scaling.py, profiles/r04_virtual_scaling.json); even at 100 MP.
-    // SR_MARCH=2 marches whatever the size, SR_MARCH_MIN_MP moves the threshold (A/B runs).
+    // SR_MARCH=2 marches whatever the size.
     const char *env_force = std::getenv("SR_MARCH");               // read per plan: the tests switch it
-    const char *env_min = std::getenv("SR_MARCH_MIN_MP");
-    const double min_px = (env_min ? atof(env_min) : 90.0) * 1e6;
-    const bool big = (env_force && env_force[0] == '2') || (double)rows * (double)cw >= min_px;
+    const bool big = (env_force && env_force[0] == '2') || (double)rows * (double)cw >= 90e6;
     const bool on = P->march && big && fits32 && n <= 128 && ncx >= 3 && ncy >= 2;
     if (on) {
         auto xclass = [&](const TileDev &T, int x0) -> unsigned char {
@@ -3310,7 +3119,7 @@ static void plan_march(const sr_blend_plan *P, int nbx_r, int nby_r, std::vector
             // Rounds per list, measured (profiles/r04_e_gather_sweep.txt): four for the 1-tile list, three for the 2-tile list, two
             // for the short 3- / 4-tile lists (an item's warm-up is ~2.5 steps: at six rounds the 4-tile list was cut into 8-step
             // items); the tapered end of a list (below) is what makes long items affordable.
-            // SR_MARCH_ROUNDS="r1,r2,r4" / SR_MARCH_SEG_MAX: A/B runs.
+            // SR_MARCH_ROUNDS="r1,r2,r4": A/B runs.
             double rounds = nt >= 3 ? MARCH_ROUNDS_N : (nt == 2 ? MARCH_ROUNDS_2 : MARCH_ROUNDS);
             if (const char *e_r = std::getenv("SR_MARCH_ROUNDS")) {
                 double r[3] = {0, 0, 0};
@@ -3318,33 +3127,25 @@ static void plan_march(const sr_blend_plan *P, int nbx_r, int nby_r, std::vector
                 const int k = nt == 1 ? 0 : (nt == 2 ? 1 : 2);
                 if (got >= 1 && r[std::min(k, got - 1)] > 0) rounds = r[std::min(k, got - 1)];
             }
-            const char *e_s = std::getenv("SR_MARCH_SEG_MAX");
-            const int seg_max = e_s && atoi(e_s) >= 8 ? std::min(atoi(e_s), 64) : MARCH_SEG;
             const long long want_items = std::max<long long>((long long)((double)(P->ctx->num_cu * 8 / nt) * rounds), 1);   // rounds at two waves per SIMD
-            int seg = (int)std::min<long long>(seg_max, std::max<long long>(8, steps_of[nt] / want_items));
+            int seg = (int)std::min<long long>(MARCH_SEG, std::max<long long>(8, steps_of[nt] / want_items));
             seg = seg / 2 * 2;
             // The items of a list run in list order, a few rounds of them: the last round leaves the GPU emptier and emptier
             // while its long items finish (half an item's duration per launch, ~30 us of march1's 300).  So the list ends
             // with short items: the last `tail` strip-steps (about one round of full-length items) are cut into segments of
             // half the length, the last quarter of those into the shortest ones (8 steps: an item's warm-up is ~2).
             // SR_MARCH_TAIL=0: uniform segments (A/B runs).  Which segment a canvas row falls into changes no value.
-            const int taper = std::getenv("SR_MARCH_TAIL") ? atoi(std::getenv("SR_MARCH_TAIL")) : 1;   // read per plan
+            const bool taper = !(std::getenv("SR_MARCH_TAIL") && atoi(std::getenv("SR_MARCH_TAIL")) == 0);   // read per plan
             const long long slots = std::max<long long>((long long)P->ctx->num_cu * 8 / nt, 1);
-            const long long tail = taper && seg > 8 ? std::min<long long>(slots * seg * (taper == 3 ? 2 : 1), steps_of[nt] / (taper == 3 ? 2 : 3)) : 0;
+            const long long tail = taper && seg > 8 ? std::min<long long>(slots * seg, steps_of[nt] / 3) : 0;
             long long done = 0;
             for (const Strip &st : strips) {
                 if (st.nt != nt) continue;
                 for (int sy = st.ya; sy < st.ye;) {
                     const long long left = steps_of[nt] - done;
                     int sg = seg;
-                    if (taper == 2) {                                     // (A/B) three levels: 1/2, 1/4, shortest
-                        if (left <= tail / 8) sg = 8;
-                        else if (left <= tail / 2) sg = std::max(8, seg / 8 * 2);
-                        else if (left <= tail) sg = std::max(8, seg / 4 * 2);
-                    } else {
-                        if (left <= tail / 4) sg = 8;
-                        else if (left <= tail) sg = std::max(8, seg / 4 * 2);
-                    }
+                    if (left <= tail / 4) sg = 8;
+                    else if (left <= tail) sg = std::max(8, seg / 4 * 2);
                     MarchItem it;
                     memset(&it, 0, sizeof(it));
                     it.x0 = 4 * (st.ca - 1);
@@ -3362,30 +3163,6 @@ static void plan_march(const sr_blend_plan *P, int nbx_r, int nby_r, std::vector
                         steps_of[nt], cells_of[nt], 100.0 * (double)cells_of[nt] / ((double)ncx * ncy), ncx, ncy, seg, items[nt].size());
         }
     }
-    // the regular blocks that still hold unmarched cells: block id + the marched cell columns of each of its CPB cell rows
-    static_assert(FU_BW == 128 && FU_BH == 16, "one mask word per cell row of a regular block, one bit per cell column");
-    for (int by = 0; by < nby_r; ++by)
-        for (int bx = 0; bx < nbx_r; ++bx) {
-            const int cells = std::min(32, (cw - bx * FU_BW + 3) / 4);
-            const unsigned all = cells >= 32 ? 0xFFFFFFFFu : ((1u << cells) - 1u);
-            const int crows = std::min(CPB, (rows - by * FU_BH + 1) / 2);
-            unsigned m[8];
-            bool dead = true;
-            for (int cy = 0; cy < CPB; ++cy) {
-                m[cy] = cy < crows ? cover[(size_t)(by * CPB + cy) * nbx_r + bx] : 0xFFFFFFFFu;
-                if (cy < crows && (m[cy] & all) != all) dead = false;
-            }
-            if (dead) continue;                                     // every cell of the block is marched
-            reg_list.push_back(by * nbx_r + bx);
-            for (int cy = 0; cy < CPB; ++cy) reg_list.push_back((int)m[cy]);
-        }
-    if (std::getenv("SR_MARCH_STATS")) {
-        long long left = 0;
-        for (size_t i = 0; i < reg_list.size(); i += 9)
-            for (int cy = 0; cy < CPB; ++cy) left += 32 - __builtin_popcount((unsigned)reg_list[i + 1 + cy]);
-        fprintf(stderr, "[march] block kernel: %zu regular blocks of %d x %d with %lld unmarched cell slots (%.2f %% of the canvas cells)\n",
-                reg_list.size() / 9, nbx_r, nby_r, left, 100.0 * (double)left / ((double)ncx * ncy));
-    }
 }
 
 // What the marched zones leave, cut into rectangles of cells for k_final_rect: every cell row's runs of unmarched cells --
@@ -3399,10 +3176,9 @@ static void plan_rects(const sr_blend_plan *P, int nbx_r, const std::vector<unsi
     const int ncxp = (cw + 3) / 4, ncyp = (rows + 1) / 2;
     const char *e_cells = std::getenv("SR_RECT_CELLS");                   // A/B runs: most cells per rectangle (<= 256 threads)
     const int max_cells = e_cells && atoi(e_cells) >= 32 ? std::min(atoi(e_cells), 256) : 256;
-    const bool colmajor_on = !(std::getenv("SR_RECT_COLMAJOR") && std::getenv("SR_RECT_COLMAJOR")[0] == '0');
     // window pitch: two pixel pairs more than needed, so that consecutive rows start 36 (not 32) dwords apart for a band 5 cells
-    // wide -- column-major lanes read the same columns of consecutive rows (SR_RECT_PAD=0: the bare pitch, A/B runs)
-    const int pad = (std::getenv("SR_RECT_PAD") && std::getenv("SR_RECT_PAD")[0] == '0') ? 0 : 2;
+    // wide -- column-major lanes read the same columns of consecutive rows
+    const int pad = 2;
     auto hmax = [max_cells, pad](int w) {
         int h = std::max(max_cells / w, 1);
         while (h > 1 && rect_rows(h) * (rect_lp(w) + pad) > FU_PLANE) --h;
@@ -3425,12 +3201,11 @@ static void plan_rects(const sr_blend_plan *P, int nbx_r, const std::vector<unsi
         }
         it.ncand = (int)rcand.size() - it.cand;
         it.lp = rect_lp(it.w) + pad;
-        it.colmajor = (colmajor_on && it.h > it.w) ? 1 : 0;
+        it.colmajor = it.h > it.w ? 1 : 0;
         rects.push_back(it);
     };
     std::vector<std::pair<int, int>> segs;
     std::map<std::pair<int, int>, std::pair<int, int>> wide;      // wide run (first cell, end) -> (piece width, last row seen)
-    const bool wide_on = !(std::getenv("SR_RECT_WIDE") && std::getenv("SR_RECT_WIDE")[0] == '0');
     auto unmarched = [&](int cy, int cx) { return !((cover[(size_t)cy * nbx_r + (cx >> 5)] >> (cx & 31)) & 1u); };
     auto run_is = [&](int cy, int xa, int xe) {                   // row cy holds exactly the run [xa, xe) of unmarched cells
         if (xa > 0 && unmarched(cy, xa - 1)) return false;
@@ -3461,7 +3236,7 @@ static void plan_rects(const sr_blend_plan *P, int nbx_r, const std::vector<unsi
                 } else {
                     int H = 1;
                     while (H < 9 && cy + H < ncyp && run_is(cy + H, cx, xe)) ++H;
-                    if (wide_on && H <= 8) {
+                    if (H <= 8) {
                         pw = std::min(64, 256 / H) / 4 * 4;
                         while (pw > 32 && rect_rows(H) * (rect_lp(pw) + pad) > FU_PLANE) pw -= 4;
                         pw = std::max(pw, 32);
@@ -3592,14 +3367,6 @@ int sr_ctx_destroy(sr_ctx *ctx)
         if (ctx->extract_tab.d) (void)hipFree(ctx->extract_tab.d);
         if (ctx->resize_tab.d) (void)hipFree(ctx->resize_tab.d);
         if (ctx->cubic_tab.d) (void)hipFree(ctx->cubic_tab.d);
-        for (int i = 0; i < 2; ++i) {
-            if (ctx->side[i]) {
-                (void)hipStreamSynchronize(ctx->side[i]);
-                (void)hipStreamDestroy(ctx->side[i]);
-            }
-            if (ctx->side_join[i]) (void)hipEventDestroy(ctx->side_join[i]);
-        }
-        if (ctx->side_fork) (void)hipEventDestroy(ctx->side_fork);
         if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     }
     delete ctx;
@@ -3874,8 +3641,6 @@ int sr_blend_plan_destroy(sr_blend_plan *plan)
         if (plan->d_fcand_idx) (void)hipFree(plan->d_fcand_idx);
         if (plan->d_fedge_blocks) (void)hipFree(plan->d_fedge_blocks);
         if (plan->d_fedge_cand) (void)hipFree(plan->d_fedge_cand);
-        if (plan->d_freg_list) (void)hipFree(plan->d_freg_list);
-        if (plan->d_freg_all) (void)hipFree(plan->d_freg_all);
         if (plan->d_rects) (void)hipFree(plan->d_rects);
         if (plan->d_rect_cand) (void)hipFree(plan->d_rect_cand);
         for (int k = 0; k <= MARCH_NT; ++k)
@@ -3917,8 +3682,7 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
     P->tiles.resize(n);
     P->tile_rows.resize(n);
     {
-        const char *env = std::getenv("SR_FUSED_FINAL");
-        P->fused = (cn == 3 || cn == 1) && !(env && env[0] == '0');     // SR_FUSED_FINAL=0: the unfused pair (A/B runs)
+        P->fused = cn == 3 || cn == 1;
         const char *env2 = std::getenv("SR_MARCH");
         P->march = P->fused && !(env2 && env2[0] == '0');               // SR_MARCH=0: every zone through k_final_fused (A/B runs)
         const char *env3 = std::getenv("SR_DOWN2");
@@ -4250,11 +4014,10 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
         if ((e = hipMalloc((void **)&P->d_fcand_idx, sizeof(int) * cidx.size())) != hipSuccess) return fail(e, "fused candidate table");
         if ((e = hipMemcpy(P->d_fcand_off, coff.data(), sizeof(int) * coff.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
         if ((e = hipMemcpy(P->d_fcand_idx, cidx.data(), sizeof(int) * cidx.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-        // ---- marched zones and what is left for the regular blocks -----------------------------------------------------
+        // ---- marched zones and the rectangles of what they leave --------------------------------------------------------
         std::vector<MarchItem> mitems[MARCH_NT + 1];
-        std::vector<int> reg_list;
         std::vector<unsigned> cover;
-        plan_march(P, nbx_r, nby_r, mitems, reg_list, cover);
+        plan_march(P, nbx_r, nby_r, mitems, cover);
         {
             bool any_march = false;
             for (int k = 1; k <= MARCH_NT; ++k) any_march = any_march || !mitems[k].empty();
@@ -4269,16 +4032,6 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
                 if (!rcand.empty() && (e = hipMemcpy(P->d_rect_cand, rcand.data(), sizeof(int) * rcand.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
             }
         }
-        {
-            std::vector<int> all(nblk * 9, 0);
-            for (size_t b = 0; b < nblk; ++b) all[b * 9] = (int)b;
-            P->n_freg_all = (long long)nblk;
-            if ((e = hipMalloc((void **)&P->d_freg_all, sizeof(int) * all.size())) != hipSuccess) return fail(e, "regular block list");
-            if ((e = hipMemcpy(P->d_freg_all, all.data(), sizeof(int) * all.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-        }
-        P->n_freg = (long long)(reg_list.size() / 9);
-        if ((e = hipMalloc((void **)&P->d_freg_list, sizeof(int) * std::max<size_t>(reg_list.size(), 1))) != hipSuccess) return fail(e, "regular block list");
-        if (!reg_list.empty() && (e = hipMemcpy(P->d_freg_list, reg_list.data(), sizeof(int) * reg_list.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
         for (int k = 1; k <= MARCH_NT; ++k) {
             P->n_march_items[k] = (int)mitems[k].size();
             P->n_march_total += (long long)mitems[k].size();
@@ -4335,9 +4088,6 @@ static int blend_pyramids(sr_blend_plan *P, int dtype, void *const *h_d_tiles, c
     const int rows = P->row_end - P->row_begin;
     if (rows <= 0 || P->max_nl <= 1) return SR_OK;
     dim3 block(64, 4);
-    // TIMING PROBE ONLY (wrong pixels): leaves out the small launches of the chain -- level-2 border columns, levels 2 -> 5 down,
-    // the collapse 5 -> 2 -- to see what their stretched time beside the assessment costs the image stream
-    static const bool probe_skip_small = std::getenv("SR_PROBE_SKIP_SMALL") != nullptr;
     if (first && !P->weights_ready) {
         // weight pyramids: level 0 analytic (LUT) -> 1, then planar chain.  They depend only on the tile shapes and
         // the row windows, both fixed per plan: built by the first blend, kept in the arena for every later one.
@@ -4421,15 +4171,13 @@ static int blend_pyramids(sr_blend_plan *P, int dtype, void *const *h_d_tiles, c
             // levels 1 and 2 of the tiles with full row windows in one march (sr_down2.inc); the others keep the two launches
             if (i == 0) {
                 // Segment length (level-2 rows per work item).  Every item pays three extra level-1 rows, yet short segments win:
-                // measured at 200 MP (tools/down2_seg_sweep.sh) 6 .. 12 rows 0.51-0.54 ms, 16: 0.58, 32: 0.61, 64: 0.68 -- the
+                // measured at 200 MP (a sweep on one box) 6 .. 12 rows 0.51-0.54 ms, 16: 0.58, 32: 0.61, 64: 0.68 -- the
                 // kernel is bound by its stores' way through the memory system, which many short items keep busier.  The longest
                 // length up to 12 that still gives every wave slot four items, never below 6.
                 int items = 0, seg2 = 12;
                 {
                     const long long slots = (long long)ctx->num_cu * 16;    // four waves per SIMD
-                    const char *envs = std::getenv("SR_DOWN2_SEG");     // timing runs: a fixed segment length
-                    const int hi = envs ? std::max(2, atoi(envs)) : 12, lo = envs ? hi : 6;
-                    for (int cand = hi; cand >= lo; --cand) {
+                    for (int cand = 12; cand >= 6; --cand) {
                         long long total = 0;
                         items = 0;
                         seg2 = cand;
@@ -4443,18 +4191,16 @@ static int blend_pyramids(sr_blend_plan *P, int dtype, void *const *h_d_tiles, c
                         if (total >= 4 * slots) break;
                     }
                 }
-                const bool probe_nb = std::getenv("SR_DOWN2_PROBE_NOBORDER") != nullptr;     // timing probe only (wrong border columns)
-                dim3 grid2(items + (probe_nb ? 0 : (max_take_h1 + 3) / 4), 1, n_idx);
+                dim3 grid2(items + (max_take_h1 + 3) / 4, 1, n_idx);
                 hipLaunchKernelGGL((k_down2_march<3>), grid2, dim3(64), 0, ctx->stream, d_tiles, d_srcs, seg2, items, P->d_arena,
                                    (unsigned)(P->arena_floats * sizeof(float)), P->d_arena, P->d_luts);
-            } else if (!probe_skip_small) {
+            } else {
                 dim3 grid2((max_take_cols + 255) / 256, 1, n_idx);
                 hipLaunchKernelGGL(k_down2_cols, grid2, dim3(256), 0, ctx->stream, d_tiles, P->d_arena);
             }
             if (n_take == n_idx) continue;
             skip2 = 1;
         }
-        if (blk && probe_skip_small && i >= 2) continue;
         if (blk) {
             int max_cells = 0, seg_rows = 2;
             for (int cand = 32; cand >= 2; cand /= 2) {       // longest segments that still give ~8 blocks per CU;
@@ -4497,7 +4243,7 @@ static int blend_pyramids(sr_blend_plan *P, int dtype, void *const *h_d_tiles, c
     if (rc) return rc;
     // collapse chain: levels max_nl-1 .. 1 (.. 2 when the gather is fused: it builds R_1 itself, in LDS)
     for (int i = max_nl - 1; i >= (P->fused ? 2 : 1); --i) {
-        if (max_r[i] <= 0 || probe_skip_small) continue;
+        if (max_r[i] <= 0) continue;
         ProfScope ps(ctx, "up_level");
         if (P->cn == 3 || P->cn == 1) {
             dim3 grid((max_w[i] + 255) / 256, (max_r[i] + 7) / 8, n_idx);
@@ -4535,110 +4281,63 @@ static int blend_gather(sr_blend_plan *P, bool lap, int dtype, void *const *h_d_
         if (lap && P->fused) {
             const int nbx_r = std::max((P->canvas_w + FU_BW - 1) / FU_BW, 1), nby_r = std::max((rows + FU_BH - 1) / FU_BH, 1);
             const int n_edge = P->n_fedge_blocks;
-            // the marched zones first (long work items), then the edge and regular blocks of what is left; float tiles take
-            // the regular blocks everywhere
+            // the marched zones first (long work items), then what is left; float tiles take the block kernel everywhere
             const bool marched = dtype == SR_U8 && P->n_march_total > 0;
-            // The marched zones and the block kernel write disjoint cells of the canvas: with SR_GATHER_STREAMS=1 the small,
-            // latency-bound launches (3- / 4-tile zones, the block kernel) run on the context's side streams (forked off its
-            // stream here, joined below) beside the large 1- and 2-tile ones; default:
-            // one after the other on the context's stream (per-kernel timing).
-            static const bool side_ok = std::getenv("SR_GATHER_STREAMS") && std::getenv("SR_GATHER_STREAMS")[0] == '1';
-            bool forked = false;
-            hipStream_t ms[3] = {ctx->stream, ctx->stream, ctx->stream};
-            // (per-kernel timing of the parts wants them one after the other; timing the whole gather, or another family, does not)
-            const bool want_parts = ctx->prof && (ctx->prof_only.empty() || ctx->prof_only.rfind("gather_", 0) == 0);
-            if (marched && side_ok && !want_parts) {
-                if (!ctx->side_fork) {
-                    HIPCHK(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
-                    for (int i = 0; i < 2; ++i) {
-                        HIPCHK(hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking));
-                        HIPCHK(hipEventCreateWithFlags(&ctx->side_join[i], hipEventDisableTiming));
-                    }
-                }
-                HIPCHK(hipEventRecord(ctx->side_fork, ctx->stream));
-                for (int i = 0; i < 2; ++i) HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->side_fork, 0));
-                ms[1] = ctx->side[0];
-                ms[2] = ctx->side[1];
-                forked = true;
-            }
             const unsigned arena_bytes = (unsigned)std::min<size_t>(P->arena_floats * sizeof(float), 0xFFFFFFFFu);
             if (dtype == SR_U8 && P->n_march_items[1] > 0) {
                 ProfScope ps2(ctx, "gather_march1");
                 if (P->cn == 3)
-                    hipLaunchKernelGGL((k_final_march1<3>), dim3((unsigned)P->n_march_items[1]), dim3(64), 0, ms[0], P->d_march_items[1],
+                    hipLaunchKernelGGL((k_final_march1<3>), dim3((unsigned)P->n_march_items[1]), dim3(64), 0, ctx->stream, P->d_march_items[1],
                                        P->d_fdesc, P->d_arena, arena_bytes, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w);
                 else
-                    hipLaunchKernelGGL((k_final_march1<1>), dim3((unsigned)P->n_march_items[1]), dim3(64), 0, ms[0], P->d_march_items[1],
+                    hipLaunchKernelGGL((k_final_march1<1>), dim3((unsigned)P->n_march_items[1]), dim3(64), 0, ctx->stream, P->d_march_items[1],
                                        P->d_fdesc, P->d_arena, arena_bytes, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w);
             }
 #define LAUNCH_MARCHN(CNV, NTV)                                                                                          \
-    hipLaunchKernelGGL((k_final_marchn<CNV, NTV>), dim3((unsigned)P->n_march_items[NTV]), dim3(64 * NTV), 0, ms[NTV == 2 ? 0 : 1],  \
-                       P->d_march_items[NTV], P->d_fdesc, P->d_arena, arena_bytes, P->d_luts, d_canvas,                      \
-                       (long long)canvas_stride, d_canvas_f32, P->canvas_w)
-#define LAUNCH_MARCHP(NTV)                                                                                               \
-    hipLaunchKernelGGL((k_final_marchp<NTV>), dim3((unsigned)P->n_march_items[NTV]), dim3(192 * NTV), 0, ms[NTV == 2 ? 0 : 1],  \
+    hipLaunchKernelGGL((k_final_marchn<CNV, NTV>), dim3((unsigned)P->n_march_items[NTV]), dim3(64 * NTV), 0, ctx->stream,       \
                        P->d_march_items[NTV], P->d_fdesc, P->d_arena, arena_bytes, P->d_luts, d_canvas,                      \
                        (long long)canvas_stride, d_canvas_f32, P->canvas_w)
             static_assert(MARCH_NT == 4, "the tile counts launched here");
             for (int nt = 2; nt <= MARCH_NT && dtype == SR_U8; ++nt) {
                 if (P->n_march_items[nt] <= 0) continue;
                 ProfScope ps2(ctx, nt == 2 ? "gather_march2" : (nt == 3 ? "gather_march3" : "gather_march4"));
-                // SR_MARCH_PLANES=1 (A/B runs): a wave per (tile, plane) (k_final_marchp) instead of a wave per tile with all planes.
-                // Measured and rejected: two tiles 0.42 -> 0.59 ms, four 0.165 -> 0.216 -- the step waits on its requests, and
-                // three waves that each fetch the shared pixels and W_1 issue 30 requests per strip and step where two issued 18.
-                static const bool planes = std::getenv("SR_MARCH_PLANES") && std::getenv("SR_MARCH_PLANES")[0] == '1';
-                if (P->cn == 3 && planes) { if (nt == 2) LAUNCH_MARCHP(2); else if (nt == 3) LAUNCH_MARCHP(3); else LAUNCH_MARCHP(4); }
-                else if (P->cn == 3) { if (nt == 2) LAUNCH_MARCHN(3, 2); else if (nt == 3) LAUNCH_MARCHN(3, 3); else LAUNCH_MARCHN(3, 4); }
+                if (P->cn == 3) { if (nt == 2) LAUNCH_MARCHN(3, 2); else if (nt == 3) LAUNCH_MARCHN(3, 3); else LAUNCH_MARCHN(3, 4); }
                 else            { if (nt == 2) LAUNCH_MARCHN(1, 2); else if (nt == 3) LAUNCH_MARCHN(1, 3); else LAUNCH_MARCHN(1, 4); }
             }
 #undef LAUNCH_MARCHN
-#undef LAUNCH_MARCHP
-            const long long n_reg = marched ? P->n_freg : P->n_freg_all;
-            const int *reg_list = marched ? P->d_freg_list : P->d_freg_all;
             ProfScope ps3(ctx, "gather_rest");
             // beside a march the remainder runs as rectangles of cells (k_final_rect: every cell finished in one visit, no edge
-            // blocks); SR_RECT=0 restores the masked 128 x 16 blocks + edge blocks (A/B runs; identical bytes)
-            const bool rect_on = !(std::getenv("SR_RECT") && std::getenv("SR_RECT")[0] == '0');     // read per call: the tests switch it
-            const bool use_rects = marched && rect_on && P->d_rects != nullptr;
-            if (use_rects && P->n_rects > 0) {
-                if (P->cn == 3)
-                    hipLaunchKernelGGL((k_final_rect<3>), dim3((unsigned)P->n_rects), dim3(FU_THREADS), 0, ms[2], P->d_fdesc, P->d_rects,
-                                       P->d_rect_cand, P->d_arena, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w,
-                                       P->row_begin, P->row_end);
-                else
-                    hipLaunchKernelGGL((k_final_rect<1>), dim3((unsigned)P->n_rects), dim3(FU_THREADS), 0, ms[2], P->d_fdesc, P->d_rects,
-                                       P->d_rect_cand, P->d_arena, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w,
-                                       P->row_begin, P->row_end);
-            }
-            dim3 grid((unsigned)std::max<long long>(n_edge + n_reg, 1)), blk1(FU_THREADS);
+            // blocks); without one, the edge blocks and every regular block of k_final_fused
+            if (marched) {
+                if (P->n_rects > 0) {
+                    if (P->cn == 3)
+                        hipLaunchKernelGGL((k_final_rect<3>), dim3((unsigned)P->n_rects), dim3(FU_THREADS), 0, ctx->stream, P->d_fdesc, P->d_rects,
+                                           P->d_rect_cand, P->d_arena, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w,
+                                           P->row_begin, P->row_end);
+                    else
+                        hipLaunchKernelGGL((k_final_rect<1>), dim3((unsigned)P->n_rects), dim3(FU_THREADS), 0, ctx->stream, P->d_fdesc, P->d_rects,
+                                           P->d_rect_cand, P->d_arena, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w,
+                                           P->row_begin, P->row_end);
+                }
+            } else {
+                dim3 grid((unsigned)(n_edge + (long long)nbx_r * nby_r)), blk1(FU_THREADS);
 #define LAUNCH_FUSED(DT, CNV)                                                                                          \
-    hipLaunchKernelGGL((k_final_fused<DT, CNV>), grid, blk1, 0, ms[2], P->d_fdesc, P->d_fcand_off, P->d_fcand_idx,  \
-                       P->d_fedge_blocks, P->d_fedge_cand, n_edge, nbx_r, reg_list, P->d_arena, P->d_luts, d_canvas,   \
+    hipLaunchKernelGGL((k_final_fused<DT, CNV>), grid, blk1, 0, ctx->stream, P->d_fdesc, P->d_fcand_off, P->d_fcand_idx,  \
+                       P->d_fedge_blocks, P->d_fedge_cand, n_edge, nbx_r, P->d_arena, P->d_luts, d_canvas,             \
                        (long long)canvas_stride, d_canvas_f32, P->canvas_w, P->row_begin, P->row_end)
-            if (!use_rects && n_edge + n_reg > 0) {
                 if (P->cn == 3) { if (dtype == SR_U8) LAUNCH_FUSED(SRC_U8, 3); else LAUNCH_FUSED(SRC_F32, 3); }
                 else            { if (dtype == SR_U8) LAUNCH_FUSED(SRC_U8, 1); else LAUNCH_FUSED(SRC_F32, 1); }
-            }
 #undef LAUNCH_FUSED
-            if (forked) {
-                for (int i = 0; i < 2; ++i) HIPCHK(hipEventRecord(ctx->side_join[i], ctx->side[i]));
-                for (int i = 0; i < 2; ++i) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->side_join[i], 0));
             }
-        } else if (P->cn == 3 || P->cn == 1) {
+        } else if (P->cn == 3 || P->cn == 1) {                  // weighted average (their Laplacian blend is fused, above)
             const int nbx_r = std::max((P->canvas_w + FIN_BW - 1) / FIN_BW, 1), nby_r = std::max((rows + FIN_BH - 1) / FIN_BH, 1);
             dim3 grid((unsigned)(P->n_edge_blocks + (long long)nbx_r * nby_r));     // edge blocks first, then the regular ones
-#define LAUNCH_BLK(DT, LAPV, CNV)                                                                               \
-    hipLaunchKernelGGL((k_final_fast<DT, LAPV, CNV>), grid, block, 0, ctx->stream, P->d_fdesc, P->d_cand_off,     \
-                       P->d_cand_idx, P->d_edge_blocks, P->d_edge_cand, P->n_edge_blocks, nbx_r, P->d_arena, \
-                       P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w, P->row_begin,   \
-                       P->row_end)
-            if (P->cn == 3) {
-                if (lap) { if (dtype == SR_U8) LAUNCH_BLK(SRC_U8, true, 3); else LAUNCH_BLK(SRC_F32, true, 3); }
-                else     { if (dtype == SR_U8) LAUNCH_BLK(SRC_U8, false, 3); else LAUNCH_BLK(SRC_F32, false, 3); }
-            } else {
-                if (lap) { if (dtype == SR_U8) LAUNCH_BLK(SRC_U8, true, 1); else LAUNCH_BLK(SRC_F32, true, 1); }
-                else     { if (dtype == SR_U8) LAUNCH_BLK(SRC_U8, false, 1); else LAUNCH_BLK(SRC_F32, false, 1); }
-            }
+#define LAUNCH_BLK(DT, CNV)                                                                                     \
+    hipLaunchKernelGGL((k_final_fast<DT, CNV>), grid, block, 0, ctx->stream, P->d_fdesc, P->d_cand_off,           \
+                       P->d_cand_idx, P->d_edge_blocks, P->d_edge_cand, P->n_edge_blocks, nbx_r, P->d_luts,  \
+                       d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w, P->row_begin, P->row_end)
+            if (P->cn == 3) { if (dtype == SR_U8) LAUNCH_BLK(SRC_U8, 3); else LAUNCH_BLK(SRC_F32, 3); }
+            else            { if (dtype == SR_U8) LAUNCH_BLK(SRC_U8, 1); else LAUNCH_BLK(SRC_F32, 1); }
 #undef LAUNCH_BLK
         } else {
             dim3 grid((P->canvas_w + 63) / 64, (rows + 3) / 4);
@@ -5557,9 +5256,8 @@ static int assess_impl(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const 
         {
             ProfScope ps(ctx, scope);
             const dim3 grid((unsigned)gbx, (unsigned)gby), block(AM_TX);
-            static const size_t lds_pad = std::getenv("SR_ASSESS_PAD") ? (size_t)atoi(std::getenv("SR_ASSESS_PAD")) : 0;   // experiments: fewer blocks per CU
 #define LAUNCH_ASSESS(CNV, GS, US, SC)                                                                               \
-    hipLaunchKernelGGL((k_assess_march<CNV, GS, US, SC>), grid, block, lds_pad, ctx->stream, d_a, (long long)stride_a, d_b,   \
+    hipLaunchKernelGGL((k_assess_march<CNV, GS, US, SC>), grid, block, 0, ctx->stream, d_a, (long long)stride_a, d_b,   \
                        (long long)stride_b, P, part)
 #define LAUNCH_ASSESS_V(CNV)                                                                                            \
     do {                                                                                                                \

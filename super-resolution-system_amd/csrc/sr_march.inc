@@ -62,24 +62,11 @@ __device__ __forceinline__ u3_t march_ld3(march_rsrc r, unsigned voff, unsigned 
 {
     return __builtin_bit_cast(u3_t, __builtin_amdgcn_raw_buffer_load_b96(r, voff, soff, 0));
 }
-// a level-2 row at the lane's three columns
-__device__ __forceinline__ u3_t march_ld_l2(march_rsrc r, unsigned voff, unsigned soff)
-{
-#ifdef MARCH_PROBE_L2          /* timing probe only (wrong values): one dword per lane instead of three overlapping ones */
-    const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(r, voff + 4, soff, 0);
-    u3_t o;
-    o.x = v; o.y = v; o.z = v;
-    return o;
-#else
-    return march_ld3(r, voff, soff);
-#endif
-}
 
 // the value `v` of the lane to the left / right: a whole-wave shift by one lane (DPP wave_shr:1 / wave_shl:1 -- probed on
 // gfx950, tools/ubench_cvt.hip: lane i takes lane i - 1 / i + 1 across all 64 lanes; the end lane keeps `v`).  One VALU move
 // with a few cycles of latency; the same fetch through the LDS crossbar (ds_bpermute_b32) costs no VALU slot but parks the
 // wave for a full LDS round trip four times per plane and step -- 58 % of the waves' time in the first version.
-#ifndef MARCH_BPERMUTE
 __device__ __forceinline__ float lane_left(float v)
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x138, 0xf, 0xf, false));
@@ -88,16 +75,6 @@ __device__ __forceinline__ float lane_right(float v)
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x130, 0xf, 0xf, false));
 }
-#define LANE_FROM_L(v) lane_left(v)
-#define LANE_FROM_R(v) lane_right(v)
-#else
-__device__ __forceinline__ float lane_from(int addr, float v)
-{
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
-}
-#define LANE_FROM_L(v) lane_from(addr_l, v)
-#define LANE_FROM_R(v) lane_from(addr_r, v)
-#endif
 
 enum { MT_XO = 1, MT_YO = 2, MT_P1 = 4, MT_FXUNIT = 8, MT_W1UNIT = 16 };
 #define MARCH_W1_MARGIN 6            /* pixels beyond the feather width from which the level-1 weight is exactly 1, too */
@@ -150,7 +127,7 @@ __device__ __forceinline__ void march_l2_hpass(bool p1, u3_t g, u3_t r, f2_t &na
 // pyrUp sums of the four pixel columns (up_pairs' expressions, pixel columns paired by phase): hg / hr = {(h0, h2), (h1, h3)}
 // of G_1 / R_1.  g = G_1 at the own columns (a, a + 1), w = W_1 there, l2g / l2r = the new level-2 row (EVEN rows only).
 template <bool EVEN, bool W1U = false>
-__device__ __forceinline__ void march_l1_row(unsigned flags, MarchP &S, f2_t g, f2_t w, u3_t l2g, u3_t l2r, int addr_l, int addr_r,
+__device__ __forceinline__ void march_l1_row(unsigned flags, MarchP &S, f2_t g, f2_t w, u3_t l2g, u3_t l2r,
                                              f2_t (&hg)[2], f2_t (&hr)[2])
 {
     const bool p1 = (flags & MT_P1) != 0;
@@ -174,13 +151,11 @@ __device__ __forceinline__ void march_l1_row(unsigned flags, MarchP &S, f2_t g, 
     const float rb = W1U ? ub.y + (g.y - ub.x) : ub.y + (g.y - ub.x) * w.y;
     // taps 0 .. 3 of the cell: the left lane's column a + 1, the own columns, the right lane's column a
     f2_t g01, g23, r01, r12, r23;
-    g01.x = LANE_FROM_L(g.y); g01.y = g.x;
-    g23.x = g.y; g23.y = LANE_FROM_R(g.x);
-    r01.x = LANE_FROM_L(rb); r01.y = ra;
+    g01.x = lane_left(g.y); g01.y = g.x;
+    g23.x = g.y; g23.y = lane_right(g.x);
+    r01.x = lane_left(rb); r01.y = ra;
     r12.x = ra; r12.y = rb;
-    r23.x = rb; r23.y = LANE_FROM_R(ra);
-    (void)addr_l;
-    (void)addr_r;
+    r23.x = rb; r23.y = lane_right(ra);
     if (!(flags & MT_XO)) {
         hg[0] = (g01 + g * 6.0f) + g23;
         hg[1] = g + g23;
@@ -295,7 +270,7 @@ __device__ __forceinline__ void march_tile_uv(MarchU &U, MarchV &V, const FinalD
 // g1 / w1 / g2 / r2: this plane's arena offsets of rows r0 / m0 (not advanced here: the caller advances the tile's rows
 // once for all planes).  Loads are waited for on the spot: once per work item.
 __device__ __forceinline__ void march_plane_warmup(const MarchU &U, const MarchV &V, MarchP &S, march_rsrc arena, unsigned g1,
-                                                   unsigned w1, unsigned g2, unsigned r2, int addr_l, int addr_r)
+                                                   unsigned w1, unsigned g2, unsigned r2)
 {
     const bool p1 = (U.flags & MT_P1) != 0;
 #pragma unroll
@@ -306,11 +281,11 @@ __device__ __forceinline__ void march_plane_warmup(const MarchU &U, const MarchV
     const f2_t ga = march_ld2(arena, V.v1, g1), gb = march_ld2(arena, V.v1, g1 + U.p1b);
     const f2_t wa = march_ld2(arena, V.v1, w1), wb = march_ld2(arena, V.v1, w1 + U.p1b);
     if (U.r0 & 1) {
-        march_l1_row<false>(U.flags, S, ga, wa, n2g, n2r, addr_l, addr_r, S.HG[0], S.HR[0]);
-        march_l1_row<true>(U.flags, S, gb, wb, n2g, n2r, addr_l, addr_r, S.HG[1], S.HR[1]);
+        march_l1_row<false>(U.flags, S, ga, wa, n2g, n2r, S.HG[0], S.HR[0]);
+        march_l1_row<true>(U.flags, S, gb, wb, n2g, n2r, S.HG[1], S.HR[1]);
     } else {
-        march_l1_row<true>(U.flags, S, ga, wa, n2g, n2r, addr_l, addr_r, S.HG[0], S.HR[0]);
-        march_l1_row<false>(U.flags, S, gb, wb, n2g, n2r, addr_l, addr_r, S.HG[1], S.HR[1]);
+        march_l1_row<true>(U.flags, S, ga, wa, n2g, n2r, S.HG[0], S.HR[0]);
+        march_l1_row<false>(U.flags, S, gb, wb, n2g, n2r, S.HG[1], S.HR[1]);
     }
 }
 
@@ -374,8 +349,8 @@ __device__ __forceinline__ void march_request_planes(MarchU &U, const MarchV &V,
     if (EVEN) {
 #pragma unroll
         for (int c = 0; c < CN; ++c) {
-            L.l2g[c] = march_ld_l2(arena, V.v2, U.g2 + c * U.plane2b);
-            L.l2r[c] = march_ld_l2(arena, V.v2, U.r2 + c * U.plane2b);
+            L.l2g[c] = march_ld3(arena, V.v2, U.g2 + c * U.plane2b);
+            L.l2r[c] = march_ld3(arena, V.v2, U.r2 + c * U.plane2b);
         }
         U.g2 += U.p2b;
         U.r2 += U.p2b;
@@ -443,9 +418,9 @@ __device__ __forceinline__ f2_t march_px_pair(const unsigned (&wd)[CN == 3 ? 3 :
 // L / H hold this step's data on entry and, when `more`, the data of the step after next (same parity) on return.
 template <int CN, int PH, bool EVEN, bool UNIT, int FL, bool W1U>
 __device__ __forceinline__ void march1_step(MarchU &U, const MarchV &V, MarchP (&S)[CN], MarchPlaneLoad<CN> &L,
-                                            MarchSharedLoad<CN> &H, march_rsrc arena, bool more,
-                                            int addr_l, int addr_r, bool useful, march_rsrc out, unsigned vout, unsigned o_e,
-                                            unsigned o_o, march_rsrc outf, bool with_f, unsigned f_e, unsigned f_o)
+                                            MarchSharedLoad<CN> &H, march_rsrc arena, bool more, bool useful, march_rsrc out,
+                                            unsigned vout, unsigned o_e, unsigned o_o, march_rsrc outf, bool with_f, unsigned f_e,
+                                            unsigned f_o)
 {
     const unsigned flags = FL >= 0 ? (unsigned)FL : U.flags;          // the phases as constants where the caller knows them
     f2_t zero;
@@ -475,12 +450,12 @@ __device__ __forceinline__ void march1_step(MarchU &U, const MarchV &V, MarchP (
 #pragma unroll
     for (int c = 0; c < CN; ++c) {
         f2_t hg[2], hr[2], ug[2][2], ur[2][2];
-        march_l1_row<EVEN, W1U>(flags, S[c], L.g[c], H.w, L.l2g[c], L.l2r[c], addr_l, addr_r, hg, hr);
+        march_l1_row<EVEN, W1U>(flags, S[c], L.g[c], H.w, L.l2g[c], L.l2r[c], hg, hr);
         if (more) {                                                 // this plane's rows of the step after next
             L.g[c] = march_ld2(arena, V.v1, U.g1 + c * U.plane1b);
             if (EVEN) {
-                L.l2g[c] = march_ld_l2(arena, V.v2, U.g2 + c * U.plane2b);
-                L.l2r[c] = march_ld_l2(arena, V.v2, U.r2 + c * U.plane2b);
+                L.l2g[c] = march_ld3(arena, V.v2, U.g2 + c * U.plane2b);
+                L.l2r[c] = march_ld3(arena, V.v2, U.r2 + c * U.plane2b);
             }
         }
         march_vpass<PH>(flags, S[c], hg, hr, ug, ur);
@@ -511,11 +486,7 @@ __device__ __forceinline__ void march1_step(MarchU &U, const MarchV &V, MarchP (
         }
         march_request_shared<CN, W1U>(U, V, arena, H);
     }
-#ifdef MARCH_PROBE_NOSTORE      /* timing probe only */
-    if (useful && vout == 0x7fffffffu) {
-#else
     if (useful) {
-#endif
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             if constexpr (CN == 3) {
@@ -535,9 +506,9 @@ __device__ __forceinline__ void march1_step(MarchU &U, const MarchV &V, MarchP (
 // exists once per phase combination: straight-line code, no scalar tests and branches (at two waves per SIMD a wave's own
 // instruction stream, scalar instructions included, is what bounds a step).
 template <int CN, bool E0, bool UNIT, int FL, bool W1U>
-__device__ __forceinline__ void march1_loop(MarchU &U, const MarchV &V, MarchP (&S)[CN], march_rsrc arena, int nstep, int addr_l,
-                                            int addr_r, bool useful, march_rsrc out, unsigned vout, unsigned cstride,
-                                            march_rsrc outf, bool with_f, unsigned fstride)
+__device__ __forceinline__ void march1_loop(MarchU &U, const MarchV &V, MarchP (&S)[CN], march_rsrc arena, int nstep,
+                                            bool useful, march_rsrc out, unsigned vout, unsigned cstride, march_rsrc outf,
+                                            bool with_f, unsigned fstride)
 {
     MarchPlaneLoad<CN> LA, LB;
     MarchSharedLoad<CN> HA, HB;
@@ -550,16 +521,16 @@ __device__ __forceinline__ void march1_loop(MarchU &U, const MarchV &V, MarchP (
 #pragma unroll 1
     for (int s = 0; s < nstep; s += 2) {
         const bool more = s + 2 < nstep;
-        march1_step<CN, 0, E0, UNIT, FL, W1U>(U, V, S, LA, HA, arena, more, addr_l, addr_r, useful, out, vout, o_e, o_o, outf, with_f, f_e, f_o);
+        march1_step<CN, 0, E0, UNIT, FL, W1U>(U, V, S, LA, HA, arena, more, useful, out, vout, o_e, o_o, outf, with_f, f_e, f_o);
         o_e += 2 * cstride; o_o += 2 * cstride; f_e += 2 * fstride; f_o += 2 * fstride;
-        march1_step<CN, 1, !E0, UNIT, FL, W1U>(U, V, S, LB, HB, arena, more, addr_l, addr_r, useful, out, vout, o_e, o_o, outf, with_f, f_e, f_o);
+        march1_step<CN, 1, !E0, UNIT, FL, W1U>(U, V, S, LB, HB, arena, more, useful, out, vout, o_e, o_o, outf, with_f, f_e, f_o);
         o_e += 2 * cstride; o_o += 2 * cstride; f_e += 2 * fstride; f_o += 2 * fstride;
     }
 }
 
 // The work item's common start: lanes, the tile's uniform and per-lane parts, the warm-up of every plane.
 struct MarchLanes {
-    int addr_l, addr_r, x_lane, x_px;
+    int x_lane, x_px;
     bool useful;
 };
 __device__ __forceinline__ MarchLanes march_lanes(const MarchItem &it, int lane)
@@ -571,8 +542,6 @@ __device__ __forceinline__ MarchLanes march_lanes(const MarchItem &it, int lane)
     m.useful = lane >= 1 && lane <= ncell;
     m.x_lane = it.x0 + 4 * lane_c;
     m.x_px = it.x0 + 4 * lane_p;
-    m.addr_l = max(lane - 1, 0) * 4;
-    m.addr_r = min(lane + 1, 63) * 4;
     return m;
 }
 
@@ -594,7 +563,7 @@ __global__ __launch_bounds__(64, MARCH1_WAVES) void k_final_march1(const MarchIt
     march_tile_uv(U, V, D, luts, M.x_lane, M.x_px, it.y0, M.useful, CN);
 #pragma unroll
     for (int c = 0; c < CN; ++c)
-        march_plane_warmup(U, V, S[c], arena, U.g1 + c * U.plane1b, U.w1, U.g2 + c * U.plane2b, U.r2 + c * U.plane2b, M.addr_l, M.addr_r);
+        march_plane_warmup(U, V, S[c], arena, U.g1 + c * U.plane1b, U.w1, U.g2 + c * U.plane2b, U.r2 + c * U.plane2b);
     march_after_warmup(U);
     // every row weight of the item is lut[fw] == 1 (the column weights: MT_FXUNIT)
     const int ly0 = it.y0 - D.y;
@@ -606,7 +575,7 @@ __global__ __launch_bounds__(64, MARCH1_WAVES) void k_final_march1(const MarchIt
                                             with_f ? 0xFFFFFFFFu : 0u);
     const unsigned vout = (unsigned)M.x_px * CN;
     const bool e0 = !(U.r0 & 1);                                    // the first step produces level-1 row r0 + 2
-#define MARCH_GO(EV, UV, FLV, WV) march1_loop<CN, EV, UV, FLV, WV>(U, V, S, arena, nstep, M.addr_l, M.addr_r, M.useful, out, vout, (unsigned)cstride, outf, with_f, fstride)
+#define MARCH_GO(EV, UV, FLV, WV) march1_loop<CN, EV, UV, FLV, WV>(U, V, S, arena, nstep, M.useful, out, vout, (unsigned)cstride, outf, with_f, fstride)
 #define MARCH_GO_FL(FLV) do { if (e0) MARCH_GO(true, true, FLV, true); else MARCH_GO(false, true, FLV, true); } while (0)
     // ... and W_1 is 1 as well MARCH_W1_MARGIN pixels further in (all of a grid's single coverage but the strips that touch the
     // feather ramps): the phase-specialised loops leave W_1 out; unit items closer to the ramps take the general loop
@@ -649,8 +618,8 @@ struct MarchX {
 // wave's canvas row] (finishers only)
 template <int CN, int NT, int PH, bool EVEN, int FL>
 __device__ __forceinline__ void marchn_step(MarchU &U, const MarchV &V, MarchP (&S)[CN], MarchPlaneLoad<CN> &L,
-                                            MarchSharedLoad<CN> &H, march_rsrc arena, bool more,
-                                            int addr_l, int addr_r, bool useful, bool finisher, float *xw, const float *xr,
+                                            MarchSharedLoad<CN> &H, march_rsrc arena, bool more, bool useful, bool finisher,
+                                            float *xw, const float *xr,
                                             march_rsrc out, unsigned vout, unsigned o_fin, march_rsrc outf, bool with_f,
                                             unsigned f_fin)
 {
@@ -663,12 +632,12 @@ __device__ __forceinline__ void marchn_step(MarchU &U, const MarchV &V, MarchP (
 #pragma unroll
     for (int c = 0; c < CN; ++c) {
         f2_t hg[2], hr[2], ug[2][2], ur[2][2];
-        march_l1_row<EVEN>(flags, S[c], L.g[c], H.w, L.l2g[c], L.l2r[c], addr_l, addr_r, hg, hr);
+        march_l1_row<EVEN>(flags, S[c], L.g[c], H.w, L.l2g[c], L.l2r[c], hg, hr);
         if (more) {                                                 // this plane's rows of the step after next
             L.g[c] = march_ld2(arena, V.v1, U.g1 + c * U.plane1b);
             if (EVEN) {
-                L.l2g[c] = march_ld_l2(arena, V.v2, U.g2 + c * U.plane2b);
-                L.l2r[c] = march_ld_l2(arena, V.v2, U.r2 + c * U.plane2b);
+                L.l2g[c] = march_ld3(arena, V.v2, U.g2 + c * U.plane2b);
+                L.l2r[c] = march_ld3(arena, V.v2, U.r2 + c * U.plane2b);
             }
         }
         march_vpass<PH>(flags, S[c], hg, hr, ug, ur);
@@ -738,11 +707,7 @@ __device__ __forceinline__ void marchn_step(MarchU &U, const MarchV &V, MarchP (
             wd[b1 >> 2] = march_put_u8(a[p].y, b1 & 3, wd[b1 >> 2]);
         }
     }
-#ifdef MARCH_PROBE_NOSTORE      /* timing probe only */
-    if (useful && vout == 0x7fffffffu) {
-#else
     if (useful) {
-#endif
         if constexpr (CN == 3) {
             u3_t o;
             o.x = wd[0]; o.y = wd[1]; o.z = wd[2];
@@ -754,9 +719,9 @@ __device__ __forceinline__ void marchn_step(MarchU &U, const MarchV &V, MarchP (
 }
 
 template <int CN, int NT, bool E0, int FL>
-__device__ __forceinline__ void marchn_loop(MarchU &U, const MarchV &V, MarchP (&S)[CN], march_rsrc arena, int nstep, int addr_l,
-                                            int addr_r, bool useful, bool finisher, float *xw, const float *xr, march_rsrc out,
-                                            unsigned vout, unsigned o_fin, unsigned cstride, march_rsrc outf, bool with_f,
+__device__ __forceinline__ void marchn_loop(MarchU &U, const MarchV &V, MarchP (&S)[CN], march_rsrc arena, int nstep,
+                                            bool useful, bool finisher, float *xw, const float *xr, march_rsrc out, unsigned vout,
+                                            unsigned o_fin, unsigned cstride, march_rsrc outf, bool with_f,
                                             unsigned f_fin, unsigned fstride)
 {
     typedef MarchX<CN, NT> X;
@@ -769,9 +734,9 @@ __device__ __forceinline__ void marchn_loop(MarchU &U, const MarchV &V, MarchP (
 #pragma unroll 1
     for (int s = 0; s < nstep; s += 2) {
         const bool more = s + 2 < nstep;
-        marchn_step<CN, NT, 0, E0, FL>(U, V, S, LA, HA, arena, more, addr_l, addr_r, useful, finisher, xw, xr, out, vout, o_fin, outf, with_f, f_fin);
+        marchn_step<CN, NT, 0, E0, FL>(U, V, S, LA, HA, arena, more, useful, finisher, xw, xr, out, vout, o_fin, outf, with_f, f_fin);
         o_fin += 2 * cstride; f_fin += 2 * fstride;
-        marchn_step<CN, NT, 1, !E0, FL>(U, V, S, LB, HB, arena, more, addr_l, addr_r, useful, finisher, xw + X::SLOT, xr + X::SLOT, out, vout, o_fin, outf, with_f, f_fin);
+        marchn_step<CN, NT, 1, !E0, FL>(U, V, S, LB, HB, arena, more, useful, finisher, xw + X::SLOT, xr + X::SLOT, out, vout, o_fin, outf, with_f, f_fin);
         o_fin += 2 * cstride; f_fin += 2 * fstride;
     }
 }
@@ -797,7 +762,7 @@ __global__ __launch_bounds__(64 * NT, MARCHN_WAVES) void k_final_marchn(const Ma
     march_tile_uv(U, V, D, luts, M.x_lane, M.x_px, it.y0, M.useful, CN);
 #pragma unroll
     for (int c = 0; c < CN; ++c)
-        march_plane_warmup(U, V, S[c], arena, U.g1 + c * U.plane1b, U.w1, U.g2 + c * U.plane2b, U.r2 + c * U.plane2b, M.addr_l, M.addr_r);
+        march_plane_warmup(U, V, S[c], arena, U.g1 + c * U.plane1b, U.w1, U.g2 + c * U.plane2b, U.r2 + c * U.plane2b);
     march_after_warmup(U);
     const unsigned fstride = (unsigned)cw * CN * 4u;
     const bool with_f = canvas_f32 != nullptr;
@@ -810,7 +775,7 @@ __global__ __launch_bounds__(64 * NT, MARCHN_WAVES) void k_final_marchn(const Ma
     const float *xr = &xch[(wv & 1) * X::ROW + lane * 2];
     const unsigned o_fin = (wv & 1) ? (unsigned)cstride : 0u, f_fin = (wv & 1) ? fstride : 0u;
     const bool e0 = !(U.r0 & 1);
-#define MARCHN_GO(EV, FLV) marchn_loop<CN, NT, EV, FLV>(U, V, S, arena, nstep, M.addr_l, M.addr_r, M.useful, finisher, xw, xr, out, vout, o_fin, (unsigned)cstride, outf, with_f, f_fin, fstride)
+#define MARCHN_GO(EV, FLV) marchn_loop<CN, NT, EV, FLV>(U, V, S, arena, nstep, M.useful, finisher, xw, xr, out, vout, o_fin, (unsigned)cstride, outf, with_f, f_fin, fstride)
 #define MARCHN_GO_FL(FLV) do { if (e0) MARCHN_GO(true, FLV); else MARCHN_GO(false, FLV); } while (0)
     switch (U.flags & (MT_XO | MT_YO | MT_P1)) {                    // straight-line loops: one per phase combination of this wave's tile
     case 0: MARCHN_GO_FL(0); break;
@@ -824,194 +789,4 @@ __global__ __launch_bounds__(64 * NT, MARCHN_WAVES) void k_final_marchn(const Ma
     }
 #undef MARCHN_GO_FL
 #undef MARCHN_GO
-}
-
-// ---------------------------------------------------------------------------------------------
-// Several tiles, RGB, a wave per (tile, PLANE): a workgroup of 3 NT waves per strip.  The step of k_final_marchn's wave is
-// three planes of level-2 / level-1 / vertical passes one after the other (~420 instructions before the exchange, ~120 more
-// for the two finishing waves) at two waves per SIMD; here a wave carries one plane's state (24 registers instead of 72) and
-// a third of that chain, and four waves fit a SIMD.  What the planes share is fetched by each of them -- the tile's pixel
-// dwords (all 12 bytes: the plane's four are picked with two v_perm_b32 whose selectors are wave-uniform) and W_1 -- and
-// found in the L1 by two of the three.  The exchange slots, the finishing (waves 0 and 1: canvas rows 0 and 1, tiles summed
-// in list order) and the results are those of k_final_marchn<3, NT>.
-// NOT the default (SR_MARCH_PLANES=1 selects it): bit-identical, but slower -- 0.59 against 0.42 ms for the two-tile zones of
-// the 200 MP grid, 0.216 against 0.165 for the four-tile ones (profiles/r04_gather_probes.txt): the steps wait on memory
-// requests, not on their instruction chain, and this form issues 30 requests per strip and step where the other issues 18.
-// ---------------------------------------------------------------------------------------------
-#ifndef MARCHP_WAVES
-#define MARCHP_WAVES 4
-#endif
-template <int NT, int PH, bool EVEN, int FL>
-__device__ __forceinline__ void marchp_step(MarchU &U, const MarchV &V, MarchP &S, MarchPlaneLoad<1> &L, MarchSharedLoad<3> &H,
-                                            march_rsrc arena, bool more, int addr_l, int addr_r, bool useful, bool finisher,
-                                            int plane, unsigned sel1, unsigned sel2, float *xw, const float *xr, march_rsrc out,
-                                            unsigned vout, unsigned o_fin, march_rsrc outf, bool with_f, unsigned f_fin)
-{
-    constexpr int CN = 3;
-    typedef MarchX<CN, NT> X;
-    const unsigned flags = (unsigned)FL;
-    f2_t w0[2][2];
-    march_weights(U, V, w0);
-    const int row_e = (flags & MT_YO) ? X::ROW : 0, row_o = X::ROW - row_e;
-    {
-        f2_t hg[2], hr[2], ug[2][2], ur[2][2];
-        march_l1_row<EVEN>(flags, S, L.g[0], H.w, L.l2g[0], L.l2r[0], addr_l, addr_r, hg, hr);
-        if (more) {                                                 // the plane's rows of the step after next
-            L.g[0] = march_ld2(arena, V.v1, U.g1);
-            if (EVEN) {
-                L.l2g[0] = march_ld_l2(arena, V.v2, U.g2);
-                L.l2r[0] = march_ld_l2(arena, V.v2, U.r2);
-            }
-        }
-        march_vpass<PH>(flags, S, hg, hr, ug, ur);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            // bytes plane, plane + 3, plane + 6, plane + 9 of the row's twelve into one dword
-            unsigned pw[1];
-            pw[0] = __builtin_amdgcn_perm(H.pxw[q][2], __builtin_amdgcn_perm(H.pxw[q][1], H.pxw[q][0], sel1), sel2);
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const f2_t a = ur[q][p] + (march_px_pair<1>(pw, p, 0) - ug[q][p]) * w0[q][p];
-                *(f2_t *)(xw + (q ? row_o : row_e) + p * 128) = a;  // xw: this tile's slot, this plane's vector
-            }
-        }
-    }
-    if (plane == 0) {                                               // wave-uniform
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) *(f2_t *)(xw + (q ? row_o : row_e) + CN * 256 + p * 128) = w0[q][p];
-    }
-    if (more) {
-        U.g1 += U.p1b;
-        if (EVEN) {
-            U.g2 += U.p2b;
-            U.r2 += U.p2b;
-        }
-        march_request_shared<CN>(U, V, arena, H);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (!finisher) return;
-    f2_t zero;
-    zero.x = zero.y = 0.f;
-    f2_t wsum[2];
-    wsum[0] = wsum[1] = zero;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {                                  // wacc = 0; wacc += W_0 of every tile, list order
-        wsum[0] += *(const f2_t *)(xr + t * 2 * X::ROW + CN * 256);
-        wsum[1] += *(const f2_t *)(xr + t * 2 * X::ROW + CN * 256 + 128);
-    }
-    const bool ones = wsum[0].x == 1.0f && wsum[0].y == 1.0f && wsum[1].x == 1.0f && wsum[1].y == 1.0f;
-    const bool dodiv = __all(ones || !useful) == 0;
-    f2_t wc[2], rr[2];
-    if (dodiv) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) rr[p] = march_recip(wsum[p], wc[p]);
-    }
-    unsigned wd[3] = {0u, 0u, 0u};
-#pragma unroll
-    for (int c = 0; c < CN; ++c) {
-        f2_t a[2];
-        a[0] = a[1] = zero;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {                              // acc = 0; acc += R_0 of every tile, list order
-            a[0] += *(const f2_t *)(xr + t * 2 * X::ROW + c * 256);
-            a[1] += *(const f2_t *)(xr + t * 2 * X::ROW + c * 256 + 128);
-        }
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            if (dodiv) a[p] = march_div(a[p], wc[p], rr[p]);
-            const int b0 = CN * p + c, b1 = CN * (p + 2) + c;
-            if (with_f && useful) {
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a[p].x), outf, vout * 4u + b0 * 4, f_fin, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a[p].y), outf, vout * 4u + b1 * 4, f_fin, 0);
-            }
-            wd[b0 >> 2] = march_put_u8(a[p].x, b0 & 3, wd[b0 >> 2]);
-            wd[b1 >> 2] = march_put_u8(a[p].y, b1 & 3, wd[b1 >> 2]);
-        }
-    }
-    if (useful) {
-        u3_t o;
-        o.x = wd[0]; o.y = wd[1]; o.z = wd[2];
-        __builtin_amdgcn_raw_buffer_store_b96(o, out, vout, o_fin, 0);
-    }
-}
-
-template <int NT, bool E0, int FL>
-__device__ __forceinline__ void marchp_loop(MarchU &U, const MarchV &V, MarchP &S, march_rsrc arena, int nstep, int addr_l,
-                                            int addr_r, bool useful, bool finisher, int plane, unsigned sel1, unsigned sel2, float *xw,
-                                            const float *xr, march_rsrc out, unsigned vout, unsigned o_fin, unsigned cstride,
-                                            march_rsrc outf, bool with_f, unsigned f_fin, unsigned fstride)
-{
-    typedef MarchX<3, NT> X;
-    MarchPlaneLoad<1> LA, LB;
-    MarchSharedLoad<3> HA, HB;
-    march_request_planes<1, E0>(U, V, arena, LA);
-    march_request_shared<3>(U, V, arena, HA);
-    march_request_planes<1, !E0>(U, V, arena, LB);
-    march_request_shared<3>(U, V, arena, HB);
-#pragma unroll 1
-    for (int s = 0; s < nstep; s += 2) {
-        const bool more = s + 2 < nstep;
-        marchp_step<NT, 0, E0, FL>(U, V, S, LA, HA, arena, more, addr_l, addr_r, useful, finisher, plane, sel1, sel2, xw, xr, out, vout, o_fin, outf, with_f, f_fin);
-        o_fin += 2 * cstride; f_fin += 2 * fstride;
-        marchp_step<NT, 1, !E0, FL>(U, V, S, LB, HB, arena, more, addr_l, addr_r, useful, finisher, plane, sel1, sel2, xw + X::SLOT, xr + X::SLOT, out, vout, o_fin, outf, with_f, f_fin);
-        o_fin += 2 * cstride; f_fin += 2 * fstride;
-    }
-}
-
-template <int NT>
-__global__ __launch_bounds__(192 * NT, MARCHP_WAVES) void k_final_marchp(const MarchItem *__restrict__ items, const FinalDesc *__restrict__ descs,
-                                                        const float *__restrict__ arena_p, unsigned arena_bytes,
-                                                        const float *__restrict__ luts, unsigned char *__restrict__ canvas,
-                                                        long long cstride, float *__restrict__ canvas_f32, int cw)
-{
-    constexpr int CN = 3;
-    typedef MarchX<CN, NT> X;
-    __shared__ __attribute__((aligned(16))) float xch[2 * X::SLOT];
-    const MarchItem &it = items[blockIdx.x];
-    const int nstep = it.nstep;
-    const int lane = (int)threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int tl = wv / 3, plane = wv - 3 * tl;                     // wave = (tile of the list, plane)
-    const MarchLanes M = march_lanes(it, lane);
-    const FinalDesc &D = descs[it.tile[tl]];
-    const march_rsrc arena = march_make_rsrc(arena_p, arena_bytes);
-    MarchU U;
-    MarchV V;
-    MarchP S;
-    march_tile_uv(U, V, D, luts, M.x_lane, M.x_px, it.y0, M.useful, CN);
-    march_plane_warmup(U, V, S, arena, U.g1 + plane * U.plane1b, U.w1, U.g2 + plane * U.plane2b, U.r2 + plane * U.plane2b, M.addr_l, M.addr_r);
-    march_after_warmup(U);
-    U.g1 += plane * U.plane1b;                                      // from here on the row offsets are this plane's
-    U.g2 += plane * U.plane2b;
-    U.r2 += plane * U.plane2b;
-    // bytes plane + 3 k (k = 0 .. 3) of twelve: first those in dwords 0 and 1, then dword 2's
-    const unsigned sel1 = plane == 0 ? 0x0c060300u : (plane == 1 ? 0x0c070401u : 0x0c0c0502u);
-    const unsigned sel2 = plane == 0 ? 0x05020100u : (plane == 1 ? 0x06020100u : 0x07040100u);
-    const unsigned fstride = (unsigned)cw * CN * 4u;
-    const bool with_f = canvas_f32 != nullptr;
-    const march_rsrc out = march_make_rsrc(canvas + (long long)it.y0 * cstride, 0xFFFFFFFFu);
-    const march_rsrc outf = march_make_rsrc(with_f ? (const void *)((const char *)canvas_f32 + (long long)it.y0 * fstride) : (const void *)canvas,
-                                            with_f ? 0xFFFFFFFFu : 0u);
-    const unsigned vout = (unsigned)M.x_px * CN;
-    const bool finisher = wv < 2;                                   // wave 0: canvas row 0, wave 1: canvas row 1
-    float *xw = &xch[tl * 2 * X::ROW + plane * 256 + lane * 2];
-    const float *xr = &xch[(wv & 1) * X::ROW + lane * 2];
-    const unsigned o_fin = (wv & 1) ? (unsigned)cstride : 0u, f_fin = (wv & 1) ? fstride : 0u;
-    const bool e0 = !(U.r0 & 1);
-#define MARCHP_GO(EV, FLV) marchp_loop<NT, EV, FLV>(U, V, S, arena, nstep, M.addr_l, M.addr_r, M.useful, finisher, plane, sel1, sel2, xw, xr, out, vout, o_fin, (unsigned)cstride, outf, with_f, f_fin, fstride)
-#define MARCHP_GO_FL(FLV) do { if (e0) MARCHP_GO(true, FLV); else MARCHP_GO(false, FLV); } while (0)
-    switch (U.flags & (MT_XO | MT_YO | MT_P1)) {
-    case 0: MARCHP_GO_FL(0); break;
-    case 1: MARCHP_GO_FL(1); break;
-    case 2: MARCHP_GO_FL(2); break;
-    case 3: MARCHP_GO_FL(3); break;
-    case 4: MARCHP_GO_FL(4); break;
-    case 5: MARCHP_GO_FL(5); break;
-    case 6: MARCHP_GO_FL(6); break;
-    default: MARCHP_GO_FL(7); break;
-    }
-#undef MARCHP_GO_FL
-#undef MARCHP_GO
 }

@@ -52,9 +52,12 @@ GRIDS = [
 ]
 
 
-# the marched gather forced (its remainder as rectangles of cells: k_final_rect) / the same with the remainder through the masked
-# blocks + edge blocks / with uniform item segments cut for six rounds / the default of a small canvas: the block kernel alone
-MARCH_FORMS = [("2", {}), ("2", {"SR_RECT": "0"}), ("2", {"SR_MARCH_TAIL": "0", "SR_MARCH_ROUNDS": "6,6,6", "SR_RECT_CELLS": "64"}), ("1", {})]
+# the marched gather forced (its remainder as rectangles of cells: k_final_rect) / the same with uniform item segments cut for
+# six rounds / the default of a small canvas: the block kernel alone.  (The ids are those the forms had beside a fourth one,
+# env1, whose path was removed.)
+MARCH_FORMS = [pytest.param("2", {}, id="2-env0"),
+               pytest.param("2", {"SR_MARCH_TAIL": "0", "SR_MARCH_ROUNDS": "6,6,6", "SR_RECT_CELLS": "64"}, id="2-env2"),
+               pytest.param("1", {}, id="1-env3")]
 
 
 @pytest.mark.parametrize("march,env", MARCH_FORMS)
