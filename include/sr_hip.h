@@ -330,6 +330,36 @@ SR_API int sr_tile_ssim_sums_u8(sr_ctx *ctx, const uint8_t *d_canvas, int64_t ca
                                 int cn, const sr_tile_rect *h_rects, void *const *h_d_tiles, const int64_t *h_strides, int n,
                                 int gray_shift, uint64_t *h_sums);
 
+/* ---- commercial / no-reference metrics (quality_assessment_module.py:611-1193) ---------------------------------------
+ * sr_commercial_u8: one u8 image in HBM (cn 1 = gray, 3 = RGB, 4 = RGBA with alpha ignored), gray = the RGB2GRAY rule of
+ * gray_shift.  Rectangle 0 is the whole image with the metrics of `flags`; rectangles 1..n_roi are h_rois[i] (inside the
+ * image, non-empty) with the metrics of h_roi_flags[i] (only LAPG, TEX, LAB, SKIN, RGB), every stencil taken with
+ * reflect-101 at the rectangle's own border.  Flag bits and what lands in h_ints[r * 40 + k] / h_flts[r * 8 + k]:
+ *   1 LAPG     k 0..3   exact sum l, l^2 (cv2.Laplacian ksize 1), sum g, g^2
+ *   2 NOISE    k 4, 5   exact sum n, n^2, n = 16 (g - GaussianBlur3x3(g)) (an integer)
+ *   4 SOBEL    k 6      exact sum gx^2 + gy^2 (3x3 Sobel, reflect-101);   flt 3: fp64 sum sqrt(gx^2 + gy^2)
+ *   8 MSCN     flt 0..2 fp64 sums of m, m^2, |m| with m the fp32 MSCN coefficient (7x7 Gaussian sigma 7/6, fixed order)
+ *  16 TEX      flt 4    fp64 sum of the fp32 5x5 box local variance
+ *  32 LAB      k 7..12  exact sums L, L^2, a, a^2, b, b^2 of cv2's 8-bit RGB2Lab (cn >= 3)
+ *  64 SKIN     k 13     count of 133 <= Cr <= 173 and 77 <= Cb <= 127 (8-bit RGB2YCrCb; cn >= 3); LAB sums as well
+ * 128 RGB      k 14..16 exact sums R, G, B (cn >= 3)
+ * 256 BLOCKS   (rect 0) k 17 sum v, k 18 / 19 low / high 32 bits of sum v^2, v = 64 sum x^2 - (sum x)^2 over the 8x8 blocks
+ *              of range(0, h - 8, 8) x range(0, w - 8, 8); k 38 the block count
+ * 512 REGIONS  (rect 0) k 20..35 the 16 region sums (h // 4 x w // 4 regions, row-major; zeros when h or w < 4)
+ * 1024 CANNY   (rect 0) k 36 cv2.Canny(gray, 50, 150) edge pixel count, k 37 hysteresis sweeps taken
+ * 2048 HF      (rect 0) flt 5 / 6: fp64 sum of |F| outside the radius min(h, w) // 4 / over all of the 2-D DFT of the gray
+ *              image (centred frequencies; fp32 FFT and magnitude).  SR_ERR_UNSUPPORTED for a side above sr_fft_max_len().
+ * Every fp64 sum is per-block partials added in a fixed order: equal inputs give equal bits.  The caller finishes the
+ * metrics (means, variances, clips) in fp64. */
+SR_API int sr_commercial_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, int cn, int gray_shift,
+                            int flags, const sr_tile_rect *h_rois, const int *h_roi_flags, int n_roi, int64_t *h_ints,
+                            double *h_flts);
+/* Longest line sr_fft_c2c (and the DFT of sr_commercial_u8) transforms. */
+SR_API int sr_fft_max_len(void);
+/* Forward DFT (sign -1, unscaled) of `lines` rows of n interleaved fp32 complex values, d_in -> d_out (may alias): the
+ * mixed-radix / Bluestein FFT behind the high-frequency ratio.  Synchronous. */
+SR_API int sr_fft_c2c(sr_ctx *ctx, const void *d_in, void *d_out, int64_t lines, int n);
+
 /* ---- quality metrics (quality_assessment_module.py:277-417) ---------------------------- */
 /* Sum of squared differences over h rows of rowlen u8 elements -> *h_sse (exact integer).
  * PSNR = 10 log10(data_range^2 / (sse / (h*rowlen))) is finished on the host (and partial sums

@@ -53,6 +53,9 @@ class AssessSums(C.Structure):
 
 
 ASSESS_SSE, ASSESS_UNIFORM7, ASSESS_GAUSS11, ASSESS_SIMPLE, ASSESS_ALL = 1, 2, 4, 8, 15
+# metric bits of sr_commercial_u8 (include/sr_hip.h)
+(CM_LAPG, CM_NOISE, CM_SOBEL, CM_MSCN, CM_TEX, CM_LAB, CM_SKIN, CM_RGB, CM_BLOCKS, CM_REGIONS, CM_CANNY,
+ CM_HF) = (1 << i for i in range(12))
 
 
 class ProfRecord(C.Structure):
@@ -130,6 +133,10 @@ SIGNATURES = {
     "sr_gradient_stats_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(C.c_uint64), C.POINTER(_dbl)]),
     "sr_tile_ssim_sums_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(TileRect), C.POINTER(_vp), C.POINTER(_i64), _i, _i,
                                   C.POINTER(C.c_uint64)]),
+    "sr_commercial_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, C.POINTER(TileRect), _pi, _i, C.POINTER(_i64),
+                              C.POINTER(_dbl)]),
+    "sr_fft_max_len": (_i, []),
+    "sr_fft_c2c": (_i, [_vp, _vp, _vp, _i64, _i]),
     "sr_sse_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i64, C.POINTER(C.c_uint64)]),
     "sr_sse_u8_async": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i64, _vp]),
     "sr_psnr_from_sse": (_dbl, [C.c_uint64, C.c_uint64, _dbl]),
@@ -641,6 +648,24 @@ class Context:
         check(self.lib.sr_gradient_stats_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w), int(cn),
                                             C.byref(sq), C.byref(mag)))
         return sq.value, mag.value
+
+    def commercial_u8(self, d_img: int, stride: int, h: int, w: int, cn: int, flags: int, rois=(), roi_flags=(),
+                      gray_shift: int = 15) -> Tuple[np.ndarray, np.ndarray]:
+        """sr_commercial_u8 -> (ints (1 + n, 40) int64, flts (1 + n, 8) float64); row 0 is the whole image, row 1 + i the
+        ROI rois[i] = (x, y, w, h) with the metrics of roi_flags[i] (see include/sr_hip.h for the slots)."""
+        n = len(rois)
+        ints = np.zeros((1 + n, 40), dtype=np.int64)
+        flts = np.zeros((1 + n, 8), dtype=np.float64)
+        rects = (TileRect * max(n, 1))(*[TileRect(int(x), int(y), int(rw), int(rh)) for (x, y, rw, rh) in rois])
+        rf = (C.c_int * max(n, 1))(*[int(f) for f in roi_flags])
+        check(self.lib.sr_commercial_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w), int(cn), int(gray_shift),
+                                        int(flags), rects, rf, n, ints.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        flts.ctypes.data_as(C.POINTER(C.c_double))))
+        return ints, flts
+
+    def fft_c2c(self, d_in: int, d_out: int, lines: int, n: int):
+        """sr_fft_c2c: forward DFT of `lines` rows of n complex64 values in HBM (synchronous)."""
+        check(self.lib.sr_fft_c2c(self.handle, C.c_void_p(d_in), C.c_void_p(d_out), int(lines), int(n)))
 
     def tile_ssim_sums_u8(self, d_canvas: int, canvas_stride: int, h: int, w: int, cn: int, rects_xywh,
                           d_tiles: Sequence[int], strides: Sequence[int], gray_shift: int = 15) -> np.ndarray:

@@ -53,6 +53,8 @@ struct sr_ctx {
     CachedTable cubic_tab;                              // cubic tables of sr_resize_cubic_u8
     void *gray_planes = nullptr;                        // resized gray planes + SSE partials of the resized assessment
     size_t gray_planes_bytes = 0;
+    void *cm_ws = nullptr;                              // commercial / no-reference metrics: planes, FFT buffers, partials
+    size_t cm_ws_bytes = 0;
 };
 
 // Enqueue a small host->device table upload whose source stays alive until the next sync.

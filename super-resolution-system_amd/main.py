@@ -147,6 +147,15 @@ class SuperResolutionPipeline:
             with open(output_path.rsplit('.', 1)[0] + '_qa_report.json', 'w', encoding='utf-8') as f:
                 json.dump(report, f, indent=2, ensure_ascii=False, default=str)
 
+    @staticmethod
+    def _commercial(evaluate) -> Dict[str, Any]:
+        """Stage 4's commercial section (main.py:369-386 of the reference); a canvas with a side beyond the hand-written
+        DFT (sr_fft_max_len) gets a labelled stub instead of failing the image."""
+        try:
+            return evaluate()
+        except NotImplementedError as exc:
+            return {"available": False, "note": str(exc)}
+
     async def _process_device(self, input_path: str, output_path: str, roi_regions, start: float) -> PipelineResult:
         """The five stages with the data resident in HBM (main.py:293-410 order): the decoded source goes up once
         (the only large H2D), tiles are cut and padded, the bicubic SR stand-in runs per tile, the tiles are fused and
@@ -196,7 +205,8 @@ class SuperResolutionPipeline:
                 qa = self.quality_module.evaluate_full_reference_device(ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3),
                                                                         scale_factor=W / iw)
                 report = {'full_reference': qa,
-                          'commercial': self.quality_module.evaluate_commercial(None, roi_regions or []),
+                          'commercial': self._commercial(lambda: self.quality_module.evaluate_commercial_device(
+                              canvas.ptr, (H, W, 3), roi_regions or [])),
                           'timestamp': datetime.now().isoformat()}
                 score = qa.get('overall_score', 0)
             lap("assess")
@@ -285,7 +295,8 @@ class SuperResolutionPipeline:
                     qa = self.quality_module.evaluate_full_reference_device(ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3),
                                                                             scale_factor=W / iw)
                     report = {'full_reference': qa,
-                              'commercial': self.quality_module.evaluate_commercial(None, roi_regions or []),
+                              'commercial': self._commercial(lambda: self.quality_module.evaluate_commercial_device(
+                                  canvas.data_ptr(), (H, W, 3), roi_regions or [])),
                               'timestamp': datetime.now().isoformat()}
                     score = qa.get('overall_score', 0)
                 fused = qctx.download(canvas.data_ptr(), (H, W, 3), np.uint8)
@@ -357,7 +368,7 @@ class SuperResolutionPipeline:
                 qa = self.quality_module.evaluate_full_reference(original=original, upscaled=fused,
                                                                  scale_factor=fused.shape[1] / original.shape[1])
                 report = {'full_reference': qa,
-                          'commercial': self.quality_module.evaluate_commercial(fused, roi_regions or []),
+                          'commercial': self._commercial(lambda: self.quality_module.evaluate_commercial(fused, roi_regions or [])),
                           'timestamp': datetime.now().isoformat()}
                 score = qa.get('overall_score', 0)
             # Stage 5: output

@@ -17,9 +17,16 @@ reference's constructor downloads pretrained weights by model name; this one nev
 from ``lpips_weights={'vgg': <.npz path or dict>, 'alex': ...}`` (or SR_LPIPS_WEIGHTS_VGG / SR_LPIPS_WEIGHTS_ALEX),
 a flat .npz of ``lpips.LPIPS(net).state_dict()`` arrays read with allow_pickle=False.  Without weights
 ``lpips_model_vgg`` stays None exactly like the reference when its import fails: ``evaluate_full_reference`` omits
-the LPIPS keys and ``calculate_lpips`` raises RuntimeError.  NIQE / BRISQUE / commercial heuristics are outside
-the tile -> blend -> assess path; ``evaluate_commercial`` returns an empty, labelled result so
-main.process keeps its report structure.
+the LPIPS keys and ``calculate_lpips`` raises RuntimeError.
+
+No-reference and commercial metrics (quality_assessment_module.py:611-1193): ``evaluate_commercial`` (and
+``evaluate_commercial_device`` for a canvas already in HBM) and ``evaluate_no_reference`` run every metric -- Laplacian
+sharpness, contrast, 8-bit Lab colour statistics, YCrCb skin ratio, 5x5 texture, 3x3 noise residual, 8x8 block artifacts,
+brightness regions, Canny edge density, the DFT high-frequency ratio and the MSCN / Sobel NIQE and BRISQUE stand-ins -- in
+one sr_commercial_u8 call (csrc/sr_commercial.hip), all ROIs included; the host only finishes the scalar formulas and
+keeps the reference's key order.  The pyiqa NIQE / BRISQUE models stay unavailable (``_niqe_available`` is False).
+u8 HxW, HxWx3 and HxWx4 (alpha ignored) images only; an image side above the FFT's longest line (32768) raises
+NotImplementedError before any device work.
 """
 from __future__ import annotations
 
@@ -468,11 +475,398 @@ class QualityAssessmentModule:
             scores.append(max(0, (1 - metrics['lpips_vgg']) * 100))
         return float(np.mean(scores)) if scores else 0.0
 
-    # -- outside the path -------------------------------------------------------------------------------------
-    def evaluate_commercial(self, image: Any, roi_regions: Optional[List[Dict]] = None) -> Dict[str, Any]:
-        return {"available": False,
-                "note": "commercial / no-reference heuristics are outside the MI355X tile->blend->assess path",
-                "roi_count": len(roi_regions or [])}
+    # -- no-reference and commercial metrics (quality_assessment_module.py:611-1193) -----------------------------------
+    # Every metric runs in ONE sr_commercial_u8 call (csrc/sr_commercial.hip) that returns exact integer sums and fixed-order
+    # fp64 sums; the scalar formulas below finish them.  The private helpers keep the reference's names and each take one
+    # (host) image, like the reference's.
 
+    def _commercial_image(self, image: Any, what: str) -> np.ndarray:
+        img = self._require_u8(np.asarray(self._preprocess_image(image)), what)
+        if img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (3, 4)) or img.shape[0] < 1 or img.shape[1] < 1:
+            raise ValueError(f"{what}: expected a u8 HxW, HxWx3 or HxWx4 image, got shape {img.shape}")
+        return img
+
+    @staticmethod
+    def _check_dev_shape(shape, what: str) -> Tuple[int, ...]:
+        shape = tuple(int(v) for v in shape)
+        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] not in (3, 4)) or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"{what}: expected a u8 HxW, HxWx3 or HxWx4 image, got shape {shape}")
+        return shape
+
+    def _cm_sums(self, d: _DevImage, flags: int, rois=(), roi_flags=()):
+        if flags & _native.CM_HF and max(d.h, d.w) > _FFT_MAX_LEN:
+            raise NotImplementedError(f"high-frequency ratio: image side {max(d.h, d.w)} is above the longest DFT line "
+                                      f"the HIP FFT supports ({_FFT_MAX_LEN})")
+        return d.ctx.commercial_u8(d.ptr, d.stride, d.h, d.w, d.cn, flags, rois, roi_flags, gray_shift=self.gray_shift)
+
+    def _cm_host(self, image: Any, flags: int, what: str):
+        img = self._commercial_image(image, what)
+        ctx = self._ctx()
+        if flags & _native.CM_HF and max(img.shape[:2]) > _FFT_MAX_LEN:
+            raise NotImplementedError(f"{what}: image side {max(img.shape[:2])} is above the longest DFT line the HIP FFT "
+                                      f"supports ({_FFT_MAX_LEN})")
+        d = _DevImage(ctx, img)
+        try:
+            ints, flts = self._cm_sums(d, flags)
+        finally:
+            d.free()
+        return img, ints[0], flts[0]
+
+    # scalar finishing ----------------------------------------------------------------------------------------------
+    @staticmethod
+    def _var(s1: int, s2: int, n: int) -> float:
+        """Population variance from exact integer sums, correctly rounded."""
+        s1, s2, n = int(s1), int(s2), int(n)
+        return (n * s2 - s1 * s1) / (n * n)
+
+    @staticmethod
+    def _color_variance_of(r, n: int) -> float:
+        return float(QualityAssessmentModule._var(r[7], r[8], n))
+
+    @staticmethod
+    def _colorfulness_of(r, n: int) -> float:
+        v = QualityAssessmentModule._var
+        return float(np.sqrt(np.sqrt(v(r[9], r[10], n)) ** 2 + np.sqrt(v(r[11], r[12], n)) ** 2))
+
+    @staticmethod
+    def _noise_of(r, n: int) -> float:
+        return float(np.sqrt(max(QualityAssessmentModule._var(r[4], r[5], n), 0.0)) / 16.0)
+
+    @staticmethod
+    def _artifact_of(r) -> float:
+        nb = int(r[38])
+        if nb <= 1:
+            return 100.0
+        s, q = int(r[17]), int(r[18]) + (int(r[19]) << 32)
+        vv = (nb * q - s * s) / (nb * nb * 4096 * 4096)              # np.var of the block variances
+        return float(max(0, 100 - vv / 100))
+
+    @staticmethod
+    def _uniformity_of(r, h: int, w: int) -> float:
+        rh, rw = h // 4, w // 4
+        if rh == 0 or rw == 0:
+            return 0.0                                                # empty regions: NaN, and max(0, nan) is 0
+        means = np.array([int(v) / (rh * rw) for v in r[20:36]], dtype=np.float64)
+        return float(max(0, 100 - np.std(means)))
+
+    @staticmethod
+    def _oversharpen_of(r, n: int) -> float:
+        return float(max(0, 100 - (int(r[36]) / n) * 500))
+
+    @staticmethod
+    def _hf_of(f) -> float:
+        return float(f[5] / (f[6] + 1e-10))
+
+    @staticmethod
+    def _mscn_stats(f, n: int):
+        mean = f[0] / n
+        std = float(np.sqrt(max(f[1] / n - mean * mean, 0.0)))
+        return float(mean), std, float(f[2] / n)
+
+    def _niqe_of(self, f, n: int) -> float:
+        mean, std, _ = self._mscn_stats(f, n)
+        return float(np.clip((std + abs(mean)) * 2.0 + 3.0, 1.0, 15.0))
+
+    def _brisque_of(self, r, f, n: int) -> float:
+        mean, std, mabs = self._mscn_stats(f, n)
+        gmean = f[3] / n
+        gstd = float(np.sqrt(max(int(r[6]) / n - gmean * gmean, 0.0)))
+        return float(np.clip(np.mean([mean, std, mabs, gmean, gstd]) * 10 + 20, 0, 100))
+
+    @staticmethod
+    def _face_of(r, n: int) -> float:
+        ratio = int(r[13]) / n
+        return float(np.clip(100 - abs(ratio - 0.3) * 100, 0, 100))
+
+    @staticmethod
+    def _skin_tone_of(r, n: int) -> float:
+        lm, am, bm = int(r[7]) / n, int(r[9]) / n, int(r[11]) / n
+        d = np.sqrt((lm - 70) ** 2 + (am - 15) ** 2 + (bm - 20) ** 2)
+        return float(max(0, 100 - d))
+
+    @staticmethod
+    def _delta_e_of(r, n: int, reference_color) -> float:
+        mean_color = np.array([int(r[14]) / n, int(r[15]) / n, int(r[16]) / n])
+        ref_lab = _lab8(np.uint8([[reference_color]])[0, 0])
+        img_lab = _lab8(mean_color.astype(np.uint8))
+        return float(np.sqrt(np.sum((ref_lab.astype(np.float32) - img_lab.astype(np.float32)) ** 2)))
+
+    # reference-named helpers (each one device call on a host image) --------------------------------------------------
+    def _calculate_sharpness(self, image: np.ndarray) -> float:
+        img, r, _ = self._cm_host(image, _native.CM_LAPG, "_calculate_sharpness")
+        return float(self._var(r[0], r[1], img.shape[0] * img.shape[1]))
+
+    def _calculate_contrast(self, image: np.ndarray) -> float:
+        img, r, _ = self._cm_host(image, _native.CM_LAPG, "_calculate_contrast")
+        return float(np.sqrt(self._var(r[2], r[3], img.shape[0] * img.shape[1])))
+
+    def _calculate_colorfulness(self, image: np.ndarray) -> float:
+        img = self._commercial_image(image, "_calculate_colorfulness")
+        if img.ndim != 3:
+            return 0.0
+        _, r, _ = self._cm_host(img, _native.CM_LAB, "_calculate_colorfulness")
+        return self._colorfulness_of(r, img.shape[0] * img.shape[1])
+
+    def _calculate_color_variance(self, image: np.ndarray) -> float:
+        img = self._commercial_image(image, "_calculate_color_variance")
+        if img.ndim != 3:
+            return 0.0
+        _, r, _ = self._cm_host(img, _native.CM_LAB, "_calculate_color_variance")
+        return self._color_variance_of(r, img.shape[0] * img.shape[1])
+
+    def _calculate_hf_ratio(self, image: np.ndarray) -> float:
+        _, _, f = self._cm_host(image, _native.CM_HF, "_calculate_hf_ratio")
+        return self._hf_of(f)
+
+    def _detect_oversharpen(self, image: np.ndarray) -> float:
+        img, r, _ = self._cm_host(image, _native.CM_CANNY, "_detect_oversharpen")
+        return self._oversharpen_of(r, img.shape[0] * img.shape[1])
+
+    def _detect_artifacts(self, image: np.ndarray) -> float:
+        _, r, _ = self._cm_host(image, _native.CM_BLOCKS, "_detect_artifacts")
+        return self._artifact_of(r)
+
+    def _estimate_noise(self, image: np.ndarray) -> float:
+        img, r, _ = self._cm_host(image, _native.CM_NOISE, "_estimate_noise")
+        return self._noise_of(r, img.shape[0] * img.shape[1])
+
+    def _calculate_brightness_uniformity(self, image: np.ndarray) -> float:
+        img, r, _ = self._cm_host(image, _native.CM_REGIONS, "_calculate_brightness_uniformity")
+        return self._uniformity_of(r, img.shape[0], img.shape[1])
+
+    def _calculate_texture_score(self, image: np.ndarray) -> float:
+        img, _, f = self._cm_host(image, _native.CM_TEX, "_calculate_texture_score")
+        return float(f[4] / (img.shape[0] * img.shape[1]))
+
+    def _calculate_face_naturalness(self, image: np.ndarray) -> float:
+        img = self._commercial_image(image, "_calculate_face_naturalness")
+        if img.ndim != 3:
+            return 50.0
+        _, r, _ = self._cm_host(img, _native.CM_SKIN, "_calculate_face_naturalness")
+        return self._face_of(r, img.shape[0] * img.shape[1])
+
+    def _calculate_skin_tone_naturalness(self, image: np.ndarray) -> float:
+        img = self._commercial_image(image, "_calculate_skin_tone_naturalness")
+        if img.ndim != 3:
+            return 50.0
+        _, r, _ = self._cm_host(img, _native.CM_LAB, "_calculate_skin_tone_naturalness")
+        return self._skin_tone_of(r, img.shape[0] * img.shape[1])
+
+    def _calculate_delta_e(self, image: np.ndarray, reference_color: Tuple[int, int, int]) -> float:
+        img = self._commercial_image(image, "_calculate_delta_e")
+        if img.ndim != 3:
+            return 100.0
+        _, r, _ = self._cm_host(img, _native.CM_RGB, "_calculate_delta_e")
+        return self._delta_e_of(r, img.shape[0] * img.shape[1], reference_color)
+
+    def _calculate_niqe_simple(self, image: np.ndarray) -> float:
+        img, _, f = self._cm_host(image, _native.CM_MSCN, "_calculate_niqe_simple")
+        return self._niqe_of(f, img.shape[0] * img.shape[1])
+
+    def _calculate_brisque_simple(self, image: np.ndarray) -> float:
+        img, r, f = self._cm_host(image, _native.CM_MSCN | _native.CM_SOBEL, "_calculate_brisque_simple")
+        return self._brisque_of(r, f, img.shape[0] * img.shape[1])
+
+    def calculate_niqe(self, image: np.ndarray) -> float:
+        # the pyiqa model branch stays unavailable (_niqe_available is False): the simplified stand-in runs
+        return self._calculate_niqe_simple(self._preprocess_image(image))
+
+    def calculate_brisque(self, image: np.ndarray) -> float:
+        return self._calculate_brisque_simple(self._preprocess_image(image))
+
+    # levels and the composite score ------------------------------------------------------------------------------------
+    def _assess_niqe(self, v: float) -> str:
+        t = self.thresholds
+        if v <= t.NIQE_EXCELLENT:
+            return AssessmentLevel.EXCELLENT.value
+        if v <= t.NIQE_GOOD:
+            return AssessmentLevel.GOOD.value
+        if v <= t.NIQE_FAIR:
+            return AssessmentLevel.FAIR.value
+        return AssessmentLevel.POOR.value
+
+    def _assess_brisque(self, v: float) -> str:
+        t = self.thresholds
+        if v <= t.BRISQUE_EXCELLENT:
+            return AssessmentLevel.EXCELLENT.value
+        if v <= t.BRISQUE_GOOD:
+            return AssessmentLevel.GOOD.value
+        if v <= t.BRISQUE_FAIR:
+            return AssessmentLevel.FAIR.value
+        return AssessmentLevel.POOR.value
+
+    def _assess_delta_e(self, v: float) -> str:
+        t = self.thresholds
+        if v <= t.DELTA_E_EXCELLENT:
+            return AssessmentLevel.EXCELLENT.value
+        if v <= t.DELTA_E_GOOD:
+            return AssessmentLevel.GOOD.value
+        if v <= t.DELTA_E_FAIR:
+            return AssessmentLevel.FAIR.value
+        return AssessmentLevel.POOR.value
+
+    def _calculate_commercial_score(self, metrics: Dict[str, float]) -> float:
+        scores = []
+        if 'global_sharpness' in metrics:
+            scores.append(min(100, metrics['global_sharpness'] / 10))
+        if 'high_frequency_ratio' in metrics:
+            scores.append(min(100, metrics['high_frequency_ratio'] * 500))
+        if 'oversharpen_score' in metrics:
+            scores.append(metrics['oversharpen_score'])
+        if 'artifact_score' in metrics:
+            scores.append(metrics['artifact_score'])
+        return float(np.mean(scores)) if scores else 50.0
+
+    # public evaluations ----------------------------------------------------------------------------------------------
     def evaluate_no_reference(self, image: Any) -> Dict[str, Any]:
-        raise NotImplementedError("NIQE / BRISQUE stand-ins are outside the MI355X tile->blend->assess path")
+        """quality_assessment_module.py:749-780: NIQE / BRISQUE stand-ins, sharpness, contrast, colorfulness from one
+        device pass."""
+        img = self._commercial_image(image, "evaluate_no_reference")
+        flags = _native.CM_LAPG | _native.CM_MSCN | _native.CM_SOBEL | (_native.CM_LAB if img.ndim == 3 else 0)
+        _, r, f = self._cm_host(img, flags, "evaluate_no_reference")
+        n = img.shape[0] * img.shape[1]
+        m: Dict[str, Any] = {}
+        m['niqe'] = self._niqe_of(f, n)
+        m['niqe_level'] = self._assess_niqe(m['niqe'])
+        m['brisque'] = self._brisque_of(r, f, n)
+        m['brisque_level'] = self._assess_brisque(m['brisque'])
+        m['sharpness'] = float(self._var(r[0], r[1], n))
+        m['contrast'] = float(np.sqrt(self._var(r[2], r[3], n)))
+        m['colorfulness'] = self._colorfulness_of(r, n) if img.ndim == 3 else 0.0
+        return m
+
+    def evaluate_commercial(self, image: Any, roi_regions: Optional[List[Dict]] = None) -> Dict[str, Any]:
+        """quality_assessment_module.py:873-1193 with the reference's key order; one upload, one device pass."""
+        img = self._commercial_image(image, "evaluate_commercial")
+        plan = self._roi_plan(img.shape, roi_regions)
+        if max(img.shape[:2]) > _FFT_MAX_LEN:
+            raise NotImplementedError(f"evaluate_commercial: image side {max(img.shape[:2])} is above the longest DFT line "
+                                      f"the HIP FFT supports ({_FFT_MAX_LEN})")
+        ctx = self._ctx()
+        d = _DevImage(ctx, img)
+        try:
+            return self._evaluate_commercial_dev(d, plan)
+        finally:
+            d.free()
+
+    def evaluate_commercial_device(self, d_image: int, shape, roi_regions: Optional[List[Dict]] = None) -> Dict[str, Any]:
+        """evaluate_commercial on a dense u8 image already in HBM (device address + shape): nothing is uploaded, a few
+        hundred bytes of sums come back."""
+        shape = self._check_dev_shape(shape, "evaluate_commercial")
+        plan = self._roi_plan(shape, roi_regions)
+        if max(shape[:2]) > _FFT_MAX_LEN:
+            raise NotImplementedError(f"evaluate_commercial: image side {max(shape[:2])} is above the longest DFT line the "
+                                      f"HIP FFT supports ({_FFT_MAX_LEN})")
+        return self._evaluate_commercial_dev(_DevImage(self._ctx(), shape=shape, ptr=d_image), plan)
+
+    @staticmethod
+    def _roi_plan(shape, roi_regions) -> List[Tuple[int, str, Tuple[int, int, int, int], Any]]:
+        """The reference's ROI rules (:905-925, :1010-1030): (index, type, clipped bbox, reference_color) of every ROI that
+        keeps a non-empty area.  Raises like the reference would (before any device work) on a malformed bbox."""
+        H, W = int(shape[0]), int(shape[1])
+        plan = []
+        if not roi_regions:
+            return plan
+        for i, roi in enumerate(roi_regions):
+            rtype = roi.get('type', f'roi_{i}')
+            bbox = roi.get('bbox', [0, 0, W, H])
+            x, y, w, h = bbox
+            for v in (x, y, w, h):
+                if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                    raise TypeError(f"roi {i}: bbox values must be integers, got {bbox!r}")
+            x, y = max(0, int(x)), max(0, int(y))
+            w, h = min(int(w), W - x), min(int(h), H - y)
+            if w > 0 and h > 0:
+                plan.append((i, rtype, (x, y, w, h), roi.get('reference_color', None)))
+        return plan
+
+    def _evaluate_commercial_dev(self, d: _DevImage, plan) -> Dict[str, Any]:
+        colour = d.cn >= 3
+        rois, rflags, slot = [], [], {}
+        for i, rtype, box, ref in plan:
+            f = 0
+            if rtype == 'text':
+                f = _native.CM_LAPG
+            elif rtype == 'product':
+                f = _native.CM_TEX
+            elif rtype == 'face' and colour:
+                f = _native.CM_SKIN
+            elif rtype == 'brand' and ref is not None and colour:
+                np.uint8([[ref]])                                     # a bad reference colour raises before the device call
+                f = _native.CM_RGB
+            if f:
+                slot[i] = 1 + len(rois)
+                rois.append(box)
+                rflags.append(f)
+        flags = (_native.CM_LAPG | _native.CM_NOISE | _native.CM_BLOCKS | _native.CM_REGIONS | _native.CM_CANNY |
+                 _native.CM_HF | (_native.CM_LAB if colour else 0))
+        ints, flts = self._cm_sums(d, flags, rois, rflags)
+        g, gf = ints[0], flts[0]
+        h, w = d.h, d.w
+        n = h * w
+        m: Dict[str, Any] = {}
+        # 1. detail fidelity
+        m['global_sharpness'] = float(self._var(g[0], g[1], n))
+        m['high_frequency_ratio'] = self._hf_of(gf)
+        for i, rtype, (x, y, rw, rh), _ in plan:
+            nr = rw * rh
+            if rtype == 'text':
+                r = ints[slot[i]]
+                m[f'text_sharpness_{i}'] = float(self._var(r[0], r[1], nr))
+                m[f'text_contrast_{i}'] = float(np.sqrt(self._var(r[2], r[3], nr)))
+            elif rtype == 'product':
+                m[f'product_texture_{i}'] = float(flts[slot[i]][4] / nr)
+            elif rtype == 'face':
+                m[f'face_naturalness_{i}'] = self._face_of(ints[slot[i]], nr) if colour else 50.0
+        # 2. colour accuracy
+        m['color_variance'] = self._color_variance_of(g, n) if colour else 0.0
+        for i, rtype, (x, y, rw, rh), ref in plan:
+            nr = rw * rh
+            if rtype == 'brand' and ref is not None:
+                de = self._delta_e_of(ints[slot[i]], nr, ref) if colour else 100.0
+                m[f'brand_color_delta_e_{i}'] = de
+                m[f'brand_color_accuracy_{i}'] = self._assess_delta_e(de)
+            elif rtype == 'face':
+                m[f'skin_tone_naturalness_{i}'] = self._skin_tone_of(ints[slot[i]], nr) if colour else 50.0
+        # 3. visual comfort
+        m['oversharpen_score'] = self._oversharpen_of(g, n)
+        m['artifact_score'] = self._artifact_of(g)
+        m['noise_level'] = self._noise_of(g, n)
+        m['brightness_uniformity'] = self._uniformity_of(g, h, w)
+        # 4. composite
+        m['commercial_score'] = self._calculate_commercial_score(m)
+        return m
+
+
+_FFT_MAX_LEN = 32768          # sr_fft_max_len(): longest DFT line of the hand-written FFT (checked against the library)
+
+
+def _lab_tables_b() -> Tuple[np.ndarray, np.ndarray]:
+    """cv2's 8-bit RGB2Lab tables (OpenCV 4.x color_lab.cpp initLabTabs), the rule k_lab_tables builds on the device:
+    sRGB gamma x 255 x 2^3 and the cube-root table x 2^15 over 3072 steps of 1 / (255 x 2^3), computed in fp64 and
+    rounded half to even."""
+    x = np.arange(256, dtype=np.float64) / 255.0
+    gamma = np.rint(255.0 * 8.0 * np.where(x <= 0.04045, x / 12.92, ((x + 0.055) / 1.055) ** 2.4)).astype(np.int64)
+    t = np.arange(3072, dtype=np.float64) / (255.0 * 8.0)
+    cb = np.rint(32768.0 * np.where(t < 216.0 / 24389.0, t * (841.0 / 108.0) + 16.0 / 116.0, np.cbrt(t))).astype(np.int64)
+    return gamma, cb
+
+
+_LAB_COEFFS = np.array([[int(np.rint(4096.0 * c / wp)) for c in row] for row, wp in zip(
+    ((0.412453, 0.357580, 0.180423), (0.212671, 0.715160, 0.072169), (0.019334, 0.119193, 0.950227)),
+    (0.950456, 1.0, 1.088754))], dtype=np.int64)
+
+
+def _lab8(rgb) -> np.ndarray:
+    """cv2.cvtColor(np.uint8([[rgb]]), COLOR_RGB2LAB)[0, 0] for one colour (alpha ignored) -> uint8[3]."""
+    gamma, cb = _LAB_TABLES
+    v = np.asarray(rgb, dtype=np.int64).reshape(-1)[:3]
+    lin = gamma[v]
+    f = cb[(_LAB_COEFFS @ lin + (1 << 11)) >> 12]
+    L = (296 * f[1] - ((16 * 255 * (1 << 15) + 50) // 100) + (1 << 14)) >> 15
+    a = (500 * (f[0] - f[1]) + 128 * (1 << 15) + (1 << 14)) >> 15
+    b = (200 * (f[1] - f[2]) + 128 * (1 << 15) + (1 << 14)) >> 15
+    return np.clip(np.array([L, a, b]), 0, 255).astype(np.uint8)
+
+
+_LAB_TABLES = _lab_tables_b()
