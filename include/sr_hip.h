@@ -360,6 +360,33 @@ SR_API int sr_fft_max_len(void);
  * mixed-radix / Bluestein FFT behind the high-frequency ratio.  Synchronous. */
 SR_API int sr_fft_c2c(sr_ctx *ctx, const void *d_in, void *d_out, int64_t lines, int n);
 
+/* ---- content analysis (tiling_module.py:174-370, :752-757) ------------------------------------------------------------
+ * The u8 image (cn 1 = gray, 3 = RGB, 4 = RGBA with alpha ignored) is in HBM; gray = cv2.COLOR_BGR2GRAY applied to the RGB
+ * data as the reference does (channel 0 takes the blue weight, 15-bit rule; cn 1: the value itself).  Every output plane is
+ * contiguous (row length w) and stays in HBM.
+ *
+ * sr_saliency_u8: ContentAnalyzer.compute_saliency_map's spectral-residual branch (:261-289) -> d_sal (h * w bytes).
+ * F = fft2(gray), L = log(|F| + 1e-8), the 5x5 mean of L taken on the fftshift-ed array (shift n / 2, reflect-101 at that
+ * array's own border), R = L - mean, the inverse 2-D DFT of exp(R) F / |F| (unit phase where F = 0) with its 1 / (h w)
+ * scale, its magnitude, the 5x5 Gaussian of sigma 0 ([1 4 6 4 1] / 16, reflect-101), then
+ * u8((s - min) / (max - min + 1e-8) * 255) truncated.  fp32 throughout (the FFT of sr_fft_c2c); min and max are taken in a
+ * fixed order: equal inputs give equal bytes.  SR_ERR_UNSUPPORTED for a side above sr_fft_max_len().  Asynchronous. */
+SR_API int sr_saliency_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, int cn, uint8_t *d_sal);
+/* compute_local_entropy (:291-321) -> d_out (h * w floats): per window x window cell of the gray image (edge cells
+ * partial; 1 <= window <= 32768) the 256-bin histogram with exact counts, p = count / pixels and
+ * H = -sum p log2(p + 1e-10) in fp32 (fixed summation order), written to every pixel of the cell.  Asynchronous. */
+SR_API int sr_local_entropy_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, int cn, int window,
+                               float *d_out);
+/* create_forbidden_zone_map's map (:344-370) -> d_map (h * w bytes, 0 or 1): d_sal[y, x] > threshold (d_sal may be NULL:
+ * zeros) OR-ed with the n filled rectangles [y:y+h, x:x+w] of h_rects, clipped to the image (w, h >= 0).  Asynchronous. */
+SR_API int sr_forbidden_map(sr_ctx *ctx, const uint8_t *d_sal, int h, int w, int threshold, const sr_tile_rect *h_rects,
+                            int n, uint8_t *d_map);
+/* Per-tile forbidden counts (:753-757): h_counts[i] = the exact number of non-zero bytes of the u8 plane d_map (h x w, row
+ * stride in bytes) inside h_rects[i] clipped to the plane (0 for an empty clip).  One launch for all rectangles (per 32768);
+ * synchronous. */
+SR_API int sr_rect_counts_u8(sr_ctx *ctx, const uint8_t *d_map, int64_t stride, int h, int w, const sr_tile_rect *h_rects,
+                             int n, uint64_t *h_counts);
+
 /* ---- quality metrics (quality_assessment_module.py:277-417) ---------------------------- */
 /* Sum of squared differences over h rows of rowlen u8 elements -> *h_sse (exact integer).
  * PSNR = 10 log10(data_range^2 / (sse / (h*rowlen))) is finished on the host (and partial sums

@@ -137,6 +137,10 @@ SIGNATURES = {
                               C.POINTER(_dbl)]),
     "sr_fft_max_len": (_i, []),
     "sr_fft_c2c": (_i, [_vp, _vp, _vp, _i64, _i]),
+    "sr_saliency_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
+    "sr_local_entropy_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sr_forbidden_map": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(TileRect), _i, _vp]),
+    "sr_rect_counts_u8": (_i, [_vp, _vp, _i64, _i, _i, C.POINTER(TileRect), _i, C.POINTER(C.c_uint64)]),
     "sr_sse_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i64, C.POINTER(C.c_uint64)]),
     "sr_sse_u8_async": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i64, _vp]),
     "sr_psnr_from_sse": (_dbl, [C.c_uint64, C.c_uint64, _dbl]),
@@ -666,6 +670,32 @@ class Context:
     def fft_c2c(self, d_in: int, d_out: int, lines: int, n: int):
         """sr_fft_c2c: forward DFT of `lines` rows of n complex64 values in HBM (synchronous)."""
         check(self.lib.sr_fft_c2c(self.handle, C.c_void_p(d_in), C.c_void_p(d_out), int(lines), int(n)))
+
+    # content analysis (sr_content.hip) ------------------------------------------------------
+    def saliency_u8(self, d_img: int, stride: int, h: int, w: int, cn: int, d_sal: int):
+        """sr_saliency_u8: u8 image in HBM -> u8 spectral-residual saliency map (h * w bytes at d_sal).  Asynchronous."""
+        check(self.lib.sr_saliency_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w), int(cn), C.c_void_p(d_sal)))
+
+    def local_entropy_u8(self, d_img: int, stride: int, h: int, w: int, cn: int, window: int, d_out: int):
+        """sr_local_entropy_u8: per-cell entropy of the gray image -> h * w float32 at d_out.  Asynchronous."""
+        check(self.lib.sr_local_entropy_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w), int(cn), int(window),
+                                           C.c_void_p(d_out)))
+
+    def forbidden_map(self, d_sal: Optional[int], h: int, w: int, threshold: int, rects_xywh, d_map: int):
+        """sr_forbidden_map: d_map = (saliency > threshold) | filled rectangles (x, y, w, h), clipped.  d_sal None: rectangles
+        only.  Asynchronous."""
+        n = len(rects_xywh)
+        rects = (TileRect * max(n, 1))(*[TileRect(int(x), int(y), int(rw), int(rh)) for (x, y, rw, rh) in rects_xywh])
+        check(self.lib.sr_forbidden_map(self.handle, C.c_void_p(d_sal), int(h), int(w), int(threshold), rects, n,
+                                        C.c_void_p(d_map)))
+
+    def rect_counts_u8(self, d_map: int, stride: int, h: int, w: int, rects_xywh) -> List[int]:
+        """sr_rect_counts_u8 -> the exact count of non-zero bytes of the plane inside each rectangle (x, y, w, h)."""
+        n = len(rects_xywh)
+        out = (C.c_uint64 * max(n, 1))()
+        rects = (TileRect * max(n, 1))(*[TileRect(int(x), int(y), int(rw), int(rh)) for (x, y, rw, rh) in rects_xywh])
+        check(self.lib.sr_rect_counts_u8(self.handle, C.c_void_p(d_map), int(stride), int(h), int(w), rects, n, out))
+        return [int(out[i]) for i in range(n)]
 
     def tile_ssim_sums_u8(self, d_canvas: int, canvas_stride: int, h: int, w: int, cn: int, rects_xywh,
                           d_tiles: Sequence[int], strides: Sequence[int], gray_shift: int = 15) -> np.ndarray:

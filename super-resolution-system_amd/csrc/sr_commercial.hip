@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "sr_ctx.h"
+#include "sr_fft.h"
 
 namespace {
 
@@ -441,6 +442,9 @@ __global__ void k_twiddle(float2 *__restrict__ tw, int n)
 // One Stockham autosort pass of radix R over `lines` lines of length N (Ns: product of the radices already applied):
 // butterfly j (k = j mod Ns) reads in[j + r N/R], twiddles by W_{Ns R}^{r k}, takes the R-point DFT and writes
 // out[(j / Ns) Ns R + k + q Ns].  A block holds nb = max(1, 256 / R) butterflies in LDS; W_R comes from LDS too.
+// COMP: the R-term sums carry a Kahan compensation term (the saliency map's long direct-DFT passes; the metrics keep the
+// plain sums their recorded values were taken with).
+template <bool COMP>
 __global__ __launch_bounds__(CM_THREADS) void k_fft_pass(const float2 *__restrict__ in, float2 *__restrict__ out,
                                                          long long lines, int N, int R, int Ns, const float2 *__restrict__ tw)
 {
@@ -469,12 +473,21 @@ __global__ __launch_bounds__(CM_THREADS) void k_fft_pass(const float2 *__restric
         const int q = e / nb, b = e - q * nb;
         const long long g = g0 + b;
         if (g >= total) continue;
-        float2 acc = make_float2(0.0f, 0.0f);
+        float2 acc = make_float2(0.0f, 0.0f), lost = make_float2(0.0f, 0.0f);
         int idx = 0;
         for (int r = 0; r < R; ++r) {
             const float2 p = cmul(v[r * nb + b], wr[idx]);
-            acc.x = __fadd_rn(acc.x, p.x);
-            acc.y = __fadd_rn(acc.y, p.y);
+            if (COMP) {
+                const float yx = __fsub_rn(p.x, lost.x), yy = __fsub_rn(p.y, lost.y);
+                const float tx = __fadd_rn(acc.x, yx), ty = __fadd_rn(acc.y, yy);
+                lost.x = __fsub_rn(__fsub_rn(tx, acc.x), yx);
+                lost.y = __fsub_rn(__fsub_rn(ty, acc.y), yy);
+                acc.x = tx;
+                acc.y = ty;
+            } else {
+                acc.x = __fadd_rn(acc.x, p.x);
+                acc.y = __fadd_rn(acc.y, p.y);
+            }
             idx += q;
             if (idx >= R) idx -= R;
         }
@@ -652,13 +665,15 @@ unsigned grid1(long long n, int per = 256, long long cap = 1 << 16)
 }
 
 // Stockham passes over `lines` lines of length n: ping-pong a <-> b, returns the buffer holding the result
-float2 *run_passes(sr_ctx *ctx, float2 *a, float2 *b, long long lines, int n, const float2 *tw)
+float2 *run_passes(sr_ctx *ctx, float2 *a, float2 *b, long long lines, int n, const float2 *tw, bool comp = false)
 {
     int Ns = 1;
     for (int R : radices(n)) {
         const int nb = R >= CM_THREADS ? 1 : CM_THREADS / R;
         const long long total = lines * (n / R);
-        hipLaunchKernelGGL(k_fft_pass, dim3((unsigned)((total + nb - 1) / nb)), dim3(CM_THREADS), 0, ctx->stream,
+        // compensated sums where the sum is long (a merged radix of up to 32 terms gains nothing from them)
+        auto pass = comp && R > 32 ? k_fft_pass<true> : k_fft_pass<false>;
+        hipLaunchKernelGGL(pass, dim3((unsigned)((total + nb - 1) / nb)), dim3(CM_THREADS), 0, ctx->stream,
                            (const float2 *)a, b, lines, n, R, Ns, tw);
         std::swap(a, b);
         Ns *= R;
@@ -679,12 +694,12 @@ size_t fft_work_len(int n) { return needs_bluestein(n) ? (size_t)blu_len(n) : (s
 
 // Forward DFT of `lines` lines of length n held in X; P, Q are work buffers of lines * fft_work_len(n) elements, tab of
 // fft_tab_elems(n).  Returns the buffer with the result (X or P).
-float2 *fft_lines(sr_ctx *ctx, float2 *X, float2 *P, float2 *Q, float2 *tab, long long lines, int n)
+float2 *fft_lines(sr_ctx *ctx, float2 *X, float2 *P, float2 *Q, float2 *tab, long long lines, int n, bool comp = false)
 {
     if (n == 1) return X;
     if (!needs_bluestein(n)) {
         hipLaunchKernelGGL(k_twiddle, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, tab, n);
-        return run_passes(ctx, X, P, lines, n, tab);
+        return run_passes(ctx, X, P, lines, n, tab, comp);
     }
     const int M = blu_len(n);
     float2 *twM = tab, *w = twM + M, *bA = w + n, *bB = bA + M;
@@ -742,6 +757,15 @@ int cm_workspace(sr_ctx *ctx, size_t bytes, char **out)
 size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
+
+// the line engine for the other translation units (sr_fft.h)
+size_t sr_fft_tab_elems(int n) { return fft_tab_elems(n); }
+size_t sr_fft_work_len(int n) { return fft_work_len(n); }
+float2 *sr_fft_lines(sr_ctx *ctx, float2 *X, float2 *P, float2 *Q, float2 *tab, long long lines, int n, bool comp)
+{
+    return fft_lines(ctx, X, P, Q, tab, lines, n, comp);
+}
+int sr_fft_workspace(sr_ctx *ctx, size_t bytes, char **out) { return cm_workspace(ctx, bytes, out); }
 
 int sr_fft_max_len(void) { return CM_MAX_LEN; }
 

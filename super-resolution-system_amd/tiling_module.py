@@ -5,11 +5,19 @@ Keeps the reference's names, fields, integer bookkeeping and error behaviour
 the neighbour graph come from the C ABI's host functions (bit-exact restatements); tile extraction
 with border padding and the feather merge run as HIP kernels.  No CPU compute fallback.
 
-Not on this path: ContentAnalyzer (Haar / MSER / saliency need OpenCV models) -- tiles
-are never moved by it in the reference either (positions are always the uniform grid), so only the
-``roi_flags`` annotation is absent.  The L1/L2 tile caches and the JSON checkpoint are host-side
-persistence outside the tile -> blend -> assess path and are NOT rebuilt; only the constructor's cache-directory
-side effect and the ``restore_from_cache`` probe of main.py:299-304 exist.
+ContentAnalyzer (tiling_module.py:174-370): the spectral-residual saliency map (the branch the reference
+takes without cv2's contrib saliency module), the local entropy map, the forbidden-zone map and the per-tile
+``roi_flags`` run as HIP kernels (csrc/sr_content.hip) on the image already uploaded for the tiles; with
+``device_resident=True`` only the per-tile counts come back.  Tiles are never moved by the analyzer in the reference
+either (positions are always the uniform grid): the flags are an annotation.  An analyzer is opt-in
+(``TilingModule(content_analyzer=ContentAnalyzer())``); without one nothing is launched and ``roi_flags`` stays ``{}``.
+
+Not on this path: the Haar face cascade and MSER text detection (OpenCV models and internals that cannot be restated) --
+``ContentAnalyzer`` takes them as optional host callables; without a face detector ``detect_faces`` returns ``[]`` (what
+the reference does when the cascade file is missing), without a text detector ``detect_text_regions`` raises
+NotImplementedError.  The ``cv2.saliency`` fine-grained branch is not rebuilt.  The L1/L2 tile caches and the JSON
+checkpoint are host-side persistence outside the tile -> blend -> assess path and are NOT rebuilt; only
+the constructor's cache-directory side effect and the ``restore_from_cache`` probe of main.py:299-304 exist.
 
 Reference quirks kept: the last-row/column overlap override (can exceed the tile size), merge_tiles
 resizing padded tiles into the unpadded output size and casting without clip, the cache directory
@@ -28,7 +36,7 @@ import uuid
 from dataclasses import asdict, dataclass, field
 from enum import Enum, auto
 from pathlib import Path
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -115,12 +123,223 @@ class Tile:
         return (x1, y1, x2, y2)
 
 
-class DeviceTileSet:
-    """What split_array(device_resident=True) leaves in HBM: the source image and its n padded block x block tiles."""
+_FFT_MAX_LEN = 32768          # sr_fft_max_len(): longest DFT line of the hand-written FFT
 
-    def __init__(self, ctx, d_img, d_tiles, n: int, block: int, image_h: int, image_w: int):
+
+class DeviceForbiddenMap:
+    """What the device forms of ContentAnalyzer.create_forbidden_zone_map leave in HBM: the h x w map (one byte per pixel,
+    0 or 1) and, when saliency was asked for, the u8 saliency plane it was thresholded from."""
+
+    def __init__(self, ctx, d_map, d_saliency, h: int, w: int):
+        self.ctx, self.d_map, self.d_saliency, self.h, self.w = ctx, d_map, d_saliency, h, w
+
+    @property
+    def ptr(self) -> int:
+        return self.d_map.ptr
+
+    def download(self) -> np.ndarray:
+        return self.ctx.download(self.d_map.ptr, (self.h, self.w), np.uint8).astype(bool)
+
+    def free(self):
+        for b in (self.d_map, self.d_saliency):
+            if b is not None:
+                b.free()
+        self.d_map = self.d_saliency = None
+
+
+Box = Tuple[int, int, int, int]
+
+
+class ContentAnalyzer:
+    """Key-region analysis for content-aware tiling (tiling_module.py:174-370) on the GPU.
+
+    ``face_detector`` / ``text_detector``: optional host callables ``image -> [(x, y, w, h)]`` standing in for the
+    reference's Haar cascade and MSER (not restated).  Images are uint8 HxW or HxWx{1,3,4} (alpha ignored); every check
+    runs before device work.  The ``*_device`` forms take the address of a dense u8 image already in HBM and leave their
+    result there."""
+
+    def __init__(self, device: int = 0, face_detector: Optional[Callable[[np.ndarray], Sequence[Box]]] = None,
+                 text_detector: Optional[Callable[[np.ndarray], Sequence[Box]]] = None):
+        self.device = device
+        self.face_detector = face_detector
+        self.text_detector = text_detector
+        self.face_cascade = None              # the reference's attribute; no cascade is ever loaded here
+        self._face_note_logged = False
+
+    def _ctx(self) -> "_native.Context":
+        return _native.default_context(self.device)
+
+    # -- argument checks (no device work) --------------------------------------------------------------
+    @staticmethod
+    def _check_shape(shape, what: str) -> Tuple[int, int, int]:
+        shape = tuple(int(v) for v in shape)
+        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] not in (1, 3, 4)) or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"{what}: expected a u8 HxW or HxWx{{1,3,4}} image, got shape {shape}")
+        return shape[0], shape[1], (shape[2] if len(shape) == 3 else 1)
+
+    @classmethod
+    def _check_image(cls, image, what: str) -> np.ndarray:
+        img = np.asarray(image)
+        if img.dtype != np.uint8:
+            raise NotImplementedError(f"{what}: only uint8 images are on the HIP path; got {img.dtype}")
+        cls._check_shape(img.shape, what)
+        return np.ascontiguousarray(img)
+
+    @staticmethod
+    def _check_fft(h: int, w: int, what: str):
+        if max(h, w) > _FFT_MAX_LEN:
+            raise NotImplementedError(f"{what}: image side {max(h, w)} is above the longest DFT line the HIP FFT supports "
+                                      f"({_FFT_MAX_LEN})")
+
+    # -- detectors (host callables) ------------------------------------------------------------------------
+    def detect_faces(self, image: np.ndarray) -> List[Box]:
+        if self.face_detector is None:
+            if not self._face_note_logged:
+                logger.info("ContentAnalyzer: no face detector given; detect_faces returns [] (the reference's answer "
+                            "without its cascade file)")
+                self._face_note_logged = True
+            return []
+        return [(int(x), int(y), int(w), int(h)) for x, y, w, h in self.face_detector(image)]
+
+    def detect_text_regions(self, image: np.ndarray) -> List[Box]:
+        if self.text_detector is None:
+            raise NotImplementedError("detect_text_regions: cv2.MSER is not restated; pass text_detector= to ContentAnalyzer "
+                                      "or call create_forbidden_zone_map(protect_text=False)")
+        return [(int(x), int(y), int(w), int(h)) for x, y, w, h in self.text_detector(image)]
+
+    # -- saliency (tiling_module.py:261-289) ---------------------------------------------------------------
+    def compute_saliency_map_device(self, d_image: int, shape) -> "_native.DeviceBuffer":
+        """-> the u8 HxW saliency plane in HBM (the caller frees it)."""
+        h, w, cn = self._check_shape(shape, "compute_saliency_map")
+        self._check_fft(h, w, "compute_saliency_map")
+        ctx = self._ctx()
+        d_sal = ctx.alloc(h * w)
+        ctx.saliency_u8(d_image, w * cn, h, w, cn, d_sal.ptr)
+        return d_sal
+
+    def compute_saliency_map(self, image: np.ndarray) -> np.ndarray:
+        img = self._check_image(image, "compute_saliency_map")
+        self._check_fft(img.shape[0], img.shape[1], "compute_saliency_map")
+        ctx = self._ctx()
+        d_img = ctx.upload(img)
+        try:
+            d_sal = self.compute_saliency_map_device(d_img.ptr, img.shape)
+            try:
+                return ctx.download(d_sal.ptr, img.shape[:2], np.uint8)
+            finally:
+                d_sal.free()
+        finally:
+            d_img.free()
+
+    # -- local entropy (tiling_module.py:291-321) --------------------------------------------------------------
+    @staticmethod
+    def _check_window(window_size) -> int:
+        if int(window_size) != window_size or not (1 <= int(window_size) <= 32768):
+            raise ValueError(f"compute_local_entropy: window_size must be an integer in 1..32768, got {window_size}")
+        return int(window_size)
+
+    def compute_local_entropy_device(self, d_image: int, shape, window_size: int = 64) -> "_native.DeviceBuffer":
+        """-> the float32 HxW entropy plane in HBM (the caller frees it)."""
+        h, w, cn = self._check_shape(shape, "compute_local_entropy")
+        win = self._check_window(window_size)
+        ctx = self._ctx()
+        d_out = ctx.alloc(h * w * 4)
+        ctx.local_entropy_u8(d_image, w * cn, h, w, cn, win, d_out.ptr)
+        return d_out
+
+    def compute_local_entropy(self, image: np.ndarray, window_size: int = 64) -> np.ndarray:
+        img = self._check_image(image, "compute_local_entropy")
+        self._check_window(window_size)
+        ctx = self._ctx()
+        d_img = ctx.upload(img)
+        try:
+            d_out = self.compute_local_entropy_device(d_img.ptr, img.shape, window_size)
+            try:
+                return ctx.download(d_out.ptr, img.shape[:2], np.float32)
+            finally:
+                d_out.free()
+        finally:
+            d_img.free()
+
+    # -- forbidden zones (tiling_module.py:323-370) --------------------------------------------------------------
+    def _zone_rects(self, host_image: Optional[np.ndarray], protect_faces: bool, protect_text: bool) -> List[Box]:
+        """Face boxes grown by int(max(w, h) * 0.2) and text boxes as given; clipping is the map kernel's."""
+        if protect_text and self.text_detector is None:
+            self.detect_text_regions(host_image)          # raises NotImplementedError
+        need_host = (protect_faces and self.face_detector is not None) or protect_text
+        if need_host and host_image is None:
+            raise ValueError("create_forbidden_zone_map: the face / text detectors are host callables and need host_image=")
+        rects: List[Box] = []
+        if protect_faces:
+            for x, y, w, h in self.detect_faces(host_image):
+                margin = int(max(w, h) * 0.2)
+                x1, y1 = max(0, x - margin), max(0, y - margin)
+                rects.append((x1, y1, max(0, x + w + margin - x1), max(0, y + h + margin - y1)))
+        if protect_text:
+            for x, y, w, h in self.detect_text_regions(host_image):
+                # numpy's [y:y+h, x:x+w]: a negative start counts from the far edge there; detectors return boxes with
+                # x, y >= 0, anything else is refused rather than wrapped
+                if x < 0 or y < 0:
+                    raise ValueError(f"text box ({x}, {y}, {w}, {h}) starts outside the image")
+                rects.append((x, y, max(0, w), max(0, h)))
+        return rects
+
+    def create_forbidden_zone_map_device(self, d_image: int, shape, protect_faces: bool = True, protect_text: bool = True,
+                                         protect_salient: bool = True, saliency_threshold: float = 0.7,
+                                         host_image: Optional[np.ndarray] = None) -> DeviceForbiddenMap:
+        """create_forbidden_zone_map on a dense u8 image already in HBM: the map (and the saliency plane) stay there.
+        ``host_image``: the same image on the host, needed only when a detector callable has to run."""
+        h, w, cn = self._check_shape(shape, "create_forbidden_zone_map")
+        rects = self._zone_rects(host_image, protect_faces, protect_text)
+        if protect_salient:
+            self._check_fft(h, w, "create_forbidden_zone_map")
+        threshold = int(255 * saliency_threshold)
+        ctx = self._ctx()
+        d_sal = self.compute_saliency_map_device(d_image, shape) if protect_salient else None
+        d_map = ctx.alloc(h * w)
+        ctx.forbidden_map(d_sal.ptr if d_sal is not None else None, h, w, threshold, rects, d_map.ptr)
+        return DeviceForbiddenMap(ctx, d_map, d_sal, h, w)
+
+    def create_forbidden_zone_map(self, image: np.ndarray, protect_faces: bool = True, protect_text: bool = True,
+                                  protect_salient: bool = True, saliency_threshold: float = 0.7) -> np.ndarray:
+        img = self._check_image(image, "create_forbidden_zone_map")
+        if protect_text and self.text_detector is None:
+            self.detect_text_regions(img)                 # raises before any device call
+        if protect_salient:
+            self._check_fft(img.shape[0], img.shape[1], "create_forbidden_zone_map")
+        ctx = self._ctx()
+        d_img = ctx.upload(img)
+        try:
+            fmap = self.create_forbidden_zone_map_device(d_img.ptr, img.shape, protect_faces, protect_text, protect_salient,
+                                                         saliency_threshold, host_image=img)
+            try:
+                return fmap.download()
+            finally:
+                fmap.free()
+        finally:
+            d_img.free()
+
+    def tile_flags(self, d_map: DeviceForbiddenMap, positions: Sequence[Box]) -> List[Dict]:
+        """metadata.roi_flags of every tile (tiling_module.py:752-757) from exact counts over the map in HBM: the unpadded
+        rectangle [y:y+h, x:x+w] clipped by the image as the slice is; ratio = count / pixels in Python floats."""
+        areas = []
+        for x, y, w, h in positions:
+            if x < 0 or y < 0 or w < 1 or h < 1 or x >= d_map.w or y >= d_map.h:
+                raise ValueError(f"tile_flags: rectangle ({x}, {y}, {w}, {h}) has no pixel inside the {d_map.w} x {d_map.h} map")
+            areas.append((min(x + w, d_map.w) - x) * (min(y + h, d_map.h) - y))
+        counts = d_map.ctx.rect_counts_u8(d_map.ptr, d_map.w, d_map.h, d_map.w, positions)
+        return [{'has_forbidden_zone': c > 0, 'forbidden_ratio': float(c / a)} for c, a in zip(counts, areas)]
+
+
+class DeviceTileSet:
+    """What split_array(device_resident=True) leaves in HBM: the source image and its n padded block x block tiles (and,
+    with a content analyzer, the forbidden-zone map)."""
+
+    def __init__(self, ctx, d_img, d_tiles, n: int, block: int, image_h: int, image_w: int,
+                 forbidden: Optional[DeviceForbiddenMap] = None):
         self.ctx, self.d_img, self.d_tiles = ctx, d_img, d_tiles
         self.n, self.block, self.image_h, self.image_w = n, block, image_h, image_w
+        self.forbidden = forbidden
 
     @property
     def tile_bytes(self) -> int:
@@ -131,10 +350,10 @@ class DeviceTileSet:
 
     def free(self):
         self.ctx.sync()
-        for b in (self.d_img, self.d_tiles):
+        for b in (self.d_img, self.d_tiles, self.forbidden):
             if b is not None:
                 b.free()
-        self.d_img = self.d_tiles = None
+        self.d_img = self.d_tiles = self.forbidden = None
 
 
 def _load_rgb(image_path: str) -> np.ndarray:
@@ -151,7 +370,8 @@ class TilingModule:
 
     def __init__(self, block_size: int = 2048, overlap_ratio: float = 0.2, padding_mode: str = 'mirror',
                  output_scale: float = 2.0, l1_cache_size: int = 50, l2_cache_dir: Optional[str] = None,
-                 enable_content_aware: bool = True, device: int = 0):
+                 enable_content_aware: bool = True, device: int = 0,
+                 content_analyzer: Optional[ContentAnalyzer] = None, forbidden_zone_args: Optional[dict] = None):
         if not (0.1 <= overlap_ratio <= 0.3):
             raise ValueError(f"重叠率必须在0.1-0.3之间，当前值: {overlap_ratio}")
         self.block_size = block_size
@@ -161,7 +381,10 @@ class TilingModule:
         self.enable_content_aware = enable_content_aware
         self.output_size = int(block_size * output_scale)
         self.overlap_pixels = int(block_size * overlap_ratio)
-        self.content_analyzer = None          # out of scope, see module docstring
+        if content_analyzer is not None and content_analyzer.device != device:
+            raise ValueError(f"content_analyzer is on device {content_analyzer.device}, the tiles on device {device}")
+        self.content_analyzer = content_analyzer      # opt-in (see module docstring): None launches nothing
+        self.forbidden_zone_args = dict(forbidden_zone_args or {})
         self.l1_cache_size = l1_cache_size    # accepted for signature parity; the tile caches are out of scope
         if l2_cache_dir is None:
             l2_cache_dir = os.path.expanduser("~/.cache/super_resolution/tiling")
@@ -236,19 +459,30 @@ class TilingModule:
         ih, iw = image.shape[:2]
         positions = self._calculate_tile_positions(iw, ih)
         n, block = len(positions), self.block_size
+        analyzer = self.content_analyzer if self.enable_content_aware else None
+        if analyzer is not None and self.forbidden_zone_args.get('protect_text', True) and analyzer.text_detector is None:
+            analyzer.detect_text_regions(image)           # raises NotImplementedError before any device work
         ctx = self._ctx()
         d_img = ctx.upload(image)
         d_tiles = ctx.alloc(n * block * block * 3)
         ctx.tile_extract_pad(d_img.ptr, ih, iw, 3, iw * 3, positions, block, self.padding_mode.value, d_tiles.ptr)
+        fmap, roi_flags = None, None
+        if analyzer is not None:
+            # the map is built once from the uploaded source image; only the per-tile counts come back
+            fmap = analyzer.create_forbidden_zone_map_device(d_img.ptr, image.shape, host_image=image,
+                                                             **self.forbidden_zone_args)
+            roi_flags = analyzer.tile_flags(fmap, positions)
         data, scores = None, None
         if device_resident:
             self.release_device_tiles()
-            self.device_tiles = DeviceTileSet(ctx, d_img, d_tiles, n, block, ih, iw)
+            self.device_tiles = DeviceTileSet(ctx, d_img, d_tiles, n, block, ih, iw, forbidden=fmap)
             if self.enable_content_aware:
                 scores = ctx.gray_std_u8(d_tiles.ptr, n, block * block * 3, block * 3, block, block)
         else:
             data = ctx.download(d_tiles.ptr, (n, block, block, 3), np.uint8)
             d_img.free(); d_tiles.free()
+            if fmap is not None:
+                fmap.free()
         tiles: List[Tile] = []
         for idx, (x, y, w, h) in enumerate(positions):
             top, bottom, left, right = self._calculate_overlap_for_tile(x, y, w, h, iw, ih)
@@ -264,6 +498,8 @@ class TilingModule:
                 t = tile_img.astype(np.int64)
                 gray = (t[..., 0] * 3735 + t[..., 1] * 19235 + t[..., 2] * 9798 + (1 << 14)) >> 15
                 meta.complexity_score = float(np.std(gray.astype(np.uint8)))
+            if roi_flags is not None:
+                meta.roi_flags = roi_flags[idx]
             tile = Tile(metadata=meta, data=tile_img)
             tiles.append(tile)
             if save_metadata:
