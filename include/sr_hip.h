@@ -387,6 +387,45 @@ SR_API int sr_forbidden_map(sr_ctx *ctx, const uint8_t *d_sal, int h, int w, int
 SR_API int sr_rect_counts_u8(sr_ctx *ctx, const uint8_t *d_map, int64_t stride, int h, int w, const sr_tile_rect *h_rects,
                              int n, uint64_t *h_counts);
 
+/* ---- BlendingModule.poisson_fusion / repair_seams (blending_module.py:563-659, 1148-1240; csrc/sr_poisson.hip) ---------------
+ * PARITY UNPINNED: cv2 is not available to this repository's tests, so the OpenCV behaviour below is restated from memory
+ * (Cloning::normalClone of photo/src/seamless_cloning_impl.cpp, GaussianBlur's 8-bit fixed-point path) and tested against this
+ * repository's own NumPy / SciPy restatement (tests/_poisson_ref.py).
+ *
+ * sr_poisson_clone_u8: cv2.seamlessClone's solve on ONE rectangle of h x w pixels, 3 channels: d_dest is the destination
+ * rectangle, d_patch the source pixels laid over it, d_mask (one byte per pixel) the clone mask.  fp32 throughout:
+ *   the mask is (byte != 0) eroded three times by a 3 x 3 element (a 7 x 7 minimum; pixels outside the rectangle do not erode);
+ *   forward differences I[x + 1] - I[x], I[y + 1] - I[y] of destination and patch per channel;
+ *   mode 1 (NORMAL_CLONE) takes the patch pair where the mask is set, mode 2 (MIXED_CLONE) there takes per pixel and channel the
+ *   patch pair where |pgx - pgy| > |dgx - dgy| and else the destination pair, mode 3 (MONOCHROME_TRANSFER) is mode 1 with the
+ *   patch replaced by its 8-bit RGB2GRAY value in all three channels; the destination pair where the mask is clear;
+ *   backward differences of that field give the Laplacian, the 4-neighbour Laplacian of the destination with its interior
+ *   zeroed is subtracted, and the (h - 2) x (w - 2) Dirichlet problem is solved by a DST-I along rows and columns, a division by
+ *   (2 cos(pi (x + 1) / (w - 1)) - 2) + (2 cos(pi (y + 1) / (h - 1)) - 2), and the inverse DST-I along both axes;
+ *   d_out's interior receives saturate(round-half-even(solution)), its 1-pixel frame the destination's (d_out may be d_dest).
+ * (A patch whose pixels outside the mask are zeroed, as seamlessClone prepares it, gives the same bytes: the eroded mask never
+ * selects a patch difference that reaches outside the mask.)  h or w below 3: no interior, the output is the destination.  A
+ * side above sr_poisson_max_side() (= sr_fft_max_len() / 2 + 1: the DST-I of n values is taken from the DFT of their odd
+ * extension to 2 (n + 1)): SR_ERR_UNSUPPORTED.  Fixed summation orders: equal inputs give equal bytes.  Asynchronous. */
+SR_API int sr_poisson_max_side(void);
+SR_API int sr_poisson_clone_u8(sr_ctx *ctx, const uint8_t *d_dest, int64_t dest_stride, const uint8_t *d_patch,
+                               int64_t patch_stride, const uint8_t *d_mask, int64_t mask_stride, int h, int w, int mode,
+                               uint8_t *d_out, int64_t out_stride);
+/* cv2.GaussianBlur(roi, (15, 15), 0) on u8, cn 1, 3 or 4 (repair_seams' "increase_blend_width", :1191-1193): sigma 2.6,
+ * separable, 8.8 fixed-point taps {1 3 6 12 20 29 37 40 37 ...} (side taps rounded, the centre takes what is left of 256), the
+ * row pass exact in 16 bits, the column pass rounded once ((s + 2^15) >> 16), REFLECT_101 at the rectangle's own border.
+ * d_dst may be d_src (the row pass goes through workspace).  Asynchronous. */
+SR_API int sr_gaussian_blur15_u8(sr_ctx *ctx, const uint8_t *d_src, int64_t src_stride, int h, int w, int cn, uint8_t *d_dst,
+                                 int64_t dst_stride);
+/* _compute_ssim (:855-903) of two u8 rectangles of h x w pixels (cn 1, 3 or 4; gray = cv2.COLOR_BGR2GRAY applied to the RGB
+ * data): exact integer moments on the GPU, the float64 global-statistics formula on them -> *h_ssim.  Synchronous. */
+SR_API int sr_region_ssim_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h,
+                             int w, int cn, int gray_shift, double *h_ssim);
+/* cv2.resize(src, (dw, dh)) with the default INTER_LINEAR on u8 (cn 1..4): the sampling of sr_feather_merge's resize branch
+ * (half-pixel centres, 11-bit coefficients).  Asynchronous. */
+SR_API int sr_resize_linear_u8(sr_ctx *ctx, const uint8_t *d_src, int64_t src_stride, int h, int w, int cn, uint8_t *d_dst,
+                               int64_t dst_stride, int dh, int dw);
+
 /* ---- quality metrics (quality_assessment_module.py:277-417) ---------------------------- */
 /* Sum of squared differences over h rows of rowlen u8 elements -> *h_sse (exact integer).
  * PSNR = 10 log10(data_range^2 / (sse / (h*rowlen))) is finished on the host (and partial sums

@@ -20,6 +20,9 @@ PAD_MODES = {"mirror": 0, "replicate": 1, "reflect": 2, "constant": 3}
 WEIGHT_TYPES = {"linear": 0, "cosine": 1, "sigmoid": 2, "ones": 3}
 SSIM_MODES = {"uniform": 0, "gauss": 1, "simple": 2}
 SR_U8, SR_F32, SR_F64 = 0, 1, 2
+# sr_poisson_max_side(): the longest side sr_poisson_clone_u8 solves (sr_fft_max_len() / 2 + 1); tests/test_poisson_host.py
+# holds it against the library's answer
+POISSON_MAX_SIDE = 16385
 
 
 class SrNativeError(RuntimeError):
@@ -141,6 +144,11 @@ SIGNATURES = {
     "sr_local_entropy_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sr_forbidden_map": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(TileRect), _i, _vp]),
     "sr_rect_counts_u8": (_i, [_vp, _vp, _i64, _i, _i, C.POINTER(TileRect), _i, C.POINTER(C.c_uint64)]),
+    "sr_poisson_max_side": (_i, []),
+    "sr_poisson_clone_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i64]),
+    "sr_gaussian_blur15_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
+    "sr_region_ssim_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, C.POINTER(_dbl)]),
+    "sr_resize_linear_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i]),
     "sr_sse_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i64, C.POINTER(C.c_uint64)]),
     "sr_sse_u8_async": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i64, _vp]),
     "sr_psnr_from_sse": (_dbl, [C.c_uint64, C.c_uint64, _dbl]),
@@ -696,6 +704,39 @@ class Context:
         rects = (TileRect * max(n, 1))(*[TileRect(int(x), int(y), int(rw), int(rh)) for (x, y, rw, rh) in rects_xywh])
         check(self.lib.sr_rect_counts_u8(self.handle, C.c_void_p(d_map), int(stride), int(h), int(w), rects, n, out))
         return [int(out[i]) for i in range(n)]
+
+    # Poisson fusion and seam repair (sr_poisson.hip) ------------------------------------------
+    def poisson_clone_u8(self, d_dest: int, dest_stride: int, d_patch: int, patch_stride: int, d_mask: int, mask_stride: int,
+                         h: int, w: int, mode: int, d_out: int, out_stride: int):
+        """sr_poisson_clone_u8: the seamlessClone solve on one h x w x 3 rectangle (mode 1 normal, 2 mixed, 3 monochrome).
+        A side above POISSON_MAX_SIDE is refused before the device is touched.  Asynchronous."""
+        if max(int(h), int(w)) > POISSON_MAX_SIDE:
+            raise NotImplementedError(f"poisson clone: a side of {max(h, w)} pixels is above the FFT engine's {POISSON_MAX_SIDE}")
+        rc = self.lib.sr_poisson_clone_u8(self.handle, C.c_void_p(d_dest), int(dest_stride), C.c_void_p(d_patch),
+                                          int(patch_stride), C.c_void_p(d_mask), int(mask_stride), int(h), int(w), int(mode),
+                                          C.c_void_p(d_out), int(out_stride))
+        if rc == SR_ERR_UNSUPPORTED:
+            raise NotImplementedError(last_error())
+        check(rc)
+
+    def gaussian_blur15_u8(self, d_src: int, src_stride: int, h: int, w: int, cn: int, d_dst: int, dst_stride: int):
+        """sr_gaussian_blur15_u8: cv2.GaussianBlur(roi, (15, 15), 0) on u8; d_dst may be d_src.  Asynchronous."""
+        check(self.lib.sr_gaussian_blur15_u8(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), int(cn),
+                                             C.c_void_p(d_dst), int(dst_stride)))
+
+    def region_ssim_u8(self, d_a: int, stride_a: int, d_b: int, stride_b: int, h: int, w: int, cn: int,
+                       gray_shift: int = 15) -> float:
+        """sr_region_ssim_u8: _compute_ssim of two u8 rectangles in HBM (synchronous)."""
+        out = C.c_double(0.0)
+        check(self.lib.sr_region_ssim_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h),
+                                         int(w), int(cn), int(gray_shift), C.byref(out)))
+        return out.value
+
+    def resize_linear_u8(self, d_src: int, src_stride: int, h: int, w: int, cn: int, d_dst: int, dst_stride: int, dh: int,
+                         dw: int):
+        """sr_resize_linear_u8: cv2.resize(INTER_LINEAR) on u8.  Asynchronous."""
+        check(self.lib.sr_resize_linear_u8(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), int(cn),
+                                           C.c_void_p(d_dst), int(dst_stride), int(dh), int(dw)))
 
     def tile_ssim_sums_u8(self, d_canvas: int, canvas_stride: int, h: int, w: int, cn: int, rects_xywh,
                           d_tiles: Sequence[int], strides: Sequence[int], gray_shift: int = 15) -> np.ndarray:

@@ -6,10 +6,10 @@ blend hot path (reference blending_module.py:38-56,96-136,164-363,369-561,661-76
 (include/sr_hip.h) -- there is no NumPy/OpenCV compute path here and no CPU fallback: without
 libsrhip.so or a GPU the compute methods raise.
 
-Out of scope for this path: Poisson fusion and seam repair -- those methods exist so callers get a clear
-NotImplementedError instead of an AttributeError.  Built from SURVEY 8(f): detect_seams (rank 1), multi_band_fusion,
-feather_blend and color_correction (rank 4); since then gradient_domain_fusion and the module-level compute_blend_quality
-(blending_module.py:1377-1489, 1563-1608).
+Built from SURVEY 8(f): detect_seams (rank 1), multi_band_fusion, feather_blend and color_correction (rank 4); since then
+gradient_domain_fusion and the module-level compute_blend_quality (blending_module.py:1377-1489, 1563-1608), and
+poisson_fusion / repair_seams (:563-659, 1148-1240) on a DST-I Poisson solver (csrc/sr_poisson.hip; the only NumPy
+arithmetic is the reference's own few-line _fallback_blend for inputs OpenCV would refuse).
 
 Reference quirks kept: bare arrays without output_shape fail like the
 reference (ValueError: max() of an empty sequence); the canvas perimeter, where every tile's cosine
@@ -349,13 +349,90 @@ class BlendingModule:
         d = np.minimum(np.minimum(y, height - 1 - y), np.minimum(x, width - 1 - x))
         return lut[np.minimum(d, feather_width)]
 
-    # -- not on this path ---------------------------------------------------------------------------
-    def _out_of_scope(self, name: str):
-        raise NotImplementedError(f"BlendingModule.{name} is outside the MI355X tile->blend->assess path "
-                                  f"(SURVEY.md 2c); use the reference implementation for it")
+    # -- Poisson fusion (blending_module.py:563-659) --------------------------------------------------------------
+    @staticmethod
+    def _clone_rects(mask: np.ndarray, dst_shape, center):
+        """cv2.seamlessClone's bookkeeping (restated, parity unpinned): the mask's outer 1-pixel frame is zeroed, roi_s is the
+        bounding rectangle of what is left and roi_d the rectangle of the same size at (cx - w // 2, cy - h // 2) of the
+        destination.  -> ((x, y, w, h) roi_s, (x, y, w, h) roi_d); None when nothing is left of the mask or roi_d is not
+        inside the destination (OpenCV returns early / asserts)."""
+        m = mask != 0
+        m[0, :] = m[-1, :] = False
+        m[:, 0] = m[:, -1] = False
+        ys, xs = np.flatnonzero(m.any(axis=1)), np.flatnonzero(m.any(axis=0))
+        if ys.size == 0:
+            return None
+        x0, y0, rw, rh = int(xs[0]), int(ys[0]), int(xs[-1] - xs[0] + 1), int(ys[-1] - ys[0] + 1)
+        dx, dy = int(center[0]) - rw // 2, int(center[1]) - rh // 2
+        if dx < 0 or dy < 0 or dx + rw > dst_shape[1] or dy + rh > dst_shape[0]:
+            return None
+        return (x0, y0, rw, rh), (dx, dy, rw, rh)
 
-    def poisson_fusion(self, *a, **k):
-        self._out_of_scope("poisson_fusion")
+    def poisson_fusion(self, src: np.ndarray, dst: np.ndarray, mask: Optional[np.ndarray] = None,
+                       center: Optional[Tuple[int, int]] = None, mode: PoissonMode = PoissonMode.NORMAL) -> np.ndarray:
+        """blending_module.py:563-625: cv2.seamlessClone(src, dst, mask, center, mode).  The rectangle bookkeeping runs here,
+        the solve (Cloning::normalClone on roi_d: DST-I Poisson solver) on the GPU (sr_poisson_clone_u8).  The reference
+        catches every exception of the OpenCV call and returns _fallback_blend; mirrored only for what OpenCV itself would
+        reject, decided before any device work: inputs that are not 3-channel, a mask whose shape is not src's, roi_d outside
+        dst, and a mask with nothing left after its frame is zeroed (an all-zero mask then gives dst back unchanged).  Library
+        and device errors are never swallowed; a side above the FFT engine's limit raises NotImplementedError."""
+        if not isinstance(src, np.ndarray) or not isinstance(dst, np.ndarray) or not isinstance(mask, (np.ndarray, type(None))):
+            raise NotImplementedError("poisson_fusion: ndarray inputs only on the HIP path")
+        if src.dtype != np.uint8:
+            src = np.clip(src, 0, 255).astype(np.uint8)
+        if dst.dtype != np.uint8:
+            dst = np.clip(dst, 0, 255).astype(np.uint8)
+        if mask is None:
+            mask = np.ones(src.shape[:2], dtype=np.uint8) * 255
+        elif mask.dtype != np.uint8:
+            mask = (mask > 0).astype(np.uint8) * 255
+        if center is None:
+            center = (dst.shape[1] // 2, dst.shape[0] // 2)
+        mode = PoissonMode(mode)
+        ok = src.ndim == 3 and dst.ndim == 3 and src.shape[2] == 3 and dst.shape[2] == 3 and mask.shape == src.shape[:2]
+        rects = self._clone_rects(mask.copy(), dst.shape, center) if ok else None
+        if rects is None:
+            if ok and not mask.any():
+                return dst.copy()
+            logger.warning("poisson_fusion: falling back to the weighted average blend")
+            return self._fallback_blend(src, dst, mask, center)
+        (sx, sy, rw, rh), (dx, dy, _, _) = rects
+        if max(rw, rh) > _native.POISSON_MAX_SIDE:
+            raise NotImplementedError(f"poisson_fusion: a clone rectangle of {rw}x{rh} is above the FFT engine's side limit "
+                                      f"of {_native.POISSON_MAX_SIDE}")
+        mroi = np.ascontiguousarray(mask[sy:sy + rh, sx:sx + rw])
+        patch = src[sy:sy + rh, sx:sx + rw] * (mroi != 0)[..., None].astype(np.uint8)
+        ctx = self._ctx()
+        bufs = []
+        try:
+            for a in (np.ascontiguousarray(dst[dy:dy + rh, dx:dx + rw]), patch, mroi):
+                bufs.append(ctx.upload(a))
+            ctx.poisson_clone_u8(bufs[0].ptr, rw * 3, bufs[1].ptr, rw * 3, bufs[2].ptr, rw, rh, rw, mode.value,
+                                 bufs[0].ptr, rw * 3)
+            out = dst.copy()
+            out[dy:dy + rh, dx:dx + rw] = ctx.download(bufs[0].ptr, (rh, rw, 3), np.uint8)
+            return out
+        finally:
+            ctx.sync()
+            for b in bufs:
+                b.free()
+
+    @staticmethod
+    def _fallback_blend(src: np.ndarray, dst: np.ndarray, mask: np.ndarray, center: Tuple[int, int]) -> np.ndarray:
+        """blending_module.py:627-659: the float32 blend roi (1 - m) + src m at the centred position, truncated to uint8.
+        A few lines of host arithmetic on a path the reference only takes when OpenCV refuses its inputs."""
+        h, w = src.shape[:2]
+        cx, cy = center
+        x1, y1 = max(0, cx - w // 2), max(0, cy - h // 2)
+        x2, y2 = min(dst.shape[1], x1 + w), min(dst.shape[0], y1 + h)
+        s = src[:y2 - y1, :x2 - x1]
+        m = mask[:y2 - y1, :x2 - x1].astype(np.float32) / 255.0
+        if s.ndim == 3:
+            m = np.expand_dims(m, axis=-1)
+        result = dst.copy()
+        roi = result[y1:y2, x1:x2]
+        result[y1:y2, x1:x2] = (roi * (1 - m) + s * m).astype(np.uint8)
+        return result
 
     def feather_blend(self, tiles: List[Union[np.ndarray, TileInfo]], feather_width: int = 50,
                       output_shape: Optional[Tuple[int, int]] = None) -> np.ndarray:
@@ -478,8 +555,112 @@ class BlendingModule:
                                ssim_score=float(np.mean([s.ssim_score for s in g]))))
         return merged
 
-    def repair_seams(self, *a, **k):
-        self._out_of_scope("repair_seams")
+    def repair_seams(self, image: np.ndarray, seams: List[Seam], tiles: List[np.ndarray],
+                     repair_method: str = "auto") -> np.ndarray:
+        """blending_module.py:1148-1240, quirks kept: seams are repaired in list order on one working copy (a later seam
+        sees earlier repairs); the method is seam.suggested_fix under "auto", else the string given -- the documented "blend"
+        and "poisson" match neither branch and change nothing; the box is the seam padded by max(width, height) and clipped
+        to the image.  "increase_blend_width": the 15 x 15 Gaussian blur of the box (sr_gaussian_blur15_u8).
+        "poisson_refinement": the tile of the largest global SSIM against the box, every tile resized to it (first maximum;
+        sr_resize_linear_u8, sr_region_ssim_u8), cloned in MIXED mode through the seam rectangle with poisson_fusion's
+        bookkeeping and fallback rules.  Image and tiles are uploaded once, every seam works on device sub-rectangles, the
+        image is downloaded once.  uint8 images and tiles with 3 channels only (NotImplementedError otherwise)."""
+        image = np.asarray(image)
+        tiles = [np.asarray(t) for t in tiles]
+        methods = [s.suggested_fix if repair_method == "auto" else repair_method for s in seams]
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise NotImplementedError(f"repair_seams: uint8 HxWx3 images only on the HIP path (got {image.dtype} {image.shape})")
+        if not any(m in ("increase_blend_width", "poisson_refinement") for m in methods):
+            return image.copy()
+        need_tiles = "poisson_refinement" in methods
+        if need_tiles:
+            if not tiles:
+                raise IndexError("repair_seams: poisson_refinement needs at least one tile")       # the reference's tiles[0]
+            for t in tiles:
+                if t.dtype != np.uint8 or t.ndim != 3 or t.shape[2] != 3:
+                    raise NotImplementedError(f"repair_seams: uint8 HxWx3 tiles only on the HIP path (got {t.dtype} {t.shape})")
+        H, W = image.shape[:2]
+        stride = W * 3
+        ctx = self._ctx()
+        bufs = []
+        try:
+            d_img = ctx.upload(image)
+            bufs.append(d_img)
+            d_tiles = []
+            if need_tiles:
+                for t in tiles:
+                    d_tiles.append(ctx.upload(t))
+                    bufs.append(d_tiles[-1])
+            for seam, method in zip(seams, methods):
+                if method not in ("increase_blend_width", "poisson_refinement"):
+                    continue
+                x1, y1 = int(seam.x), int(seam.y)
+                x2, y2 = x1 + int(seam.width), y1 + int(seam.height)
+                pad = max(int(seam.width), int(seam.height))
+                xa, ya, xb, yb = max(0, x1 - pad), max(0, y1 - pad), min(W, x2 + pad), min(H, y2 + pad)
+                bw, bh = xb - xa, yb - ya
+                if bw < 1 or bh < 1:
+                    continue
+                d_box = d_img.ptr + ya * stride + xa * 3
+                if method == "increase_blend_width":
+                    ctx.gaussian_blur15_u8(d_box, stride, bh, bw, 3, d_box, stride)
+                    continue
+                self._refine_box(ctx, d_box, stride, bw, bh, (x1 - xa, y1 - ya, x2 - xa, y2 - ya), tiles, d_tiles)
+            return ctx.download(d_img.ptr, image.shape, np.uint8)
+        finally:
+            ctx.sync()
+            for b in bufs:
+                b.free()
+
+    def _refine_box(self, ctx, d_box: int, stride: int, bw: int, bh: int, seam_box, tiles, d_tiles) -> None:
+        """"poisson_refinement" of one padded box that lives in HBM at d_box: _find_best_matching_tile, then
+        poisson_fusion(best, box, mask of the seam rectangle, centre of the box, MIXED) in place."""
+        cand = [ctx.alloc(bw * bh * 3), ctx.alloc(bw * bh * 3)]
+        d_mask = None
+        try:
+            best, best_score = None, -1
+            for t, d_t in zip(tiles, d_tiles):
+                ctx.resize_linear_u8(d_t.ptr, t.shape[1] * 3, t.shape[0], t.shape[1], 3, cand[1].ptr, bw * 3, bh, bw)
+                score = ctx.region_ssim_u8(d_box, stride, cand[1].ptr, bw * 3, bh, bw, 3)
+                if score > best_score:
+                    best, best_score = cand[1], score
+                    cand.reverse()
+            if best is None:                                  # no score above -1: the reference keeps tiles[0]
+                t = tiles[0]
+                ctx.resize_linear_u8(d_tiles[0].ptr, t.shape[1] * 3, t.shape[0], t.shape[1], 3, cand[0].ptr, bw * 3, bh, bw)
+            d_best = cand[0].ptr
+            mask = np.zeros((bh, bw), dtype=np.uint8)
+            sx1, sy1, sx2, sy2 = seam_box
+            mask[max(sy1, 0):max(sy2, 0), max(sx1, 0):max(sx2, 0)] = 255
+            center = (bw // 2, bh // 2)
+            rects = self._clone_rects(mask.copy(), (bh, bw), center)
+            if rects is None:
+                if mask.any():                                # only the frame of the box is masked: the host blend
+                    box = self._download_box(ctx, d_box, stride, bw, bh)
+                    src = ctx.download(d_best, (bh, bw, 3), np.uint8)
+                    self._upload_box(ctx, self._fallback_blend(src, box, mask, center), d_box, stride)
+                return
+            (sx, sy, rw, rh), (dx, dy, _, _) = rects
+            # the seam rectangle is filled, so mask[roi_s] is all 255
+            d_mask = ctx.alloc(rw * rh)
+            ctx.memset(d_mask.ptr, 255, rw * rh)
+            d_dest = d_box + dy * stride + dx * 3
+            ctx.poisson_clone_u8(d_dest, stride, d_best + (sy * bw + sx) * 3, bw * 3, d_mask.ptr, rw, rh, rw,
+                                 PoissonMode.MIXED.value, d_dest, stride)
+        finally:
+            ctx.sync()
+            for b in cand + ([d_mask] if d_mask is not None else []):
+                b.free()
+
+    @staticmethod
+    def _download_box(ctx, d_box: int, stride: int, bw: int, bh: int) -> np.ndarray:
+        return np.stack([ctx.download(d_box + y * stride, (bw, 3), np.uint8) for y in range(bh)])
+
+    @staticmethod
+    def _upload_box(ctx, box: np.ndarray, d_box: int, stride: int) -> None:
+        for y in range(box.shape[0]):
+            row = np.ascontiguousarray(box[y])
+            _native.check(ctx.lib.sr_memcpy_h2d(ctx.handle, d_box + y * stride, row.ctypes.data, row.nbytes))
 
     # -- colour consistency (blending_module.py:969-1146) ---------------------------------------------------------
     @staticmethod
