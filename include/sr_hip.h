@@ -239,7 +239,9 @@ SR_API int sr_blend_plan_workspace_bytes(const sr_blend_plan *plan, size_t *byte
  * never touched, so the address may be virtual); h_strides[i]: row stride in bytes.
  * d_canvas: u8 HWC canvas (row stride canvas_stride bytes), only rows [row_begin,row_end)
  * are written.  d_canvas_f32 (nullable): dense fp32 HWC canvas receiving the normalised value
- * before clip / truncation (parity tests). */
+ * before clip / truncation (parity tests).
+ * Any stride of at least the row length is addressed: where h_strides[i] * h_i or canvas_stride times the rows of one march
+ * segment does not fit the 32-bit byte offsets of the marched canvas gather, the block gather (64-bit row addresses) writes the same bytes. */
 SR_API int sr_laplacian_blend(sr_blend_plan *plan, int dtype, void *const *h_d_tiles,
                               const int64_t *h_strides, uint8_t *d_canvas, int64_t canvas_stride,
                               float *d_canvas_f32);

@@ -488,6 +488,10 @@ class Context:
     def memset(self, ptr: int, value: int, nbytes: int):
         check(self.lib.sr_memset_d(self.handle, C.c_void_p(ptr), value, nbytes))
 
+    def copy_d2d(self, dst: int, src: int, nbytes: int):
+        """sr_memcpy_d2d: nbytes from one device address to another (rows of a strided view are copied one call each)."""
+        check(self.lib.sr_memcpy_d2d(self.handle, C.c_void_p(dst), C.c_void_p(src), int(nbytes)))
+
     # profiling ------------------------------------------------------------------------
     def prof_enable(self, on: bool = True):
         check(self.lib.sr_prof_enable(self.handle, 1 if on else 0))
@@ -606,12 +610,18 @@ class Context:
         return {"sse": out.sse, "ssim_uniform": out.ssim_uniform, "ssim_gauss": out.ssim_gauss,
                 "ssim_simple": out.ssim_simple}
 
-    def gray_std_u8(self, d_tiles, n, tile_bytes, stride, h, w, gray_shift=15, swap_rb=True) -> np.ndarray:
-        """np.std of the u8 gray image of n RGB tiles in HBM (from exact integer moments, float64)."""
+    def gray_moments_u8(self, d_tiles, n, tile_bytes, stride, h, w, gray_shift=15, swap_rb=True) -> np.ndarray:
+        """sr_gray_moments_u8 -> (n, 2) uint64: the exact sums of gray and gray^2 of n RGB u8 tiles in HBM (tile i at
+        d_tiles + i * tile_bytes, row stride in bytes)."""
         sums = np.zeros(2 * max(n, 1), dtype=np.uint64)
         check(self.lib.sr_gray_moments_u8(self.handle, C.c_void_p(d_tiles), int(n), int(tile_bytes), int(stride), int(h),
                                           int(w), int(gray_shift), 1 if swap_rb else 0,
                                           sums.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return sums[:2 * n].reshape(n, 2)
+
+    def gray_std_u8(self, d_tiles, n, tile_bytes, stride, h, w, gray_shift=15, swap_rb=True) -> np.ndarray:
+        """np.std of the u8 gray image of n RGB tiles in HBM (from exact integer moments, float64)."""
+        sums = self.gray_moments_u8(d_tiles, n, tile_bytes, stride, h, w, gray_shift, swap_rb).reshape(-1)
         cnt = float(h) * float(w)
         s1, s2 = sums[0:2 * n:2].astype(np.float64), sums[1:2 * n:2].astype(np.float64)
         m = s1 / cnt
@@ -823,14 +833,10 @@ def _feather_merge_np(self, arrays, descs, output_width: int, output_height: int
         raise ValueError("feather_merge_np: tiles must be all uint8 or all float32")
     es = 4 if is_f32 else 1
     bufs = [self.upload(a) for a in arrays]
-    mt = (MergeTile * n)(*[MergeTile(*[int(d[k]) for k in ("x", "y", "src_w", "src_h", "out_w", "out_h",
-                                                             "ov_t", "ov_b", "ov_l", "ov_r")]) for d in descs])
-    ptrs = (C.c_void_p * n)(*[C.c_void_p(b.ptr) for b in bufs])
-    st = (C.c_int64 * n)(*[a.shape[1] * 3 * es for a in arrays])
     canvas = self.alloc(output_width * output_height * 3)
     try:
-        check(self.lib.sr_feather_merge_dt(self.handle, SR_F32 if is_f32 else SR_U8, mt, n, ptrs, st, 1 if blending else 0,
-                                           C.c_void_p(canvas.ptr), output_width * 3, output_height, output_width))
+        self.feather_merge(SR_F32 if is_f32 else SR_U8, descs, [b.ptr for b in bufs], [a.shape[1] * 3 * es for a in arrays],
+                           blending, canvas.ptr, output_width * 3, output_height, output_width)
         return self.download(canvas.ptr, (output_height, output_width, 3), np.uint8)
     finally:
         self.sync()
@@ -839,6 +845,20 @@ def _feather_merge_np(self, arrays, descs, output_width: int, output_height: int
         canvas.free()
 
 
+def _feather_merge(self, dtype: int, descs, d_tiles: Sequence[int], strides: Sequence[int], blending: bool, d_canvas: int,
+                   canvas_stride: int, canvas_h: int, canvas_w: int):
+    """sr_feather_merge_dt on device pointers: tiles (SR_U8 / SR_F32, row strides in bytes) -> u8 canvas view.  descs are
+    dicts with the sr_merge_tile fields.  Asynchronous."""
+    n = len(descs)
+    mt = (MergeTile * max(n, 1))(*[MergeTile(*[int(d[k]) for k in ("x", "y", "src_w", "src_h", "out_w", "out_h",
+                                                                     "ov_t", "ov_b", "ov_l", "ov_r")]) for d in descs])
+    ptrs = (C.c_void_p * max(n, 1))(*[C.c_void_p(p) for p in d_tiles])
+    st = (C.c_int64 * max(n, 1))(*[int(s) for s in strides])
+    check(self.lib.sr_feather_merge_dt(self.handle, int(dtype), mt, n, ptrs, st, 1 if blending else 0, C.c_void_p(d_canvas),
+                                       int(canvas_stride), int(canvas_h), int(canvas_w)))
+
+
+Context.feather_merge = _feather_merge
 Context.feather_merge_np = _feather_merge_np
 
 

@@ -3006,6 +3006,11 @@ static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // (an even number: an odd last cell row is left to the rectangles).
 // cover: [cell row][word of 32 cell columns] bits of the marched cells (row pitch nbx_r words).
 // ---------------------------------------------------------------------------------------------
+// The marched kernels' byte offsets are 32-bit (buffer instructions): one item of at most MARCH_SEG steps spans
+// 2 MARCH_SEG + 2 canvas rows, and the column offset the instruction adds stays below one more row; offsets stay below
+// MARCH_OFF_LIMIT.  plan_march applies the bound to what it knows (arena, dense fp32 canvas), blend_gather to the strides.
+static constexpr unsigned long long MARCH_SPAN_ROWS = 2ull * MARCH_SEG + 3ull, MARCH_OFF_LIMIT = 0xFFFF0000ull;
+
 static void plan_march(const sr_blend_plan *P, int nbx_r, int nby_r, std::vector<MarchItem> (&items)[MARCH_NT + 1],
                        std::vector<unsigned> &cover)
 {
@@ -3014,7 +3019,7 @@ static void plan_march(const sr_blend_plan *P, int nbx_r, int nby_r, std::vector
     const int CPB = FU_BH / 2;                                 // cell rows per regular block
     cover.assign((size_t)nbx_r * nby_r * CPB, 0u);                         // [cell row][block column]: cell column bits (1 = marched)
     // the marched kernels address the arena and a tile's pixels with 32-bit byte offsets (buffer instructions)
-    bool fits32 = P->arena_floats * sizeof(float) < 0xFFFF0000ull && (unsigned long long)cw * P->cn * 4ull * (2 * 64 + 2) < 0xFFFF0000ull;
+    bool fits32 = P->arena_floats * sizeof(float) < MARCH_OFF_LIMIT && (unsigned long long)cw * P->cn * 4ull * MARCH_SPAN_ROWS < MARCH_OFF_LIMIT;
     for (int t = 0; t < n && fits32; ++t) fits32 = (unsigned long long)P->tiles[t].h * P->tiles[t].w * P->cn * 4ull < 0x7FFF0000ull;
     // The march is four launches of long work items: it wins on a big canvas (200 MP: 1.12 against 1.22 ms for the block kernel
     // alone) and loses on a small one, where every launch is a few short items deep -- a rank's strip of a world of 4 / 8:
@@ -4283,9 +4288,17 @@ static int blend_gather(sr_blend_plan *P, bool lap, int dtype, void *const *h_d_
             const int nbx_r = std::max((P->canvas_w + FU_BW - 1) / FU_BW, 1), nby_r = std::max((rows + FU_BH - 1) / FU_BH, 1);
             const int n_edge = P->n_fedge_blocks;
             // the marched zones first (long work items), then what is left; float tiles take the block kernel everywhere
-            const bool marched = dtype == SR_U8 && P->n_march_total > 0;
+            // The marched kernels form 32-bit byte offsets from the strides, which are known only here: a tile row as
+            // (unsigned)ly * (unsigned)stride (ly < h), a canvas row as (unsigned)cstride advanced by 2 * cstride per step of an
+            // item of at most MARCH_SEG steps.  A stride that does not fit (or is not positive) takes k_final_fused, whose row
+            // addresses are 64-bit products, for the whole canvas: the same values from the same expressions.  (The bounds
+            // leave room for the column offset the buffer instruction adds to the row's: one more canvas row, 64 KiB of a tile.)
+            bool marched = dtype == SR_U8 && P->n_march_total > 0 &&
+                           (unsigned long long)canvas_stride * MARCH_SPAN_ROWS < MARCH_OFF_LIMIT;
+            for (int t = 0; t < P->n && marched; ++t)
+                marched = h_strides[t] > 0 && (unsigned long long)h_strides[t] * (unsigned long long)P->tiles[t].h < MARCH_OFF_LIMIT;
             const unsigned arena_bytes = (unsigned)std::min<size_t>(P->arena_floats * sizeof(float), 0xFFFFFFFFu);
-            if (dtype == SR_U8 && P->n_march_items[1] > 0) {
+            if (marched && P->n_march_items[1] > 0) {
                 ProfScope ps2(ctx, "gather_march1");
                 if (P->cn == 3)
                     hipLaunchKernelGGL((k_final_march1<3>), dim3((unsigned)P->n_march_items[1]), dim3(64), 0, ctx->stream, P->d_march_items[1],
@@ -4299,7 +4312,7 @@ static int blend_gather(sr_blend_plan *P, bool lap, int dtype, void *const *h_d_
                        P->d_march_items[NTV], P->d_fdesc, P->d_arena, arena_bytes, P->d_luts, d_canvas,                      \
                        (long long)canvas_stride, d_canvas_f32, P->canvas_w)
             static_assert(MARCH_NT == 4, "the tile counts launched here");
-            for (int nt = 2; nt <= MARCH_NT && dtype == SR_U8; ++nt) {
+            for (int nt = 2; nt <= MARCH_NT && marched; ++nt) {
                 if (P->n_march_items[nt] <= 0) continue;
                 ProfScope ps2(ctx, nt == 2 ? "gather_march2" : (nt == 3 ? "gather_march3" : "gather_march4"));
                 if (P->cn == 3) { if (nt == 2) LAUNCH_MARCHN(3, 2); else if (nt == 3) LAUNCH_MARCHN(3, 3); else LAUNCH_MARCHN(3, 4); }
