@@ -495,6 +495,31 @@ SR_API int sr_assess_resized_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_
                                 double data_range, int flags, sr_assess_sums *h_out);
 /* number of SSIM-map samples of `mode` inside rows [row_begin,row_end) (host only) */
 SR_API int sr_ssim_count(int h, int w, int mode, int row_begin, int row_end, uint64_t *count);
+/* Per-cell quality map (csrc/sr_qmap.hip; no reference counterpart: the reference's UI shows a difference heat-map it never
+ * computes).  The squared error and the SSIM maps of sr_assess_u8, binned into the cells of a separable grid given as two
+ * strictly increasing host edge lists h_xedges[0..gw] (0 .. w) and h_yedges[0..gh] (0 .. h): cell (gy, gx) is rows
+ * [ye[gy], ye[gy+1]) x columns [xe[gx], xe[gx+1]).  A cell is a bin for results, not a crop of the input -- the filters read
+ * across cell boundaries -- so the cells add up to the global sums: sse exactly, the SSIM sums up to the order of the fp64
+ * additions.  h_out: gh * gw records, row-major; sse = the exact sum of (a - b)^2 over the cell's pixels and channels, each
+ * ssim_* = the fp64 sum of that variant's SSIM-map samples whose position lies in the cell and in the variant's valid region
+ * (uniform-7: cropped by 3, gauss-11: by 5, simple: the whole map); fields not selected by `flags` (sr_assess_flags) are 0,
+ * a cell without a valid sample has sum 0.  Divide by sr_quality_map_counts / the cell's pixels * cn.  No floating-point
+ * atomics: equal inputs give equal bits.  Synchronous; the workspace (about h / 128 + gh rows of w 8-byte words per selected
+ * sum) is allocated and freed inside.  SR_ERR_INVALID_ARG for edges that are not strictly increasing or do not span the side,
+ * gw or gh < 1, cn not 1 or 3, unknown flag bits; every argument is checked before any device work. */
+typedef struct sr_quality_cell {
+    uint64_t sse;
+    double ssim_uniform;
+    double ssim_gauss;
+    double ssim_simple;
+} sr_quality_cell;
+SR_API int sr_quality_map_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b,
+                             int h, int w, int cn, int gray_shift, double data_range, const int *h_xedges, int gw,
+                             const int *h_yedges, int gh, int flags, sr_quality_cell *h_out);
+/* number of valid SSIM-map samples of `mode` per cell, in closed form (host only): counts[gh * gw], row-major; their total
+ * is sr_ssim_count(h, w, mode, 0, h) */
+SR_API int sr_quality_map_counts(int h, int w, int mode, const int *h_xedges, int gw, const int *h_yedges, int gh,
+                                 uint64_t *counts);
 /* cv2.cvtColor(RGB2GRAY) on u8 (quality_assessment_module.py:359-360) */
 SR_API int sr_rgb2gray_u8(sr_ctx *ctx, const uint8_t *d_rgb, int64_t stride, int h, int w,
                           int gray_shift, uint8_t *d_gray, int64_t gray_stride);

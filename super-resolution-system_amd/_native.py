@@ -56,6 +56,12 @@ class AssessSums(C.Structure):
 
 
 ASSESS_SSE, ASSESS_UNIFORM7, ASSESS_GAUSS11, ASSESS_SIMPLE, ASSESS_ALL = 1, 2, 4, 8, 15
+
+
+class QualityCell(C.Structure):
+    _fields_ = [("sse", C.c_uint64), ("ssim_uniform", C.c_double), ("ssim_gauss", C.c_double), ("ssim_simple", C.c_double)]
+
+
 # metric bits of sr_commercial_u8 (include/sr_hip.h)
 (CM_LAPG, CM_NOISE, CM_SOBEL, CM_MSCN, CM_TEX, CM_LAB, CM_SKIN, CM_RGB, CM_BLOCKS, CM_REGIONS, CM_CANNY,
  CM_HF) = (1 << i for i in range(12))
@@ -164,6 +170,8 @@ SIGNATURES = {
     "sr_assess_resized_u8_async": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _dbl, _i, _vp]),
     "sr_assess_resized_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _dbl, _i, C.POINTER(AssessSums)]),
     "sr_ssim_count": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_uint64)]),
+    "sr_quality_map_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _dbl, _pi, _i, _pi, _i, _i, C.POINTER(QualityCell)]),
+    "sr_quality_map_counts": (_i, [_i, _i, _i, _pi, _i, _pi, _i, C.POINTER(C.c_uint64)]),
     "sr_rgb2gray_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
     "sr_resize_cubic_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i]),
     "sr_resize_cubic_window_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64]),
@@ -410,6 +418,27 @@ def ssim_count(h: int, w: int, mode: str, row_begin: int = 0, row_end: Optional[
     return n.value
 
 
+def _edge_array(edges, name: str):
+    """An edge list as a C int array; anything that is not a flat list of at least two whole numbers is a ValueError."""
+    e = np.asarray(edges)
+    if e.ndim != 1 or e.size < 2 or e.dtype.kind not in "iu":
+        raise ValueError(f"{name}: need a flat list of at least two integer edges")
+    if e.min() < -2 ** 31 or e.max() >= 2 ** 31:
+        raise ValueError(f"{name}: edge out of range")
+    return (C.c_int * e.size)(*[int(v) for v in e]), int(e.size) - 1
+
+
+def quality_map_counts(h: int, w: int, mode: str, x_edges, y_edges) -> np.ndarray:
+    """Host-only: (gh, gw) uint64 numbers of valid SSIM-map samples of `mode` per cell of the separable grid
+    (sr_quality_map_counts).  ValueError for edges that are not strictly increasing from 0 to w / h."""
+    xe, gw = _edge_array(x_edges, "x_edges")
+    ye, gh = _edge_array(y_edges, "y_edges")
+    out = np.zeros((gh, gw), dtype=np.uint64)
+    check(load().sr_quality_map_counts(int(h), int(w), SSIM_MODES[mode], xe, gw, ye, gh,
+                                       out.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return out
+
+
 def psnr_from_sse(sse: int, count: int, data_range: float = 255.0) -> float:
     return float(load().sr_psnr_from_sse(C.c_uint64(sse), C.c_uint64(count), data_range))
 
@@ -600,6 +629,31 @@ class Context:
                                     C.byref(out)))
         return {"sse": out.sse, "ssim_uniform": out.ssim_uniform, "ssim_gauss": out.ssim_gauss,
                 "ssim_simple": out.ssim_simple}
+
+    def quality_map_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, x_edges, y_edges, flags=ASSESS_ALL, gray_shift=15,
+                       data_range=255.0) -> dict:
+        """sr_quality_map_u8: the assess_u8 sums per cell of the separable grid x_edges x y_edges -> (gh, gw) arrays 'sse'
+        (uint64, exact) and 'ssim_uniform' / 'ssim_gauss' / 'ssim_simple' (float64 sums over the cell's valid samples;
+        divide by quality_map_counts).  Every argument is checked before the device is touched (ValueError)."""
+        if cn not in (1, 3):
+            raise ValueError("quality_map_u8: need 1 or 3 channels")
+        if gray_shift not in (14, 15):
+            raise ValueError("quality_map_u8: gray_shift must be 14 or 15")
+        if int(flags) & ~ASSESS_ALL:
+            raise ValueError(f"quality_map_u8: unknown flag bits 0x{int(flags) & ~ASSESS_ALL:x}")
+        if h < 1 or w < 1:
+            raise ValueError("quality_map_u8: need h, w >= 1")
+        xe, gw = _edge_array(x_edges, "x_edges")
+        ye, gh = _edge_array(y_edges, "y_edges")
+        probe = np.zeros(gh * gw, dtype=np.uint64)                      # the library's own edge check, host only
+        check(load().sr_quality_map_counts(int(h), int(w), SSIM_MODES["simple"], xe, gw, ye, gh,
+                                           probe.ctypes.data_as(C.POINTER(C.c_uint64))))
+        recs = (QualityCell * (gh * gw))()
+        check(self.lib.sr_quality_map_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h),
+                                         int(w), int(cn), int(gray_shift), float(data_range), xe, gw, ye, gh, int(flags), recs))
+        arr = np.frombuffer(recs, dtype=np.dtype([("sse", "<u8"), ("ssim_uniform", "<f8"), ("ssim_gauss", "<f8"),
+                                                  ("ssim_simple", "<f8")])).reshape(gh, gw)
+        return {k: np.ascontiguousarray(arr[k]) for k in ("sse", "ssim_uniform", "ssim_gauss", "ssim_simple")}
 
     def assess_resized_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, dst_h, dst_w, flags=ASSESS_SSE | ASSESS_UNIFORM7,
                           gray_shift=15, data_range=255.0) -> dict:

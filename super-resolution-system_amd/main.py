@@ -61,6 +61,7 @@ class PipelineConfig:
     volc_sk: str = ""
     volc_region: str = "cn-beijing"
     sr_scale: int = 2          # the reference hard-codes 2 (main.py:217,322)
+    qa_map_cell: int = 0       # > 0 (with enable_qa): stage 4 also writes a per-cell quality map of this cell size
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
                                    # only the canvas comes back for the writer (a custom sr_backend gets host arrays)
 
@@ -147,6 +148,67 @@ class SuperResolutionPipeline:
             with open(output_path.rsplit('.', 1)[0] + '_qa_report.json', 'w', encoding='utf-8') as f:
                 json.dump(report, f, indent=2, ensure_ascii=False, default=str)
 
+    def _quality_map(self, ctx, d_src: int, src_shape, d_canvas: int, canvas_shape, tiles: List[Tile],
+                     output_path: str) -> Dict[str, Any]:
+        """Stage 4's optional 'quality_map' section (qa_map_cell > 0): where the canvas differs from the INTER_CUBIC resize
+        of the source to the canvas size -- per uniform cell of qa_map_cell pixels and per tile (its ownership region,
+        tile_cell_edges).  Both images are in HBM; the resize goes into a temporary.  Also writes <name>_qa_map.png, a
+        gh x gw gray image of floor(255 * clip(ms_ssim, 0, 1)) (0 for a cell without a valid sample).  One helper for the
+        device-resident, the host-array and the sharded path."""
+        import _native
+        from tiling_module import tile_cell_edges
+        qm = self.quality_module
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        ih, iw = int(src_shape[0]), int(src_shape[1])
+        ref = ctx.alloc(H * W * cn)
+        try:
+            ctx.resize_cubic_u8(d_src, iw * cn, ih, iw, cn, ref.ptr, W * cn, H, W)
+            m = qm.evaluate_quality_map_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn), cell=int(self.config.qa_map_cell))
+            try:
+                pos = [(t.metadata.global_x, t.metadata.global_y, 0, 0) for t in tiles]
+                xe, ye = tile_cell_edges(pos, self.tiling_module.overlap_pixels, self.config.sr_scale, W, H)
+                t = qm.evaluate_quality_map_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn), x_edges=xe, y_edges=ye)
+            except ValueError as exc:
+                t, tiles_section = None, {"available": False, "note": str(exc)}
+        finally:
+            ctx.sync()
+            ref.free()
+
+        def num(v):
+            v = float(v)
+            return None if v != v else v
+
+        def rows(a):
+            return [[num(v) for v in r] for r in a]
+
+        def rect(mm, gy, gx):
+            x0, y0 = mm["x_edges"][gx], mm["y_edges"][gy]
+            return [x0, y0, mm["x_edges"][gx + 1] - x0, mm["y_edges"][gy + 1] - y0]
+
+        gh, gw = m["ms_ssim"].shape
+        ms = m["ms_ssim"]
+        order = [i for i in np.argsort(np.where(np.isnan(ms), np.inf, ms), axis=None, kind="stable") if not np.isnan(ms.flat[i])]
+        worst = [{"gy": int(i // gw), "gx": int(i % gw), "rect": rect(m, int(i // gw), int(i % gw)),
+                  "ms_ssim": num(ms.flat[i]), "ssim": num(m["ssim"].flat[i]), "psnr": num(m["psnr"].flat[i])} for i in order[:5]]
+        if t is not None:
+            ncol = len(t["x_edges"]) - 1
+            col = {x: c for c, x in enumerate(sorted({p[0] for p in pos}))}
+            row = {y: r for r, y in enumerate(sorted({p[1] for p in pos}))}
+            tiles_section = []
+            for i, p in enumerate(pos):                                # list order = the order of split_image's tiles
+                gy, gx = row[p[1]], col[p[0]]
+                tiles_section.append({"index": i, "row": gy, "col": gx, "rect": rect(t, gy, gx),
+                                      "psnr": num(t["psnr"][gy, gx]), "ssim": num(t["ssim"][gy, gx]),
+                                      "ms_ssim": num(t["ms_ssim"][gy, gx])})
+            assert len(tiles_section) == ncol * (len(t["y_edges"]) - 1)
+        png = output_path.rsplit('.', 1)[0] + '_qa_map.png'
+        Path(png).parent.mkdir(parents=True, exist_ok=True)
+        gray = np.floor(255.0 * np.clip(np.nan_to_num(ms, nan=0.0), 0.0, 1.0)).astype(np.uint8)
+        _native.write_image(gray, png, png_level=3)
+        return {"cell": int(self.config.qa_map_cell), "grid": [int(gh), int(gw)], "x_edges": m["x_edges"], "y_edges": m["y_edges"],
+                "sse": [[int(v) for v in r] for r in m["sse"]], "psnr": rows(m["psnr"]), "ssim": rows(m["ssim"]),
+                "ms_ssim": rows(ms), "worst_cells": worst, "image": os.path.basename(png), "tiles": tiles_section}
+
     @staticmethod
     def _commercial(evaluate) -> Dict[str, Any]:
         """Stage 4's commercial section (main.py:369-386 of the reference); a canvas with a side beyond the hand-written
@@ -208,6 +270,8 @@ class SuperResolutionPipeline:
                           'commercial': self._commercial(lambda: self.quality_module.evaluate_commercial_device(
                               canvas.ptr, (H, W, 3), roi_regions or [])),
                           'timestamp': datetime.now().isoformat()}
+                if self.config.qa_map_cell > 0:
+                    report['quality_map'] = self._quality_map(ctx, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3), tiles, output_path)
                 score = qa.get('overall_score', 0)
             lap("assess")
             # Stage 5: the one download, then the writer
@@ -298,6 +362,9 @@ class SuperResolutionPipeline:
                               'commercial': self._commercial(lambda: self.quality_module.evaluate_commercial_device(
                                   canvas.data_ptr(), (H, W, 3), roi_regions or [])),
                               'timestamp': datetime.now().isoformat()}
+                    if self.config.qa_map_cell > 0:
+                        report['quality_map'] = self._quality_map(qctx, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3),
+                                                                  tiles, output_path)
                     score = qa.get('overall_score', 0)
                 fused = qctx.download(canvas.data_ptr(), (H, W, 3), np.uint8)
                 self._write_outputs(fused, output_path, report)
@@ -370,6 +437,14 @@ class SuperResolutionPipeline:
                 report = {'full_reference': qa,
                           'commercial': self._commercial(lambda: self.quality_module.evaluate_commercial(fused, roi_regions or [])),
                           'timestamp': datetime.now().isoformat()}
+                if self.config.qa_map_cell > 0:
+                    qctx = self.quality_module._ctx()
+                    d_src, d_fused = qctx.upload(original), qctx.upload(fused)
+                    try:
+                        report['quality_map'] = self._quality_map(qctx, d_src.ptr, original.shape, d_fused.ptr, fused.shape,
+                                                                  tiles, output_path)
+                    finally:
+                        d_src.free(); d_fused.free()
                 score = qa.get('overall_score', 0)
             # Stage 5: output
             self._write_outputs(fused, output_path, report)

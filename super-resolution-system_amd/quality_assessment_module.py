@@ -402,6 +402,80 @@ class QualityAssessmentModule:
         finally:
             d_o.free(); d_u.free()
 
+    # -- per-cell quality map (no reference counterpart: the reference's UI shows a heat-map it never computes) ----------
+    @staticmethod
+    def _map_edges(h: int, w: int, cell: Optional[int], x_edges, y_edges) -> Tuple[List[int], List[int]]:
+        """The grid of a quality map: uniform cells of `cell` pixels (None: 256; the last row / column is smaller when
+        `cell` does not divide the side) or the two edge lists.  Host only; ValueError for anything else."""
+        if (x_edges is None) != (y_edges is None):
+            raise ValueError("quality map: give both x_edges and y_edges, or neither")
+        if x_edges is not None:
+            if cell is not None:
+                raise ValueError("quality map: give either cell or the edge lists, not both")
+            xe, ye = [int(v) for v in x_edges], [int(v) for v in y_edges]
+            if any(int(v) != v for v in list(x_edges) + list(y_edges)):
+                raise ValueError("quality map: edges must be whole numbers")
+        else:
+            cell = 256 if cell is None else cell
+            if int(cell) != cell or cell < 1:
+                raise ValueError(f"quality map: cell must be a whole number >= 1, got {cell!r}")
+            cell = int(cell)
+            xe = list(range(0, w, cell)) + [w]
+            ye = list(range(0, h, cell)) + [h]
+        _native.quality_map_counts(h, w, "simple", xe, ye)              # the library's own edge check (host only)
+        return xe, ye
+
+    def evaluate_quality_map(self, img1: np.ndarray, img2: np.ndarray, cell: Optional[int] = None, x_edges=None,
+                             y_edges=None) -> Dict[str, Any]:
+        """Where the quality is bad: PSNR and SSIM per cell of a separable grid over the common top-left rectangle of the
+        two images (preprocessing, u8 requirement and channel-layout check of calculate_psnr / calculate_ssim).  The grid
+        is uniform cells of `cell` pixels (default 256) or the edge lists x_edges (0 .. W) / y_edges (0 .. H).  Returns
+        x_edges, y_edges and (gh, gw) arrays: sse, mse, psnr (inf where mse == 0), ssim / ms_ssim (per-cell means with the
+        branch rule of evaluate_full_reference: uniform / gauss for ssim_branch 'A', simple / simple for 'B'; nan for a cell
+        without a valid sample) and ssim_count / ms_ssim_count.  Cells are bins for results: the filters read across their
+        boundaries, so sums over the cells give the global metrics."""
+        a, b = self._pair(img1, img2, "evaluate_quality_map")
+        if a.ndim == 3 and a.shape[2] not in (1, 3):
+            raise ValueError("evaluate_quality_map: colour images must have 3 channels (cv2.COLOR_RGB2GRAY)")
+        h, w = min(a.shape[0], b.shape[0]), min(a.shape[1], b.shape[1])
+        xe, ye = self._map_edges(h, w, cell, x_edges, y_edges)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._quality_map_dev(da, db, xe, ye)
+        finally:
+            da.free(); db.free()
+
+    def evaluate_quality_map_device(self, d_img1: int, shape1, d_img2: int, shape2, cell: Optional[int] = None, x_edges=None,
+                                    y_edges=None) -> Dict[str, Any]:
+        """evaluate_quality_map on two dense u8 images that already live in HBM (device addresses + shapes)."""
+        shape1, shape2 = tuple(int(v) for v in shape1), tuple(int(v) for v in shape2)
+        if len(shape1) not in (2, 3) or len(shape1) != len(shape2) or (len(shape1) == 3 and shape1[2] != shape2[2]):
+            raise ValueError(f"evaluate_quality_map: images have different channel layouts {shape1} vs {shape2}")
+        if len(shape1) == 3 and shape1[2] not in (1, 3):
+            raise ValueError("evaluate_quality_map: colour images must have 3 channels (cv2.COLOR_RGB2GRAY)")
+        h, w = min(shape1[0], shape2[0]), min(shape1[1], shape2[1])
+        xe, ye = self._map_edges(h, w, cell, x_edges, y_edges)
+        ctx = self._ctx()
+        return self._quality_map_dev(_DevImage(ctx, shape=shape1, ptr=d_img1), _DevImage(ctx, shape=shape2, ptr=d_img2), xe, ye)
+
+    def _quality_map_dev(self, a: _DevImage, b: _DevImage, xe: List[int], ye: List[int]) -> Dict[str, Any]:
+        h, w, cn = min(a.h, b.h), min(a.w, b.w), a.cn
+        if self.ssim_branch == 'B':
+            flags, m1, m2 = _native.ASSESS_SSE | _native.ASSESS_SIMPLE, "simple", "simple"
+        else:
+            flags, m1, m2 = _native.ASSESS_SSE | _native.ASSESS_UNIFORM7 | _native.ASSESS_GAUSS11, "uniform", "gauss"
+        r = a.ctx.quality_map_u8(a.ptr, a.stride, b.ptr, b.stride, h, w, cn, xe, ye, flags=flags, gray_shift=self.gray_shift)
+        n1, n2 = _native.quality_map_counts(h, w, m1, xe, ye), _native.quality_map_counts(h, w, m2, xe, ye)
+        elems = np.outer(np.diff(ye), np.diff(xe)).astype(np.float64) * cn
+        mse = r["sse"].astype(np.float64) / elems
+        with np.errstate(divide="ignore", invalid="ignore"):
+            psnr = np.where(mse == 0, np.inf, 10.0 * np.log10(255.0 ** 2 / mse))
+            ssim = np.where(n1 > 0, r[f"ssim_{m1}"] / n1, np.nan)
+            ms_ssim = np.where(n2 > 0, r[f"ssim_{m2}"] / n2, np.nan)
+        return {"x_edges": list(xe), "y_edges": list(ye), "sse": r["sse"], "mse": mse, "psnr": psnr, "ssim": ssim,
+                "ms_ssim": ms_ssim, "ssim_count": n1, "ms_ssim_count": n2}
+
     def _downsample_comparison_dev(self, d_o: _DevImage, d_u: _DevImage) -> Dict[str, float]:
         out = {}
         for scale in self.scale_config.scale_factors:

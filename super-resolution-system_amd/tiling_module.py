@@ -365,6 +365,30 @@ def _load_rgb(image_path: str) -> np.ndarray:
         raise ValueError(f"无法加载图像: {image_path}") from exc
 
 
+def tile_cell_edges(positions, overlap_px: int, scale: int, W: int, H: int) -> Tuple[List[int], List[int]]:
+    """One quality-map cell per tile: the (x_edges, y_edges) of the tiles' ownership regions on the W x H canvas.
+
+    ``positions`` are the input-space (x, y, w, h) of the uniform grid of ``_calculate_tile_positions``.  The cut between
+    tile column c - 1 and c lies in the middle of their overlap, at ``scale * x_c + (scale * overlap_px) // 2``; rows
+    likewise; the first edge is 0 and the last W / H.  Host only.  Anything that is not the full product of its column and
+    row positions (a k-d tiling, a list with holes) raises ValueError, as do cuts that do not increase inside the canvas."""
+    pos = [(int(p[0]), int(p[1])) for p in positions]
+    xs, ys = sorted({x for x, _ in pos}), sorted({y for _, y in pos})
+    if not pos or len(pos) != len(xs) * len(ys) or set(pos) != {(x, y) for y in ys for x in xs}:
+        raise ValueError("tile_cell_edges: the tiles are not a uniform grid (one tile per column and row position)")
+    if overlap_px < 0 or scale < 1 or xs[0] != 0 or ys[0] != 0:
+        raise ValueError("tile_cell_edges: need overlap_px >= 0, scale >= 1 and a grid that starts at (0, 0)")
+    half = (int(scale) * int(overlap_px)) // 2
+
+    def edges(starts, size, axis):
+        e = [0] + [int(scale) * s + half for s in starts[1:]] + [int(size)]
+        if any(b <= a for a, b in zip(e, e[1:])):
+            raise ValueError(f"tile_cell_edges: the {axis} cuts {e} do not increase inside the canvas")
+        return e
+
+    return edges(xs, W, "x"), edges(ys, H, "y")
+
+
 class TilingModule:
     """Overlap tiling of an image and feather re-assembly (tiling_module.py:428-1217)."""
 
