@@ -586,6 +586,37 @@ SR_API int sr_lpips_tile_count(int h, int w, int tile, int *n_tiles);
 SR_API int sr_lpips_u8(sr_lpips_model *model, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b,
                        int h, int w, int cn, int tile, int tile_begin, int tile_end, double *h_layer_sums);
 
+/* ---- local SR backend: compact "VGG-style" SR network (csrc/sr_srnet.hip) ------------------------------------------------
+ * Stage 2 of the reference is a remote API client (main.py:194-267); this is a local learned upscaler of the family
+ * Real-ESRGAN ships as SRVGGNetCompact, restated (parity with that package is unpinned: neither it nor a checkpoint exists
+ * offline).  Layers k = 0 .. D + 1 are 3 x 3, stride 1, zero padding 1 at the image border, with bias, all fp32:
+ * layer 0 maps x = u8 / 255 (3 channels) to F, layers 1 .. D map F to F, each followed by y >= 0 ? y : slope[c] * y, and
+ * layer D + 1 maps F to 3 s^2 without activation.  The output is
+ *     o[c, Y, X] = t[c s^2 + (Y % s) s + (X % s), Y / s, X / s] + x[c, Y / s, X / s]
+ * (PixelShuffle(s) plus the nearest-upsampled input), written as HWC fp32 unclamped (sr_srnet_f32) or as HWC u8
+ * rintf(fminf(fmaxf(o, 0), 1) * 255) (sr_srnet_u8).  F in {64, 128, 192, 256}, 0 <= D <= 64, s in {1, 2, 3, 4}; anything
+ * else is SR_ERR_UNSUPPORTED, decided on the host before any device call.
+ * sr_srnet_create: h_w[k] = weights of layer k, dense OIHW fp32; h_b[k] its bias (k = 0 .. D + 1); h_slope[k] the F slopes
+ * after layer k (k = 0 .. D; ReLU is all zeros, LeakyReLU a constant, PReLU learned).  The arrays are re-laid and uploaded.
+ * sr_srnet_plan (host only, no context, no GPU): the image is streamed in tile x tile sub-tiles of the INPUT (tile 0: the
+ * library's choice, 2048), each recomputing a halo of *halo = D + 2 input pixels; *n_tiles sub-tiles; *workspace_bytes =
+ * the model's two planar F-channel fp32 buffers of one padded sub-tile (side min(tile, side) + 2 halo clipped to the image,
+ * rows padded to 4 floats).  Outputs may be NULL.
+ * sr_srnet_u8 / sr_srnet_f32: d_src h x w x 3 u8, d_dst (h s) x (w s) x 3; strides in bytes (fp32: a multiple of 4).
+ * SR_ERR_INVALID_ARG for null pointers and a tile < 0, SR_ERR_SHAPE for h or w < 1, a stride shorter than a row, an output
+ * size beyond int or a sub-tile too large for 32-bit offsets -- all before any launch.  Fixed summation order that does not
+ * depend on the sub-tile: every tile size gives the same bits.  Asynchronous. */
+typedef struct sr_srnet_model sr_srnet_model;
+SR_API int sr_srnet_create(sr_ctx *ctx, int n_feat, int n_body, int scale, const float *const *h_w, const float *const *h_b,
+                           const float *const *h_slope, sr_srnet_model **out);
+SR_API int sr_srnet_destroy(sr_srnet_model *model);
+SR_API int sr_srnet_plan(int h, int w, int n_feat, int n_body, int scale, int tile, int *halo, int *n_tiles,
+                         size_t *workspace_bytes);
+SR_API int sr_srnet_u8(sr_srnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                       int64_t dst_stride, int tile);
+SR_API int sr_srnet_f32(sr_srnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                        int64_t dst_stride, int tile);
+
 #ifdef __cplusplus
 }
 #endif

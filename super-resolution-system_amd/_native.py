@@ -187,6 +187,11 @@ SIGNATURES = {
     "sr_lpips_layer_sizes": (_i, [_i, _i, _i, _pi]),
     "sr_lpips_tile_count": (_i, [_i, _i, _i, _pi]),
     "sr_lpips_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(_dbl)]),
+    "sr_srnet_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "sr_srnet_destroy": (_i, [_vp]),
+    "sr_srnet_plan": (_i, [_i, _i, _i, _i, _i, _i, _pi, _pi, C.POINTER(_sz)]),
+    "sr_srnet_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_srnet_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
 }
 
 
@@ -1184,6 +1189,75 @@ class LpipsModel:
     def close(self):
         if getattr(self, "handle", None):
             self.ctx.lib.sr_lpips_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+# ------------------------------------------------------------------------------------------
+# local SR network (sr_srnet_*): caller-supplied weights; sr_network.CompactSRNet parses state dicts into these arrays
+# ------------------------------------------------------------------------------------------
+def _check_unsupported(rc: int) -> None:
+    """SR_ERR_UNSUPPORTED -> NotImplementedError, everything else as check()."""
+    if rc == SR_ERR_UNSUPPORTED:
+        raise NotImplementedError(last_error())
+    check(rc)
+
+
+def srnet_plan(h: int, w: int, n_feat: int, n_body: int, scale: int, tile: int = 0) -> Tuple[int, int, int]:
+    """sr_srnet_plan (host only) -> (halo, sub-tiles, workspace bytes)."""
+    halo, n, ws = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check_unsupported(load().sr_srnet_plan(int(h), int(w), int(n_feat), int(n_body), int(scale), int(tile), C.byref(halo),
+                                            C.byref(n), C.byref(ws)))
+    return halo.value, n.value, int(ws.value)
+
+
+class SrNetModel:
+    """sr_srnet_model: the compact SR network resident on the GPU.  weights / biases: D + 2 arrays in layer order (OIHW fp32),
+    slopes: D + 1 arrays of F values."""
+
+    def __init__(self, ctx: Context, n_feat: int, n_body: int, scale: int, weights, biases, slopes):
+        n_feat, n_body, scale = int(n_feat), int(n_body), int(scale)
+        srnet_plan(1, 1, n_feat, n_body, scale)                  # the supported range, refused before any array is touched
+        if len(weights) != n_body + 2 or len(biases) != n_body + 2 or len(slopes) != n_body + 1:
+            raise ValueError(f"SR network with {n_body} body convolutions needs {n_body + 2} weight / bias arrays and {n_body + 1} slope vectors")
+        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
+        bs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in biases]
+        ss = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in slopes]
+        for k, (w, b) in enumerate(zip(ws, bs)):
+            want = (3 * scale * scale if k == n_body + 1 else n_feat, 3 if k == 0 else n_feat, 3, 3)
+            if w.shape != want or b.shape != (want[0],):
+                raise ValueError(f"SR network layer {k}: expected {want} / {(want[0],)}, got {w.shape} / {b.shape}")
+        if any(s.shape != (n_feat,) for s in ss):
+            raise ValueError(f"SR network slopes must hold {n_feat} values each")
+        self.ctx, self.n_feat, self.n_body, self.scale = ctx, n_feat, n_body, scale
+        pw = (C.c_void_p * len(ws))(*[a.ctypes.data for a in ws])
+        pb = (C.c_void_p * len(bs))(*[a.ctypes.data for a in bs])
+        ps = (C.c_void_p * len(ss))(*[a.ctypes.data for a in ss])
+        h = C.c_void_p()
+        _check_unsupported(ctx.lib.sr_srnet_create(ctx.handle, n_feat, n_body, scale, pw, pb, ps, C.byref(h)))
+        self.handle = h
+
+    def plan(self, h: int, w: int, tile: int = 0) -> Tuple[int, int, int]:
+        return srnet_plan(h, w, self.n_feat, self.n_body, self.scale, tile)
+
+    def upscale_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0):
+        """sr_srnet_u8: h x w x 3 u8 -> (h s) x (w s) x 3 u8, HBM -> HBM.  Asynchronous."""
+        check(self.ctx.lib.sr_srnet_u8(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
+                                       int(dst_stride), int(tile)))
+
+    def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0):
+        """sr_srnet_f32: the unclamped fp32 output (HWC, stride in bytes).  Asynchronous."""
+        check(self.ctx.lib.sr_srnet_f32(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
+                                        int(dst_stride), int(tile)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.sr_srnet_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

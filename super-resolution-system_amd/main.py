@@ -5,7 +5,8 @@ Keeps the reference's names, config fields and defaults, result record and five-
 (main.py:47-89,92-134,157-192,269-441).  Stages 1, 3 and 4 (tile -> blend -> assess) run on the GPU
 through tiling_module / blending_module / quality_assessment_module.  Stage 2 of the reference is a
 remote vendor API (out of scope): here it is a pluggable ``sr_backend`` whose default
-is the bicubic stub of BASELINE.json's configs, executed on the GPU with the resize kernel.
+is the bicubic stub of BASELINE.json's configs, executed on the GPU with the resize kernel; with
+``PipelineConfig.sr_weights`` set it is the local compact SR network of sr_network.py (caller-supplied weights).
 
 What is wired differently from the reference, because the reference's own wiring cannot run
 (SURVEY.md 0.3): tiles are read from ``tile.data``; ``TileInfo(image, x, y, row, col)`` is built with
@@ -64,6 +65,9 @@ class PipelineConfig:
     qa_map_cell: int = 0       # > 0 (with enable_qa): stage 4 also writes a per-cell quality map of this cell size
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
                                    # only the canvas comes back for the writer (a custom sr_backend gets host arrays)
+    sr_weights: str = ""       # path of a compact SR network's weights (.npz, or .pth / .pt where torch imports): stage 2
+                               # runs the network (sr_network.CompactSRNet) instead of the bicubic stub, device-resident too
+    sr_act: str = "prelu"      # activation of that network when the weights hold no PReLU slopes: 'relu' or 'leakyrelu'
 
 
 @dataclass
@@ -87,6 +91,11 @@ def bicubic_stub_backend(pipeline: "SuperResolutionPipeline", tile: Tile, prompt
     return pipeline.quality_module.upsample_bicubic(data, (data.shape[0] * s, data.shape[1] * s))
 
 
+def compact_net_backend(pipeline: "SuperResolutionPipeline", tile: Tile, prompt: str) -> Optional[np.ndarray]:
+    """Local SR: the compact network of PipelineConfig.sr_weights on the padded tile (host array in, host array out)."""
+    return pipeline.sr_net.upscale(np.ascontiguousarray(tile.data))
+
+
 class SuperResolutionPipeline:
     """tiling -> super-resolution -> blending -> quality assessment -> output."""
 
@@ -97,6 +106,13 @@ class SuperResolutionPipeline:
                                           padding_mode=config.padding_mode, output_scale=float(config.sr_scale))
         self.blending_module = BlendingModule(method=config.blend_method, num_levels=config.num_pyramid_levels)
         self.quality_module = QualityAssessmentModule(device=config.qa_device)
+        self.sr_net = None
+        if config.sr_weights and sr_backend is None:
+            from sr_network import CompactSRNet
+            self.sr_net = CompactSRNet.from_file(config.sr_weights, act=config.sr_act)       # host work: no device call yet
+            if self.sr_net.scale != config.sr_scale:
+                raise ValueError(f"the network of {config.sr_weights} upscales by {self.sr_net.scale} but sr_scale is {config.sr_scale}")
+            sr_backend = compact_net_backend
         self.sr_backend = sr_backend or bicubic_stub_backend
         self.sr_module = None
         self.scheduler = None
@@ -120,6 +136,18 @@ class SuperResolutionPipeline:
         except Exception:  # noqa: BLE001
             self.logger.warning("无法解析目标分辨率: %s，使用默认100MP", target_resolution)
             return (12245, 8163)
+
+    def _builtin_backend(self) -> bool:
+        """The SR stage is one of the pipeline's own GPU backends (stub or network): the device-resident paths apply."""
+        return self.sr_backend is bicubic_stub_backend or (self.sr_net is not None and self.sr_backend is compact_net_backend)
+
+    def _sr_tile_device(self, ctx, d_src: int, block: int, d_dst: int, dst_stride: int):
+        """Stage 2 for one block x block x 3 tile, HBM -> HBM, on ctx's stream: the network, or the bicubic stand-in."""
+        out_block = block * self.config.sr_scale
+        if self.sr_net is not None:
+            self.sr_net.upscale_device(d_src, (block, block, 3), d_dst, dst_stride, ctx=ctx)
+        else:
+            ctx.resize_cubic_u8(d_src, block * 3, block, block, 3, d_dst, dst_stride, out_block, out_block)
 
     async def _process_single_tile(self, tile: Tile, prompt: str) -> Optional[np.ndarray]:
         try:
@@ -249,12 +277,12 @@ class SuperResolutionPipeline:
         sr_bufs, canvas = [], None
         lap("upload+tile")
         try:
-            # Stage 2: SR stand-in, tile by tile, HBM -> HBM
+            # Stage 2: SR (the network, or the bicubic stand-in), tile by tile, HBM -> HBM
             for i in range(len(tiles)):
                 buf = ctx.alloc(out_block * out_block * 3)
                 sr_bufs.append(buf)
-                ctx.resize_cubic_u8(ts.tile_ptr(i), block * 3, block, block, 3, buf.ptr, out_block * 3, out_block, out_block)
-            lap("sr_stub")
+                self._sr_tile_device(ctx, ts.tile_ptr(i), block, buf.ptr, out_block * 3)
+            lap("sr_net" if self.sr_net is not None else "sr_stub")
             # Stage 3: blending (the canvas is cropped to the un-padded image, scaled)
             rects = [(t.metadata.global_x * s, t.metadata.global_y * s, out_block, out_block) for t in tiles]
             H, W = ih * s, iw * s
@@ -344,7 +372,7 @@ class SuperResolutionPipeline:
             # stage 2: the SR stand-in for the tiles this rank owns, into the buffers the exchange sends from
             for t in pipe.owned:
                 buf = pipe.local_tiles[t]
-                pipe.ctx.resize_cubic_u8(ts.tile_ptr(t), block * 3, block, block, 3, buf.data_ptr(), buf.stride(0), out_block, out_block)
+                self._sr_tile_device(pipe.ctx, ts.tile_ptr(t), block, buf.data_ptr(), buf.stride(0))
             # stage 3: rows to the strip owners, strip blend
             pending = pipe.stage_exchange(0)
             pipe.stage_blend(pending)
@@ -386,7 +414,7 @@ class SuperResolutionPipeline:
         start = time.time()
         import _launch
         rank, world, local_rank = _launch.dist_env()
-        if (world > 1 and self.config.device_resident and self.sr_backend is bicubic_stub_backend
+        if (world > 1 and self.config.device_resident and self._builtin_backend()
                 and self.config.blend_method != 'weighted'):
             try:
                 return await self._process_sharded(input_path, output_path, roi_regions, start, rank, world, local_rank)
@@ -397,7 +425,7 @@ class SuperResolutionPipeline:
             # what does not shard (a custom SR backend hands host arrays around; the weighted blend has no strip form): rank 0
             # runs the one-GPU path, the others have nothing to do
             return PipelineResult(True, None, time.time() - start, 0, 0, 0, None, None, None)
-        if self.config.device_resident and self.sr_backend is bicubic_stub_backend:
+        if self.config.device_resident and self._builtin_backend():
             try:
                 return await self._process_device(input_path, output_path, roi_regions, start)
             except Exception as exc:  # noqa: BLE001 - the reference reports every failure in the result record
@@ -477,6 +505,9 @@ async def main() -> int:
     ap.add_argument("output")
     ap.add_argument("--block-size", type=int, default=2048)
     ap.add_argument("--sr-scale", type=int, default=2)
+    ap.add_argument("--sr-weights", default="", metavar="PATH",
+                    help="weights of a compact SR network (.npz / .pth): stage 2 runs it instead of the bicubic stub")
+    ap.add_argument("--sr-act", default="prelu", metavar="NAME", help="prelu (slopes in the weights), relu or leakyrelu")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node to use: N > 1 starts one process per GPU (RCCL)")
     ap.add_argument("--deadline-s", type=float, default=1800.0,
                     help="--gpus N: ranks still running after this many seconds are terminated (status 124)")
@@ -496,7 +527,7 @@ async def main() -> int:
         print(f"main.py: launched with WORLD_SIZE={world} but --gpus {args.gpus}", file=sys.stderr)
         return 2
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
-    cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale)
+    cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act)
     if args.plan_only:
         from PIL import Image
         with Image.open(args.input) as im:
