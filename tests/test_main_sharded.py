@@ -92,6 +92,32 @@ def test_two_rank_rehearsal_equals_one_rank(tmp_path, ext):
 
 
 @pytest.mark.gpu
+def test_two_rank_rehearsal_with_sr_network_equals_one_rank(tmp_path):
+    """The same rehearsal with --sr-weights: stage 2 is the compact SR network on the sharding pipeline's context, writing
+    into the torch buffers the exchange sends from.  One rank and two ranks give the same file bytes and QA report, and not
+    the bicubic stub's image."""
+    import _srnet_ref as ref
+    from PIL import Image
+    src, weights = str(tmp_path / "in.png"), str(tmp_path / "net.npz")
+    _source(src)
+    np.savez(weights, **ref.synthetic_state(64, 2, 2))
+    out1, out2, stub = str(tmp_path / "one.png"), str(tmp_path / "two.png"), str(tmp_path / "stub.png")
+    r1 = _run([src, out1, "--block-size", "128", "--sr-weights", weights], timeout=600)
+    assert r1.returncode == 0, r1.stdout[-2000:] + r1.stderr[-2000:]
+    r2 = _run([src, out2, "--block-size", "128", "--sr-weights", weights, "--gpus", "2"], env={"SR_DIST_BACKEND": "gloo"}, timeout=900)
+    assert r2.returncode == 0, r2.stdout[-2000:] + r2.stderr[-2000:]
+    assert open(out1, "rb").read() == open(out2, "rb").read()
+    q1 = json.load(open(out1.rsplit(".", 1)[0] + "_qa_report.json"))
+    q2 = json.load(open(out2.rsplit(".", 1)[0] + "_qa_report.json"))
+    q1.pop("timestamp"), q2.pop("timestamp")
+    assert q1 == q2 and np.isfinite(q1["full_reference"]["psnr"]) and 0.0 < q1["full_reference"]["ssim"] <= 1.0
+    r0 = _run([src, stub, "--block-size", "128"], timeout=600)
+    assert r0.returncode == 0, r0.stdout[-2000:] + r0.stderr[-2000:]
+    a, b = np.asarray(Image.open(out1)), np.asarray(Image.open(stub))
+    assert a.shape == b.shape == (600, 840, 3) and not np.array_equal(a, b)
+
+
+@pytest.mark.gpu
 def test_laplacian_fusion_across_ranks(tmp_path):
     """BlendingModule.laplacian_fusion called SPMD under an initialised process group (2 gloo ranks on the one GPU): every
     rank blends its strip, the strips are all-gathered -- the canvas equals the one-process result byte for byte."""
