@@ -617,6 +617,64 @@ SR_API int sr_srnet_u8(sr_srnet_model *model, const uint8_t *d_src, int64_t src_
 SR_API int sr_srnet_f32(sr_srnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
                         int64_t dst_stride, int tile);
 
+/* ---- local SR backend: residual family, MSRResNet / EDSR (csrc/sr_resnet.hip) ----------------------------------------------
+ * BasicSR's MSRResNet (SRResNet without batch norm) and EDSR (baseline and large), restated (parity with that package is
+ * unpinned: neither it nor a checkpoint exists offline).  Everything is fp32 in, fp32 accumulate; every convolution is 3 x 3,
+ * stride 1, zero padding 1 at the true image border, with bias.  A model is an sr_resnet_desc:
+ *     F = n_feat in {64, 128, 192, 256};  B = n_blocks, 0 <= B <= 64;  s = scale in {1, 2, 3, 4};
+ *     flags long_skip, conv_hr, bilinear_base (0 / 1);  slopes a_head, a_up, a_hr (1.0: no activation), where
+ *     act(y, a) = y >= 0 ? y : a * y;  res_scale;  mean[3], range.
+ *  1. input      x[c] = (u8 / 255 - mean[c]) * range (fp32: one division, one subtraction, one product); zero is padded
+ *                after this step.
+ *  2. head       h = act(conv 3 -> F (x), a_head).
+ *  3. blocks     t_0 = h;  for i = 1 .. B:  t = relu(conv1_i(t_{i-1})),  t_i = fmaf(res_scale, conv2_i(t), t_{i-1}).
+ *  4. long skip  if long_skip:  t = conv_after_body(t_B) + h  (one fp32 add).
+ *  5. upsampling s = 4: two stages with r = 2;  s in {2, 3}: one stage with r = s;  s = 1: none.  A stage is conv F -> F r^2,
+ *                PixelShuffle(r):  u[c, Y, X] = v[c r^2 + (Y % r) r + (X % r), Y / r, X / r],  then act(u, a_up).
+ *  6. HR conv    if conv_hr:  t = act(conv F -> F (t), a_hr) at full resolution.
+ *  7. last conv  y = conv F -> 3 (t) at full resolution.
+ *  8. output     o[c] = y[c] / range + mean[c]  (one division, one add);  with bilinear_base  o[c] = o[c] + base[c, Y, X], the
+ *                bilinear upsample of p = u8 / 255 in torch's align_corners=False arithmetic, in fp32 and in this order:
+ *                    sy = max((float)(1.0 / s) * (Y + 0.5f) - 0.5f, 0),  y0 = (int)sy,  y1 = y0 + (y0 < h - 1),
+ *                    ly1 = sy - y0,  ly0 = 1 - ly1  (x alike),
+ *                    base = ly0 * (lx0 * p[y0, x0] + lx1 * p[y0, x1]) + ly1 * (lx0 * p[y1, x0] + lx1 * p[y1, x1]).
+ *                Stored as HWC fp32 unclamped (sr_resnet_f32) or as HWC u8 rintf(fminf(fmaxf(o, 0), 1) * 255) (sr_resnet_u8).
+ * Presets: MSRResNet = a_head a_up a_hr 0.1, conv_hr, bilinear_base, no long_skip, res_scale 1, mean 0, range 1;
+ *          EDSR = slopes 1, long_skip, no conv_hr, no bilinear_base, the caller's res_scale, mean and range.
+ * Anything outside the ranges above (non-finite values and range 0 included) is SR_ERR_UNSUPPORTED, decided on the host before
+ * any device call.
+ * Summation order: body, upsampling, HR and last convolutions: bias, then channel pairs (2p, 2p + 1) ascending, then taps
+ * ascending, one two-term MFMA step each (even channel, then odd); head: bias, then channels, then taps, as fmaf; a skip add
+ * is one fmaf (or add) after the chain.  The order does not depend on where an output lies in a block or a sub-tile.
+ * sr_resnet_create: h_w[k] / h_b[k] = weights (dense OIHW fp32) and bias of convolution k in forward order: head, (conv1,
+ * conv2) per block, conv_after_body if long_skip, the upsampling stages, conv_hr if conv_hr, the last convolution; n_conv must
+ * be that count.  The arrays are re-laid and uploaded.
+ * sr_resnet_plan (host only, no context, no GPU): the image is streamed in tile x tile sub-tiles of the INPUT.  Every layer's
+ * extent is derived backwards from the sub-tile's output rectangle: grown by one per convolution, divided by r (rounded
+ * outwards) across a shuffle, clipped to the layer's image.  *halo = input pixels a sub-tile reads beyond its edge;
+ * *n_tiles sub-tiles; *workspace_bytes = the model's three planar F-channel fp32 buffers, each sized for the largest layer of
+ * one sub-tile (rows padded to 4 floats).  tile 0: the largest multiple of 32 up to 2048 (at least 32) with
+ * 3 F (s (tile + 2 halo))^2 floats <= 1 GiB.  Outputs may be NULL.
+ * sr_resnet_u8 / sr_resnet_f32: d_src h x w x 3 u8, d_dst (h s) x (w s) x 3; strides in bytes (fp32: a multiple of 4).
+ * SR_ERR_INVALID_ARG for null pointers, a wrong n_conv and a tile < 0, SR_ERR_SHAPE for h or w < 1, a stride shorter than a
+ * row, an output size beyond int or a sub-tile too large for 32-bit offsets -- all before any launch.  Every tile size gives
+ * the same bits.  Asynchronous. */
+typedef struct sr_resnet_desc {
+    int n_feat, n_blocks, scale;
+    int long_skip, conv_hr, bilinear_base;
+    float a_head, a_up, a_hr, res_scale;
+    float mean[3], range;
+} sr_resnet_desc;
+typedef struct sr_resnet_model sr_resnet_model;
+SR_API int sr_resnet_create(sr_ctx *ctx, const sr_resnet_desc *desc, const float *const *h_w, const float *const *h_b, int n_conv,
+                            sr_resnet_model **out);
+SR_API int sr_resnet_destroy(sr_resnet_model *model);
+SR_API int sr_resnet_plan(const sr_resnet_desc *desc, int h, int w, int tile, int *halo, int *n_tiles, size_t *workspace_bytes);
+SR_API int sr_resnet_u8(sr_resnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                        int64_t dst_stride, int tile);
+SR_API int sr_resnet_f32(sr_resnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                         int64_t dst_stride, int tile);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,13 @@ class QualityCell(C.Structure):
  CM_HF) = (1 << i for i in range(12))
 
 
+class ResNetDesc(C.Structure):
+    """sr_resnet_desc (include/sr_hip.h)."""
+    _fields_ = [("n_feat", C.c_int), ("n_blocks", C.c_int), ("scale", C.c_int), ("long_skip", C.c_int), ("conv_hr", C.c_int),
+                ("bilinear_base", C.c_int), ("a_head", C.c_float), ("a_up", C.c_float), ("a_hr", C.c_float),
+                ("res_scale", C.c_float), ("mean", C.c_float * 3), ("range", C.c_float)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("launches", C.c_int64)]
 
@@ -192,6 +199,11 @@ SIGNATURES = {
     "sr_srnet_plan": (_i, [_i, _i, _i, _i, _i, _i, _pi, _pi, C.POINTER(_sz)]),
     "sr_srnet_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
     "sr_srnet_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_resnet_create": (_i, [_vp, C.POINTER(ResNetDesc), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_vp)]),
+    "sr_resnet_destroy": (_i, [_vp]),
+    "sr_resnet_plan": (_i, [C.POINTER(ResNetDesc), _i, _i, _i, _pi, _pi, C.POINTER(_sz)]),
+    "sr_resnet_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_resnet_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
 }
 
 
@@ -1258,6 +1270,80 @@ class SrNetModel:
     def close(self):
         if getattr(self, "handle", None):
             self.ctx.lib.sr_srnet_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+# ------------------------------------------------------------------------------------------
+# local SR network, residual family (sr_resnet_*): sr_network.ResidualSRNet parses BasicSR state dicts into these arrays
+# ------------------------------------------------------------------------------------------
+def resnet_desc(n_feat: int, n_blocks: int, scale: int, long_skip: bool = False, conv_hr: bool = False, bilinear_base: bool = False,
+                a_head: float = 1.0, a_up: float = 1.0, a_hr: float = 1.0, res_scale: float = 1.0, mean=(0.0, 0.0, 0.0),
+                range: float = 1.0) -> ResNetDesc:  # noqa: A002 (the header's name)
+    mean = [float(v) for v in np.asarray(mean, dtype=np.float64).reshape(-1)]
+    if len(mean) != 3:
+        raise ValueError(f"mean holds 3 values, got {len(mean)}")
+    return ResNetDesc(int(n_feat), int(n_blocks), int(scale), int(bool(long_skip)), int(bool(conv_hr)), int(bool(bilinear_base)),
+                      float(a_head), float(a_up), float(a_hr), float(res_scale), (C.c_float * 3)(*mean), float(range))
+
+
+def resnet_conv_shapes(desc: ResNetDesc) -> List[Tuple[int, int]]:
+    """(cout, cin) of every convolution in sr_resnet_create's order."""
+    F, s = desc.n_feat, desc.scale
+    ups = {1: [], 2: [2], 3: [3], 4: [2, 2]}.get(s, [])
+    return ([(F, 3)] + [(F, F)] * (2 * desc.n_blocks + (1 if desc.long_skip else 0)) + [(F * r * r, F) for r in ups]
+            + ([(F, F)] if desc.conv_hr else []) + [(3, F)])
+
+
+def resnet_plan(desc: ResNetDesc, h: int, w: int, tile: int = 0) -> Tuple[int, int, int]:
+    """sr_resnet_plan (host only) -> (halo, sub-tiles, workspace bytes)."""
+    halo, n, ws = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check_unsupported(load().sr_resnet_plan(C.byref(desc), int(h), int(w), int(tile), C.byref(halo), C.byref(n), C.byref(ws)))
+    return halo.value, n.value, int(ws.value)
+
+
+class ResNetModel:
+    """sr_resnet_model: a residual SR network (MSRResNet / EDSR) resident on the GPU.  weights / biases: one OIHW fp32 array
+    and one bias vector per convolution in forward order (resnet_conv_shapes)."""
+
+    def __init__(self, ctx: Context, desc: ResNetDesc, weights, biases):
+        resnet_plan(desc, 1, 1)                                  # the supported range, refused before any array is touched
+        shapes = resnet_conv_shapes(desc)
+        if len(weights) != len(shapes) or len(biases) != len(shapes):
+            raise ValueError(f"this residual SR network has {len(shapes)} convolutions, got {len(weights)} weight / {len(biases)} bias arrays")
+        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
+        bs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in biases]
+        for k, (w, b, (co, ci)) in enumerate(zip(ws, bs, shapes)):
+            if w.shape != (co, ci, 3, 3) or b.shape != (co,):
+                raise ValueError(f"residual SR network convolution {k}: expected {(co, ci, 3, 3)} / {(co,)}, got {w.shape} / {b.shape}")
+        self.ctx, self.desc, self.scale = ctx, desc, desc.scale
+        pw = (C.c_void_p * len(ws))(*[a.ctypes.data for a in ws])
+        pb = (C.c_void_p * len(bs))(*[a.ctypes.data for a in bs])
+        h = C.c_void_p()
+        _check_unsupported(ctx.lib.sr_resnet_create(ctx.handle, C.byref(desc), pw, pb, len(ws), C.byref(h)))
+        self.handle = h
+
+    def plan(self, h: int, w: int, tile: int = 0) -> Tuple[int, int, int]:
+        return resnet_plan(self.desc, h, w, tile)
+
+    def upscale_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0):
+        """sr_resnet_u8: h x w x 3 u8 -> (h s) x (w s) x 3 u8, HBM -> HBM.  Asynchronous."""
+        check(self.ctx.lib.sr_resnet_u8(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
+                                        int(dst_stride), int(tile)))
+
+    def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0):
+        """sr_resnet_f32: the unclamped fp32 output (HWC, stride in bytes).  Asynchronous."""
+        check(self.ctx.lib.sr_resnet_f32(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
+                                         int(dst_stride), int(tile)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.sr_resnet_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -65,9 +65,11 @@ class PipelineConfig:
     qa_map_cell: int = 0       # > 0 (with enable_qa): stage 4 also writes a per-cell quality map of this cell size
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
                                    # only the canvas comes back for the writer (a custom sr_backend gets host arrays)
-    sr_weights: str = ""       # path of a compact SR network's weights (.npz, or .pth / .pt where torch imports): stage 2
-                               # runs the network (sr_network.CompactSRNet) instead of the bicubic stub, device-resident too
-    sr_act: str = "prelu"      # activation of that network when the weights hold no PReLU slopes: 'relu' or 'leakyrelu'
+    sr_weights: str = ""       # path of an SR network's weights (.npz, or .pth / .pt where torch imports): stage 2 runs the
+                               # network (sr_network.load_network: compact, or MSRResNet / EDSR) instead of the bicubic stub,
+                               # device-resident too
+    sr_act: str = "prelu"      # activation of a compact network whose weights hold no PReLU slopes: 'relu' or 'leakyrelu'
+                               # (ignored for the residual family)
 
 
 @dataclass
@@ -108,8 +110,8 @@ class SuperResolutionPipeline:
         self.quality_module = QualityAssessmentModule(device=config.qa_device)
         self.sr_net = None
         if config.sr_weights and sr_backend is None:
-            from sr_network import CompactSRNet
-            self.sr_net = CompactSRNet.from_file(config.sr_weights, act=config.sr_act)       # host work: no device call yet
+            from sr_network import load_network
+            self.sr_net = load_network(config.sr_weights, act=config.sr_act)                 # host work: no device call yet
             if self.sr_net.scale != config.sr_scale:
                 raise ValueError(f"the network of {config.sr_weights} upscales by {self.sr_net.scale} but sr_scale is {config.sr_scale}")
             sr_backend = compact_net_backend

@@ -155,3 +155,136 @@ class CompactSRNet:
         for m in self._models.values():
             m.close()
         self._models = {}
+
+
+# ------------------------------------------------------------------------------------------
+# The residual family: BasicSR's MSRResNet (SRResNet without batch norm) and EDSR, run by csrc/sr_resnet.hip.
+# PARITY UNPINNED here too: neither the BasicSR package nor a checkpoint exists offline; the arithmetic is written out in
+# include/sr_hip.h and held against a torch-CPU restatement (tests/_resnet_ref.py).
+# ------------------------------------------------------------------------------------------
+EDSR_RGB_MEAN = (0.4488, 0.4371, 0.4040)                        # BasicSR's defaults (DIV2K)
+EDSR_IMG_RANGE = 255.0
+_BLOCK_KEY = re.compile(r"^body\.(\d+)\.(conv1|conv2)\.(weight|bias)$")
+_UPSAMPLE_KEY = re.compile(r"^upsample\.(\d+)\.weight$")
+
+
+def _array(state: Mapping, key: str) -> np.ndarray:
+    a = state[key]
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def parse_residual_state(state: Mapping, res_scale: float = 1.0, img_range: float = EDSR_IMG_RANGE, rgb_mean=EDSR_RGB_MEAN):
+    """-> (_native.ResNetDesc, weights, biases) in sr_resnet_create's order, contiguous fp32.
+
+    BasicSR key names: ``conv_first``, ``body.{i}.conv1`` / ``body.{i}.conv2``, then either MSRResNet's ``upconv1`` (and
+    ``upconv2`` at scale 4), ``conv_hr``, ``conv_last`` -- or EDSR's ``conv_after_body``, ``upsample.{k}``, ``conv_last``.
+    ``conv_after_body.weight`` tells the two apart.  res_scale, img_range and rgb_mean are not in a state dict: they apply to
+    EDSR only (MSRResNet: 1, range 1, mean 0).  Every shape is checked; a ValueError names the offending key."""
+    state = _unwrap(state)
+    keys = {str(k) for k in state}
+    if "conv_first.weight" not in keys:
+        raise ValueError("conv_first.weight: not in the state (not a residual SR network)")
+    convs = []                                                   # (key, cout or None for 'any multiple', cin)
+
+    def conv(name: str, cin: int, cout=None):
+        for part in ("weight", "bias"):
+            if f"{name}.{part}" not in keys:
+                raise ValueError(f"{name}.{part}: not in the state")
+        w = np.ascontiguousarray(_array(state, f"{name}.weight"), dtype=np.float32)
+        b = np.ascontiguousarray(_array(state, f"{name}.bias"), dtype=np.float32).reshape(-1)
+        if w.ndim != 4 or w.shape[2:] != (3, 3):
+            raise ValueError(f"{name}.weight: only 3x3 convolutions, got shape {w.shape}")
+        if w.shape[1] != cin:
+            raise ValueError(f"{name}.weight takes {w.shape[1]} channels but the layer before it gives {cin}")
+        if cout is not None and w.shape[0] != cout:
+            raise ValueError(f"{name}.weight gives {w.shape[0]} channels, expected {cout}")
+        if b.shape != (w.shape[0],):
+            raise ValueError(f"{name}.bias: expected {w.shape[0]} values, got {b.shape}")
+        convs.append((w, b))
+        return w
+
+    F = int(conv("conv_first", 3).shape[0])
+    blocks = sorted({int(m.group(1)) for m in map(_BLOCK_KEY.match, keys) if m})
+    if blocks != list(range(len(blocks))):
+        raise ValueError(f"body.{len(blocks)}.conv1.weight: residual blocks must be numbered 0 .. B - 1, got {blocks}")
+    for i in blocks:
+        conv(f"body.{i}.conv1", F, F)
+        conv(f"body.{i}.conv2", F, F)
+    edsr = "conv_after_body.weight" in keys
+    if edsr:
+        conv("conv_after_body", F, F)
+        ups = [f"upsample.{k}" for k in sorted(int(m.group(1)) for m in map(_UPSAMPLE_KEY.match, keys) if m)
+               if _array(state, f"upsample.{k}.weight").ndim == 4]
+    else:
+        ups = [n for n in ("upconv1", "upconv2") if f"{n}.weight" in keys or f"{n}.bias" in keys]
+        if ups == ["upconv2"]:
+            raise ValueError("upconv1.weight: not in the state, but upconv2 is")
+    if len(ups) > 2:
+        raise ValueError(f"{ups[2]}.weight: at most two upsampling stages (scale 4)")
+    scale = 1
+    for name in ups:
+        cout = int(np.shape(_array(state, f"{name}.weight"))[0]) if f"{name}.weight" in keys else 0
+        r = {4 * F: 2, 9 * F: 3}.get(cout)
+        if r is None or (len(ups) == 2 and r != 2):
+            want = f"{4 * F}" if len(ups) == 2 else f"{4 * F} or {9 * F}"
+            raise ValueError(f"{name}.weight gives {cout} channels, expected F r^2 = {want}")
+        conv(name, F, cout)
+        scale *= r
+    if not edsr:
+        conv("conv_hr", F, F)
+    conv("conv_last", F, 3)
+    if edsr:
+        desc = _native.resnet_desc(F, len(blocks), scale, long_skip=True, res_scale=float(res_scale), mean=rgb_mean, range=float(img_range))
+    else:
+        desc = _native.resnet_desc(F, len(blocks), scale, conv_hr=True, bilinear_base=True, a_head=0.1, a_up=0.1, a_hr=0.1)
+    _native.resnet_plan(desc, 1, 1)                              # NotImplementedError outside the kernels' range (host only)
+    return desc, [w for w, _ in convs], [b for _, b in convs]
+
+
+class ResidualSRNet(CompactSRNet):
+    """MSRResNet / EDSR on the GPU, with CompactSRNet's surface (from_file, model, upscale, upscale_device, close).
+    ``state``: a BasicSR state dict (see parse_residual_state)."""
+
+    def __init__(self, state: Mapping, res_scale: float = 1.0, img_range: float = EDSR_IMG_RANGE, rgb_mean=EDSR_RGB_MEAN, device: int = 0):
+        self.desc, self._w, self._b = parse_residual_state(state, res_scale, img_range, rgb_mean)
+        self.n_feat, self.n_blocks, self.scale = self.desc.n_feat, self.desc.n_blocks, self.desc.scale
+        self.preset = "edsr" if self.desc.long_skip else "msrresnet"
+        self.device = int(device)
+        self._models = {}
+
+    @classmethod
+    def from_file(cls, path: str, device: int = 0, **extras) -> "ResidualSRNet":
+        """A .npz may hold the EDSR constants a state dict lacks as 0-d ``res_scale`` / ``img_range`` and 3-vector ``rgb_mean``
+        entries; keyword arguments win over them, BasicSR's defaults stand in for the rest."""
+        state = load_state(path)
+        return cls(state, device=device, **{**_residual_extras(state), **extras})
+
+    def model(self, ctx: Optional["_native.Context"] = None) -> "_native.ResNetModel":
+        ctx = ctx or _native.default_context(self.device)
+        m = self._models.get(id(ctx))
+        if m is None or m.handle is None or m.ctx is not ctx:
+            m = _native.ResNetModel(ctx, self.desc, self._w, self._b)
+            self._models[id(ctx)] = m
+        return m
+
+
+def _residual_extras(state: Mapping) -> dict:
+    out = {}
+    if not isinstance(state, Mapping):
+        return out
+    for key, size in (("res_scale", 1), ("img_range", 1), ("rgb_mean", 3)):
+        if key in state:
+            a = np.asarray(_array(state, key), dtype=np.float64).reshape(-1)
+            if a.size != size:
+                raise ValueError(f"{key}: expected {size} value{'s' if size > 1 else ''}, got shape {np.shape(_array(state, key))}")
+            out[key] = tuple(a.tolist()) if size == 3 else float(a[0])
+    return out
+
+
+def load_network(path: str, act: str = "prelu", device: int = 0):
+    """The network a weights file holds: a ``conv_first.weight`` entry makes it a ResidualSRNet (``act`` is ignored for this
+    family), ``body.{i}.weight`` entries a CompactSRNet exactly as CompactSRNet.from_file."""
+    state = load_state(path)
+    if "conv_first.weight" in {str(k) for k in _unwrap(state)}:
+        return ResidualSRNet(state, device=device, **_residual_extras(state))
+    return CompactSRNet(state, act=act, device=device)
