@@ -5,8 +5,16 @@ PARITY UNPINNED: the BasicSR package and its checkpoints do not exist offline.  
 float64 restatement within 8 x the error torch's own float32 forward makes on the same input (the project's yardstick;
 tests/test_resnet_host.py holds the documented summation order alone inside it), the u8 output byte for byte away from rounding
 boundaries, streamed == unstreamed bit for bit across both resolution changes, strided views, determinism, reuse across shapes,
-the refusals, and the pipeline with ``sr_weights``."""
+the refusals, and the pipeline with ``sr_weights``.
+
+Beyond the two presets the loader produces, the C ABI's descriptor is driven directly (_native.ResNetModel): the descriptor-space
+list (every flag combination, every scale, distinct non-preset slopes, res_scale, mean and range) against the same bars, and
+the exact-arithmetic networks and one-hot probes of _resnet_ref -- every partial sum representable in fp32, proved on the CPU
+in tests/test_resnet_host.py -- which the GPU must reproduce bit for bit whatever its summation order: the zero-tolerance
+check of the register -> cout map, the weight-slab layout, the tap order, the shuffle scatter, the in-place skip and the
+padding at the true border."""
 import asyncio
+import dataclasses
 
 import numpy as np
 import pytest
@@ -91,6 +99,7 @@ def test_degenerate_and_block_edge_shapes(ctx, nets, case):
     ("msr", 64, 2, 2, 20, 30, {4: 5 * 8}),                                  # sub-tile (4) smaller than the halo (7): every extent clipped
     ("edsr", 64, 2, 2, 5, 6, {1: 30}),                                      # one-pixel sub-tiles; in-place blocks behind a kept h
     ("msr", 64, 0, 1, 20, 35, {7: 3 * 5}),                                  # no block, no shuffle
+    ("edsr", 64, 16, 2, 16, 40, {8: 2 * 5}),                                # the shipped depth: a halo of 35 beyond the image, every extent clipped on all sides
 ])
 def test_streaming_is_bit_equal(ctx, nets, preset, F, B, s, h, w, tiles):
     """fp32 bits and u8 bytes of every sub-tile size equal those of one sub-tile."""
@@ -276,3 +285,115 @@ def test_pipeline_with_sr_weights(tmp_path, preset):
     ref.check_u8(pipe.sr_net.upscale(tile0), f64, e32)
     with pytest.raises(ValueError, match="sr_scale"):
         sr_main.SuperResolutionPipeline(sr_main.PipelineConfig(sr_weights=wpath, block_size=64, sr_scale=4))
+
+
+# ---- the descriptor itself, through _native.ResNetModel ---------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def models(ctx):
+    """One model per (descriptor, weights tag), created once and closed at teardown."""
+    import _native
+    cache = {}
+
+    def get(desc, tag, weights, biases):
+        key = (desc, tag)
+        if key not in cache:
+            cache[key] = _native.ResNetModel(ctx, _native.resnet_desc(**dataclasses.asdict(desc)), weights, biases)
+        return cache[key]
+
+    yield get
+    for m in cache.values():
+        m.close()
+
+
+def _run(ctx, m, img, tile=0, u8=False):
+    h, w = img.shape[:2]
+    s, esz = m.scale, 1 if u8 else 4
+    d_src, d_dst = ctx.upload(img), ctx.alloc(h * s * w * s * 3 * esz)
+    try:
+        (m.upscale_u8 if u8 else m.forward_f32)(d_src.ptr, w * 3, h, w, d_dst.ptr, w * s * 3 * esz, tile)
+        return ctx.download(d_dst.ptr, (h * s, w * s, 3), np.uint8 if u8 else np.float32)
+    finally:
+        d_src.free(); d_dst.free()
+
+
+def _round_u8(f):
+    return np.rint(np.clip(f, 0.0, 1.0) * np.float32(255.0)).astype(np.uint8)
+
+
+@pytest.mark.parametrize("case", ref.DESC_CASES, ids=ref.desc_id)
+def test_descriptor_space(ctx, models, case):
+    """Every flag combination, every scale and distinct non-preset slopes, res_scale, mean and range (tests/test_resnet_host.py
+    shows that each field moves the result by more than 100 e32): the float bar, the u8 check, u8 == the float form rounded, and
+    sub-tiles of 5 and 16 bit-equal to one sub-tile.  Prints every figure before it asserts."""
+    name, desc = case
+    ws, bs, img, f64, e32 = ref.desc_case(desc)
+    e_chain = ref.desc_chain_case(desc)[1]
+    m = models(desc, "synthetic", ws, bs)
+    got = _run(ctx, m, img)
+    err = float(np.max(np.abs(got.astype(np.float64) - f64)))
+    print(f"resnet desc {name}: e32 {e32:.3e}  e_chain {e_chain:.3e}  gpu err {err:.3e}  gpu / e32 {err / e32:.3f}  "
+          f"e_chain / e32 {e_chain / e32:.3f}  gpu / e_chain {err / e_chain:.3f}")
+    assert 0 < e32 < 1e-5
+    assert err <= 8 * e32, (err, e32, err / e32)
+    u8 = _run(ctx, m, img, u8=True)
+    share = ref.check_u8(u8, f64, e32)
+    print(f"  u8: exempt share {share:.4%}, bytes != rint(f64): {int((u8 != ref.quantize(f64)).sum())}")
+    assert np.array_equal(u8, _round_u8(got))
+    for tile in (5, 16):
+        assert m.plan(ref.DESC_H, ref.DESC_W, tile)[1] == -(-ref.DESC_H // tile) * -(-ref.DESC_W // tile)
+        assert np.array_equal(_bits(_run(ctx, m, img, tile=tile)), _bits(got)), tile
+        assert np.array_equal(_run(ctx, m, img, tile=tile, u8=True), u8), tile
+
+
+def _same_bits(got, want, what):
+    bad = np.argwhere(_bits(got) != _bits(want)) if got.dtype == np.float32 else np.argwhere(got != want)
+    if len(bad):
+        y, x, c = bad[0]
+        raise AssertionError(f"{what}: {len(bad)} of {got.size} values differ, first at (Y {y}, X {x}, channel {c}): "
+                             f"got {got[y, x, c]!r}, expected {want[y, x, c]!r}; rows {sorted(set(bad[:, 0].tolist()))[:12]}, "
+                             f"columns {sorted(set(bad[:, 1].tolist()))[:12]}")
+
+
+def _check_exact(ctx, models, name, k):
+    """GPU == chain_forward_desc bit for bit (fp32) and byte for byte (u8): one sub-tile, sub-tiles of 4, and through a padded,
+    offset source view into guarded destinations."""
+    desc, ws, bs, img, chain = ref.exact_case(name)
+    h, w = img.shape[:2]
+    s = desc.scale
+    want_u8 = _round_u8(chain)
+    m = models(desc, name, ws, bs)
+    for tile in (0, 4):
+        assert m.plan(h, w, tile)[1] == (1 if tile == 0 else -(-h // 4) * -(-w // 4))
+        _same_bits(_run(ctx, m, img, tile=tile), chain, f"{name}: fp32, tile {tile}")
+        _same_bits(_run(ctx, m, img, tile=tile, u8=True), want_u8, f"{name}: u8, tile {tile}")
+    for fill in V.FILLS:
+        src, d_src, sstride = V.embed(ctx, img.reshape(h, w * 3), *V.pick(V.LAYOUTS_U8, k), fill)
+        dst, d_dst, dstride = V.out_view(ctx, h * s, w * s * 3, *V.pick(V.LAYOUTS_U8, k + 5), fill)
+        dstf, d_dstf, dstridef = V.out_view(ctx, h * s, w * s * 3 * 4, *V.pick(V.LAYOUTS_F32, k), fill)
+        try:
+            m.upscale_u8(d_src, sstride, h, w, d_dst, dstride, 4)
+            m.forward_f32(d_src, sstride, h, w, d_dstf, dstridef, 0)
+            got_u = V.check_guard(ctx, dst, np.uint8, (h * s, w * s, 3), what=f"{name} u8")
+            got_f = V.check_guard(ctx, dstf, np.float32, (h * s, w * s, 3), what=f"{name} f32")
+        finally:
+            src.free(); dst.free(); dstf.free()
+        _same_bits(got_u, want_u8, f"{name}: u8 through views, fill {fill:#x}")
+        _same_bits(got_f, chain, f"{name}: fp32 through views, fill {fill:#x}")
+
+
+EXACT_IDS = [n[0] for n in ref.EXACT_NETS]
+PROBE_IDS = [p[0] for p in ref.PROBES]
+
+
+@pytest.mark.parametrize("name", EXACT_IDS)
+def test_exact_networks_bit_equal(ctx, models, name):
+    """Networks whose every partial sum is exact in fp32 (proved in tests/test_resnet_host.py): no summation order, and nothing the
+    MFMA does inside its two-term step, can change a bit, so any difference is an index error."""
+    _check_exact(ctx, models, name, EXACT_IDS.index(name) + 1)        # k: the view layouts walked, one pair per network
+
+
+@pytest.mark.parametrize("name", PROBE_IDS)
+def test_one_hot_probes_bit_equal(ctx, models, name):
+    """One convolution is a pure tap with permuted channels, every other one the centre-tap identity: the output is a shifted,
+    permuted copy with zeros entering at the true image border only, and a failure names the layer and the tap."""
+    _check_exact(ctx, models, name, PROBE_IDS.index(name))
