@@ -1,5 +1,6 @@
 // sr_ctx.h -- the device context shared by the .hip translation units of libsrhip.so (sr_engine.hip owns the
-// definitions; sr_lpips.hip and sr_adjust.hip use them).  Internal: nothing here is part of the C ABI.
+// definitions; every other .hip file and sr_comm.cpp use them, the convolution networks through sr_conv_mfma.h).
+// Internal: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

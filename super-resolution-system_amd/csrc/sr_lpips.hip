@@ -18,10 +18,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <set>
 #include <vector>
 
-#include "sr_ctx.h"
+#include "sr_conv_mfma.h"
 
 namespace {
 
@@ -33,9 +32,6 @@ struct LpLayer {
     int tap;                  // LP_TAP: LPIPS layer index 0..4
     int widx;                 // LP_CONV: index into the weight arrays
 };
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4v __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------------------------
 // Stem convolution (Cin = 3) straight from the u8 image: one thread = one output pixel x 64 output channels.
@@ -93,20 +89,10 @@ __global__ __launch_bounds__(256) void k_lp_conv_stem(const unsigned char *__res
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Implicit-GEMM convolution + bias + ReLU on v_mfma_f32_32x32x2_f32, stride 1, KS x KS, zero padding P = KS / 2.
-//   GEMM view: D[cout][pixel] = sum_k W[cout][k] * X[k][pixel], k = (cin, tap).
-//   A operand = weights (lane l: cout l & 31, k-half l >> 5), B operand = input pixels (lane l: pixel l & 31, k-half
-//   l >> 5); the accumulator then holds pixel l & 31 on the lane and 16 couts in its registers, so every store
-//   instruction writes two contiguous 128-byte row segments of two output planes.
-//   Block = 4 waves = 8 output rows x 32 columns x 64 couts; wave w owns rows 2w, 2w + 1 and both 32-cout halves
-//   (four 32 x 32 accumulators, 64 VGPRs).  Cin is walked in chunks of CC channels: the input patch
-//   [CC][8 + KS - 1][32 + KS - 1] and the weight slab [CC][KS*KS][64] are staged in LDS, the k-half of a lane selects
-//   the channel parity, so the per-step LDS addresses are lane base + compile-time immediates.
-//   Per k-step a wave issues 2 + 2 LDS dword reads for 4 MFMAs (256 matrix-pipe cycles): the kernel is matrix-pipe
-//   bound by a wide margin; global loads of the next chunk are in flight during the MFMAs of the current one.
-// The input is a planar buffer covering rows [in_ya, ..) x cols [in_xa, ..) of the layer's global index space; taps
-// outside the image extent (H_in, W_in) read as zero -- that is the layer's own zero padding, also in the interior
-// of a tiled forward where the buffer holds real neighbour data instead.
+// Implicit-GEMM convolution + bias + ReLU on v_mfma_f32_32x32x2_f32, stride 1, KS x KS, zero padding P = KS / 2:
+// conv_mfma_mainloop<KS, CC, 2, false> (sr_conv_mfma.h states the GEMM view, the block shape, the LDS staging and the
+// summation order) plus a ReLU epilogue.  Block = 4 waves = 8 output rows x 32 columns x 64 couts.  GUARD is off: this
+// kernel is not told how many rows and columns its input buffer holds.
 // ---------------------------------------------------------------------------------------------------------------
 template <int KS, int CC>
 __global__ __launch_bounds__(256) void k_lp_conv_mfma(const float *__restrict__ in, long long in_plane, int in_pitch,
@@ -115,99 +101,21 @@ __global__ __launch_bounds__(256) void k_lp_conv_mfma(const float *__restrict__ 
                                                       float *__restrict__ out, long long out_plane, int out_pitch,
                                                       int out_ya, int out_xa, int rows, int cols)
 {
-    constexpr int T = KS * KS, P = KS / 2;
-    constexpr int PH = 8 + KS - 1, PW = 32 + KS - 1;
-    constexpr int NPATCH = CC * PH * PW, NW4 = CC * T * 16;            // patch floats, weight float4s per chunk
-    constexpr int PE = (NPATCH + 255) / 256, WE = (NW4 + 255) / 256;   // per-thread staging counts
-    __shared__ __attribute__((aligned(16))) float s_patch[NPATCH];
-    __shared__ __attribute__((aligned(16))) float s_w[CC * T * 64];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
-    const int ox0 = blockIdx.x * 32, oy0 = blockIdx.y * 8;              // tile origin inside the output range
-    const int ct = blockIdx.z;                                          // 64-cout tile
-    const int nchunk = cin / CC;
-
-    // staging map of this thread: patch element e -> (channel, row, col) is the same for every chunk
-    int p_off[PE];
-    unsigned p_ok = 0;
-#pragma unroll
-    for (int i = 0; i < PE; ++i) {
-        const int e = tid + i * 256;
-        const int c = e / (PH * PW), r = (e / PW) % PH, x = e % PW;
-        const int gy = out_ya + oy0 - P + r, gx = out_xa + ox0 - P + x;   // global index in the input layer
-        const bool ok = e < NPATCH && gy >= 0 && gy < H_in && gx >= 0 && gx < W_in;
-        p_off[i] = ok ? (int)((long long)c * in_plane + (long long)(gy - in_ya) * in_pitch + (gx - in_xa)) : 0;
-        if (ok) p_ok |= 1u << i;
-    }
-    const f4v *wsrc = (const f4v *)(wslab + (size_t)ct * nchunk * (CC * T * 64));
-
+    const MfmaLane ln = mfma_lane();
     f32x16 acc[2][2];
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float b = bias[ct * 64 + c2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
-            acc[c2][0][r] = b;
-            acc[c2][1][r] = b;
-        }
-
-    float pv[PE];
-    f4v wv[WE];
-    auto load_chunk = [&](int ch) {
-        const float *ib = in + (size_t)ch * CC * in_plane;
-#pragma unroll
-        for (int i = 0; i < PE; ++i) pv[i] = (p_ok >> i) & 1u ? ib[p_off[i]] : 0.0f;
-        const f4v *wb = wsrc + (size_t)ch * NW4;
-#pragma unroll
-        for (int i = 0; i < WE; ++i) {
-            const int e = tid + i * 256;
-            wv[i] = e < NW4 ? wb[e] : f4v{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    load_chunk(0);
-    // lane bases: the k-half selects the odd channel of a pair
-    const float *a_base = s_w + half * (T * 64) + l32;
-    const float *b_base = s_patch + half * (PH * PW) + (2 * wave) * PW + l32;
-#pragma unroll 1
-    for (int ch = 0; ch < nchunk; ++ch) {
-        __syncthreads();                                   // the previous chunk has been consumed
-#pragma unroll
-        for (int i = 0; i < PE; ++i) {
-            const int e = tid + i * 256;
-            if (e < NPATCH) s_patch[e] = pv[i];
-        }
-#pragma unroll
-        for (int i = 0; i < WE; ++i) {
-            const int e = tid + i * 256;
-            if (e < NW4) ((f4v *)s_w)[e] = wv[i];
-        }
-        __syncthreads();
-        if (ch + 1 < nchunk) load_chunk(ch + 1);           // in flight under the MFMAs below
-#pragma unroll
-        for (int cp = 0; cp < CC / 2; ++cp)
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const int dy = t / KS, dx = t % KS;
-                const float a0 = a_base[(2 * cp * T + t) * 64], a1 = a_base[(2 * cp * T + t) * 64 + 32];
-                const float b0 = b_base[2 * cp * PH * PW + dy * PW + dx], b1 = b_base[2 * cp * PH * PW + (dy + 1) * PW + dx];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-            }
-    }
+    conv_mfma_mainloop<KS, CC, 2, false>(ln, in, in_plane, in_pitch, in_ya, in_xa, 0, 0, H_in, W_in, cin, wslab, bias, out_ya, out_xa, acc);
     // epilogue: ReLU, masked store
-    const int col = ox0 + l32;
+    const int col = ln.ox0 + ln.l32;
     if (col >= cols) return;
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
-        const int row = oy0 + 2 * wave + pr;
+        const int row = ln.oy0 + 2 * ln.wave + pr;
         if (row >= rows) continue;
 #pragma unroll
         for (int c2 = 0; c2 < 2; ++c2)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = ct * 64 + c2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int co = ln.ct * 64 + mfma_cout(c2, r, ln.half);
                 out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = fmaxf(acc[c2][pr][r], 0.0f);
             }
     }
@@ -319,14 +227,7 @@ struct sr_lpips_model {
     size_t part_cap = 0;
 };
 
-static std::mutex g_lp_mu;
-static std::set<const void *> g_lp_live;
-
-static bool lp_is_live(const sr_lpips_model *m)
-{
-    std::lock_guard<std::mutex> lk(g_lp_mu);
-    return m && g_lp_live.count(m) != 0;
-}
+static LiveSet g_lp_live;
 
 static void lp_arch(int net, std::vector<LpLayer> &L)
 {
@@ -428,10 +329,7 @@ int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, const fl
         M->shift[c] = h_shift ? h_shift[c] : def_shift[c];
         M->scale[c] = h_scale ? h_scale[c] : def_scale[c];
     }
-    {
-        std::lock_guard<std::mutex> lk(g_lp_mu);
-        g_lp_live.insert(M);
-    }
+    g_lp_live.insert(M);
     auto fail = [&](int code, const char *what) {
         sr_set_error(code, "sr_lpips_create: %s", what);
         sr_lpips_destroy(M);
@@ -447,9 +345,10 @@ int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, const fl
         const float *w = h_conv_w[l.widx], *b = h_conv_b[l.widx];
         if (!w || !b) return fail(SR_ERR_INVALID_ARG, "null weight array");
         const int T = l.k * l.k;
-        std::vector<float> arranged((size_t)l.cout * l.cin * T);
+        std::vector<float> arranged;
         if (l.cin == 3) {                                   // stem: [c][tap][cout]
             if (l.cout != 64) return fail(SR_ERR_UNSUPPORTED, "stem convolution must have 64 outputs");
+            arranged.resize((size_t)l.cout * l.cin * T);
             for (int co = 0; co < l.cout; ++co)
                 for (int c = 0; c < 3; ++c)
                     for (int t = 0; t < T; ++t) arranged[((size_t)c * T + t) * 64 + co] = w[((size_t)co * 3 + c) * T + t];
@@ -457,14 +356,7 @@ int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, const fl
             const int CC = l.k == 3 ? 8 : 4;
             if (l.cout % 64 || l.cin % CC || l.s != 1 || (l.k != 3 && l.k != 5) || l.p != l.k / 2)
                 return fail(SR_ERR_UNSUPPORTED, "convolution shape outside the MFMA kernel's cases");
-            const int nch = l.cin / CC;
-            for (int ct = 0; ct < l.cout / 64; ++ct)
-                for (int ch = 0; ch < nch; ++ch)
-                    for (int c = 0; c < CC; ++c)
-                        for (int t = 0; t < T; ++t)
-                            for (int co = 0; co < 64; ++co)
-                                arranged[((((size_t)ct * nch + ch) * CC + c) * T + t) * 64 + co] =
-                                    w[((size_t)(ct * 64 + co) * l.cin + ch * CC + c) * T + t];
+            arranged = arrange_mfma_weights(w, b, l.cout, l.cin, T, CC, 64).w;     // cout % 64 == 0: the bias needs no padding
         }
         float *dw = nullptr, *db = nullptr;
         if (hipMalloc((void **)&dw, arranged.size() * sizeof(float)) != hipSuccess) return fail(SR_ERR_OOM, "weights");
@@ -489,10 +381,7 @@ int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, const fl
 int sr_lpips_destroy(sr_lpips_model *m)
 {
     if (!m) return SR_OK;
-    {
-        std::lock_guard<std::mutex> lk(g_lp_mu);
-        if (!g_lp_live.erase(m)) return SR_OK;
-    }
+    if (!g_lp_live.erase(m)) return SR_OK;
     if (ctx_is_live(m->ctx)) {
         Guard g(m->ctx);
         (void)hipStreamSynchronize(m->ctx->stream);
@@ -534,7 +423,7 @@ int sr_lpips_tile_count(int h, int w, int tile, int *n_tiles)
 int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h,
                 int w, int cn, int tile, int tile_begin, int tile_end, double *h_layer_sums)
 {
-    if (!lp_is_live(m)) return sr_set_error(SR_ERR_INVALID_ARG, "sr_lpips_u8: null or destroyed model");
+    if (!g_lp_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "sr_lpips_u8: null or destroyed model");
     sr_ctx *ctx = m->ctx;
     CTX_ENTER(ctx);
     if (!d_a || !d_b || !h_layer_sums) return sr_set_error(SR_ERR_INVALID_ARG, "sr_lpips_u8: null argument");
@@ -568,24 +457,8 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
             plane[j] = (long long)ny[j].n() * pitch[j];
             need_floats = std::max(need_floats, (size_t)plane[j] * G.C[j]);
         }
-        if (need_floats > m->buf_floats) {
-            HIPCHK(stream_sync(ctx));
-            for (auto &im : m->buf)
-                for (auto &p : im) {
-                    if (p) (void)hipFree(p);
-                    p = nullptr;
-                }
-            m->buf_floats = 0;
-            for (auto &im : m->buf)
-                for (auto &p : im) {
-                    hipError_t e = hipMalloc((void **)&p, need_floats * sizeof(float));
-                    if (e != hipSuccess)
-                        return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP,
-                                            "sr_lpips_u8: activation buffers (4 x %zu MB; use a smaller tile): %s",
-                                            need_floats * 4 >> 20, hipGetErrorString(e));
-                }
-            m->buf_floats = need_floats;
-        }
+        rc = ensure_activation_buffers(ctx, &m->buf[0][0], 4, m->buf_floats, need_floats, "sr_lpips_u8");
+        if (rc) return rc;
         int cur = 0;                       // ping-pong index of the current activation (both images in step)
         for (size_t li = 0; li < L.size(); ++li) {
             const LpLayer &l = L[li];

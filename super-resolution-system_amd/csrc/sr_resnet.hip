@@ -1,5 +1,5 @@
 // sr_resnet.hip -- local super-resolution backend: the classic residual family (BasicSR's MSRResNet = SRResNet without batch
-// norm, and EDSR baseline / large) on gfx950.  A sibling of sr_srnet.hip: that file and its instruction streams are left alone.
+// norm, and EDSR baseline / large) on gfx950.
 //
 //   head        3 x 3 convolution 3 -> F from the u8 image, x[c] = (u8 / 255 - mean[c]) * range, slope a_head   -> h
 //   blocks      B x { t' = relu(conv1(t));  t = fmaf(res_scale, conv2(t'), t) }
@@ -9,8 +9,8 @@
 //   last conv   3 x 3 convolution F -> 3 at full resolution, o[c] = y[c] / range + mean[c] (+ the bilinear base), HWC store
 //
 // Everything is fp32 (fp32 in, fp32 accumulate).  Every F-input convolution is one implicit-GEMM kernel on
-// v_mfma_f32_32x32x2_f32 with the block shape and LDS staging of k_sn_conv (4 waves = 8 rows x 32 columns x 64 couts), templated
-// on its epilogue; the 3 -> F head is the direct VALU kernel of k_sn_head with the input affine added.
+// v_mfma_f32_32x32x2_f32 (the mainloop of sr_conv_mfma.h, shared with sr_lpips.hip and sr_srnet.hip), templated on its
+// epilogue; the 3 -> F head is the direct VALU kernel of k_sn_head with the input affine added.
 //
 // Memory: activations are planar fp32 [F][rows][pitch] in three buffers owned by the model (in, out, and the skip / h).  The
 // image is walked in square sub-tiles of the INPUT.  Every layer's extent is derived backwards from the sub-tile's output
@@ -19,8 +19,7 @@
 // overwrites its skip in place (each thread reads exactly the element it then writes) unless that skip is the h a long skip
 // still needs.
 //
-// Determinism: one output value is bias, then for channel pairs (2p, 2p + 1) ascending, for taps ascending, one two-term MFMA
-// step (even channel, then odd channel); the head is bias, then channels ascending, then taps, as fmaf; a skip add is one fmaf
+// Determinism: the summation orders are those of sr_conv_mfma.h (conv_mfma_mainloop, head_accumulate); a skip add is one fmaf
 // after the chain.  The order does not depend on where the output lies in a block or a sub-tile.
 //
 // Weights are caller-supplied (sr_resnet_create); nothing is fetched.
@@ -28,15 +27,11 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <set>
 #include <vector>
 
-#include "sr_ctx.h"
+#include "sr_conv_mfma.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4v __attribute__((ext_vector_type(4)));
 
 constexpr size_t RN_WORKSPACE_CAP = (size_t)1 << 30;   // tile = 0: the largest sub-tile whose three buffers stay under 1 GiB
 constexpr int RN_MAX_TILE = 2048, RN_TILE_STEP = 32;
@@ -66,30 +61,8 @@ __global__ __launch_bounds__(256) void k_rn_head(const unsigned char *__restrict
     __syncthreads();
     const int lx = blockIdx.x * 64 + threadIdx.x, ly = blockIdx.y * 4 + threadIdx.y, ct = blockIdx.z;
     if (lx >= cols || ly >= rows) return;
-    const int oy = ya + ly, ox = xa + lx;
-    wt += (size_t)ct * 27 * 64;
-    bias += ct * 64;
     float acc[64];
-#pragma unroll
-    for (int co = 0; co < 64; ++co) acc[co] = bias[co];
-#pragma unroll 1
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll 1
-        for (int ky = 0; ky < 3; ++ky) {
-            const int gy = oy - 1 + ky;
-            const bool yok = gy >= 0 && gy < H;
-            const unsigned char *row = img + (size_t)(yok ? gy : 0) * stride;
-#pragma unroll 1
-            for (int kx = 0; kx < 3; ++kx) {
-                const int gx = ox - 1 + kx;
-                float v = 0.0f;
-                if (yok && gx >= 0 && gx < W) v = lut[c][row[(size_t)gx * 3 + c]];
-                const float *wp = wt + ((size_t)c * 9 + ky * 3 + kx) * 64;
-#pragma unroll
-                for (int co = 0; co < 64; ++co) acc[co] = fmaf(wp[co], v, acc[co]);
-            }
-        }
-    }
+    head_accumulate<256>(img, stride, H, W, wt, bias, ct, &lut[0][0], ya + ly, xa + lx, acc);
     float *o = out + (size_t)ct * 64 * plane + (size_t)ly * pitch + lx;
 #pragma unroll
     for (int co = 0; co < 64; ++co) {
@@ -129,8 +102,8 @@ __device__ __forceinline__ float rn_bilinear(const unsigned char *r0, const unsi
 
 // ---------------------------------------------------------------------------------------------------------------
 // 3 x 3 implicit-GEMM convolution on v_mfma_f32_32x32x2_f32, stride 1, zero padding 1 at the image border.
-//   GEMM view, operand layout, block shape (4 waves = 8 output rows x 32 columns, wave w owns rows 2w, 2w + 1) and LDS
-//   staging are those of k_sn_conv (sr_srnet.hip); NC2 = 32-cout halves per block (2, the last convolution 1).
+//   conv_mfma_mainloop<3, 8, NC2, true> (sr_conv_mfma.h) plus an epilogue; NC2 = 32-cout halves per block (2, the last
+//   convolution 1).
 //   RN_SLOPE     slope, planar store
 //   RN_SKIP      fmaf(res_scale, y, skip), planar store
 //   RN_SHUF2/3   couts F r^2 in tiles of 64; cout co goes to channel co / r^2 at (r row + (co % r^2) / r, r col + co % r) of
@@ -144,102 +117,24 @@ __global__ __launch_bounds__(256) void k_rn_conv(const float *__restrict__ in, l
                                                  const float *__restrict__ bias, float *out, long long out_plane, int out_pitch,
                                                  int out_ya, int out_xa, int rows, int cols, RnEpi ep)
 {
-    constexpr int CC = 8, T = 9, NC = NC2 * 32;
-    constexpr int PH = 8 + 2, PW = 32 + 2;
-    constexpr int NPATCH = CC * PH * PW, NW4 = CC * T * NC / 4;        // patch floats, weight float4s per chunk
-    constexpr int PE = (NPATCH + 255) / 256, WE = (NW4 + 255) / 256;   // per-thread staging counts
-    __shared__ __attribute__((aligned(16))) float s_patch[NPATCH];
-    __shared__ __attribute__((aligned(16))) float s_w[CC * T * NC];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
-    const int ox0 = blockIdx.x * 32, oy0 = blockIdx.y * 8;              // block origin inside the output range
-    const int ct = blockIdx.z;                                          // cout tile of NC
-    const int nchunk = cin / CC;
-
-    // staging map of this thread: patch element e -> (channel, row, col) is the same for every chunk
-    int p_off[PE];
-    unsigned p_ok = 0;
-#pragma unroll
-    for (int i = 0; i < PE; ++i) {
-        const int e = tid + i * 256;
-        const int c = e / (PH * PW), r = (e / PW) % PH, x = e % PW;
-        const int gy = out_ya + oy0 - 1 + r, gx = out_xa + ox0 - 1 + x;   // global index in the input layer
-        // inside the image (else: zero padding) and inside what the input buffer holds (beyond it only masked outputs read)
-        const bool ok = e < NPATCH && gy >= 0 && gy < H_in && gx >= 0 && gx < W_in && gy >= in_ya && gy - in_ya < in_rows &&
-                        gx >= in_xa && gx - in_xa < in_cols;
-        p_off[i] = ok ? (int)((long long)c * in_plane + (long long)(gy - in_ya) * in_pitch + (gx - in_xa)) : 0;
-        if (ok) p_ok |= 1u << i;
-    }
-    const f4v *wsrc = (const f4v *)(wslab + (size_t)ct * nchunk * (CC * T * NC));
-
+    constexpr int NC = NC2 * 32;
+    const MfmaLane ln = mfma_lane();
+    const int half = ln.half, ct = ln.ct;
     f32x16 acc[NC2][2];
-#pragma unroll
-    for (int c2 = 0; c2 < NC2; ++c2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float b = bias[ct * NC + c2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
-            acc[c2][0][r] = b;
-            acc[c2][1][r] = b;
-        }
-
-    float pv[PE];
-    f4v wv[WE];
-    auto load_chunk = [&](int ch) {
-        const float *ib = in + (size_t)ch * CC * in_plane;
-#pragma unroll
-        for (int i = 0; i < PE; ++i) pv[i] = (p_ok >> i) & 1u ? ib[p_off[i]] : 0.0f;
-        const f4v *wb = wsrc + (size_t)ch * NW4;
-#pragma unroll
-        for (int i = 0; i < WE; ++i) {
-            const int e = tid + i * 256;
-            wv[i] = e < NW4 ? wb[e] : f4v{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    load_chunk(0);
-    // lane bases: the k-half selects the odd channel of a pair
-    const float *a_base = s_w + half * (T * NC) + l32;
-    const float *b_base = s_patch + half * (PH * PW) + (2 * wave) * PW + l32;
-#pragma unroll 1
-    for (int ch = 0; ch < nchunk; ++ch) {
-        __syncthreads();                                   // the previous chunk has been consumed
-#pragma unroll
-        for (int i = 0; i < PE; ++i) {
-            const int e = tid + i * 256;
-            if (e < NPATCH) s_patch[e] = pv[i];
-        }
-#pragma unroll
-        for (int i = 0; i < WE; ++i) {
-            const int e = tid + i * 256;
-            if (e < NW4) ((f4v *)s_w)[e] = wv[i];
-        }
-        __syncthreads();
-        if (ch + 1 < nchunk) load_chunk(ch + 1);           // in flight under the MFMAs below
-#pragma unroll
-        for (int cp = 0; cp < CC / 2; ++cp)
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const int dy = t / 3, dx = t % 3;
-                const float b0 = b_base[2 * cp * PH * PW + dy * PW + dx], b1 = b_base[2 * cp * PH * PW + (dy + 1) * PW + dx];
-#pragma unroll
-                for (int c2 = 0; c2 < NC2; ++c2) {
-                    const float a = a_base[(2 * cp * T + t) * NC + c2 * 32];
-                    acc[c2][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc[c2][0], 0, 0, 0);
-                    acc[c2][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc[c2][1], 0, 0, 0);
-                }
-            }
-    }
-    const int col = ox0 + l32;
+    conv_mfma_mainloop<3, 8, NC2, true>(ln, in, in_plane, in_pitch, in_ya, in_xa, in_rows, in_cols, H_in, W_in, cin, wslab, bias, out_ya,
+                                        out_xa, acc);
+    const int col = ln.ox0 + ln.l32;
     if (col >= cols) return;
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
-        const int row = oy0 + 2 * wave + pr;
+        const int row = ln.oy0 + 2 * ln.wave + pr;
         if (row >= rows) continue;
         if constexpr (EPI == RN_SLOPE) {
 #pragma unroll
             for (int c2 = 0; c2 < NC2; ++c2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int co = ct * NC + c2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int co = ct * NC + mfma_cout(c2, r, half);
                     const float y = acc[c2][pr][r];
                     out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = y >= 0.0f ? y : ep.slope * y;
                 }
@@ -249,7 +144,7 @@ __global__ __launch_bounds__(256) void k_rn_conv(const float *__restrict__ in, l
             for (int c2 = 0; c2 < NC2; ++c2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int co = ct * NC + c2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int co = ct * NC + mfma_cout(c2, r, half);
                     const float sk = ep.skip[(size_t)co * ep.skip_plane + so];
                     out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = fmaf(ep.res_scale, acc[c2][pr][r], sk);
                 }
@@ -259,7 +154,7 @@ __global__ __launch_bounds__(256) void k_rn_conv(const float *__restrict__ in, l
             for (int c2 = 0; c2 < NC2; ++c2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int co = ct * NC + c2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int co = ct * NC + mfma_cout(c2, r, half);
                     const int c = co / (R * R), rem = co % (R * R), dy = rem / R, dx = rem % R;
                     const float y = acc[c2][pr][r];
                     out[(size_t)c * out_plane + ((size_t)row * R + dy) * out_pitch + (size_t)col * R + dx] = y >= 0.0f ? y : ep.slope * y;
@@ -433,14 +328,7 @@ struct sr_resnet_model {
     size_t buf_floats = 0;
 };
 
-static std::mutex g_rn_mu;
-static std::set<const void *> g_rn_live;
-
-static bool rn_is_live(const sr_resnet_model *m)
-{
-    std::lock_guard<std::mutex> lk(g_rn_mu);
-    return m && g_rn_live.count(m) != 0;
-}
+static LiveSet g_rn_live;
 
 template <int NC2, int EPI>
 static void rn_launch(hipStream_t st, const RnTen &in, int H_in, int W_in, int F, int ncout_tiles, const float *dw, const float *db, float *out,
@@ -453,36 +341,17 @@ static void rn_launch(hipStream_t st, const RnTen &in, int H_in, int W_in, int F
 static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride,
                       int tile, bool u8, const char *who)
 {
-    if (!rn_is_live(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
+    if (!g_rn_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
     sr_ctx *ctx = m->ctx;
     CTX_ENTER(ctx);
-    if (!d_src || !d_dst) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null argument", who);
-    RnGeom g;
-    int rc = rn_geometry(who, m->d, m->ops, h, w, tile, g);
-    if (rc) return rc;
     const int F = m->d.n_feat, S = m->d.scale;
-    const int64_t esz = u8 ? 1 : 4;
-    if (src_stride < (int64_t)w * 3) return sr_set_error(SR_ERR_SHAPE, "%s: source stride smaller than a row", who);
-    if (dst_stride < (int64_t)w * S * 3 * esz) return sr_set_error(SR_ERR_SHAPE, "%s: destination stride smaller than a row", who);
-    if (!u8 && (dst_stride % 4 || (uintptr_t)d_dst % 4))
-        return sr_set_error(SR_ERR_INVALID_ARG, "%s: fp32 destination pointer and stride must be multiples of 4 bytes", who);
-    const size_t need_floats = (size_t)g.plane * F;
-    if (need_floats > m->buf_floats) {
-        HIPCHK(stream_sync(ctx));
-        for (auto &p : m->buf) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-        }
-        m->buf_floats = 0;
-        for (auto &p : m->buf) {
-            hipError_t e = hipMalloc((void **)&p, need_floats * sizeof(float));
-            if (e != hipSuccess)
-                return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP,
-                                    "%s: activation buffers (3 x %zu MB; use a smaller tile): %s", who, need_floats * 4 >> 20,
-                                    hipGetErrorString(e));
-        }
-        m->buf_floats = need_floats;
-    }
+    int rc = check_sr_forward_args(who, d_src, src_stride, w, d_dst, dst_stride, S, u8);
+    if (rc) return rc;
+    RnGeom g;
+    rc = rn_geometry(who, m->d, m->ops, h, w, tile, g);
+    if (rc) return rc;
+    rc = ensure_activation_buffers(ctx, m->buf, 3, m->buf_floats, (size_t)g.plane * F, who);
+    if (rc) return rc;
     const std::vector<RnOp> &ops = m->ops;
     const size_t n = ops.size();
     const RnAffine af = {{m->d.mean[0], m->d.mean[1], m->d.mean[2]}, m->d.range};
@@ -610,47 +479,20 @@ int sr_resnet_create(sr_ctx *ctx, const sr_resnet_desc *desc, const float *const
     M->ctx = ctx;
     M->d = *desc;
     M->ops = ops;
-    {
-        std::lock_guard<std::mutex> lk(g_rn_mu);
-        g_rn_live.insert(M);
-    }
+    g_rn_live.insert(M);
     auto fail = [&](int code, const char *what) {
         sr_set_error(code, "sr_resnet_create: %s", what);
         sr_resnet_destroy(M);
         return code;
     };
-    auto upload = [&](const std::vector<float> &v, std::vector<float *> &dst) {
-        float *d = nullptr;
-        if (hipMalloc((void **)&d, v.size() * sizeof(float)) != hipSuccess) return SR_ERR_OOM;
-        dst.push_back(d);
-        return hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? SR_OK : SR_ERR_HIP;
-    };
     const int F = desc->n_feat;
     for (int k = 0; k < n_conv; ++k) {
-        const float *w = h_w[k];
-        std::vector<float> arranged, b;
-        if (ops[k].kind == OP_HEAD) {                            // head: [cout tile][c][tap][64]
-            arranged.resize((size_t)F * 27);
-            for (int co = 0; co < F; ++co)
-                for (int c = 0; c < 3; ++c)
-                    for (int t = 0; t < 9; ++t)
-                        arranged[(((size_t)(co / 64) * 3 + c) * 9 + t) * 64 + co % 64] = w[((size_t)co * 3 + c) * 9 + t];
-            b.assign(h_b[k], h_b[k] + F);
-        } else {                                                 // MFMA: [cout tile][chunk][c in chunk][tap][NC], zero-padded couts
-            const bool last = ops[k].kind == OP_LAST;
-            const int cout = last ? 3 : F * ops[k].r * ops[k].r, NC = last ? 32 : 64, nct = last ? 1 : cout / 64, nch = F / 8;
-            arranged.assign((size_t)nct * NC * F * 9, 0.0f);
-            b.assign((size_t)nct * NC, 0.0f);
-            for (int co = 0; co < cout; ++co) {
-                b[co] = h_b[k][co];
-                for (int ci = 0; ci < F; ++ci)
-                    for (int t = 0; t < 9; ++t)
-                        arranged[(((((size_t)(co / NC) * nch + ci / 8) * 8 + ci % 8) * 9 + t) * NC) + co % NC] =
-                            w[((size_t)co * F + ci) * 9 + t];
-            }
-        }
-        if ((rc = upload(arranged, M->d_w)) != SR_OK) return fail(rc, "weight upload");
-        if ((rc = upload(b, M->d_b)) != SR_OK) return fail(rc, "bias upload");
+        const bool last = ops[k].kind == OP_LAST;
+        MfmaWeights a;
+        if (ops[k].kind == OP_HEAD) a = {arrange_head_weights(h_w[k], F), std::vector<float>(h_b[k], h_b[k] + F)};
+        else a = arrange_mfma_weights(h_w[k], h_b[k], last ? 3 : F * ops[k].r * ops[k].r, F, 9, 8, last ? 32 : 64);
+        if ((rc = upload_floats(a.w, M->d_w)) != SR_OK) return fail(rc, "weight upload");
+        if ((rc = upload_floats(a.b, M->d_b)) != SR_OK) return fail(rc, "bias upload");
     }
     *out = M;
     return SR_OK;
@@ -659,10 +501,7 @@ int sr_resnet_create(sr_ctx *ctx, const sr_resnet_desc *desc, const float *const
 int sr_resnet_destroy(sr_resnet_model *m)
 {
     if (!m) return SR_OK;
-    {
-        std::lock_guard<std::mutex> lk(g_rn_mu);
-        if (!g_rn_live.erase(m)) return SR_OK;
-    }
+    if (!g_rn_live.erase(m)) return SR_OK;
     if (ctx_is_live(m->ctx)) {
         Guard g(m->ctx);
         (void)hipStreamSynchronize(m->ctx->stream);

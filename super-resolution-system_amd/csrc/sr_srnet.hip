@@ -7,38 +7,32 @@
 //                  (one fp32 add) and the store: HWC fp32 unclamped, or HWC u8 rintf(clamp(o, 0, 1) * 255)
 //
 // Everything is fp32 (fp32 in, fp32 accumulate): the F -> F and F -> 3 s^2 layers are implicit GEMMs on
-// v_mfma_f32_32x32x2_f32 with the tiling of sr_lpips.hip's k_lp_conv_mfma (a sibling kernel: the LPIPS instruction stream is
-// left alone), the 3 -> F head is a direct VALU kernel.  The 3 s^2-channel tensor is never written.
+// v_mfma_f32_32x32x2_f32 (the mainloop of sr_conv_mfma.h, shared with sr_lpips.hip and sr_resnet.hip), the 3 -> F head is a
+// direct VALU kernel.  The 3 s^2-channel tensor is never written.
 //
 // Memory: activations are planar fp32 [F][rows][pitch] in two ping-pong buffers owned by the model.  The image is walked in
 // square sub-tiles of the INPUT; a sub-tile recomputes a halo of D + 2 input pixels (layer k's valid extent is the sub-tile
 // grown by D + 1 - k, clipped to the image), and zero padding is applied per layer at the true image border only, so every
 // value equals the unstreamed forward's.
 //
-// Determinism: one output value is bias, then for channel pairs (2p, 2p + 1) ascending, for taps ascending, one
-// two-term MFMA step (even channel, then odd channel); the head is bias, then channels ascending, then taps, as fmaf.  The
-// order does not depend on where the output lies in a block or a sub-tile: streamed and unstreamed results are bit-equal.
+// Determinism: the summation orders are those of sr_conv_mfma.h (conv_mfma_mainloop, head_accumulate); neither depends on
+// where the output lies in a block or a sub-tile: streamed and unstreamed results are bit-equal.
 //
 // Weights are caller-supplied (sr_srnet_create); nothing is fetched.
 #include <algorithm>
 #include <climits>
 #include <cstring>
-#include <set>
 #include <vector>
 
-#include "sr_ctx.h"
+#include "sr_conv_mfma.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4v __attribute__((ext_vector_type(4)));
 
 constexpr int SN_DEFAULT_TILE = 2048;      // tile = 0: one pipeline tile is one sub-tile (no halo recompute)
 
 // ---------------------------------------------------------------------------------------------------------------
 // Head (3 -> F) from the u8 image: one thread = one output pixel x 64 output channels (blockIdx.z: 64-cout tile).
-// x = u8 / 255 inside the image, 0 outside (the layer's zero padding); the 256 values are tabulated in LDS with exactly
-// that fp32 division.  Weights are [cout tile][c][tap][64]: the 64 multipliers of one input value are wave-uniform.
+// x = u8 / 255 (tabulated in LDS with exactly that fp32 division) through head_accumulate, then the per-channel slope.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sn_head(const unsigned char *__restrict__ img, long long stride, int H, int W,
                                                  const float *__restrict__ wt, const float *__restrict__ bias,
@@ -51,31 +45,9 @@ __global__ __launch_bounds__(256) void k_sn_head(const unsigned char *__restrict
     __syncthreads();
     const int lx = blockIdx.x * 64 + threadIdx.x, ly = blockIdx.y * 4 + threadIdx.y, ct = blockIdx.z;
     if (lx >= cols || ly >= rows) return;
-    const int oy = ya + ly, ox = xa + lx;
-    wt += (size_t)ct * 27 * 64;
-    bias += ct * 64;
     slope += ct * 64;
     float acc[64];
-#pragma unroll
-    for (int co = 0; co < 64; ++co) acc[co] = bias[co];
-#pragma unroll 1
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll 1
-        for (int ky = 0; ky < 3; ++ky) {
-            const int gy = oy - 1 + ky;
-            const bool yok = gy >= 0 && gy < H;
-            const unsigned char *row = img + (size_t)(yok ? gy : 0) * stride;
-#pragma unroll 1
-            for (int kx = 0; kx < 3; ++kx) {
-                const int gx = ox - 1 + kx;
-                float v = 0.0f;
-                if (yok && gx >= 0 && gx < W) v = lut[row[(size_t)gx * 3 + c]];
-                const float *wp = wt + ((size_t)c * 9 + ky * 3 + kx) * 64;
-#pragma unroll
-                for (int co = 0; co < 64; ++co) acc[co] = fmaf(wp[co], v, acc[co]);
-            }
-        }
-    }
+    head_accumulate<0>(img, stride, H, W, wt, bias, ct, lut, ya + ly, xa + lx, acc);
     float *o = out + (size_t)ct * 64 * plane + (size_t)ly * pitch + lx;
 #pragma unroll
     for (int co = 0; co < 64; ++co) {
@@ -94,8 +66,7 @@ struct SnTail {
 
 // ---------------------------------------------------------------------------------------------------------------
 // 3 x 3 implicit-GEMM convolution on v_mfma_f32_32x32x2_f32, stride 1, zero padding 1 at the image border.
-//   GEMM view, operand layout, block shape (4 waves = 8 output rows x 32 columns, wave w owns rows 2w, 2w + 1) and LDS
-//   staging are those of k_lp_conv_mfma<3, 8> (sr_lpips.hip); NC2 = 32-cout halves per block.
+//   conv_mfma_mainloop<3, 8, NC2, true> (sr_conv_mfma.h) plus an epilogue; NC2 = 32-cout halves per block.
 //   S == 0: body layer, NC2 = 2, epilogue = per-channel slope, planar store.
 //   S >= 1: tail layer, couts 3 S^2 zero-padded to 32 NC2; epilogue = pixel shuffle + base add + HWC store (U8: clamp,
 //           scale, round half even).  out_ya / out_xa are then the sub-tile's own origin in the image.
@@ -107,102 +78,24 @@ __global__ __launch_bounds__(256) void k_sn_conv(const float *__restrict__ in, l
                                                  float *__restrict__ out, long long out_plane, int out_pitch, int out_ya,
                                                  int out_xa, int rows, int cols, SnTail tail)
 {
-    constexpr int CC = 8, T = 9, NC = NC2 * 32;
-    constexpr int PH = 8 + 2, PW = 32 + 2;
-    constexpr int NPATCH = CC * PH * PW, NW4 = CC * T * NC / 4;        // patch floats, weight float4s per chunk
-    constexpr int PE = (NPATCH + 255) / 256, WE = (NW4 + 255) / 256;   // per-thread staging counts
-    __shared__ __attribute__((aligned(16))) float s_patch[NPATCH];
-    __shared__ __attribute__((aligned(16))) float s_w[CC * T * NC];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
-    const int ox0 = blockIdx.x * 32, oy0 = blockIdx.y * 8;              // block origin inside the output range
-    const int ct = blockIdx.z;                                          // cout tile of NC
-    const int nchunk = cin / CC;
-
-    // staging map of this thread: patch element e -> (channel, row, col) is the same for every chunk
-    int p_off[PE];
-    unsigned p_ok = 0;
-#pragma unroll
-    for (int i = 0; i < PE; ++i) {
-        const int e = tid + i * 256;
-        const int c = e / (PH * PW), r = (e / PW) % PH, x = e % PW;
-        const int gy = out_ya + oy0 - 1 + r, gx = out_xa + ox0 - 1 + x;   // global index in the input layer
-        // inside the image (else: zero padding) and inside what the input buffer holds (beyond it only masked outputs read)
-        const bool ok = e < NPATCH && gy >= 0 && gy < H_in && gx >= 0 && gx < W_in && gy >= in_ya && gy - in_ya < in_rows &&
-                        gx >= in_xa && gx - in_xa < in_cols;
-        p_off[i] = ok ? (int)((long long)c * in_plane + (long long)(gy - in_ya) * in_pitch + (gx - in_xa)) : 0;
-        if (ok) p_ok |= 1u << i;
-    }
-    const f4v *wsrc = (const f4v *)(wslab + (size_t)ct * nchunk * (CC * T * NC));
-
+    constexpr int NC = NC2 * 32;
+    const MfmaLane ln = mfma_lane();
+    const int half = ln.half, ct = ln.ct;
     f32x16 acc[NC2][2];
-#pragma unroll
-    for (int c2 = 0; c2 < NC2; ++c2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float b = bias[ct * NC + c2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
-            acc[c2][0][r] = b;
-            acc[c2][1][r] = b;
-        }
-
-    float pv[PE];
-    f4v wv[WE];
-    auto load_chunk = [&](int ch) {
-        const float *ib = in + (size_t)ch * CC * in_plane;
-#pragma unroll
-        for (int i = 0; i < PE; ++i) pv[i] = (p_ok >> i) & 1u ? ib[p_off[i]] : 0.0f;
-        const f4v *wb = wsrc + (size_t)ch * NW4;
-#pragma unroll
-        for (int i = 0; i < WE; ++i) {
-            const int e = tid + i * 256;
-            wv[i] = e < NW4 ? wb[e] : f4v{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    load_chunk(0);
-    // lane bases: the k-half selects the odd channel of a pair
-    const float *a_base = s_w + half * (T * NC) + l32;
-    const float *b_base = s_patch + half * (PH * PW) + (2 * wave) * PW + l32;
-#pragma unroll 1
-    for (int ch = 0; ch < nchunk; ++ch) {
-        __syncthreads();                                   // the previous chunk has been consumed
-#pragma unroll
-        for (int i = 0; i < PE; ++i) {
-            const int e = tid + i * 256;
-            if (e < NPATCH) s_patch[e] = pv[i];
-        }
-#pragma unroll
-        for (int i = 0; i < WE; ++i) {
-            const int e = tid + i * 256;
-            if (e < NW4) ((f4v *)s_w)[e] = wv[i];
-        }
-        __syncthreads();
-        if (ch + 1 < nchunk) load_chunk(ch + 1);           // in flight under the MFMAs below
-#pragma unroll
-        for (int cp = 0; cp < CC / 2; ++cp)
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const int dy = t / 3, dx = t % 3;
-                const float b0 = b_base[2 * cp * PH * PW + dy * PW + dx], b1 = b_base[2 * cp * PH * PW + (dy + 1) * PW + dx];
-#pragma unroll
-                for (int c2 = 0; c2 < NC2; ++c2) {
-                    const float a = a_base[(2 * cp * T + t) * NC + c2 * 32];
-                    acc[c2][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc[c2][0], 0, 0, 0);
-                    acc[c2][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc[c2][1], 0, 0, 0);
-                }
-            }
-    }
-    const int col = ox0 + l32;
+    conv_mfma_mainloop<3, 8, NC2, true>(ln, in, in_plane, in_pitch, in_ya, in_xa, in_rows, in_cols, H_in, W_in, cin, wslab, bias, out_ya,
+                                        out_xa, acc);
+    const int col = ln.ox0 + ln.l32;
     if (col >= cols) return;
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
-        const int row = oy0 + 2 * wave + pr;
+        const int row = ln.oy0 + 2 * ln.wave + pr;
         if (row >= rows) continue;
         if constexpr (S == 0) {                            // slope activation, planar store
 #pragma unroll
             for (int c2 = 0; c2 < NC2; ++c2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int co = ct * NC + c2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int co = ct * NC + mfma_cout(c2, r, half);
                     const float y = acc[c2][pr][r];
                     out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = y >= 0.0f ? y : slope[co] * y;
                 }
@@ -215,7 +108,7 @@ __global__ __launch_bounds__(256) void k_sn_conv(const float *__restrict__ in, l
             for (int c2 = 0; c2 < NC2; ++c2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int co = c2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int co = mfma_cout(c2, r, half);
                     if (co >= 3 * S * S) continue;
                     const int c = co / (S * S), rem = co % (S * S), dy = rem / S, dx = rem % S;
                     const float o = acc[c2][pr][r] + (c == 0 ? x0 : (c == 1 ? x1 : x2));
@@ -272,14 +165,7 @@ struct sr_srnet_model {
     size_t buf_floats = 0;
 };
 
-static std::mutex g_sn_mu;
-static std::set<const void *> g_sn_live;
-
-static bool sn_is_live(const sr_srnet_model *m)
-{
-    std::lock_guard<std::mutex> lk(g_sn_mu);
-    return m && g_sn_live.count(m) != 0;
-}
+static LiveSet g_sn_live;
 
 template <int S, bool U8>
 static void sn_launch_tail(dim3 grid, hipStream_t st, const float *src, long long plane, int pitch, int in_ya, int in_xa, int in_rows,
@@ -293,36 +179,17 @@ static void sn_launch_tail(dim3 grid, hipStream_t st, const float *src, long lon
 static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride,
                       int tile, bool u8, const char *who)
 {
-    if (!sn_is_live(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
+    if (!g_sn_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
     sr_ctx *ctx = m->ctx;
     CTX_ENTER(ctx);
-    if (!d_src || !d_dst) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null argument", who);
-    SnGeom g;
-    int rc = sn_geometry(who, h, w, m->D, m->S, tile, g);
-    if (rc) return rc;
     const int F = m->F, D = m->D, S = m->S;
-    const int64_t esz = u8 ? 1 : 4;
-    if (src_stride < (int64_t)w * 3) return sr_set_error(SR_ERR_SHAPE, "%s: source stride smaller than a row", who);
-    if (dst_stride < (int64_t)w * S * 3 * esz) return sr_set_error(SR_ERR_SHAPE, "%s: destination stride smaller than a row", who);
-    if (!u8 && (dst_stride % 4 || (uintptr_t)d_dst % 4))
-        return sr_set_error(SR_ERR_INVALID_ARG, "%s: fp32 destination pointer and stride must be multiples of 4 bytes", who);
-    const size_t need_floats = (size_t)g.plane * F;
-    if (need_floats > m->buf_floats) {
-        HIPCHK(stream_sync(ctx));
-        for (auto &p : m->buf) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-        }
-        m->buf_floats = 0;
-        for (auto &p : m->buf) {
-            hipError_t e = hipMalloc((void **)&p, need_floats * sizeof(float));
-            if (e != hipSuccess)
-                return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP,
-                                    "%s: activation buffers (2 x %zu MB; use a smaller tile): %s", who, need_floats * 4 >> 20,
-                                    hipGetErrorString(e));
-        }
-        m->buf_floats = need_floats;
-    }
+    int rc = check_sr_forward_args(who, d_src, src_stride, w, d_dst, dst_stride, S, u8);
+    if (rc) return rc;
+    SnGeom g;
+    rc = sn_geometry(who, h, w, D, S, tile, g);
+    if (rc) return rc;
+    rc = ensure_activation_buffers(ctx, m->buf, 2, m->buf_floats, (size_t)g.plane * F, who);
+    if (rc) return rc;
     const SnTail tail = {d_src, (long long)src_stride, d_dst, (long long)dst_stride};
     for (int ty = 0; ty < g.tiles_y; ++ty)
         for (int tx = 0; tx < g.tiles_x; ++tx) {
@@ -360,18 +227,13 @@ static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_strid
             {
                 ProfScope ps(ctx, "srnet_tail");
                 const dim3 grid((cols + 31) / 32, (rows + 7) / 8, 1);
-#define SN_TAIL(SC)                                                                                                            \
-    if (u8) sn_launch_tail<SC, true>(grid, ctx->stream, m->buf[cur], plane, pitch, in_ya, in_xa, in_rows, in_cols, h, w, F, m->d_w[D + 1],       \
-                                     m->d_b[D + 1], ya, xa, rows, cols, tail);                                                 \
-    else sn_launch_tail<SC, false>(grid, ctx->stream, m->buf[cur], plane, pitch, in_ya, in_xa, in_rows, in_cols, h, w, F, m->d_w[D + 1],         \
-                                   m->d_b[D + 1], ya, xa, rows, cols, tail)
-                switch (S) {
-                case 1: SN_TAIL(1); break;
-                case 2: SN_TAIL(2); break;
-                case 3: SN_TAIL(3); break;
-                default: SN_TAIL(4); break;
-                }
-#undef SN_TAIL
+                using TailFn = decltype(&sn_launch_tail<1, false>);
+                static const TailFn launch[4][2] = {{sn_launch_tail<1, false>, sn_launch_tail<1, true>},
+                                                    {sn_launch_tail<2, false>, sn_launch_tail<2, true>},
+                                                    {sn_launch_tail<3, false>, sn_launch_tail<3, true>},
+                                                    {sn_launch_tail<4, false>, sn_launch_tail<4, true>}};
+                launch[S - 1][u8 ? 1 : 0](grid, ctx->stream, m->buf[cur], plane, pitch, in_ya, in_xa, in_rows, in_cols, h, w, F, m->d_w[D + 1],
+                                  m->d_b[D + 1], ya, xa, rows, cols, tail);
             }
             rc = check_launch(who);
             if (rc) return rc;
@@ -396,47 +258,20 @@ int sr_srnet_create(sr_ctx *ctx, int n_feat, int n_body, int scale, const float 
     sr_srnet_model *M = new sr_srnet_model();
     M->ctx = ctx;
     M->F = F; M->D = D; M->S = S;
-    {
-        std::lock_guard<std::mutex> lk(g_sn_mu);
-        g_sn_live.insert(M);
-    }
+    g_sn_live.insert(M);
     auto fail = [&](int code, const char *what) {
         sr_set_error(code, "sr_srnet_create: %s", what);
         sr_srnet_destroy(M);
         return code;
     };
-    auto upload = [&](const std::vector<float> &v, std::vector<float *> &dst) {
-        float *d = nullptr;
-        if (hipMalloc((void **)&d, v.size() * sizeof(float)) != hipSuccess) return SR_ERR_OOM;
-        dst.push_back(d);
-        return hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? SR_OK : SR_ERR_HIP;
-    };
     const int tail_c = 3 * S * S, tail_nc = tail_c > 32 ? 64 : 32;
     for (int k = 0; k < nl; ++k) {
-        const float *w = h_w[k];
-        std::vector<float> arranged, b;
-        if (k == 0) {                                            // head: [cout tile][c][tap][64]
-            arranged.resize((size_t)F * 27);
-            for (int co = 0; co < F; ++co)
-                for (int c = 0; c < 3; ++c)
-                    for (int t = 0; t < 9; ++t)
-                        arranged[(((size_t)(co / 64) * 3 + c) * 9 + t) * 64 + co % 64] = w[((size_t)co * 3 + c) * 9 + t];
-            b.assign(h_b[k], h_b[k] + F);
-        } else {                                                 // MFMA: [cout tile][chunk][c in chunk][tap][NC], zero-padded couts
-            const int cout = k <= D ? F : tail_c, NC = k <= D ? 64 : tail_nc, nct = k <= D ? F / 64 : 1, nch = F / 8;
-            arranged.assign((size_t)nct * NC * F * 9, 0.0f);
-            b.assign((size_t)nct * NC, 0.0f);
-            for (int co = 0; co < cout; ++co) {
-                b[co] = h_b[k][co];
-                for (int ci = 0; ci < F; ++ci)
-                    for (int t = 0; t < 9; ++t)
-                        arranged[(((((size_t)(co / NC) * nch + ci / 8) * 8 + ci % 8) * 9 + t) * NC) + co % NC] =
-                            w[((size_t)co * F + ci) * 9 + t];
-            }
-        }
-        if ((rc = upload(arranged, M->d_w)) != SR_OK) return fail(rc, "weight upload");
-        if ((rc = upload(b, M->d_b)) != SR_OK) return fail(rc, "bias upload");
-        if (k <= D && (rc = upload(std::vector<float>(h_slope[k], h_slope[k] + F), M->d_slope)) != SR_OK) return fail(rc, "slope upload");
+        MfmaWeights a;
+        if (k == 0) a = {arrange_head_weights(h_w[k], F), std::vector<float>(h_b[k], h_b[k] + F)};
+        else a = arrange_mfma_weights(h_w[k], h_b[k], k <= D ? F : tail_c, F, 9, 8, k <= D ? 64 : tail_nc);
+        if ((rc = upload_floats(a.w, M->d_w)) != SR_OK) return fail(rc, "weight upload");
+        if ((rc = upload_floats(a.b, M->d_b)) != SR_OK) return fail(rc, "bias upload");
+        if (k <= D && (rc = upload_floats(std::vector<float>(h_slope[k], h_slope[k] + F), M->d_slope)) != SR_OK) return fail(rc, "slope upload");
     }
     *out = M;
     return SR_OK;
@@ -445,10 +280,7 @@ int sr_srnet_create(sr_ctx *ctx, int n_feat, int n_body, int scale, const float 
 int sr_srnet_destroy(sr_srnet_model *m)
 {
     if (!m) return SR_OK;
-    {
-        std::lock_guard<std::mutex> lk(g_sn_mu);
-        if (!g_sn_live.erase(m)) return SR_OK;
-    }
+    if (!g_sn_live.erase(m)) return SR_OK;
     if (ctx_is_live(m->ctx)) {
         Guard g(m->ctx);
         (void)hipStreamSynchronize(m->ctx->stream);
