@@ -1,5 +1,6 @@
 // sr_ctx.h -- the device context shared by the .hip translation units of libsrhip.so (sr_engine.hip owns the
-// definitions; every other .hip file and sr_comm.cpp use them, the convolution networks through sr_conv_mfma.h).
+// definitions, except reduce_partials: sr_assess.hip; every other .hip file and sr_comm.cpp use them, the convolution
+// networks through sr_conv_mfma.h).
 // Internal: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -73,7 +74,8 @@ bool plan_describe(const sr_blend_plan *p, sr_ctx **ctx, int *n, int *cn);
 int ctx_scratch(sr_ctx *c, size_t bytes, void **out);
 hipEvent_t prof_event(sr_ctx *c);
 int check_launch(const char *what);
-// Deterministic tree sum of part[n][ncomp] -> pointer (inside the two ping-pong buffers) to the ncomp results.
+// Deterministic tree sum of part[n][ncomp] -> pointer (inside the two ping-pong buffers) to the ncomp results
+// (sr_assess.hip, beside k_reduce_partials).
 const double *reduce_partials(sr_ctx *ctx, const double *part, long long n, int ncomp, double *buf0, double *buf1);
 
 struct Guard {

@@ -1,4 +1,5 @@
-// Internal declarations shared by sr_host.cpp (pure host bookkeeping) and sr_engine.hip.
+// Internal declarations shared by sr_host.cpp (pure host bookkeeping) and the device sources (sr_engine.hip plans with
+// them; every .hip file reports errors through sr_set_error).
 #pragma once
 #include <cstdarg>
 #include <cstdio>

@@ -3,7 +3,7 @@
 // The reference delegates to the third-party package `lpips` (>= 0.1.4, requirements.txt:16): AlexNet / VGG16 feature
 // stacks, unit-normalised channel vectors, squared difference, learned 1x1 `lin` weights, spatial mean, sum over five
 // taps.  This is the one dense contraction of the tile -> blend -> assess path, so -- unlike everything in
-// sr_engine.hip -- it runs on the matrix cores: every convolution with Cin >= 64 is an implicit GEMM on
+// sr_engine.hip and sr_assess.hip -- it runs on the matrix cores: every convolution with Cin >= 64 is an implicit GEMM on
 // v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate: the reference's arithmetic is torch fp32, there is no reduced
 // precision anywhere).  The two 3-channel stem convolutions are a direct VALU kernel that also applies the u8 -> [-1, 1]
 // -> ScalingLayer preprocessing, so the fp32 input tensor is never materialised.

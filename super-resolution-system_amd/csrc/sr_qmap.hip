@@ -13,7 +13,7 @@
 //                 neighbours' vertical results through LDS.  Samples are added per column in row order; at the end the
 //                 thread stores its column sums into the slab ws[sum][chunk][column].
 //   k_qmap_cells  a block per cell adds the slab entries of the cell's chunks and columns in a fixed order.
-// fp64 throughout, like the rest of the assessment.  A plain separable form: k_assess_march (sr_engine.hip) stays the
+// fp64 throughout, like the rest of the assessment.  A plain separable form: k_assess_march (sr_assess.hip) stays the
 // tuned kernel of the global metrics.
 #include <algorithm>
 #include <cmath>
