@@ -14,8 +14,8 @@
 //
 // Numerics contract: integer sums are exact, and every fp32 expression is evaluated in the order written in
 // oracle/sr_oracle.c (build with -ffp-contract=off).  Between sr_engine.hip and this file fp64 is used only here, in the
-// SSIM kernels and the partial sums, where the reference computes in float64 (the seam scan alone finishes a window's
-// score in fp64 over there).
+// SSIM kernels and the partial sums, where the reference computes in float64 (in sr_tiles.hip the seam scan finishes a
+// window's score, and the feather merge forms its ramp weights, in fp64).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

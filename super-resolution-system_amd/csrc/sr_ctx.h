@@ -1,6 +1,6 @@
-// sr_ctx.h -- the device context shared by the .hip translation units of libsrhip.so (sr_engine.hip owns the
-// definitions, except reduce_partials: sr_assess.hip; every other .hip file and sr_comm.cpp use them, the convolution
-// networks through sr_conv_mfma.h).
+// sr_ctx.h -- the device context shared by the .hip translation units of libsrhip.so (sr_runtime.hip owns the
+// definitions, except plan_describe and destroy_plans_of: sr_engine.hip, and reduce_partials: sr_assess.hip; every
+// other .hip file and sr_comm.cpp use them, the convolution networks through sr_conv_mfma.h).
 // Internal: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -71,6 +71,8 @@ bool ctx_is_live(const sr_ctx *c);
 // null or destroyed.
 struct sr_blend_plan;
 bool plan_describe(const sr_blend_plan *p, sr_ctx **ctx, int *n, int *cn);
+// Destroys every live plan of the context (sr_engine.hip, which alone knows a plan's context; for sr_ctx_destroy).
+void destroy_plans_of(sr_ctx *ctx);
 int ctx_scratch(sr_ctx *c, size_t bytes, void **out);
 hipEvent_t prof_event(sr_ctx *c);
 int check_launch(const char *what);

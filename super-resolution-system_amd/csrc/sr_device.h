@@ -1,5 +1,6 @@
-// sr_device.h -- device helpers shared by sr_engine.hip (blend engine) and sr_assess.hip (quality assessment):
-// border rules, vector load / store typedefs and the integer RGB -> gray of cv2.cvtColor.
+// sr_device.h -- device helpers shared by sr_engine.hip (blend engine), sr_tiles.hip (stand-alone tile kernels) and
+// sr_assess.hip (quality assessment): border rules, vector load / store typedefs, the integer RGB -> gray of
+// cv2.cvtColor, the tile-source descriptor with its data-type tags, and the shared-reciprocal division.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,4 +51,46 @@ __device__ __forceinline__ int gray_rgb(int r, int g, int b, int shift)
 {
     return shift == 15 ? (r * 9798 + g * 19235 + b * 3735 + (1 << 14)) >> 15
                        : (r * 4899 + g * 9617 + b * 1868 + (1 << 13)) >> 14;
+}
+
+// Level-0 data of one tile (row 0, possibly virtual) and its row stride in bytes; the SRC_* tags select how a kernel
+// reads it (SRC_PLANAR, SRC_LUT: the engine's pyrDown sources).
+struct TileSrc {
+    const void *p;
+    long long stride;
+};
+
+enum { SRC_U8 = 0, SRC_F32 = 1, SRC_PLANAR = 2, SRC_LUT = 3 };
+
+// a / w for the channels of one pixel, IEEE-correct: exactly the fma chain the compiler emits for an fp32 division
+// (rcp, one Newton step, quotient, two residual corrections) without the v_div_scale / v_div_fixup wrapping, which is
+// the identity for these operands (w in [1e-6, n_tiles], |a| a few thousand at most) -- and with the reciprocal
+// refined once per pixel instead of once per channel.
+template <int CN>
+__device__ __forceinline__ void div_shared(const float (&a)[CN], float w, float (&q)[CN])
+{
+    float r = __builtin_amdgcn_rcpf(w);
+    r = fmaf(fmaf(-w, r, 1.0f), r, r);
+    if (CN == 3) {
+        // channels 0 and 1 as one packed pair (v_pk_mul / v_pk_fma: the same fma chain per element), channel 2 scalar
+        f2_t a01, nw, rr;
+        a01.x = a[0]; a01.y = a[1];
+        nw.x = nw.y = -w;
+        rr.x = rr.y = r;
+        f2_t t = a01 * rr;
+        t = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, t, a01), rr, t);
+        t = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, t, a01), rr, t);
+        q[0] = t.x;
+        q[1] = t.y;
+        float t2 = a[2] * r;
+        t2 = fmaf(fmaf(-w, t2, a[2]), r, t2);
+        q[2] = fmaf(fmaf(-w, t2, a[2]), r, t2);
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < CN; ++c) {
+        float t = a[c] * r;
+        t = fmaf(fmaf(-w, t, a[c]), r, t);
+        q[c] = fmaf(fmaf(-w, t, a[c]), r, t);
+    }
 }

@@ -1,5 +1,5 @@
 // sr_linear.h -- cv::resize INTER_LINEAR on u8 data (half-pixel centres, 11-bit fixed-point coefficients), shared by
-// TilingModule.merge_tiles' resize branch (k_feather_merge, sr_engine.hip) and compute_blend_quality's resize of a tile
+// TilingModule.merge_tiles' resize branch (k_feather_merge, sr_tiles.hip) and compute_blend_quality's resize of a tile
 // clipped by the canvas (sr_gradient.hip).  Internal: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

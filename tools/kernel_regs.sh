@@ -2,6 +2,7 @@
 # VGPRs / spills / occupancy of the kernels of one .hip file whose mangled name matches a pattern.
 #   tools/kernel_regs.sh [pattern] [file]       e.g. tools/kernel_regs.sh 'k_final_fast|k_down_march'
 #                                               or   tools/kernel_regs.sh k_assess_march csrc/sr_assess.hip
+#                                               or   tools/kernel_regs.sh 'k_feather_merge|k_seam_scan' csrc/sr_tiles.hip
 cd "$(dirname "$0")/../super-resolution-system_amd" || exit 1
 pat=${1:-.}
 src=${2:-csrc/sr_engine.hip}
