@@ -675,6 +675,66 @@ SR_API int sr_resnet_u8(sr_resnet_model *model, const uint8_t *d_src, int64_t sr
 SR_API int sr_resnet_f32(sr_resnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
                          int64_t dst_stride, int tile);
 
+/* ---- local SR backend: RRDBNet, ESRGAN / Real-ESRGAN x4 (csrc/sr_rrdb.hip) -------------------------------------------------
+ * BasicSR's RRDBNet at scale 4 (ESRGAN, RealESRGAN_x4plus with 23 blocks, RealESRGAN_x4plus_anime_6B with 6), restated (parity
+ * with the BasicSR / Real-ESRGAN packages is unpinned: neither they nor a checkpoint exist offline).  Everything is fp32 in,
+ * fp32 accumulate; every convolution is 3 x 3, stride 1, zero padding 1 at the true image border, with bias.  A model is an
+ * sr_rrdb_desc:
+ *     F = n_feat in {64, 128, 192, 256};  G = n_grow in {32, 64};  B = n_blocks, 0 <= B <= 32;  scale = 4;
+ *     slope a (BasicSR: 0.2), act(y, a) = y >= 0 ? y : a * y;  res_scale beta (BasicSR: 0.2).
+ *  1. input      x[c] = u8 / 255 (one fp32 division); zero is padded after this step.
+ *  2. head       h = conv_first(x), 3 -> F, no activation.
+ *  3. RRDB i = 1 .. B takes r = t_{i-1} (t_0 = h) through three dense blocks, then t_i = fmaf(beta, u, r) with u the third
+ *                dense block's output.  A dense block on input x:  x_k = act(conv_k(cat(x, x_1, .., x_{k-1})), a) for
+ *                k = 1 .. 4, each F + (k - 1) G -> G;  y = conv_5(cat(x, x_1 .. x_4)), F + 4 G -> F, no activation;  output
+ *                fmaf(beta, y, x).  The concatenation's channel order is the weights' cin order: channels [0, F) are x,
+ *                channels [F + (j - 1) G, F + j G) are x_j.  The third dense block is two fmafs in this order: first
+ *                fmaf(beta, y, x), then fmaf(beta, that, r).
+ *  4. trunk end  f = conv_body(t_B) + h  (one fp32 add).
+ *  5. upsampling twice:  n[c, Y, X] = f[c, Y >> 1, X >> 1] (nearest), f' = act(conv_up1(n), a) at 2 x; the same again with
+ *                conv_up2 at 4 x.
+ *  6. HR convs   act(conv_hr(.), a), then conv_last F -> 3, both at 4 x.
+ *  7. output     o = conv_last's value, no affine and no base.  Stored as HWC fp32 unclamped (sr_rrdb_f32) or as HWC u8
+ *                rintf(fminf(fmaxf(o, 0), 1) * 255) (sr_rrdb_u8).
+ * Anything outside the ranges above (non-finite slope / res_scale and scale != 4 included) is SR_ERR_UNSUPPORTED, decided on the
+ * host before any device call.  Out of scope: the x2 / x1 variants that put a pixel-unshuffle in front of conv_first (its weight
+ * then takes 12 or 48 channels), and fp16 / bf16.
+ * Summation order: every F-input convolution: bias, then channel pairs (2p, 2p + 1) of the CONCATENATION ascending, then taps
+ * ascending, one two-term MFMA step each (even channel, then odd); head: bias, then channels, then taps, as fmaf.  Nothing
+ * depends on the position in a block, a trunk piece or a tail piece.
+ * sr_rrdb_create: h_w[k] / h_b[k] = weights (dense OIHW fp32) and bias of convolution k in forward order: head, per RRDB
+ * rdb1.conv1 .. conv5, rdb2 .., rdb3 .., then conv_body, conv_up1, conv_up2, conv_hr, conv_last; n_conv must be 1 + 15 B + 5.
+ * sr_rrdb_plan (host only, no context, no GPU): two-phase streaming.  Every layer's extent is derived backwards from a piece's
+ * output rectangle: divided by r (rounded outwards) across a 2 x 2 replication (r = 2 behind conv_body and conv_up1), grown by
+ * one per convolution, clipped to the layer's image; *halo = 15 B + 4 input pixels a piece reads beyond its edge.
+ *   trunk phase  tile x tile pieces of the INPUT (*n_tiles): head, RRDBs and conv_body, leaving f replicated to 2 x;
+ *   tail phase   each trunk piece in tail x tail sub-pieces of the input (*n_tail_tiles in all): conv_up1 .. conv_last.
+ * *workspace_bytes = 4 ((3 (F + 4 G) + F) P0 + F P2 + 2 F P4): three dense buffers of F + 4 G planes and h (F planes) of P0
+ * floats, P0 = the largest head extent of a trunk piece (rows x columns padded to 4); f, F planes of P2 = the largest conv_body
+ * extent at 2 x; two F-plane tail buffers of P4 = the largest 4 x extent of a tail sub-piece.  tail 0: 256.  tile 0: the
+ * largest multiple of 32 up to 2048 (at least 32) whose trunk part 4 ((3 (F + 4 G) + F) P0 + F P2), laid out for this image, is
+ * <= SR_RRDB_TRUNK_CAP = 16 GiB -- a policy, chosen so that F 64, G 32 on a 2048 x 2048 input (3.5 KiB per input pixel) runs the
+ * trunk in one piece.  Outputs may be NULL.
+ * sr_rrdb_u8 / sr_rrdb_f32: d_src h x w x 3 u8, d_dst (4 h) x (4 w) x 3; strides in bytes (fp32: a multiple of 4).
+ * SR_ERR_INVALID_ARG for null pointers, a wrong n_conv, a destroyed model and a tile or tail < 0, SR_ERR_SHAPE for h or w < 1, a
+ * stride shorter than a row, an output size beyond int or a piece too large for 32-bit offsets -- all before any launch.  Every
+ * (tile, tail) gives the same bits.  Asynchronous. */
+#define SR_RRDB_TRUNK_CAP ((size_t)16 << 30)
+typedef struct sr_rrdb_desc {
+    int n_feat, n_grow, n_blocks, scale;
+    float slope, res_scale;
+} sr_rrdb_desc;
+typedef struct sr_rrdb_model sr_rrdb_model;
+SR_API int sr_rrdb_create(sr_ctx *ctx, const sr_rrdb_desc *desc, const float *const *h_w, const float *const *h_b, int n_conv,
+                          sr_rrdb_model **out);
+SR_API int sr_rrdb_destroy(sr_rrdb_model *model);
+SR_API int sr_rrdb_plan(const sr_rrdb_desc *desc, int h, int w, int tile, int tail, int *halo, int *n_tiles, int *n_tail_tiles,
+                        size_t *workspace_bytes);
+SR_API int sr_rrdb_u8(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                      int64_t dst_stride, int tile, int tail);
+SR_API int sr_rrdb_f32(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                       int64_t dst_stride, int tile, int tail);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,12 @@ class ResNetDesc(C.Structure):
                 ("res_scale", C.c_float), ("mean", C.c_float * 3), ("range", C.c_float)]
 
 
+class RrdbDesc(C.Structure):
+    """sr_rrdb_desc (include/sr_hip.h)."""
+    _fields_ = [("n_feat", C.c_int), ("n_grow", C.c_int), ("n_blocks", C.c_int), ("scale", C.c_int), ("slope", C.c_float),
+                ("res_scale", C.c_float)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("launches", C.c_int64)]
 
@@ -204,6 +210,11 @@ SIGNATURES = {
     "sr_resnet_plan": (_i, [C.POINTER(ResNetDesc), _i, _i, _i, _pi, _pi, C.POINTER(_sz)]),
     "sr_resnet_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
     "sr_resnet_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_rrdb_create": (_i, [_vp, C.POINTER(RrdbDesc), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_vp)]),
+    "sr_rrdb_destroy": (_i, [_vp]),
+    "sr_rrdb_plan": (_i, [C.POINTER(RrdbDesc), _i, _i, _i, _i, _pi, _pi, _pi, C.POINTER(_sz)]),
+    "sr_rrdb_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_rrdb_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
 }
 
 
@@ -1344,6 +1355,74 @@ class ResNetModel:
     def close(self):
         if getattr(self, "handle", None):
             self.ctx.lib.sr_resnet_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+# ------------------------------------------------------------------------------------------
+# local SR network, RRDBNet (sr_rrdb_*): sr_network.RRDBSRNet parses BasicSR state dicts into these arrays
+# ------------------------------------------------------------------------------------------
+def rrdb_desc(n_feat: int, n_grow: int, n_blocks: int, scale: int = 4, slope: float = 0.2, res_scale: float = 0.2) -> RrdbDesc:
+    return RrdbDesc(int(n_feat), int(n_grow), int(n_blocks), int(scale), float(slope), float(res_scale))
+
+
+def rrdb_conv_shapes(desc: RrdbDesc) -> List[Tuple[int, int]]:
+    """(cout, cin) of every convolution in sr_rrdb_create's order."""
+    F, G = desc.n_feat, desc.n_grow
+    dense = [(G, F + k * G) for k in range(4)] + [(F, F + 4 * G)]
+    return [(F, 3)] + dense * (3 * desc.n_blocks) + [(F, F)] * 4 + [(3, F)]
+
+
+def rrdb_plan(desc: RrdbDesc, h: int, w: int, tile: int = 0, tail: int = 0) -> Tuple[int, int, int, int]:
+    """sr_rrdb_plan (host only) -> (halo, trunk pieces, tail sub-pieces, workspace bytes)."""
+    halo, n, nt, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check_unsupported(load().sr_rrdb_plan(C.byref(desc), int(h), int(w), int(tile), int(tail), C.byref(halo), C.byref(n), C.byref(nt),
+                                           C.byref(ws)))
+    return halo.value, n.value, nt.value, int(ws.value)
+
+
+class RrdbModel:
+    """sr_rrdb_model: an RRDBNet (ESRGAN / Real-ESRGAN x4) resident on the GPU.  weights / biases: one OIHW fp32 array and one
+    bias vector per convolution in forward order (rrdb_conv_shapes)."""
+
+    def __init__(self, ctx: Context, desc: RrdbDesc, weights, biases):
+        rrdb_plan(desc, 1, 1)                                    # the supported range, refused before any array is touched
+        shapes = rrdb_conv_shapes(desc)
+        if len(weights) != len(shapes) or len(biases) != len(shapes):
+            raise ValueError(f"this RRDB network has {len(shapes)} convolutions, got {len(weights)} weight / {len(biases)} bias arrays")
+        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
+        bs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in biases]
+        for k, (w, b, (co, ci)) in enumerate(zip(ws, bs, shapes)):
+            if w.shape != (co, ci, 3, 3) or b.shape != (co,):
+                raise ValueError(f"RRDB network convolution {k}: expected {(co, ci, 3, 3)} / {(co,)}, got {w.shape} / {b.shape}")
+        self.ctx, self.desc, self.scale = ctx, desc, desc.scale
+        pw = (C.c_void_p * len(ws))(*[a.ctypes.data for a in ws])
+        pb = (C.c_void_p * len(bs))(*[a.ctypes.data for a in bs])
+        h = C.c_void_p()
+        _check_unsupported(ctx.lib.sr_rrdb_create(ctx.handle, C.byref(desc), pw, pb, len(ws), C.byref(h)))
+        self.handle = h
+
+    def plan(self, h: int, w: int, tile: int = 0, tail: int = 0) -> Tuple[int, int, int, int]:
+        return rrdb_plan(self.desc, h, w, tile, tail)
+
+    def upscale_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0, tail: int = 0):
+        """sr_rrdb_u8: h x w x 3 u8 -> (4 h) x (4 w) x 3 u8, HBM -> HBM.  Asynchronous."""
+        check(self.ctx.lib.sr_rrdb_u8(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
+                                      int(dst_stride), int(tile), int(tail)))
+
+    def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0, tail: int = 0):
+        """sr_rrdb_f32: the unclamped fp32 output (HWC, stride in bytes).  Asynchronous."""
+        check(self.ctx.lib.sr_rrdb_f32(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
+                                       int(dst_stride), int(tile), int(tail)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.sr_rrdb_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -1,4 +1,4 @@
-// sr_conv_mfma.h -- the fp32 implicit-GEMM convolution shared by sr_lpips.hip, sr_srnet.hip and sr_resnet.hip: one device
+// sr_conv_mfma.h -- the fp32 implicit-GEMM convolution shared by sr_lpips.hip, sr_srnet.hip, sr_resnet.hip and sr_rrdb.hip: one device
 // mainloop, one 3 -> F head accumulate, and the host helpers around them (weight layouts, upload, the live-model set, the
 // activation buffers, the forward calls' argument checks).  Internal: nothing here is part of the C ABI.
 #pragma once
@@ -257,7 +257,7 @@ inline int ensure_activation_buffers(sr_ctx *ctx, float **bufs, int n, size_t &b
     return SR_OK;
 }
 
-// What sr_srnet_* and sr_resnet_* forwards check of their image arguments: HWC u8 source of w pixels per row, HWC
+// What sr_srnet_*, sr_resnet_* and sr_rrdb_* forwards check of their image arguments: HWC u8 source of w pixels per row, HWC
 // destination (u8 or fp32) of w * scale.
 inline int check_sr_forward_args(const char *who, const void *d_src, int64_t src_stride, int w, const void *d_dst, int64_t dst_stride,
                                  int scale, bool u8)

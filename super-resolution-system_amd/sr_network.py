@@ -281,10 +281,141 @@ def _residual_extras(state: Mapping) -> dict:
     return out
 
 
+# ------------------------------------------------------------------------------------------
+# RRDBNet: BasicSR's ESRGAN / Real-ESRGAN x4 generator (RealESRGAN_x4plus: 23 blocks, RealESRGAN_x4plus_anime_6B: 6), run by
+# csrc/sr_rrdb.hip.  PARITY UNPINNED here too: neither the BasicSR / Real-ESRGAN packages nor a checkpoint exist offline; the
+# arithmetic is written out in include/sr_hip.h and held against a torch-CPU restatement (tests/_rrdb_ref.py).
+# ------------------------------------------------------------------------------------------
+RRDB_KEY = "body.0.rdb1.conv1.weight"                           # what tells an RRDBNet state from the residual family
+_RRDB_BLOCK_KEY = re.compile(r"^body\.(\d+)\.rdb[123]\.conv[1-5]\.(weight|bias)$")
+
+
+def parse_rrdb_state(state: Mapping, slope: float = 0.2, res_scale: float = 0.2):
+    """-> (_native.RrdbDesc, weights, biases) in sr_rrdb_create's order, contiguous fp32.
+
+    BasicSR key names: ``conv_first``, ``body.{i}.rdb{1,2,3}.conv{1..5}``, ``conv_body``, ``conv_up1``, ``conv_up2``,
+    ``conv_hr``, ``conv_last``.  slope and res_scale are not in a state dict (BasicSR hard-codes 0.2 for both).  Every shape is
+    checked; a ValueError names the offending key.  The x2 / x1 variants, whose ``conv_first`` takes the 12 / 48 channels of a
+    pixel-unshuffle, are refused with NotImplementedError."""
+    state = _unwrap(state)
+    keys = {str(k) for k in state}
+    if "conv_first.weight" not in keys:
+        raise ValueError("conv_first.weight: not in the state (not an RRDB network)")
+    convs = []
+
+    def conv(name: str, cin: int, cout=None):
+        for part in ("weight", "bias"):
+            if f"{name}.{part}" not in keys:
+                raise ValueError(f"{name}.{part}: not in the state")
+        w = np.ascontiguousarray(_array(state, f"{name}.weight"), dtype=np.float32)
+        b = np.ascontiguousarray(_array(state, f"{name}.bias"), dtype=np.float32).reshape(-1)
+        if w.ndim != 4 or w.shape[2:] != (3, 3):
+            raise ValueError(f"{name}.weight: only 3x3 convolutions, got shape {w.shape}")
+        if name == "conv_first" and w.shape[1] in (12, 48):
+            raise NotImplementedError(f"conv_first.weight takes {w.shape[1]} channels: the x{2 if w.shape[1] == 12 else 1} RRDBNet puts a "
+                                      "pixel-unshuffle in front of conv_first, which is not supported (x4 only)")
+        if w.shape[1] != cin:
+            raise ValueError(f"{name}.weight takes {w.shape[1]} channels, expected {cin}")
+        if cout is not None and w.shape[0] != cout:
+            raise ValueError(f"{name}.weight gives {w.shape[0]} channels, expected {cout}")
+        if b.shape != (w.shape[0],):
+            raise ValueError(f"{name}.bias: expected {w.shape[0]} values, got {b.shape}")
+        convs.append((w, b))
+        return w
+
+    F = int(conv("conv_first", 3).shape[0])
+    blocks = sorted({int(m.group(1)) for m in map(_RRDB_BLOCK_KEY.match, keys) if m})
+    if blocks != list(range(len(blocks))):
+        gap = next(i for i in range(len(blocks) + 1) if i not in blocks)
+        raise ValueError(f"body.{gap}.rdb1.conv1.weight: RRDBs must be numbered 0 .. B - 1, got {blocks}")
+    G = None
+    for i in blocks:
+        for d in (1, 2, 3):
+            for k in range(1, 5):
+                name = f"body.{i}.rdb{d}.conv{k}"
+                if G is None:
+                    if f"{name}.weight" not in keys:
+                        raise ValueError(f"{name}.weight: not in the state")
+                    G = int(np.shape(_array(state, f"{name}.weight"))[0])
+                conv(name, F + (k - 1) * G, G)                   # every convolution 1 .. 4 has the first one's growth
+            conv(f"body.{i}.rdb{d}.conv5", F + 4 * G, F)
+    for name in ("conv_body", "conv_up1", "conv_up2", "conv_hr"):
+        conv(name, F, F)
+    conv("conv_last", F, 3)
+    desc = _native.rrdb_desc(F, 32 if G is None else G, len(blocks), 4, float(slope), float(res_scale))
+    _native.rrdb_plan(desc, 1, 1)                                # NotImplementedError outside the kernels' range (host only)
+    return desc, [w for w, _ in convs], [b for _, b in convs]
+
+
+class RRDBSRNet(CompactSRNet):
+    """RRDBNet x4 on the GPU, with CompactSRNet's surface (from_file, model, upscale, upscale_device, close) plus the tail
+    phase's ``tail``.  ``state``: a BasicSR state dict (see parse_rrdb_state)."""
+
+    def __init__(self, state: Mapping, slope: float = 0.2, res_scale: float = 0.2, device: int = 0):
+        self.desc, self._w, self._b = parse_rrdb_state(state, slope, res_scale)
+        self.n_feat, self.n_grow, self.n_blocks, self.scale = self.desc.n_feat, self.desc.n_grow, self.desc.n_blocks, self.desc.scale
+        self.device = int(device)
+        self._models = {}
+
+    @classmethod
+    def from_file(cls, path: str, device: int = 0, **extras) -> "RRDBSRNet":
+        """A .npz may hold the two constants a state dict lacks as 0-d ``slope`` / ``res_scale`` entries; keyword arguments win
+        over them, BasicSR's 0.2 stands in for the rest."""
+        state = load_state(path)
+        return cls(state, device=device, **{**_rrdb_extras(state), **extras})
+
+    def model(self, ctx: Optional["_native.Context"] = None) -> "_native.RrdbModel":
+        ctx = ctx or _native.default_context(self.device)
+        m = self._models.get(id(ctx))
+        if m is None or m.handle is None or m.ctx is not ctx:
+            m = _native.RrdbModel(ctx, self.desc, self._w, self._b)
+            self._models[id(ctx)] = m
+        return m
+
+    def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
+                       ctx: Optional["_native.Context"] = None, tail: int = 0):
+        h, w = self._check_image_shape(shape)
+        self.model(ctx).upscale_u8(d_src, w * 3 if src_stride is None else src_stride, h, w, d_dst, dst_stride, tile, tail)
+
+    def upscale(self, image: np.ndarray, tile: int = 0, tail: int = 0) -> np.ndarray:
+        """Host array in, host array out."""
+        image = np.asarray(image)
+        h, w = self._check_image_shape(image.shape)
+        if image.dtype != np.uint8:
+            raise ValueError(f"the SR network takes u8 images, got {image.dtype}")
+        ctx = _native.default_context(self.device)
+        d_src, d_dst = ctx.upload(image), None
+        try:
+            d_dst = ctx.alloc(h * 4 * w * 4 * 3)
+            self.upscale_device(d_src.ptr, (h, w, 3), d_dst.ptr, w * 4 * 3, tile=tile, ctx=ctx, tail=tail)
+            return ctx.download(d_dst.ptr, (h * 4, w * 4, 3), np.uint8)
+        finally:
+            ctx.sync()
+            d_src.free()
+            if d_dst is not None:
+                d_dst.free()
+
+
+def _rrdb_extras(state: Mapping) -> dict:
+    out = {}
+    if not isinstance(state, Mapping):
+        return out
+    for key in ("slope", "res_scale"):
+        if key in state:
+            a = np.asarray(_array(state, key), dtype=np.float64).reshape(-1)
+            if a.size != 1:
+                raise ValueError(f"{key}: expected 1 value, got shape {np.shape(_array(state, key))}")
+            out[key] = float(a[0])
+    return out
+
+
 def load_network(path: str, act: str = "prelu", device: int = 0):
-    """The network a weights file holds: a ``conv_first.weight`` entry makes it a ResidualSRNet (``act`` is ignored for this
-    family), ``body.{i}.weight`` entries a CompactSRNet exactly as CompactSRNet.from_file."""
+    """The network a weights file holds: a ``body.0.rdb1.conv1.weight`` entry makes it an RRDBSRNet, otherwise a
+    ``conv_first.weight`` entry a ResidualSRNet (``act`` is ignored for these two families), ``body.{i}.weight`` entries a
+    CompactSRNet exactly as CompactSRNet.from_file."""
     state = load_state(path)
+    if RRDB_KEY in {str(k) for k in _unwrap(state)}:
+        return RRDBSRNet(state, device=device, **_rrdb_extras(state))
     if "conv_first.weight" in {str(k) for k in _unwrap(state)}:
         return ResidualSRNet(state, device=device, **_residual_extras(state))
     return CompactSRNet(state, act=act, device=device)
