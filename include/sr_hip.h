@@ -234,6 +234,10 @@ SR_API int sr_comm_allreduce_f64(sr_ctx *ctx, sr_comm *comm, double *d_buf, int 
  * owner must hold / receive for that tile. */
 SR_API int sr_blend_plan_tile_rows(const sr_blend_plan *plan, int t, int *r0, int *r1);
 SR_API int sr_blend_plan_workspace_bytes(const sr_blend_plan *plan, size_t *bytes);
+/* host only: how a blend of tiles of `dtype` (SR_U8 / SR_F32) keeps the level-1 Gaussian planes in the plan's workspace:
+ * *fmt = 0 fp32, 1 the exact 16-bit integers 256 * G_1 (three-channel u8 tiles whose levels 1 and 2 all come from the fused
+ * down march; SR_G1_U16=0 at plan creation selects fp32).  The canvases are the same bits either way. */
+SR_API int sr_blend_plan_g1_format(const sr_blend_plan *plan, int dtype, int *fmt);
 
 /* h_d_tiles[i]: device address of row 0 of tile i (rows outside sr_blend_plan_tile_rows are
  * never touched, so the address may be virtual); h_strides[i]: row stride in bytes.

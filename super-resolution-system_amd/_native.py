@@ -143,6 +143,7 @@ SIGNATURES = {
     "sr_exchange_plan": (_i, [C.POINTER(TileRect), _i, _i, _i, _i, _i, _i, _i, _i, _pi, _pi, _pi, _pi]),
     "sr_blend_plan_tile_rows": (_i, [_vp, _i, _pi, _pi]),
     "sr_blend_plan_workspace_bytes": (_i, [_vp, C.POINTER(_sz)]),
+    "sr_blend_plan_g1_format": (_i, [_vp, _i, C.POINTER(_i)]),
     "sr_laplacian_blend": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i64), _vp, _i64, _vp]),
     "sr_weighted_blend": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i64), _vp, _i64, _vp]),
     "sr_blend_pyramids": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i64), _pi, _i, _i]),
@@ -1053,6 +1054,12 @@ class BlendPlan:
         b = C.c_size_t(0)
         check(self.ctx.lib.sr_blend_plan_workspace_bytes(self.handle, C.byref(b)))
         return b.value
+
+    def g1_format(self, dtype: int = SR_U8) -> int:
+        """0: a blend of tiles of `dtype` keeps G_1 as fp32 planes, 1: as the exact 16-bit integers 256 * G_1."""
+        f = C.c_int(-1)
+        check(self.ctx.lib.sr_blend_plan_g1_format(self.handle, int(dtype), C.byref(f)))
+        return f.value
 
     def blend(self, d_tiles: Sequence[int], strides: Sequence[int], d_canvas: int, canvas_stride: int,
               dtype: int = SR_U8, d_canvas_f32: Optional[int] = None, laplacian: bool = True):

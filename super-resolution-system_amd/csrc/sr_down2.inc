@@ -30,6 +30,9 @@
 // planner's level-1 window covers what the level-2 window reads); gray and float tiles and tiles of fewer than three
 // levels keep the two-launch form (down2_takes).
 //
+// G1F = G1_U16 (sr_engine.hip: the plan and the call decide): level 1 is stored as the 16-bit integers 256 G_1 the march holds
+// anyway -- half the bytes of its largest store and of the gather's largest read; G_2 is formed from the fp32 values as before.
+//
 // Left to the per-pixel border rule: level-1 columns outside groups 1 .. ncg (trailing blocks of this launch, as in
 // k_down_march) and level-2 columns outside 4 .. 2 ncg - 1 (k_down2_cols, a second small launch: it reads G_1).
 
@@ -59,6 +62,11 @@ __host__ __device__ __forceinline__ bool down2_takes(const TileDev &T)
     if (T.g0[1] > (2 * T.g0[2] - 2 > 0 ? 2 * T.g0[2] - 2 : 0)) return false;
     if (T.g1[1] < (2 * T.g1[2] + 1 < T.H[1] ? 2 * T.g1[2] + 1 : T.H[1])) return false;
     return down_ncg(T.W[0], T.W[1]) >= 1;
+}
+// the tile row strides the march's 32-bit row offsets hold for (h0: rows of level 0)
+static inline bool down2_stride_fits(long long stride, int h0)
+{
+    return stride > 0 && (unsigned long long)stride * (unsigned long long)(h0 + 2) < 0x7FFF0000ull;
 }
 // strips of a row of groups 0 .. ncg (group 0 is a border group: its lane stores nothing)
 __host__ __device__ __forceinline__ int down2_nstrip(int ncg) { return (ncg + D2_OUT) / D2_OUT; }
@@ -140,25 +148,34 @@ __device__ __forceinline__ void d2_hpass(const D2Raw &R, D2Row &H)
     for (int n = 0; n < 2; ++n) H.b[n] = c[4 * n + 2] * k6 + ((c[4 * n + 1] + c[4 * n + 3]) * k4 + (c[4 * n] + c[4 * n + 4]));
 }
 
-// 256 G_1 of one row from the five row sums around it, as fp32 G_1 per plane: f[plane][0] = columns (0, 1), [1] = (2, 3)
+// 256 G_1 of one row from the five row sums around it, as fp32 G_1 per plane: f[plane][0] = columns (0, 1), [1] = (2, 3), and
+// the integers themselves per plane as they are stored under G1_U16: q[plane][0] = columns (0, 1) in one dword, [1] = (2, 3)
 __device__ __forceinline__ void d2_vpass(const D2Row &e0, const D2Row &o0, const D2Row &e1, const D2Row &o1, const D2Row &e2,
-                                         f2_t (&f)[3][2])
+                                         f2_t (&f)[3][2], unsigned (&q)[3][2])
 {
     const d2_us2 k4 = d2_k(0x00040004u), k6 = d2_k(0x00060006u);
     f2_t sc;
     sc.x = sc.y = 1.0f / 256.0f;
     float t[3][4];
+    unsigned rg[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const d2_us2 v = e1.rg[k] * k6 + ((o0.rg[k] + o1.rg[k]) * k4 + (e0.rg[k] + e2.rg[k]));
         t[0][k] = (float)v.x;
         t[1][k] = (float)v.y;
+        rg[k] = __builtin_bit_cast(unsigned, v);
+    }
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {                                   // (R, G) per column -> two columns per plane
+        q[0][n] = __builtin_amdgcn_perm(rg[2 * n + 1], rg[2 * n], 0x05040100u);
+        q[1][n] = __builtin_amdgcn_perm(rg[2 * n + 1], rg[2 * n], 0x07060302u);
     }
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         const d2_us2 v = e1.b[n] * k6 + ((o0.b[n] + o1.b[n]) * k4 + (e0.b[n] + e2.b[n]));
         t[2][2 * n] = (float)v.x;
         t[2][2 * n + 1] = (float)v.y;
+        q[2][n] = __builtin_bit_cast(unsigned, v);
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c)
@@ -190,7 +207,7 @@ struct D2Out {
     march_rsrc arena;
     unsigned v1, v2;                 // per-lane byte offsets of the group's level-1 / level-2 columns
     unsigned g1, g2;                 // byte offsets of plane 0, row 0 of G_1 / G_2
-    unsigned p1b, p2b, plane1b, plane2b;
+    unsigned p1b, p2b, plane1b, plane2b;        // (level 1: in the elements G_1 is stored in)
     bool st1, st2;                   // the lane stores level 1 / level 2
 };
 
@@ -215,7 +232,7 @@ __device__ __forceinline__ void d2_store2(const D2Out &O, int Y, const f2_t (&v)
 // One level-1 row r of the march.  EVEN: r is even.  `cur` holds level-0 rows 2r + 1 and 2r + 2 on entry and is re-requested
 // for row r + 2 (rows 2r + 5, 2r + 6) as soon as its bytes are consumed.  Ring: e0 o0 e1 = rows 2r - 2, 2r - 1, 2r; the row
 // leaves o1 e2 = rows 2r + 1, 2r + 2 in `n1`, `n2`.
-template <bool EVEN>
+template <bool EVEN, int G1F>
 __device__ __forceinline__ void d2_step(int r, int rn, const D2Row &e0, const D2Row &o0, const D2Row &e1, D2Row &n1, D2Row &n2,
                                         D2Raw (&cur)[2], march_rsrc px, unsigned plo, unsigned stride, int hs, int z0, int z1,
                                         unsigned voff_lo, unsigned voff_hi, D2Acc &G, const D2Out &O, int own_lo, int own_hi, int Y0, int Y1, int h1,
@@ -228,10 +245,17 @@ __device__ __forceinline__ void d2_step(int r, int rn, const D2Row &e0, const D2
     d2_request(px, plo, stride, d2_row(2 * rn + 1, hs, z0, z1), voff_lo, voff_hi, cur[0]);
     d2_request(px, plo, stride, d2_row(2 * rn + 2, hs, z0, z1), voff_lo, voff_hi, cur[1]);
     f2_t f[3][2];
-    d2_vpass(e0, o0, e1, n1, n2, f);
+    unsigned q[3][2];
+    d2_vpass(e0, o0, e1, n1, n2, f, q);
     if (O.st1 && r >= own_lo && r < own_hi) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
+            if constexpr (G1F == G1_U16) {                          // the integers as they stand: 8 bytes per lane and plane
+                u2_t o;
+                o.x = q[c][0]; o.y = q[c][1];
+                __builtin_amdgcn_raw_buffer_store_b64(o, O.arena, O.v1, O.g1 + c * O.plane1b + (unsigned)r * O.p1b, D2_ST_AUX);
+                continue;
+            }
             u4_t o;
             o.x = __float_as_uint(f[c][0].x); o.y = __float_as_uint(f[c][0].y); o.z = __float_as_uint(f[c][1].x); o.w = __float_as_uint(f[c][1].y);
             __builtin_amdgcn_raw_buffer_store_b128(o, O.arena, O.v1, O.g1 + c * O.plane1b + (unsigned)r * O.p1b, D2_ST_AUX);
@@ -278,7 +302,7 @@ __device__ __forceinline__ void d2_step(int r, int rn, const D2Row &e0, const D2
     (void)h2;
 }
 
-template <int CN>
+template <int CN, int G1F>
 __global__ __launch_bounds__(64, D2_WAVES) void k_down2_march(const TileDev *__restrict__ tiles, const TileSrc *__restrict__ srcs, int seg2,
                                                     int march_items, const float *__restrict__ arena_p, unsigned arena_bytes,
                                                     float *__restrict__ arena_w, const float *__restrict__ luts)
@@ -296,7 +320,7 @@ __global__ __launch_bounds__(64, D2_WAVES) void k_down2_march(const TileDev *__r
         const int x = e < 4 ? e : 4 * (ncg + 1) + (e - 4);
         const int y = a1 + ((int)blockIdx.x - march_items) * 4 + (tid >> 4);
         if (x >= w1 || y >= b1) return;
-        down_pixel<SRC_U8>(T, srcs[blockIdx.z], 0, CN, x, y, arena_w, luts);
+        down_pixel<SRC_U8, G1F>(T, srcs[blockIdx.z], 0, CN, x, y, arena_w, luts);
         return;
     }
     const int nstrip = down2_nstrip(ncg), nseg = (b2 - a2 + seg2 - 1) / seg2;
@@ -313,11 +337,11 @@ __global__ __launch_bounds__(64, D2_WAVES) void k_down2_march(const TileDev *__r
     const unsigned voff_lo = 24u * (unsigned)min(max(g, 1), ncg + 1), voff_hi = 24u * (unsigned)min(max(g, 1), ncg) + 12u;
     D2Out O;
     O.arena = march_make_rsrc(arena_p, arena_bytes);
-    O.v1 = 16u * (unsigned)g;
+    O.v1 = 4u * G1<G1F>::ES * (unsigned)g;
     O.v2 = 8u * (unsigned)g;
     O.g1 = (unsigned)T.g_off[1] * 4u;
     O.g2 = (unsigned)T.g_off[2] * 4u;
-    O.p1b = (unsigned)T.P[1] * 4u;
+    O.p1b = (unsigned)T.P[1] * G1<G1F>::ES;
     O.p2b = (unsigned)T.P[2] * 4u;
     O.plane1b = (unsigned)h1 * O.p1b;
     O.plane2b = (unsigned)h2 * O.p2b;
@@ -355,10 +379,10 @@ __global__ __launch_bounds__(64, D2_WAVES) void k_down2_march(const TileDev *__r
 #define D2_ROUND(R, S0, S1)                                                                                                        \
     do {                                                                                                                           \
         if ((R) <= re) {                                                                                                           \
-            d2_step<true>((R), min((R) + 2 * D2_AHEAD, re), A0, A1, A2, B0, B1, rq[S0], px, plo, stride, hs, z0, z1, voff_lo, voff_hi, G, O, \
+            d2_step<true, G1F>((R), min((R) + 2 * D2_AHEAD, re), A0, A1, A2, B0, B1, rq[S0], px, plo, stride, hs, z0, z1, voff_lo, voff_hi, G, O, \
                           st_lo, st_hi, Y0, Y1, h1, h2);                                                                                 \
             if ((R) + 1 <= re)                                                                                                     \
-                d2_step<false>((R) + 1, min((R) + 1 + 2 * D2_AHEAD, re), A2, B0, B1, B2, B3, rq[S1], px, plo, stride, hs, z0, z1, voff_lo, voff_hi, \
+                d2_step<false, G1F>((R) + 1, min((R) + 1 + 2 * D2_AHEAD, re), A2, B0, B1, B2, B3, rq[S1], px, plo, stride, hs, z0, z1, voff_lo, voff_hi, \
                                G, O, st_lo, st_hi, Y0, Y1, h1, h2);                                                                 \
             A0 = B1; A1 = B2; A2 = B3;                                                                                             \
         }                                                                                                                          \
@@ -389,6 +413,7 @@ __host__ __device__ __forceinline__ int down2_cols_count(const TileDev &T)
     return (w2 < 4 ? w2 : 4) + (w2 > c_right ? w2 - c_right : 0);
 }
 
+template <int G1F>
 __global__ __launch_bounds__(256, 4) void k_down2_cols(const TileDev *__restrict__ tiles, float *__restrict__ arena)
 {
     const TileDev &T = tiles[blockIdx.z];
@@ -415,7 +440,7 @@ __global__ __launch_bounds__(256, 4) void k_down2_cols(const TileDev *__restrict
 #pragma unroll
         for (int k = 0; k < 5; ++k)
 #pragma unroll
-            for (int j = 0; j < 5; ++j) s[c][k][j] = src[c * splane + (size_t)yi[k] * p1 + xi[j]];
+            for (int j = 0; j < 5; ++j) s[c][k][j] = G1<G1F>::at(src, c * splane + (size_t)yi[k] * p1 + xi[j]);
     float v[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

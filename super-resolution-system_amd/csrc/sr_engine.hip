@@ -11,7 +11,7 @@
 //   * external images / tiles / canvas: row-major HWC, u8 (or fp32 tiles), byte strides --
 //     exactly the reference's ndarrays.
 //   * internal pyramid levels i >= 1 of every tile live in one arena: planar fp32, plane
-//     c of level i at  off[i] + c * H_i * P_i,  row pitch P_i = round_up(W_i, 32) floats (whole 128-byte lines).
+//     c of level i at  off[i] + c * H_i * P_i,  row pitch P_i = round_up(W_i, 32) floats (whole 128-byte lines; level 1: 64, see G1<>).
 //     G_i = Gaussian level, R_i = collapsed weighted-Laplacian level, W_i = weight level
 //     (one per distinct tile shape).
 //   * the fp32 canvas accumulators of the reference are never materialised: the final kernel
@@ -24,6 +24,7 @@
 #include <map>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 #include "sr_ctx.h"
@@ -102,9 +103,51 @@ struct FinalDesc {
 };
 static_assert(sizeof(FinalDesc) == 128, "FinalDesc layout");
 
+// How the level-1 Gaussian planes G_1 lie in the arena.  G1_F32: fp32.  G1_U16: the integer 256 G_1 in 16 bits -- for u8
+// tiles it is exact and below 2^16 (sr_down2.inc), and k_down2_march holds it in that form anyway.  A 16-bit plane starts where
+// the fp32 plane it replaces would (same offsets, same pitch and plane size IN ELEMENTS: every index below is shared), so
+// its rows are half as long in bytes.  Which format a call uses: g1_format() on the host, the same in sr_blend_pyramids and
+// sr_blend_gather.  Every reader of G_1 goes through G1<>: (float)n * (1 / 256) is exact, the bits of the fp32 value.
+enum { G1_F32 = 0, G1_U16 = 1 };
+template <int G1F>
+struct G1 {
+    static constexpr unsigned ES = G1F == G1_U16 ? 2u : 4u;         // bytes per element
+    typedef typename std::conditional<G1F == G1_U16, unsigned, f2_t>::type pair_t;      // two neighbouring elements as loaded
+    static __device__ __forceinline__ float value(unsigned n) { return (float)n * (1.0f / 256.0f); }
+    // element i of the planes that start at `planes` (the arena + g_off[1] / FinalDesc::g1)
+    static __device__ __forceinline__ float at(const float *planes, size_t i)
+    {
+        if constexpr (G1F == G1_U16) return value(((const unsigned short *)planes)[i]);
+        else return planes[i];
+    }
+    // elements i .. i + 3 (i a multiple of 4)
+    static __device__ __forceinline__ f4_t quad(const float *planes, size_t i)
+    {
+        if constexpr (G1F == G1_U16) {
+            const u2_t q = *(const u2_t *)((const unsigned short *)planes + i);
+            f4_t v;
+            v.x = value(q.x & 0xFFFFu); v.y = value(q.x >> 16); v.z = value(q.y & 0xFFFFu); v.w = value(q.y >> 16);
+            return v;
+        } else {
+            return ld_f4(planes + i);
+        }
+    }
+    static __device__ __forceinline__ f2_t pair(pair_t q)
+    {
+        if constexpr (G1F == G1_U16) {
+            f2_t v;
+            v.x = value(q & 0xFFFFu); v.y = value(q >> 16);
+            return v;
+        } else {
+            return q;
+        }
+    }
+};
+
 // Source accessors for the pyrDown kernel -----------------------------------------------------
 // One output pixel (all planes) of level lvl+1 from level lvl -- the generic form with every border rule.
-template <int SRC>
+// G1F = G1_U16 (level 0 -> 1 of u8 tiles only): the sum itself is stored, in 16 bits.
+template <int SRC, int G1F = G1_F32>
 __device__ __forceinline__ void down_pixel(const TileDev &T, const TileSrc S, int lvl, int cn, int x, int y,
                                            float *__restrict__ arena, const float *__restrict__ luts, int c_only = -1)
 {
@@ -148,6 +191,11 @@ __device__ __forceinline__ void down_pixel(const TileDev &T, const TileSrc S, in
             rowv[k] = ((s[2] * 6.0f + (s[1] + s[3]) * 4.0f) + s[0]) + s[4];
         }
         const float v = ((rowv[2] * 6.0f + (rowv[1] + rowv[3]) * 4.0f) + rowv[0]) + rowv[4];
+        if constexpr (G1F == G1_U16) {
+            static_assert(SRC == SRC_U8, "256 G_1 is a 16-bit integer for u8 tiles only");
+            ((unsigned short *)(arena + T.g_off[lvl + 1]))[c * dplane + (size_t)y * po + x] = (unsigned short)v;
+            continue;
+        }
         dst[c * dplane] = v * (1.0f / 256.0f);
     }
 }
@@ -1025,7 +1073,7 @@ __device__ __forceinline__ bool fused_window(const FinalDesc &D, int lxa, int ly
 // Stage 1: R_1 and G_1 of the window into LDS, interleaved per pixel as (g, r) pairs: lds[plane][row][col][2] -- stage 2
 // then reads a pixel's two values as one aligned 8-byte pair and runs the pyrUp of both arrays in packed fp32 (v_pk_*,
 // IEEE per element: same roundings as the scalar form).  One item = one 4 x 2 patch of one plane = up_level_thread's work.
-template <int CN>
+template <int CN, int G1F>
 __device__ __forceinline__ void fused_stage1(const FinalDesc &D, const float *__restrict__ arena, float *lds, int R0, int C0,
                                              int npr, int npc, int LP, int tid)
 {
@@ -1042,9 +1090,9 @@ __device__ __forceinline__ void fused_stage1(const FinalDesc &D, const float *__
         // every load of the item is issued before the first use (no branch between them: a conditional second row would
         // put a full memory round trip between the two halves); a patch on the last odd row re-reads its own row
         const int row1 = (py + 1 < D.H1) ? D.P1 : 0;
-        const float *g = arena + D.g1 + c * plane1 + (size_t)py * D.P1 + px;
+        const size_t gi = c * plane1 + (size_t)py * D.P1 + px;
         const float *wr = arena + D.w1 + (size_t)py * D.P1 + px;
-        const f4_t g0v = ld_f4(g), g1v = ld_f4(g + row1);
+        const f4_t g0v = G1<G1F>::quad(arena + D.g1, gi), g1v = G1<G1F>::quad(arena + D.g1, gi + row1);
         const f4_t w0v = ld_f4(wr), w1v = ld_f4(wr + row1);
         f4_t o0, o1;
         if (D.nl == 2) {                         // level 1 is the top of this tile's pyramid: R = G * W
@@ -1290,7 +1338,7 @@ __device__ __forceinline__ void fused_gather_generic(const FinalDesc &D, const f
 }
 
 // Edge blocks of the fused gather: the 4 x 2 cells with a border visit, generic per-pixel rules from the LDS window.
-template <int DT, int CN>
+template <int DT, int CN, int G1F>
 __device__ __forceinline__ void fused_edge_block(const FinalDesc *__restrict__ descs, const int4 *__restrict__ edge_blocks, int ebi,
                                                  const int *__restrict__ cand_idx, const float *__restrict__ arena,
                                                  const float *__restrict__ luts, float *lds, unsigned char *__restrict__ canvas,
@@ -1326,7 +1374,7 @@ __device__ __forceinline__ void fused_edge_block(const FinalDesc *__restrict__ d
         const FinalDesc &D = descs[cand_idx[i]];
         int R0 = 0, C0 = 0, npr = 0, npc = 0;
         const bool win = D.nl > 1 && fused_window(D, eb.x - D.x, eb.y - D.y, bw, bh, R0, C0, npr, npc);
-        if (win) fused_stage1<CN>(D, arena, lds, R0, C0, npr, npc, LP, tid);
+        if (win) fused_stage1<CN, G1F>(D, arena, lds, R0, C0, npr, npc, LP, tid);
         __syncthreads();
         const int lx0 = x0 - D.x, ly0 = y0 - D.y;
         const bool touches = edge && !(lx0 + nx <= 0 || ly0 + ny <= 0 || lx0 >= D.w || ly0 >= D.h);
@@ -1375,7 +1423,7 @@ __device__ __forceinline__ void fused_edge_block(const FinalDesc *__restrict__ d
     if (edge) store_pixels<CN>(acc, wacc, canvas, cstride, canvas_f32, cw, x0, y0, nx, ny);
 }
 
-template <int DT, int CN>
+template <int DT, int CN, int G1F>
 __global__ __launch_bounds__(FU_THREADS, FU_WAVES) void k_final_fused(const FinalDesc *__restrict__ descs, const int *__restrict__ cand_off,
                                                         const int *__restrict__ cand_idx, const int4 *__restrict__ edge_blocks,
                                                         const int *__restrict__ edge_cand, int n_edge, int nbx_r,
@@ -1385,7 +1433,7 @@ __global__ __launch_bounds__(FU_THREADS, FU_WAVES) void k_final_fused(const Fina
 {
     __shared__ __attribute__((aligned(16))) float lds[2 * CN * FU_PLANE];
     if ((int)blockIdx.x < n_edge) {
-        fused_edge_block<DT, CN>(descs, edge_blocks, (int)blockIdx.x, edge_cand, arena, luts, lds, canvas, cstride, canvas_f32, cw,
+        fused_edge_block<DT, CN, G1F>(descs, edge_blocks, (int)blockIdx.x, edge_cand, arena, luts, lds, canvas, cstride, canvas_f32, cw,
                                  row_begin, row_end);
         return;
     }
@@ -1427,7 +1475,7 @@ __global__ __launch_bounds__(FU_THREADS, FU_WAVES) void k_final_fused(const Fina
         if (visit && !visit_is_interior<true>(D, lx0, ly0, nx, ny)) visit = alive = false;
         CellPixels<DT, CN> cp;
         if (visit) fused_load_pixels<DT, CN>(D, lx0, ly0, cp);                                     // in flight during stage 1
-        if (win) fused_stage1<CN>(D, arena, lds, R0, C0, npr, npc, FU_LP, tid);
+        if (win) fused_stage1<CN, G1F>(D, arena, lds, R0, C0, npr, npc, FU_LP, tid);
         __syncthreads();
         if (visit) {
             const bool xo = (D.x & 1) != 0;                      // x0 is a multiple of 4
@@ -1479,7 +1527,7 @@ static inline int rect_rows(int h) { return 2 * ((h + 2) / 2) + 2; }
 #ifndef FR_WAVES
 #define FR_WAVES FU_WAVES     /* waves per SIMD the register allocation of k_final_rect is held to */
 #endif
-template <int CN>
+template <int CN, int G1F>
 __global__ __launch_bounds__(FU_THREADS, FR_WAVES) void k_final_rect(const FinalDesc *__restrict__ descs, const RectItem *__restrict__ rects,
                                                         const int *__restrict__ rect_cand, const float *__restrict__ arena,
                                                         const float *__restrict__ luts, unsigned char *__restrict__ canvas,
@@ -1521,7 +1569,7 @@ __global__ __launch_bounds__(FU_THREADS, FR_WAVES) void k_final_rect(const Final
         const bool inner = touches && visit_is_interior<true>(D, lx0, ly0, nx, ny);
         CellPixels<DT, CN> cp;
         if (inner) fused_load_pixels<DT, CN>(D, lx0, ly0, cp);                                        // in flight during stage 1
-        if (win) fused_stage1<CN>(D, arena, lds, R0, C0, npr, npc, LP, tid);
+        if (win) fused_stage1<CN, G1F>(D, arena, lds, R0, C0, npr, npc, LP, tid);
         __syncthreads();
         const bool xo = (D.x & 1) != 0;                      // x0 is a multiple of 4
         const bool yo = ((row_begin - D.y) & 1) != 0;        // y0 - row_begin is a multiple of 2
@@ -1631,6 +1679,7 @@ struct sr_blend_plan {
     // marched zones (k_final_march): work items per tile count
     bool march = false;
     bool down2 = true;               // levels 1 and 2 of full-window u8 RGB tiles in one march (sr_down2.inc); SR_DOWN2=0: two launches
+    bool g1_u16 = false;             // G_1 of u8 tiles as 16-bit integers (G1_U16): every tile whose level 1 is in use takes that march; SR_G1_U16=0: fp32
     MarchItem *d_march_items[MARCH_NT + 1] = {nullptr};
     int n_march_items[MARCH_NT + 1] = {0};
     long long n_march_total = 0;
@@ -2069,7 +2118,7 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
             for (int i = 0; i < T.nl; ++i) {
                 C.H[i] = lv[t].H[i];
                 C.W[i] = lv[t].W[i];
-                C.P[i] = round_up(C.W[i], 32);
+                C.P[i] = round_up(C.W[i], i == 1 ? 64 : 32);
                 C.g0[i] = C.g1[i] = 0;
                 if (i >= 1) {
                     C.g_off[i] = (long long)off;
@@ -2086,7 +2135,7 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
         for (int i = 0; i < T.nl; ++i) {
             T.H[i] = lv[t].H[i];
             T.W[i] = lv[t].W[i];
-            T.P[i] = round_up(T.W[i], 32);
+            T.P[i] = round_up(T.W[i], i == 1 ? 64 : 32);       // level 1: rows of 16-bit planes start on 128-byte lines, too
             T.g0[i] = lv[t].gw[i].a;
             T.g1[i] = lv[t].gw[i].b;
             T.r0[i] = lv[t].rw[i].a;
@@ -2126,6 +2175,17 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
         }
     }
     P->arena_floats = off;
+    {
+        // the plan's part of the G_1 format: the only writer of 16-bit planes is k_down2_march, the readers are the fused gather's
+        const char *env4 = std::getenv("SR_G1_U16");
+        bool ok = P->down2 && P->fused && cn == 3 && !(env4 && env4[0] == '0') && off * sizeof(float) < 0xFFFF0000ull, any = false;
+        for (const TileDev &T : P->tiles) {
+            if (T.nl < 2 || T.g0[1] >= T.g1[1]) continue;            // no level 1, or none of its rows in use
+            any = true;
+            ok = ok && down2_takes(T);
+        }
+        P->g1_u16 = ok && any;
+    }
 
     auto fail = [&](hipError_t e, const char *what) {
         int code = (e == hipErrorOutOfMemory) ? SR_ERR_OOM : SR_ERR_HIP;
@@ -2412,6 +2472,24 @@ static int blend_check_tiles(sr_blend_plan *P, int dtype, void *const *h_d_tiles
     return SR_OK;
 }
 
+// The format of G_1 for one call (G1<>): the plan's part, u8 tiles, and tile strides k_down2_march's 32-bit row offsets hold
+// for -- every tile's, so that a subset's pyramids and the gather over all tiles decide alike.  h_strides == nullptr: strides
+// that fit (the query).
+static int g1_format(const sr_blend_plan *P, int dtype, const int64_t *h_strides)
+{
+    if (!P->g1_u16 || dtype != SR_U8) return G1_F32;
+    for (int t = 0; t < P->n && h_strides; ++t)
+        if (!down2_stride_fits(h_strides[t], P->tiles[t].H[0])) return G1_F32;
+    return G1_U16;
+}
+
+int sr_blend_plan_g1_format(const sr_blend_plan *plan, int dtype, int *fmt)
+{
+    if (!plan_is_live(plan) || !fmt || (dtype != SR_U8 && dtype != SR_F32)) return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_g1_format: bad args");
+    *fmt = g1_format(plan, dtype, nullptr);
+    return SR_OK;
+}
+
 // Stage A of the Laplacian blend: weight pyramids (when `first`) and the down / up chains of the listed tiles.
 // The listed tiles' descriptors are compacted into a scratch table, so kernels are launched over exactly them.
 static int blend_pyramids(sr_blend_plan *P, int dtype, void *const *h_d_tiles, const int64_t *h_strides,
@@ -2481,11 +2559,11 @@ static int blend_pyramids(sr_blend_plan *P, int dtype, void *const *h_d_tiles, c
     }
     // tiles whose levels 1 and 2 come out of one march (u8 RGB, 32-bit offsets inside a tile and the arena; a strip's row
     // windows included)
+    const int g1f = g1_format(P, dtype, h_strides);                 // G1_U16: every listed tile with level-1 rows in use is taken below
     int n_take = 0, max_take_h1 = 0, max_take_cols = 0;
     if (P->down2 && P->cn == 3 && dtype == SR_U8 && P->arena_floats * sizeof(float) < 0xFFFF0000ull) {
         bool ok = true;
-        for (int k = 0; k < n_idx && ok; ++k)
-            ok = sub_s[k].stride > 0 && (unsigned long long)sub_s[k].stride * (unsigned long long)(P->tiles[idx[k]].H[0] + 2) < 0x7FFF0000ull;
+        for (int k = 0; k < n_idx && ok; ++k) ok = down2_stride_fits(sub_s[k].stride, P->tiles[idx[k]].H[0]);
         for (int k = 0; k < n_idx && ok; ++k) {
             const TileDev &T = P->tiles[idx[k]];
             if (!down2_takes(T)) continue;
@@ -2525,11 +2603,16 @@ static int blend_pyramids(sr_blend_plan *P, int dtype, void *const *h_d_tiles, c
                     }
                 }
                 dim3 grid2(items + (max_take_h1 + 3) / 4, 1, n_idx);
-                hipLaunchKernelGGL((k_down2_march<3>), grid2, dim3(64), 0, ctx->stream, d_tiles, d_srcs, seg2, items, P->d_arena,
-                                   (unsigned)(P->arena_floats * sizeof(float)), P->d_arena, P->d_luts);
+                if (g1f == G1_U16)
+                    hipLaunchKernelGGL((k_down2_march<3, G1_U16>), grid2, dim3(64), 0, ctx->stream, d_tiles, d_srcs, seg2, items, P->d_arena,
+                                       (unsigned)(P->arena_floats * sizeof(float)), P->d_arena, P->d_luts);
+                else
+                    hipLaunchKernelGGL((k_down2_march<3, G1_F32>), grid2, dim3(64), 0, ctx->stream, d_tiles, d_srcs, seg2, items, P->d_arena,
+                                       (unsigned)(P->arena_floats * sizeof(float)), P->d_arena, P->d_luts);
             } else {
                 dim3 grid2((max_take_cols + 255) / 256, 1, n_idx);
-                hipLaunchKernelGGL(k_down2_cols, grid2, dim3(256), 0, ctx->stream, d_tiles, P->d_arena);
+                if (g1f == G1_U16) hipLaunchKernelGGL(k_down2_cols<G1_U16>, grid2, dim3(256), 0, ctx->stream, d_tiles, P->d_arena);
+                else hipLaunchKernelGGL(k_down2_cols<G1_F32>, grid2, dim3(256), 0, ctx->stream, d_tiles, P->d_arena);
             }
             if (n_take == n_idx) continue;
             skip2 = 1;
@@ -2625,25 +2708,28 @@ static int blend_gather(sr_blend_plan *P, bool lap, int dtype, void *const *h_d_
             for (int t = 0; t < P->n && marched; ++t)
                 marched = h_strides[t] > 0 && (unsigned long long)h_strides[t] * (unsigned long long)P->tiles[t].h < MARCH_OFF_LIMIT;
             const unsigned arena_bytes = (unsigned)std::min<size_t>(P->arena_floats * sizeof(float), 0xFFFFFFFFu);
+            const bool u16 = g1_format(P, dtype, h_strides) == G1_U16;      // (three planes, u8 tiles: the plan's and the call's part)
             if (marched && P->n_march_items[1] > 0) {
                 ProfScope ps2(ctx, "gather_march1");
-                if (P->cn == 3)
-                    hipLaunchKernelGGL((k_final_march1<3>), dim3((unsigned)P->n_march_items[1]), dim3(64), 0, ctx->stream, P->d_march_items[1],
-                                       P->d_fdesc, P->d_arena, arena_bytes, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w);
-                else
-                    hipLaunchKernelGGL((k_final_march1<1>), dim3((unsigned)P->n_march_items[1]), dim3(64), 0, ctx->stream, P->d_march_items[1],
-                                       P->d_fdesc, P->d_arena, arena_bytes, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w);
+#define LAUNCH_MARCH1(CNV, G1V)                                                                                          \
+    hipLaunchKernelGGL((k_final_march1<CNV, G1V>), dim3((unsigned)P->n_march_items[1]), dim3(64), 0, ctx->stream, P->d_march_items[1], \
+                       P->d_fdesc, P->d_arena, arena_bytes, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w)
+                if (u16) LAUNCH_MARCH1(3, G1_U16);
+                else if (P->cn == 3) LAUNCH_MARCH1(3, G1_F32);
+                else LAUNCH_MARCH1(1, G1_F32);
+#undef LAUNCH_MARCH1
             }
-#define LAUNCH_MARCHN(CNV, NTV)                                                                                          \
-    hipLaunchKernelGGL((k_final_marchn<CNV, NTV>), dim3((unsigned)P->n_march_items[NTV]), dim3(64 * NTV), 0, ctx->stream,       \
+#define LAUNCH_MARCHN(CNV, NTV, G1V)                                                                                     \
+    hipLaunchKernelGGL((k_final_marchn<CNV, NTV, G1V>), dim3((unsigned)P->n_march_items[NTV]), dim3(64 * NTV), 0, ctx->stream,       \
                        P->d_march_items[NTV], P->d_fdesc, P->d_arena, arena_bytes, P->d_luts, d_canvas,                      \
                        (long long)canvas_stride, d_canvas_f32, P->canvas_w)
             static_assert(MARCH_NT == 4, "the tile counts launched here");
             for (int nt = 2; nt <= MARCH_NT && marched; ++nt) {
                 if (P->n_march_items[nt] <= 0) continue;
                 ProfScope ps2(ctx, nt == 2 ? "gather_march2" : (nt == 3 ? "gather_march3" : "gather_march4"));
-                if (P->cn == 3) { if (nt == 2) LAUNCH_MARCHN(3, 2); else if (nt == 3) LAUNCH_MARCHN(3, 3); else LAUNCH_MARCHN(3, 4); }
-                else            { if (nt == 2) LAUNCH_MARCHN(1, 2); else if (nt == 3) LAUNCH_MARCHN(1, 3); else LAUNCH_MARCHN(1, 4); }
+                if (u16)             { if (nt == 2) LAUNCH_MARCHN(3, 2, G1_U16); else if (nt == 3) LAUNCH_MARCHN(3, 3, G1_U16); else LAUNCH_MARCHN(3, 4, G1_U16); }
+                else if (P->cn == 3) { if (nt == 2) LAUNCH_MARCHN(3, 2, G1_F32); else if (nt == 3) LAUNCH_MARCHN(3, 3, G1_F32); else LAUNCH_MARCHN(3, 4, G1_F32); }
+                else                 { if (nt == 2) LAUNCH_MARCHN(1, 2, G1_F32); else if (nt == 3) LAUNCH_MARCHN(1, 3, G1_F32); else LAUNCH_MARCHN(1, 4, G1_F32); }
             }
 #undef LAUNCH_MARCHN
             ProfScope ps3(ctx, "gather_rest");
@@ -2651,23 +2737,24 @@ static int blend_gather(sr_blend_plan *P, bool lap, int dtype, void *const *h_d_
             // blocks); without one, the edge blocks and every regular block of k_final_fused
             if (marched) {
                 if (P->n_rects > 0) {
-                    if (P->cn == 3)
-                        hipLaunchKernelGGL((k_final_rect<3>), dim3((unsigned)P->n_rects), dim3(FU_THREADS), 0, ctx->stream, P->d_fdesc, P->d_rects,
-                                           P->d_rect_cand, P->d_arena, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w,
-                                           P->row_begin, P->row_end);
-                    else
-                        hipLaunchKernelGGL((k_final_rect<1>), dim3((unsigned)P->n_rects), dim3(FU_THREADS), 0, ctx->stream, P->d_fdesc, P->d_rects,
-                                           P->d_rect_cand, P->d_arena, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w,
-                                           P->row_begin, P->row_end);
+#define LAUNCH_RECT(CNV, G1V)                                                                                            \
+    hipLaunchKernelGGL((k_final_rect<CNV, G1V>), dim3((unsigned)P->n_rects), dim3(FU_THREADS), 0, ctx->stream, P->d_fdesc, P->d_rects, \
+                       P->d_rect_cand, P->d_arena, P->d_luts, d_canvas, (long long)canvas_stride, d_canvas_f32, P->canvas_w,  \
+                       P->row_begin, P->row_end)
+                    if (u16) LAUNCH_RECT(3, G1_U16);
+                    else if (P->cn == 3) LAUNCH_RECT(3, G1_F32);
+                    else LAUNCH_RECT(1, G1_F32);
+#undef LAUNCH_RECT
                 }
             } else {
                 dim3 grid((unsigned)(n_edge + (long long)nbx_r * nby_r)), blk1(FU_THREADS);
-#define LAUNCH_FUSED(DT, CNV)                                                                                          \
-    hipLaunchKernelGGL((k_final_fused<DT, CNV>), grid, blk1, 0, ctx->stream, P->d_fdesc, P->d_fcand_off, P->d_fcand_idx,  \
+#define LAUNCH_FUSED(DT, CNV, G1V)                                                                                     \
+    hipLaunchKernelGGL((k_final_fused<DT, CNV, G1V>), grid, blk1, 0, ctx->stream, P->d_fdesc, P->d_fcand_off, P->d_fcand_idx,  \
                        P->d_fedge_blocks, P->d_fedge_cand, n_edge, nbx_r, P->d_arena, P->d_luts, d_canvas,             \
                        (long long)canvas_stride, d_canvas_f32, P->canvas_w, P->row_begin, P->row_end)
-                if (P->cn == 3) { if (dtype == SR_U8) LAUNCH_FUSED(SRC_U8, 3); else LAUNCH_FUSED(SRC_F32, 3); }
-                else            { if (dtype == SR_U8) LAUNCH_FUSED(SRC_U8, 1); else LAUNCH_FUSED(SRC_F32, 1); }
+                if (u16)             LAUNCH_FUSED(SRC_U8, 3, G1_U16);
+                else if (P->cn == 3) { if (dtype == SR_U8) LAUNCH_FUSED(SRC_U8, 3, G1_F32); else LAUNCH_FUSED(SRC_F32, 3, G1_F32); }
+                else                 { if (dtype == SR_U8) LAUNCH_FUSED(SRC_U8, 1, G1_F32); else LAUNCH_FUSED(SRC_F32, 1, G1_F32); }
 #undef LAUNCH_FUSED
             }
         } else if (P->cn == 3 || P->cn == 1) {                  // weighted average (their Laplacian blend is fused, above)

@@ -62,6 +62,14 @@ __device__ __forceinline__ u3_t march_ld3(march_rsrc r, unsigned voff, unsigned 
 {
     return __builtin_bit_cast(u3_t, __builtin_amdgcn_raw_buffer_load_b96(r, voff, soff, 0));
 }
+// G_1 at a lane's two own columns as it is stored (G1<>, sr_engine.hip): 8 bytes of fp32, or 4 bytes of 16-bit integers (at
+// an odd column a request that is only 2-byte aligned, like the pixel rows' 12-byte ones)
+template <int G1F>
+__device__ __forceinline__ typename G1<G1F>::pair_t march_ldg1(march_rsrc r, unsigned voff, unsigned soff)
+{
+    if constexpr (G1F == G1_U16) return __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0);
+    else return march_ld2(r, voff, soff);
+}
 
 // the value `v` of the lane to the left / right: a whole-wave shift by one lane (DPP wave_shr:1 / wave_shl:1 -- probed on
 // gfx950, tools/ubench_cvt.hip: lane i takes lane i - 1 / i + 1 across all 64 lanes; the end lane keeps `v`).  One VALU move
@@ -85,8 +93,9 @@ struct MarchU {
     unsigned g1, w1;                 // arena byte offset of the level-1 row the next request takes (plane 0 / weight level)
     unsigned g2, r2;                 // arena byte offset of the level-2 row the next even level-1 row takes (plane 0)
     unsigned pxe, pxo;               // byte offset of the next step's pixel row of even / odd pyrUp phase
-    unsigned p1b, p2b, px2;          // row pitches of levels 1 and 2, two pixel rows, in bytes
-    unsigned plane1b, plane2b;       // plane sizes of levels 1 and 2 in bytes
+    unsigned p1b, p2b, px2;          // row pitches of levels 1 (W_1) and 2, two pixel rows, in bytes
+    unsigned p1g;                    // row pitch of G_1 in bytes (p1b, or half of it where G_1 is stored in 16 bits)
+    unsigned plane1b, plane2b;       // plane sizes of G_1 and of level 2 in bytes
     int r0;                          // level-1 row of the first step's first tap row (its parity picks the loop variant)
     int lye, lyo;                    // tile-local row of the next step's even- / odd-phase pixel row
     int h1, fw;                      // tile height - 1, feather width
@@ -97,7 +106,8 @@ struct MarchU {
 };
 // per tile: per-lane part that does not depend on the plane
 struct MarchV {
-    unsigned v1, v2, vpx;            // byte offsets: own column a of level 1, column n0 of level 2, the cell's first pixel
+    unsigned v1, v2, vpx;            // byte offsets: own column a of level 1 (W_1), column n0 of level 2, the cell's first pixel
+    unsigned v1g;                    // own column a of G_1
     f2_t fx02, fx13;                 // column weights
 };
 // per tile and plane
@@ -220,6 +230,7 @@ __device__ __forceinline__ int march_smin(int a, int b)
 }
 
 // the uniform and per-lane parts of one tile for the item at (x of the lane's cell, first canvas row y0)
+template <int G1F>
 __device__ __forceinline__ void march_tile_uv(MarchU &U, MarchV &V, const FinalDesc &D, const float *__restrict__ luts, int x_lane,
                                               int x_px, int y0, bool useful, int pxsize)
 {
@@ -232,12 +243,13 @@ __device__ __forceinline__ void march_tile_uv(MarchU &U, MarchV &V, const FinalD
     U.p1b = (unsigned)D.P1 * 4u;
     U.p2b = (unsigned)D.P2 * 4u;
     U.px2 = (unsigned)(2 * D.stride);
-    U.plane1b = (unsigned)D.H1 * U.p1b;
+    U.p1g = (unsigned)D.P1 * G1<G1F>::ES;
+    U.plane1b = (unsigned)D.H1 * U.p1g;
     U.plane2b = (unsigned)D.H2 * U.p2b;
     U.h1 = D.h - 1;
     U.fw = D.fw;
     U.lut = luts + D.lut_off;
-    U.g1 = (unsigned)(D.g1 * 4) + (unsigned)r0 * U.p1b;
+    U.g1 = (unsigned)(D.g1 * 4) + (unsigned)r0 * U.p1g;
     U.w1 = (unsigned)(D.w1 * 4) + (unsigned)r0 * U.p1b;
     U.g2 = (unsigned)(D.g2 * 4) + (unsigned)m0 * U.p2b;
     U.r2 = (unsigned)(D.r2 * 4) + (unsigned)m0 * U.p2b;
@@ -249,6 +261,7 @@ __device__ __forceinline__ void march_tile_uv(MarchU &U, MarchV &V, const FinalD
     U.pxo = (unsigned)U.lyo * (unsigned)D.stride;
     U.r0 = r0;
     V.v1 = (unsigned)a * 4u;
+    V.v1g = (unsigned)a * G1<G1F>::ES;
     V.v2 = (unsigned)n0 * 4u;
     V.vpx = (unsigned)(x_px - D.x) * (unsigned)pxsize;
     float fx[4];
@@ -269,6 +282,7 @@ __device__ __forceinline__ void march_tile_uv(MarchU &U, MarchV &V, const FinalD
 // warm-up of one plane: the level-2 ring (rows m0, m0 + 1), then level-1 rows r0 and r0 + 1 into ring slots 0 and 1.
 // g1 / w1 / g2 / r2: this plane's arena offsets of rows r0 / m0 (not advanced here: the caller advances the tile's rows
 // once for all planes).  Loads are waited for on the spot: once per work item.
+template <int G1F>
 __device__ __forceinline__ void march_plane_warmup(const MarchU &U, const MarchV &V, MarchP &S, march_rsrc arena, unsigned g1,
                                                    unsigned w1, unsigned g2, unsigned r2)
 {
@@ -278,7 +292,7 @@ __device__ __forceinline__ void march_plane_warmup(const MarchU &U, const MarchV
         march_l2_hpass(p1, march_ld3(arena, V.v2, g2 + i * U.p2b), march_ld3(arena, V.v2, r2 + i * U.p2b), S.H2[i][0], S.H2[i][1]);
     // r0 odd: row r0 takes no new level-2 row, row r0 + 1 does (row m0 + 2); r0 even: the other way round
     const u3_t n2g = march_ld3(arena, V.v2, g2 + 2 * U.p2b), n2r = march_ld3(arena, V.v2, r2 + 2 * U.p2b);
-    const f2_t ga = march_ld2(arena, V.v1, g1), gb = march_ld2(arena, V.v1, g1 + U.p1b);
+    const f2_t ga = G1<G1F>::pair(march_ldg1<G1F>(arena, V.v1g, g1)), gb = G1<G1F>::pair(march_ldg1<G1F>(arena, V.v1g, g1 + U.p1g));
     const f2_t wa = march_ld2(arena, V.v1, w1), wb = march_ld2(arena, V.v1, w1 + U.p1b);
     if (U.r0 & 1) {
         march_l1_row<false>(U.flags, S, ga, wa, n2g, n2r, S.HG[0], S.HR[0]);
@@ -292,7 +306,7 @@ __device__ __forceinline__ void march_plane_warmup(const MarchU &U, const MarchV
 // the tile's row offsets after the warm-up: level-1 rows r0, r0 + 1 and level-2 rows m0 .. m0 + 2 are consumed
 __device__ __forceinline__ void march_after_warmup(MarchU &U)
 {
-    U.g1 += 2 * U.p1b;
+    U.g1 += 2 * U.p1g;
     U.w1 += 2 * U.p1b;
     U.g2 += 3 * U.p2b;
     U.r2 += 3 * U.p2b;
@@ -306,9 +320,9 @@ __device__ __forceinline__ void march_after_warmup(MarchU &U)
 // unrolled by two), each refilled for the step after next the moment its values are consumed -- the per-plane arrays right
 // after the plane's level-1 row, what all planes share (W_1, the pixel bytes) at the end of the step.  Only the set of the
 // even level-1 rows carries level-2 rows, so the second set costs six registers.
-template <int CN>
+template <int CN, int G1F>
 struct MarchPlaneLoad {
-    f2_t g[CN];
+    typename G1<G1F>::pair_t g[CN];                                 // as stored: converted where the row is formed
     u3_t l2g[CN], l2r[CN];
 };
 template <int CN>
@@ -341,11 +355,11 @@ __device__ __forceinline__ void march_request_shared(MarchU &U, const MarchV &V,
 }
 
 // the per-plane part of the first step
-template <int CN, bool EVEN>
-__device__ __forceinline__ void march_request_planes(MarchU &U, const MarchV &V, march_rsrc arena, MarchPlaneLoad<CN> &L)
+template <int CN, bool EVEN, int G1F>
+__device__ __forceinline__ void march_request_planes(MarchU &U, const MarchV &V, march_rsrc arena, MarchPlaneLoad<CN, G1F> &L)
 {
 #pragma unroll
-    for (int c = 0; c < CN; ++c) L.g[c] = march_ld2(arena, V.v1, U.g1 + c * U.plane1b);
+    for (int c = 0; c < CN; ++c) L.g[c] = march_ldg1<G1F>(arena, V.v1g, U.g1 + c * U.plane1b);
     if (EVEN) {
 #pragma unroll
         for (int c = 0; c < CN; ++c) {
@@ -355,7 +369,7 @@ __device__ __forceinline__ void march_request_planes(MarchU &U, const MarchV &V,
         U.g2 += U.p2b;
         U.r2 += U.p2b;
     }
-    U.g1 += U.p1b;
+    U.g1 += U.p1g;
 }
 
 // one byte of an output row into its dword: clip, then truncate (blending_module.py:501-506).  v_cvt_pk_u8_f32 saturates to
@@ -416,8 +430,8 @@ __device__ __forceinline__ f2_t march_px_pair(const unsigned (&wd)[CN == 3 ? 3 :
 // UNIT: every weight the item touches is exactly 1 (beyond the feather width of a linear / cosine ramp), so lap * w == lap
 // and the weight sum is 1: multiplies, weights and the division are left out (bit-identical: x * 1 == x, x / 1 == x).
 // L / H hold this step's data on entry and, when `more`, the data of the step after next (same parity) on return.
-template <int CN, int PH, bool EVEN, bool UNIT, int FL, bool W1U>
-__device__ __forceinline__ void march1_step(MarchU &U, const MarchV &V, MarchP (&S)[CN], MarchPlaneLoad<CN> &L,
+template <int CN, int PH, bool EVEN, bool UNIT, int FL, bool W1U, int G1F>
+__device__ __forceinline__ void march1_step(MarchU &U, const MarchV &V, MarchP (&S)[CN], MarchPlaneLoad<CN, G1F> &L,
                                             MarchSharedLoad<CN> &H, march_rsrc arena, bool more, bool useful, march_rsrc out,
                                             unsigned vout, unsigned o_e, unsigned o_o, march_rsrc outf, bool with_f, unsigned f_e,
                                             unsigned f_o)
@@ -450,9 +464,9 @@ __device__ __forceinline__ void march1_step(MarchU &U, const MarchV &V, MarchP (
 #pragma unroll
     for (int c = 0; c < CN; ++c) {
         f2_t hg[2], hr[2], ug[2][2], ur[2][2];
-        march_l1_row<EVEN, W1U>(flags, S[c], L.g[c], H.w, L.l2g[c], L.l2r[c], hg, hr);
+        march_l1_row<EVEN, W1U>(flags, S[c], G1<G1F>::pair(L.g[c]), H.w, L.l2g[c], L.l2r[c], hg, hr);
         if (more) {                                                 // this plane's rows of the step after next
-            L.g[c] = march_ld2(arena, V.v1, U.g1 + c * U.plane1b);
+            L.g[c] = march_ldg1<G1F>(arena, V.v1g, U.g1 + c * U.plane1b);
             if (EVEN) {
                 L.l2g[c] = march_ld3(arena, V.v2, U.g2 + c * U.plane2b);
                 L.l2r[c] = march_ld3(arena, V.v2, U.r2 + c * U.plane2b);
@@ -479,7 +493,7 @@ __device__ __forceinline__ void march1_step(MarchU &U, const MarchV &V, MarchP (
         MARCH_PLANE_FENCE;                                          // plane by plane: the next plane's work is not pulled up
     }
     if (more) {
-        U.g1 += U.p1b;
+        U.g1 += U.p1g;
         if (EVEN) {
             U.g2 += U.p2b;
             U.r2 += U.p2b;
@@ -505,25 +519,25 @@ __device__ __forceinline__ void march1_step(MarchU &U, const MarchV &V, MarchP (
 // phase flags (MT_XO | MT_YO | MT_P1) as a constant -- the unit-weight loop, which runs over two thirds of a grid's canvas,
 // exists once per phase combination: straight-line code, no scalar tests and branches (at two waves per SIMD a wave's own
 // instruction stream, scalar instructions included, is what bounds a step).
-template <int CN, bool E0, bool UNIT, int FL, bool W1U>
+template <int CN, bool E0, bool UNIT, int FL, bool W1U, int G1F>
 __device__ __forceinline__ void march1_loop(MarchU &U, const MarchV &V, MarchP (&S)[CN], march_rsrc arena, int nstep,
                                             bool useful, march_rsrc out, unsigned vout, unsigned cstride, march_rsrc outf,
                                             bool with_f, unsigned fstride)
 {
-    MarchPlaneLoad<CN> LA, LB;
+    MarchPlaneLoad<CN, G1F> LA, LB;
     MarchSharedLoad<CN> HA, HB;
     const bool yo = (U.flags & MT_YO) != 0;
     unsigned o_e = yo ? cstride : 0u, o_o = yo ? 0u : cstride, f_e = yo ? fstride : 0u, f_o = yo ? 0u : fstride;
-    march_request_planes<CN, E0>(U, V, arena, LA);
+    march_request_planes<CN, E0, G1F>(U, V, arena, LA);
     march_request_shared<CN, W1U>(U, V, arena, HA);
-    march_request_planes<CN, !E0>(U, V, arena, LB);
+    march_request_planes<CN, !E0, G1F>(U, V, arena, LB);
     march_request_shared<CN, W1U>(U, V, arena, HB);
 #pragma unroll 1
     for (int s = 0; s < nstep; s += 2) {
         const bool more = s + 2 < nstep;
-        march1_step<CN, 0, E0, UNIT, FL, W1U>(U, V, S, LA, HA, arena, more, useful, out, vout, o_e, o_o, outf, with_f, f_e, f_o);
+        march1_step<CN, 0, E0, UNIT, FL, W1U, G1F>(U, V, S, LA, HA, arena, more, useful, out, vout, o_e, o_o, outf, with_f, f_e, f_o);
         o_e += 2 * cstride; o_o += 2 * cstride; f_e += 2 * fstride; f_o += 2 * fstride;
-        march1_step<CN, 1, !E0, UNIT, FL, W1U>(U, V, S, LB, HB, arena, more, useful, out, vout, o_e, o_o, outf, with_f, f_e, f_o);
+        march1_step<CN, 1, !E0, UNIT, FL, W1U, G1F>(U, V, S, LB, HB, arena, more, useful, out, vout, o_e, o_o, outf, with_f, f_e, f_o);
         o_e += 2 * cstride; o_o += 2 * cstride; f_e += 2 * fstride; f_o += 2 * fstride;
     }
 }
@@ -546,7 +560,7 @@ __device__ __forceinline__ MarchLanes march_lanes(const MarchItem &it, int lane)
 }
 
 // arena_bytes < 4 GB and the rows of one item < 4 GB of canvas: checked on the host when the plan is made
-template <int CN>
+template <int CN, int G1F>
 __global__ __launch_bounds__(64, MARCH1_WAVES) void k_final_march1(const MarchItem *__restrict__ items, const FinalDesc *__restrict__ descs,
                                                       const float *__restrict__ arena_p, unsigned arena_bytes,
                                                       const float *__restrict__ luts, unsigned char *__restrict__ canvas,
@@ -560,10 +574,10 @@ __global__ __launch_bounds__(64, MARCH1_WAVES) void k_final_march1(const MarchIt
     MarchU U;
     MarchV V;
     MarchP S[CN];
-    march_tile_uv(U, V, D, luts, M.x_lane, M.x_px, it.y0, M.useful, CN);
+    march_tile_uv<G1F>(U, V, D, luts, M.x_lane, M.x_px, it.y0, M.useful, CN);
 #pragma unroll
     for (int c = 0; c < CN; ++c)
-        march_plane_warmup(U, V, S[c], arena, U.g1 + c * U.plane1b, U.w1, U.g2 + c * U.plane2b, U.r2 + c * U.plane2b);
+        march_plane_warmup<G1F>(U, V, S[c], arena, U.g1 + c * U.plane1b, U.w1, U.g2 + c * U.plane2b, U.r2 + c * U.plane2b);
     march_after_warmup(U);
     // every row weight of the item is lut[fw] == 1 (the column weights: MT_FXUNIT)
     const int ly0 = it.y0 - D.y;
@@ -575,7 +589,7 @@ __global__ __launch_bounds__(64, MARCH1_WAVES) void k_final_march1(const MarchIt
                                             with_f ? 0xFFFFFFFFu : 0u);
     const unsigned vout = (unsigned)M.x_px * CN;
     const bool e0 = !(U.r0 & 1);                                    // the first step produces level-1 row r0 + 2
-#define MARCH_GO(EV, UV, FLV, WV) march1_loop<CN, EV, UV, FLV, WV>(U, V, S, arena, nstep, M.useful, out, vout, (unsigned)cstride, outf, with_f, fstride)
+#define MARCH_GO(EV, UV, FLV, WV) march1_loop<CN, EV, UV, FLV, WV, G1F>(U, V, S, arena, nstep, M.useful, out, vout, (unsigned)cstride, outf, with_f, fstride)
 #define MARCH_GO_FL(FLV) do { if (e0) MARCH_GO(true, true, FLV, true); else MARCH_GO(false, true, FLV, true); } while (0)
     // ... and W_1 is 1 as well MARCH_W1_MARGIN pixels further in (all of a grid's single coverage but the strips that touch the
     // feather ramps): the phase-specialised loops leave W_1 out; unit items closer to the ramps take the general loop
@@ -616,8 +630,8 @@ struct MarchX {
 
 // one step of one wave: xw = this tile's [canvas row 0] vector 0 of the step's slot for this lane, xr = tile 0's [this
 // wave's canvas row] (finishers only)
-template <int CN, int NT, int PH, bool EVEN, int FL>
-__device__ __forceinline__ void marchn_step(MarchU &U, const MarchV &V, MarchP (&S)[CN], MarchPlaneLoad<CN> &L,
+template <int CN, int NT, int PH, bool EVEN, int FL, int G1F>
+__device__ __forceinline__ void marchn_step(MarchU &U, const MarchV &V, MarchP (&S)[CN], MarchPlaneLoad<CN, G1F> &L,
                                             MarchSharedLoad<CN> &H, march_rsrc arena, bool more, bool useful, bool finisher,
                                             float *xw, const float *xr,
                                             march_rsrc out, unsigned vout, unsigned o_fin, march_rsrc outf, bool with_f,
@@ -632,9 +646,9 @@ __device__ __forceinline__ void marchn_step(MarchU &U, const MarchV &V, MarchP (
 #pragma unroll
     for (int c = 0; c < CN; ++c) {
         f2_t hg[2], hr[2], ug[2][2], ur[2][2];
-        march_l1_row<EVEN>(flags, S[c], L.g[c], H.w, L.l2g[c], L.l2r[c], hg, hr);
+        march_l1_row<EVEN>(flags, S[c], G1<G1F>::pair(L.g[c]), H.w, L.l2g[c], L.l2r[c], hg, hr);
         if (more) {                                                 // this plane's rows of the step after next
-            L.g[c] = march_ld2(arena, V.v1, U.g1 + c * U.plane1b);
+            L.g[c] = march_ldg1<G1F>(arena, V.v1g, U.g1 + c * U.plane1b);
             if (EVEN) {
                 L.l2g[c] = march_ld3(arena, V.v2, U.g2 + c * U.plane2b);
                 L.l2r[c] = march_ld3(arena, V.v2, U.r2 + c * U.plane2b);
@@ -657,7 +671,7 @@ __device__ __forceinline__ void marchn_step(MarchU &U, const MarchV &V, MarchP (
 #pragma unroll
         for (int p = 0; p < 2; ++p) *(f2_t *)(xw + (q ? row_o : row_e) + CN * 256 + p * 128) = w0[q][p];
     if (more) {
-        U.g1 += U.p1b;
+        U.g1 += U.p1g;
         if (EVEN) {
             U.g2 += U.p2b;
             U.r2 += U.p2b;
@@ -718,30 +732,30 @@ __device__ __forceinline__ void marchn_step(MarchU &U, const MarchV &V, MarchP (
     }
 }
 
-template <int CN, int NT, bool E0, int FL>
+template <int CN, int NT, bool E0, int FL, int G1F>
 __device__ __forceinline__ void marchn_loop(MarchU &U, const MarchV &V, MarchP (&S)[CN], march_rsrc arena, int nstep,
                                             bool useful, bool finisher, float *xw, const float *xr, march_rsrc out, unsigned vout,
                                             unsigned o_fin, unsigned cstride, march_rsrc outf, bool with_f,
                                             unsigned f_fin, unsigned fstride)
 {
     typedef MarchX<CN, NT> X;
-    MarchPlaneLoad<CN> LA, LB;
+    MarchPlaneLoad<CN, G1F> LA, LB;
     MarchSharedLoad<CN> HA, HB;
-    march_request_planes<CN, E0>(U, V, arena, LA);
+    march_request_planes<CN, E0, G1F>(U, V, arena, LA);
     march_request_shared<CN>(U, V, arena, HA);
-    march_request_planes<CN, !E0>(U, V, arena, LB);
+    march_request_planes<CN, !E0, G1F>(U, V, arena, LB);
     march_request_shared<CN>(U, V, arena, HB);
 #pragma unroll 1
     for (int s = 0; s < nstep; s += 2) {
         const bool more = s + 2 < nstep;
-        marchn_step<CN, NT, 0, E0, FL>(U, V, S, LA, HA, arena, more, useful, finisher, xw, xr, out, vout, o_fin, outf, with_f, f_fin);
+        marchn_step<CN, NT, 0, E0, FL, G1F>(U, V, S, LA, HA, arena, more, useful, finisher, xw, xr, out, vout, o_fin, outf, with_f, f_fin);
         o_fin += 2 * cstride; f_fin += 2 * fstride;
-        marchn_step<CN, NT, 1, !E0, FL>(U, V, S, LB, HB, arena, more, useful, finisher, xw + X::SLOT, xr + X::SLOT, out, vout, o_fin, outf, with_f, f_fin);
+        marchn_step<CN, NT, 1, !E0, FL, G1F>(U, V, S, LB, HB, arena, more, useful, finisher, xw + X::SLOT, xr + X::SLOT, out, vout, o_fin, outf, with_f, f_fin);
         o_fin += 2 * cstride; f_fin += 2 * fstride;
     }
 }
 
-template <int CN, int NT>
+template <int CN, int NT, int G1F>
 __global__ __launch_bounds__(64 * NT, MARCHN_WAVES) void k_final_marchn(const MarchItem *__restrict__ items, const FinalDesc *__restrict__ descs,
                                                        const float *__restrict__ arena_p, unsigned arena_bytes,
                                                        const float *__restrict__ luts, unsigned char *__restrict__ canvas,
@@ -759,10 +773,10 @@ __global__ __launch_bounds__(64 * NT, MARCHN_WAVES) void k_final_marchn(const Ma
     MarchU U;
     MarchV V;
     MarchP S[CN];
-    march_tile_uv(U, V, D, luts, M.x_lane, M.x_px, it.y0, M.useful, CN);
+    march_tile_uv<G1F>(U, V, D, luts, M.x_lane, M.x_px, it.y0, M.useful, CN);
 #pragma unroll
     for (int c = 0; c < CN; ++c)
-        march_plane_warmup(U, V, S[c], arena, U.g1 + c * U.plane1b, U.w1, U.g2 + c * U.plane2b, U.r2 + c * U.plane2b);
+        march_plane_warmup<G1F>(U, V, S[c], arena, U.g1 + c * U.plane1b, U.w1, U.g2 + c * U.plane2b, U.r2 + c * U.plane2b);
     march_after_warmup(U);
     const unsigned fstride = (unsigned)cw * CN * 4u;
     const bool with_f = canvas_f32 != nullptr;
@@ -775,7 +789,7 @@ __global__ __launch_bounds__(64 * NT, MARCHN_WAVES) void k_final_marchn(const Ma
     const float *xr = &xch[(wv & 1) * X::ROW + lane * 2];
     const unsigned o_fin = (wv & 1) ? (unsigned)cstride : 0u, f_fin = (wv & 1) ? fstride : 0u;
     const bool e0 = !(U.r0 & 1);
-#define MARCHN_GO(EV, FLV) marchn_loop<CN, NT, EV, FLV>(U, V, S, arena, nstep, M.useful, finisher, xw, xr, out, vout, o_fin, (unsigned)cstride, outf, with_f, f_fin, fstride)
+#define MARCHN_GO(EV, FLV) marchn_loop<CN, NT, EV, FLV, G1F>(U, V, S, arena, nstep, M.useful, finisher, xw, xr, out, vout, o_fin, (unsigned)cstride, outf, with_f, f_fin, fstride)
 #define MARCHN_GO_FL(FLV) do { if (e0) MARCHN_GO(true, FLV); else MARCHN_GO(false, FLV); } while (0)
     switch (U.flags & (MT_XO | MT_YO | MT_P1)) {                    // straight-line loops: one per phase combination of this wave's tile
     case 0: MARCHN_GO_FL(0); break;

@@ -15,7 +15,11 @@ Rules (round-2 verdict, weak #3):
     the factor measured on k_tile_extract (a pure copy whose byte count is known);
   * the script FAILS when a bench kernel family's corrected traffic is below 0.9 x its algorithmic bytes (that can only be
     a bookkeeping error).
-usage: tools/summarize_profiles.py <tag> <prefix>      e.g.  r03a  r03_a
+  * bench.py's byte model counts G_1 as fp32 (down_l0 6.75 B, final_gather 8.5 B per tile pixel).  A build that keeps G_1 of
+    u8 tiles in 16 bits (sr_blend_plan_g1_format) writes and reads 1.5 B per tile pixel less in each of the two families: a
+    third argument `g1u16` takes them off the model the refusal above compares with (the bench line's own GBps fields keep
+    bench.py's model and so understate such a build).
+usage: tools/summarize_profiles.py <tag> <prefix> [g1u16]      e.g.  r03a  r03_a
 """
 import collections
 import csv
@@ -88,7 +92,10 @@ for k in sorted(set(fetch) | set(write)):
 
 # consistency: corrected traffic of a bench family can not be below its algorithmic bytes
 geo = type("G", (), {"tile_pixels": tile_px, "canvas_pixels": canvas_px})
-alg = bench_mod.algorithmic_bytes(geo)
+alg = dict(bench_mod.algorithmic_bytes(geo))
+if len(sys.argv) > 3 and sys.argv[3] == "g1u16":
+    for fam in ("down_l0", "final_gather"):
+        alg[fam] -= 1.5 * tile_px
 fam_tot = collections.defaultdict(float)
 for k, rec in out["kernels"].items():
     fam = bench_mod.family_of(k)
