@@ -1246,48 +1246,51 @@ def srnet_plan(h: int, w: int, n_feat: int, n_body: int, scale: int, tile: int =
     return halo.value, n.value, int(ws.value)
 
 
-class SrNetModel:
-    """sr_srnet_model: the compact SR network resident on the GPU.  weights / biases: D + 2 arrays in layer order (OIHW fp32),
-    slopes: D + 1 arrays of F values."""
+class _SrModel:
+    """What SrNetModel, ResNetModel and RrdbModel share: the caller's tables as checked fp32 arrays, the create call, the two
+    forwards, close.  ``_kind`` names the sr_<kind>_* entry points, ``_run_args`` what their forwards take after the
+    destination stride."""
+    _kind = ""
+    _run_args = ("tile",)
 
-    def __init__(self, ctx: Context, n_feat: int, n_body: int, scale: int, weights, biases, slopes):
-        n_feat, n_body, scale = int(n_feat), int(n_body), int(scale)
-        srnet_plan(1, 1, n_feat, n_body, scale)                  # the supported range, refused before any array is touched
-        if len(weights) != n_body + 2 or len(biases) != n_body + 2 or len(slopes) != n_body + 1:
-            raise ValueError(f"SR network with {n_body} body convolutions needs {n_body + 2} weight / bias arrays and {n_body + 1} slope vectors")
+    @staticmethod
+    def _conv_arrays(weights, biases, shapes, what: str):
+        """-> (weights, biases) as contiguous fp32, checked against ``shapes`` = (cout, cin) per convolution."""
         ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
         bs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in biases]
-        ss = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in slopes]
-        for k, (w, b) in enumerate(zip(ws, bs)):
-            want = (3 * scale * scale if k == n_body + 1 else n_feat, 3 if k == 0 else n_feat, 3, 3)
-            if w.shape != want or b.shape != (want[0],):
-                raise ValueError(f"SR network layer {k}: expected {want} / {(want[0],)}, got {w.shape} / {b.shape}")
-        if any(s.shape != (n_feat,) for s in ss):
-            raise ValueError(f"SR network slopes must hold {n_feat} values each")
-        self.ctx, self.n_feat, self.n_body, self.scale = ctx, n_feat, n_body, scale
-        pw = (C.c_void_p * len(ws))(*[a.ctypes.data for a in ws])
-        pb = (C.c_void_p * len(bs))(*[a.ctypes.data for a in bs])
-        ps = (C.c_void_p * len(ss))(*[a.ctypes.data for a in ss])
+        for k, (w, b, (co, ci)) in enumerate(zip(ws, bs, shapes)):
+            if w.shape != (co, ci, 3, 3) or b.shape != (co,):
+                raise ValueError(f"{what} {k}: expected {(co, ci, 3, 3)} / {(co,)}, got {w.shape} / {b.shape}")
+        return ws, bs
+
+    def _create(self, ctx: Context, args, *tables, count: bool = False):
+        """sr_<kind>_create(ctx, *args, one pointer table per entry of ``tables``[, their length], &handle)."""
+        ptrs = [(C.c_void_p * len(t))(*[a.ctypes.data for a in t]) for t in tables]
         h = C.c_void_p()
-        _check_unsupported(ctx.lib.sr_srnet_create(ctx.handle, n_feat, n_body, scale, pw, pb, ps, C.byref(h)))
-        self.handle = h
+        create = getattr(ctx.lib, f"sr_{self._kind}_create")
+        _check_unsupported(create(ctx.handle, *args, *ptrs, *([len(tables[0])] if count else []), C.byref(h)))
+        self.ctx, self.handle = ctx, h
 
-    def plan(self, h: int, w: int, tile: int = 0) -> Tuple[int, int, int]:
-        return srnet_plan(h, w, self.n_feat, self.n_body, self.scale, tile)
+    def _run(self, entry: str, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, args, named):
+        names = self._run_args
+        if len(args) > len(names) or not set(named) <= set(names[len(args):]):
+            raise TypeError(f"sr_{self._kind}_{entry} takes {', '.join(names)} after the strides, got {args} {named}")
+        ints = [int(v) for v in args] + [int(named.get(n, 0)) for n in names[len(args):]]
+        check(getattr(self.ctx.lib, f"sr_{self._kind}_{entry}")(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w),
+                                                                C.c_void_p(d_dst), int(dst_stride), *ints))
 
-    def upscale_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0):
-        """sr_srnet_u8: h x w x 3 u8 -> (h s) x (w s) x 3 u8, HBM -> HBM.  Asynchronous."""
-        check(self.ctx.lib.sr_srnet_u8(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
-                                       int(dst_stride), int(tile)))
+    def upscale_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, *args, **named):
+        """sr_<kind>_u8: h x w x 3 u8 -> (h s) x (w s) x 3 u8, HBM -> HBM; then ``tile = 0`` (RrdbModel: and ``tail = 0``), by
+        position or by name.  Asynchronous."""
+        self._run("u8", d_src, src_stride, h, w, d_dst, dst_stride, args, named)
 
-    def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0):
-        """sr_srnet_f32: the unclamped fp32 output (HWC, stride in bytes).  Asynchronous."""
-        check(self.ctx.lib.sr_srnet_f32(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
-                                        int(dst_stride), int(tile)))
+    def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, *args, **named):
+        """sr_<kind>_f32: the unclamped fp32 output (HWC, stride in bytes); arguments as upscale_u8.  Asynchronous."""
+        self._run("f32", d_src, src_stride, h, w, d_dst, dst_stride, args, named)
 
     def close(self):
         if getattr(self, "handle", None):
-            self.ctx.lib.sr_srnet_destroy(self.handle)
+            getattr(self.ctx.lib, f"sr_{self._kind}_destroy")(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1295,6 +1298,28 @@ class SrNetModel:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+class SrNetModel(_SrModel):
+    """sr_srnet_model: the compact SR network resident on the GPU.  weights / biases: D + 2 arrays in layer order (OIHW fp32),
+    slopes: D + 1 arrays of F values."""
+    _kind = "srnet"
+
+    def __init__(self, ctx: Context, n_feat: int, n_body: int, scale: int, weights, biases, slopes):
+        n_feat, n_body, scale = int(n_feat), int(n_body), int(scale)
+        srnet_plan(1, 1, n_feat, n_body, scale)                  # the supported range, refused before any array is touched
+        if len(weights) != n_body + 2 or len(biases) != n_body + 2 or len(slopes) != n_body + 1:
+            raise ValueError(f"SR network with {n_body} body convolutions needs {n_body + 2} weight / bias arrays and {n_body + 1} slope vectors")
+        ss = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in slopes]
+        shapes = [(n_feat, 3)] + [(n_feat, n_feat)] * n_body + [(3 * scale * scale, n_feat)]
+        ws, bs = self._conv_arrays(weights, biases, shapes, "SR network layer")
+        if any(s.shape != (n_feat,) for s in ss):
+            raise ValueError(f"SR network slopes must hold {n_feat} values each")
+        self.n_feat, self.n_body, self.scale = n_feat, n_body, scale
+        self._create(ctx, (n_feat, n_body, scale), ws, bs, ss)
+
+    def plan(self, h: int, w: int, tile: int = 0) -> Tuple[int, int, int]:
+        return srnet_plan(h, w, self.n_feat, self.n_body, self.scale, tile)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1325,50 +1350,22 @@ def resnet_plan(desc: ResNetDesc, h: int, w: int, tile: int = 0) -> Tuple[int, i
     return halo.value, n.value, int(ws.value)
 
 
-class ResNetModel:
+class ResNetModel(_SrModel):
     """sr_resnet_model: a residual SR network (MSRResNet / EDSR) resident on the GPU.  weights / biases: one OIHW fp32 array
     and one bias vector per convolution in forward order (resnet_conv_shapes)."""
+    _kind = "resnet"
 
     def __init__(self, ctx: Context, desc: ResNetDesc, weights, biases):
         resnet_plan(desc, 1, 1)                                  # the supported range, refused before any array is touched
         shapes = resnet_conv_shapes(desc)
         if len(weights) != len(shapes) or len(biases) != len(shapes):
             raise ValueError(f"this residual SR network has {len(shapes)} convolutions, got {len(weights)} weight / {len(biases)} bias arrays")
-        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
-        bs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in biases]
-        for k, (w, b, (co, ci)) in enumerate(zip(ws, bs, shapes)):
-            if w.shape != (co, ci, 3, 3) or b.shape != (co,):
-                raise ValueError(f"residual SR network convolution {k}: expected {(co, ci, 3, 3)} / {(co,)}, got {w.shape} / {b.shape}")
-        self.ctx, self.desc, self.scale = ctx, desc, desc.scale
-        pw = (C.c_void_p * len(ws))(*[a.ctypes.data for a in ws])
-        pb = (C.c_void_p * len(bs))(*[a.ctypes.data for a in bs])
-        h = C.c_void_p()
-        _check_unsupported(ctx.lib.sr_resnet_create(ctx.handle, C.byref(desc), pw, pb, len(ws), C.byref(h)))
-        self.handle = h
+        ws, bs = self._conv_arrays(weights, biases, shapes, "residual SR network convolution")
+        self.desc, self.scale = desc, desc.scale
+        self._create(ctx, (C.byref(desc),), ws, bs, count=True)
 
     def plan(self, h: int, w: int, tile: int = 0) -> Tuple[int, int, int]:
         return resnet_plan(self.desc, h, w, tile)
-
-    def upscale_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0):
-        """sr_resnet_u8: h x w x 3 u8 -> (h s) x (w s) x 3 u8, HBM -> HBM.  Asynchronous."""
-        check(self.ctx.lib.sr_resnet_u8(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
-                                        int(dst_stride), int(tile)))
-
-    def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0):
-        """sr_resnet_f32: the unclamped fp32 output (HWC, stride in bytes).  Asynchronous."""
-        check(self.ctx.lib.sr_resnet_f32(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
-                                         int(dst_stride), int(tile)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.lib.sr_resnet_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 # ------------------------------------------------------------------------------------------
@@ -1393,50 +1390,23 @@ def rrdb_plan(desc: RrdbDesc, h: int, w: int, tile: int = 0, tail: int = 0) -> T
     return halo.value, n.value, nt.value, int(ws.value)
 
 
-class RrdbModel:
+class RrdbModel(_SrModel):
     """sr_rrdb_model: an RRDBNet (ESRGAN / Real-ESRGAN x4) resident on the GPU.  weights / biases: one OIHW fp32 array and one
     bias vector per convolution in forward order (rrdb_conv_shapes)."""
+    _kind = "rrdb"
+    _run_args = ("tile", "tail")
 
     def __init__(self, ctx: Context, desc: RrdbDesc, weights, biases):
         rrdb_plan(desc, 1, 1)                                    # the supported range, refused before any array is touched
         shapes = rrdb_conv_shapes(desc)
         if len(weights) != len(shapes) or len(biases) != len(shapes):
             raise ValueError(f"this RRDB network has {len(shapes)} convolutions, got {len(weights)} weight / {len(biases)} bias arrays")
-        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
-        bs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in biases]
-        for k, (w, b, (co, ci)) in enumerate(zip(ws, bs, shapes)):
-            if w.shape != (co, ci, 3, 3) or b.shape != (co,):
-                raise ValueError(f"RRDB network convolution {k}: expected {(co, ci, 3, 3)} / {(co,)}, got {w.shape} / {b.shape}")
-        self.ctx, self.desc, self.scale = ctx, desc, desc.scale
-        pw = (C.c_void_p * len(ws))(*[a.ctypes.data for a in ws])
-        pb = (C.c_void_p * len(bs))(*[a.ctypes.data for a in bs])
-        h = C.c_void_p()
-        _check_unsupported(ctx.lib.sr_rrdb_create(ctx.handle, C.byref(desc), pw, pb, len(ws), C.byref(h)))
-        self.handle = h
+        ws, bs = self._conv_arrays(weights, biases, shapes, "RRDB network convolution")
+        self.desc, self.scale = desc, desc.scale
+        self._create(ctx, (C.byref(desc),), ws, bs, count=True)
 
     def plan(self, h: int, w: int, tile: int = 0, tail: int = 0) -> Tuple[int, int, int, int]:
         return rrdb_plan(self.desc, h, w, tile, tail)
-
-    def upscale_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0, tail: int = 0):
-        """sr_rrdb_u8: h x w x 3 u8 -> (4 h) x (4 w) x 3 u8, HBM -> HBM.  Asynchronous."""
-        check(self.ctx.lib.sr_rrdb_u8(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
-                                      int(dst_stride), int(tile), int(tail)))
-
-    def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, tile: int = 0, tail: int = 0):
-        """sr_rrdb_f32: the unclamped fp32 output (HWC, stride in bytes).  Asynchronous."""
-        check(self.ctx.lib.sr_rrdb_f32(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), C.c_void_p(d_dst),
-                                       int(dst_stride), int(tile), int(tail)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.lib.sr_rrdb_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 _default_ctx = {}

@@ -9,8 +9,11 @@
 //   last conv   3 x 3 convolution F -> 3 at full resolution, o[c] = y[c] / range + mean[c] (+ the bilinear base), HWC store
 //
 // Everything is fp32 (fp32 in, fp32 accumulate).  Every F-input convolution is one implicit-GEMM kernel on
-// v_mfma_f32_32x32x2_f32 (the mainloop of sr_conv_mfma.h, shared with sr_lpips.hip and sr_srnet.hip), templated on its
-// epilogue; the 3 -> F head is the direct VALU kernel of k_sn_head with the input affine added.
+// v_mfma_f32_32x32x2_f32 (the mainloop of sr_conv_mfma.h, shared with sr_lpips.hip, sr_srnet.hip and sr_rrdb.hip), templated on
+// its epilogue; the 3 -> F head is the direct VALU kernel of k_sn_head with the input affine added.  What the three SR backends
+// share around the mainloop -- the head frame, leaky / skip_offset / store_hwc, the backward extent rule, the planar tensor, the
+// convolution launch, the models' lifetime -- is sr_net_common.h; this file holds the network's own kernels and epilogues,
+// its op list, its tile policy and its layer walk.
 //
 // Memory: activations are planar fp32 [F][rows][pitch] in three buffers owned by the model (in, out, and the skip / h).  The
 // image is walked in square sub-tiles of the INPUT.  Every layer's extent is derived backwards from the sub-tile's output
@@ -23,13 +26,11 @@
 // after the chain.  The order does not depend on where the output lies in a block or a sub-tile.
 //
 // Weights are caller-supplied (sr_resnet_create); nothing is fetched.
-#include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "sr_conv_mfma.h"
+#include "sr_net_common.h"
 
 namespace {
 
@@ -59,16 +60,7 @@ __global__ __launch_bounds__(256) void k_rn_head(const unsigned char *__restrict
         for (int c = 0; c < 3; ++c) lut[c][tid] = (v - af.mean[c]) * af.range;
     }
     __syncthreads();
-    const int lx = blockIdx.x * 64 + threadIdx.x, ly = blockIdx.y * 4 + threadIdx.y, ct = blockIdx.z;
-    if (lx >= cols || ly >= rows) return;
-    float acc[64];
-    head_accumulate<256>(img, stride, H, W, wt, bias, ct, &lut[0][0], ya + ly, xa + lx, acc);
-    float *o = out + (size_t)ct * 64 * plane + (size_t)ly * pitch + lx;
-#pragma unroll
-    for (int co = 0; co < 64; ++co) {
-        const float y = acc[co];
-        o[(size_t)co * plane] = y >= 0.0f ? y : slope * y;
-    }
+    head_frame<256>(img, stride, H, W, wt, bias, &lut[0][0], out, ya, xa, rows, cols, pitch, plane, [&](int, float y) { return leaky(y, slope); });
 }
 
 // The epilogues of k_rn_conv.
@@ -136,10 +128,10 @@ __global__ __launch_bounds__(256) void k_rn_conv(const float *__restrict__ in, l
                 for (int r = 0; r < 16; ++r) {
                     const int co = ct * NC + mfma_cout(c2, r, half);
                     const float y = acc[c2][pr][r];
-                    out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = y >= 0.0f ? y : ep.slope * y;
+                    out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = leaky(y, ep.slope);
                 }
         } else if constexpr (EPI == RN_SKIP) {
-            const size_t so = (size_t)(out_ya + row - ep.skip_ya) * ep.skip_pitch + (out_xa + col - ep.skip_xa);
+            const size_t so = skip_offset(out_ya + row, out_xa + col, ep.skip_ya, ep.skip_xa, ep.skip_pitch);
 #pragma unroll
             for (int c2 = 0; c2 < NC2; ++c2)
 #pragma unroll
@@ -157,7 +149,7 @@ __global__ __launch_bounds__(256) void k_rn_conv(const float *__restrict__ in, l
                     const int co = ct * NC + mfma_cout(c2, r, half);
                     const int c = co / (R * R), rem = co % (R * R), dy = rem / R, dx = rem % R;
                     const float y = acc[c2][pr][r];
-                    out[(size_t)c * out_plane + ((size_t)row * R + dy) * out_pitch + (size_t)col * R + dx] = y >= 0.0f ? y : ep.slope * y;
+                    out[(size_t)c * out_plane + ((size_t)row * R + dy) * out_pitch + (size_t)col * R + dx] = leaky(y, ep.slope);
                 }
         } else {                                           // output affine + bilinear base + HWC store
             if (half != 0) continue;                       // couts 0 .. 2 live in registers 0 .. 2 of the lower half-wave
@@ -177,9 +169,7 @@ __global__ __launch_bounds__(256) void k_rn_conv(const float *__restrict__ in, l
             for (int c = 0; c < 3; ++c) {
                 float o = acc[0][pr][c] / ep.af.range + ep.af.mean[c];
                 if (ep.bilinear) o = o + base[c];
-                const size_t e = (size_t)gx * 3 + c;
-                if constexpr (EPI == RN_LAST_U8) ((unsigned char *)d)[e] = (unsigned char)rintf(fminf(fmaxf(o, 0.0f), 1.0f) * 255.0f);
-                else ((float *)d)[e] = o;
+                store_hwc<EPI == RN_LAST_U8>(d, (size_t)gx * 3 + c, o);
             }
         }
     }
@@ -236,31 +226,12 @@ std::vector<RnOp> rn_build_ops(const sr_resnet_desc &d)
 // Resolution multiplier of a level for this scale.
 int rn_mult(int scale, int lvl) { return lvl == 0 ? 1 : (scale == 4 ? (lvl == 1 ? 2 : 4) : scale); }
 
-// One axis of the backward extent rule: the sub-tile [lo, hi) of an axis of n input pixels -> per op the half-open range
-// [a[i], b[i]) of its output at its own resolution.
-void rn_extents(const std::vector<RnOp> &ops, int scale, int lo, int hi, int n, std::vector<int> &a, std::vector<int> &b)
+// The extent rule's view of the ops (backward_extents, backward_halo: sr_net_common.h).
+std::vector<ExtStep> rn_steps(const std::vector<RnOp> &ops, int scale)
 {
-    a.resize(ops.size());
-    b.resize(ops.size());
-    long long na = (long long)lo * scale, nb = (long long)hi * scale;
-    for (int i = (int)ops.size() - 1; i >= 0; --i) {
-        const int r = ops[i].r;
-        na = na / r;                                       // outward: floor, ceil
-        nb = (nb + r - 1) / r;
-        a[i] = (int)na;
-        b[i] = (int)nb;
-        const long long len = (long long)n * rn_mult(scale, ops[i].lvl);
-        na = std::max(na - 1, 0LL);
-        nb = std::min(nb + 1, len);
-    }
-}
-
-// LR pixels a sub-tile reads beyond its own edge: the rule above without clipping.
-int rn_halo(const std::vector<RnOp> &ops)
-{
-    int g = 0;
-    for (int i = (int)ops.size() - 1; i >= 0; --i) g = (g + ops[i].r - 1) / ops[i].r + 1;
-    return g;
+    std::vector<ExtStep> steps;
+    for (const RnOp &op : ops) steps.push_back({op.r, rn_mult(scale, op.lvl)});
+    return steps;
 }
 
 struct RnGeom {
@@ -271,12 +242,10 @@ struct RnGeom {
 // Host only: sub-tile grid and buffer geometry of an h x w input.
 int rn_geometry(const char *who, const sr_resnet_desc &d, const std::vector<RnOp> &ops, int h, int w, int tile, RnGeom &g)
 {
-    if (h < 1 || w < 1) return sr_set_error(SR_ERR_SHAPE, "%s: %dx%d image", who, w, h);
-    if (tile < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: tile must be >= 1, or 0 for the library's choice", who);
-    const int s = d.scale;
-    if ((long long)h * s > INT_MAX || (long long)w * s * 3 > INT_MAX)
-        return sr_set_error(SR_ERR_SHAPE, "%s: a %dx%d output (x%d) overflows int", who, w, h, s);
-    g.halo = rn_halo(ops);
+    const int s = d.scale, rc = check_sr_geometry(who, h, w, s, tile < 0, "tile");
+    if (rc) return rc;
+    const std::vector<ExtStep> steps = rn_steps(ops, s);
+    g.halo = backward_halo(steps.data(), (int)steps.size());
     if (tile == 0) {                  // the largest multiple of 32 whose three F (s (tile + 2 halo))^2 buffers fit the cap
         tile = RN_TILE_STEP;
         for (int t = RN_MAX_TILE; t > RN_TILE_STEP; t -= RN_TILE_STEP) {
@@ -295,12 +264,12 @@ int rn_geometry(const char *who, const sr_resnet_desc &d, const std::vector<RnOp
     std::vector<long long> rows(n, 0), pitch(n, 0);
     std::vector<int> a, b;
     for (int ty = 0; ty < g.tiles_y; ++ty) {
-        rn_extents(ops, s, ty * tile, (int)std::min<long long>((long long)ty * tile + tile, h), h, a, b);
+        backward_extents(steps.data(), (int)n, s, ty * tile, (int)std::min<long long>((long long)ty * tile + tile, h), h, a, b);
         for (size_t i = 0; i < n; ++i) rows[i] = std::max(rows[i], (long long)(b[i] - a[i]) * ops[i].r);
     }
     for (int tx = 0; tx < g.tiles_x; ++tx) {
-        rn_extents(ops, s, tx * tile, (int)std::min<long long>((long long)tx * tile + tile, w), w, a, b);
-        for (size_t i = 0; i < n; ++i) pitch[i] = std::max(pitch[i], ((long long)(b[i] - a[i]) * ops[i].r + 3) / 4 * 4);
+        backward_extents(steps.data(), (int)n, s, tx * tile, (int)std::min<long long>((long long)tx * tile + tile, w), w, a, b);
+        for (size_t i = 0; i < n; ++i) pitch[i] = std::max(pitch[i], pad4((long long)(b[i] - a[i]) * ops[i].r));
     }
     g.plane = 0;
     for (size_t i = 0; i + 1 < n; ++i) g.plane = std::max(g.plane, rows[i] * pitch[i]);     // the last convolution stores no plane
@@ -309,34 +278,21 @@ int rn_geometry(const char *who, const sr_resnet_desc &d, const std::vector<RnOp
     return SR_OK;
 }
 
-// A planar tensor held in one of the model's buffers: element (c, gy, gx) at p[c * plane + (gy - ya) * pitch + gx - xa].
-struct RnTen {
-    float *p = nullptr;
+// A planar tensor held in buffer buf of the model.
+struct RnTen : PlanarTen {
     int buf = -1;
-    int ya = 0, xa = 0, rows = 0, cols = 0, pitch = 0;
-    long long plane = 0;
 };
 
 }  // namespace
 
-struct sr_resnet_model {
-    sr_ctx *ctx = nullptr;
+struct sr_resnet_model : SrModelBase {         // d_w, d_b: per op
     sr_resnet_desc d{};
     std::vector<RnOp> ops;
-    std::vector<float *> d_w, d_b;            // per op
     float *buf[3] = {nullptr, nullptr, nullptr};
     size_t buf_floats = 0;
 };
 
 static LiveSet g_rn_live;
-
-template <int NC2, int EPI>
-static void rn_launch(hipStream_t st, const RnTen &in, int H_in, int W_in, int F, int ncout_tiles, const float *dw, const float *db, float *out,
-                      long long out_plane, int out_pitch, int ya, int xa, int rows, int cols, const RnEpi &ep)
-{
-    hipLaunchKernelGGL((k_rn_conv<NC2, EPI>), dim3((cols + 31) / 32, (rows + 7) / 8, ncout_tiles), dim3(256), 0, st, in.p, in.plane, in.pitch,
-                       in.ya, in.xa, in.rows, in.cols, H_in, W_in, F, dw, db, out, out_plane, out_pitch, ya, xa, rows, cols, ep);
-}
 
 static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride,
                       int tile, bool u8, const char *who)
@@ -354,6 +310,7 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
     if (rc) return rc;
     const std::vector<RnOp> &ops = m->ops;
     const size_t n = ops.size();
+    const std::vector<ExtStep> steps = rn_steps(ops, S);
     const RnAffine af = {{m->d.mean[0], m->d.mean[1], m->d.mean[2]}, m->d.range};
     RnEpi ep0{};
     ep0.slope = 1.0f;
@@ -368,8 +325,8 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
     ep0.dst = d_dst;
     ep0.dst_stride = (long long)dst_stride;
     std::vector<std::vector<int>> ya(g.tiles_y), yb(g.tiles_y), xa(g.tiles_x), xb(g.tiles_x);
-    for (int ty = 0; ty < g.tiles_y; ++ty) rn_extents(ops, S, ty * g.tile, (int)std::min<long long>((long long)ty * g.tile + g.tile, h), h, ya[ty], yb[ty]);
-    for (int tx = 0; tx < g.tiles_x; ++tx) rn_extents(ops, S, tx * g.tile, (int)std::min<long long>((long long)tx * g.tile + g.tile, w), w, xa[tx], xb[tx]);
+    for (int ty = 0; ty < g.tiles_y; ++ty) backward_extents(steps.data(), (int)n, S, ty * g.tile, (int)std::min<long long>((long long)ty * g.tile + g.tile, h), h, ya[ty], yb[ty]);
+    for (int tx = 0; tx < g.tiles_x; ++tx) backward_extents(steps.data(), (int)n, S, tx * g.tile, (int)std::min<long long>((long long)tx * g.tile + g.tile, w), w, xa[tx], xb[tx]);
     auto other = [](int x, int y) {                        // a buffer that is neither x nor y
         for (int i = 0; i < 3; ++i)
             if (i != x && i != y) return i;
@@ -387,11 +344,8 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
                 // where a freshly laid out result goes: r x the convolution's own extent
                 auto fresh = [&](int b) {
                     RnTen o;
+                    static_cast<PlanarTen &>(o) = planar_tensor(m->buf[b], oya * op.r, oxa * op.r, rows * op.r, cols * op.r);
                     o.buf = b;
-                    o.p = m->buf[b];
-                    o.ya = oya * op.r; o.xa = oxa * op.r; o.rows = rows * op.r; o.cols = cols * op.r;
-                    o.pitch = (o.cols + 3) / 4 * 4;
-                    o.plane = (long long)o.rows * o.pitch;
                     return o;
                 };
                 RnEpi ep = ep0;
@@ -411,7 +365,7 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
                     ProfScope ps(ctx, op.lvl == 0 ? "resnet_body" : "resnet_hr");
                     blk = t;                               // a block's first convolution: its input is the block's skip
                     RnTen o = fresh(other(t.buf, h_buf));
-                    rn_launch<2, RN_SLOPE>(ctx->stream, t, H_in, W_in, F, F / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa, rows,
+                    launch_conv(k_rn_conv<2, RN_SLOPE>, ctx->stream, t, H_in, W_in, F, F / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa, rows,
                                            cols, ep);
                     t = o;
                 } else if (op.kind == OP_SKIP) {
@@ -431,7 +385,7 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
                     ep.skip_pitch = sk.pitch;
                     ep.skip_ya = sk.ya;
                     ep.skip_xa = sk.xa;
-                    rn_launch<2, RN_SKIP>(ctx->stream, t, H_in, W_in, F, F / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa, rows,
+                    launch_conv(k_rn_conv<2, RN_SKIP>, ctx->stream, t, H_in, W_in, F, F / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa, rows,
                                           cols, ep);
                     t = o;
                     if (op.skip == 2) h_buf = -1;
@@ -439,18 +393,18 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
                     ProfScope ps(ctx, "resnet_up");
                     RnTen o = fresh(other(t.buf, -1));
                     if (op.r == 2)
-                        rn_launch<2, RN_SHUF2>(ctx->stream, t, H_in, W_in, F, F * 4 / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa,
+                        launch_conv(k_rn_conv<2, RN_SHUF2>, ctx->stream, t, H_in, W_in, F, F * 4 / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa,
                                                rows, cols, ep);
                     else
-                        rn_launch<2, RN_SHUF3>(ctx->stream, t, H_in, W_in, F, F * 9 / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa,
+                        launch_conv(k_rn_conv<2, RN_SHUF3>, ctx->stream, t, H_in, W_in, F, F * 9 / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa,
                                                rows, cols, ep);
                     t = o;
                 } else {
                     ProfScope ps(ctx, "resnet_last");
                     if (u8)
-                        rn_launch<1, RN_LAST_U8>(ctx->stream, t, H_in, W_in, F, 1, m->d_w[i], m->d_b[i], nullptr, 0LL, 0, oya, oxa, rows, cols, ep);
+                        launch_conv(k_rn_conv<1, RN_LAST_U8>, ctx->stream, t, H_in, W_in, F, 1, m->d_w[i], m->d_b[i], nullptr, 0LL, 0, oya, oxa, rows, cols, ep);
                     else
-                        rn_launch<1, RN_LAST_F32>(ctx->stream, t, H_in, W_in, F, 1, m->d_w[i], m->d_b[i], nullptr, 0LL, 0, oya, oxa, rows, cols, ep);
+                        launch_conv(k_rn_conv<1, RN_LAST_F32>, ctx->stream, t, H_in, W_in, F, 1, m->d_w[i], m->d_b[i], nullptr, 0LL, 0, oya, oxa, rows, cols, ep);
                 }
             }
             rc = check_launch(who);
@@ -469,30 +423,23 @@ int sr_resnet_create(sr_ctx *ctx, const sr_resnet_desc *desc, const float *const
     int rc = rn_check_desc("sr_resnet_create", desc);                       // host decision, before any device call
     if (rc) return rc;
     std::vector<RnOp> ops = rn_build_ops(*desc);
-    if (!h_w || !h_b) return sr_set_error(SR_ERR_INVALID_ARG, "sr_resnet_create: null weight table");
-    if (n_conv != (int)ops.size())
-        return sr_set_error(SR_ERR_INVALID_ARG, "sr_resnet_create: this description has %d convolutions, %d given", (int)ops.size(), n_conv);
-    for (int k = 0; k < n_conv; ++k)
-        if (!h_w[k] || !h_b[k]) return sr_set_error(SR_ERR_INVALID_ARG, "sr_resnet_create: null array of convolution %d", k);
+    if ((rc = check_weight_tables("sr_resnet_create", "convolution", (int)ops.size(), n_conv, h_w, h_b))) return rc;
     CTX_ENTER(ctx);
     sr_resnet_model *M = new sr_resnet_model();
     M->ctx = ctx;
     M->d = *desc;
     M->ops = ops;
     g_rn_live.insert(M);
-    auto fail = [&](int code, const char *what) {
-        sr_set_error(code, "sr_resnet_create: %s", what);
-        sr_resnet_destroy(M);
-        return code;
-    };
     const int F = desc->n_feat;
     for (int k = 0; k < n_conv; ++k) {
         const bool last = ops[k].kind == OP_LAST;
         MfmaWeights a;
         if (ops[k].kind == OP_HEAD) a = {arrange_head_weights(h_w[k], F), std::vector<float>(h_b[k], h_b[k] + F)};
         else a = arrange_mfma_weights(h_w[k], h_b[k], last ? 3 : F * ops[k].r * ops[k].r, F, 9, 8, last ? 32 : 64);
-        if ((rc = upload_floats(a.w, M->d_w)) != SR_OK) return fail(rc, "weight upload");
-        if ((rc = upload_floats(a.b, M->d_b)) != SR_OK) return fail(rc, "bias upload");
+        if ((rc = upload_conv("sr_resnet_create", *M, a))) {
+            sr_resnet_destroy(M);
+            return rc;
+        }
     }
     *out = M;
     return SR_OK;
@@ -500,17 +447,7 @@ int sr_resnet_create(sr_ctx *ctx, const sr_resnet_desc *desc, const float *const
 
 int sr_resnet_destroy(sr_resnet_model *m)
 {
-    if (!m) return SR_OK;
-    if (!g_rn_live.erase(m)) return SR_OK;
-    if (ctx_is_live(m->ctx)) {
-        Guard g(m->ctx);
-        (void)hipStreamSynchronize(m->ctx->stream);
-        for (auto p : m->d_w) if (p) (void)hipFree(p);
-        for (auto p : m->d_b) if (p) (void)hipFree(p);
-        for (auto p : m->buf) if (p) (void)hipFree(p);
-    }
-    delete m;
-    return SR_OK;
+    return destroy_model(m, g_rn_live, [](const sr_resnet_model &m) { return std::vector<float *>(m.buf, m.buf + 3); });
 }
 
 int sr_resnet_plan(const sr_resnet_desc *desc, int h, int w, int tile, int *halo, int *n_tiles, size_t *workspace_bytes)

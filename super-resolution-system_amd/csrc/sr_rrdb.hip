@@ -10,7 +10,9 @@
 //
 // Everything is fp32 (fp32 in, fp32 accumulate).  Every F-input convolution is the implicit-GEMM mainloop of sr_conv_mfma.h
 // (v_mfma_f32_32x32x2_f32, shared with sr_lpips.hip, sr_srnet.hip and sr_resnet.hip) behind one of the epilogues below; the
-// 3 -> F head is head_accumulate with the u8 / 255 table.
+// 3 -> F head is head_accumulate with the u8 / 255 table.  What the three SR backends share around the mainloop -- the head
+// frame, leaky / skip_offset / store_hwc, the backward extent rule, the planar tensor, the convolution launch, the models'
+// lifetime -- is sr_net_common.h; this file holds the network's own kernels and epilogues, its two-phase geometry and its layer walk.
 //
 // Dense buffer: one planar fp32 buffer of F + 4 G planes.  Planar activations make a dense block's concatenation
 // cat(x, x_1 .. x_k) "the first F + k G planes of one buffer": convolution k reads planes [0, F + (k - 1) G) and writes planes
@@ -38,13 +40,11 @@
 // add) after the chain.  Nothing depends on the position in a block, a trunk piece or a tail piece.
 //
 // Weights are caller-supplied (sr_rrdb_create); nothing is fetched.
-#include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "sr_conv_mfma.h"
+#include "sr_net_common.h"
 
 namespace {
 
@@ -63,13 +63,7 @@ __global__ __launch_bounds__(256) void k_rr_head(const unsigned char *__restrict
     const int tid = threadIdx.y * 64 + threadIdx.x;
     lut[tid] = (float)tid / 255.0f;
     __syncthreads();
-    const int lx = blockIdx.x * 64 + threadIdx.x, ly = blockIdx.y * 4 + threadIdx.y, ct = blockIdx.z;
-    if (lx >= cols || ly >= rows) return;
-    float acc[64];
-    head_accumulate<0>(img, stride, H, W, wt, bias, ct, lut, ya + ly, xa + lx, acc);
-    float *o = out + (size_t)ct * 64 * plane + (size_t)ly * pitch + lx;
-#pragma unroll
-    for (int co = 0; co < 64; ++co) o[(size_t)co * plane] = acc[co];
+    head_frame<0>(img, stride, H, W, wt, bias, lut, out, ya, xa, rows, cols, pitch, plane, [](int, float y) { return y; });
 }
 
 // The epilogues of k_rr_conv.
@@ -124,10 +118,10 @@ __global__ __launch_bounds__(256) void k_rr_conv(const float *__restrict__ in, l
                 for (int r = 0; r < 16; ++r) {
                     const int co = ct * NC + mfma_cout(c2, r, half);
                     const float y = acc[c2][pr][r];
-                    out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = y >= 0.0f ? y : ep.slope * y;
+                    out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = leaky(y, ep.slope);
                 }
         } else if constexpr (EPI == RR_SKIP || EPI == RR_SKIP2) {
-            const size_t so = (size_t)(out_ya + row - ep.skip_ya) * ep.skip_pitch + (out_xa + col - ep.skip_xa);
+            const size_t so = skip_offset(out_ya + row, out_xa + col, ep.skip_ya, ep.skip_xa, ep.skip_pitch);
 #pragma unroll
             for (int c2 = 0; c2 < NC2; ++c2)
 #pragma unroll
@@ -138,7 +132,7 @@ __global__ __launch_bounds__(256) void k_rr_conv(const float *__restrict__ in, l
                     out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = v;
                 }
         } else if constexpr (EPI == RR_REP_SKIP || EPI == RR_REP_ACT) {
-            const size_t so = (size_t)(out_ya + row - ep.skip_ya) * ep.skip_pitch + (out_xa + col - ep.skip_xa);
+            const size_t so = skip_offset(out_ya + row, out_xa + col, ep.skip_ya, ep.skip_xa, ep.skip_pitch);
             const size_t oo = (size_t)(2 * row) * out_pitch + 2 * col;     // out_pitch and out_plane are even: 8-byte aligned
 #pragma unroll
             for (int c2 = 0; c2 < NC2; ++c2)
@@ -147,7 +141,7 @@ __global__ __launch_bounds__(256) void k_rr_conv(const float *__restrict__ in, l
                     const int co = ct * NC + mfma_cout(c2, r, half);
                     float v = acc[c2][pr][r];
                     if constexpr (EPI == RR_REP_SKIP) v = v + ep.skip[(size_t)co * ep.skip_plane + so];
-                    else v = v >= 0.0f ? v : ep.slope * v;
+                    else v = leaky(v, ep.slope);
                     float *o = out + (size_t)co * out_plane + oo;
                     const float2 vv = make_float2(v, v);
                     *(float2 *)o = vv;
@@ -159,10 +153,7 @@ __global__ __launch_bounds__(256) void k_rr_conv(const float *__restrict__ in, l
             char *d = (char *)ep.dst + (size_t)gy * ep.dst_stride;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float o = acc[0][pr][c];
-                const size_t e = (size_t)gx * 3 + c;
-                if constexpr (EPI == RR_LAST_U8) ((unsigned char *)d)[e] = (unsigned char)rintf(fminf(fmaxf(o, 0.0f), 1.0f) * 255.0f);
-                else ((float *)d)[e] = o;
+                store_hwc<EPI == RR_LAST_U8>(d, (size_t)gx * 3 + c, acc[0][pr][c]);
             }
         }
     }
@@ -189,34 +180,19 @@ int rr_n_conv(int B) { return 1 + 15 * B + 5; }
 int rr_rep(int n, int i) { return (i == n - 5 || i == n - 4) ? 2 : 1; }
 int rr_mult(int n, int i) { return i >= n - 3 ? 4 : (i == n - 4 ? 2 : 1); }
 
-// One axis of the backward extent rule: the piece [lo, hi) of an axis of len input pixels -> per convolution the half-open
-// range [a[i], b[i]) of its output at its own resolution.
-void rr_extents(int n, int lo, int hi, int len, std::vector<int> &a, std::vector<int> &b)
+// The extent rule's view of the n convolutions (backward_extents, backward_halo: sr_net_common.h; the halo is 15 B + 4).
+std::vector<ExtStep> rr_steps(int n)
 {
-    a.resize(n);
-    b.resize(n);
-    long long na = (long long)lo * 4, nb = (long long)hi * 4;
-    for (int i = n - 1; i >= 0; --i) {
-        const int r = rr_rep(n, i);
-        na = na / r;                                       // outward: floor, ceil
-        nb = (nb + r - 1) / r;
-        a[i] = (int)na;
-        b[i] = (int)nb;
-        const long long full = (long long)len * rr_mult(n, i);
-        na = std::max(na - 1, 0LL);
-        nb = std::min(nb + 1, full);
-    }
+    std::vector<ExtStep> steps(n);
+    for (int i = 0; i < n; ++i) steps[i] = {rr_rep(n, i), rr_mult(n, i)};
+    return steps;
 }
 
-// Input pixels a piece reads beyond its own edge: the rule above without clipping (15 B + 4).
-int rr_halo(int n)
+// One axis: the piece [lo, hi) of an axis of len input pixels -> per convolution the range [a[i], b[i]) of its output.
+void rr_extents(const std::vector<ExtStep> &steps, int lo, int hi, int len, std::vector<int> &a, std::vector<int> &b)
 {
-    int g = 0;
-    for (int i = n - 1; i >= 0; --i) g = (g + rr_rep(n, i) - 1) / rr_rep(n, i) + 1;
-    return g;
+    backward_extents(steps.data(), (int)steps.size(), 4, lo, hi, len, a, b);
 }
-
-long long rr_pad4(long long v) { return (v + 3) / 4 * 4; }
 
 struct RrGeom {
     int tile = 0, tail = 0, tiles_x = 0, tiles_y = 0, halo = 0;
@@ -227,19 +203,20 @@ struct RrGeom {
 
 // Largest trunk planes over the pieces of one tile size: the extents of an axis depend on that axis alone, so the tallest and
 // the widest piece make the largest plane.
-void rr_trunk_planes(int n, int h, int w, int tile, long long &plane0, long long &plane2)
+void rr_trunk_planes(const std::vector<ExtStep> &steps, int h, int w, int tile, long long &plane0, long long &plane2)
 {
+    const int n = (int)steps.size();
     std::vector<int> a, b;
     long long rows0 = 0, rows2 = 0, pitch0 = 0, pitch2 = 0;
     for (long long lo = 0; lo < h; lo += tile) {
-        rr_extents(n, (int)lo, (int)std::min<long long>(lo + tile, h), h, a, b);
+        rr_extents(steps, (int)lo, (int)std::min<long long>(lo + tile, h), h, a, b);
         rows0 = std::max(rows0, (long long)b[0] - a[0]);
         rows2 = std::max(rows2, 2LL * (b[n - 5] - a[n - 5]));
     }
     for (long long lo = 0; lo < w; lo += tile) {
-        rr_extents(n, (int)lo, (int)std::min<long long>(lo + tile, w), w, a, b);
-        pitch0 = std::max(pitch0, rr_pad4((long long)b[0] - a[0]));
-        pitch2 = std::max(pitch2, rr_pad4(2LL * (b[n - 5] - a[n - 5])));
+        rr_extents(steps, (int)lo, (int)std::min<long long>(lo + tile, w), w, a, b);
+        pitch0 = std::max(pitch0, pad4((long long)b[0] - a[0]));
+        pitch2 = std::max(pitch2, pad4(2LL * (b[n - 5] - a[n - 5])));
     }
     plane0 = rows0 * pitch0;
     plane2 = rows2 * pitch2;
@@ -253,17 +230,16 @@ size_t rr_trunk_floats(const sr_rrdb_desc &d, long long plane0, long long plane2
 // Host only: piece grids and buffer geometry of an h x w input.
 int rr_geometry(const char *who, const sr_rrdb_desc &d, int h, int w, int tile, int tail, RrGeom &g)
 {
-    if (h < 1 || w < 1) return sr_set_error(SR_ERR_SHAPE, "%s: %dx%d image", who, w, h);
-    if (tile < 0 || tail < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: tile and tail must be >= 1, or 0 for the library's choice", who);
-    if ((long long)h * 4 > INT_MAX || (long long)w * 4 * 3 > INT_MAX)
-        return sr_set_error(SR_ERR_SHAPE, "%s: a %dx%d output (x4) overflows int", who, w, h);
+    const int rc = check_sr_geometry(who, h, w, 4, tile < 0 || tail < 0, "tile and tail");
+    if (rc) return rc;
     const int n = rr_n_conv(d.n_blocks);
-    g.halo = rr_halo(n);
+    const std::vector<ExtStep> steps = rr_steps(n);
+    g.halo = backward_halo(steps.data(), n);
     if (tile == 0) {                  // the largest multiple of 32 whose trunk buffers, as laid out for this image, fit the cap
         tile = RR_TILE_STEP;
         for (int t = RR_MAX_TILE; t > RR_TILE_STEP; t -= RR_TILE_STEP) {
             long long p0, p2;
-            rr_trunk_planes(n, h, w, t, p0, p2);
+            rr_trunk_planes(steps, h, w, t, p0, p2);
             if (rr_trunk_floats(d, p0, p2) * sizeof(float) <= RR_TRUNK_CAP) {
                 tile = t;
                 break;
@@ -275,7 +251,7 @@ int rr_geometry(const char *who, const sr_rrdb_desc &d, int h, int w, int tile, 
     g.tail = tail;
     g.tiles_x = (int)(((long long)w + tile - 1) / tile);
     g.tiles_y = (int)(((long long)h + tile - 1) / tile);
-    rr_trunk_planes(n, h, w, tile, g.plane0, g.plane2);
+    rr_trunk_planes(steps, h, w, tile, g.plane0, g.plane2);
     // tail sub-pieces: every trunk piece is walked from its own origin
     std::vector<int> a, b;
     long long rows4 = 0, pitch4 = 0, cnt_y = 0, cnt_x = 0;
@@ -284,11 +260,11 @@ int rr_geometry(const char *who, const sr_rrdb_desc &d, int h, int w, int tile, 
         for (long long lo = 0; lo < len; lo += tile) {
             const long long hi = std::min<long long>(lo + tile, len);
             for (long long s = lo; s < hi; s += tail) {
-                rr_extents(n, (int)s, (int)std::min<long long>(s + tail, hi), len, a, b);
+                rr_extents(steps, (int)s, (int)std::min<long long>(s + tail, hi), len, a, b);
                 long long m = 0;
                 for (int i = n - 4; i < n - 1; ++i) m = std::max(m, (long long)(b[i] - a[i]) * rr_rep(n, i));   // conv_last stores no plane
                 if (axis == 0) { rows4 = std::max(rows4, m); ++cnt_y; }
-                else { pitch4 = std::max(pitch4, rr_pad4(m)); ++cnt_x; }
+                else { pitch4 = std::max(pitch4, pad4(m)); ++cnt_x; }
             }
         }
     }
@@ -304,28 +280,10 @@ int rr_geometry(const char *who, const sr_rrdb_desc &d, int h, int w, int tile, 
     return SR_OK;
 }
 
-// A planar tensor: element (c, gy, gx) at p[c * plane + (gy - ya) * pitch + gx - xa]; rows x cols is what the buffer holds.
-struct RrTen {
-    float *p = nullptr;
-    int ya = 0, xa = 0, rows = 0, cols = 0, pitch = 0;
-    long long plane = 0;
-};
-
-RrTen rr_tensor(float *p, int ya, int xa, int rows, int cols)
-{
-    RrTen t;
-    t.p = p; t.ya = ya; t.xa = xa; t.rows = rows; t.cols = cols;
-    t.pitch = (int)rr_pad4(cols);
-    t.plane = (long long)rows * t.pitch;
-    return t;
-}
-
 }  // namespace
 
-struct sr_rrdb_model {
-    sr_ctx *ctx = nullptr;
+struct sr_rrdb_model : SrModelBase {
     sr_rrdb_desc d{};
-    std::vector<float *> d_w, d_b;            // per convolution
     float *dense[3] = {nullptr, nullptr, nullptr};
     float *hbuf[1] = {nullptr};               // h, until conv_body has added it
     float *f2[1] = {nullptr};                 // f replicated to 2 x: what the trunk phase leaves to the tail phase
@@ -334,16 +292,6 @@ struct sr_rrdb_model {
 };
 
 static LiveSet g_rr_live;
-
-// in: the tensor read (its first cin planes); out: pointer to the element (cout 0, oya, oxa) of the output -- or, for the
-// replicating epilogues, to (cout 0, 2 oya, 2 oxa) of the output at twice the resolution.
-template <int NC2, int EPI>
-static void rr_launch(hipStream_t st, const RrTen &in, int H_in, int W_in, int cin, int ncout_tiles, const float *dw, const float *db, float *out,
-                      long long out_plane, int out_pitch, int ya, int xa, int rows, int cols, const RrEpi &ep)
-{
-    hipLaunchKernelGGL((k_rr_conv<NC2, EPI>), dim3((cols + 31) / 32, (rows + 7) / 8, ncout_tiles), dim3(256), 0, st, in.p, in.plane, in.pitch,
-                       in.ya, in.xa, in.rows, in.cols, H_in, W_in, cin, dw, db, out, out_plane, out_pitch, ya, xa, rows, cols, ep);
-}
 
 static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride,
                       int tile, int tail, bool u8, const char *who)
@@ -362,6 +310,7 @@ static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride
     if ((rc = ensure_activation_buffers(ctx, m->f2, 1, m->f2_floats, (size_t)g.plane2 * F, who))) return rc;
     if ((rc = ensure_activation_buffers(ctx, m->tailbuf, 2, m->tail_floats, (size_t)g.plane4 * F, who))) return rc;
     hipStream_t st = ctx->stream;
+    const std::vector<ExtStep> steps = rr_steps(n);
     RrEpi ep0{};
     ep0.slope = m->d.slope;
     ep0.beta = m->d.res_scale;
@@ -372,11 +321,11 @@ static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride
         for (int tx = 0; tx < g.tiles_x; ++tx) {
             const int py0 = (int)((long long)ty * g.tile), py1 = (int)std::min<long long>((long long)py0 + g.tile, h);
             const int px0 = (int)((long long)tx * g.tile), px1 = (int)std::min<long long>((long long)px0 + g.tile, w);
-            rr_extents(n, py0, py1, h, ya, yb);
-            rr_extents(n, px0, px1, w, xa, xb);
+            rr_extents(steps, py0, py1, h, ya, yb);
+            rr_extents(steps, px0, px1, w, xa, xb);
             // ---- trunk phase: every tensor of the piece in the head's layout ----
-            const RrTen L = rr_tensor(nullptr, ya[0], xa[0], yb[0] - ya[0], xb[0] - xa[0]);
-            auto ten = [&](float *base) { RrTen t = L; t.p = base; return t; };
+            const PlanarTen L = planar_tensor(nullptr, ya[0], xa[0], yb[0] - ya[0], xb[0] - xa[0]);
+            auto ten = [&](float *base) { PlanarTen t = L; t.p = base; return t; };
             auto at = [&](float *base, int i) { return base + (size_t)(ya[i] - L.ya) * L.pitch + (xa[i] - L.xa); };
             RrEpi ep = ep0;
             ep.skip_plane = L.plane;
@@ -399,35 +348,35 @@ static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride
                     // The guard is the buffer's stored extent (the head's).  Planes of x_j hold stale values outside convolution
                     // j's extent; by the extent rule (each extent is the next one grown by one, clipped) these reach only masked
                     // outputs, and an output depends on its own pixel's patch alone.
-                    const RrTen in = ten(D);
+                    const PlanarTen in = ten(D);
                     for (int k = 1; k <= 4; ++k, ++i) {
                         ProfScope ps(ctx, "rrdb_dense");
                         const int cin = F + (k - 1) * G, rows = yb[i] - ya[i], cols = xb[i] - xa[i];
                         float *o = at(D + (size_t)cin * L.plane, i);
                         if (G == 32)
-                            rr_launch<1, RR_ACT>(st, in, h, w, cin, 1, m->d_w[i], m->d_b[i], o, L.plane, L.pitch, ya[i], xa[i], rows, cols, ep);
+                            launch_conv(k_rr_conv<1, RR_ACT>, st, in, h, w, cin, 1, m->d_w[i], m->d_b[i], o, L.plane, L.pitch, ya[i], xa[i], rows, cols, ep);
                         else
-                            rr_launch<2, RR_ACT>(st, in, h, w, cin, 1, m->d_w[i], m->d_b[i], o, L.plane, L.pitch, ya[i], xa[i], rows, cols, ep);
+                            launch_conv(k_rr_conv<2, RR_ACT>, st, in, h, w, cin, 1, m->d_w[i], m->d_b[i], o, L.plane, L.pitch, ya[i], xa[i], rows, cols, ep);
                     }
                     ProfScope ps(ctx, "rrdb_blockout");
                     const int rows = yb[i] - ya[i], cols = xb[i] - xa[i];
                     ep.skip = D;
                     if (db < 2) {
-                        rr_launch<2, RR_SKIP>(st, in, h, w, DP, F / 64, m->d_w[i], m->d_b[i], at(m->dense[db + 1], i), L.plane, L.pitch, ya[i],
+                        launch_conv(k_rr_conv<2, RR_SKIP>, st, in, h, w, DP, F / 64, m->d_w[i], m->d_b[i], at(m->dense[db + 1], i), L.plane, L.pitch, ya[i],
                                               xa[i], rows, cols, ep);
                     } else {                               // in place over the RRDB's input r
                         ep.skip2 = m->dense[0];
-                        rr_launch<2, RR_SKIP2>(st, in, h, w, DP, F / 64, m->d_w[i], m->d_b[i], at(m->dense[0], i), L.plane, L.pitch, ya[i],
+                        launch_conv(k_rr_conv<2, RR_SKIP2>, st, in, h, w, DP, F / 64, m->d_w[i], m->d_b[i], at(m->dense[0], i), L.plane, L.pitch, ya[i],
                                                xa[i], rows, cols, ep);
                     }
                     ++i;
                 }
             // conv_body + h, replicated to 2 x
-            const RrTen f2 = rr_tensor(m->f2[0], 2 * ya[i], 2 * xa[i], 2 * (yb[i] - ya[i]), 2 * (xb[i] - xa[i]));
+            const PlanarTen f2 = planar_tensor(m->f2[0], 2 * ya[i], 2 * xa[i], 2 * (yb[i] - ya[i]), 2 * (xb[i] - xa[i]));
             {
                 ProfScope ps(ctx, "rrdb_bodyup");
                 ep.skip = B > 0 ? m->hbuf[0] : m->dense[0];
-                rr_launch<2, RR_REP_SKIP>(st, ten(m->dense[0]), h, w, F, F / 64, m->d_w[i], m->d_b[i], f2.p, f2.plane, f2.pitch, ya[i], xa[i],
+                launch_conv(k_rr_conv<2, RR_REP_SKIP>, st, ten(m->dense[0]), h, w, F, F / 64, m->d_w[i], m->d_b[i], f2.p, f2.plane, f2.pitch, ya[i], xa[i],
                                           yb[i] - ya[i], xb[i] - xa[i], ep);
             }
             rc = check_launch(who);
@@ -436,32 +385,32 @@ static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride
             const int u1 = n - 4, u2 = n - 3, hr = n - 2, la = n - 1;
             for (int sy = py0; sy < py1; sy = (int)std::min<long long>((long long)sy + g.tail, py1))
                 for (int sx = px0; sx < px1; sx = (int)std::min<long long>((long long)sx + g.tail, px1)) {
-                    rr_extents(n, sy, (int)std::min<long long>((long long)sy + g.tail, py1), h, sya, syb);
-                    rr_extents(n, sx, (int)std::min<long long>((long long)sx + g.tail, px1), w, sxa, sxb);
+                    rr_extents(steps, sy, (int)std::min<long long>((long long)sy + g.tail, py1), h, sya, syb);
+                    rr_extents(steps, sx, (int)std::min<long long>((long long)sx + g.tail, px1), w, sxa, sxb);
                     auto rows = [&](int k) { return syb[k] - sya[k]; };
                     auto cols = [&](int k) { return sxb[k] - sxa[k]; };
-                    const RrTen a = rr_tensor(m->tailbuf[0], 2 * sya[u1], 2 * sxa[u1], 2 * rows(u1), 2 * cols(u1));
-                    const RrTen b = rr_tensor(m->tailbuf[1], sya[u2], sxa[u2], rows(u2), cols(u2));
-                    const RrTen c = rr_tensor(m->tailbuf[0], sya[hr], sxa[hr], rows(hr), cols(hr));
+                    const PlanarTen a = planar_tensor(m->tailbuf[0], 2 * sya[u1], 2 * sxa[u1], 2 * rows(u1), 2 * cols(u1));
+                    const PlanarTen b = planar_tensor(m->tailbuf[1], sya[u2], sxa[u2], rows(u2), cols(u2));
+                    const PlanarTen c = planar_tensor(m->tailbuf[0], sya[hr], sxa[hr], rows(hr), cols(hr));
                     {
                         ProfScope ps(ctx, "rrdb_bodyup");
-                        rr_launch<2, RR_REP_ACT>(st, f2, 2 * h, 2 * w, F, F / 64, m->d_w[u1], m->d_b[u1], a.p, a.plane, a.pitch, sya[u1], sxa[u1],
+                        launch_conv(k_rr_conv<2, RR_REP_ACT>, st, f2, 2 * h, 2 * w, F, F / 64, m->d_w[u1], m->d_b[u1], a.p, a.plane, a.pitch, sya[u1], sxa[u1],
                                                  rows(u1), cols(u1), ep);
-                        rr_launch<2, RR_ACT>(st, a, 4 * h, 4 * w, F, F / 64, m->d_w[u2], m->d_b[u2], b.p, b.plane, b.pitch, sya[u2], sxa[u2],
+                        launch_conv(k_rr_conv<2, RR_ACT>, st, a, 4 * h, 4 * w, F, F / 64, m->d_w[u2], m->d_b[u2], b.p, b.plane, b.pitch, sya[u2], sxa[u2],
                                              rows(u2), cols(u2), ep);
                     }
                     {
                         ProfScope ps(ctx, "rrdb_hr");
-                        rr_launch<2, RR_ACT>(st, b, 4 * h, 4 * w, F, F / 64, m->d_w[hr], m->d_b[hr], c.p, c.plane, c.pitch, sya[hr], sxa[hr],
+                        launch_conv(k_rr_conv<2, RR_ACT>, st, b, 4 * h, 4 * w, F, F / 64, m->d_w[hr], m->d_b[hr], c.p, c.plane, c.pitch, sya[hr], sxa[hr],
                                              rows(hr), cols(hr), ep);
                     }
                     {
                         ProfScope ps(ctx, "rrdb_last");
                         if (u8)
-                            rr_launch<1, RR_LAST_U8>(st, c, 4 * h, 4 * w, F, 1, m->d_w[la], m->d_b[la], nullptr, 0LL, 0, sya[la], sxa[la], rows(la),
+                            launch_conv(k_rr_conv<1, RR_LAST_U8>, st, c, 4 * h, 4 * w, F, 1, m->d_w[la], m->d_b[la], nullptr, 0LL, 0, sya[la], sxa[la], rows(la),
                                                      cols(la), ep);
                         else
-                            rr_launch<1, RR_LAST_F32>(st, c, 4 * h, 4 * w, F, 1, m->d_w[la], m->d_b[la], nullptr, 0LL, 0, sya[la], sxa[la], rows(la),
+                            launch_conv(k_rr_conv<1, RR_LAST_F32>, st, c, 4 * h, 4 * w, F, 1, m->d_w[la], m->d_b[la], nullptr, 0LL, 0, sya[la], sxa[la], rows(la),
                                                       cols(la), ep);
                     }
                     rc = check_launch(who);
@@ -480,20 +429,12 @@ int sr_rrdb_create(sr_ctx *ctx, const sr_rrdb_desc *desc, const float *const *h_
     int rc = rr_check_desc("sr_rrdb_create", desc);                         // host decision, before any device call
     if (rc) return rc;
     const int F = desc->n_feat, G = desc->n_grow, n = rr_n_conv(desc->n_blocks);
-    if (!h_w || !h_b) return sr_set_error(SR_ERR_INVALID_ARG, "sr_rrdb_create: null weight table");
-    if (n_conv != n) return sr_set_error(SR_ERR_INVALID_ARG, "sr_rrdb_create: this description has %d convolutions, %d given", n, n_conv);
-    for (int k = 0; k < n; ++k)
-        if (!h_w[k] || !h_b[k]) return sr_set_error(SR_ERR_INVALID_ARG, "sr_rrdb_create: null array of convolution %d", k);
+    if ((rc = check_weight_tables("sr_rrdb_create", "convolution", n, n_conv, h_w, h_b))) return rc;
     CTX_ENTER(ctx);
     sr_rrdb_model *M = new sr_rrdb_model();
     M->ctx = ctx;
     M->d = *desc;
     g_rr_live.insert(M);
-    auto fail = [&](int code, const char *what) {
-        sr_set_error(code, "sr_rrdb_create: %s", what);
-        sr_rrdb_destroy(M);
-        return code;
-    };
     for (int k = 0; k < n; ++k) {
         MfmaWeights a;
         if (k == 0) {
@@ -507,8 +448,10 @@ int sr_rrdb_create(sr_ctx *ctx, const sr_rrdb_desc *desc, const float *const *h_
         } else {
             a = arrange_mfma_weights(h_w[k], h_b[k], 3, F, 9, 8, 32);
         }
-        if ((rc = upload_floats(a.w, M->d_w)) != SR_OK) return fail(rc, "weight upload");
-        if ((rc = upload_floats(a.b, M->d_b)) != SR_OK) return fail(rc, "bias upload");
+        if ((rc = upload_conv("sr_rrdb_create", *M, a))) {
+            sr_rrdb_destroy(M);
+            return rc;
+        }
     }
     *out = M;
     return SR_OK;
@@ -516,18 +459,9 @@ int sr_rrdb_create(sr_ctx *ctx, const sr_rrdb_desc *desc, const float *const *h_
 
 int sr_rrdb_destroy(sr_rrdb_model *m)
 {
-    if (!m) return SR_OK;
-    if (!g_rr_live.erase(m)) return SR_OK;
-    if (ctx_is_live(m->ctx)) {
-        Guard g(m->ctx);
-        (void)hipStreamSynchronize(m->ctx->stream);
-        for (auto p : m->d_w) if (p) (void)hipFree(p);
-        for (auto p : m->d_b) if (p) (void)hipFree(p);
-        for (float *p : {m->dense[0], m->dense[1], m->dense[2], m->hbuf[0], m->f2[0], m->tailbuf[0], m->tailbuf[1]})
-            if (p) (void)hipFree(p);
-    }
-    delete m;
-    return SR_OK;
+    return destroy_model(m, g_rr_live, [](const sr_rrdb_model &m) {
+        return std::vector<float *>{m.dense[0], m.dense[1], m.dense[2], m.hbuf[0], m.f2[0], m.tailbuf[0], m.tailbuf[1]};
+    });
 }
 
 int sr_rrdb_plan(const sr_rrdb_desc *desc, int h, int w, int tile, int tail, int *halo, int *n_tiles, int *n_tail_tiles,

@@ -7,8 +7,10 @@
 //                  (one fp32 add) and the store: HWC fp32 unclamped, or HWC u8 rintf(clamp(o, 0, 1) * 255)
 //
 // Everything is fp32 (fp32 in, fp32 accumulate): the F -> F and F -> 3 s^2 layers are implicit GEMMs on
-// v_mfma_f32_32x32x2_f32 (the mainloop of sr_conv_mfma.h, shared with sr_lpips.hip and sr_resnet.hip), the 3 -> F head is a
-// direct VALU kernel.  The 3 s^2-channel tensor is never written.
+// v_mfma_f32_32x32x2_f32 (the mainloop of sr_conv_mfma.h, shared with sr_lpips.hip, sr_resnet.hip and sr_rrdb.hip), the 3 -> F
+// head is a direct VALU kernel.  The 3 s^2-channel tensor is never written.  What the three SR backends share around the
+// mainloop -- the head frame, store_hwc, the backward extent rule, the models' lifetime -- is sr_net_common.h; this file holds the
+// network's own kernels and epilogues, its geometry policy and its layer walk.
 //
 // Memory: activations are planar fp32 [F][rows][pitch] in two ping-pong buffers owned by the model.  The image is walked in
 // square sub-tiles of the INPUT; a sub-tile recomputes a halo of D + 2 input pixels (layer k's valid extent is the sub-tile
@@ -19,16 +21,18 @@
 // where the output lies in a block or a sub-tile: streamed and unstreamed results are bit-equal.
 //
 // Weights are caller-supplied (sr_srnet_create); nothing is fetched.
-#include <algorithm>
-#include <climits>
 #include <cstring>
 #include <vector>
 
-#include "sr_conv_mfma.h"
+#include "sr_net_common.h"
 
 namespace {
 
 constexpr int SN_DEFAULT_TILE = 2048;      // tile = 0: one pipeline tile is one sub-tile (no halo recompute)
+
+// The per-channel activation.  Not leaky(y, slope[co]): the slope is loaded for negative values only, as it always was -- an
+// unconditional load costs the body kernel 40 VGPRs and a wave per SIMD.
+__device__ __forceinline__ float sn_act(float y, const float *__restrict__ slope, int co) { return y >= 0.0f ? y : slope[co] * y; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Head (3 -> F) from the u8 image: one thread = one output pixel x 64 output channels (blockIdx.z: 64-cout tile).
@@ -43,17 +47,8 @@ __global__ __launch_bounds__(256) void k_sn_head(const unsigned char *__restrict
     const int tid = threadIdx.y * 64 + threadIdx.x;
     lut[tid] = (float)tid / 255.0f;
     __syncthreads();
-    const int lx = blockIdx.x * 64 + threadIdx.x, ly = blockIdx.y * 4 + threadIdx.y, ct = blockIdx.z;
-    if (lx >= cols || ly >= rows) return;
-    slope += ct * 64;
-    float acc[64];
-    head_accumulate<0>(img, stride, H, W, wt, bias, ct, lut, ya + ly, xa + lx, acc);
-    float *o = out + (size_t)ct * 64 * plane + (size_t)ly * pitch + lx;
-#pragma unroll
-    for (int co = 0; co < 64; ++co) {
-        const float y = acc[co];
-        o[(size_t)co * plane] = y >= 0.0f ? y : slope[co] * y;
-    }
+    slope += (int)blockIdx.z * 64;
+    head_frame<0>(img, stride, H, W, wt, bias, lut, out, ya, xa, rows, cols, pitch, plane, [&](int co, float y) { return sn_act(y, slope, co); });
 }
 
 // What the fused tail needs beside the convolution's own arguments.
@@ -97,7 +92,7 @@ __global__ __launch_bounds__(256) void k_sn_conv(const float *__restrict__ in, l
                 for (int r = 0; r < 16; ++r) {
                     const int co = ct * NC + mfma_cout(c2, r, half);
                     const float y = acc[c2][pr][r];
-                    out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = y >= 0.0f ? y : slope[co] * y;
+                    out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = sn_act(y, slope, co);
                 }
         } else {                                           // pixel shuffle + nearest base + HWC store
             const int gy = out_ya + row, gx = out_xa + col;
@@ -113,9 +108,7 @@ __global__ __launch_bounds__(256) void k_sn_conv(const float *__restrict__ in, l
                     const int c = co / (S * S), rem = co % (S * S), dy = rem / S, dx = rem % S;
                     const float o = acc[c2][pr][r] + (c == 0 ? x0 : (c == 1 ? x1 : x2));
                     const size_t e = ((size_t)gx * S + dx) * 3 + c;
-                    char *d = drow + (size_t)dy * tail.dst_stride;
-                    if constexpr (U8) ((unsigned char *)d)[e] = (unsigned char)rintf(fminf(fmaxf(o, 0.0f), 1.0f) * 255.0f);
-                    else ((float *)d)[e] = o;
+                    store_hwc<U8>(drow + (size_t)dy * tail.dst_stride, e, o);
                 }
         }
     }
@@ -135,20 +128,22 @@ int sn_check_arch(const char *who, int n_feat, int n_body, int scale)
     return SR_OK;
 }
 
+// The extent rule's view of the D + 2 convolutions: no replication, one resolution (layer k's valid extent is the sub-tile grown
+// by D + 1 - k, clipped to the image).
+std::vector<ExtStep> sn_steps(int n_body) { return std::vector<ExtStep>(n_body + 2, ExtStep{1, 1}); }
+
 // Host only: sub-tile grid and buffer geometry of an h x w input.
 int sn_geometry(const char *who, int h, int w, int n_body, int scale, int tile, SnGeom &g)
 {
-    if (h < 1 || w < 1) return sr_set_error(SR_ERR_SHAPE, "%s: %dx%d image", who, w, h);
-    if (tile < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: tile must be >= 1, or 0 for the library's choice", who);
-    if ((long long)h * scale > INT_MAX || (long long)w * scale * 3 > INT_MAX)
-        return sr_set_error(SR_ERR_SHAPE, "%s: a %dx%d output (x%d) overflows int", who, w, h, scale);
+    const int rc = check_sr_geometry(who, h, w, scale, tile < 0, "tile");
+    if (rc) return rc;
     g.tile = tile == 0 ? SN_DEFAULT_TILE : tile;
-    g.halo = n_body + 2;
+    g.halo = backward_halo(sn_steps(n_body).data(), n_body + 2);
     g.tiles_x = (w + g.tile - 1) / g.tile;
     g.tiles_y = (h + g.tile - 1) / g.tile;
     g.rows = (int)std::min<long long>((long long)std::min(g.tile, h) + 2 * g.halo, h);
     const int cols = (int)std::min<long long>((long long)std::min(g.tile, w) + 2 * g.halo, w);
-    g.pitch = (cols + 3) / 4 * 4;
+    g.pitch = (int)pad4(cols);
     g.plane = (long long)g.rows * g.pitch;
     if (g.plane * 8 > INT_MAX)        // the convolution indexes one 8-channel chunk of a buffer with 32-bit offsets
         return sr_set_error(SR_ERR_SHAPE, "%s: a sub-tile of %d x %d activations is too large; use a smaller tile", who, g.pitch, g.rows);
@@ -157,10 +152,9 @@ int sn_geometry(const char *who, int h, int w, int n_body, int scale, int tile, 
 
 }  // namespace
 
-struct sr_srnet_model {
-    sr_ctx *ctx = nullptr;
+struct sr_srnet_model : SrModelBase {
     int F = 0, D = 0, S = 0;
-    std::vector<float *> d_w, d_b, d_slope;   // per layer 0 .. D + 1 (no slope for the tail)
+    std::vector<float *> d_slope;             // per layer 0 .. D (d_w, d_b: 0 .. D + 1; no slope for the tail)
     float *buf[2] = {nullptr, nullptr};       // ping-pong activation buffers
     size_t buf_floats = 0;
 };
@@ -191,20 +185,17 @@ static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_strid
     rc = ensure_activation_buffers(ctx, m->buf, 2, m->buf_floats, (size_t)g.plane * F, who);
     if (rc) return rc;
     const SnTail tail = {d_src, (long long)src_stride, d_dst, (long long)dst_stride};
+    const std::vector<ExtStep> steps = sn_steps(D);
+    std::vector<int> ea, eb, fa, fb;                       // per layer: rows [ea, eb), columns [fa, fb)
     for (int ty = 0; ty < g.tiles_y; ++ty)
         for (int tx = 0; tx < g.tiles_x; ++tx) {
             const int y0 = ty * g.tile, y1 = std::min(y0 + g.tile, h), x0 = tx * g.tile, x1 = std::min(x0 + g.tile, w);
-            // extent of layer k's output: the sub-tile grown by D + 1 - k, clipped to the image
-            auto ext = [&](int k, int &ya, int &xa, int &rows, int &cols) {
-                const int gr = D + 1 - k;
-                ya = std::max(y0 - gr, 0);
-                xa = std::max(x0 - gr, 0);
-                rows = std::min(y1 + gr, h) - ya;
-                cols = std::min(x1 + gr, w) - xa;
-            };
+            backward_extents(steps.data(), D + 2, 1, y0, y1, h, ea, eb);
+            backward_extents(steps.data(), D + 2, 1, x0, x1, w, fa, fb);
             int ya, xa, rows, cols;
-            ext(0, ya, xa, rows, cols);
-            const int pitch = (cols + 3) / 4 * 4;
+            auto ext = [&](int k) { ya = ea[k]; xa = fa[k]; rows = eb[k] - ya; cols = fb[k] - xa; };
+            ext(0);
+            const int pitch = (int)pad4(cols);
             const long long plane = (long long)rows * pitch;      // <= g.plane: one geometry for every layer of the sub-tile
             int cur = 0;
             {
@@ -215,7 +206,7 @@ static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_strid
             }
             int in_ya = ya, in_xa = xa, in_rows = rows, in_cols = cols;
             for (int k = 1; k <= D; ++k) {
-                ext(k, ya, xa, rows, cols);
+                ext(k);
                 ProfScope ps(ctx, "srnet_body");
                 hipLaunchKernelGGL((k_sn_conv<2, 0, false>), dim3((cols + 31) / 32, (rows + 7) / 8, F / 64), dim3(256), 0, ctx->stream,
                                    m->buf[cur], plane, pitch, in_ya, in_xa, in_rows, in_cols, h, w, F, m->d_w[k], m->d_b[k], m->d_slope[k],
@@ -223,7 +214,7 @@ static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_strid
                 cur ^= 1;
                 in_ya = ya; in_xa = xa; in_rows = rows; in_cols = cols;
             }
-            ext(D + 1, ya, xa, rows, cols);
+            ext(D + 1);
             {
                 ProfScope ps(ctx, "srnet_tail");
                 const dim3 grid((cols + 31) / 32, (rows + 7) / 8, 1);
@@ -250,28 +241,25 @@ int sr_srnet_create(sr_ctx *ctx, int n_feat, int n_body, int scale, const float 
     *out = nullptr;
     int rc = sn_check_arch("sr_srnet_create", n_feat, n_body, scale);       // host decision, before any device call
     if (rc) return rc;
-    if (!h_w || !h_b || !h_slope) return sr_set_error(SR_ERR_INVALID_ARG, "sr_srnet_create: null weight table");
     const int F = n_feat, D = n_body, S = scale, nl = D + 2;
-    for (int k = 0; k < nl; ++k)
-        if (!h_w[k] || !h_b[k] || (k <= D && !h_slope[k])) return sr_set_error(SR_ERR_INVALID_ARG, "sr_srnet_create: null array of layer %d", k);
+    if ((rc = check_weight_tables("sr_srnet_create", "layer", nl, nl, h_w, h_b, h_slope, D + 1))) return rc;
     CTX_ENTER(ctx);
     sr_srnet_model *M = new sr_srnet_model();
     M->ctx = ctx;
     M->F = F; M->D = D; M->S = S;
     g_sn_live.insert(M);
-    auto fail = [&](int code, const char *what) {
-        sr_set_error(code, "sr_srnet_create: %s", what);
-        sr_srnet_destroy(M);
-        return code;
-    };
     const int tail_c = 3 * S * S, tail_nc = tail_c > 32 ? 64 : 32;
     for (int k = 0; k < nl; ++k) {
         MfmaWeights a;
         if (k == 0) a = {arrange_head_weights(h_w[k], F), std::vector<float>(h_b[k], h_b[k] + F)};
         else a = arrange_mfma_weights(h_w[k], h_b[k], k <= D ? F : tail_c, F, 9, 8, k <= D ? 64 : tail_nc);
-        if ((rc = upload_floats(a.w, M->d_w)) != SR_OK) return fail(rc, "weight upload");
-        if ((rc = upload_floats(a.b, M->d_b)) != SR_OK) return fail(rc, "bias upload");
-        if (k <= D && (rc = upload_floats(std::vector<float>(h_slope[k], h_slope[k] + F), M->d_slope)) != SR_OK) return fail(rc, "slope upload");
+        rc = upload_conv("sr_srnet_create", *M, a);
+        if (!rc && k <= D && (rc = upload_floats(std::vector<float>(h_slope[k], h_slope[k] + F), M->d_slope)) != SR_OK)
+            sr_set_error(rc, "sr_srnet_create: slope upload");
+        if (rc) {
+            sr_srnet_destroy(M);
+            return rc;
+        }
     }
     *out = M;
     return SR_OK;
@@ -279,18 +267,11 @@ int sr_srnet_create(sr_ctx *ctx, int n_feat, int n_body, int scale, const float 
 
 int sr_srnet_destroy(sr_srnet_model *m)
 {
-    if (!m) return SR_OK;
-    if (!g_sn_live.erase(m)) return SR_OK;
-    if (ctx_is_live(m->ctx)) {
-        Guard g(m->ctx);
-        (void)hipStreamSynchronize(m->ctx->stream);
-        for (auto p : m->d_w) if (p) (void)hipFree(p);
-        for (auto p : m->d_b) if (p) (void)hipFree(p);
-        for (auto p : m->d_slope) if (p) (void)hipFree(p);
-        for (auto p : m->buf) if (p) (void)hipFree(p);
-    }
-    delete m;
-    return SR_OK;
+    return destroy_model(m, g_sn_live, [](const sr_srnet_model &m) {
+        std::vector<float *> v(m.d_slope);
+        v.insert(v.end(), m.buf, m.buf + 2);
+        return v;
+    });
 }
 
 int sr_srnet_plan(int h, int w, int n_feat, int n_body, int scale, int tile, int *halo, int *n_tiles, size_t *workspace_bytes)

@@ -111,12 +111,15 @@ class CompactSRNet:
     def from_file(cls, path: str, act: str = "prelu", device: int = 0) -> "CompactSRNet":
         return cls(load_state(path), act=act, device=device)
 
-    def model(self, ctx: Optional["_native.Context"] = None) -> "_native.SrNetModel":
+    def _make_model(self, ctx: "_native.Context"):
+        return _native.SrNetModel(ctx, self.n_feat, self.n_body, self.scale, self._w, self._b, self._s)
+
+    def model(self, ctx: Optional["_native.Context"] = None):
+        """The family's _native model on ``ctx`` (the device's default context if None), made on first use."""
         ctx = ctx or _native.default_context(self.device)
         m = self._models.get(id(ctx))
         if m is None or m.handle is None or m.ctx is not ctx:
-            m = _native.SrNetModel(ctx, self.n_feat, self.n_body, self.scale, self._w, self._b, self._s)
-            self._models[id(ctx)] = m
+            m = self._models[id(ctx)] = self._make_model(ctx)
         return m
 
     @staticmethod
@@ -126,13 +129,13 @@ class CompactSRNet:
         return int(shape[0]), int(shape[1])
 
     def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
-                       ctx: Optional["_native.Context"] = None):
+                       ctx: Optional["_native.Context"] = None, **run):
         """h x w x 3 u8 at d_src (dense unless src_stride is given) -> (h s) x (w s) x 3 u8 at d_dst, HBM -> HBM.
-        Asynchronous on the context's stream."""
+        Asynchronous on the context's stream.  ``run``: what the family's forward takes beside ``tile`` (RRDBSRNet: ``tail``)."""
         h, w = self._check_image_shape(shape)
-        self.model(ctx).upscale_u8(d_src, w * 3 if src_stride is None else src_stride, h, w, d_dst, dst_stride, tile)
+        self.model(ctx).upscale_u8(d_src, w * 3 if src_stride is None else src_stride, h, w, d_dst, dst_stride, tile, **run)
 
-    def upscale(self, image: np.ndarray, tile: int = 0) -> np.ndarray:
+    def upscale(self, image: np.ndarray, tile: int = 0, **run) -> np.ndarray:
         """Host array in, host array out."""
         image = np.asarray(image)
         h, w = self._check_image_shape(image.shape)
@@ -143,7 +146,7 @@ class CompactSRNet:
         d_src, d_dst = ctx.upload(image), None
         try:
             d_dst = ctx.alloc(h * s * w * s * 3)
-            self.upscale_device(d_src.ptr, (h, w, 3), d_dst.ptr, w * s * 3, tile=tile, ctx=ctx)
+            self.upscale_device(d_src.ptr, (h, w, 3), d_dst.ptr, w * s * 3, tile=tile, ctx=ctx, **run)
             return ctx.download(d_dst.ptr, (h * s, w * s, 3), np.uint8)
         finally:
             ctx.sync()
@@ -173,6 +176,42 @@ def _array(state: Mapping, key: str) -> np.ndarray:
     return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
 
 
+def _read_conv(state: Mapping, keys, name: str, cin: int, cout, cin_text: str, refuse=None):
+    """-> (weight, bias) of the 3x3 convolution ``name`` as contiguous fp32, every shape checked; a ValueError names the
+    offending key.  ``cin_text`` ends the message about a wrong input width; ``refuse(w)`` may raise before that check."""
+    for part in ("weight", "bias"):
+        if f"{name}.{part}" not in keys:
+            raise ValueError(f"{name}.{part}: not in the state")
+    w = np.ascontiguousarray(_array(state, f"{name}.weight"), dtype=np.float32)
+    b = np.ascontiguousarray(_array(state, f"{name}.bias"), dtype=np.float32).reshape(-1)
+    if w.ndim != 4 or w.shape[2:] != (3, 3):
+        raise ValueError(f"{name}.weight: only 3x3 convolutions, got shape {w.shape}")
+    if refuse is not None:
+        refuse(w)
+    if w.shape[1] != cin:
+        raise ValueError(f"{name}.weight takes {w.shape[1]} channels{cin_text.format(cin)}")
+    if cout is not None and w.shape[0] != cout:
+        raise ValueError(f"{name}.weight gives {w.shape[0]} channels, expected {cout}")
+    if b.shape != (w.shape[0],):
+        raise ValueError(f"{name}.bias: expected {w.shape[0]} values, got {b.shape}")
+    return w, b
+
+
+def _scalar_extras(state: Mapping, spec) -> dict:
+    """The constants a .npz holds beside the state dict: ``spec`` is (key, number of values) pairs; one value comes back as
+    a float, several as a tuple."""
+    out = {}
+    if not isinstance(state, Mapping):
+        return out
+    for key, size in spec:
+        if key in state:
+            a = np.asarray(_array(state, key), dtype=np.float64).reshape(-1)
+            if a.size != size:
+                raise ValueError(f"{key}: expected {size} value{'s' if size > 1 else ''}, got shape {np.shape(_array(state, key))}")
+            out[key] = tuple(a.tolist()) if size > 1 else float(a[0])
+    return out
+
+
 def parse_residual_state(state: Mapping, res_scale: float = 1.0, img_range: float = EDSR_IMG_RANGE, rgb_mean=EDSR_RGB_MEAN):
     """-> (_native.ResNetDesc, weights, biases) in sr_resnet_create's order, contiguous fp32.
 
@@ -187,21 +226,8 @@ def parse_residual_state(state: Mapping, res_scale: float = 1.0, img_range: floa
     convs = []                                                   # (key, cout or None for 'any multiple', cin)
 
     def conv(name: str, cin: int, cout=None):
-        for part in ("weight", "bias"):
-            if f"{name}.{part}" not in keys:
-                raise ValueError(f"{name}.{part}: not in the state")
-        w = np.ascontiguousarray(_array(state, f"{name}.weight"), dtype=np.float32)
-        b = np.ascontiguousarray(_array(state, f"{name}.bias"), dtype=np.float32).reshape(-1)
-        if w.ndim != 4 or w.shape[2:] != (3, 3):
-            raise ValueError(f"{name}.weight: only 3x3 convolutions, got shape {w.shape}")
-        if w.shape[1] != cin:
-            raise ValueError(f"{name}.weight takes {w.shape[1]} channels but the layer before it gives {cin}")
-        if cout is not None and w.shape[0] != cout:
-            raise ValueError(f"{name}.weight gives {w.shape[0]} channels, expected {cout}")
-        if b.shape != (w.shape[0],):
-            raise ValueError(f"{name}.bias: expected {w.shape[0]} values, got {b.shape}")
-        convs.append((w, b))
-        return w
+        convs.append(_read_conv(state, keys, name, cin, cout, " but the layer before it gives {}"))
+        return convs[-1][0]
 
     F = int(conv("conv_first", 3).shape[0])
     blocks = sorted({int(m.group(1)) for m in map(_BLOCK_KEY.match, keys) if m})
@@ -259,26 +285,12 @@ class ResidualSRNet(CompactSRNet):
         state = load_state(path)
         return cls(state, device=device, **{**_residual_extras(state), **extras})
 
-    def model(self, ctx: Optional["_native.Context"] = None) -> "_native.ResNetModel":
-        ctx = ctx or _native.default_context(self.device)
-        m = self._models.get(id(ctx))
-        if m is None or m.handle is None or m.ctx is not ctx:
-            m = _native.ResNetModel(ctx, self.desc, self._w, self._b)
-            self._models[id(ctx)] = m
-        return m
+    def _make_model(self, ctx: "_native.Context"):
+        return _native.ResNetModel(ctx, self.desc, self._w, self._b)
 
 
 def _residual_extras(state: Mapping) -> dict:
-    out = {}
-    if not isinstance(state, Mapping):
-        return out
-    for key, size in (("res_scale", 1), ("img_range", 1), ("rgb_mean", 3)):
-        if key in state:
-            a = np.asarray(_array(state, key), dtype=np.float64).reshape(-1)
-            if a.size != size:
-                raise ValueError(f"{key}: expected {size} value{'s' if size > 1 else ''}, got shape {np.shape(_array(state, key))}")
-            out[key] = tuple(a.tolist()) if size == 3 else float(a[0])
-    return out
+    return _scalar_extras(state, (("res_scale", 1), ("img_range", 1), ("rgb_mean", 3)))
 
 
 # ------------------------------------------------------------------------------------------
@@ -303,25 +315,14 @@ def parse_rrdb_state(state: Mapping, slope: float = 0.2, res_scale: float = 0.2)
         raise ValueError("conv_first.weight: not in the state (not an RRDB network)")
     convs = []
 
-    def conv(name: str, cin: int, cout=None):
-        for part in ("weight", "bias"):
-            if f"{name}.{part}" not in keys:
-                raise ValueError(f"{name}.{part}: not in the state")
-        w = np.ascontiguousarray(_array(state, f"{name}.weight"), dtype=np.float32)
-        b = np.ascontiguousarray(_array(state, f"{name}.bias"), dtype=np.float32).reshape(-1)
-        if w.ndim != 4 or w.shape[2:] != (3, 3):
-            raise ValueError(f"{name}.weight: only 3x3 convolutions, got shape {w.shape}")
-        if name == "conv_first" and w.shape[1] in (12, 48):
+    def unshuffled(w):
+        if w.shape[1] in (12, 48):
             raise NotImplementedError(f"conv_first.weight takes {w.shape[1]} channels: the x{2 if w.shape[1] == 12 else 1} RRDBNet puts a "
                                       "pixel-unshuffle in front of conv_first, which is not supported (x4 only)")
-        if w.shape[1] != cin:
-            raise ValueError(f"{name}.weight takes {w.shape[1]} channels, expected {cin}")
-        if cout is not None and w.shape[0] != cout:
-            raise ValueError(f"{name}.weight gives {w.shape[0]} channels, expected {cout}")
-        if b.shape != (w.shape[0],):
-            raise ValueError(f"{name}.bias: expected {w.shape[0]} values, got {b.shape}")
-        convs.append((w, b))
-        return w
+
+    def conv(name: str, cin: int, cout=None):
+        convs.append(_read_conv(state, keys, name, cin, cout, ", expected {}", unshuffled if name == "conv_first" else None))
+        return convs[-1][0]
 
     F = int(conv("conv_first", 3).shape[0])
     blocks = sorted({int(m.group(1)) for m in map(_RRDB_BLOCK_KEY.match, keys) if m})
@@ -364,49 +365,12 @@ class RRDBSRNet(CompactSRNet):
         state = load_state(path)
         return cls(state, device=device, **{**_rrdb_extras(state), **extras})
 
-    def model(self, ctx: Optional["_native.Context"] = None) -> "_native.RrdbModel":
-        ctx = ctx or _native.default_context(self.device)
-        m = self._models.get(id(ctx))
-        if m is None or m.handle is None or m.ctx is not ctx:
-            m = _native.RrdbModel(ctx, self.desc, self._w, self._b)
-            self._models[id(ctx)] = m
-        return m
-
-    def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
-                       ctx: Optional["_native.Context"] = None, tail: int = 0):
-        h, w = self._check_image_shape(shape)
-        self.model(ctx).upscale_u8(d_src, w * 3 if src_stride is None else src_stride, h, w, d_dst, dst_stride, tile, tail)
-
-    def upscale(self, image: np.ndarray, tile: int = 0, tail: int = 0) -> np.ndarray:
-        """Host array in, host array out."""
-        image = np.asarray(image)
-        h, w = self._check_image_shape(image.shape)
-        if image.dtype != np.uint8:
-            raise ValueError(f"the SR network takes u8 images, got {image.dtype}")
-        ctx = _native.default_context(self.device)
-        d_src, d_dst = ctx.upload(image), None
-        try:
-            d_dst = ctx.alloc(h * 4 * w * 4 * 3)
-            self.upscale_device(d_src.ptr, (h, w, 3), d_dst.ptr, w * 4 * 3, tile=tile, ctx=ctx, tail=tail)
-            return ctx.download(d_dst.ptr, (h * 4, w * 4, 3), np.uint8)
-        finally:
-            ctx.sync()
-            d_src.free()
-            if d_dst is not None:
-                d_dst.free()
+    def _make_model(self, ctx: "_native.Context"):
+        return _native.RrdbModel(ctx, self.desc, self._w, self._b)
 
 
 def _rrdb_extras(state: Mapping) -> dict:
-    out = {}
-    if not isinstance(state, Mapping):
-        return out
-    for key in ("slope", "res_scale"):
-        if key in state:
-            a = np.asarray(_array(state, key), dtype=np.float64).reshape(-1)
-            if a.size != 1:
-                raise ValueError(f"{key}: expected 1 value, got shape {np.shape(_array(state, key))}")
-            out[key] = float(a[0])
-    return out
+    return _scalar_extras(state, (("slope", 1), ("res_scale", 1)))
 
 
 def load_network(path: str, act: str = "prelu", device: int = 0):
