@@ -524,6 +524,50 @@ SR_API int sr_quality_map_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, 
  * is sr_ssim_count(h, w, mode, 0, h) */
 SR_API int sr_quality_map_counts(int h, int w, int mode, const int *h_xedges, int gw, const int *h_yedges, int gh,
                                  uint64_t *counts);
+/* ---- multi-scale SSIM (csrc/sr_msssim.hip; Wang, Simoncelli, Bovik 2003) ------------------------------------------------
+ * No reference counterpart: the reference's 'ms_ssim' report key is its single-scale Gaussian SSIM under another name
+ * (sr_ssim_u8 mode SR_SSIM_GAUSS11), and stays that.  This is the real thing, defined as follows.
+ * Inputs: two u8 images of h x w with cn = 1 or 3 (3: grayed with the OpenCV fixed-point rule of sr_ssim_u8, gray_shift 15 or
+ * 14).  L levels, 1 <= L <= 5, weights w_0 .. w_{L-1} (default: the first L of 0.0448, 0.2856, 0.3001, 0.2363, 0.1333).
+ *   planes   x_0, y_0 = the gray images; x_{j+1} = the 2 x 2 mean of x_j, floor(h_j / 2) x floor(w_j / 2): a last odd row or
+ *            column is dropped.  The pooling is EXACT: a level-j value is (sum of 4^j u8 values) / 4^j, the sums (<= 255 * 256
+ *            = 65280 at j = 4, which is why L stops at 5) are kept as 16-bit integers and nothing ever rounds.
+ *   terms    per level the Gaussian window of 11 taps, sigma 1.5 (the taps of SR_SSIM_GAUSS11), valid region only -- the map
+ *            is (h_j - 10) x (w_j - 10) --, population covariance, C1 = (0.01 R)^2, C2 = (0.03 R)^2 with R = data_range,
+ *            float64 throughout:  l = (2 ux uy + C1) / (ux^2 + uy^2 + C1),  cs = (2 sxy + C2) / (sx^2 + sy^2 + C2),
+ *            S_j = mean(l cs), CS_j = mean(cs).  (The kernels work on the integer sums with C1, C2 scaled by 16^j, which
+ *            leaves l and cs unchanged up to rounding at the 1e-16 level.)
+ *   value    prod_{j < L-1} max(CS_j, 0)^{w_j} * max(S_{L-1}, 0)^{w_{L-1}}, in float64 on the host with pow(); a negative
+ *            mean clamps to 0, so the product is then exactly 0.0.
+ *   sizes    every level needs h_j, w_j >= 11, i.e. both sides >= 11 * 2^(L-1) (176 for L = 5); a smaller image is
+ *            SR_ERR_SHAPE naming the minimum -- the level count is never silently reduced.
+ * Pinned: with L = 1 and w = (1) this is scikit-image's Gaussian SSIM (tests/golden/metrics_skimage.npz), and every S_j equals
+ * scikit-image 0.18.3 on the exactly pooled float64 planes (tests/golden/msssim_skimage.npz).  scikit-image does not expose
+ * cs, so CS_j rests on the NumPy restatement in tests/_msssim_ref.py alone.  PARITY UNPINNED with pytorch-msssim and
+ * TensorFlow's ssim_multiscale: neither is available offline, and they differ from this definition (and from each other) in
+ * how they pad odd sides before pooling. */
+typedef struct sr_ms_ssim_level {
+    double sum_lcs;     /* sum of l * cs over the level's map */
+    double sum_cs;      /* sum of cs */
+    uint64_t count;     /* map samples, (h_j - 10) * (w_j - 10) */
+} sr_ms_ssim_level;
+/* Host only, no context: per-level sizes and map sample counts (arrays of `levels` entries, each may be NULL) and the bytes
+ * of context scratch a call will hold.  SR_ERR_INVALID_ARG for levels outside 1..5, SR_ERR_SHAPE for a too-small image. */
+SR_API int sr_ms_ssim_plan(int h, int w, int levels, int *level_h, int *level_w, uint64_t *counts, size_t *scratch_bytes);
+/* One launch per level; level 0 reads both images once (2 * cn bytes / pixel) and writes the level-1 sums (4 bytes per
+ * level-1 pixel).  Strides in bytes, arbitrary (>= a row).  h_out: `levels` records.  Per-block partial sums are added in a
+ * fixed order, no floating-point atomics: equal inputs give equal bits.  Synchronous.  The level planes and partials are
+ * context scratch, grown on demand (about h * w / 3 * 4 bytes).  Refused before any device call: null pointers, a stride
+ * shorter than a row (SR_ERR_SHAPE), cn not 1 or 3, gray_shift not 14 or 15, data_range not finite and positive, levels
+ * outside 1..5, a too-small image (SR_ERR_SHAPE). */
+SR_API int sr_ms_ssim_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
+                         int cn, int gray_shift, double data_range, int levels, sr_ms_ssim_level *h_out);
+/* The value formula above on the records of sr_ms_ssim_u8 (host only); weights: `levels` doubles, or NULL for the default.
+ * NaN (and sr_last_error) for a null record list, levels outside 1..5 or a level without samples. */
+SR_API double sr_ms_ssim_value(const sr_ms_ssim_level *out, int levels, const double *weights);
+/* The pooled planes the context's last completed sr_ms_ssim_u8 call left in its scratch, for inspection: the exact integer
+ * sums of 4^level gray values of level 1 <= level < levels of that call, h_x / h_y dense (h >> level) x (w >> level). */
+SR_API int sr_ms_ssim_planes(sr_ctx *ctx, int level, uint16_t *h_x, uint16_t *h_y);
 /* cv2.cvtColor(RGB2GRAY) on u8 (quality_assessment_module.py:359-360) */
 SR_API int sr_rgb2gray_u8(sr_ctx *ctx, const uint8_t *d_rgb, int64_t stride, int h, int w,
                           int gray_shift, uint8_t *d_gray, int64_t gray_stride);

@@ -62,6 +62,15 @@ class QualityCell(C.Structure):
     _fields_ = [("sse", C.c_uint64), ("ssim_uniform", C.c_double), ("ssim_gauss", C.c_double), ("ssim_simple", C.c_double)]
 
 
+class MsSsimLevel(C.Structure):
+    """sr_ms_ssim_level (include/sr_hip.h)."""
+    _fields_ = [("sum_lcs", C.c_double), ("sum_cs", C.c_double), ("count", C.c_uint64)]
+
+
+MS_SSIM_MAX_LEVELS = 5
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
 # metric bits of sr_commercial_u8 (include/sr_hip.h)
 (CM_LAPG, CM_NOISE, CM_SOBEL, CM_MSCN, CM_TEX, CM_LAB, CM_SKIN, CM_RGB, CM_BLOCKS, CM_REGIONS, CM_CANNY,
  CM_HF) = (1 << i for i in range(12))
@@ -186,6 +195,10 @@ SIGNATURES = {
     "sr_ssim_count": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_uint64)]),
     "sr_quality_map_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _dbl, _pi, _i, _pi, _i, _i, C.POINTER(QualityCell)]),
     "sr_quality_map_counts": (_i, [_i, _i, _i, _pi, _i, _pi, _i, C.POINTER(C.c_uint64)]),
+    "sr_ms_ssim_plan": (_i, [_i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), C.POINTER(_sz)]),
+    "sr_ms_ssim_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _dbl, _i, C.POINTER(MsSsimLevel)]),
+    "sr_ms_ssim_value": (_dbl, [C.POINTER(MsSsimLevel), _i, C.POINTER(_dbl)]),
+    "sr_ms_ssim_planes": (_i, [_vp, _i, _vp, _vp]),
     "sr_rgb2gray_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
     "sr_resize_cubic_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i]),
     "sr_resize_cubic_window_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64]),
@@ -468,6 +481,51 @@ def quality_map_counts(h: int, w: int, mode: str, x_edges, y_edges) -> np.ndarra
     return out
 
 
+def _whole(v, name: str) -> int:
+    if isinstance(v, bool) or int(v) != v:
+        raise ValueError(f"{name} must be a whole number, got {v!r}")
+    return int(v)
+
+
+def ms_ssim_plan(h: int, w: int, levels: int = 5) -> dict:
+    """Host only (sr_ms_ssim_plan): the per-level sizes [(h_j, w_j)], the per-level map sample counts and the bytes of context
+    scratch of an MS-SSIM call.  ValueError for levels outside 1..5, SrShapeError (a ValueError) naming the minimum side for
+    an image too small for that many levels."""
+    h, w, levels = _whole(h, "h"), _whole(w, "w"), _whole(levels, "levels")
+    n = max(1, min(levels, MS_SSIM_MAX_LEVELS))
+    lh, lw, cnt, nbytes = (C.c_int * n)(), (C.c_int * n)(), (C.c_uint64 * n)(), C.c_size_t(0)
+    check(load().sr_ms_ssim_plan(h, w, levels, lh, lw, cnt, C.byref(nbytes)))
+    return {"sizes": [(lh[j], lw[j]) for j in range(n)], "counts": [int(cnt[j]) for j in range(n)],
+            "scratch_bytes": int(nbytes.value)}
+
+
+def _ms_ssim_weights(weights, levels: int):
+    if weights is None:
+        return None
+    wt = [float(v) for v in weights]
+    if len(wt) != levels:
+        raise ValueError(f"ms_ssim: {levels} levels need {levels} weights, got {len(wt)}")
+    if not all(np.isfinite(wt)):
+        raise ValueError("ms_ssim: weights must be finite")
+    return (C.c_double * levels)(*wt)
+
+
+def ms_ssim_value(levels_out, weights=None) -> float:
+    """Host only (sr_ms_ssim_value): prod_{j < L-1} max(CS_j, 0)^w_j * max(S_{L-1}, 0)^w_{L-1} of per-level records
+    [(sum_lcs, sum_cs, count)]; weights: L numbers, default Wang's."""
+    recs = [(float(a), float(b), int(n)) for (a, b, n) in levels_out]
+    n = len(recs)
+    if n < 1 or n > MS_SSIM_MAX_LEVELS:
+        raise ValueError(f"ms_ssim_value: levels must be 1 .. {MS_SSIM_MAX_LEVELS} (got {n})")
+    if any(r[2] < 1 for r in recs):
+        raise ValueError("ms_ssim_value: a level without samples")
+    arr = (MsSsimLevel * n)(*[MsSsimLevel(*r) for r in recs])
+    v = float(load().sr_ms_ssim_value(arr, n, _ms_ssim_weights(weights, n)))
+    if v != v:
+        raise ValueError(last_error())
+    return v
+
+
 def psnr_from_sse(sse: int, count: int, data_range: float = 255.0) -> float:
     return float(load().sr_psnr_from_sse(C.c_uint64(sse), C.c_uint64(count), data_range))
 
@@ -683,6 +741,26 @@ class Context:
         arr = np.frombuffer(recs, dtype=np.dtype([("sse", "<u8"), ("ssim_uniform", "<f8"), ("ssim_gauss", "<f8"),
                                                   ("ssim_simple", "<f8")])).reshape(gh, gw)
         return {k: np.ascontiguousarray(arr[k]) for k in ("sse", "ssim_uniform", "ssim_gauss", "ssim_simple")}
+
+    def ms_ssim_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, levels=5, gray_shift=15, data_range=255.0):
+        """sr_ms_ssim_u8 -> [(sum of l cs, sum of cs, count)] per level (S_j = sum_lcs / count, CS_j = sum_cs / count; finish
+        with ms_ssim_value).  Every argument is checked before the device is touched: ValueError, or its subclass
+        SrShapeError for a short stride or an image too small for `levels`."""
+        levels = _whole(levels, "levels")
+        if not d_a or not d_b:
+            raise ValueError("ms_ssim_u8: null image pointer")
+        n = max(1, min(levels, MS_SSIM_MAX_LEVELS))
+        out = (MsSsimLevel * n)()
+        check(self.lib.sr_ms_ssim_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
+                                     int(cn), int(gray_shift), float(data_range), levels, out))
+        return [(out[j].sum_lcs, out[j].sum_cs, int(out[j].count)) for j in range(n)]
+
+    def ms_ssim_planes(self, level: int, shape) -> Tuple[np.ndarray, np.ndarray]:
+        """sr_ms_ssim_planes: the exact integer sums (uint16, 4^level gray values each) of level `level` that the last
+        ms_ssim_u8 call of this context left in its scratch; shape = that level's (h_j, w_j) from ms_ssim_plan."""
+        x, y = np.zeros(shape, dtype=np.uint16), np.zeros(shape, dtype=np.uint16)
+        check(self.lib.sr_ms_ssim_planes(self.handle, int(level), x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p)))
+        return x, y
 
     def assess_resized_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, dst_h, dst_w, flags=ASSESS_SSE | ASSESS_UNIFORM7,
                           gray_shift=15, data_range=255.0) -> dict:

@@ -57,6 +57,9 @@ struct sr_ctx {
     size_t gray_planes_bytes = 0;
     void *cm_ws = nullptr;                              // commercial / no-reference metrics: planes, FFT buffers, partials
     size_t cm_ws_bytes = 0;
+    void *msssim_ws = nullptr;                          // MS-SSIM: level planes (x | y << 16 sums), partials, per-level results
+    size_t msssim_ws_bytes = 0;
+    int msssim_h = 0, msssim_w = 0, msssim_levels = 0;  // what the planes hold (levels == 0: nothing valid)
 };
 
 // Enqueue a small host->device table upload whose source stays alive until the next sync.

@@ -64,6 +64,8 @@ class PipelineConfig:
     volc_region: str = "cn-beijing"
     sr_scale: int = 2          # the reference hard-codes 2 (main.py:217,322)
     qa_map_cell: int = 0       # > 0 (with enable_qa): stage 4 also writes a per-cell quality map of this cell size
+    qa_ms_ssim: bool = False   # (with enable_qa): stage 4 also reports the 5-scale MS-SSIM of the canvas against the INTER_CUBIC
+                               # resize of the source ('ms_ssim_5scale'; the 'ms_ssim' key keeps the reference's single-scale value)
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
                                    # only the canvas comes back for the writer (a custom sr_backend gets host arrays)
     sr_weights: str = ""       # path of an SR network's weights (.npz, or .pth / .pt where torch imports): stage 2 runs the
@@ -178,6 +180,29 @@ class SuperResolutionPipeline:
         if report:
             with open(output_path.rsplit('.', 1)[0] + '_qa_report.json', 'w', encoding='utf-8') as f:
                 json.dump(report, f, indent=2, ensure_ascii=False, default=str)
+
+    def _ms_ssim(self, ctx, report: Dict[str, Any], d_src: int, src_shape, d_canvas: int, canvas_shape) -> None:
+        """Stage 4's optional 'ms_ssim_5scale' / 'ms_ssim_5scale_levels' entries (qa_ms_ssim): Wang's 5-scale MS-SSIM of the
+        canvas against the INTER_CUBIC resize of the source to the canvas size, both in HBM.  A canvas below 176 pixels on a
+        side has no fifth level: both entries are None and 'ms_ssim_5scale_note' says why (the run does not fail).  One helper
+        for the device-resident, the host-array and the sharded path."""
+        import _native
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        ih, iw = int(src_shape[0]), int(src_shape[1])
+        try:
+            _native.ms_ssim_plan(H, W, 5)
+        except ValueError as exc:
+            report['ms_ssim_5scale'], report['ms_ssim_5scale_levels'], report['ms_ssim_5scale_note'] = None, None, str(exc)
+            return
+        ref = ctx.alloc(H * W * cn)
+        try:
+            ctx.resize_cubic_u8(d_src, iw * cn, ih, iw, cn, ref.ptr, W * cn, H, W)
+            v, lv = self.quality_module.calculate_ms_ssim_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn), levels=5,
+                                                                 return_levels=True)
+        finally:
+            ctx.sync()
+            ref.free()
+        report['ms_ssim_5scale'], report['ms_ssim_5scale_levels'] = float(v), lv
 
     def _quality_map(self, ctx, d_src: int, src_shape, d_canvas: int, canvas_shape, tiles: List[Tile],
                      output_path: str) -> Dict[str, Any]:
@@ -303,6 +328,8 @@ class SuperResolutionPipeline:
                           'timestamp': datetime.now().isoformat()}
                 if self.config.qa_map_cell > 0:
                     report['quality_map'] = self._quality_map(ctx, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3), tiles, output_path)
+                if self.config.qa_ms_ssim:
+                    self._ms_ssim(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 score = qa.get('overall_score', 0)
             lap("assess")
             # Stage 5: the one download, then the writer
@@ -396,6 +423,8 @@ class SuperResolutionPipeline:
                     if self.config.qa_map_cell > 0:
                         report['quality_map'] = self._quality_map(qctx, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3),
                                                                   tiles, output_path)
+                    if self.config.qa_ms_ssim:
+                        self._ms_ssim(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     score = qa.get('overall_score', 0)
                 fused = qctx.download(canvas.data_ptr(), (H, W, 3), np.uint8)
                 self._write_outputs(fused, output_path, report)
@@ -476,6 +505,13 @@ class SuperResolutionPipeline:
                                                                   tiles, output_path)
                     finally:
                         d_src.free(); d_fused.free()
+                if self.config.qa_ms_ssim:
+                    qctx = self.quality_module._ctx()
+                    d_src, d_fused = qctx.upload(original), qctx.upload(fused)
+                    try:
+                        self._ms_ssim(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
+                    finally:
+                        d_src.free(); d_fused.free()
                 score = qa.get('overall_score', 0)
             # Stage 5: output
             self._write_outputs(fused, output_path, report)
@@ -512,6 +548,9 @@ async def main() -> int:
                     help="weights of an SR network (.npz / .pth: compact, MSRResNet / EDSR, or RRDBNet x4 with --sr-scale 4): stage 2 runs it "
                          "instead of the bicubic stub")
     ap.add_argument("--sr-act", default="prelu", metavar="NAME", help="prelu (slopes in the weights), relu or leakyrelu")
+    ap.add_argument("--qa-ms-ssim", action="store_true",
+                    help="stage 4 also reports Wang's 5-scale MS-SSIM of the result against the bicubic resize of the input "
+                         "(report key ms_ssim_5scale)")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node to use: N > 1 starts one process per GPU (RCCL)")
     ap.add_argument("--deadline-s", type=float, default=1800.0,
                     help="--gpus N: ranks still running after this many seconds are terminated (status 124)")
@@ -531,7 +570,8 @@ async def main() -> int:
         print(f"main.py: launched with WORLD_SIZE={world} but --gpus {args.gpus}", file=sys.stderr)
         return 2
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
-    cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act)
+    cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act,
+                         qa_ms_ssim=args.qa_ms_ssim)
     if args.plan_only:
         from PIL import Image
         with Image.open(args.input) as im:

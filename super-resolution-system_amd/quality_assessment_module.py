@@ -304,6 +304,64 @@ class QualityAssessmentModule:
         finally:
             da.free(); db.free()
 
+    # -- multi-scale SSIM (no reference counterpart: the reference's 'ms_ssim' key is its single-scale Gaussian SSIM) ----------
+    @staticmethod
+    def _ms_ssim_args(h: int, w: int, cn: int, data_range: float, levels: int, weights):
+        """Every refusal of the MS-SSIM methods, on the host: ValueError (SrShapeError for an image too small for `levels`)."""
+        if cn not in (1, 3):
+            raise ValueError("calculate_ms_ssim: colour images must have 3 channels (cv2.COLOR_RGB2GRAY)")
+        if not (np.isfinite(data_range) and data_range > 0):
+            raise ValueError(f"calculate_ms_ssim: data_range must be finite and positive, got {data_range!r}")
+        plan = _native.ms_ssim_plan(h, w, levels)                       # levels outside 1..5, sides below 11 * 2^(levels-1)
+        wt = _native.MS_SSIM_WEIGHTS[:int(levels)] if weights is None else tuple(float(v) for v in weights)
+        if len(wt) != int(levels):
+            raise ValueError(f"calculate_ms_ssim: {int(levels)} levels need {int(levels)} weights, got {len(wt)}")
+        if not all(np.isfinite(wt)):
+            raise ValueError("calculate_ms_ssim: weights must be finite")
+        return plan, wt
+
+    def _ms_ssim_dev(self, a: _DevImage, b: _DevImage, data_range: float, levels: int, wt, return_levels: bool):
+        h, w = min(a.h, b.h), min(a.w, b.w)
+        recs = a.ctx.ms_ssim_u8(a.ptr, a.stride, b.ptr, b.stride, h, w, a.cn, levels=int(levels), gray_shift=self.gray_shift,
+                                data_range=float(data_range))
+        v = _native.ms_ssim_value(recs, wt)
+        if not return_levels:
+            return v
+        return v, {"s": [r[0] / r[2] for r in recs], "cs": [r[1] / r[2] for r in recs], "weights": list(wt)}
+
+    def calculate_ms_ssim(self, img1: np.ndarray, img2: np.ndarray, data_range: float = 255.0, levels: int = 5, weights=None,
+                          return_levels: bool = False):
+        """Wang / Simoncelli / Bovik multi-scale SSIM of the common top-left rectangle of two u8 images (the preprocessing,
+        u8 requirement and channel-layout check of calculate_ssim), as include/sr_hip.h defines it: exact 2 x 2 mean pooling
+        (a last odd row or column dropped), Gaussian-11 SSIM over the valid region per level, the weighted product of the
+        first levels' cs means and the last level's SSIM mean (weights: `levels` numbers, default Wang's).  Both sides must
+        be at least 11 * 2^(levels - 1) (176 for 5 levels): a smaller image is a ValueError, the level count is never
+        reduced.  return_levels: also {'s': [S_j], 'cs': [CS_j], 'weights': [...]}.  This is NOT the 'ms_ssim' key of
+        evaluate_full_reference, which keeps the reference's single-scale value."""
+        a, b = self._pair(img1, img2, "calculate_ms_ssim")
+        cn = a.shape[2] if a.ndim == 3 else 1
+        _, wt = self._ms_ssim_args(min(a.shape[0], b.shape[0]), min(a.shape[1], b.shape[1]), cn, data_range, levels, weights)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._ms_ssim_dev(da, db, data_range, levels, wt, return_levels)
+        finally:
+            da.free(); db.free()
+
+    def calculate_ms_ssim_device(self, d_img1: int, shape1, d_img2: int, shape2, data_range: float = 255.0, levels: int = 5,
+                                 weights=None, return_levels: bool = False):
+        """calculate_ms_ssim on two dense u8 images that already live in HBM (device addresses + shapes)."""
+        shape1, shape2 = tuple(int(v) for v in shape1), tuple(int(v) for v in shape2)
+        if len(shape1) not in (2, 3) or len(shape1) != len(shape2) or (len(shape1) == 3 and shape1[2] != shape2[2]):
+            raise ValueError(f"calculate_ms_ssim: images have different channel layouts {shape1} vs {shape2}")
+        if not d_img1 or not d_img2:
+            raise ValueError("calculate_ms_ssim: null device pointer")
+        cn = shape1[2] if len(shape1) == 3 else 1
+        _, wt = self._ms_ssim_args(min(shape1[0], shape2[0]), min(shape1[1], shape2[1]), cn, data_range, levels, weights)
+        ctx = self._ctx()
+        return self._ms_ssim_dev(_DevImage(ctx, shape=shape1, ptr=d_img1), _DevImage(ctx, shape=shape2, ptr=d_img2), data_range,
+                                 levels, wt, return_levels)
+
     def _calculate_ssim_simple(self, img1: np.ndarray, img2: np.ndarray) -> float:
         """quality_assessment_module.py:391-417 on already-gray u8 images."""
         a = self._require_u8(np.asarray(img1), "_calculate_ssim_simple")
