@@ -568,6 +568,52 @@ SR_API double sr_ms_ssim_value(const sr_ms_ssim_level *out, int levels, const do
 /* The pooled planes the context's last completed sr_ms_ssim_u8 call left in its scratch, for inspection: the exact integer
  * sums of 4^level gray values of level 1 <= level < levels of that call, h_x / h_y dense (h >> level) x (w >> level). */
 SR_API int sr_ms_ssim_planes(sr_ctx *ctx, int level, uint16_t *h_x, uint16_t *h_y);
+/* ---- SR-benchmark PSNR / SSIM (csrc/sr_srbench.hip) -----------------------------------------------------------------------
+ * The two numbers the papers and model cards of the SR networks quote: PSNR and SSIM on the BT.601 luma (Y) channel with a
+ * border of `scale` pixels cropped -- BasicSR's calculate_psnr / calculate_ssim(crop_border, test_y_channel=True) and the
+ * MATLAB evaluation scripts before it.  No reference counterpart.  PARITY UNPINNED with BasicSR: the package is not available
+ * offline.  Known distance: BasicSR rounds Y to float32 on the way; measured on the CPU at four sizes, that moves its PSNR
+ * by about 1e-6 dB and its SSIM by about 1e-8 against this definition.
+ * Inputs: two u8 images of h x w x cn, strides in bytes.  crop_border = cb >= 0: both images are first cropped to rows
+ * [cb, h - cb) and columns [cb, w - cb), ch x cw.  Both sides must be at least 11 after the crop, else SR_ERR_SHAPE naming
+ * the minimum; nothing is silently reduced.
+ *   planes   SR_BENCH_CHANNELS  cn = 1 or 3: the channels as they are (cn planes)
+ *            SR_BENCH_Y         cn = 3: one plane Y = 16 + (65.481 R + 128.553 G + 24.966 B) / 255, carried EXACTLY as the
+ *                               integer X = 65481 R + 128553 G + 24966 B + 4080000, Y = X / 255000, X <= 59 925 000 < 2^26;
+ *                               X X' and X^2 + X'^2 are below 2^53, exact in float64: nothing rounds before the filter
+ *            SR_BENCH_Y_ROUND   cn = 3: one u8 plane floor((2 X + 255000) / 510000): MATLAB's uint8 rgb2ycbcr (round half
+ *                               up), which the older tables used
+ *   PSNR     sse = the sum over planes and pixels of the squared plane difference in gray-level units: an exact integer in
+ *            CHANNELS and Y_ROUND, sum (X - X')^2 / 255000^2 in Y (each (X - X')^2 and each thread's sum of them an exact
+ *            integer; the fp64 additions of the final tree and the one division round).
+ *            psnr = 10 log10(R^2 / (sse / n_elems)), inf for sse == 0; R = data_range.
+ *   SSIM     per plane the Gaussian window of 11 taps, sigma 1.5 (the taps of SR_SSIM_GAUSS11), valid region only -- the
+ *            map is (ch - 10) x (cw - 10) --, population covariance, C1 = (0.01 R)^2, C2 = (0.03 R)^2, float64 throughout;
+ *            the value is the mean over the maps of all planes, ssim_sum / n_map.  Every SSIM term is a ratio homogeneous
+ *            of degree 0 in (planes, C1, C2), so in SR_BENCH_Y the kernel filters the integers X with C1, C2 multiplied
+ *            by 255000^2 (as sr_ms_ssim_u8 does with 16^j).
+ * Pinned: all three modes by scikit-image 0.18.3 (structural_similarity(gaussian_weights=True, sigma=1.5,
+ * use_sample_covariance=False, data_range=255) and peak_signal_noise_ratio on the float64 planes;
+ * tests/golden/srbench_skimage.npz) and by the NumPy restatement tests/_srbench_ref.py. */
+enum sr_bench_mode { SR_BENCH_CHANNELS = 0, SR_BENCH_Y = 1, SR_BENCH_Y_ROUND = 2 };
+typedef struct sr_bench_sums {
+    double sse;         /* see PSNR above */
+    double ssim_sum;    /* sum of the SSIM maps of all planes */
+    uint64_t n_elems;   /* ch * cw * planes */
+    uint64_t n_map;     /* (ch - 10) * (cw - 10) * planes */
+} sr_bench_sums;
+/* Host only, no context: the cropped size, both counts and the bytes of context scratch a call will hold (each output may
+ * be NULL).  Carries every shape refusal: SR_ERR_INVALID_ARG for cn not 1 or 3, an unknown mode, a Y mode with cn = 1,
+ * crop_border < 0, h or w < 1; SR_ERR_SHAPE for a side below 11 after the crop. */
+SR_API int sr_bench_plan(int h, int w, int cn, int crop_border, int mode, int *ch, int *cw, uint64_t *n_elems, uint64_t *n_map,
+                         size_t *scratch_bytes);
+/* One launch, one pass over both images for sse and the SSIM sum.  The crop is pointer arithmetic; pixels are read byte by
+ * byte, so no alignment is assumed.  Per-block partial sums are added in a fixed order, no floating-point atomics: equal
+ * inputs give equal bits.  Synchronous; the partials are context scratch, grown on demand.  Refused before any device call:
+ * null pointers, data_range not finite and positive, everything sr_bench_plan refuses, a stride shorter than a row of the
+ * uncropped image (SR_ERR_SHAPE). */
+SR_API int sr_bench_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
+                       int cn, int crop_border, int mode, double data_range, sr_bench_sums *h_out);
 /* cv2.cvtColor(RGB2GRAY) on u8 (quality_assessment_module.py:359-360) */
 SR_API int sr_rgb2gray_u8(sr_ctx *ctx, const uint8_t *d_rgb, int64_t stride, int h, int w,
                           int gray_shift, uint8_t *d_gray, int64_t gray_stride);

@@ -5,6 +5,7 @@ the compute entry points raise (SrNativeError), they never route through oracle/
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 from typing import List, Optional, Sequence, Tuple
@@ -66,6 +67,14 @@ class MsSsimLevel(C.Structure):
     """sr_ms_ssim_level (include/sr_hip.h)."""
     _fields_ = [("sum_lcs", C.c_double), ("sum_cs", C.c_double), ("count", C.c_uint64)]
 
+
+class BenchSums(C.Structure):
+    """sr_bench_sums (include/sr_hip.h)."""
+    _fields_ = [("sse", C.c_double), ("ssim_sum", C.c_double), ("n_elems", C.c_uint64), ("n_map", C.c_uint64)]
+
+
+# enum sr_bench_mode (include/sr_hip.h)
+BENCH_CHANNELS, BENCH_Y, BENCH_Y_ROUND = 0, 1, 2
 
 MS_SSIM_MAX_LEVELS = 5
 MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
@@ -199,6 +208,8 @@ SIGNATURES = {
     "sr_ms_ssim_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _dbl, _i, C.POINTER(MsSsimLevel)]),
     "sr_ms_ssim_value": (_dbl, [C.POINTER(MsSsimLevel), _i, C.POINTER(_dbl)]),
     "sr_ms_ssim_planes": (_i, [_vp, _i, _vp, _vp]),
+    "sr_bench_plan": (_i, [_i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_sz)]),
+    "sr_bench_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _dbl, C.POINTER(BenchSums)]),
     "sr_rgb2gray_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
     "sr_resize_cubic_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i]),
     "sr_resize_cubic_window_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64]),
@@ -526,6 +537,24 @@ def ms_ssim_value(levels_out, weights=None) -> float:
     return v
 
 
+def bench_plan(h: int, w: int, cn: int, crop_border: int = 0, mode: int = BENCH_Y) -> dict:
+    """Host only (sr_bench_plan): the cropped size, the element and map sample counts and the bytes of context scratch of an
+    SR-benchmark PSNR / SSIM call.  ValueError for cn not 1 or 3, an unknown mode, a Y mode on one channel or a negative
+    crop_border; SrShapeError (a ValueError) naming the minimum for a side below 11 after the crop."""
+    h, w, cn, crop_border, mode = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn"), (crop_border, "crop_border"),
+                                                             (mode, "mode")))
+    ch, cw, ne, nm, nbytes = C.c_int(0), C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_size_t(0)
+    check(load().sr_bench_plan(h, w, cn, crop_border, mode, C.byref(ch), C.byref(cw), C.byref(ne), C.byref(nm), C.byref(nbytes)))
+    return {"size": (ch.value, cw.value), "n_elems": int(ne.value), "n_map": int(nm.value), "scratch_bytes": int(nbytes.value)}
+
+
+def bench_values(sums: dict, data_range: float = 255.0) -> Tuple[float, float]:
+    """(psnr, ssim) of a bench_u8 record: 10 log10(R^2 / (sse / n_elems)), inf for sse == 0, and ssim_sum / n_map."""
+    sse = sums["sse"]
+    psnr = float("inf") if sse == 0 else 10.0 * math.log10(float(data_range) * float(data_range) / (sse / sums["n_elems"]))
+    return psnr, sums["ssim_sum"] / sums["n_map"]
+
+
 def psnr_from_sse(sse: int, count: int, data_range: float = 255.0) -> float:
     return float(load().sr_psnr_from_sse(C.c_uint64(sse), C.c_uint64(count), data_range))
 
@@ -754,6 +783,18 @@ class Context:
         check(self.lib.sr_ms_ssim_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
                                      int(cn), int(gray_shift), float(data_range), levels, out))
         return [(out[j].sum_lcs, out[j].sum_cs, int(out[j].count)) for j in range(n)]
+
+    def bench_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, crop_border=0, mode=BENCH_Y, data_range=255.0) -> dict:
+        """sr_bench_u8 -> {'sse', 'ssim_sum', 'n_elems', 'n_map'} of the two images cropped by crop_border (finish with
+        bench_values).  Every argument is checked before the device is touched: ValueError, or its subclass SrShapeError
+        for a short stride or a crop that leaves a side below 11."""
+        crop_border, mode = _whole(crop_border, "crop_border"), _whole(mode, "mode")
+        if not d_a or not d_b:
+            raise ValueError("bench_u8: null image pointer")
+        out = BenchSums()
+        check(self.lib.sr_bench_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
+                                   int(cn), crop_border, mode, float(data_range), C.byref(out)))
+        return {"sse": out.sse, "ssim_sum": out.ssim_sum, "n_elems": int(out.n_elems), "n_map": int(out.n_map)}
 
     def ms_ssim_planes(self, level: int, shape) -> Tuple[np.ndarray, np.ndarray]:
         """sr_ms_ssim_planes: the exact integer sums (uint16, 4^level gray values each) of level `level` that the last

@@ -60,6 +60,8 @@ struct sr_ctx {
     void *msssim_ws = nullptr;                          // MS-SSIM: level planes (x | y << 16 sums), partials, per-level results
     size_t msssim_ws_bytes = 0;
     int msssim_h = 0, msssim_w = 0, msssim_levels = 0;  // what the planes hold (levels == 0: nothing valid)
+    void *bench_ws = nullptr;                           // SR-benchmark PSNR / SSIM: per-block partials
+    size_t bench_ws_bytes = 0;
 };
 
 // Enqueue a small host->device table upload whose source stays alive until the next sync.

@@ -66,6 +66,8 @@ class PipelineConfig:
     qa_map_cell: int = 0       # > 0 (with enable_qa): stage 4 also writes a per-cell quality map of this cell size
     qa_ms_ssim: bool = False   # (with enable_qa): stage 4 also reports the 5-scale MS-SSIM of the canvas against the INTER_CUBIC
                                # resize of the source ('ms_ssim_5scale'; the 'ms_ssim' key keeps the reference's single-scale value)
+    qa_benchmark: bool = False # (with enable_qa): stage 4 also reports the SR-benchmark PSNR / SSIM (Y channel and RGB, a border of
+                               # sr_scale pixels cropped) of the canvas against the INTER_CUBIC resize of the source ('sr_benchmark')
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
                                    # only the canvas comes back for the writer (a custom sr_backend gets host arrays)
     sr_weights: str = ""       # path of an SR network's weights (.npz, or .pth / .pt where torch imports): stage 2 runs the
@@ -204,6 +206,34 @@ class SuperResolutionPipeline:
             ref.free()
         report['ms_ssim_5scale'], report['ms_ssim_5scale_levels'] = float(v), lv
 
+    def _sr_benchmark(self, ctx, report: Dict[str, Any], d_src: int, src_shape, d_canvas: int, canvas_shape) -> None:
+        """Stage 4's optional 'sr_benchmark' entry (qa_benchmark): the PSNR / SSIM convention of the SR literature -- a border
+        of sr_scale pixels cropped, on the BT.601 luma ('psnr_y', 'ssim_y') and on the RGB channels ('psnr_rgb', 'ssim_rgb') --
+        of the canvas against the INTER_CUBIC resize of the source to the canvas size, both in HBM.  A canvas with a side
+        below 11 after the crop has no SSIM window: the four values are None and 'sr_benchmark_note' says why (the run does
+        not fail).  One helper for the device-resident, the host-array and the sharded path."""
+        import _native
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        ih, iw = int(src_shape[0]), int(src_shape[1])
+        cb = int(self.config.sr_scale)
+        out = {'psnr_y': None, 'ssim_y': None, 'psnr_rgb': None, 'ssim_rgb': None, 'crop_border': cb}
+        report['sr_benchmark'] = out
+        try:
+            _native.bench_plan(H, W, cn, cb, _native.BENCH_Y)
+        except ValueError as exc:
+            report['sr_benchmark_note'] = str(exc)
+            return
+        ref = ctx.alloc(H * W * cn)
+        try:
+            ctx.resize_cubic_u8(d_src, iw * cn, ih, iw, cn, ref.ptr, W * cn, H, W)
+            q = self.quality_module
+            y = q.evaluate_sr_benchmark_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn), crop_border=cb, test_y_channel=True)
+            rgb = q.evaluate_sr_benchmark_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn), crop_border=cb, test_y_channel=False)
+        finally:
+            ctx.sync()
+            ref.free()
+        out.update(psnr_y=y['psnr'], ssim_y=y['ssim'], psnr_rgb=rgb['psnr'], ssim_rgb=rgb['ssim'])
+
     def _quality_map(self, ctx, d_src: int, src_shape, d_canvas: int, canvas_shape, tiles: List[Tile],
                      output_path: str) -> Dict[str, Any]:
         """Stage 4's optional 'quality_map' section (qa_map_cell > 0): where the canvas differs from the INTER_CUBIC resize
@@ -330,6 +360,8 @@ class SuperResolutionPipeline:
                     report['quality_map'] = self._quality_map(ctx, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3), tiles, output_path)
                 if self.config.qa_ms_ssim:
                     self._ms_ssim(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
+                if self.config.qa_benchmark:
+                    self._sr_benchmark(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 score = qa.get('overall_score', 0)
             lap("assess")
             # Stage 5: the one download, then the writer
@@ -425,6 +457,8 @@ class SuperResolutionPipeline:
                                                                   tiles, output_path)
                     if self.config.qa_ms_ssim:
                         self._ms_ssim(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
+                    if self.config.qa_benchmark:
+                        self._sr_benchmark(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     score = qa.get('overall_score', 0)
                 fused = qctx.download(canvas.data_ptr(), (H, W, 3), np.uint8)
                 self._write_outputs(fused, output_path, report)
@@ -512,6 +546,13 @@ class SuperResolutionPipeline:
                         self._ms_ssim(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
                     finally:
                         d_src.free(); d_fused.free()
+                if self.config.qa_benchmark:
+                    qctx = self.quality_module._ctx()
+                    d_src, d_fused = qctx.upload(original), qctx.upload(fused)
+                    try:
+                        self._sr_benchmark(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
+                    finally:
+                        d_src.free(); d_fused.free()
                 score = qa.get('overall_score', 0)
             # Stage 5: output
             self._write_outputs(fused, output_path, report)
@@ -551,6 +592,9 @@ async def main() -> int:
     ap.add_argument("--qa-ms-ssim", action="store_true",
                     help="stage 4 also reports Wang's 5-scale MS-SSIM of the result against the bicubic resize of the input "
                          "(report key ms_ssim_5scale)")
+    ap.add_argument("--qa-benchmark", action="store_true",
+                    help="stage 4 also reports the SR-benchmark PSNR / SSIM (Y channel and RGB, a border of --sr-scale pixels "
+                         "cropped) of the result against the bicubic resize of the input (report key sr_benchmark)")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node to use: N > 1 starts one process per GPU (RCCL)")
     ap.add_argument("--deadline-s", type=float, default=1800.0,
                     help="--gpus N: ranks still running after this many seconds are terminated (status 124)")
@@ -571,7 +615,7 @@ async def main() -> int:
         return 2
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act,
-                         qa_ms_ssim=args.qa_ms_ssim)
+                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark)
     if args.plan_only:
         from PIL import Image
         with Image.open(args.input) as im:

@@ -362,6 +362,64 @@ class QualityAssessmentModule:
         return self._ms_ssim_dev(_DevImage(ctx, shape=shape1, ptr=d_img1), _DevImage(ctx, shape=shape2, ptr=d_img2), data_range,
                                  levels, wt, return_levels)
 
+    # -- SR-benchmark PSNR / SSIM (no reference counterpart: BasicSR's calculate_psnr / calculate_ssim convention) -----------
+    @staticmethod
+    def _sr_benchmark_args(shape1, shape2, crop_border, test_y_channel: bool, y_round: bool, data_range: float):
+        """Every refusal of the SR-benchmark methods, on the host: ValueError (SrShapeError for a crop that leaves a side
+        below 11).  -> (h, w, cn, crop_border, mode, channel)."""
+        shape1, shape2 = tuple(int(v) for v in shape1), tuple(int(v) for v in shape2)
+        if shape1 != shape2:
+            raise ValueError(f"evaluate_sr_benchmark: images must have the same shape, got {shape1} vs {shape2} "
+                             "(nothing is cropped to a common rectangle)")
+        if len(shape1) not in (2, 3):
+            raise ValueError(f"evaluate_sr_benchmark: need an H x W or H x W x C image, got shape {shape1}")
+        cn = shape1[2] if len(shape1) == 3 else 1
+        if cn not in (1, 3):
+            raise ValueError("evaluate_sr_benchmark: colour images must have 3 channels (RGB)")
+        if test_y_channel and cn != 3:
+            raise ValueError("evaluate_sr_benchmark: test_y_channel needs a 3-channel RGB image")
+        if y_round and not test_y_channel:
+            raise ValueError("evaluate_sr_benchmark: y_round applies to the Y channel only (test_y_channel=True)")
+        if not (np.isfinite(data_range) and data_range > 0):
+            raise ValueError(f"evaluate_sr_benchmark: data_range must be finite and positive, got {data_range!r}")
+        mode = (_native.BENCH_Y_ROUND if y_round else _native.BENCH_Y) if test_y_channel else _native.BENCH_CHANNELS
+        channel = ("y_round" if y_round else "y") if test_y_channel else ("rgb" if cn == 3 else "gray")
+        _native.bench_plan(shape1[0], shape1[1], cn, crop_border, mode)          # crop_border < 0, a too-small crop
+        return shape1[0], shape1[1], cn, int(crop_border), mode, channel
+
+    @staticmethod
+    def _sr_benchmark_dev(ctx, d1: int, d2: int, args, data_range: float) -> Dict[str, Any]:
+        h, w, cn, cb, mode, channel = args
+        sums = ctx.bench_u8(d1, w * cn, d2, w * cn, h, w, cn, crop_border=cb, mode=mode, data_range=float(data_range))
+        psnr, ssim = _native.bench_values(sums, data_range)
+        return {"psnr": psnr, "ssim": ssim, "crop_border": cb, "channel": channel}
+
+    def evaluate_sr_benchmark(self, img1: np.ndarray, img2: np.ndarray, crop_border: int = 0, test_y_channel: bool = True,
+                              y_round: bool = False, data_range: float = 255.0) -> Dict[str, Any]:
+        """The PSNR and SSIM the SR papers and model cards quote (BasicSR's calculate_psnr / calculate_ssim with crop_border
+        and test_y_channel), as include/sr_hip.h defines them: both u8 images cropped by crop_border on every side, then on
+        the BT.601 luma Y carried exactly (test_y_channel; y_round: MATLAB's rounded u8 luma instead) or on the channels as
+        they are; Gaussian-11 SSIM over the valid region, the mean over all planes.  -> {'psnr', 'ssim', 'crop_border',
+        'channel'} with channel in 'y', 'y_round', 'rgb', 'gray'.  u8 images of equal shape only: another shape is a
+        ValueError (nothing is cropped to a common rectangle), as is a crop that leaves a side below 11."""
+        a = self._require_u8(np.asarray(img1), "evaluate_sr_benchmark")
+        b = self._require_u8(np.asarray(img2), "evaluate_sr_benchmark")
+        args = self._sr_benchmark_args(a.shape, b.shape, crop_border, test_y_channel, y_round, data_range)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._sr_benchmark_dev(ctx, da.ptr, db.ptr, args, data_range)
+        finally:
+            da.free(); db.free()
+
+    def evaluate_sr_benchmark_device(self, d_img1: int, shape1, d_img2: int, shape2, crop_border: int = 0,
+                                     test_y_channel: bool = True, y_round: bool = False, data_range: float = 255.0) -> Dict[str, Any]:
+        """evaluate_sr_benchmark on two dense u8 images that already live in HBM (device addresses + shapes)."""
+        args = self._sr_benchmark_args(shape1, shape2, crop_border, test_y_channel, y_round, data_range)
+        if not d_img1 or not d_img2:
+            raise ValueError("evaluate_sr_benchmark: null device pointer")
+        return self._sr_benchmark_dev(self._ctx(), int(d_img1), int(d_img2), args, data_range)
+
     def _calculate_ssim_simple(self, img1: np.ndarray, img2: np.ndarray) -> float:
         """quality_assessment_module.py:391-417 on already-gray u8 images."""
         a = self._require_u8(np.asarray(img1), "_calculate_ssim_simple")
