@@ -829,6 +829,56 @@ SR_API int sr_rrdb_u8(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_st
 SR_API int sr_rrdb_f32(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
                        int64_t dst_stride, int tile, int tail);
 
+/* ---- geometric self-ensemble of the local SR backends (csrc/sr_ensemble.hip) ------------------------------------------------
+ * The "+" results of the SR literature (EDSR+, RCAN+: Timofte et al., Lim et al.): the network runs on the eight flips and
+ * rotations of the input, each output is mapped back and the eight are averaged.  No new weights; the forwards are the
+ * families' own, unchanged.
+ * The eight transforms: for k = 0 .. 7, on an H x W x C image, T_k(x) applies in this order
+ *     1. if k & 1, a horizontal flip   x[:, ::-1]
+ *     2. if k & 2, a vertical flip     x[::-1]
+ *     3. if k & 4, a transpose of the two spatial axes (the result is W x H x C)
+ * and T_k^-1 undoes the three steps in reverse order.  The T_k are the dihedral group D4; T_0 is the identity.
+ * The members: mask has bits 0 .. 7, 1 <= mask <= 255, bit k = member k in use; n = the number of set bits.
+ * The output: with f the family's existing forward (the value sr_<kind>_f32 stores) and y_k = T_k^-1(f(T_k(x))),
+ *     s = y_k1;  s = s + y_k2;  ...  (members ascending, every + one IEEE fp32 addition per element)
+ *     o = s / (float)n               (a correctly rounded fp32 division, never a reciprocal multiply)
+ * *_f32 stores o as HWC fp32 unclamped, *_u8 stores rintf(fminf(fmaxf(o, 0), 1) * 255), the forwards' rule.  So mask 1 gives
+ * the plain forward bit for bit, a one-bit mask gives y_k itself, and -- the forwards not depending on the sub-tile -- no
+ * result depends on tile / tail.
+ * sr_d4_u8: d_dst = T_k(d_src), d_src h x w x 3 u8, d_dst w x h x 3 for k & 4; the two must not overlap.
+ * sr_d4_acc_f32: d_acc (H x W x 3 fp32) = T_k^-1(d_y) if first, else d_acc + T_k^-1(d_y); d_y is H x W, or W x H for k & 4.
+ * sr_ens_finish_f32 / _u8: d_dst = d_acc / n by the two store rules; n in 1 .. 8.
+ * sr_ens_plan (host only, no context, no GPU): *n_members = n; *workspace_bytes = what an ensemble call holds: the
+ * accumulator (h scale rows of w scale x 12 bytes), one forward output (the same, and w scale rows of h scale x 12 bytes when
+ * a member k >= 4 is in use: the larger) and the transformed u8 input (h rows of 3 w bytes for a member 1 .. 3, w rows of 3 h
+ * for a member k >= 4: the larger; nothing for mask 1) -- every row stride rounded up to 16 bytes, every section to 256.
+ * Outputs may be NULL.  Refuses an output size beyond int (for k >= 4: of the transposed image too), as the forwards do.
+ * sr_<kind>_ens_u8 / _f32: the plain form's arguments, then mask.  The workspace belongs to the model, is grown on demand and
+ * is freed with it, like the activation buffers.  Everything runs on the model's stream.  Asynchronous.
+ * Refusals, all before any launch: SR_ERR_INVALID_ARG for a null pointer, k outside 0 .. 7, a mask outside 1 .. 255, n
+ * outside 1 .. 8, a scale < 1, overlapping buffers, an fp32 pointer that is not a multiple of 4; SR_ERR_SHAPE for a side below
+ * 1, a stride shorter than a row, an fp32 stride that is not a multiple of 4, a size beyond int.  Strides in bytes. */
+SR_API int sr_d4_u8(sr_ctx *ctx, const uint8_t *d_src, int64_t src_stride, int h, int w, int k, uint8_t *d_dst, int64_t dst_stride);
+SR_API int sr_d4_acc_f32(sr_ctx *ctx, const float *d_y, int64_t y_stride, int H, int W, int k, int first, float *d_acc,
+                         int64_t acc_stride);
+SR_API int sr_ens_finish_f32(sr_ctx *ctx, const float *d_acc, int64_t acc_stride, int H, int W, int n, float *d_dst,
+                             int64_t dst_stride);
+SR_API int sr_ens_finish_u8(sr_ctx *ctx, const float *d_acc, int64_t acc_stride, int H, int W, int n, uint8_t *d_dst,
+                            int64_t dst_stride);
+SR_API int sr_ens_plan(int h, int w, int scale, int mask, int *n_members, size_t *workspace_bytes);
+SR_API int sr_srnet_ens_u8(sr_srnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                           int64_t dst_stride, int tile, int mask);
+SR_API int sr_srnet_ens_f32(sr_srnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                            int64_t dst_stride, int tile, int mask);
+SR_API int sr_resnet_ens_u8(sr_resnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                            int64_t dst_stride, int tile, int mask);
+SR_API int sr_resnet_ens_f32(sr_resnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                             int64_t dst_stride, int tile, int mask);
+SR_API int sr_rrdb_ens_u8(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                          int64_t dst_stride, int tile, int tail, int mask);
+SR_API int sr_rrdb_ens_f32(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                           int64_t dst_stride, int tile, int tail, int mask);
+
 #ifdef __cplusplus
 }
 #endif

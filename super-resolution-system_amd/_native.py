@@ -240,6 +240,17 @@ SIGNATURES = {
     "sr_rrdb_plan": (_i, [C.POINTER(RrdbDesc), _i, _i, _i, _i, _pi, _pi, _pi, C.POINTER(_sz)]),
     "sr_rrdb_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
     "sr_rrdb_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_d4_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
+    "sr_d4_acc_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i64]),
+    "sr_ens_finish_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
+    "sr_ens_finish_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
+    "sr_ens_plan": (_i, [_i, _i, _i, _i, _pi, C.POINTER(_sz)]),
+    "sr_srnet_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_srnet_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_resnet_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_resnet_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_rrdb_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i, _i]),
+    "sr_rrdb_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i, _i]),
 }
 
 
@@ -1365,6 +1376,36 @@ def srnet_plan(h: int, w: int, n_feat: int, n_body: int, scale: int, tile: int =
     return halo.value, n.value, int(ws.value)
 
 
+def ens_plan(h: int, w: int, scale: int, mask: int) -> Tuple[int, int]:
+    """sr_ens_plan (host only) -> (members, workspace bytes) of a self-ensemble of an h x w input at ``scale`` over ``mask``."""
+    n, ws = C.c_int(0), C.c_size_t(0)
+    check(load().sr_ens_plan(_whole(h, "h"), _whole(w, "w"), _whole(scale, "scale"), _whole(mask, "mask"), C.byref(n), C.byref(ws)))
+    return n.value, int(ws.value)
+
+
+def _ctx_handle(ctx):
+    return ctx.handle if ctx is not None else None
+
+
+def d4_u8(ctx, d_src: int, src_stride: int, h: int, w: int, k: int, d_dst: int, dst_stride: int) -> None:
+    """sr_d4_u8: d_dst = T_k(d_src), h x w x 3 u8 (w x h x 3 out for k & 4).  Arguments are refused before the context is
+    looked at, so ``ctx`` may be None where only the refusal matters.  Asynchronous."""
+    check(load().sr_d4_u8(_ctx_handle(ctx), C.c_void_p(d_src), int(src_stride), int(h), int(w), _whole(k, "k"), C.c_void_p(d_dst),
+                          int(dst_stride)))
+
+
+def d4_acc_f32(ctx, d_y: int, y_stride: int, H: int, W: int, k: int, first: bool, d_acc: int, acc_stride: int) -> None:
+    """sr_d4_acc_f32: d_acc (H x W x 3 fp32) = T_k^-1(d_y) if ``first`` else d_acc + T_k^-1(d_y).  Asynchronous."""
+    check(load().sr_d4_acc_f32(_ctx_handle(ctx), C.c_void_p(d_y), int(y_stride), int(H), int(W), _whole(k, "k"), int(bool(first)),
+                               C.c_void_p(d_acc), int(acc_stride)))
+
+
+def ens_finish(ctx, d_acc: int, acc_stride: int, H: int, W: int, n: int, d_dst: int, dst_stride: int, u8: bool) -> None:
+    """sr_ens_finish_u8 / sr_ens_finish_f32: d_dst = d_acc / n, as u8 by the forwards' rule or as fp32.  Asynchronous."""
+    fn = load().sr_ens_finish_u8 if u8 else load().sr_ens_finish_f32
+    check(fn(_ctx_handle(ctx), C.c_void_p(d_acc), int(acc_stride), int(H), int(W), _whole(n, "n"), C.c_void_p(d_dst), int(dst_stride)))
+
+
 class _SrModel:
     """What SrNetModel, ResNetModel and RrdbModel share: the caller's tables as checked fp32 arrays, the create call, the two
     forwards, close.  ``_kind`` names the sr_<kind>_* entry points, ``_run_args`` what their forwards take after the
@@ -1390,11 +1431,11 @@ class _SrModel:
         _check_unsupported(create(ctx.handle, *args, *ptrs, *([len(tables[0])] if count else []), C.byref(h)))
         self.ctx, self.handle = ctx, h
 
-    def _run(self, entry: str, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, args, named):
+    def _run(self, entry: str, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, args, named, last=()):
         names = self._run_args
         if len(args) > len(names) or not set(named) <= set(names[len(args):]):
             raise TypeError(f"sr_{self._kind}_{entry} takes {', '.join(names)} after the strides, got {args} {named}")
-        ints = [int(v) for v in args] + [int(named.get(n, 0)) for n in names[len(args):]]
+        ints = [int(v) for v in args] + [int(named.get(n, 0)) for n in names[len(args):]] + [int(v) for v in last]
         check(getattr(self.ctx.lib, f"sr_{self._kind}_{entry}")(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w),
                                                                 C.c_void_p(d_dst), int(dst_stride), *ints))
 
@@ -1406,6 +1447,15 @@ class _SrModel:
     def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, *args, **named):
         """sr_<kind>_f32: the unclamped fp32 output (HWC, stride in bytes); arguments as upscale_u8.  Asynchronous."""
         self._run("f32", d_src, src_stride, h, w, d_dst, dst_stride, args, named)
+
+    def ensemble_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, *args, mask: int, **named):
+        """sr_<kind>_ens_u8: the geometric self-ensemble over the members of ``mask`` (bit k: the transform T_k of
+        include/sr_hip.h; 1 .. 255), u8 out; the other arguments as upscale_u8.  Asynchronous."""
+        self._run("ens_u8", d_src, src_stride, h, w, d_dst, dst_stride, args, named, last=(_whole(mask, "mask"),))
+
+    def ensemble_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, *args, mask: int, **named):
+        """sr_<kind>_ens_f32: the ensemble's unclamped fp32 output; arguments as ensemble_u8.  Asynchronous."""
+        self._run("ens_f32", d_src, src_stride, h, w, d_dst, dst_stride, args, named, last=(_whole(mask, "mask"),))
 
     def close(self):
         if getattr(self, "handle", None):

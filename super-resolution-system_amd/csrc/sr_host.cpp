@@ -466,3 +466,46 @@ void sr_plan_windows(int tile_h, int tile_w, int tile_y, int levels, int row_beg
     L.gw[L.nl - 1] = L.rw[L.nl - 1];
     for (int i = L.nl - 2; i >= 0; --i) L.gw[i] = hull(L.rw[i], need_down(L.gw[i + 1], L.H[i]));
 }
+
+// ---- geometric self-ensemble: members and workspace (sr_ensemble.hip runs what is planned here) ------------------------------
+int sr_ens_check_mask(const char *who, int mask)
+{
+    if (mask < 1 || mask > 255) return sr_set_error(SR_ERR_INVALID_ARG, "%s: mask %d is outside 1..255", who, mask);
+    return SR_OK;
+}
+
+int sr_ens_layout(const char *who, int h, int w, int scale, int mask, SrEnsLayout *out)
+{
+    int rc = sr_ens_check_mask(who, mask);
+    if (rc) return rc;
+    if (scale < 1) return sr_set_error(SR_ERR_INVALID_ARG, "%s: scale %d", who, scale);
+    if (h < 1 || w < 1) return sr_set_error(SR_ERR_SHAPE, "%s: %dx%d image", who, w, h);
+    const bool plain = (mask & 0x0F) != 0, transposing = (mask & 0xF0) != 0;
+    const long long H = (long long)h * scale, W = (long long)w * scale;
+    // a forward sees h x w and, for a transposing member, w x h: both outputs must fit the forwards' int sizes
+    if (H > INT32_MAX || W * 3 > INT32_MAX || (transposing && (W > INT32_MAX || H * 3 > INT32_MAX)))
+        return sr_set_error(SR_ERR_SHAPE, "%s: a %dx%d output (x%d) overflows int", who, w, h, scale);
+    SrEnsLayout L;
+    for (int k = 0; k < 8; ++k)
+        if (mask >> k & 1) L.members[L.n++] = k;
+    auto sect = [](long long rows, long long row_bytes) { return (size_t)((rows * sr_ens_row_stride(row_bytes) + 255) / 256 * 256); };
+    const size_t acc = sect(H, W * 12);
+    const size_t y = std::max(plain ? sect(H, W * 12) : 0, transposing ? sect(W, H * 12) : 0);
+    const size_t in = std::max((mask & 0x0E) ? sect(h, (long long)w * 3) : 0, transposing ? sect(w, (long long)h * 3) : 0);
+    L.acc_off = 0;
+    L.y_off = acc;
+    L.in_off = acc + y;
+    L.total = acc + y + in;
+    if (out) *out = L;
+    return SR_OK;
+}
+
+extern "C" int sr_ens_plan(int h, int w, int scale, int mask, int *n_members, size_t *workspace_bytes)
+{
+    SrEnsLayout L;
+    const int rc = sr_ens_layout("sr_ens_plan", h, w, scale, mask, &L);
+    if (rc) return rc;
+    if (n_members) *n_members = L.n;
+    if (workspace_bytes) *workspace_bytes = L.total;
+    return SR_OK;
+}

@@ -28,3 +28,18 @@ struct SrTileLevels {
 void sr_level_dims(int h, int w, int levels, int *nl, int *H, int *W);
 void sr_plan_windows(int tile_h, int tile_w, int tile_y, int levels, int row_begin, int row_end,
                      int canvas_h, SrTileLevels *out);
+
+// Geometric self-ensemble (sr_host.cpp plans, sr_ensemble.hip runs): members of a mask and the workspace of one call.  The
+// workspace is one allocation of three sections, each starting at a multiple of 256 bytes: the accumulator (H x W x 3 fp32,
+// H = h scale, W = w scale), one forward output (H x W, and W x H when a transposing member is in use) and the transformed u8
+// input (h x w and / or w x h; absent when member 0 is the only one).  A row of r bytes has a stride of r rounded up to 16.
+struct SrEnsLayout {
+    int n = 0;                        // members in use
+    int members[8] = {0};             // ascending
+    size_t acc_off = 0, y_off = 0, in_off = 0, total = 0;
+};
+inline long long sr_ens_row_stride(long long row_bytes) { return (row_bytes + 15) / 16 * 16; }
+// SR_ERR_INVALID_ARG for a mask outside 1..255.
+int sr_ens_check_mask(const char *who, int mask);
+// Every host-side refusal of sr_ens_plan; who names the caller in the message.
+int sr_ens_layout(const char *who, int h, int w, int scale, int mask, SrEnsLayout *out);

@@ -8,6 +8,7 @@
 #pragma once
 #include <algorithm>
 #include <climits>
+#include <functional>
 
 #include "sr_conv_mfma.h"
 
@@ -119,7 +120,15 @@ inline int check_sr_geometry(const char *who, int h, int w, int scale, bool nega
 struct SrModelBase {
     sr_ctx *ctx = nullptr;
     std::vector<float *> d_w, d_b;            // per convolution
+    float *ens_ws[1] = {nullptr};             // workspace of the geometric self-ensemble (sr_ensemble.hip), grown on demand
+    size_t ens_floats = 0;
 };
+
+// The geometric self-ensemble over one family's forward (sr_ensemble.hip; the definition is in include/sr_hip.h).
+// fwd(d_src, src_stride, h, w, d_dst, dst_stride) is the family's fp32 forward with its own tile arguments bound; m is live.
+using EnsForward = std::function<int(const uint8_t *, int64_t, int, int, float *, int64_t)>;
+int ens_run(const char *who, SrModelBase &m, int scale, const EnsForward &fwd, const uint8_t *d_src, int64_t src_stride, int h, int w,
+            void *d_dst, int64_t dst_stride, int mask, bool u8);
 
 // The caller's tables of a *_create: n entries each, given as n_given; the first n_s entries of the optional third table too.
 inline int check_weight_tables(const char *who, const char *what, int n, int n_given, const float *const *h_w, const float *const *h_b,
@@ -154,6 +163,7 @@ inline int destroy_model(Model *m, LiveSet &live, Extra &&extra)
         for (auto p : m->d_w) if (p) (void)hipFree(p);
         for (auto p : m->d_b) if (p) (void)hipFree(p);
         for (float *p : extra(*m)) if (p) (void)hipFree(p);
+        if (m->ens_ws[0]) (void)hipFree(m->ens_ws[0]);
     }
     delete m;
     return SR_OK;

@@ -413,6 +413,19 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
     return SR_OK;
 }
 
+// The self-ensemble over rn_forward (driver: sr_ensemble.hip).
+static int rn_ensemble(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride, int tile,
+                       int mask, bool u8, const char *who)
+{
+    const int rc = sr_ens_check_mask(who, mask);
+    if (rc) return rc;
+    if (tile < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: %s must be >= 1, or 0 for the library's choice", who, "tile");
+    if (!g_rn_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
+    return ens_run(who, *m, m->d.scale, [&](const uint8_t *s, int64_t ss, int hh, int ww, float *d, int64_t ds) {
+        return rn_forward(m, s, ss, hh, ww, d, ds, tile, false, who);
+    }, d_src, src_stride, h, w, d_dst, dst_stride, mask, u8);
+}
+
 extern "C" {
 
 int sr_resnet_create(sr_ctx *ctx, const sr_resnet_desc *desc, const float *const *h_w, const float *const *h_b, int n_conv,
@@ -473,6 +486,18 @@ int sr_resnet_f32(sr_resnet_model *model, const uint8_t *d_src, int64_t src_stri
                   int tile)
 {
     return rn_forward(model, d_src, src_stride, h, w, d_dst, dst_stride, tile, false, "sr_resnet_f32");
+}
+
+int sr_resnet_ens_u8(sr_resnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst, int64_t dst_stride,
+                     int tile, int mask)
+{
+    return rn_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tile, mask, true, "sr_resnet_ens_u8");
+}
+
+int sr_resnet_ens_f32(sr_resnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst, int64_t dst_stride,
+                      int tile, int mask)
+{
+    return rn_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tile, mask, false, "sr_resnet_ens_f32");
 }
 
 }  // extern "C"

@@ -420,6 +420,19 @@ static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride
     return SR_OK;
 }
 
+// The self-ensemble over rr_forward (driver: sr_ensemble.hip).
+static int rr_ensemble(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride, int tile,
+                       int tail, int mask, bool u8, const char *who)
+{
+    const int rc = sr_ens_check_mask(who, mask);
+    if (rc) return rc;
+    if (tile < 0 || tail < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: %s must be >= 1, or 0 for the library's choice", who, "tile and tail");
+    if (!g_rr_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
+    return ens_run(who, *m, 4, [&](const uint8_t *s, int64_t ss, int hh, int ww, float *d, int64_t ds) {
+        return rr_forward(m, s, ss, hh, ww, d, ds, tile, tail, false, who);
+    }, d_src, src_stride, h, w, d_dst, dst_stride, mask, u8);
+}
+
 extern "C" {
 
 int sr_rrdb_create(sr_ctx *ctx, const sr_rrdb_desc *desc, const float *const *h_w, const float *const *h_b, int n_conv, sr_rrdb_model **out)
@@ -489,6 +502,18 @@ int sr_rrdb_f32(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, 
                 int tail)
 {
     return rr_forward(model, d_src, src_stride, h, w, d_dst, dst_stride, tile, tail, false, "sr_rrdb_f32");
+}
+
+int sr_rrdb_ens_u8(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst, int64_t dst_stride, int tile,
+                   int tail, int mask)
+{
+    return rr_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tile, tail, mask, true, "sr_rrdb_ens_u8");
+}
+
+int sr_rrdb_ens_f32(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst, int64_t dst_stride, int tile,
+                    int tail, int mask)
+{
+    return rr_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tile, tail, mask, false, "sr_rrdb_ens_f32");
 }
 
 }  // extern "C"

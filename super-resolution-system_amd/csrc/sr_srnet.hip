@@ -232,6 +232,19 @@ static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_strid
     return SR_OK;
 }
 
+// The self-ensemble over sn_forward (driver: sr_ensemble.hip).
+static int sn_ensemble(sr_srnet_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride, int tile,
+                       int mask, bool u8, const char *who)
+{
+    const int rc = sr_ens_check_mask(who, mask);
+    if (rc) return rc;
+    if (tile < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: %s must be >= 1, or 0 for the library's choice", who, "tile");
+    if (!g_sn_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
+    return ens_run(who, *m, m->S, [&](const uint8_t *s, int64_t ss, int hh, int ww, float *d, int64_t ds) {
+        return sn_forward(m, s, ss, hh, ww, d, ds, tile, false, who);
+    }, d_src, src_stride, h, w, d_dst, dst_stride, mask, u8);
+}
+
 extern "C" {
 
 int sr_srnet_create(sr_ctx *ctx, int n_feat, int n_body, int scale, const float *const *h_w, const float *const *h_b,
@@ -297,6 +310,18 @@ int sr_srnet_f32(sr_srnet_model *model, const uint8_t *d_src, int64_t src_stride
                  int tile)
 {
     return sn_forward(model, d_src, src_stride, h, w, d_dst, dst_stride, tile, false, "sr_srnet_f32");
+}
+
+int sr_srnet_ens_u8(sr_srnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst, int64_t dst_stride,
+                    int tile, int mask)
+{
+    return sn_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tile, mask, true, "sr_srnet_ens_u8");
+}
+
+int sr_srnet_ens_f32(sr_srnet_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst, int64_t dst_stride,
+                     int tile, int mask)
+{
+    return sn_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tile, mask, false, "sr_srnet_ens_f32");
 }
 
 }  // extern "C"

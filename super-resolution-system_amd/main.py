@@ -75,6 +75,8 @@ class PipelineConfig:
                                # device-resident too
     sr_act: str = "prelu"      # activation of a compact network whose weights hold no PReLU slopes: 'relu' or 'leakyrelu'
                                # (ignored for the residual family)
+    sr_ensemble: int = 1       # (with sr_weights) geometric self-ensemble of the network: 1 off, 2 identity + horizontal flip, 4 the
+                               # four flips, 8 all eight flips / rotations, averaged on the device (the "+" results of SR papers)
 
 
 @dataclass
@@ -100,7 +102,7 @@ def bicubic_stub_backend(pipeline: "SuperResolutionPipeline", tile: Tile, prompt
 
 def compact_net_backend(pipeline: "SuperResolutionPipeline", tile: Tile, prompt: str) -> Optional[np.ndarray]:
     """Local SR: the compact network of PipelineConfig.sr_weights on the padded tile (host array in, host array out)."""
-    return pipeline.sr_net.upscale(np.ascontiguousarray(tile.data))
+    return pipeline.sr_net.upscale(np.ascontiguousarray(tile.data), ensemble=pipeline.config.sr_ensemble)
 
 
 class SuperResolutionPipeline:
@@ -114,6 +116,11 @@ class SuperResolutionPipeline:
         self.blending_module = BlendingModule(method=config.blend_method, num_levels=config.num_pyramid_levels)
         self.quality_module = QualityAssessmentModule(device=config.qa_device)
         self.sr_net = None
+        if config.sr_ensemble != 1:
+            from sr_network import ensemble_mask
+            ensemble_mask(config.sr_ensemble)                                                # ValueError outside {1, 2, 4, 8}
+            if not config.sr_weights:
+                raise ValueError("sr_ensemble needs sr_weights: the bicubic stub has nothing to ensemble")
         if config.sr_weights and sr_backend is None:
             from sr_network import load_network
             self.sr_net = load_network(config.sr_weights, act=config.sr_act)                 # host work: no device call yet
@@ -152,7 +159,7 @@ class SuperResolutionPipeline:
         """Stage 2 for one block x block x 3 tile, HBM -> HBM, on ctx's stream: the network, or the bicubic stand-in."""
         out_block = block * self.config.sr_scale
         if self.sr_net is not None:
-            self.sr_net.upscale_device(d_src, (block, block, 3), d_dst, dst_stride, ctx=ctx)
+            self.sr_net.upscale_device(d_src, (block, block, 3), d_dst, dst_stride, ctx=ctx, ensemble=self.config.sr_ensemble)
         else:
             ctx.resize_cubic_u8(d_src, block * 3, block, block, 3, d_dst, dst_stride, out_block, out_block)
 
@@ -589,6 +596,9 @@ async def main() -> int:
                     help="weights of an SR network (.npz / .pth: compact, MSRResNet / EDSR, or RRDBNet x4 with --sr-scale 4): stage 2 runs it "
                          "instead of the bicubic stub")
     ap.add_argument("--sr-act", default="prelu", metavar="NAME", help="prelu (slopes in the weights), relu or leakyrelu")
+    ap.add_argument("--sr-ensemble", type=int, choices=(1, 2, 4, 8), default=1,
+                    help="with --sr-weights: geometric self-ensemble of the network over 2 (identity + horizontal flip), 4 (the four "
+                         "flips) or 8 (all flips and rotations) members, averaged on the GPU; 1 = off")
     ap.add_argument("--qa-ms-ssim", action="store_true",
                     help="stage 4 also reports Wang's 5-scale MS-SSIM of the result against the bicubic resize of the input "
                          "(report key ms_ssim_5scale)")
@@ -614,7 +624,7 @@ async def main() -> int:
         print(f"main.py: launched with WORLD_SIZE={world} but --gpus {args.gpus}", file=sys.stderr)
         return 2
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
-    cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act,
+    cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act, sr_ensemble=args.sr_ensemble,
                          qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark)
     if args.plan_only:
         from PIL import Image

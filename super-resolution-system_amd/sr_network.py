@@ -99,6 +99,17 @@ def load_state(path: str) -> Mapping:
         return {k: np.asarray(z[k]) for k in z.files}
 
 
+ENSEMBLE_MASKS = {1: 0x01, 2: 0x03, 4: 0x0F, 8: 0xFF}            # members of the geometric self-ensemble (include/sr_hip.h)
+
+
+def ensemble_mask(ensemble) -> int:
+    """``ensemble`` (1: off, 2: identity + horizontal flip, 4: the four flips, 8: all of D4) -> the mask of sr_<kind>_ens_*.
+    Anything else is a ValueError."""
+    if isinstance(ensemble, (bool, np.bool_)) or not isinstance(ensemble, (int, np.integer)) or int(ensemble) not in ENSEMBLE_MASKS:
+        raise ValueError(f"ensemble must be one of {sorted(ENSEMBLE_MASKS)}, got {ensemble!r}")
+    return ENSEMBLE_MASKS[int(ensemble)]
+
+
 class CompactSRNet:
     """The compact SR network on the GPU.  ``state``: mapping of ``body.{i}.weight`` / ``body.{i}.bias`` arrays."""
 
@@ -129,14 +140,20 @@ class CompactSRNet:
         return int(shape[0]), int(shape[1])
 
     def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
-                       ctx: Optional["_native.Context"] = None, **run):
+                       ctx: Optional["_native.Context"] = None, ensemble: int = 1, **run):
         """h x w x 3 u8 at d_src (dense unless src_stride is given) -> (h s) x (w s) x 3 u8 at d_dst, HBM -> HBM.
-        Asynchronous on the context's stream.  ``run``: what the family's forward takes beside ``tile`` (RRDBSRNet: ``tail``)."""
+        Asynchronous on the context's stream.  ``run``: what the family's forward takes beside ``tile`` (RRDBSRNet: ``tail``).
+        ``ensemble``: 1 (the plain forward), or 2 / 4 / 8 members of the geometric self-ensemble (ensemble_mask)."""
+        mask = ensemble_mask(ensemble)
         h, w = self._check_image_shape(shape)
-        self.model(ctx).upscale_u8(d_src, w * 3 if src_stride is None else src_stride, h, w, d_dst, dst_stride, tile, **run)
+        if mask == 1:
+            self.model(ctx).upscale_u8(d_src, w * 3 if src_stride is None else src_stride, h, w, d_dst, dst_stride, tile, **run)
+        else:
+            self.model(ctx).ensemble_u8(d_src, w * 3 if src_stride is None else src_stride, h, w, d_dst, dst_stride, tile, mask=mask, **run)
 
-    def upscale(self, image: np.ndarray, tile: int = 0, **run) -> np.ndarray:
+    def upscale(self, image: np.ndarray, tile: int = 0, ensemble: int = 1, **run) -> np.ndarray:
         """Host array in, host array out."""
+        ensemble_mask(ensemble)
         image = np.asarray(image)
         h, w = self._check_image_shape(image.shape)
         if image.dtype != np.uint8:
@@ -146,7 +163,7 @@ class CompactSRNet:
         d_src, d_dst = ctx.upload(image), None
         try:
             d_dst = ctx.alloc(h * s * w * s * 3)
-            self.upscale_device(d_src.ptr, (h, w, 3), d_dst.ptr, w * s * 3, tile=tile, ctx=ctx, **run)
+            self.upscale_device(d_src.ptr, (h, w, 3), d_dst.ptr, w * s * 3, tile=tile, ctx=ctx, ensemble=ensemble, **run)
             return ctx.download(d_dst.ptr, (h * s, w * s, 3), np.uint8)
         finally:
             ctx.sync()

@@ -92,6 +92,27 @@ int main(int argc, char **argv)
         }
     }
     for (int l = 1; l <= MAX_LEVELS; ++l) { int b, a; CHECK(sr_pyramid_halo(l, &b, &a) == SR_OK && b >= 0 && a >= 0); }
+    // ---- self-ensemble planner -------------------------------------------------------------------------------------
+    for (int it = 0; it < 400; ++it) {
+        const int h = rint_(-1, 5000), w = rint_(-1, 5000), scale = rint_(0, 5), mask = rint_(-2, 258);
+        int n = -1;
+        size_t ws = 0;
+        const int rc = sr_ens_plan(h, w, scale, mask, &n, &ws);
+        const bool good = h >= 1 && w >= 1 && scale >= 1 && mask >= 1 && mask <= 255;
+        CHECK((rc == SR_OK) == good);
+        if (good) CHECK(n == __builtin_popcount((unsigned)mask) && ws >= (size_t)2 * h * scale * w * scale * 12);
+        CHECK(sr_ens_plan(h, w, scale, mask, nullptr, nullptr) == rc);
+        ++calls;
+    }
+    {   // the sizes where the arithmetic is widest: the largest outputs that fit int, and the first that do not
+        size_t ws = 0;
+        CHECK(sr_ens_plan(536870911, 1, 4, 0x0F, nullptr, &ws) == SR_OK && ws > ((size_t)1 << 34));
+        CHECK(sr_ens_plan(536870911, 1, 4, 0x1F, nullptr, &ws) == SR_ERR_SHAPE);
+        CHECK(sr_ens_plan(1, 178956970, 4, 0xFF, nullptr, &ws) == SR_OK);
+        CHECK(sr_ens_plan(1, 178956971, 4, 0x01, nullptr, &ws) == SR_ERR_SHAPE);
+        CHECK(sr_ens_plan(2147483647, 2147483647, 1, 0xFF, nullptr, &ws) == SR_ERR_SHAPE);
+        CHECK(sr_ens_plan(715827882, 715827882, 1, 0xFF, nullptr, &ws) == SR_OK);
+    }
     // ---- encoders --------------------------------------------------------------------------------------------------
     const int sizes[][2] = {{1, 1}, {1, 17}, {17, 1}, {7, 9}, {16, 16}, {33, 65}, {257, 131}, {600, 811}};
     for (auto &sz : sizes)
