@@ -68,6 +68,8 @@ SR_API int sr_ctx_create(int device_id, sr_ctx **out);
 SR_API int sr_ctx_create_on_stream(int device_id, void *hip_stream, sr_ctx **out);
 SR_API int sr_ctx_destroy(sr_ctx *ctx);
 SR_API int sr_ctx_sync(sr_ctx *ctx);
+/* compute units of the context's device: what the launch-shape rules (the march's segment length among them) are sized by */
+SR_API int sr_ctx_num_cu(sr_ctx *ctx, int *num_cu);
 
 /* device memory helpers, so a host language needs no HIP binding of its own */
 SR_API int sr_dev_alloc(sr_ctx *ctx, size_t bytes, void **d_ptr);
@@ -238,6 +240,13 @@ SR_API int sr_blend_plan_workspace_bytes(const sr_blend_plan *plan, size_t *byte
  * *fmt = 0 fp32, 1 the exact 16-bit integers 256 * G_1 (three-channel u8 tiles whose levels 1 and 2 all come from the fused
  * down march; SR_G1_U16=0 at plan creation selects fp32).  The canvases are the same bits either way. */
 SR_API int sr_blend_plan_g1_format(const sr_blend_plan *plan, int dtype, int *fmt);
+/* host only: the work lists of the marched canvas gather as the plan launches them (empty where the plan does not march).
+ * nt = 1 .. 4: the items of the `nt`-tile list in launch order, 8 ints each: x0 (canvas x of the left halo cell, a multiple
+ * of 4), y0 (first canvas row), ncell (useful cells of 4 pixels: lanes 1 .. ncell), nstep (steps of two canvas rows), tile[4]
+ * (the zone's tiles in list order, the first nt valid).  nt = 0: the rectangles that finish what the marched zones leave,
+ * 4 ints each: x, y (canvas pixel of the first cell), w, h (cells of 4 x 2 pixels across / down).
+ * *count receives the number of items; out (nullable: count only) receives at most `cap` of them. */
+SR_API int sr_blend_plan_march_items(const sr_blend_plan *plan, int nt, int32_t *out, int64_t cap, int64_t *count);
 
 /* h_d_tiles[i]: device address of row 0 of tile i (rows outside sr_blend_plan_tile_rows are
  * never touched, so the address may be virtual); h_strides[i]: row stride in bytes.

@@ -117,6 +117,7 @@ SIGNATURES = {
     "sr_ctx_create_on_stream": (_i, [_i, _vp, C.POINTER(_vp)]),
     "sr_ctx_destroy": (_i, [_vp]),
     "sr_ctx_sync": (_i, [_vp]),
+    "sr_ctx_num_cu": (_i, [_vp, _pi]),
     "sr_dev_alloc": (_i, [_vp, _sz, C.POINTER(_vp)]),
     "sr_dev_free": (_i, [_vp, _vp]),
     "sr_memcpy_h2d": (_i, [_vp, _vp, _vp, _sz]),
@@ -162,6 +163,7 @@ SIGNATURES = {
     "sr_blend_plan_tile_rows": (_i, [_vp, _i, _pi, _pi]),
     "sr_blend_plan_workspace_bytes": (_i, [_vp, C.POINTER(_sz)]),
     "sr_blend_plan_g1_format": (_i, [_vp, _i, C.POINTER(_i)]),
+    "sr_blend_plan_march_items": (_i, [_vp, _i, C.POINTER(C.c_int32), _i64, C.POINTER(_i64)]),
     "sr_laplacian_blend": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i64), _vp, _i64, _vp]),
     "sr_weighted_blend": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i64), _vp, _i64, _vp]),
     "sr_blend_pyramids": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i64), _pi, _i, _i]),
@@ -623,6 +625,12 @@ class Context:
 
     def sync(self):
         check(self.lib.sr_ctx_sync(self.handle))
+
+    def num_cu(self) -> int:
+        """Compute units of the device (the launch-shape rules are sized by it)."""
+        n = C.c_int(0)
+        check(self.lib.sr_ctx_num_cu(self.handle, C.byref(n)))
+        return n.value
 
     # memory ---------------------------------------------------------------------------
     def alloc(self, nbytes: int) -> DeviceBuffer:
@@ -1190,6 +1198,18 @@ class BlendPlan:
         f = C.c_int(-1)
         check(self.ctx.lib.sr_blend_plan_g1_format(self.handle, int(dtype), C.byref(f)))
         return f.value
+
+    def march_items(self, nt: int) -> np.ndarray:
+        """The plan's work lists of the marched gather (sr_blend_plan_march_items): nt = 1 .. 4 -> int32 [items, 8] of
+        (x0, y0, ncell, nstep, tile[4]) in launch order; nt = 0 -> int32 [rectangles, 4] of (x, y, w, h)."""
+        per = 4 if nt == 0 else 8
+        cnt = _i64(0)
+        check(self.ctx.lib.sr_blend_plan_march_items(self.handle, int(nt), None, 0, C.byref(cnt)))
+        out = np.zeros((cnt.value, per), dtype=np.int32)
+        if cnt.value:
+            check(self.ctx.lib.sr_blend_plan_march_items(self.handle, int(nt), out.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         cnt.value, C.byref(cnt)))
+        return out
 
     def blend(self, d_tiles: Sequence[int], strides: Sequence[int], d_canvas: int, canvas_stride: int,
               dtype: int = SR_U8, d_canvas_f32: Optional[int] = None, laplacian: bool = True):

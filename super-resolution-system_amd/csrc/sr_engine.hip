@@ -1686,7 +1686,9 @@ struct sr_blend_plan {
     RectItem *d_rects = nullptr;                            // what the marched zones leave, as rectangles of cells (k_final_rect)
     int *d_rect_cand = nullptr;
     long long n_rects = 0;
-    std::vector<char> sh_srcs, sh_fdesc;                // host shadows of d_srcs / d_fdesc (upload_if_changed)
+    std::vector<MarchItem> h_march_items[MARCH_NT + 1];     // host copies of the work lists (sr_blend_plan_march_items): a few KB
+    std::vector<RectItem> h_rects;
+    std::vector<char> sh_srcs, sh_fdesc;               // host shadows of d_srcs / d_fdesc (upload_if_changed)
     CachedTable subset_tabs[4];                         // compacted {TileDev, TileSrc} tables of recent tile subsets
     int subset_next = 0;
     float *d_luts = nullptr;
@@ -2423,6 +2425,7 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
                 if (!rects.empty() && (e = hipMemcpy(P->d_rects, rects.data(), sizeof(RectItem) * rects.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
                 if ((e = hipMalloc((void **)&P->d_rect_cand, sizeof(int) * std::max<size_t>(rcand.size(), 1))) != hipSuccess) return fail(e, "rectangle candidates");
                 if (!rcand.empty() && (e = hipMemcpy(P->d_rect_cand, rcand.data(), sizeof(int) * rcand.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
+                P->h_rects.swap(rects);
             }
         }
         for (int k = 1; k <= MARCH_NT; ++k) {
@@ -2431,6 +2434,7 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
             if (mitems[k].empty()) continue;
             if ((e = hipMalloc((void **)&P->d_march_items[k], sizeof(MarchItem) * mitems[k].size())) != hipSuccess) return fail(e, "march items");
             if ((e = hipMemcpy(P->d_march_items[k], mitems[k].data(), sizeof(MarchItem) * mitems[k].size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
+            P->h_march_items[k].swap(mitems[k]);
         }
     }
     if ((e = hipMemcpyAsync(P->d_tiles, P->tiles.data(), sizeof(TileDev) * n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return fail(e, "upload");
@@ -2487,6 +2491,26 @@ int sr_blend_plan_g1_format(const sr_blend_plan *plan, int dtype, int *fmt)
 {
     if (!plan_is_live(plan) || !fmt || (dtype != SR_U8 && dtype != SR_F32)) return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_g1_format: bad args");
     *fmt = g1_format(plan, dtype, nullptr);
+    return SR_OK;
+}
+
+int sr_blend_plan_march_items(const sr_blend_plan *plan, int nt, int32_t *out, int64_t cap, int64_t *count)
+{
+    if (!plan_is_live(plan) || nt < 0 || nt > MARCH_NT || !count || (out && cap < 0))
+        return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_march_items: bad args");
+    if (nt == 0) {
+        const std::vector<RectItem> &r = plan->h_rects;
+        *count = (int64_t)r.size();
+        for (int64_t i = 0; out && i < std::min<int64_t>(cap, *count); ++i) {
+            const int v[4] = {r[i].x, r[i].y, r[i].w, r[i].h};
+            memcpy(out + 4 * i, v, sizeof(v));
+        }
+        return SR_OK;
+    }
+    static_assert(sizeof(MarchItem) == 8 * sizeof(int32_t), "eight ints per item");
+    const std::vector<MarchItem> &m = plan->h_march_items[nt];
+    *count = (int64_t)m.size();
+    if (out && !m.empty()) memcpy(out, m.data(), sizeof(MarchItem) * (size_t)std::min<int64_t>(cap, *count));
     return SR_OK;
 }
 

@@ -210,6 +210,14 @@ int sr_ctx_sync(sr_ctx *ctx)
     return SR_OK;
 }
 
+int sr_ctx_num_cu(sr_ctx *ctx, int *num_cu)
+{
+    CTX_ENTER(ctx);
+    if (!num_cu) return sr_set_error(SR_ERR_INVALID_ARG, "sr_ctx_num_cu: null out");
+    *num_cu = ctx->num_cu;
+    return SR_OK;
+}
+
 int sr_dev_alloc(sr_ctx *ctx, size_t bytes, void **d_ptr)
 {
     CTX_ENTER(ctx);
