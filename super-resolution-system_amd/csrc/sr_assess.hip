@@ -28,6 +28,7 @@
 
 #include "sr_ctx.h"
 #include "sr_device.h"
+#include "sr_ssim11.h"
 
 // ---------------------------------------------------------------------------------------------
 // metrics
@@ -173,23 +174,7 @@ __device__ __forceinline__ void load_gray_pair(const unsigned char *__restrict__
 {
     const unsigned char *pa = a + (size_t)sy * sa + (size_t)sx * CN;
     const unsigned char *pb = b + (size_t)sy * sb + (size_t)sx * CN;
-    if (CN == 1) {
-        ga = pa[0];
-        gb = pb[0];
-        const int d = ga - gb;
-        sq = (unsigned)(d * d);
-    } else {
-        const int r0 = pa[0], g0 = pa[1], b0 = pa[2], r1 = pb[0], g1 = pb[1], b1 = pb[2];
-        if (shift == 15) {
-            ga = (r0 * 9798 + g0 * 19235 + b0 * 3735 + (1 << 14)) >> 15;
-            gb = (r1 * 9798 + g1 * 19235 + b1 * 3735 + (1 << 14)) >> 15;
-        } else {
-            ga = (r0 * 4899 + g0 * 9617 + b0 * 1868 + (1 << 13)) >> 14;
-            gb = (r1 * 4899 + g1 * 9617 + b1 * 1868 + (1 << 13)) >> 14;
-        }
-        const int dr = r0 - r1, dg = g0 - g1, db = b0 - b1;
-        sq = (unsigned)(dr * dr + dg * dg + db * db);
-    }
+    gray_pair<CN>(pa, pb, shift, ga, gb, sq);
 }
 
 
@@ -360,23 +345,6 @@ __device__ __forceinline__ lds_cu32 *lds_row_base(lds_cu32 *row0, int bytes)
     lds_cu32 *q;
     asm volatile("v_add_u32 %0, %2, %1" : "=v"(q) : "v"(row0), "n"(bytes));     // literal goes in src0
     return q;
-}
-
-// 1 / d for the SSIM quotient: hardware estimate + one Newton step (relative error ~1e-15; the metric's bar is 1e-9
-// against the oracle, 1e-4 against the reference)
-__device__ __forceinline__ double ssim_recip(double d)
-{
-    double r = __builtin_amdgcn_rcp(d);
-    return fma(fma(-d, r, 1.0), r, r);
-}
-
-__device__ __forceinline__ double ssim_quot(double ux, double uy, double spq, double dpq, double c1, double c2)
-{
-    // spq = uxx + uyy,  dpq = uxy
-    const double uxuy = ux * uy, uu = fma(ux, ux, uy * uy);
-    const double a1 = fma(2.0, uxuy, c1), a2 = fma(2.0, dpq - uxuy, c2);
-    const double b1 = uu + c1, b2 = (spq - uu) + c2;
-    return (a1 * a2) * ssim_recip(b1 * b2);
 }
 
 // Compile-time variants: GAUSS (the two Gaussian-11 sums and their 88-register FIFO), UNIF (the uniform-7 sum and its LDS
@@ -1293,17 +1261,6 @@ int sr_sse_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *
     HIPCHK(hipMemcpyAsync(h_sse, scr, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(stream_sync(ctx));
     return SR_OK;
-}
-
-static void gauss_taps(double *k6)
-{
-    double k[11], sum = 0.0;
-    for (int i = 0; i < 11; ++i) {
-        const double x = i - 5;
-        k[i] = std::exp(-0.5 / (1.5 * 1.5) * x * x);     // scipy.ndimage._gaussian_kernel1d(sigma=1.5, radius=5)
-        sum += k[i];
-    }
-    for (int j = 0; j <= 5; ++j) k6[j] = k[5 + j] / sum;
 }
 
 int sr_ssim_count(int h, int w, int mode, int row_begin, int row_end, uint64_t *count)

@@ -1,6 +1,7 @@
 // sr_ctx.h -- the device context shared by the .hip translation units of libsrhip.so (sr_runtime.hip owns the
 // definitions, except plan_describe and destroy_plans_of: sr_engine.hip, and reduce_partials: sr_assess.hip; every
-// other .hip file and sr_comm.cpp use them, the convolution networks through sr_conv_mfma.h).
+// other .hip file and sr_comm.cpp use them, the convolution networks through sr_conv_mfma.h, the SSIM column march and its
+// workspace growth through sr_ssim11.h).
 // Internal: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,6 @@
-// sr_device.h -- device helpers shared by sr_engine.hip (blend engine), sr_tiles.hip (stand-alone tile kernels) and
-// sr_assess.hip (quality assessment): border rules, vector load / store typedefs, the integer RGB -> gray of
+// sr_device.h -- device helpers shared by sr_engine.hip (blend engine), sr_tiles.hip (stand-alone tile kernels),
+// sr_assess.hip (quality assessment), sr_msssim.hip and sr_srbench.hip (the SSIM helpers those share are in sr_ssim11.h):
+// border rules, vector load / store typedefs, the integer RGB -> gray of
 // cv2.cvtColor, the tile-source descriptor with its data-type tags, and the shared-reciprocal division.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -4,40 +4,35 @@
 // is dropped), per level the Gaussian-11 (sigma 1.5) SSIM over the valid region with the population covariance, split into
 // l and cs; S_j = mean(l cs), CS_j = mean(cs); the value is the weighted product, finished on the host.
 //
-// One kernel, one launch per level:
+// One kernel, one launch per level, on the column march of sr_ssim11.h (window, vertical pass, LDS rows, horizontal pass,
+// quotient, block tree are there).  What is this file's own:
 //   k_msssim_level<SRC>  SRC = 1 / 3: the two u8 images (level 0; 3: RGB -> gray once per pixel), SRC = 0: a level plane.
-//     A block owns MS_OUT map columns and one chunk of map rows.  Each thread owns an input column and walks down the chunk:
-//     the vertical pass of its column comes from an 11-row register window of exact integers (x, y, x y, x^2 + y^2), the
-//     horizontal pass reads the neighbours' vertical results through LDS; l cs and cs are added per column in row order.
-//     Each input row is read once per block (10 halo rows per chunk, 10 halo columns per block).  On every second row the
-//     thread of an even column adds its column's last two rows to its right neighbour's (one wave shuffle) and stores the
-//     2 x 2 SUM as one dword x | y << 16 of the next level's plane: a level-j value is the integer sum of 4^j u8 values
-//     (<= 255 * 256 = 65280 at j = 4), never divided, so nothing rounds.  Chunks start on even rows, MS_OUT is even, the
-//     last chunk / column block takes the rest: every pooled pixel is written exactly once.
+//     A block owns S11_OUT map columns and one chunk of map rows, valid region only (no border rule): 10 halo rows per chunk,
+//     10 halo columns per block, each input row is read once per block.  l cs and cs come from one reciprocal and are added
+//     per column in row order.
+//     Pooling in the same pass: on every second row the thread of an even column adds its column's last two rows to its
+//     right neighbour's (one wave shuffle) and stores the 2 x 2 SUM as one dword x | y << 16 of the next level's plane: a
+//     level-j value is the integer sum of 4^j u8 values (<= 255 * 256 = 65280 at j = 4), never divided, so nothing rounds.
+//     Chunks start on even rows, S11_OUT is even, the last chunk / column block takes the rest: every pooled pixel is
+//     written exactly once.
 //     SSIM does not change when x and y are scaled by 4^j and C1, C2 by 16^j, so level j works on the integer sums as they are.
-//     Level 0 keeps x | y << 14 packed and its products in 32 bits (as sr_qmap.hip does); from level 1 on x y still fits 32
-//     bits unsigned (65280^2 < 2^32) but x^2 + y^2 does not: it is formed and kept in fp64, exact below 2^53.
-//   The block's 256 column sums go through a fixed tree, the per-block partials through reduce_partials: no floating-point
-//   atomics, equal inputs give equal bits.
+//     Level 0 uses the packed u8 window; from level 1 on x y still fits 32 bits unsigned (65280^2 < 2^32) but x^2 + y^2 does
+//     not: it is formed and kept in fp64, exact below 2^53 (the 16-bit-sums window).
+//   The per-block partials go through reduce_partials.
 // The level planes and the partials are context scratch (sr_ctx::msssim_ws), grown on demand: 4 bytes per level-1 pixel and a
 // third more for the coarser levels, about h w / 3 * 4 bytes.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "sr_ctx.h"
 #include "sr_device.h"
+#include "sr_ssim11.h"
 
 namespace {
 
-constexpr int MS_TX = 256;                 // threads = input columns of a block
-constexpr int MS_R = 5;                    // radius of the Gaussian
-constexpr int MS_OUT = MS_TX - 2 * MS_R;   // map columns a block produces (even: a pooled pair never straddles two blocks)
-constexpr int MS_ROWS = 128;               // longest chunk of map rows (10 halo rows on top: 8 %)
-constexpr int MS_ROWS_MIN = 16;            // shortest chunk a small level is cut into ...
-constexpr int MS_BLOCKS = 1024;            // ... to reach this many blocks
 constexpr int MS_MAX_LEVELS = 5;
-constexpr int MS_MIN_SIDE = 2 * MS_R + 1;
 
 struct MsParams {
     int h, w;                   // this level's size
@@ -53,7 +48,8 @@ struct MsPlan {
     int lh[MS_MAX_LEVELS], lw[MS_MAX_LEVELS];
     uint64_t count[MS_MAX_LEVELS];
     size_t off_plane[MS_MAX_LEVELS];        // [0] unused
-    size_t off_part, off_buf0, off_buf1, off_res, total;
+    PartialsLayout red;
+    size_t off_res, total;
     int step[MS_MAX_LEVELS], gx[MS_MAX_LEVELS], gy[MS_MAX_LEVELS];
 };
 
@@ -74,65 +70,44 @@ __device__ __forceinline__ void ms_load(const unsigned char *__restrict__ pa, co
     }
 }
 
-// 1 / d: hardware estimate + one Newton step (relative error ~1e-15), d a product of positive SSIM terms
-__device__ __forceinline__ double ms_recip(double d)
-{
-    const double r = __builtin_amdgcn_rcp(d);
-    return fma(fma(-d, r, 1.0), r, r);
-}
-
 template <int SRC>
-__global__ __launch_bounds__(MS_TX) void k_msssim_level(const unsigned char *__restrict__ a, long long sa,
-                                                        const unsigned char *__restrict__ b, long long sb, MsParams P,
-                                                        unsigned *__restrict__ next, double *__restrict__ part)
+__global__ __launch_bounds__(S11_TX) void k_msssim_level(const unsigned char *__restrict__ a, long long sa,
+                                                         const unsigned char *__restrict__ b, long long sb, MsParams P,
+                                                         unsigned *__restrict__ next, double *__restrict__ part)
 {
     constexpr bool WIDE = SRC == 0;
     constexpr int PX = SRC == 0 ? 4 : SRC;                               // bytes per pixel of a source row
-    // vertical results of one row, double-buffered by row parity: one barrier per row
-    __shared__ double F[2][4][MS_TX];
+    __shared__ double F[2][4][S11_TX];
     const int t = threadIdx.x;
-    const int mh = P.h - 2 * MS_R;                                       // map rows
+    const int mh = P.h - 2 * S11_R;                                      // map rows
     const int y0 = (int)blockIdx.x * P.step, y1 = min(y0 + P.step, mh);  // this chunk's map rows = its first input rows
     const bool last_chunk = blockIdx.x == gridDim.x - 1, last_cols = blockIdx.y == gridDim.y - 1;
-    const int c = (int)blockIdx.y * MS_OUT + t;                          // the input column this thread filters vertically
+    const int c = (int)blockIdx.y * S11_OUT + t;                         // the input column this thread filters vertically
     const bool in = c < P.w;
-    const bool own = t < MS_OUT && c <= P.w - MS_MIN_SIDE;               // ... and the map column it produces
+    const bool own = t < S11_OUT && c <= P.w - S11_SIDE;                 // ... and the map column it produces
     // pooling: input rows [y0, pool_end) and the block's own columns (the last block of either axis takes the rest)
     const int pool_end = last_chunk ? P.h : y1;
-    const bool pool_col = !(t & 1) && (t < MS_OUT || last_cols) && c + 1 < P.w;
+    const bool pool_col = !(t & 1) && (t < S11_OUT || last_cols) && c + 1 < P.w;
     const unsigned char *ca = a + (size_t)(in ? c : 0) * PX, *cb = WIDE ? ca : b + (size_t)(in ? c : 0) * PX;
     if constexpr (WIDE) sb = sa;
-    // rows lr - 10 .. lr of this column.  Level 0: x | y << 14 packed (pair sums <= 510 stay in their fields)
-    unsigned wx[11], wy[WIDE ? 11 : 1], wq[11], wp[WIDE ? 1 : 11];
-    double wpd[WIDE ? 11 : 1];
-#pragma unroll
-    for (int i = 0; i < 11; ++i) {
-        wx[i] = wq[i] = 0u;
-        if constexpr (WIDE) { wy[i] = 0u; wpd[i] = 0.0; }
-        else wp[i] = 0u;
-    }
+    // level 0: wx holds x | y << 14 and wy is not used; from level 1 on x^2 + y^2 is fp64
+    Window11<unsigned> wx, wy, wq;
+    Window11<std::conditional_t<WIDE, double, unsigned>> wp;
     double sum_s = 0.0, sum_cs = 0.0;
     const double kk[6] = {P.k[0], P.k[1], P.k[2], P.k[3], P.k[4], P.k[5]};
-    const int nrows = (y1 - y0) + 2 * MS_R;                              // input rows y0 .. y1 + 9 (< h)
+    const int nrows = (y1 - y0) + 2 * S11_R;                             // input rows y0 .. y1 + 9 (< h)
     unsigned nx = 0u, ny = 0u;
     if (in) ms_load<SRC>(ca + (size_t)y0 * (size_t)sa, cb + (size_t)y0 * (size_t)sb, P.shift, nx, ny);
 #pragma unroll 1
     for (int lr = 0; lr < nrows; ++lr) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) {
-            wx[i] = wx[i + 1];
-            wq[i] = wq[i + 1];
-            if constexpr (WIDE) { wy[i] = wy[i + 1]; wpd[i] = wpd[i + 1]; }
-            else wp[i] = wp[i + 1];
-        }
-        wq[10] = nx * ny;                                                // <= 65280^2 < 2^32
+        wq.push(nx * ny);                                                // <= 65280^2 < 2^32
         if constexpr (WIDE) {
-            wx[10] = nx;
-            wy[10] = ny;
-            wpd[10] = fma((double)nx, (double)nx, (double)ny * (double)ny);   // exact: < 2^34
+            wx.push(nx);
+            wy.push(ny);
+            wp.push(fma((double)nx, (double)nx, (double)ny * (double)ny));    // exact: < 2^34
         } else {
-            wx[10] = nx | (ny << 14);
-            wp[10] = nx * nx + ny * ny;
+            wx.push(nx | (ny << 14));
+            wp.push(nx * nx + ny * ny);
         }
         if (in) {   // the next row is requested before this one is worked on (the last iteration reads its own row again)
             const size_t sy = (size_t)(y0 + min(lr + 1, nrows - 1));
@@ -153,88 +128,27 @@ __global__ __launch_bounds__(MS_TX) void k_msssim_level(const unsigned char *__r
             }
             if (pool_col) next[(size_t)(r >> 1) * (size_t)P.ow + (size_t)(c >> 1)] = px | (py << 16);
         }
-        if (lr < 2 * MS_R) continue;                                     // block-uniform
+        if (lr < 2 * S11_R) continue;                                    // block-uniform
         const int pb = lr & 1;
         {
-            double hx, hy, hp, hq;
-            if constexpr (WIDE) {
-                hx = (double)wx[5] * kk[0];
-                hy = (double)wy[5] * kk[0];
-                hp = wpd[5] * kk[0];
-                hq = (double)wq[5] * kk[0];
-#pragma unroll
-                for (int j = 1; j <= MS_R; ++j) {
-                    hx = fma((double)(wx[5 - j] + wx[5 + j]), kk[j], hx);
-                    hy = fma((double)(wy[5 - j] + wy[5 + j]), kk[j], hy);
-                    hp = fma(wpd[5 - j] + wpd[5 + j], kk[j], hp);
-                    hq = fma((double)wq[5 - j] + (double)wq[5 + j], kk[j], hq);   // the integer pair sum can pass 2^32
-                }
-            } else {
-                hx = (double)(wx[5] & 0x3FFFu) * kk[0];
-                hy = (double)(wx[5] >> 14) * kk[0];
-                hp = (double)wp[5] * kk[0];
-                hq = (double)wq[5] * kk[0];
-#pragma unroll
-                for (int j = 1; j <= MS_R; ++j) {
-                    const unsigned sxy = wx[5 - j] + wx[5 + j];          // both images in one add
-                    hx = fma((double)(sxy & 0x3FFFu), kk[j], hx);
-                    hy = fma((double)(sxy >> 14), kk[j], hy);
-                    hp = fma((double)(wp[5 - j] + wp[5 + j]), kk[j], hp);
-                    hq = fma((double)(wq[5 - j] + wq[5 + j]), kk[j], hq);
-                }
-            }
-            F[pb][0][t] = hx; F[pb][1][t] = hy; F[pb][2][t] = hp; F[pb][3][t] = hq;
+            double hv[4];
+            if constexpr (WIDE) s11_col_pass<true>(wx, wy, wp, wq, kk, hv);    // the integer pair sum of two x y can pass 2^32
+            else s11_col_pass_packed(wx, wp, wq, kk, hv);
+            s11_store_col(F[pb], t, hv);
         }
         __syncthreads();
         if (!own) continue;
         double u[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            double acc = F[pb][m][t + MS_R] * kk[0];
-#pragma unroll
-            for (int j = 1; j <= MS_R; ++j) acc = fma(F[pb][m][t + MS_R - j] + F[pb][m][t + MS_R + j], kk[j], acc);
-            u[m] = acc;
-        }
-        // u[2] = E[x^2 + y^2], u[3] = E[x y]
-        const double uxuy = u[0] * u[1], uu = fma(u[0], u[0], u[1] * u[1]);
-        const double a1 = fma(2.0, uxuy, P.c1), a2 = fma(2.0, u[3] - uxuy, P.c2);
-        const double b1 = uu + P.c1, b2 = (u[2] - uu) + P.c2;
-        const double rb = ms_recip(b1 * b2);
-        sum_cs += (a2 * b1) * rb;
-        sum_s += (a1 * a2) * rb;
+        s11_row_pass(F[pb], t + S11_R, kk, u);
+        const SsimTerms q = ssim_terms(u[0], u[1], u[2], u[3], P.c1, P.c2);
+        const double rb = ssim_recip(q.b1 * q.b2);
+        sum_cs += (q.a2 * q.b1) * rb;
+        sum_s += (q.a1 * q.a2) * rb;
     }
-    // the block's column sums in a fixed tree (columns that produce nothing add 0)
-    __syncthreads();
-    double *sd0 = &F[0][0][0], *sd1 = &F[0][1][0];
-    sd0[t] = own ? sum_s : 0.0;
-    sd1[t] = own ? sum_cs : 0.0;
-    __syncthreads();
-    for (int s = MS_TX / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            sd0[t] += sd0[t + s];
-            sd1[t] += sd1[t + s];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        part[blk * 2 + 0] = sd0[0];
-        part[blk * 2 + 1] = sd1[0];
-    }
+    // columns that produce nothing add 0
+    s11_block_sum2(&F[0][0][0], &F[0][1][0], t, own ? sum_s : 0.0, own ? sum_cs : 0.0,
+                   part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2);
 }
-
-void ms_gauss_taps(double *k6)
-{
-    double k[11], sum = 0.0;
-    for (int i = 0; i < 11; ++i) {
-        const double x = i - 5;
-        k[i] = std::exp(-0.5 / (1.5 * 1.5) * x * x);     // scipy.ndimage._gaussian_kernel1d(sigma=1.5, radius=5)
-        sum += k[i];
-    }
-    for (int j = 0; j <= 5; ++j) k6[j] = k[5 + j] / sum;
-}
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 // sizes, counts, launch shapes and the scratch layout; the refusals of sr_ms_ssim_plan
 int ms_plan(const char *scope, int h, int w, int levels, MsPlan *p)
@@ -242,7 +156,7 @@ int ms_plan(const char *scope, int h, int w, int levels, MsPlan *p)
     if (levels < 1 || levels > MS_MAX_LEVELS)
         return sr_set_error(SR_ERR_INVALID_ARG, "%s: levels must be 1 .. %d (got %d)", scope, MS_MAX_LEVELS, levels);
     if (h < 1 || w < 1) return sr_set_error(SR_ERR_INVALID_ARG, "%s: need h, w >= 1", scope);
-    const int min_side = MS_MIN_SIDE << (levels - 1);
+    const int min_side = S11_SIDE << (levels - 1);
     if (h < min_side || w < min_side)
         return sr_set_error(SR_ERR_SHAPE, "%s: image %dx%d is too small for %d levels: both sides must be at least %d (11 at the "
                             "coarsest level)", scope, w, h, levels, min_side);
@@ -251,32 +165,21 @@ int ms_plan(const char *scope, int h, int w, int levels, MsPlan *p)
     for (int j = 0; j < levels; ++j) {
         p->lh[j] = h >> j;
         p->lw[j] = w >> j;
-        const int mh = p->lh[j] - 2 * MS_R, mw = p->lw[j] - 2 * MS_R;
+        const int mh = p->lh[j] - 2 * S11_R, mw = p->lw[j] - 2 * S11_R;
         p->count[j] = (uint64_t)mh * (uint64_t)mw;
-        // Chunks of at most MS_ROWS map rows; a small level takes shorter ones (down to MS_ROWS_MIN) until it has MS_BLOCKS
-        // blocks: a block walks its rows one after the other, so a coarse level cut into a few long chunks would take as long
-        // as a chunk takes on an empty chip.  The cut depends on the size alone, never on the device: equal bits everywhere.
-        p->gy[j] = (mw + MS_OUT - 1) / MS_OUT;
-        int rows = MS_ROWS;
-        while (rows > MS_ROWS_MIN && (long long)((mh + rows - 1) / rows) * p->gy[j] < MS_BLOCKS) rows /= 2;
-        const int n = (mh + rows - 1) / rows;
-        p->step[j] = ((mh + n - 1) / n + 1) & ~1;                       // even: a pooled row pair never straddles two chunks
-        p->gx[j] = (mh + p->step[j] - 1) / p->step[j];
+        p->gy[j] = (mw + S11_OUT - 1) / S11_OUT;
+        const ChunkCut cut = s11_chunk_cut(mh, p->gy[j], true);         // even: a pooled row pair never straddles two chunks
+        p->step[j] = cut.step;
+        p->gx[j] = cut.count;
         nblk_max = std::max(nblk_max, (size_t)p->gx[j] * (size_t)p->gy[j]);
         if (j >= 1) {
             p->off_plane[j] = off;
             off += up256((size_t)p->lh[j] * (size_t)p->lw[j] * 4);
         }
     }
-    p->off_part = off;
-    off += up256(nblk_max * 2 * sizeof(double));
-    p->off_buf0 = off;
-    off += up256((nblk_max / 1024 + 2) * 2 * sizeof(double));
-    p->off_buf1 = off;
-    off += up256((nblk_max / 1024 + 2) * 2 * sizeof(double));
-    p->off_res = off;
-    off += up256(MS_MAX_LEVELS * 2 * sizeof(double));
-    p->total = off;
+    p->red = s11_partials_layout(off, nblk_max);
+    p->off_res = p->red.end;
+    p->total = p->off_res + up256(MS_MAX_LEVELS * 2 * sizeof(double));
     return SR_OK;
 }
 
@@ -316,23 +219,10 @@ int sr_ms_ssim_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8
     if (stride_a < min_stride || stride_b < min_stride) return sr_set_error(SR_ERR_SHAPE, "sr_ms_ssim_u8: stride smaller than a row");
     CTX_ENTER(ctx);
     ctx->msssim_levels = 0;                                              // the planes are about to be overwritten
-    if (p.total > ctx->msssim_ws_bytes) {
-        if (ctx->msssim_ws) {
-            HIPCHK(stream_sync(ctx));
-            HIPCHK(hipFree(ctx->msssim_ws));
-            ctx->msssim_ws = nullptr;
-            ctx->msssim_ws_bytes = 0;
-        }
-        hipError_t e = hipMalloc(&ctx->msssim_ws, p.total);
-        if (e != hipSuccess) {
-            ctx->msssim_ws = nullptr;
-            return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "sr_ms_ssim_u8: scratch of %zu bytes: %s", p.total,
-                                hipGetErrorString(e));
-        }
-        ctx->msssim_ws_bytes = p.total;
-    }
+    rc = ctx_grow_ws(ctx, "sr_ms_ssim_u8", &ctx->msssim_ws, &ctx->msssim_ws_bytes, p.total);
+    if (rc) return rc;
     char *ws = (char *)ctx->msssim_ws;
-    double *part = (double *)(ws + p.off_part), *buf0 = (double *)(ws + p.off_buf0), *buf1 = (double *)(ws + p.off_buf1),
+    double *part = (double *)(ws + p.red.off_part), *buf0 = (double *)(ws + p.red.off_buf0), *buf1 = (double *)(ws + p.red.off_buf1),
            *res = (double *)(ws + p.off_res);
     static const char *const names[MS_MAX_LEVELS] = {"msssim_l0", "msssim_l1", "msssim_l2", "msssim_l3", "msssim_l4"};
     double scale = 1.0;                                                  // 16^level
@@ -344,9 +234,9 @@ int sr_ms_ssim_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8
         P.ow = P.w / 2;
         P.c1 = (0.01 * data_range) * (0.01 * data_range) * scale;
         P.c2 = (0.03 * data_range) * (0.03 * data_range) * scale;
-        ms_gauss_taps(P.k);
+        gauss_taps(P.k);
         unsigned *next = P.emit ? (unsigned *)(ws + p.off_plane[j + 1]) : nullptr;
-        const dim3 grid((unsigned)p.gx[j], (unsigned)p.gy[j]), block(MS_TX);
+        const dim3 grid((unsigned)p.gx[j], (unsigned)p.gy[j]), block(S11_TX);
         {
             ProfScope ps(ctx, names[j]);
             if (j > 0) {

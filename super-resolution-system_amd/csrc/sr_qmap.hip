@@ -7,11 +7,13 @@
 // up exactly.
 //
 // Two kernels, no floating-point atomics -- equal inputs give equal bits:
-//   k_qmap_cols   a block owns QM_OUT columns and ONE row chunk (a cell row, or a piece of at most QM_ROWS rows of it).  Each
-//                 thread owns a column and walks down the chunk: the vertical pass of its column comes from an 11-row
-//                 register window of exact integers (x | y << 14, x y, x^2 + y^2), the horizontal pass reads the
-//                 neighbours' vertical results through LDS.  Samples are added per column in row order; at the end the
-//                 thread stores its column sums into the slab ws[sum][chunk][column].
+//   k_qmap_cols   a block owns S11_OUT columns and ONE row chunk (a cell row, or a piece of at most S11_ROWS rows of it).  The
+//                 Gaussian half is the column march of sr_ssim11.h with the packed u8 window.  This file's own: the columns
+//                 are image columns - 5 .. + 250 with REFLECT_101 (the full-frame variant needs the border), so the
+//                 horizontal pass is centred on the thread's own column; the uniform-7 variant takes its 7-row box sums
+//                 from the same window and its horizontal pass from the integer rows U; the chunk table.  Samples are
+//                 added per column in row order; at the end the thread stores its column sums into the slab
+//                 ws[sum][chunk][column].
 //   k_qmap_cells  a block per cell adds the slab entries of the cell's chunks and columns in a fixed order.
 // fp64 throughout, like the rest of the assessment.  A plain separable form: k_assess_march (sr_assess.hip) stays the
 // tuned kernel of the global metrics.
@@ -21,15 +23,11 @@
 #include <vector>
 
 #include "sr_ctx.h"
+#include "sr_ssim11.h"
 
 namespace {
 
 enum { QM_SSE = 1, QM_UNIFORM = 2, QM_GAUSS = 4, QM_SIMPLE = 8, QM_ALL_BITS = 15 };
-
-constexpr int QM_TX = 256;                 // threads = columns a block filters vertically
-constexpr int QM_R = 5;                    // radius of the Gaussian
-constexpr int QM_OUT = QM_TX - 2 * QM_R;   // columns a block produces
-constexpr int QM_ROWS = 128;               // longest row chunk (10 halo rows on top: 8 %)
 
 struct QmapParams {
     int h, w, shift, flags, same_c;
@@ -58,102 +56,61 @@ __device__ __forceinline__ void qm_load(const unsigned char *__restrict__ pa, co
                                         unsigned &xy, unsigned &q, unsigned &p, unsigned &sq)
 {
     int ga, gb;
-    if (CN == 1) {
-        ga = pa[0];
-        gb = pb[0];
-        const int d = ga - gb;
-        sq = (unsigned)(d * d);
-    } else {
-        const int r0 = pa[0], g0 = pa[1], b0 = pa[2], r1 = pb[0], g1 = pb[1], b1 = pb[2];
-        if (shift == 15) {
-            ga = (r0 * 9798 + g0 * 19235 + b0 * 3735 + (1 << 14)) >> 15;
-            gb = (r1 * 9798 + g1 * 19235 + b1 * 3735 + (1 << 14)) >> 15;
-        } else {
-            ga = (r0 * 4899 + g0 * 9617 + b0 * 1868 + (1 << 13)) >> 14;
-            gb = (r1 * 4899 + g1 * 9617 + b1 * 1868 + (1 << 13)) >> 14;
-        }
-        const int dr = r0 - r1, dg = g0 - g1, db = b0 - b1;
-        sq = (unsigned)(dr * dr + dg * dg + db * db);
-    }
+    gray_pair<CN>(pa, pb, shift, ga, gb, sq);
     // x and y travel packed: pair sums (<= 510), 7-row sums (<= 1785) and 49-sample sums (<= 12495 < 2^14) stay in their fields
     xy = (unsigned)ga | ((unsigned)gb << 14);
     q = (unsigned)(ga * gb);
     p = (unsigned)(ga * ga + gb * gb);
 }
 
-// 1 / d: hardware estimate + one Newton step (relative error ~1e-15), d a product of positive SSIM terms
-__device__ __forceinline__ double qm_recip(double d)
-{
-    const double r = __builtin_amdgcn_rcp(d);
-    return fma(fma(-d, r, 1.0), r, r);
-}
-
-__device__ __forceinline__ double qm_ssim(double ux, double uy, double spq, double dpq, double c1, double c2)
-{
-    // spq = uxx + uyy, dpq = uxy
-    const double uxuy = ux * uy, uu = fma(ux, ux, uy * uy);
-    const double a1 = fma(2.0, uxuy, c1), a2 = fma(2.0, dpq - uxuy, c2);
-    const double b1 = uu + c1, b2 = (spq - uu) + c2;
-    return (a1 * a2) * qm_recip(b1 * b2);
-}
-
 template <int CN>
-__global__ __launch_bounds__(QM_TX) void k_qmap_cols(const unsigned char *__restrict__ a, long long sa,
-                                                     const unsigned char *__restrict__ b, long long sb, QmapParams P,
-                                                     const int2 *__restrict__ chunks, unsigned long long *__restrict__ ws)
+__global__ __launch_bounds__(S11_TX) void k_qmap_cols(const unsigned char *__restrict__ a, long long sa,
+                                                      const unsigned char *__restrict__ b, long long sb, QmapParams P,
+                                                      const int2 *__restrict__ chunks, unsigned long long *__restrict__ ws)
 {
-    // vertical results of one row, double-buffered by row parity: one barrier per row
-    __shared__ double F[2][4][QM_TX];
-    __shared__ unsigned U[2][3][QM_TX];
+    __shared__ double F[2][4][S11_TX];
+    __shared__ unsigned U[2][3][S11_TX];
     const int t = threadIdx.x;
     const int2 ck = chunks[blockIdx.x];
     const int y0 = ck.x, y1 = ck.y;
-    const int mx = (int)blockIdx.y * QM_OUT - QM_R + t;                  // the column this thread filters vertically
-    const bool own = t >= QM_R && t < QM_TX - QM_R && mx < P.w;          // ... and produces (mx >= 0 there)
+    const int mx = (int)blockIdx.y * S11_OUT - S11_R + t;                // the column this thread filters vertically
+    const bool own = t >= S11_R && t < S11_TX - S11_R && mx < P.w;       // ... and produces (mx >= 0 there)
     const bool want_g = (P.flags & (QM_GAUSS | QM_SIMPLE)) != 0, want_u = (P.flags & QM_UNIFORM) != 0;
     const size_t col = (size_t)qm_reflect101(mx, P.w) * CN;
     const unsigned char *ca = a + col, *cb = b + col;
-    unsigned wxy[11], wq[11], wp[11], wsq[6];                           // rows oy - 5 .. oy + 5 of this column
-#pragma unroll
-    for (int i = 0; i < 11; ++i) wxy[i] = wq[i] = wp[i] = 0u;
+    Window11<unsigned> wxy, wq, wp;                                     // rows oy - 5 .. oy + 5 of this column
+    unsigned wsq[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) wsq[i] = 0u;
     double sum_u = 0.0, sum_g = 0.0, sum_s = 0.0;
-    unsigned sse = 0;                   // at most QM_ROWS * 3 * 255^2 = 2.5e7 per thread
+    unsigned sse = 0;                   // at most S11_ROWS * 3 * 255^2 = 2.5e7 per thread
     const double k0 = P.k[0], k1 = P.k[1], k2 = P.k[2], k3 = P.k[3], k4 = P.k[4], k5 = P.k[5];
-    const int nrows = (y1 - y0) + 2 * QM_R;
+    const int nrows = (y1 - y0) + 2 * S11_R;
     unsigned nxy, nq, np, nsq;
     {
-        const size_t sy = (size_t)qm_reflect101(y0 - QM_R, P.h);
+        const size_t sy = (size_t)qm_reflect101(y0 - S11_R, P.h);
         qm_load<CN>(ca + sy * (size_t)sa, cb + sy * (size_t)sb, P.shift, nxy, nq, np, nsq);
     }
 #pragma unroll 1
     for (int lr = 0; lr < nrows; ++lr) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) { wxy[i] = wxy[i + 1]; wq[i] = wq[i + 1]; wp[i] = wp[i + 1]; }
+        wxy.push(nxy);
+        wq.push(nq);
+        wp.push(np);
 #pragma unroll
         for (int i = 0; i < 5; ++i) wsq[i] = wsq[i + 1];
-        wxy[10] = nxy; wq[10] = nq; wp[10] = np; wsq[5] = nsq;
+        wsq[5] = nsq;
         {   // the next row is requested before this one is worked on (the last iteration reads its own row again)
-            const size_t sy = (size_t)qm_reflect101(y0 - QM_R + min(lr + 1, nrows - 1), P.h);
+            const size_t sy = (size_t)qm_reflect101(y0 - S11_R + min(lr + 1, nrows - 1), P.h);
             qm_load<CN>(ca + sy * (size_t)sa, cb + sy * (size_t)sb, P.shift, nxy, nq, np, nsq);
         }
-        if (lr < 2 * QM_R) continue;                                    // block-uniform
-        const int oy = y0 + lr - 2 * QM_R;                              // the window's centre row, inside the chunk
+        if (lr < 2 * S11_R) continue;                                   // block-uniform
+        const int oy = y0 + lr - 2 * S11_R;                             // the window's centre row, inside the chunk
         const int pb = lr & 1;
         if (want_g) {
             const double kk[6] = {k0, k1, k2, k3, k4, k5};
-            double hx = (double)(wxy[5] & 0x3FFFu) * kk[0], hy = (double)(wxy[5] >> 14) * kk[0];
-            double hp = (double)wp[5] * kk[0], hq = (double)wq[5] * kk[0];
-#pragma unroll
-            for (int j = 1; j <= QM_R; ++j) {
-                const unsigned sxy = wxy[5 - j] + wxy[5 + j];           // both images in one add
-                hx = fma((double)(sxy & 0x3FFFu), kk[j], hx);
-                hy = fma((double)(sxy >> 14), kk[j], hy);
-                hp = fma((double)(wp[5 - j] + wp[5 + j]), kk[j], hp);
-                hq = fma((double)(wq[5 - j] + wq[5 + j]), kk[j], hq);
-            }
-            F[pb][0][t] = hx; F[pb][1][t] = hy; F[pb][2][t] = hp; F[pb][3][t] = hq;
+            double hv[4];
+            s11_col_pass_packed(wxy, wp, wq, kk, hv);
+            s11_store_col(F[pb], t, hv);
         }
         if (want_u) {
             unsigned uxy = wxy[2], up = wp[2], uq = wq[2];
@@ -167,21 +124,15 @@ __global__ __launch_bounds__(QM_TX) void k_qmap_cols(const unsigned char *__rest
         if (want_g) {
             const double kk[6] = {k0, k1, k2, k3, k4, k5};
             double u[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                double acc = F[pb][m][t] * kk[0];
-#pragma unroll
-                for (int j = 1; j <= QM_R; ++j) acc = fma(F[pb][m][t - j] + F[pb][m][t + j], kk[j], acc);
-                u[m] = acc;
-            }
-            const bool inner_row = oy >= QM_R && oy < P.h - QM_R;       // block-uniform
+            s11_row_pass(F[pb], t, kk, u);
+            const bool inner_row = oy >= S11_R && oy < P.h - S11_R;     // block-uniform
             if (P.same_c) {
-                const double sv = qm_ssim(u[0], u[1], u[2], u[3], P.c1a, P.c2a);
+                const double sv = ssim_quot(u[0], u[1], u[2], u[3], P.c1a, P.c2a);
                 sum_s += sv;
                 if (inner_row) sum_g += sv;
             } else {
-                if (P.flags & QM_SIMPLE) sum_s += qm_ssim(u[0], u[1], u[2], u[3], P.c1b, P.c2b);
-                if (inner_row && (P.flags & QM_GAUSS)) sum_g += qm_ssim(u[0], u[1], u[2], u[3], P.c1a, P.c2a);
+                if (P.flags & QM_SIMPLE) sum_s += ssim_quot(u[0], u[1], u[2], u[3], P.c1b, P.c2b);
+                if (inner_row && (P.flags & QM_GAUSS)) sum_g += ssim_quot(u[0], u[1], u[2], u[3], P.c1a, P.c2a);
             }
         }
         if (want_u && oy >= 3 && oy < P.h - 3) {                        // block-uniform
@@ -201,12 +152,12 @@ __global__ __launch_bounds__(QM_TX) void k_qmap_cols(const unsigned char *__rest
             const int ncov = 49 * (int)t_q - sxsy, nvar = 49 * (int)t_p - ss;
             const double a1 = fma(2.0, (double)sxsy, P.k1u), a2 = fma(2.0, (double)ncov, P.k2u);
             const double b1 = (double)ss + P.k1u, b2 = (double)nvar + P.k2u;
-            sum_u += (a1 * a2) * qm_recip(b1 * b2);
+            sum_u += (a1 * a2) * ssim_recip(b1 * b2);
         }
     }
     if (!own) return;
     // column validity, once: the full-frame variant counts every image column, the cropped ones lose 5 / 3 per side
-    if (!(mx >= QM_R && mx < P.w - QM_R)) sum_g = 0.0;
+    if (!(mx >= S11_R && mx < P.w - S11_R)) sum_g = 0.0;
     if (!(mx >= 3 && mx < P.w - 3)) sum_u = 0.0;
     const size_t at = (size_t)blockIdx.x * (size_t)P.w + (size_t)mx;
     if (P.flags & QM_SSE) ws[(size_t)P.p_sse * (size_t)P.plane + at] = (unsigned long long)sse;
@@ -259,17 +210,6 @@ __global__ __launch_bounds__(256) void k_qmap_cells(const unsigned long long *__
         r.ssim_simple = sd[2][0];
         out[blockIdx.x] = r;
     }
-}
-
-void qm_gauss_taps(double *k6)
-{
-    double k[11], sum = 0.0;
-    for (int i = 0; i < 11; ++i) {
-        const double x = i - 5;
-        k[i] = std::exp(-0.5 / (1.5 * 1.5) * x * x);     // scipy.ndimage._gaussian_kernel1d(sigma=1.5, radius=5)
-        sum += k[i];
-    }
-    for (int j = 0; j <= 5; ++j) k6[j] = k[5 + j] / sum;
 }
 
 int qm_check_edges(const char *scope, const char *axis, const int *e, int n, int size)
@@ -345,18 +285,18 @@ int sr_quality_map_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const u
     P.same_c = (P.c1a == P.c1b && P.c2a == P.c2b) ? 1 : 0;
     P.k1u = 2401.0 * P.c1a;
     P.k2u = 2352.0 * P.c2a;
-    qm_gauss_taps(P.k);
+    gauss_taps(P.k);
     int nsel = 0;
     if (flags & QM_SSE) P.p_sse = nsel++;
     if (flags & QM_UNIFORM) P.p_u = nsel++;
     if (flags & QM_GAUSS) P.p_g = nsel++;
     if (flags & QM_SIMPLE) P.p_s = nsel++;
-    // row chunks: every cell row in equal pieces of at most QM_ROWS rows
+    // row chunks: every cell row in equal pieces of at most S11_ROWS rows
     std::vector<int> chunks, cstart((size_t)gh + 1);
     for (int gy = 0; gy < gh; ++gy) {
         cstart[(size_t)gy] = (int)(chunks.size() / 2);
         const int y0 = h_yedges[gy], rows = h_yedges[gy + 1] - y0;
-        const int n = (rows + QM_ROWS - 1) / QM_ROWS, step = (rows + n - 1) / n;
+        const int n = (rows + S11_ROWS - 1) / S11_ROWS, step = (rows + n - 1) / n;
         for (int r = 0; r < rows; r += step) {
             chunks.push_back(y0 + r);
             chunks.push_back(y0 + std::min(r + step, rows));
@@ -365,7 +305,6 @@ int sr_quality_map_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const u
     const size_t nchunk = chunks.size() / 2;
     cstart[(size_t)gh] = (int)nchunk;
     P.plane = (long long)nchunk * (long long)w;
-    auto up256 = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t off_chunks = 0, off_cstart = up256(chunks.size() * sizeof(int)),
                  off_xe = off_cstart + up256(cstart.size() * sizeof(int)),
                  off_out = off_xe + up256(((size_t)gw + 1) * sizeof(int)), off_ws = off_out + up256(ncell * sizeof(QmapRecord)),
@@ -381,7 +320,7 @@ int sr_quality_map_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const u
     if (e == hipSuccess) e = hipMemcpyAsync(dev + off_xe, h_xedges, ((size_t)gw + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         ProfScope ps(ctx, "qmap");
-        const dim3 grid((unsigned)nchunk, (unsigned)((w + QM_OUT - 1) / QM_OUT)), block(QM_TX);
+        const dim3 grid((unsigned)nchunk, (unsigned)((w + S11_OUT - 1) / S11_OUT)), block(S11_TX);
         if (cn == 3)
             hipLaunchKernelGGL(k_qmap_cols<3>, grid, block, 0, ctx->stream, d_a, (long long)stride_a, d_b, (long long)stride_b, P,
                                (const int2 *)(dev + off_chunks), (unsigned long long *)(dev + off_ws));

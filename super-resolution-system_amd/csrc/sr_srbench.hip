@@ -2,40 +2,33 @@
 // channels as they are, the BT.601 luma Y carried exactly, or MATLAB's rounded u8 luma.
 //
 // The definition is in include/sr_hip.h.  One kernel, one launch, one pass over both images for the squared differences AND
-// the Gaussian-11 SSIM (the march of k_msssim_level, sr_msssim.hip):
-//   k_srbench<MODE, PX>  A block owns SB_OUT map columns and one chunk of map rows of one plane (blockIdx.z: the channel in
-//     SR_BENCH_CHANNELS with 3 channels).  Each thread owns an input column and walks down the chunk: the vertical pass of
-//     its column comes from an 11-row register window of exact values, the horizontal pass reads the neighbours' vertical
-//     results through LDS (double-buffered by row parity: one barrier per row); the SSIM terms are added per column in row
-//     order.  The squared difference of a pixel is added by the block that owns it: input rows [y0, y1) of the chunk and the
-//     block's own SB_OUT columns, the last block of either axis taking the rest (the 10 halo rows / columns), so every
-//     cropped pixel is counted exactly once.  Per thread that sum stays an integer and becomes fp64 once.
+// the Gaussian-11 SSIM, on the column march of sr_ssim11.h (window, vertical pass, LDS rows, horizontal pass, quotient, block
+// tree are there).  What is this file's own:
+//   k_srbench<MODE, PX>  A block owns S11_OUT map columns and one chunk of map rows of one plane (blockIdx.z: the channel in
+//     SR_BENCH_CHANNELS with 3 channels), valid region only.  The SSIM terms are added per column in row order.  The squared
+//     difference of a pixel is added by the block that owns it: input rows [y0, y1) of the chunk and the block's own S11_OUT
+//     columns, the last block of either axis taking the rest (the 10 halo rows / columns), so every cropped pixel is counted
+//     exactly once.  Per thread that sum stays an integer and becomes fp64 once.
 //   The window, by mode:
-//     u8 planes (CHANNELS, Y_ROUND)  x | y << 14 packed, x y and x^2 + y^2 in 32 bits: 33 registers.
+//     u8 planes (CHANNELS, Y_ROUND)  the packed u8 window.
 //     Y                              X = 65481 R + 128553 G + 24966 B + 4080000 (= 255000 Y, < 2^26) and X' as 32-bit
-//                                    integers, X X' and X^2 + X'^2 as fp64, exact below 2^53 and formed once per pixel: 66
-//                                    registers.  SSIM is homogeneous of degree 0 in (planes, C1, C2): C1, C2 come in
+//                                    integers, X X' and X^2 + X'^2 as fp64, exact below 2^53 and formed once per pixel (the
+//                                    26-bit-luma window).  SSIM is homogeneous of degree 0 in (planes, C1, C2): C1, C2 come in
 //                                    multiplied by 255000^2 and the integers are filtered as they are.
 //   Pixels are read byte by byte: the crop is pointer arithmetic on the host and crop_border * cn has any residue mod 4.
-//   The block's 256 column sums go through a fixed tree, the per-block partials through reduce_partials: no floating-point
-//   atomics, equal inputs give equal bits.
+//   The per-block partials go through reduce_partials.
 // The partials are context scratch (sr_ctx::bench_ws), grown on demand: 16 bytes per block.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "sr_ctx.h"
 #include "sr_device.h"
+#include "sr_ssim11.h"
 
 namespace {
 
-constexpr int SB_TX = 256;                 // threads = input columns of a block
-constexpr int SB_R = 5;                    // radius of the Gaussian
-constexpr int SB_OUT = SB_TX - 2 * SB_R;   // map columns a block produces
-constexpr int SB_ROWS = 128;               // longest chunk of map rows (10 halo rows on top: 8 %)
-constexpr int SB_ROWS_MIN = 16;            // shortest chunk a small image is cut into ...
-constexpr int SB_BLOCKS = 1024;            // ... to reach this many blocks
-constexpr int SB_MIN_SIDE = 2 * SB_R + 1;
 constexpr int SB_YSCALE = 255000;          // X = SB_YSCALE * Y
 
 enum { SB_PLANE = 0, SB_YROUND = 1, SB_Y = 2 };       // what a kernel instantiation filters
@@ -51,7 +44,8 @@ struct SbPlan {
     int ch, cw, planes;
     uint64_t n_elems, n_map;
     int step, gx, gy;
-    size_t off_part, off_buf0, off_buf1, total;
+    PartialsLayout red;
+    size_t total;
 };
 
 __device__ __forceinline__ unsigned sb_x(const unsigned char *p)
@@ -75,66 +69,47 @@ __device__ __forceinline__ void sb_load(const unsigned char *__restrict__ pa, co
     }
 }
 
-// 1 / d: hardware estimate + one Newton step (relative error ~1e-15), d a product of positive SSIM terms
-__device__ __forceinline__ double sb_recip(double d)
-{
-    const double r = __builtin_amdgcn_rcp(d);
-    return fma(fma(-d, r, 1.0), r, r);
-}
-
 template <int MODE, int PX>
-__global__ __launch_bounds__(SB_TX) void k_srbench(const unsigned char *__restrict__ a, long long sa,
-                                                   const unsigned char *__restrict__ b, long long sb, SbParams P,
-                                                   double *__restrict__ part)
+__global__ __launch_bounds__(S11_TX) void k_srbench(const unsigned char *__restrict__ a, long long sa,
+                                                    const unsigned char *__restrict__ b, long long sb, SbParams P,
+                                                    double *__restrict__ part)
 {
     constexpr bool WIDE = MODE == SB_Y;
-    // vertical results of one row, double-buffered by row parity: one barrier per row
-    __shared__ double F[2][4][SB_TX];
+    __shared__ double F[2][4][S11_TX];
     const int t = threadIdx.x;
-    const int mh = P.h - 2 * SB_R;                                       // map rows
+    const int mh = P.h - 2 * S11_R;                                      // map rows
     const int y0 = (int)blockIdx.x * P.step, y1 = min(y0 + P.step, mh);  // this chunk's map rows = its first input rows
     const bool last_chunk = blockIdx.x == gridDim.x - 1, last_cols = blockIdx.y == gridDim.y - 1;
-    const int c = (int)blockIdx.y * SB_OUT + t;                          // the input column this thread filters vertically
+    const int c = (int)blockIdx.y * S11_OUT + t;                         // the input column this thread filters vertically
     const bool in = c < P.w;
-    const bool own = t < SB_OUT && c <= P.w - SB_MIN_SIDE;               // ... and the map column it produces
+    const bool own = t < S11_OUT && c <= P.w - S11_SIDE;                 // ... and the map column it produces
     // squared differences: input rows [y0, sse_end) of the block's own columns (the last block of either axis takes the rest)
     const int sse_rows = (last_chunk ? P.h : y1) - y0;
-    const bool sse_col = in && (t < SB_OUT || last_cols);
+    const bool sse_col = in && (t < S11_OUT || last_cols);
     const size_t coff = (size_t)(in ? c : 0) * PX + (MODE == SB_PLANE ? blockIdx.z : 0);
     const unsigned char *ca = a + coff, *cb = b + coff;
-    // rows lr - 10 .. lr of this column.  u8 planes: x | y << 14 packed (pair sums <= 510 stay in their fields)
-    unsigned wx[11], wy[WIDE ? 11 : 1], wq[WIDE ? 1 : 11], wp[WIDE ? 1 : 11];
-    double wqd[WIDE ? 11 : 1], wpd[WIDE ? 11 : 1];
-#pragma unroll
-    for (int i = 0; i < 11; ++i) {
-        wx[i] = 0u;
-        if constexpr (WIDE) { wy[i] = 0u; wqd[i] = 0.0; wpd[i] = 0.0; }
-        else { wq[i] = 0u; wp[i] = 0u; }
-    }
+    // u8 planes: wx holds x | y << 14 and wy is not used
+    using prod_t = std::conditional_t<WIDE, double, unsigned>;
+    Window11<unsigned> wx, wy;
+    Window11<prod_t> wq, wp;
     double sum_s = 0.0;
     unsigned long long sse = 0ull;                                       // one chunk column of (X - X')^2 < 2^52 fits
     const double kk[6] = {P.k[0], P.k[1], P.k[2], P.k[3], P.k[4], P.k[5]};
-    const int nrows = (y1 - y0) + 2 * SB_R;                              // input rows y0 .. y1 + 9 (< h)
+    const int nrows = (y1 - y0) + 2 * S11_R;                             // input rows y0 .. y1 + 9 (< h)
     unsigned nx = 0u, ny = 0u;
     if (in) sb_load<MODE>(ca + (size_t)y0 * (size_t)sa, cb + (size_t)y0 * (size_t)sb, nx, ny);
 #pragma unroll 1
     for (int lr = 0; lr < nrows; ++lr) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) {
-            wx[i] = wx[i + 1];
-            if constexpr (WIDE) { wy[i] = wy[i + 1]; wqd[i] = wqd[i + 1]; wpd[i] = wpd[i + 1]; }
-            else { wq[i] = wq[i + 1]; wp[i] = wp[i + 1]; }
-        }
         if constexpr (WIDE) {
             const double dx = (double)nx, dy = (double)ny;               // < 2^26: every product below is exact
-            wx[10] = nx;
-            wy[10] = ny;
-            wqd[10] = dx * dy;
-            wpd[10] = fma(dx, dx, dy * dy);                              // < 2^53
+            wx.push(nx);
+            wy.push(ny);
+            wq.push(dx * dy);
+            wp.push(fma(dx, dx, dy * dy));                               // < 2^53
         } else {
-            wx[10] = nx | (ny << 14);
-            wq[10] = nx * ny;
-            wp[10] = nx * nx + ny * ny;
+            wx.push(nx | (ny << 14));
+            wq.push(nx * ny);
+            wp.push(nx * nx + ny * ny);
         }
         if (lr < sse_rows && sse_col) {
             const long long d = (long long)nx - (long long)ny;
@@ -144,86 +119,24 @@ __global__ __launch_bounds__(SB_TX) void k_srbench(const unsigned char *__restri
             const size_t sy = (size_t)(y0 + min(lr + 1, nrows - 1));
             sb_load<MODE>(ca + sy * (size_t)sa, cb + sy * (size_t)sb, nx, ny);
         }
-        if (lr < 2 * SB_R) continue;                                     // block-uniform
+        if (lr < 2 * S11_R) continue;                                    // block-uniform
         const int pb = lr & 1;
         {
-            double hx, hy, hp, hq;
-            if constexpr (WIDE) {
-                hx = (double)wx[5] * kk[0];
-                hy = (double)wy[5] * kk[0];
-                hp = wpd[5] * kk[0];
-                hq = wqd[5] * kk[0];
-#pragma unroll
-                for (int j = 1; j <= SB_R; ++j) {
-                    hx = fma((double)(wx[5 - j] + wx[5 + j]), kk[j], hx);    // < 2^27
-                    hy = fma((double)(wy[5 - j] + wy[5 + j]), kk[j], hy);
-                    hp = fma(wpd[5 - j] + wpd[5 + j], kk[j], hp);
-                    hq = fma(wqd[5 - j] + wqd[5 + j], kk[j], hq);
-                }
-            } else {
-                hx = (double)(wx[5] & 0x3FFFu) * kk[0];
-                hy = (double)(wx[5] >> 14) * kk[0];
-                hp = (double)wp[5] * kk[0];
-                hq = (double)wq[5] * kk[0];
-#pragma unroll
-                for (int j = 1; j <= SB_R; ++j) {
-                    const unsigned sxy = wx[5 - j] + wx[5 + j];          // both images in one add
-                    hx = fma((double)(sxy & 0x3FFFu), kk[j], hx);
-                    hy = fma((double)(sxy >> 14), kk[j], hy);
-                    hp = fma((double)(wp[5 - j] + wp[5 + j]), kk[j], hp);
-                    hq = fma((double)(wq[5 - j] + wq[5 + j]), kk[j], hq);
-                }
-            }
-            F[pb][0][t] = hx; F[pb][1][t] = hy; F[pb][2][t] = hp; F[pb][3][t] = hq;
+            double hv[4];
+            if constexpr (WIDE) s11_col_pass<false>(wx, wy, wp, wq, kk, hv);   // pair sums < 2^27
+            else s11_col_pass_packed(wx, wp, wq, kk, hv);
+            s11_store_col(F[pb], t, hv);
         }
         __syncthreads();
         if (!own) continue;
         double u[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            double acc = F[pb][m][t + SB_R] * kk[0];
-#pragma unroll
-            for (int j = 1; j <= SB_R; ++j) acc = fma(F[pb][m][t + SB_R - j] + F[pb][m][t + SB_R + j], kk[j], acc);
-            u[m] = acc;
-        }
-        // u[2] = E[x^2 + y^2], u[3] = E[x y]
-        const double uxuy = u[0] * u[1], uu = fma(u[0], u[0], u[1] * u[1]);
-        const double a1 = fma(2.0, uxuy, P.c1), a2 = fma(2.0, u[3] - uxuy, P.c2);
-        const double b1 = uu + P.c1, b2 = (u[2] - uu) + P.c2;
-        sum_s += (a1 * a2) * sb_recip(b1 * b2);
+        s11_row_pass(F[pb], t + S11_R, kk, u);
+        sum_s += ssim_quot(u[0], u[1], u[2], u[3], P.c1, P.c2);
     }
-    // the block's column sums in a fixed tree (columns that produce nothing add 0)
-    __syncthreads();
-    double *sd0 = &F[0][0][0], *sd1 = &F[0][1][0];
-    sd0[t] = own ? sum_s : 0.0;
-    sd1[t] = (double)sse;
-    __syncthreads();
-    for (int s = SB_TX / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            sd0[t] += sd0[t + s];
-            sd1[t] += sd1[t + s];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        part[blk * 2 + 0] = sd0[0];
-        part[blk * 2 + 1] = sd1[0];
-    }
+    // columns that produce nothing add 0
+    s11_block_sum2(&F[0][0][0], &F[0][1][0], t, own ? sum_s : 0.0, (double)sse,
+                   part + (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2);
 }
-
-void sb_gauss_taps(double *k6)
-{
-    double k[11], sum = 0.0;
-    for (int i = 0; i < 11; ++i) {
-        const double x = i - 5;
-        k[i] = std::exp(-0.5 / (1.5 * 1.5) * x * x);     // scipy.ndimage._gaussian_kernel1d(sigma=1.5, radius=5)
-        sum += k[i];
-    }
-    for (int j = 0; j <= 5; ++j) k6[j] = k[5 + j] / sum;
-}
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 // the cropped size, counts, launch shape and scratch layout; every shape refusal of sr_bench_plan
 int sb_plan(const char *scope, int h, int w, int cn, int crop_border, int mode, SbPlan *p)
@@ -236,33 +149,22 @@ int sb_plan(const char *scope, int h, int w, int cn, int crop_border, int mode, 
     if (crop_border < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: crop_border must be >= 0 (got %d)", scope, crop_border);
     if (h < 1 || w < 1) return sr_set_error(SR_ERR_INVALID_ARG, "%s: need h, w >= 1", scope);
     const long long ch = (long long)h - 2LL * crop_border, cw = (long long)w - 2LL * crop_border;
-    if (ch < SB_MIN_SIDE || cw < SB_MIN_SIDE)
+    if (ch < S11_SIDE || cw < S11_SIDE)
         return sr_set_error(SR_ERR_SHAPE, "%s: image %dx%d with crop_border %d leaves %lldx%lld: both sides must be at least %d "
-                            "after the crop", scope, w, h, crop_border, std::max(cw, 0LL), std::max(ch, 0LL), SB_MIN_SIDE);
+                            "after the crop", scope, w, h, crop_border, std::max(cw, 0LL), std::max(ch, 0LL), S11_SIDE);
     memset(p, 0, sizeof(*p));
     p->ch = (int)ch;
     p->cw = (int)cw;
     p->planes = mode == SR_BENCH_CHANNELS ? cn : 1;
-    const int mh = p->ch - 2 * SB_R, mw = p->cw - 2 * SB_R;
+    const int mh = p->ch - 2 * S11_R, mw = p->cw - 2 * S11_R;
     p->n_elems = (uint64_t)p->ch * (uint64_t)p->cw * (uint64_t)p->planes;
     p->n_map = (uint64_t)mh * (uint64_t)mw * (uint64_t)p->planes;
-    // Chunks of at most SB_ROWS map rows; a small image takes shorter ones (down to SB_ROWS_MIN) until it has SB_BLOCKS
-    // blocks.  The cut depends on the size alone, never on the device: equal bits everywhere.
-    p->gy = (mw + SB_OUT - 1) / SB_OUT;
-    int rows = SB_ROWS;
-    while (rows > SB_ROWS_MIN && (long long)((mh + rows - 1) / rows) * p->gy * p->planes < SB_BLOCKS) rows /= 2;
-    const int n = (mh + rows - 1) / rows;
-    p->step = (mh + n - 1) / n;
-    p->gx = (mh + p->step - 1) / p->step;
-    const size_t nblk = (size_t)p->gx * (size_t)p->gy * (size_t)p->planes;
-    size_t off = 0;
-    p->off_part = off;
-    off += up256(nblk * 2 * sizeof(double));
-    p->off_buf0 = off;
-    off += up256((nblk / 1024 + 2) * 2 * sizeof(double));
-    p->off_buf1 = off;
-    off += up256((nblk / 1024 + 2) * 2 * sizeof(double));
-    p->total = off;
+    p->gy = (mw + S11_OUT - 1) / S11_OUT;
+    const ChunkCut cut = s11_chunk_cut(mh, (long long)p->gy * p->planes, false);
+    p->step = cut.step;
+    p->gx = cut.count;
+    p->red = s11_partials_layout(0, (size_t)p->gx * (size_t)p->gy * (size_t)p->planes);
+    p->total = p->red.end;
     return SR_OK;
 }
 
@@ -297,34 +199,21 @@ int sr_bench_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t
     const int64_t min_stride = (int64_t)w * cn;
     if (stride_a < min_stride || stride_b < min_stride) return sr_set_error(SR_ERR_SHAPE, "sr_bench_u8: stride smaller than a row");
     CTX_ENTER(ctx);
-    if (p.total > ctx->bench_ws_bytes) {
-        if (ctx->bench_ws) {
-            HIPCHK(stream_sync(ctx));
-            HIPCHK(hipFree(ctx->bench_ws));
-            ctx->bench_ws = nullptr;
-            ctx->bench_ws_bytes = 0;
-        }
-        hipError_t e = hipMalloc(&ctx->bench_ws, p.total);
-        if (e != hipSuccess) {
-            ctx->bench_ws = nullptr;
-            return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "sr_bench_u8: scratch of %zu bytes: %s", p.total,
-                                hipGetErrorString(e));
-        }
-        ctx->bench_ws_bytes = p.total;
-    }
+    rc = ctx_grow_ws(ctx, "sr_bench_u8", &ctx->bench_ws, &ctx->bench_ws_bytes, p.total);
+    if (rc) return rc;
     char *ws = (char *)ctx->bench_ws;
-    double *part = (double *)(ws + p.off_part), *buf0 = (double *)(ws + p.off_buf0), *buf1 = (double *)(ws + p.off_buf1);
+    double *part = (double *)(ws + p.red.off_part), *buf0 = (double *)(ws + p.red.off_buf0), *buf1 = (double *)(ws + p.red.off_buf1);
     SbParams P;
     memset(&P, 0, sizeof(P));
     P.h = p.ch; P.w = p.cw; P.step = p.step;
     const double scale = mode == SR_BENCH_Y ? (double)SB_YSCALE * (double)SB_YSCALE : 1.0;
     P.c1 = (0.01 * data_range) * (0.01 * data_range) * scale;
     P.c2 = (0.03 * data_range) * (0.03 * data_range) * scale;
-    sb_gauss_taps(P.k);
+    gauss_taps(P.k);
     // the crop: rows [cb, h - cb), columns [cb, w - cb) of both images
     const unsigned char *a = d_a + (size_t)crop_border * (size_t)stride_a + (size_t)crop_border * (size_t)cn;
     const unsigned char *b = d_b + (size_t)crop_border * (size_t)stride_b + (size_t)crop_border * (size_t)cn;
-    const dim3 grid((unsigned)p.gx, (unsigned)p.gy, (unsigned)p.planes), block(SB_TX);
+    const dim3 grid((unsigned)p.gx, (unsigned)p.gy, (unsigned)p.planes), block(S11_TX);
     double h_res[2];
     {
         ProfScope ps(ctx, "srbench");
