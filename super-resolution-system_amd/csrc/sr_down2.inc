@@ -38,9 +38,6 @@
 
 typedef unsigned short d2_us2 __attribute__((ext_vector_type(2)));
 
-#ifndef D2_OUT
-#define D2_OUT 48                    /* groups a wave stores (lanes 1 .. D2_OUT): 48 = whole 128-byte lines of G_1 (6) and G_2 (3) */
-#endif
 #ifndef D2_AHEAD
 #define D2_AHEAD 1                   /* level-1 row PAIRS a row's level-0 bytes are requested ahead */
 #endif
@@ -51,25 +48,7 @@ typedef unsigned short d2_us2 __attribute__((ext_vector_type(2)));
 #define D2_WAVES 4                   /* waves per SIMD the march is compiled for */
 #endif
 
-// the tiles this kernel takes: at least three levels, rows of levels 1 and 2 in use (a strip's row windows, or the whole
-// tile), the level-1 window covering what the level-2 window reads (the planner's hull does: sr_plan_windows), sizes the
-// march's shortcuts hold for
-__host__ __device__ __forceinline__ bool down2_takes(const TileDev &T)
-{
-    if (T.nl < 3) return false;
-    if (T.g0[1] >= T.g1[1] || T.g0[2] >= T.g1[2] || T.g0[0] >= T.g1[0]) return false;
-    if (T.H[1] < 4 || T.H[0] < 8) return false;
-    if (T.g0[1] > (2 * T.g0[2] - 2 > 0 ? 2 * T.g0[2] - 2 : 0)) return false;
-    if (T.g1[1] < (2 * T.g1[2] + 1 < T.H[1] ? 2 * T.g1[2] + 1 : T.H[1])) return false;
-    return down_ncg(T.W[0], T.W[1]) >= 1;
-}
-// the tile row strides the march's 32-bit row offsets hold for (h0: rows of level 0)
-static inline bool down2_stride_fits(long long stride, int h0)
-{
-    return stride > 0 && (unsigned long long)stride * (unsigned long long)(h0 + 2) < 0x7FFF0000ull;
-}
-// strips of a row of groups 0 .. ncg (group 0 is a border group: its lane stores nothing)
-__host__ __device__ __forceinline__ int down2_nstrip(int ncg) { return (ncg + D2_OUT) / D2_OUT; }
+// (D2_OUT and the rules the host evaluates, too -- down2_takes, down2_stride_fits, down2_nstrip, down2_cols_count: sr_blend_tables.h)
 
 // the value of the lane to the right / left (DPP wave_shl:1 / wave_shr:1 as in sr_march.inc, but with bound_ctrl: the end
 // lane reads 0 and no copy of the old value is needed -- the end lanes' results are never used here)
@@ -406,13 +385,6 @@ __global__ __launch_bounds__(64, D2_WAVES) void k_down2_march(const TileDev *__r
 // block per CU and pays a loaded-memory round trip (~18 us) per block generation: the first version (16 x 16 slots of which
 // 7-11 columns were in use, the planes one after the other: three round trips) took 0.26-0.30 ms in the image stream for
 // 0.03 ms of work.  Here every lane has a pixel, and its 75 loads (three planes) are issued before the first use.
-__host__ __device__ __forceinline__ int down2_cols_count(const TileDev &T)
-{
-    const int ncg = down_ncg(T.W[0], T.W[1]), w2 = T.W[2];
-    const int c_right = ncg >= 3 ? 2 * ncg : 4;
-    return (w2 < 4 ? w2 : 4) + (w2 > c_right ? w2 - c_right : 0);
-}
-
 template <int G1F>
 __global__ __launch_bounds__(256, 4) void k_down2_cols(const TileDev *__restrict__ tiles, float *__restrict__ arena)
 {

@@ -1,5 +1,5 @@
-// sr_engine.hip -- the blend engine on gfx950 (CDNA4): the blend plan, its pyramids and gathers (with sr_march.inc and
-// sr_down2.inc), the custom-weight blend, and their part of the C ABI in include/sr_hip.h.  (Context, device memory and
+// sr_engine.hip -- the blend engine on gfx950 (CDNA4): the blend plan (its tables come from sr_blend_plan.cpp), its pyramids and
+// gathers (with sr_march.inc and sr_down2.inc), the custom-weight blend, and their part of the C ABI in include/sr_hip.h.  (Context, device memory and
 // profiling are sr_runtime.hip; tile extract, the dense pyramid primitives, seam scan and feather merge are sr_tiles.hip;
 // the quality-assessment stage is sr_assess.hip.)
 //
@@ -21,12 +21,13 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <type_traits>
 #include <vector>
 
+#include "sr_blend_tables.h"
 #include "sr_ctx.h"
 #include "sr_device.h"
 
@@ -74,34 +75,7 @@ __device__ __forceinline__ float up_sample(const float *__restrict__ src, int hs
     return ((r1 + r2) * 4.0f) * (1.0f / 64.0f);
 }
 
-// ---------------------------------------------------------------------------------------------
-// blend plan tables
-// ---------------------------------------------------------------------------------------------
-struct TileDev {
-    int h, w, x, y;
-    int nl, fw, lut_off, cls;
-    int H[SR_MAX_LEVELS], W[SR_MAX_LEVELS], P[SR_MAX_LEVELS];
-    long long g_off[SR_MAX_LEVELS], r_off[SR_MAX_LEVELS], w_off[SR_MAX_LEVELS];
-    int g0[SR_MAX_LEVELS], g1[SR_MAX_LEVELS];  // G row windows
-    int r0[SR_MAX_LEVELS], r1[SR_MAX_LEVELS];  // R row windows
-};
-
-static_assert(sizeof(TileDev) % 16 == 0, "k_final_blk reads the leading {h,w,x,y} as one int4");
-
-// What the final gather needs of one tile, 80 bytes (wave-uniform: read through the scalar cache).
-struct FinalDesc {
-    int x, y, w, h;
-    int fw, lut_off, nl, pad0;
-    int H1, W1, P1, pad1;
-    long long g1, r1;      // float offsets of plane 0 of G_1 / R_1 in the arena (r1: read by no kernel since the unfused gather went)
-    const void *src;       // level-0 tile data (row 0, possibly virtual) and its row stride in bytes
-    long long stride;
-    int H2, W2, P2, pad2;  // level 2 (the fused gather builds R_1 from it on the fly)
-    long long g2, r2;      // float offsets of plane 0 of G_2 / R_2
-    long long w1;          // float offset of the weight level 1 of the tile's class
-    long long pad3;
-};
-static_assert(sizeof(FinalDesc) == 128, "FinalDesc layout");
+// (the blend plan tables TileDev, FinalDesc, EdgeBlock, MarchItem and RectItem: sr_blend_tables.h)
 
 // How the level-1 Gaussian planes G_1 lie in the arena.  G1_F32: fp32.  G1_U16: the integer 256 G_1 in 16 bits -- for u8
 // tiles it is exact and below 2^16 (sr_down2.inc), and k_down2_march holds it in that form anyway.  A 16-bit plane starts where
@@ -231,17 +205,6 @@ __global__ __launch_bounds__(256) void k_down(const TileDev *__restrict__ tiles,
 // seg_rows (output rows per segment, chosen per launch): longer segments amortise the 3-row prologue, shorter ones
 // keep enough cells in flight on the small levels.
 // ---------------------------------------------------------------------------------------------
-
-// number of interior column groups of a level: cg = 1 .. ncg
-__host__ __device__ __forceinline__ int down_ncg(int ws, int wo)
-{
-    const int a = ws >= 10 ? (ws - 10) / 8 : 0;     // 2 x0 + 9 <= ws - 1
-    const int b = wo >= 4 ? (wo - 4) / 4 : 0;       // x0 + 3 <= wo - 1
-    return a < b ? a : b;
-}
-
-struct TileDev;
-__host__ __device__ __forceinline__ bool down2_takes(const TileDev &T);     // sr_down2.inc
 
 // REFLECT_101 of a row index that leaves [0, n) by at most n - 1 (one bounce, no loop) -- the march's rows do by <= 2
 __device__ __forceinline__ int reflect101_once(int p, int n)
@@ -973,12 +936,7 @@ __device__ __forceinline__ void final_edge_block(const FinalDesc *__restrict__ d
 #ifndef SR_FINAL_WAVES
 #define SR_FINAL_WAVES 3
 #endif
-#ifndef FIN_TX
-#define FIN_TX 64                 /* threads across a regular block */
-#endif
-#define FIN_TY (256 / FIN_TX)
-#define FIN_BW (4 * FIN_TX)       /* canvas pixels per regular block */
-#define FIN_BH (2 * FIN_TY)
+// (the regular block FIN_BW x FIN_BH of FIN_TX x FIN_TY threads: sr_blend_tables.h)
 template <int DT, int CN>
 __global__ __launch_bounds__(256, SR_FINAL_WAVES) void k_final_fast(const FinalDesc *__restrict__ descs,
                                                        const int *__restrict__ cand_off, const int *__restrict__ cand_idx,
@@ -1036,25 +994,10 @@ __global__ __launch_bounds__(256, SR_FINAL_WAVES) void k_final_fast(const FinalD
 // The kernels of this path issue at one VALU instruction per 4 cycles and wave whatever the type, so the lever is the
 // instruction count: the two LDS windows are interleaved per pixel and every pyrUp step runs on (g, r) pairs in v_pk_*.
 // ---------------------------------------------------------------------------------------------
-#ifndef FU_THREADS
-#define FU_THREADS 256        /* threads (= 4 x 2 cells) per block */
-#endif
+// (FU_THREADS, the block shapes FU_* and the LDS plane FU_PLANE: sr_blend_tables.h -- the planner cuts its work lists by them)
 #ifndef FU_WAVES
 #define FU_WAVES 4           /* waves per SIMD the register allocation is held to */
 #endif
-#define FU_BW 128
-#define FU_BH (FU_THREADS / 16)             /* 32 cells across, FU_THREADS / 32 cell rows of 2 pixels */
-#define FU_E0H (FU_THREADS / 32)            /* edge shape 0: 256 x FU_E0H pixels (64 cells across) */
-#define FU_E1W 16                           /* edge shape 1: FU_E1W x FU_E1H pixels (4 cells across: a vertical tile edge
-                                               makes 1 - 3 of them border cells) */
-#define FU_E1H (FU_THREADS / 2)
-#define FU_LP 72              /* LDS pitch (floats) of a regular block's window: 18 patches of 4 columns */
-/* pixels per plane window (two floats each): rows = block rows / 2 + 3, rounded up to even; 72 (regular), 136 (shape 0) or
-   24 (shape 1) columns */
-#define FU_ROWS_EVEN(bh) ((((bh) / 2 + 3) + 1) / 2 * 2)
-#define FU_MAX3(a, b, c) ((a) > (b) ? ((a) > (c) ? (a) : (c)) : ((b) > (c) ? (b) : (c)))
-#define FU_E1LP (((FU_E1W / 2 + 2 + 3) + 3) / 4 * 4)      /* window columns of shape 1, whole patches */
-#define FU_PLANE FU_MAX3(FU_ROWS_EVEN(FU_BH) * 72, FU_ROWS_EVEN(FU_E0H) * 136, FU_ROWS_EVEN(FU_E1H) * FU_E1LP)
 
 // The level-1 window (tile coordinates) a block of bw x bh canvas pixels at tile-local (lxa, lya) samples: rows R0 ..,
 // columns C0 .. in patches of 2 rows x 4 columns (R0 even, C0 a multiple of 4: the alignment k_up_level_blk's threads have).
@@ -1511,19 +1454,6 @@ __global__ __launch_bounds__(FU_THREADS, FU_WAVES) void k_final_fused(const Fina
 // the edge blocks are not launched at all beside a march.  Threads are dealt column-major over tall rectangles: along a
 // vertical tile edge the kind of visit is then uniform per wave.
 // ---------------------------------------------------------------------------------------------
-struct RectItem {                    // 32 bytes, block-uniform
-    int x, y;                        // canvas pixel of the first cell (y includes row_begin)
-    int w, h;                        // cells across / down
-    int cand, ncand;                 // candidate tiles: rect_cand[cand .. cand + ncand), list order
-    int lp;                          // LDS pitch of the level-1 window (floats pairs per row)
-    int colmajor;                    // 1: thread -> (column, row) with rows fastest
-};
-static_assert(sizeof(RectItem) == 32, "RectItem layout");
-
-// window columns / rows fused_window can ask for, for a rectangle of w x h cells (host and static checks)
-static inline int rect_lp(int w) { return 4 * ((2 * w + 4) / 4) + 4; }
-static inline int rect_rows(int h) { return 2 * ((h + 2) / 2) + 2; }
-
 #ifndef FR_WAVES
 #define FR_WAVES FU_WAVES     /* waves per SIMD the register allocation of k_final_rect is held to */
 #endif
@@ -1651,335 +1581,30 @@ __global__ __launch_bounds__(256) void k_weighted_custom(const TileDev *__restri
 // ---------------------------------------------------------------------------------------------
 // blend plan (host object)
 // ---------------------------------------------------------------------------------------------
-struct sr_blend_plan {
+// The planner's tables (sr_blend_tables.h, built by sr_blend_plan.cpp) and where they are on the device: one allocation per
+// table -- the gathers read several of them through the scalar cache.
+struct sr_blend_plan : BlendTables {
     sr_ctx *ctx = nullptr;
-    int n = 0, cn = 3, canvas_h = 0, canvas_w = 0, levels = 6, wtype = 1, row_begin = 0, row_end = 0;
-    int max_nl = 1;
-    std::vector<TileDev> tiles;     // per tile
-    std::vector<TileDev> classes;   // per weight class (pseudo tiles, cn = 1, g_off = weight levels)
-    std::vector<SrWin> tile_rows;   // rows of the input tiles that are read
-    std::vector<float> luts;
-    size_t arena_floats = 0;
-    float *d_arena = nullptr;
+    std::vector<void *> owned;                          // every device allocation below
+    float *d_arena = nullptr, *d_luts = nullptr;
     TileDev *d_tiles = nullptr, *d_classes = nullptr;
-    TileSrc *d_srcs = nullptr;
+    TileSrc *d_srcs = nullptr;                          // d_srcs, d_fdesc: written per call
     FinalDesc *d_fdesc = nullptr;
-    std::vector<FinalDesc> fdesc;
-    int4 *d_edge_blocks = nullptr;                      // edge pass work list: x0, y0, shape, first candidate
-    int *d_edge_cand = nullptr;
-    int n_edge_blocks = 0;
-    int *d_cand_off = nullptr, *d_cand_idx = nullptr;   // per 256 x 8 block: candidate tiles (CSR, list order)
-    bool weights_ready = false;                         // weight pyramids of the classes are in the arena
-    // fused final gather (k_final_fused): its own block tables -- regular blocks of FU_BW x FU_BH, edge blocks of
-    // 256 x 16 / 32 x 128 pixels holding every 4 x 4 cell that has a border visit
-    bool fused = false;
-    int *d_fcand_off = nullptr, *d_fcand_idx = nullptr, *d_fedge_cand = nullptr;
-    int4 *d_fedge_blocks = nullptr;
-    int n_fedge_blocks = 0;
-    // marched zones (k_final_march): work items per tile count
-    bool march = false;
-    bool down2 = true;               // levels 1 and 2 of full-window u8 RGB tiles in one march (sr_down2.inc); SR_DOWN2=0: two launches
-    bool g1_u16 = false;             // G_1 of u8 tiles as 16-bit integers (G1_U16): every tile whose level 1 is in use takes that march; SR_G1_U16=0: fp32
+    int4 *d_edge_blocks = nullptr, *d_fedge_blocks = nullptr;       // EdgeBlock lists as the kernels read them
+    int *d_edge_cand = nullptr, *d_cand_off = nullptr, *d_cand_idx = nullptr, *d_fedge_cand = nullptr, *d_fcand_off = nullptr, *d_fcand_idx = nullptr, *d_rect_cand = nullptr;
     MarchItem *d_march_items[MARCH_NT + 1] = {nullptr};
-    int n_march_items[MARCH_NT + 1] = {0};
-    long long n_march_total = 0;
-    RectItem *d_rects = nullptr;                            // what the marched zones leave, as rectangles of cells (k_final_rect)
-    int *d_rect_cand = nullptr;
-    long long n_rects = 0;
-    std::vector<MarchItem> h_march_items[MARCH_NT + 1];     // host copies of the work lists (sr_blend_plan_march_items): a few KB
-    std::vector<RectItem> h_rects;
-    std::vector<char> sh_srcs, sh_fdesc;               // host shadows of d_srcs / d_fdesc (upload_if_changed)
+    RectItem *d_rects = nullptr;
+    bool weights_ready = false;                         // weight pyramids of the classes are in the arena
+    std::vector<char> sh_srcs, sh_fdesc;                // host shadows of d_srcs / d_fdesc (upload_if_changed)
     CachedTable subset_tabs[4];                         // compacted {TileDev, TileSrc} tables of recent tile subsets
     int subset_next = 0;
-    float *d_luts = nullptr;
-    // launch extents per level
-    int max_w[SR_MAX_LEVELS] = {0}, max_grows[SR_MAX_LEVELS] = {0}, max_rrows[SR_MAX_LEVELS] = {0};
-    int cmax_w[SR_MAX_LEVELS] = {0}, cmax_rows[SR_MAX_LEVELS] = {0};
+    ~sr_blend_plan()                                    // under the context's Guard
+    {
+        for (void *p : owned) (void)hipFree(p);
+        for (auto &t : subset_tabs) (void)hipFree(t.d);
+    }
 };
-
-static int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// ---------------------------------------------------------------------------------------------
-// Work lists of the marched gather (k_final_march, sr_march.inc).  A cell column (4 canvas pixels) / cell row (2 canvas
-// rows) is, for one tile, 0 = not touched, 1 = marchable (the cell is an interior visit and neither the level-1 columns /
-// rows the lane produces nor their level-2 taps meet a border rule), 2 = touched otherwise.  Between two consecutive class
-// changes of any tile the classes are constant, so the canvas falls into rectangles with a fixed list of visiting tiles;
-// a rectangle is marched when every tile that touches it is marchable in both directions.  Rectangles lose one cell
-// column per side to the halo lanes and are cut into strips of <= MARCH_CELLS cells and segments of <= MARCH_SEG steps
-// (an even number: an odd last cell row is left to the rectangles).
-// cover: [cell row][word of 32 cell columns] bits of the marched cells (row pitch nbx_r words).
-// ---------------------------------------------------------------------------------------------
-// The marched kernels' byte offsets are 32-bit (buffer instructions): one item of at most MARCH_SEG steps spans
-// 2 MARCH_SEG + 2 canvas rows, and the column offset the instruction adds stays below one more row; offsets stay below
-// MARCH_OFF_LIMIT.  plan_march applies the bound to what it knows (arena, dense fp32 canvas), blend_gather to the strides.
-static constexpr unsigned long long MARCH_SPAN_ROWS = 2ull * MARCH_SEG + 3ull, MARCH_OFF_LIMIT = 0xFFFF0000ull;
-
-static void plan_march(const sr_blend_plan *P, int nbx_r, int nby_r, std::vector<MarchItem> (&items)[MARCH_NT + 1],
-                       std::vector<unsigned> &cover)
-{
-    const int rows = P->row_end - P->row_begin, cw = P->canvas_w, n = P->n;
-    const int ncx = cw / 4, ncy = rows / 2;                    // whole cells only: ragged ends are border visits
-    const int CPB = FU_BH / 2;                                 // cell rows per regular block
-    cover.assign((size_t)nbx_r * nby_r * CPB, 0u);                         // [cell row][block column]: cell column bits (1 = marched)
-    // the marched kernels address the arena and a tile's pixels with 32-bit byte offsets (buffer instructions)
-    bool fits32 = P->arena_floats * sizeof(float) < MARCH_OFF_LIMIT && (unsigned long long)cw * P->cn * 4ull * MARCH_SPAN_ROWS < MARCH_OFF_LIMIT;
-    for (int t = 0; t < n && fits32; ++t) fits32 = (unsigned long long)P->tiles[t].h * P->tiles[t].w * P->cn * 4ull < 0x7FFF0000ull;
-    // The march is four launches of long work items: it wins on a big canvas (200 MP: 1.12 against 1.22 ms for the block kernel
-    // alone) and loses on a small one, where every launch is a few short items deep -- a rank's strip of a world of 4 / 8:
-    // 0.39 / 0.27 ms against 0.33 / 0.18 (tools/virtual_scaling.py, profiles/r04_virtual_scaling.json); even at 100 MP.
-    // SR_MARCH=2 marches whatever the size.
-    const char *env_force = std::getenv("SR_MARCH");               // read per plan: the tests switch it
-    const bool big = (env_force && env_force[0] == '2') || (double)rows * (double)cw >= 90e6;
-    const bool on = P->march && big && fits32 && n <= 128 && ncx >= 3 && ncy >= 2;
-    if (on) {
-        auto xclass = [&](const TileDev &T, int x0) -> unsigned char {
-            const long long lx0 = (long long)x0 - T.x;
-            if (lx0 + 4 <= 0 || lx0 >= T.w) return 0;
-            if (T.nl < 3 || lx0 < 0 || lx0 + 3 >= T.w) return 2;
-            const long long c0 = (lx0 - 1) >> 1, n0 = c0 >> 1;
-            if (c0 < 0 || c0 + 3 > T.W[1] - 1 || n0 + 2 > T.W[2] - 1) return 2;
-            return 1;
-        };
-        auto yclass = [&](const TileDev &T, int y0) -> unsigned char {
-            const long long ly0 = (long long)y0 - T.y;
-            if (ly0 + 2 <= 0 || ly0 >= T.h) return 0;
-            if (T.nl < 3 || ly0 < 0 || ly0 + 1 >= T.h) return 2;
-            const long long r0 = (ly0 - 1) >> 1;
-            if (r0 < 1 || r0 + 2 > T.H[1] - 1 || ((r0 + 1) >> 1) + 2 > T.H[2] - 1) return 2;
-            return 1;
-        };
-        std::vector<std::vector<unsigned char>> xc(n, std::vector<unsigned char>(ncx)), yc(n, std::vector<unsigned char>(ncy));
-        std::vector<int> xb{0, ncx}, yb{0, ncy};
-        for (int t = 0; t < n; ++t) {
-            const TileDev &T = P->tiles[t];
-            for (int c = 0; c < ncx; ++c) {
-                xc[t][c] = xclass(T, 4 * c);
-                if (c && xc[t][c] != xc[t][c - 1]) xb.push_back(c);
-            }
-            for (int c = 0; c < ncy; ++c) {
-                yc[t][c] = yclass(T, P->row_begin + 2 * c);
-                if (c && yc[t][c] != yc[t][c - 1]) yb.push_back(c);
-            }
-        }
-        std::sort(xb.begin(), xb.end());
-        xb.erase(std::unique(xb.begin(), xb.end()), xb.end());
-        std::sort(yb.begin(), yb.end());
-        yb.erase(std::unique(yb.begin(), yb.end()), yb.end());
-        struct Strip { int ca, cb, ya, ye, nt, tile[4]; };
-        std::vector<Strip> strips;
-        std::vector<int> vis, run_vis;
-        for (size_t iy = 0; iy + 1 < yb.size(); ++iy) {
-            const int ya = yb[iy], ye = ya + (yb[iy + 1] - ya) / 2 * 2;      // an even number of steps (the loop is unrolled by two)
-            if (ye - ya < 2) continue;
-            // runs of consecutive x intervals with the same (valid) tile list
-            int run_a = -1, run_b = -1;
-            auto flush = [&]() {
-                if (run_a < 0) return;
-                const int ua = run_a + 1, ub = run_b - 1;          // one cell column per side goes to the halo lanes
-                const int nu = ub - ua, nt = (int)run_vis.size();
-                if (nu >= 1) {
-                    const int ns = (nu + MARCH_CELLS - 1) / MARCH_CELLS;
-                    for (int si = 0; si < ns; ++si) {
-                        const int ca = ua + (int)((long long)nu * si / ns), cb = ua + (int)((long long)nu * (si + 1) / ns);
-                        Strip st;
-                        st.ca = ca; st.cb = cb; st.ya = ya; st.ye = ye; st.nt = nt;
-                        for (int k = 0; k < 4; ++k) st.tile[k] = k < nt ? run_vis[k] : 0;
-                        strips.push_back(st);
-                    }
-                    for (int cy = ya; cy < ye; ++cy)
-                        for (int c = ua; c < ub; ++c) cover[(size_t)cy * nbx_r + c / 32] |= 1u << (c & 31);
-                }
-                run_a = -1;
-            };
-            for (size_t ix = 0; ix + 1 < xb.size(); ++ix) {
-                vis.clear();
-                bool ok = true;
-                for (int t = 0; t < n && ok; ++t) {
-                    const unsigned char cx = xc[t][xb[ix]], cy = yc[t][yb[iy]];
-                    if (cx == 0 || cy == 0) continue;
-                    if (cx == 1 && cy == 1) vis.push_back(t);
-                    else ok = false;
-                }
-                ok = ok && !vis.empty() && (int)vis.size() <= MARCH_NT;
-                if (ok && run_a >= 0 && vis == run_vis) {
-                    run_b = xb[ix + 1];
-                    continue;
-                }
-                flush();
-                if (ok) {
-                    run_a = xb[ix];
-                    run_b = xb[ix + 1];
-                    run_vis = vis;
-                }
-            }
-            flush();
-        }
-        // Segment length per tile count: as long as MARCH_SEG steps where that still leaves every wave slot of the GPU a few
-        // items (the warm-up of an item costs about two steps), shorter where a list is small -- a short list of long items
-        // is a latency-bound launch of one or two rounds.
-        long long steps_of[MARCH_NT + 1] = {0}, cells_of[MARCH_NT + 1] = {0};
-        for (const Strip &st : strips) {
-            steps_of[st.nt] += st.ye - st.ya;
-            cells_of[st.nt] += (long long)(st.ye - st.ya) * (st.cb - st.ca);
-        }
-        for (int nt = 1; nt <= MARCH_NT; ++nt) {
-            if (!steps_of[nt]) continue;
-            // Rounds per list, measured (profiles/r04_e_gather_sweep.txt): four for the 1-tile list, three for the 2-tile list, two
-            // for the short 3- / 4-tile lists (an item's warm-up is ~2.5 steps: at six rounds the 4-tile list was cut into 8-step
-            // items); the tapered end of a list (below) is what makes long items affordable.
-            // SR_MARCH_ROUNDS="r1,r2,r4": A/B runs.
-            double rounds = nt >= 3 ? MARCH_ROUNDS_N : (nt == 2 ? MARCH_ROUNDS_2 : MARCH_ROUNDS);
-            if (const char *e_r = std::getenv("SR_MARCH_ROUNDS")) {
-                double r[3] = {0, 0, 0};
-                const int got = sscanf(e_r, "%lf,%lf,%lf", &r[0], &r[1], &r[2]);
-                const int k = nt == 1 ? 0 : (nt == 2 ? 1 : 2);
-                if (got >= 1 && r[std::min(k, got - 1)] > 0) rounds = r[std::min(k, got - 1)];
-            }
-            const long long want_items = std::max<long long>((long long)((double)(P->ctx->num_cu * 8 / nt) * rounds), 1);   // rounds at two waves per SIMD
-            int seg = (int)std::min<long long>(MARCH_SEG, std::max<long long>(8, steps_of[nt] / want_items));
-            seg = seg / 2 * 2;
-            // The items of a list run in list order, a few rounds of them: the last round leaves the GPU emptier and emptier
-            // while its long items finish (half an item's duration per launch, ~30 us of march1's 300).  So the list ends
-            // with short items: the last `tail` strip-steps (about one round of full-length items) are cut into segments of
-            // half the length, the last quarter of those into the shortest ones (8 steps: an item's warm-up is ~2).
-            // SR_MARCH_TAIL=0: uniform segments (A/B runs).  Which segment a canvas row falls into changes no value.
-            const bool taper = !(std::getenv("SR_MARCH_TAIL") && atoi(std::getenv("SR_MARCH_TAIL")) == 0);   // read per plan
-            const long long slots = std::max<long long>((long long)P->ctx->num_cu * 8 / nt, 1);
-            const long long tail = taper && seg > 8 ? std::min<long long>(slots * seg, steps_of[nt] / 3) : 0;
-            long long done = 0;
-            for (const Strip &st : strips) {
-                if (st.nt != nt) continue;
-                for (int sy = st.ya; sy < st.ye;) {
-                    const long long left = steps_of[nt] - done;
-                    int sg = seg;
-                    if (left <= tail / 4) sg = 8;
-                    else if (left <= tail) sg = std::max(8, seg / 4 * 2);
-                    MarchItem it;
-                    memset(&it, 0, sizeof(it));
-                    it.x0 = 4 * (st.ca - 1);
-                    it.y0 = P->row_begin + 2 * sy;
-                    it.ncell = st.cb - st.ca;
-                    it.nstep = std::min(sg, st.ye - sy);
-                    for (int k = 0; k < nt; ++k) it.tile[k] = st.tile[k];
-                    items[nt].push_back(it);
-                    sy += it.nstep;
-                    done += it.nstep;
-                }
-            }
-            if (std::getenv("SR_MARCH_STATS"))
-                fprintf(stderr, "[march] %d-tile zones: %lld strip-steps, %lld cells (%.2f %% of %d x %d), segments of %d steps, %zu items\n", nt,
-                        steps_of[nt], cells_of[nt], 100.0 * (double)cells_of[nt] / ((double)ncx * ncy), ncx, ncy, seg, items[nt].size());
-        }
-    }
-}
-
-// What the marched zones leave, cut into rectangles of cells for k_final_rect: every cell row's runs of unmarched cells --
-// a narrow run (<= 8 cells: a band along a vertical tile edge) whole, a wide one in pieces that end on multiples of 32 cells
-// -- stacked downwards while the next row holds the same piece and the rectangle still fits 256 threads and the LDS window.
-// cover: plan_march's bitmap (row pitch nbx_r words); ragged cells at the right / bottom end are unmarched cells like any other.
-static void plan_rects(const sr_blend_plan *P, int nbx_r, const std::vector<unsigned> &cover, std::vector<RectItem> &rects,
-                       std::vector<int> &rcand)
-{
-    const int rows = P->row_end - P->row_begin, cw = P->canvas_w;
-    const int ncxp = (cw + 3) / 4, ncyp = (rows + 1) / 2;
-    const char *e_cells = std::getenv("SR_RECT_CELLS");                   // A/B runs: most cells per rectangle (<= 256 threads)
-    const int max_cells = e_cells && atoi(e_cells) >= 32 ? std::min(atoi(e_cells), 256) : 256;
-    // window pitch: two pixel pairs more than needed, so that consecutive rows start 36 (not 32) dwords apart for a band 5 cells
-    // wide -- column-major lanes read the same columns of consecutive rows
-    const int pad = 2;
-    auto hmax = [max_cells, pad](int w) {
-        int h = std::max(max_cells / w, 1);
-        while (h > 1 && rect_rows(h) * (rect_lp(w) + pad) > FU_PLANE) --h;
-        return h;
-    };
-    struct Open { int ya, h; };
-    std::map<std::pair<int, int>, Open> open;                     // (first cell column, end) -> rectangle still growing
-    auto emit = [&](int xa, int xb, int ya, int h) {
-        RectItem it;
-        it.x = 4 * xa;
-        it.y = P->row_begin + 2 * ya;
-        it.w = xb - xa;
-        it.h = h;
-        it.cand = (int)rcand.size();
-        const long long bx0 = it.x, bx1 = std::min<long long>(bx0 + 4ll * it.w, cw);
-        const long long by0 = it.y, by1 = std::min<long long>(by0 + 2ll * it.h, P->row_end);
-        for (int t = 0; t < P->n; ++t) {
-            const TileDev &T = P->tiles[t];
-            if (T.x < bx1 && (long long)T.x + T.w > bx0 && T.y < by1 && (long long)T.y + T.h > by0) rcand.push_back(t);
-        }
-        it.ncand = (int)rcand.size() - it.cand;
-        it.lp = rect_lp(it.w) + pad;
-        it.colmajor = it.h > it.w ? 1 : 0;
-        rects.push_back(it);
-    };
-    std::vector<std::pair<int, int>> segs;
-    std::map<std::pair<int, int>, std::pair<int, int>> wide;      // wide run (first cell, end) -> (piece width, last row seen)
-    auto unmarched = [&](int cy, int cx) { return !((cover[(size_t)cy * nbx_r + (cx >> 5)] >> (cx & 31)) & 1u); };
-    auto run_is = [&](int cy, int xa, int xe) {                   // row cy holds exactly the run [xa, xe) of unmarched cells
-        if (xa > 0 && unmarched(cy, xa - 1)) return false;
-        if (xe < ncxp && unmarched(cy, xe)) return false;
-        for (int c = xa; c < xe; ++c)
-            if (!unmarched(cy, c)) return false;
-        return true;
-    };
-    for (int cy = 0; cy < ncyp; ++cy) {
-        segs.clear();
-        const unsigned *row = cover.data() + (size_t)cy * nbx_r;
-        for (int cx = 0; cx < ncxp;) {
-            const unsigned wd = row[cx >> 5];
-            if ((cx & 31) == 0 && wd == 0xFFFFFFFFu) { cx += 32; continue; }
-            if ((wd >> (cx & 31)) & 1u) { ++cx; continue; }
-            int xe = cx;
-            while (xe < ncxp && !((row[xe >> 5] >> (xe & 31)) & 1u)) ++xe;
-            if (xe - cx <= 8) segs.emplace_back(cx, xe);
-            else {
-                // a wide run: pieces as wide as the band's height allows (a band 3-4 cell rows high along a horizontal tile
-                // edge: 60 cells x 4 rows instead of 32 x 4 -- fewer, fuller items); the width is chosen where the band starts
-                // and kept for its rows, so that the pieces of consecutive rows stack
-                int pw = 32;
-                auto rec = wide.find({cx, xe});
-                if (rec != wide.end() && rec->second.second == cy - 1) {
-                    pw = rec->second.first;
-                    rec->second.second = cy;
-                } else {
-                    int H = 1;
-                    while (H < 9 && cy + H < ncyp && run_is(cy + H, cx, xe)) ++H;
-                    if (H <= 8) {
-                        pw = std::min(64, 256 / H) / 4 * 4;
-                        while (pw > 32 && rect_rows(H) * (rect_lp(pw) + pad) > FU_PLANE) pw -= 4;
-                        pw = std::max(pw, 32);
-                    }
-                    wide[{cx, xe}] = {pw, cy};
-                }
-                for (int a = cx; a < xe;) {
-                    const int b = std::min(xe, (a / pw + 1) * pw);
-                    segs.emplace_back(a, b);
-                    a = b;
-                }
-            }
-            cx = xe;
-        }
-        std::map<std::pair<int, int>, Open> next;
-        for (const auto &sg : segs) {
-            auto f = open.find(sg);
-            if (f != open.end() && f->second.h < hmax(sg.second - sg.first)) {
-                next[sg] = Open{f->second.ya, f->second.h + 1};
-                open.erase(f);
-            } else {
-                next[sg] = Open{cy, 1};                               // (a full one stays in `open` and is closed below)
-            }
-        }
-        for (const auto &o : open) emit(o.first.first, o.first.second, o.second.ya, o.second.h);
-        open.swap(next);
-    }
-    for (const auto &o : open) emit(o.first.first, o.first.second, o.second.ya, o.second.h);
-    if (std::getenv("SR_MARCH_STATS")) {
-        long long cells = 0;
-        for (const RectItem &r : rects) cells += (long long)r.w * r.h;
-        fprintf(stderr, "[march] rectangles of the remainder: %zu items, %lld cells (%.1f per item), %zu candidate visits\n", rects.size(), cells,
-                rects.empty() ? 0.0 : (double)cells / (double)rects.size(), rcand.size());
-    }
-}
+static_assert(sizeof(int4) == sizeof(EdgeBlock), "the kernels read an EdgeBlock as one int4");
 
 bool plan_describe(const sr_blend_plan *p, sr_ctx **ctx, int *n, int *cn)
 {
@@ -1988,6 +1613,27 @@ bool plan_describe(const sr_blend_plan *p, sr_ctx **ctx, int *n, int *cn)
     if (n) *n = p->n;
     if (cn) *cn = p->cn;
     return true;
+}
+
+// The environment switches of a plan: read per plan (the tests flip them between plans), and nowhere else.
+static BlendSwitches switches_from_env()
+{
+    auto is = [](const char *name, char c) { const char *e = std::getenv(name); return e && e[0] == c; };
+    BlendSwitches sw;
+    sw.march = !is("SR_MARCH", '0');                  // SR_MARCH=0: every zone through k_final_fused (A/B runs)
+    sw.march_force = is("SR_MARCH", '2');             // SR_MARCH=2: marches whatever the size
+    sw.down2 = !is("SR_DOWN2", '0');                  // SR_DOWN2=0: levels 1 and 2 in two launches
+    sw.g1_u16 = !is("SR_G1_U16", '0');                // SR_G1_U16=0: G_1 in fp32
+    const char *e_tail = std::getenv("SR_MARCH_TAIL"), *e_rounds = std::getenv("SR_MARCH_ROUNDS"), *e_cells = std::getenv("SR_RECT_CELLS");
+    sw.march_taper = !(e_tail && atoi(e_tail) == 0);  // SR_MARCH_TAIL=0: uniform segments (A/B runs)
+    sw.stats = std::getenv("SR_MARCH_STATS") != nullptr;
+    if (e_rounds) {                                   // SR_MARCH_ROUNDS="r1,r2,r4": the last value given holds for the lists after it
+        double r[3] = {0, 0, 0};
+        const int got = sscanf(e_rounds, "%lf,%lf,%lf", &r[0], &r[1], &r[2]);
+        for (int k = 0; k < 3 && got >= 1; ++k) sw.march_rounds[k] = std::max(r[std::min(k, got - 1)], 0.0);
+    }
+    if (e_cells && atoi(e_cells) >= 32) sw.rect_cells = std::min(atoi(e_cells), 256);      // A/B runs: most cells per rectangle
+    return sw;
 }
 
 extern "C" {
@@ -2009,31 +1655,8 @@ int sr_blend_plan_destroy(sr_blend_plan *plan)
         std::lock_guard<std::mutex> lk(g_reg_mu);
         if (!g_live_plan.erase(plan)) return SR_OK;          // already destroyed (with its context)
     }
-    sr_ctx *ctx = plan->ctx;
-    {
-        Guard g(ctx);
-        (void)hipStreamSynchronize(ctx->stream);
-        if (plan->d_arena) (void)hipFree(plan->d_arena);
-        if (plan->d_tiles) (void)hipFree(plan->d_tiles);
-        if (plan->d_classes) (void)hipFree(plan->d_classes);
-        if (plan->d_srcs) (void)hipFree(plan->d_srcs);
-        if (plan->d_fdesc) (void)hipFree(plan->d_fdesc);
-        if (plan->d_edge_blocks) (void)hipFree(plan->d_edge_blocks);
-        if (plan->d_edge_cand) (void)hipFree(plan->d_edge_cand);
-        if (plan->d_cand_off) (void)hipFree(plan->d_cand_off);
-        if (plan->d_fcand_off) (void)hipFree(plan->d_fcand_off);
-        if (plan->d_fcand_idx) (void)hipFree(plan->d_fcand_idx);
-        if (plan->d_fedge_blocks) (void)hipFree(plan->d_fedge_blocks);
-        if (plan->d_fedge_cand) (void)hipFree(plan->d_fedge_cand);
-        if (plan->d_rects) (void)hipFree(plan->d_rects);
-        if (plan->d_rect_cand) (void)hipFree(plan->d_rect_cand);
-        for (int k = 0; k <= MARCH_NT; ++k)
-            if (plan->d_march_items[k]) (void)hipFree(plan->d_march_items[k]);
-        for (auto &t : plan->subset_tabs)
-            if (t.d) (void)hipFree(t.d);
-        if (plan->d_cand_idx) (void)hipFree(plan->d_cand_idx);
-        if (plan->d_luts) (void)hipFree(plan->d_luts);
-    }
+    Guard g(plan->ctx);
+    (void)hipStreamSynchronize(plan->ctx->stream);
     delete plan;
     return SR_OK;
 }
@@ -2044,408 +1667,62 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
     CTX_ENTER(ctx);
     if (!out) return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_create: null out");
     *out = nullptr;
-    if (!h_tiles || n < 1 || n > 65535) return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_create: need 1..65535 tiles");
-    if (cn < 1 || cn > 4) return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_create: channels must be 1..4");
-    if (canvas_h < 1 || canvas_w < 1) return sr_set_error(SR_ERR_SHAPE, "sr_blend_plan_create: empty canvas");
-    if (levels < 1) return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_create: levels must be >= 1");
-    if (weight_type < 0 || weight_type > SR_W_ONES) return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_create: bad weight type");
     row_begin = std::max(row_begin, 0);
     row_end = std::min(row_end, canvas_h);
     if (row_begin > row_end) row_begin = row_end;
-
-    sr_blend_plan *P = new sr_blend_plan();
+    std::unique_ptr<sr_blend_plan> P(new sr_blend_plan());      // an early return frees what it owns
     P->ctx = ctx;
-    P->n = n;
-    P->cn = cn;
-    P->canvas_h = canvas_h;
-    P->canvas_w = canvas_w;
-    P->levels = std::min(levels, SR_MAX_LEVELS);
-    P->wtype = weight_type;
-    P->row_begin = row_begin;
-    P->row_end = row_end;
-    P->tiles.resize(n);
-    P->tile_rows.resize(n);
-    {
-        P->fused = cn == 3 || cn == 1;
-        const char *env2 = std::getenv("SR_MARCH");
-        P->march = P->fused && !(env2 && env2[0] == '0');               // SR_MARCH=0: every zone through k_final_fused (A/B runs)
-        const char *env3 = std::getenv("SR_DOWN2");
-        P->down2 = !(env3 && env3[0] == '0');
-    }
-
-    std::map<std::pair<int, int>, int> cls_of;
-    std::vector<SrTileLevels> lv(n);
-    size_t off = 0;
-    for (int t = 0; t < n; ++t) {
-        const sr_tile_rect &r = h_tiles[t];
-        if (r.w < 1 || r.h < 1 || r.x < 0 || r.y < 0) {
-            delete P;
-            return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_create: tile %d has bad rectangle (%d,%d,%d,%d)", t, r.x,
-                                r.y, r.w, r.h);
-        }
-        if (std::min(r.w, r.h) < 8 && weight_type != SR_W_ONES) {
-            delete P;
-            return sr_set_error(SR_ERR_INVALID_ARG,
-                                "sr_blend_plan_create: tile %d is %dx%d; min side < 8 gives the reference a zero "
-                                "feather width (NaN weights)", t, r.w, r.h);
-        }
-        sr_plan_windows(r.h, r.w, r.y, P->levels, row_begin, row_end, canvas_h, &lv[t]);
-        TileDev &T = P->tiles[t];
-        memset(&T, 0, sizeof(T));
-        T.h = r.h;
-        T.w = r.w;
-        T.x = r.x;
-        T.y = r.y;
-        T.nl = lv[t].nl;
-        T.fw = std::max(std::min(r.w, r.h) / 8, 1);
-        P->max_nl = std::max(P->max_nl, T.nl);
-        auto key = std::make_pair(r.h, r.w);
-        auto it = cls_of.find(key);
-        if (it == cls_of.end()) {
-            const int id = (int)P->classes.size();
-            cls_of[key] = id;
-            TileDev C;
-            memset(&C, 0, sizeof(C));
-            C.h = r.h;
-            C.w = r.w;
-            C.nl = T.nl;
-            C.fw = T.fw;
-            C.lut_off = (int)P->luts.size();
-            P->luts.resize(P->luts.size() + T.fw + 1);
-            int rc = sr_weight_lut(T.fw, weight_type, P->luts.data() + C.lut_off);
-            if (rc) {
-                delete P;
-                return rc;
-            }
-            for (int i = 0; i < T.nl; ++i) {
-                C.H[i] = lv[t].H[i];
-                C.W[i] = lv[t].W[i];
-                C.P[i] = round_up(C.W[i], i == 1 ? 64 : 32);
-                C.g0[i] = C.g1[i] = 0;
-                if (i >= 1) {
-                    C.g_off[i] = (long long)off;
-                    off += (size_t)C.H[i] * C.P[i];
-                }
-            }
-            P->classes.push_back(C);
-            T.cls = id;
-        } else {
-            T.cls = it->second;
-        }
-        TileDev &C = P->classes[T.cls];
-        T.lut_off = C.lut_off;
-        for (int i = 0; i < T.nl; ++i) {
-            T.H[i] = lv[t].H[i];
-            T.W[i] = lv[t].W[i];
-            T.P[i] = round_up(T.W[i], i == 1 ? 64 : 32);       // level 1: rows of 16-bit planes start on 128-byte lines, too
-            T.g0[i] = lv[t].gw[i].a;
-            T.g1[i] = lv[t].gw[i].b;
-            T.r0[i] = lv[t].rw[i].a;
-            T.r1[i] = lv[t].rw[i].b;
-            T.w_off[i] = C.g_off[i];
-            if (i >= 1) {
-                // weight level i must cover every member tile's G window (hull)
-                if (T.g0[i] < T.g1[i]) {
-                    if (C.g0[i] >= C.g1[i]) {
-                        C.g0[i] = T.g0[i];
-                        C.g1[i] = T.g1[i];
-                    } else {
-                        C.g0[i] = std::min(C.g0[i], T.g0[i]);
-                        C.g1[i] = std::max(C.g1[i], T.g1[i]);
-                    }
-                }
-                const bool active = T.g0[i] < T.g1[i];
-                T.g_off[i] = (long long)off;
-                if (active) off += (size_t)cn * T.H[i] * T.P[i];
-                T.r_off[i] = (long long)off;
-                if (active && !(P->fused && i == 1)) off += (size_t)cn * T.H[i] * T.P[i];     // fused gather: R_1 lives in LDS only
-            }
-        }
-        P->tile_rows[t] = lv[t].gw[0];
-    }
-    for (int i = 0; i < SR_MAX_LEVELS; ++i) {
-        for (auto &T : P->tiles) {
-            if (i >= T.nl) continue;
-            P->max_w[i] = std::max(P->max_w[i], T.W[i]);
-            P->max_grows[i] = std::max(P->max_grows[i], T.g1[i] - T.g0[i]);
-            P->max_rrows[i] = std::max(P->max_rrows[i], T.r1[i] - T.r0[i]);
-        }
-        for (auto &C : P->classes) {
-            if (i >= C.nl) continue;
-            P->cmax_w[i] = std::max(P->cmax_w[i], C.W[i]);
-            P->cmax_rows[i] = std::max(P->cmax_rows[i], C.g1[i] - C.g0[i]);
-        }
-    }
-    P->arena_floats = off;
-    {
-        // the plan's part of the G_1 format: the only writer of 16-bit planes is k_down2_march, the readers are the fused gather's
-        const char *env4 = std::getenv("SR_G1_U16");
-        bool ok = P->down2 && P->fused && cn == 3 && !(env4 && env4[0] == '0') && off * sizeof(float) < 0xFFFF0000ull, any = false;
-        for (const TileDev &T : P->tiles) {
-            if (T.nl < 2 || T.g0[1] >= T.g1[1]) continue;            // no level 1, or none of its rows in use
-            any = true;
-            ok = ok && down2_takes(T);
-        }
-        P->g1_u16 = ok && any;
-    }
-
-    auto fail = [&](hipError_t e, const char *what) {
-        int code = (e == hipErrorOutOfMemory) ? SR_ERR_OOM : SR_ERR_HIP;
-        sr_set_error(code, "sr_blend_plan_create: %s: %s", what, hipGetErrorString(e));
-        {
-            std::lock_guard<std::mutex> lk(g_reg_mu);
-            g_live_plan.insert(P);
-        }
-        sr_blend_plan_destroy(P);
-        return code;
+    const int rc = sr_build_blend_tables(h_tiles, n, cn, canvas_h, canvas_w, levels, weight_type, row_begin, row_end, ctx->num_cu,
+                                         switches_from_env(), P.get());
+    if (rc) return rc;
+    // One table onto the device: an allocation of its own of max(count, 1) elements, owned by the plan, `count` elements copied
+    // into it (src == nullptr: none -- the table is written per call).  The first failure sticks: the calls after it do nothing.
+    hipError_t err = hipSuccess;
+    const char *what = "";
+    auto up = [&](auto *&d, const void *src, size_t count, const char *name) {
+        if (err != hipSuccess) return;
+        const size_t es = sizeof(*d);
+        void *p = nullptr;
+        what = name;
+        if ((err = hipMalloc(&p, es * std::max<size_t>(count, 1))) != hipSuccess) return;
+        P->owned.push_back(p);
+        d = static_cast<std::remove_reference_t<decltype(d)>>(p);
+        what = "upload";
+        if (src && count) err = hipMemcpy(p, src, es * count, hipMemcpyHostToDevice);
     };
-    hipError_t e;
-    if ((e = hipMalloc((void **)&P->d_arena, std::max<size_t>(off, 4) * sizeof(float))) != hipSuccess) return fail(e, "arena");
-    if ((e = hipMalloc((void **)&P->d_tiles, sizeof(TileDev) * n)) != hipSuccess) return fail(e, "tile table");
-    if ((e = hipMalloc((void **)&P->d_classes, sizeof(TileDev) * P->classes.size())) != hipSuccess) return fail(e, "class table");
-    if ((e = hipMalloc((void **)&P->d_srcs, sizeof(TileSrc) * n)) != hipSuccess) return fail(e, "src table");
-    if ((e = hipMalloc((void **)&P->d_fdesc, sizeof(FinalDesc) * n)) != hipSuccess) return fail(e, "final table");
-    P->fdesc.resize(n);
-    for (int t = 0; t < n; ++t) {
-        const TileDev &T = P->tiles[t];
-        FinalDesc &D = P->fdesc[t];
-        memset(&D, 0, sizeof(D));
-        D.x = T.x; D.y = T.y; D.w = T.w; D.h = T.h;
-        D.fw = T.fw; D.lut_off = T.lut_off; D.nl = T.nl;
-        D.H1 = T.nl > 1 ? T.H[1] : 1; D.W1 = T.nl > 1 ? T.W[1] : 1; D.P1 = T.nl > 1 ? T.P[1] : 16;
-        D.g1 = T.nl > 1 ? T.g_off[1] : 0; D.r1 = T.nl > 1 ? T.r_off[1] : 0;
-        D.H2 = T.nl > 2 ? T.H[2] : 1; D.W2 = T.nl > 2 ? T.W[2] : 1; D.P2 = T.nl > 2 ? T.P[2] : 16;
-        D.g2 = T.nl > 2 ? T.g_off[2] : 0; D.r2 = T.nl > 2 ? T.r_off[2] : 0;
-        D.w1 = T.nl > 1 ? T.w_off[1] : 0;
+    up(P->d_arena, nullptr, std::max<size_t>(P->arena_floats, 4), "arena");
+    up(P->d_tiles, P->tiles.data(), P->tiles.size(), "tile table");
+    up(P->d_classes, P->classes.data(), P->classes.size(), "class table");
+    up(P->d_srcs, nullptr, n, "src table");
+    up(P->d_fdesc, nullptr, n, "final table");
+    up(P->d_luts, P->luts.data(), P->luts.size(), "luts");
+    if (P->n_edge_blocks > 0) {
+        up(P->d_edge_blocks, P->edge_blocks.data(), P->edge_blocks.size(), "edge blocks");
+        up(P->d_edge_cand, P->edge_cand.data(), P->edge_cand.size(), "edge candidates");
     }
-
-    if ((e = hipMalloc((void **)&P->d_luts, sizeof(float) * P->luts.size())) != hipSuccess) return fail(e, "luts");
-    {
-        // Edge work list: the cells (4 x 2 pixel rectangles of one thread) in which a visit can be a border visit lie
-        // within 8 px of a tile edge line (or on the ragged right / bottom canvas edge).  Horizontal lines are
-        // covered by 256 x 8 blocks of the fast pass's grid (shape 0), vertical lines by 16 x 128 blocks (shape 1:
-        // 4 x 64 cells), so a wave of the edge pass is mostly border cells either way.  A cell reached through both
-        // shapes is computed twice with identical results.
-        const int rows = row_end - row_begin;
-        const int nbx = (canvas_w + 255) / 256, nby = (rows + 7) / 8;
-        const int nbx2 = (canvas_w + 15) / 16, nby2 = (rows + 127) / 128;
-        std::vector<unsigned char> mark((size_t)std::max(nbx, 1) * std::max(nby, 1), 0);
-        std::vector<unsigned char> mark2((size_t)std::max(nbx2, 1) * std::max(nby2, 1), 0);
-        auto mark_rect = [&](std::vector<unsigned char> &m, int gx, int gy, int pitch, long long x0, long long y0,
-                             long long x1, long long y1) {   // canvas px, half-open
-            x0 = std::max<long long>(x0, 0); x1 = std::min<long long>(x1, canvas_w);
-            y0 = std::max<long long>(y0, row_begin); y1 = std::min<long long>(y1, row_end);
-            if (x0 >= x1 || y0 >= y1) return;
-            for (long long by = (y0 - row_begin) / gy; by <= (y1 - 1 - row_begin) / gy; ++by)
-                for (long long bx = x0 / gx; bx <= (x1 - 1) / gx; ++bx) m[(size_t)by * pitch + bx] = 1;
-        };
-        const int M = 8;
-        for (int t = 0; t < n && rows > 0; ++t) {
-            const TileDev &T = P->tiles[t];
-            const long long xa = T.x, xb = (long long)T.x + T.w, ya = T.y, yb = (long long)T.y + T.h;
-            mark_rect(mark2, 16, 128, nbx2, xa - M, ya - M, xa + M, yb + M);
-            mark_rect(mark2, 16, 128, nbx2, xb - M, ya - M, xb + M, yb + M);
-            mark_rect(mark, 256, 8, nbx, xa - M, ya - M, xb + M, ya + M);
-            mark_rect(mark, 256, 8, nbx, xa - M, yb - M, xb + M, yb + M);
-        }
-        if (rows > 0) {
-            if (canvas_w % 4) mark_rect(mark2, 16, 128, nbx2, canvas_w - 4, row_begin, canvas_w, row_end);
-            if (rows % 2) mark_rect(mark, 256, 8, nbx, 0, row_end - 2, canvas_w, row_end);
-        }
-        std::vector<int4> eb;                       // x0, y0 (canvas), shape, first candidate
-        for (int by = 0; by < nby; ++by)
-            for (int bx = 0; bx < nbx; ++bx)
-                if (mark[(size_t)by * nbx + bx]) eb.push_back(make_int4(bx * 256, row_begin + by * 8, 0, 0));
-        for (int by = 0; by < nby2; ++by)
-            for (int bx = 0; bx < nbx2; ++bx)
-                if (mark2[(size_t)by * nbx2 + bx]) eb.push_back(make_int4(bx * 16, row_begin + by * 128, 1, 0));
-        std::vector<int> ecand;
-        for (auto &e4 : eb) {
-            const long long bx0 = e4.x, by0 = e4.y;
-            const long long bx1 = std::min<long long>(bx0 + (e4.z ? 16 : 256), canvas_w);
-            const long long by1 = std::min<long long>(by0 + (e4.z ? 128 : 8), row_end);
-            e4.w = (int)ecand.size();
-            for (int t = 0; t < n; ++t) {
-                const TileDev &T = P->tiles[t];
-                if (T.x < bx1 && (long long)T.x + T.w > bx0 && T.y < by1 && (long long)T.y + T.h > by0) ecand.push_back(t);
-            }
-        }
-        eb.push_back(make_int4(0, 0, 0, (int)ecand.size()));       // sentinel: end of the last list
-        P->n_edge_blocks = (int)eb.size() - 1;
-        if (P->n_edge_blocks > 0) {
-            if ((e = hipMalloc((void **)&P->d_edge_blocks, sizeof(int4) * eb.size())) != hipSuccess) return fail(e, "edge blocks");
-            if ((e = hipMemcpy(P->d_edge_blocks, eb.data(), sizeof(int4) * eb.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-            if ((e = hipMalloc((void **)&P->d_edge_cand, sizeof(int) * std::max<size_t>(ecand.size(), 1))) != hipSuccess) return fail(e, "edge candidates");
-            if (!ecand.empty() && (e = hipMemcpy(P->d_edge_cand, ecand.data(), sizeof(int) * ecand.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-        }
-        // candidate tiles per regular block, CSR, tiles in list order (the accumulation order of the reference)
-        const int nbx_r = std::max((canvas_w + FIN_BW - 1) / FIN_BW, 1), nby_r = std::max((rows + FIN_BH - 1) / FIN_BH, 1);
-        const size_t nblk = (size_t)nbx_r * nby_r;
-        std::vector<int> coff(nblk + 1, 0);
-        auto block_span = [&](const TileDev &T, int &bx_a, int &bx_b, int &by_a, int &by_b) {
-            const long long x0 = std::max<long long>(T.x, 0), x1 = std::min<long long>((long long)T.x + T.w, canvas_w);
-            const long long y0 = std::max<long long>(T.y, row_begin), y1 = std::min<long long>((long long)T.y + T.h, row_end);
-            if (x0 >= x1 || y0 >= y1) return false;
-            bx_a = (int)(x0 / FIN_BW); bx_b = (int)((x1 - 1) / FIN_BW);
-            by_a = (int)((y0 - row_begin) / FIN_BH); by_b = (int)((y1 - 1 - row_begin) / FIN_BH);
-            return true;
-        };
-        for (int t = 0; t < n && rows > 0; ++t) {
-            int bxa, bxb, bya, byb;
-            if (!block_span(P->tiles[t], bxa, bxb, bya, byb)) continue;
-            for (int by = bya; by <= byb; ++by)
-                for (int bx = bxa; bx <= bxb; ++bx) ++coff[(size_t)by * nbx_r + bx + 1];
-        }
-        for (size_t i = 0; i < nblk; ++i) coff[i + 1] += coff[i];
-        std::vector<int> cidx((size_t)std::max(coff[nblk], 1), 0), fill(coff.begin(), coff.end() - 1);
-        for (int t = 0; t < n && rows > 0; ++t) {
-            int bxa, bxb, bya, byb;
-            if (!block_span(P->tiles[t], bxa, bxb, bya, byb)) continue;
-            for (int by = bya; by <= byb; ++by)
-                for (int bx = bxa; bx <= bxb; ++bx) cidx[(size_t)fill[(size_t)by * nbx_r + bx]++] = t;
-        }
-        if ((e = hipMalloc((void **)&P->d_cand_off, sizeof(int) * coff.size())) != hipSuccess) return fail(e, "candidate table");
-        if ((e = hipMalloc((void **)&P->d_cand_idx, sizeof(int) * cidx.size())) != hipSuccess) return fail(e, "candidate table");
-        if ((e = hipMemcpy(P->d_cand_off, coff.data(), sizeof(int) * coff.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-        if ((e = hipMemcpy(P->d_cand_idx, cidx.data(), sizeof(int) * cidx.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-    }
+    up(P->d_cand_off, P->cand_off.data(), P->cand_off.size(), "candidate table");
+    up(P->d_cand_idx, P->cand_idx.data(), P->cand_idx.size(), "candidate table");
     if (P->fused) {
-        // ---- tables of the fused gather ---------------------------------------------------------------------------------
-        const int rows = row_end - row_begin;
-        // host mirror of visit_is_interior<true> (device): a 4 x 2 cell at tile-local (lx0, ly0), nx x ny of it on the strip
-        auto cell_interior = [](const TileDev &T, long long lx0, long long ly0, int nx, int ny) {
-            if (nx != 4 || ny != 2 || lx0 < 0 || ly0 < 0 || lx0 + 3 >= T.w || ly0 + 1 >= T.h) return false;
-            if (T.nl > 1) {
-                const long long r0 = (ly0 - 1) >> 1, c0 = (lx0 - 1) >> 1;
-                return c0 >= 0 && c0 + 3 <= T.W[1] - 1 && r0 >= 0 && r0 + 2 <= T.H[1] - 1;
-            }
-            return true;
-        };
-        const int enbx = (canvas_w + 255) / 256, enby = (rows + FU_E0H - 1) / FU_E0H;     // shape 0: 256 x FU_E0H
-        const int enbx2 = (canvas_w + FU_E1W - 1) / FU_E1W, enby2 = (rows + FU_E1H - 1) / FU_E1H;     // shape 1: FU_E1W x FU_E1H
-        std::vector<unsigned char> m0((size_t)std::max(enbx, 1) * std::max(enby, 1), 0), m1((size_t)std::max(enbx2, 1) * std::max(enby2, 1), 0);
-        // Every cell with a border visit lies within a few pixels of the edge line of the tile it visits (or on the
-        // ragged right / bottom end of the strip): walk the cells of a 24-pixel frame around each tile's outline, test
-        // them exactly, mark the block that holds them -- blocks along horizontal lines in shape 0, along vertical
-        // lines in shape 1 (a corner cell may be marked in both: computed twice, identical bytes).
-        auto scan = [&](const TileDev &T, long long xa, long long ya, long long xb, long long yb, int shape) {   // canvas px, half-open
-            xa = std::max<long long>(xa, 0); xb = std::min<long long>(xb, canvas_w);
-            ya = std::max<long long>(ya, row_begin); yb = std::min<long long>(yb, row_end);
-            if (xa >= xb || ya >= yb) return;
-            for (long long cy = (ya - row_begin) / 2; cy <= (yb - 1 - row_begin) / 2; ++cy)
-                for (long long cx = xa / 4; cx <= (xb - 1) / 4; ++cx) {
-                    const long long x0 = cx * 4, y0 = row_begin + cy * 2;
-                    const int nx = (int)std::min<long long>(4, canvas_w - x0), ny = (int)std::min<long long>(2, row_end - y0);
-                    const long long lx0 = x0 - T.x, ly0 = y0 - T.y;
-                    if (lx0 + nx <= 0 || ly0 + ny <= 0 || lx0 >= T.w || ly0 >= T.h) continue;
-                    if (cell_interior(T, lx0, ly0, nx, ny)) continue;
-                    if (shape == 0) m0[(size_t)((y0 - row_begin) / FU_E0H) * enbx + x0 / 256] = 1;
-                    else m1[(size_t)((y0 - row_begin) / FU_E1H) * enbx2 + x0 / FU_E1W] = 1;
-                }
-        };
-        const long long F = 24;
-        for (int t = 0; t < n && rows > 0; ++t) {
-            const TileDev &T = P->tiles[t];
-            const long long xa = T.x, xb = (long long)T.x + T.w, ya = T.y, yb = (long long)T.y + T.h;
-            scan(T, xa - F, ya - F, xb + F, ya + F, 0);
-            scan(T, xa - F, yb - F, xb + F, yb + F, 0);
-            scan(T, xa - F, ya - F, xa + F, yb + F, 1);
-            scan(T, xb - F, ya - F, xb + F, yb + F, 1);
-            // the ragged ends of the strip (cells narrower / shorter than 4): border visits of every tile they touch
-            if (canvas_w % 4) scan(T, canvas_w - (canvas_w % 4), row_begin, canvas_w, row_end, 1);
-            if (rows % 2) scan(T, 0, row_end - 1, canvas_w, row_end, 0);
+        up(P->d_fedge_blocks, P->fedge_blocks.data(), P->fedge_blocks.size(), "fused edge blocks");
+        up(P->d_fedge_cand, P->fedge_cand.data(), P->fedge_cand.size(), "fused edge candidates");
+        up(P->d_fcand_off, P->fcand_off.data(), P->fcand_off.size(), "fused candidate table");
+        up(P->d_fcand_idx, P->fcand_idx.data(), P->fcand_idx.size(), "fused candidate table");
+        if (P->n_march_total > 0) {
+            up(P->d_rects, P->rects.data(), P->rects.size(), "rectangle items");
+            up(P->d_rect_cand, P->rect_cand.data(), P->rect_cand.size(), "rectangle candidates");
         }
-        std::vector<int4> eb;
-        for (int by = 0; by < enby; ++by)
-            for (int bx = 0; bx < enbx; ++bx)
-                if (m0[(size_t)by * enbx + bx]) eb.push_back(make_int4(bx * 256, row_begin + by * FU_E0H, 0, 0));
-        for (int by = 0; by < enby2; ++by)
-            for (int bx = 0; bx < enbx2; ++bx)
-                if (m1[(size_t)by * enbx2 + bx]) eb.push_back(make_int4(bx * FU_E1W, row_begin + by * FU_E1H, 1, 0));
-        std::vector<int> ecand;
-        for (auto &e4 : eb) {
-            const long long bx0 = e4.x, by0 = e4.y;
-            const long long bx1 = std::min<long long>(bx0 + (e4.z ? FU_E1W : 256), canvas_w);
-            const long long by1 = std::min<long long>(by0 + (e4.z ? FU_E1H : FU_E0H), row_end);
-            e4.w = (int)ecand.size();
-            for (int t = 0; t < n; ++t) {
-                const TileDev &T = P->tiles[t];
-                if (T.x < bx1 && (long long)T.x + T.w > bx0 && T.y < by1 && (long long)T.y + T.h > by0) ecand.push_back(t);
-            }
-        }
-        eb.push_back(make_int4(0, 0, 0, (int)ecand.size()));
-        P->n_fedge_blocks = (int)eb.size() - 1;
-        if ((e = hipMalloc((void **)&P->d_fedge_blocks, sizeof(int4) * eb.size())) != hipSuccess) return fail(e, "fused edge blocks");
-        if ((e = hipMemcpy(P->d_fedge_blocks, eb.data(), sizeof(int4) * eb.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-        if ((e = hipMalloc((void **)&P->d_fedge_cand, sizeof(int) * std::max<size_t>(ecand.size(), 1))) != hipSuccess) return fail(e, "fused edge candidates");
-        if (!ecand.empty() && (e = hipMemcpy(P->d_fedge_cand, ecand.data(), sizeof(int) * ecand.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-        // candidate tiles per regular block (FU_BW x FU_BH), CSR, list order
-        const int nbx_r = std::max((canvas_w + FU_BW - 1) / FU_BW, 1), nby_r = std::max((rows + FU_BH - 1) / FU_BH, 1);
-        const size_t nblk = (size_t)nbx_r * nby_r;
-        std::vector<int> coff(nblk + 1, 0);
-        auto block_span = [&](const TileDev &T, int &bx_a, int &bx_b, int &by_a, int &by_b) {
-            const long long x0 = std::max<long long>(T.x, 0), x1 = std::min<long long>((long long)T.x + T.w, canvas_w);
-            const long long y0 = std::max<long long>(T.y, row_begin), y1 = std::min<long long>((long long)T.y + T.h, row_end);
-            if (x0 >= x1 || y0 >= y1) return false;
-            bx_a = (int)(x0 / FU_BW); bx_b = (int)((x1 - 1) / FU_BW);
-            by_a = (int)((y0 - row_begin) / FU_BH); by_b = (int)((y1 - 1 - row_begin) / FU_BH);
-            return true;
-        };
-        for (int t = 0; t < n && rows > 0; ++t) {
-            int bxa, bxb, bya, byb;
-            if (!block_span(P->tiles[t], bxa, bxb, bya, byb)) continue;
-            for (int by = bya; by <= byb; ++by)
-                for (int bx = bxa; bx <= bxb; ++bx) ++coff[(size_t)by * nbx_r + bx + 1];
-        }
-        for (size_t i = 0; i < nblk; ++i) coff[i + 1] += coff[i];
-        std::vector<int> cidx((size_t)std::max(coff[nblk], 1), 0), fill(coff.begin(), coff.end() - 1);
-        for (int t = 0; t < n && rows > 0; ++t) {
-            int bxa, bxb, bya, byb;
-            if (!block_span(P->tiles[t], bxa, bxb, bya, byb)) continue;
-            for (int by = bya; by <= byb; ++by)
-                for (int bx = bxa; bx <= bxb; ++bx) cidx[(size_t)fill[(size_t)by * nbx_r + bx]++] = t;
-        }
-        if ((e = hipMalloc((void **)&P->d_fcand_off, sizeof(int) * coff.size())) != hipSuccess) return fail(e, "fused candidate table");
-        if ((e = hipMalloc((void **)&P->d_fcand_idx, sizeof(int) * cidx.size())) != hipSuccess) return fail(e, "fused candidate table");
-        if ((e = hipMemcpy(P->d_fcand_off, coff.data(), sizeof(int) * coff.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-        if ((e = hipMemcpy(P->d_fcand_idx, cidx.data(), sizeof(int) * cidx.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-        // ---- marched zones and the rectangles of what they leave --------------------------------------------------------
-        std::vector<MarchItem> mitems[MARCH_NT + 1];
-        std::vector<unsigned> cover;
-        plan_march(P, nbx_r, nby_r, mitems, cover);
-        {
-            bool any_march = false;
-            for (int k = 1; k <= MARCH_NT; ++k) any_march = any_march || !mitems[k].empty();
-            if (any_march && (P->cn == 3 || P->cn == 1)) {
-                std::vector<RectItem> rects;
-                std::vector<int> rcand;
-                plan_rects(P, nbx_r, cover, rects, rcand);
-                P->n_rects = (long long)rects.size();
-                if ((e = hipMalloc((void **)&P->d_rects, sizeof(RectItem) * std::max<size_t>(rects.size(), 1))) != hipSuccess) return fail(e, "rectangle items");
-                if (!rects.empty() && (e = hipMemcpy(P->d_rects, rects.data(), sizeof(RectItem) * rects.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-                if ((e = hipMalloc((void **)&P->d_rect_cand, sizeof(int) * std::max<size_t>(rcand.size(), 1))) != hipSuccess) return fail(e, "rectangle candidates");
-                if (!rcand.empty() && (e = hipMemcpy(P->d_rect_cand, rcand.data(), sizeof(int) * rcand.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-                P->h_rects.swap(rects);
-            }
-        }
-        for (int k = 1; k <= MARCH_NT; ++k) {
-            P->n_march_items[k] = (int)mitems[k].size();
-            P->n_march_total += (long long)mitems[k].size();
-            if (mitems[k].empty()) continue;
-            if ((e = hipMalloc((void **)&P->d_march_items[k], sizeof(MarchItem) * mitems[k].size())) != hipSuccess) return fail(e, "march items");
-            if ((e = hipMemcpy(P->d_march_items[k], mitems[k].data(), sizeof(MarchItem) * mitems[k].size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload");
-            P->h_march_items[k].swap(mitems[k]);
-        }
+        for (int k = 1; k <= MARCH_NT; ++k)
+            if (P->n_march_items[k] > 0) up(P->d_march_items[k], P->march_items[k].data(), P->march_items[k].size(), "march items");
     }
-    if ((e = hipMemcpyAsync(P->d_tiles, P->tiles.data(), sizeof(TileDev) * n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return fail(e, "upload");
-    if ((e = hipMemcpyAsync(P->d_classes, P->classes.data(), sizeof(TileDev) * P->classes.size(), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return fail(e, "upload");
-    if ((e = hipMemcpyAsync(P->d_luts, P->luts.data(), sizeof(float) * P->luts.size(), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return fail(e, "upload");
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(e, "sync");
+    if (err != hipSuccess) {
+        const int code = (err == hipErrorOutOfMemory) ? SR_ERR_OOM : SR_ERR_HIP;
+        return sr_set_error(code, "sr_blend_plan_create: %s: %s", what, hipGetErrorString(err));
+    }
     {
         std::lock_guard<std::mutex> lk(g_reg_mu);
-        g_live_plan.insert(P);
+        g_live_plan.insert(P.get());
     }
-    *out = P;
+    *out = P.release();
     return SR_OK;
 }
 
@@ -2499,7 +1776,7 @@ int sr_blend_plan_march_items(const sr_blend_plan *plan, int nt, int32_t *out, i
     if (!plan_is_live(plan) || nt < 0 || nt > MARCH_NT || !count || (out && cap < 0))
         return sr_set_error(SR_ERR_INVALID_ARG, "sr_blend_plan_march_items: bad args");
     if (nt == 0) {
-        const std::vector<RectItem> &r = plan->h_rects;
+        const std::vector<RectItem> &r = plan->rects;
         *count = (int64_t)r.size();
         for (int64_t i = 0; out && i < std::min<int64_t>(cap, *count); ++i) {
             const int v[4] = {r[i].x, r[i].y, r[i].w, r[i].h};
@@ -2508,7 +1785,7 @@ int sr_blend_plan_march_items(const sr_blend_plan *plan, int nt, int32_t *out, i
         return SR_OK;
     }
     static_assert(sizeof(MarchItem) == 8 * sizeof(int32_t), "eight ints per item");
-    const std::vector<MarchItem> &m = plan->h_march_items[nt];
+    const std::vector<MarchItem> &m = plan->march_items[nt];
     *count = (int64_t)m.size();
     if (out && !m.empty()) memcpy(out, m.data(), sizeof(MarchItem) * (size_t)std::min<int64_t>(cap, *count));
     return SR_OK;

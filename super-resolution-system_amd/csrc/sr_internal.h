@@ -1,5 +1,5 @@
-// Internal declarations shared by sr_host.cpp (pure host bookkeeping) and the device sources (sr_engine.hip plans with
-// them; every .hip file reports errors through sr_set_error).
+// Internal declarations shared by sr_host.cpp (pure host bookkeeping), the blend planner (sr_blend_plan.cpp plans with
+// them) and the device sources (every .hip file reports errors through sr_set_error).
 #pragma once
 #include <cstdarg>
 #include <cstdio>

@@ -17,17 +17,7 @@
 //
 // Memory goes through buffer instructions: one resource per array, a per-lane 32-bit offset that never changes, and the
 // row in a scalar offset register that the scalar unit advances -- no vector instruction is spent on an address.
-#ifndef MARCH_NT
-#define MARCH_NT 4                   /* most tiles a marched zone may have */
-#endif
-#ifndef MARCH_SEG
-#define MARCH_SEG 64                 /* most steps (of two canvas rows) per work item: a multiple of 2 */
-#endif
-#ifndef MARCH_ROUNDS
-#define MARCH_ROUNDS 4.0             /* rounds of work items the 1-tile list is cut into (at two waves per SIMD) */
-#define MARCH_ROUNDS_2 3.0           /* the 2-tile list */
-#define MARCH_ROUNDS_N 2.0           /* the 3- and 4-tile lists */
-#endif
+// (MARCH_NT, MARCH_SEG, MARCH_CELLS, the rounds per list and MarchItem: sr_blend_tables.h -- the planner cuts the lists by them)
 #ifndef MARCH1_WAVES
 #define MARCH1_WAVES 2                /* waves per SIMD the one-tile kernel is held to (256 registers) */
 #endif
@@ -37,17 +27,6 @@
 #ifndef MARCH_PLANE_FENCE
 #define MARCH_PLANE_FENCE __builtin_amdgcn_sched_barrier(0)
 #endif
-#define MARCH_CELLS 62               /* useful cells per strip: 64 lanes less the two halo lanes */
-
-struct MarchItem {                   // 32 bytes, wave-uniform (read through the scalar cache)
-    int x0;                          // canvas x of lane 0's cell (the left halo cell); a multiple of 4
-    int y0;                          // first canvas row
-    int ncell;                       // useful cells: lanes 1 .. ncell store
-    int nstep;                       // steps of two canvas rows (even)
-    int tile[4];                     // the tiles of the zone, list order (their number: one item list per count)
-};
-static_assert(sizeof(MarchItem) == 32, "MarchItem layout");
-
 typedef __amdgpu_buffer_rsrc_t march_rsrc;
 
 __device__ __forceinline__ march_rsrc march_make_rsrc(const void *base, unsigned bytes)

@@ -1,4 +1,4 @@
-"""AddressSanitizer + UBSan over the host side of the C ABI: csrc/sr_host.cpp and csrc/sr_encode.cpp are
+"""AddressSanitizer + UBSan over the host side of the C ABI: csrc/sr_host.cpp, csrc/sr_blend_plan.cpp and csrc/sr_encode.cpp are
 compiled with g++ -fsanitize=address,undefined -fno-sanitize-recover=all together with tools/sanitize/host_driver.cpp, which
 calls every host-only entry point with exact-size buffers over randomised geometries.  (GPU sanitizers are not available
 on the pool; the kernels' indexing is covered by the poisoned-buffer tests of the GPU suite.)"""
@@ -20,7 +20,7 @@ def test_host_abi_under_sanitizers(tmp_path, san):
     exe = str(tmp_path / "host_driver")
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=" + san, "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
            "-DSR_BUILD", "-I", os.path.join(ROOT, "include"), "-I", csrc, os.path.join(ROOT, "tools", "sanitize", "host_driver.cpp"),
-           os.path.join(csrc, "sr_host.cpp"), os.path.join(csrc, "sr_encode.cpp"), "-lz", "-lpthread", "-o", exe]
+           os.path.join(csrc, "sr_host.cpp"), os.path.join(csrc, "sr_blend_plan.cpp"), os.path.join(csrc, "sr_encode.cpp"), "-lz", "-lpthread", "-o", exe]
     subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=600)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
                TSAN_OPTIONS="halt_on_error=1")
