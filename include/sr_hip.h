@@ -623,6 +623,78 @@ SR_API int sr_bench_plan(int h, int w, int cn, int crop_border, int mode, int *c
  * uncropped image (SR_ERR_SHAPE). */
 SR_API int sr_bench_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
                        int cn, int crop_border, int mode, double data_range, sr_bench_sums *h_out);
+/* ---- NIQE, the no-reference quality model (csrc/sr_niqe.hip, csrc/sr_niqe_host.cpp) -------------------------------------------
+ * Mittal, Soundararajan, Bovik 2013, in the arithmetic of MATLAB's computequality / estimatemodelparam and BasicSR's
+ * calculate_niqe, made exact wherever it can be.  The reference's calculate_niqe asks pyiqa for this model first; the 'niqe'
+ * key of the reports is its MSCN fallback heuristic and is NOT this number.  The model needs a 36-value mean and a 36 x 36
+ * covariance of "pristine" features: the caller supplies them (nothing is fetched), or fits them with sr_niqe_fit.
+ * PARITY UNPINNED with BasicSR, pyiqa and MATLAB: none of them is available offline, and neither is niqe_pris_params.npz.
+ * Known distances, unmeasured here, both rounding-level: BasicSR scales by / 255 ... * 255 around the resize where the plane
+ * here is exact, and it convolves with the 2-D window in one scipy.ndimage.convolve where the filter here is separable.
+ * All arithmetic is float64 without contraction.
+ *   plane    cn = 3 (RGB): MATLAB's u8 luma, SR_BENCH_Y_ROUND's floor((2 X + 255000) / 510000) with X = 65481 R + 128553 G +
+ *            24966 B + 4080000 (BasicSR rounds Y before NIQE); cn = 1: the plane as it is.  crop_border pixels per side are
+ *            cropped by pointer arithmetic (h' x w'), then the top-left H = 96 floor(h' / 96) by W = 96 floor(w' / 96) is kept:
+ *            nby x nbx blocks.  A side below 96 after the crop is SR_ERR_SHAPE.
+ *   scale 2  MATLAB imresize(., 0.5): bicubic, a = -0.5, antialiased.  At scale 1/2 every output has the same eight taps
+ *            0.5 cubic(0.25, 0.75, 1.25, 1.75) = {-3, -9, 29, 111, 111, 29, -9, -3} / 256 (they sum to 1); output i reads
+ *            inputs 2 i - 3 .. 2 i + 4, indices reflect symmetrically (j < 0 -> -j - 1, j >= n -> 2 n - 1 - j), rows first,
+ *            then columns.  The input is an integer plane, so 65536 x the result is an exact integer k, |k| < 2^25: the half
+ *            plane is kept as int32, nothing rounds and no summation order matters.
+ *   MSCN     per scale, window of 7 taps g_i = exp(-i^2 / (2 s^2)), s = 7 / 6, k_i = g_i / sum g (computed on the host),
+ *            separable: horizontal pass, then vertical pass, in each the taps added in ascending index order; the border
+ *            replicates (scipy.ndimage 'nearest').  mu = G * I, sigma = sqrt(|G * I^2 - mu^2|), m = (I - mu) / (sigma + 1); I in
+ *            gray levels at both scales (scale 2: I = k / 65536, I^2 exact in float64).
+ *   blocks   96 / scale on a side: both scales have the same nby x nbx blocks.  X_0 = m and X_s = m * roll(m, shift_s) for the
+ *            shifts (dy, dx) = (0, 1), (1, 0), (1, 1), (1, -1), roll(b, (dy, dx))[i, j] = b[(i - dy) mod n, (j - dx) mod n]:
+ *            circular INSIDE the block, as np.roll on the block is.  A record holds, per X, the counts of X < 0 and X > 0, the
+ *            sums of X^2 over each and the sum of |X|; and the block's sum of sigma.  Fixed-order sums, no floating-point
+ *            atomics: equal inputs give equal bits.
+ *   features AGGD fit of a record's moments: ls = sqrt(ssq_neg / n_neg), rs = sqrt(ssq_pos / n_pos), g = ls / rs,
+ *            r = (sabs / n)^2 / ((ssq_neg + ssq_pos) / n), R = r (g^3 + 1)(g + 1) / (g^2 + 1)^2; alpha = the entry of
+ *            gam = 0.2 + 0.001 t, t = 0 .. 9800, that minimises (Gamma(2 / gam)^2 / (Gamma(1 / gam) Gamma(3 / gam)) - R)^2
+ *            (the first on a tie); beta_l = ls sqrt(Gamma(1 / alpha) / Gamma(3 / alpha)), beta_r likewise.  Per scale 18 values:
+ *            [alpha_0, (beta_l0 + beta_r0) / 2], then per shift [alpha, (beta_r - beta_l) Gamma(2 / alpha) / Gamma(1 / alpha),
+ *            beta_l, beta_r]; scale 1 then scale 2: 36.  A fit with n_neg = 0 or n_pos = 0 gives NaN.
+ *   score    mu_d = the per-feature mean over non-NaN entries, cov_d = the sample covariance (ddof 1) over blocks without a
+ *            NaN, S = (cov_pris + cov_d) / 2, S+ = the pseudo-inverse of the symmetric S by eigen-decomposition, eigenvalues
+ *            with |l| <= 1e-15 max |l| dropped (numpy pinv's default); NIQE = sqrt((mu_pris - mu_d) S+ (mu_pris - mu_d)^T).
+ *   fit      per image sharp_b = sum_sigma_b(scale 1) / 96^2; blocks with sharp_b > T max_b sharp_b are kept (T = 0.75 in
+ *            the paper); the kept, NaN-free 36-rows of all images are pooled: mu_pris their mean, cov_pris their sample
+ *            covariance.  Fewer than 37 rows is refused. */
+typedef struct sr_niqe_moments {
+    uint64_t n_neg, n_pos;      /* counts of X < 0, X > 0 */
+    double ssq_neg, ssq_pos;    /* sums of X^2 over each */
+    double sabs;                /* sum of |X| */
+} sr_niqe_moments;
+typedef struct sr_niqe_block {
+    sr_niqe_moments x[5];       /* X_0 = m, then the four shifted products in the order above */
+    double sum_sigma;           /* the block's sum of sigma */
+} sr_niqe_block;
+/* Host only, no context: the kept size, the block grid and the bytes of context scratch a call will hold (each output may be
+ * NULL).  Carries every shape refusal: SR_ERR_INVALID_ARG for cn not 1 or 3, crop_border < 0, h or w < 1; SR_ERR_SHAPE for a
+ * side below 96 after the crop. */
+SR_API int sr_niqe_plan(int h, int w, int cn, int crop_border, int *H, int *W, int *nby, int *nbx, size_t *scratch_bytes);
+/* One read of the image for the half plane, then one workgroup per block and scale.  h_out: 2 nby nbx records, scale-major
+ * (scale 1's blocks row-major, then scale 2's).  Strides in bytes, arbitrary (>= a row).  Synchronous; the half plane and the
+ * records are context scratch, grown on demand.  Refused before any device call: null pointers, everything sr_niqe_plan
+ * refuses, a stride shorter than a row of the uncropped image (SR_ERR_SHAPE). */
+SR_API int sr_niqe_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, int cn, int crop_border,
+                      sr_niqe_block *h_out);
+/* The half plane (65536 x the scale-2 plane, dense (H / 2) x (W / 2)) the context's last completed sr_niqe_u8 call left in its
+ * scratch, for inspection. */
+SR_API int sr_niqe_half_plane(sr_ctx *ctx, int32_t *h_out);
+/* Host only.  records: 2 nblocks records, scale-major, as sr_niqe_u8 writes them; feat36: nblocks x 36. */
+SR_API int sr_niqe_features(const sr_niqe_block *records, int64_t nblocks, double *feat36);
+/* Host only.  feat: the pooled rows of n_images images, image i owning rows [image_off[i], image_off[i + 1]); sharp: sharp_b
+ * per row.  mu: 36, cov: 36 x 36; *rows_used (may be NULL) is always set once the arguments are valid.  SR_ERR_INVALID_ARG for
+ * null pointers, n_images < 1, offsets that do not ascend from 0, T not in [0, 1); SR_ERR_SHAPE, giving the count, for fewer
+ * than 37 kept rows. */
+SR_API int sr_niqe_fit(const double *feat, const double *sharp, const int64_t *image_off, int n_images, double T, double *mu,
+                       double *cov, int64_t *rows_used);
+/* Host only.  The score of nblocks feature rows under (mu_pris[36], cov_pris[36 x 36]); NaN (and sr_last_error) for null
+ * pointers or fewer than two NaN-free rows. */
+SR_API double sr_niqe_score(const double *feat, int64_t nblocks, const double *mu_pris, const double *cov_pris);
 /* cv2.cvtColor(RGB2GRAY) on u8 (quality_assessment_module.py:359-360) */
 SR_API int sr_rgb2gray_u8(sr_ctx *ctx, const uint8_t *d_rgb, int64_t stride, int h, int w,
                           int gray_shift, uint8_t *d_gray, int64_t gray_stride);

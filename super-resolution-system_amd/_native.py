@@ -76,6 +76,22 @@ class BenchSums(C.Structure):
 # enum sr_bench_mode (include/sr_hip.h)
 BENCH_CHANNELS, BENCH_Y, BENCH_Y_ROUND = 0, 1, 2
 
+
+class NiqeMoments(C.Structure):
+    """sr_niqe_moments (include/sr_hip.h)."""
+    _fields_ = [("n_neg", C.c_uint64), ("n_pos", C.c_uint64), ("ssq_neg", C.c_double), ("ssq_pos", C.c_double), ("sabs", C.c_double)]
+
+
+class NiqeBlock(C.Structure):
+    """sr_niqe_block (include/sr_hip.h)."""
+    _fields_ = [("x", NiqeMoments * 5), ("sum_sigma", C.c_double)]
+
+
+# the same records as NumPy structured arrays
+NIQE_MOMENTS = np.dtype([("n_neg", "<u8"), ("n_pos", "<u8"), ("ssq_neg", "<f8"), ("ssq_pos", "<f8"), ("sabs", "<f8")])
+NIQE_RECORD = np.dtype([("x", NIQE_MOMENTS, (5,)), ("sum_sigma", "<f8")])
+NIQE_BLOCK, NIQE_FEATURES = 96, 36
+
 MS_SSIM_MAX_LEVELS = 5
 MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 
@@ -212,6 +228,12 @@ SIGNATURES = {
     "sr_ms_ssim_planes": (_i, [_vp, _i, _vp, _vp]),
     "sr_bench_plan": (_i, [_i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_sz)]),
     "sr_bench_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _dbl, C.POINTER(BenchSums)]),
+    "sr_niqe_plan": (_i, [_i, _i, _i, _i, _pi, _pi, _pi, _pi, C.POINTER(_sz)]),
+    "sr_niqe_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sr_niqe_half_plane": (_i, [_vp, _vp]),
+    "sr_niqe_features": (_i, [_vp, _i64, _vp]),
+    "sr_niqe_fit": (_i, [_vp, _vp, _vp, _i, _dbl, _vp, _vp, C.POINTER(_i64)]),
+    "sr_niqe_score": (_dbl, [_vp, _i64, _vp, _vp]),
     "sr_rgb2gray_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
     "sr_resize_cubic_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i]),
     "sr_resize_cubic_window_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64]),
@@ -568,6 +590,74 @@ def bench_values(sums: dict, data_range: float = 255.0) -> Tuple[float, float]:
     return psnr, sums["ssim_sum"] / sums["n_map"]
 
 
+def niqe_plan(h: int, w: int, cn: int, crop_border: int = 0) -> dict:
+    """Host only (sr_niqe_plan): the kept size (multiples of 96), the block grid and the bytes of context scratch of a NIQE
+    call.  ValueError for cn not 1 or 3 or a negative crop_border; SrShapeError (a ValueError) naming the minimum for a side
+    below 96 after the crop."""
+    h, w, cn, crop_border = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn"), (crop_border, "crop_border")))
+    H, W, nby, nbx, nbytes = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    check(load().sr_niqe_plan(h, w, cn, crop_border, C.byref(H), C.byref(W), C.byref(nby), C.byref(nbx), C.byref(nbytes)))
+    return {"size": (H.value, W.value), "blocks": (nby.value, nbx.value), "scratch_bytes": int(nbytes.value)}
+
+
+def _f64(a, shape, name: str) -> np.ndarray:
+    out = np.ascontiguousarray(a, dtype=np.float64)
+    if out.shape != shape:
+        raise ValueError(f"{name}: expected shape {shape}, got {out.shape}")
+    return out
+
+
+def niqe_features(records: np.ndarray) -> np.ndarray:
+    """Host only (sr_niqe_features): records[2, nblocks] (NIQE_RECORD, scale-major) -> feat[nblocks, 36]."""
+    rec = np.ascontiguousarray(records, dtype=NIQE_RECORD)
+    if rec.ndim != 2 or rec.shape[0] != 2 or rec.shape[1] < 1:
+        raise ValueError(f"niqe_features: records must be [2, nblocks], got shape {rec.shape}")
+    feat = np.zeros((rec.shape[1], NIQE_FEATURES), dtype=np.float64)
+    check(load().sr_niqe_features(rec.ctypes.data_as(C.c_void_p), rec.shape[1], feat.ctypes.data_as(C.c_void_p)))
+    return feat
+
+
+def niqe_sharpness(records: np.ndarray) -> np.ndarray:
+    """sharp_b = sum_sigma_b(scale 1) / 96^2 of records[2, nblocks]."""
+    return np.asarray(records)[0]["sum_sigma"] / float(NIQE_BLOCK * NIQE_BLOCK)
+
+
+def niqe_fit(feats, sharps, threshold: float = 0.75):
+    """Host only (sr_niqe_fit): per-image feature rows [n_i, 36] and sharpness [n_i] -> (mu[36], cov[36, 36], rows used).
+    SrShapeError (a ValueError) giving the count when fewer than 37 rows pass."""
+    feats = [np.ascontiguousarray(f, dtype=np.float64) for f in feats]
+    sharps = [np.ascontiguousarray(s, dtype=np.float64).reshape(-1) for s in sharps]
+    if not feats or len(feats) != len(sharps):
+        raise ValueError("niqe_fit: need one sharpness array per feature array, and at least one image")
+    for f, s in zip(feats, sharps):
+        if f.ndim != 2 or f.shape[1] != NIQE_FEATURES or s.shape[0] != f.shape[0]:
+            raise ValueError(f"niqe_fit: need [n, 36] features with [n] sharpness, got {f.shape} and {s.shape}")
+    off = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int64)
+    rows, sharp = np.ascontiguousarray(np.concatenate(feats)), np.ascontiguousarray(np.concatenate(sharps))
+    if rows.shape[0] < 1:
+        raise ValueError("niqe_fit: no blocks")
+    mu, cov, used = np.zeros(NIQE_FEATURES), np.zeros((NIQE_FEATURES, NIQE_FEATURES)), C.c_int64(0)
+    check(load().sr_niqe_fit(rows.ctypes.data_as(C.c_void_p), sharp.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p),
+                             len(feats), float(threshold), mu.ctypes.data_as(C.c_void_p), cov.ctypes.data_as(C.c_void_p),
+                             C.byref(used)))
+    return mu, cov, int(used.value)
+
+
+def niqe_score(feat, mu_pris, cov_pris) -> float:
+    """Host only (sr_niqe_score): the NIQE of feature rows [nblocks, 36] under (mu_pris (36,) or (1, 36), cov_pris (36, 36));
+    NaN (the reason in last_error()) with fewer than two NaN-free rows.  ValueError for wrong parameter shapes."""
+    feat = np.ascontiguousarray(feat, dtype=np.float64)
+    if feat.ndim != 2 or feat.shape[1] != NIQE_FEATURES:
+        raise ValueError(f"niqe_score: features must be [nblocks, 36], got shape {feat.shape}")
+    mu = np.asarray(mu_pris, dtype=np.float64)
+    if mu.shape not in ((NIQE_FEATURES,), (1, NIQE_FEATURES)):
+        raise ValueError(f"niqe_score: mu_pris must have shape (36,) or (1, 36), got {mu.shape}")
+    mu = _f64(mu.reshape(-1), (NIQE_FEATURES,), "niqe_score: mu_pris")
+    cov = _f64(cov_pris, (NIQE_FEATURES, NIQE_FEATURES), "niqe_score: cov_pris")
+    return float(load().sr_niqe_score(feat.ctypes.data_as(C.c_void_p), feat.shape[0], mu.ctypes.data_as(C.c_void_p),
+                                      cov.ctypes.data_as(C.c_void_p)))
+
+
 def psnr_from_sse(sse: int, count: int, data_range: float = 255.0) -> float:
     return float(load().sr_psnr_from_sse(C.c_uint64(sse), C.c_uint64(count), data_range))
 
@@ -814,6 +904,25 @@ class Context:
         check(self.lib.sr_bench_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
                                    int(cn), crop_border, mode, float(data_range), C.byref(out)))
         return {"sse": out.sse, "ssim_sum": out.ssim_sum, "n_elems": int(out.n_elems), "n_map": int(out.n_map)}
+
+    def niqe_u8(self, d_img, stride, h, w, cn, crop_border=0) -> np.ndarray:
+        """sr_niqe_u8 -> records[2, nby * nbx] (NIQE_RECORD, scale-major) of the image cropped by crop_border (finish with
+        niqe_features and niqe_score).  Every argument is checked before the device is touched: ValueError, or its subclass
+        SrShapeError for a short stride or a side below 96 after the crop."""
+        if not d_img:
+            raise ValueError("niqe_u8: null image pointer")
+        nby, nbx = niqe_plan(h, w, cn, crop_border)["blocks"]
+        rec = np.zeros((2, nby * nbx), dtype=NIQE_RECORD)
+        check(self.lib.sr_niqe_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w), int(cn), int(crop_border),
+                                  rec.ctypes.data_as(C.c_void_p)))
+        return rec
+
+    def niqe_half_plane(self, shape) -> np.ndarray:
+        """sr_niqe_half_plane: 65536 x the scale-2 plane (int32, exact) that the last niqe_u8 call of this context left in its
+        scratch; shape = (H / 2, W / 2) of that call's niqe_plan size."""
+        out = np.zeros(shape, dtype=np.int32)
+        check(self.lib.sr_niqe_half_plane(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def ms_ssim_planes(self, level: int, shape) -> Tuple[np.ndarray, np.ndarray]:
         """sr_ms_ssim_planes: the exact integer sums (uint16, 4^level gray values each) of level `level` that the last

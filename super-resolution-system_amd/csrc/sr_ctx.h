@@ -63,6 +63,9 @@ struct sr_ctx {
     int msssim_h = 0, msssim_w = 0, msssim_levels = 0;  // what the planes hold (levels == 0: nothing valid)
     void *bench_ws = nullptr;                           // SR-benchmark PSNR / SSIM: per-block partials
     size_t bench_ws_bytes = 0;
+    void *niqe_ws = nullptr;                            // NIQE: the int32 half plane, then the block records
+    size_t niqe_ws_bytes = 0;
+    int niqe_H = 0, niqe_W = 0;                         // the kept plane whose half plane the scratch holds (0: nothing valid)
 };
 
 // Enqueue a small host->device table upload whose source stays alive until the next sync.

@@ -194,6 +194,7 @@ int sr_ctx_destroy(sr_ctx *ctx)
         if (ctx->cm_ws) (void)hipFree(ctx->cm_ws);
         if (ctx->msssim_ws) (void)hipFree(ctx->msssim_ws);
         if (ctx->bench_ws) (void)hipFree(ctx->bench_ws);
+        if (ctx->niqe_ws) (void)hipFree(ctx->niqe_ws);
         if (ctx->extract_tab.d) (void)hipFree(ctx->extract_tab.d);
         if (ctx->resize_tab.d) (void)hipFree(ctx->resize_tab.d);
         if (ctx->cubic_tab.d) (void)hipFree(ctx->cubic_tab.d);

@@ -68,6 +68,8 @@ class PipelineConfig:
                                # resize of the source ('ms_ssim_5scale'; the 'ms_ssim' key keeps the reference's single-scale value)
     qa_benchmark: bool = False # (with enable_qa): stage 4 also reports the SR-benchmark PSNR / SSIM (Y channel and RGB, a border of
                                # sr_scale pixels cropped) of the canvas against the INTER_CUBIC resize of the source ('sr_benchmark')
+    qa_niqe_params: str = ""   # (with enable_qa): path of NIQE's pristine parameters (.npz with BasicSR's keys, or .mat): stage 4 also
+                               # reports the NIQE of the canvas ('niqe_model'; the 'niqe' key keeps the reference's stand-in heuristic)
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
                                    # only the canvas comes back for the writer (a custom sr_backend gets host arrays)
     sr_weights: str = ""       # path of an SR network's weights (.npz, or .pth / .pt where torch imports): stage 2 runs the
@@ -115,6 +117,7 @@ class SuperResolutionPipeline:
                                           padding_mode=config.padding_mode, output_scale=float(config.sr_scale))
         self.blending_module = BlendingModule(method=config.blend_method, num_levels=config.num_pyramid_levels)
         self.quality_module = QualityAssessmentModule(device=config.qa_device)
+        self._niqe_params = None       # qa_niqe_params, read at the first use
         self.sr_net = None
         if config.sr_ensemble != 1:
             from sr_network import ensemble_mask
@@ -240,6 +243,23 @@ class SuperResolutionPipeline:
             ctx.sync()
             ref.free()
         out.update(psnr_y=y['psnr'], ssim_y=y['ssim'], psnr_rgb=rgb['psnr'], ssim_rgb=rgb['ssim'])
+
+    def _niqe_model(self, ctx, report: Dict[str, Any], d_canvas: int, canvas_shape) -> None:
+        """Stage 4's optional 'niqe_model' entry (qa_niqe_params): the NIQE of the canvas in HBM (no crop) under the pristine
+        parameters of the configured file.  Not the 'niqe' key of the commercial section, which is the reference's MSCN
+        stand-in.  A canvas with a side below 96, or with fewer than two blocks free of NaN features, has no score: the entry
+        is None and 'niqe_model_note' says why (the run does not fail).  One helper for the device-resident, the host-array
+        and the sharded path."""
+        import quality_assessment_module as qam
+        if self._niqe_params is None:
+            self._niqe_params = qam.load_niqe_params(self.config.qa_niqe_params)
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        try:
+            report['niqe_model'] = float(self.quality_module.calculate_niqe_model_device(d_canvas, (H, W, cn), self._niqe_params))
+        except ValueError as exc:
+            report['niqe_model'], report['niqe_model_note'] = None, str(exc)
+        finally:
+            ctx.sync()
 
     def _quality_map(self, ctx, d_src: int, src_shape, d_canvas: int, canvas_shape, tiles: List[Tile],
                      output_path: str) -> Dict[str, Any]:
@@ -369,6 +389,8 @@ class SuperResolutionPipeline:
                     self._ms_ssim(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_benchmark:
                     self._sr_benchmark(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
+                if self.config.qa_niqe_params:
+                    self._niqe_model(ctx, report, canvas.ptr, (H, W, 3))
                 score = qa.get('overall_score', 0)
             lap("assess")
             # Stage 5: the one download, then the writer
@@ -466,6 +488,8 @@ class SuperResolutionPipeline:
                         self._ms_ssim(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_benchmark:
                         self._sr_benchmark(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
+                    if self.config.qa_niqe_params:
+                        self._niqe_model(qctx, report, canvas.data_ptr(), (H, W, 3))
                     score = qa.get('overall_score', 0)
                 fused = qctx.download(canvas.data_ptr(), (H, W, 3), np.uint8)
                 self._write_outputs(fused, output_path, report)
@@ -560,6 +584,13 @@ class SuperResolutionPipeline:
                         self._sr_benchmark(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
                     finally:
                         d_src.free(); d_fused.free()
+                if self.config.qa_niqe_params:
+                    qctx = self.quality_module._ctx()
+                    d_fused = qctx.upload(fused)
+                    try:
+                        self._niqe_model(qctx, report, d_fused.ptr, fused.shape)
+                    finally:
+                        d_fused.free()
                 score = qa.get('overall_score', 0)
             # Stage 5: output
             self._write_outputs(fused, output_path, report)
@@ -605,6 +636,9 @@ async def main() -> int:
     ap.add_argument("--qa-benchmark", action="store_true",
                     help="stage 4 also reports the SR-benchmark PSNR / SSIM (Y channel and RGB, a border of --sr-scale pixels "
                          "cropped) of the result against the bicubic resize of the input (report key sr_benchmark)")
+    ap.add_argument("--qa-niqe-params", default="", metavar="PATH",
+                    help="NIQE's pristine parameters (.npz with the keys mu_pris_param / cov_pris_param, or .mat): stage 4 also "
+                         "reports the NIQE of the result (report key niqe_model; the key niqe stays the stand-in heuristic)")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node to use: N > 1 starts one process per GPU (RCCL)")
     ap.add_argument("--deadline-s", type=float, default=1800.0,
                     help="--gpus N: ranks still running after this many seconds are terminated (status 124)")
@@ -625,7 +659,8 @@ async def main() -> int:
         return 2
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act, sr_ensemble=args.sr_ensemble,
-                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark)
+                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark,
+                         qa_niqe_params=args.qa_niqe_params)
     if args.plan_only:
         from PIL import Image
         with Image.open(args.input) as im:

@@ -25,6 +25,11 @@ sharpness, contrast, 8-bit Lab colour statistics, YCrCb skin ratio, 5x5 texture,
 brightness regions, Canny edge density, the DFT high-frequency ratio and the MSCN / Sobel NIQE and BRISQUE stand-ins -- in
 one sr_commercial_u8 call (csrc/sr_commercial.hip), all ROIs included; the host only finishes the scalar formulas and
 keeps the reference's key order.  The pyiqa NIQE / BRISQUE models stay unavailable (``_niqe_available`` is False).
+
+NIQE proper (no reference counterpart in code: the reference asks pyiqa for it): ``calculate_niqe_model`` /
+``niqe_features`` / ``fit_niqe_model`` run the model of Mittal et al. as include/sr_hip.h defines it (csrc/sr_niqe.hip), with
+pristine parameters the caller supplies or fits.  ``calculate_niqe`` and the 'niqe' report key stay the reference's MSCN
+stand-in: another number under a similar name.
 u8 HxW, HxWx3 and HxWx4 (alpha ignored) images only; an image side above the FFT's longest line (32768) raises
 NotImplementedError before any device work.
 """
@@ -419,6 +424,65 @@ class QualityAssessmentModule:
         if not d_img1 or not d_img2:
             raise ValueError("evaluate_sr_benchmark: null device pointer")
         return self._sr_benchmark_dev(self._ctx(), int(d_img1), int(d_img2), args, data_range)
+
+    # -- NIQE, the model (no reference counterpart in code: the reference delegates to pyiqa.create_metric('niqe')) ----------
+    @staticmethod
+    def _niqe_args(shape, crop_border) -> Tuple[int, int, int, int]:
+        """Every refusal of the NIQE methods, on the host: ValueError (SrShapeError for a side below 96 after the crop).
+        -> (h, w, cn, crop_border)."""
+        shape = tuple(int(v) for v in shape)
+        if len(shape) not in (2, 3):
+            raise ValueError(f"niqe: need an H x W or H x W x C image, got shape {shape}")
+        cn = shape[2] if len(shape) == 3 else 1
+        if cn not in (1, 3):
+            raise ValueError("niqe: colour images must have 3 channels (RGB)")
+        _native.niqe_plan(shape[0], shape[1], cn, crop_border)                    # crop_border < 0, a too-small crop
+        return shape[0], shape[1], cn, int(crop_border)
+
+    @staticmethod
+    def _niqe_features_dev(ctx, d_img: int, args) -> Tuple[np.ndarray, np.ndarray]:
+        h, w, cn, cb = args
+        rec = ctx.niqe_u8(d_img, w * cn, h, w, cn, crop_border=cb)
+        return _native.niqe_features(rec), _native.niqe_sharpness(rec)
+
+    def niqe_features(self, image: np.ndarray, crop_border: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """The 36 NIQE features of every 96 x 96 block of a u8 image (RGB: on MATLAB's rounded u8 luma), as include/sr_hip.h
+        defines them, and every block's sharpness (its mean sigma at scale 1), which fit_niqe_model selects by.
+        -> (feat[nblocks, 36], sharpness[nblocks]), blocks row-major."""
+        a = self._require_u8(np.asarray(image), "niqe_features")
+        args = self._niqe_args(a.shape, crop_border)
+        ctx = self._ctx()
+        d = _DevImage(ctx, a)
+        try:
+            return self._niqe_features_dev(ctx, d.ptr, args)
+        finally:
+            d.free()
+
+    @staticmethod
+    def _niqe_value(feat: np.ndarray, params) -> float:
+        v = _native.niqe_score(feat, params["mu_pris_param"], params["cov_pris_param"])
+        if v != v:
+            raise _native.SrShapeError(_native.last_error())
+        return v
+
+    def calculate_niqe_model(self, image: np.ndarray, params, crop_border: int = 0) -> float:
+        """NIQE (Mittal, Soundararajan, Bovik 2013; the arithmetic of MATLAB's computequality and BasicSR's calculate_niqe) of
+        a u8 image under the pristine model params = {'mu_pris_param': (36,) or (1, 36), 'cov_pris_param': (36, 36)} -- from
+        load_niqe_params or fit_niqe_model; nothing is fetched.  Lower is better.  NOT calculate_niqe, which is the
+        reference's MSCN stand-in.  A side below 96 after the crop, or fewer than two blocks without a NaN feature, is a
+        ValueError (SrShapeError)."""
+        params = check_niqe_params(params)
+        feat, _ = self.niqe_features(image, crop_border)
+        return self._niqe_value(feat, params)
+
+    def calculate_niqe_model_device(self, d_image: int, shape, params, crop_border: int = 0) -> float:
+        """calculate_niqe_model on a dense u8 image that already lives in HBM (device address + shape)."""
+        params = check_niqe_params(params)
+        args = self._niqe_args(shape, crop_border)
+        if not d_image:
+            raise ValueError("calculate_niqe_model: null device pointer")
+        feat, _ = self._niqe_features_dev(self._ctx(), int(d_image), args)
+        return self._niqe_value(feat, params)
 
     def _calculate_ssim_simple(self, img1: np.ndarray, img2: np.ndarray) -> float:
         """quality_assessment_module.py:391-417 on already-gray u8 images."""
@@ -1029,6 +1093,73 @@ class QualityAssessmentModule:
 
 
 _FFT_MAX_LEN = 32768          # sr_fft_max_len(): longest DFT line of the hand-written FFT (checked against the library)
+
+
+# -- the pristine model of NIQE: check, fit, save, load ---------------------------------------------------------------------
+def check_niqe_params(params) -> Dict[str, np.ndarray]:
+    """-> {'mu_pris_param': float64 (36,), 'cov_pris_param': float64 (36, 36)}; ValueError for missing keys or other shapes
+    (mu may come as (36,) or (1, 36))."""
+    try:
+        mu, cov = np.asarray(params["mu_pris_param"], dtype=np.float64), np.asarray(params["cov_pris_param"], dtype=np.float64)
+    except (KeyError, TypeError, IndexError) as exc:
+        raise ValueError("NIQE parameters need the keys 'mu_pris_param' and 'cov_pris_param'") from exc
+    if mu.shape not in ((36,), (1, 36)):
+        raise ValueError(f"NIQE parameters: mu_pris_param must have shape (36,) or (1, 36), got {mu.shape}")
+    if cov.shape != (36, 36):
+        raise ValueError(f"NIQE parameters: cov_pris_param must have shape (36, 36), got {cov.shape}")
+    return {"mu_pris_param": np.ascontiguousarray(mu.reshape(36)), "cov_pris_param": np.ascontiguousarray(cov)}
+
+
+def fit_niqe_model(images, threshold: float = 0.75, module: Optional[QualityAssessmentModule] = None) -> Dict[str, np.ndarray]:
+    """The pristine model of NIQE fitted from the caller's own sharp u8 images by the published training rule (MATLAB's
+    estimatemodelparam): per image the blocks whose sharpness exceeds threshold x the image's sharpest block, pooled; their
+    mean and sample covariance.  -> {'mu_pris_param', 'cov_pris_param'}.  Fewer than 37 usable blocks is a ValueError that
+    gives the count."""
+    q = module or QualityAssessmentModule()
+    feats, sharps = [], []
+    for img in images:
+        f, s = q.niqe_features(img)
+        feats.append(f)
+        sharps.append(s)
+    mu, cov, _ = _native.niqe_fit(feats, sharps, threshold)
+    return {"mu_pris_param": mu, "cov_pris_param": cov}
+
+
+def save_niqe_params(path: str, params) -> None:
+    """.npz with BasicSR's key names (mu_pris_param (1, 36), cov_pris_param (36, 36)), or .mat with MATLAB's (mu_prisparam,
+    cov_prisparam) through scipy.io."""
+    p = check_niqe_params(params)
+    mu, cov = p["mu_pris_param"].reshape(1, 36), p["cov_pris_param"]
+    if str(path).lower().endswith(".mat"):
+        try:
+            from scipy import io as sio
+        except ImportError as exc:
+            raise RuntimeError("writing a .mat parameter file needs scipy") from exc
+        sio.savemat(str(path), {"mu_prisparam": mu, "cov_prisparam": cov})
+    elif str(path).lower().endswith(".npz"):
+        with open(str(path), "wb") as f:
+            np.savez(f, mu_pris_param=mu, cov_pris_param=cov)
+    else:
+        raise ValueError(f"NIQE parameter files are .npz or .mat, got {path!r}")
+
+
+def load_niqe_params(path: str) -> Dict[str, np.ndarray]:
+    """Reads what save_niqe_params writes: BasicSR's niqe_pris_params.npz layout, or MATLAB's modelparameters.mat layout."""
+    if str(path).lower().endswith(".mat"):
+        try:
+            from scipy import io as sio
+        except ImportError as exc:
+            raise RuntimeError("reading a .mat parameter file needs scipy") from exc
+        z = sio.loadmat(str(path))
+        if "mu_prisparam" not in z or "cov_prisparam" not in z:
+            raise ValueError(f"{path}: no mu_prisparam / cov_prisparam")
+        return check_niqe_params({"mu_pris_param": z["mu_prisparam"], "cov_pris_param": z["cov_prisparam"]})
+    if str(path).lower().endswith(".npz"):
+        with np.load(str(path), allow_pickle=False) as z:
+            if "mu_pris_param" not in z.files or "cov_pris_param" not in z.files:
+                raise ValueError(f"{path}: no mu_pris_param / cov_pris_param")
+            return check_niqe_params({"mu_pris_param": z["mu_pris_param"], "cov_pris_param": z["cov_pris_param"]})
+    raise ValueError(f"NIQE parameter files are .npz or .mat, got {path!r}")
 
 
 def _lab_tables_b() -> Tuple[np.ndarray, np.ndarray]:
