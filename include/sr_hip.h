@@ -761,6 +761,56 @@ SR_API int sr_lpips_tile_count(int h, int w, int tile, int *n_tiles);
 SR_API int sr_lpips_u8(sr_lpips_model *model, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b,
                        int h, int w, int cn, int tile, int tile_begin, int tile_end, double *h_layer_sums);
 
+/* ---- DISTS, deep image structure and texture similarity (csrc/sr_dists.hip, csrc/sr_dists_host.cpp) ---------------------------
+ * Ding, Ma, Wang, Simoncelli, "Image Quality Assessment: Unifying Structure and Texture Similarity", 2020, restated.  Not in
+ * the reference; SR papers report it beside PSNR / SSIM / LPIPS / NIQE.  PARITY UNPINNED: DISTS_pytorch, piq, pyiqa and
+ * torchvision are not available offline, and neither are the published alpha / beta.  Known distance to the package,
+ * rounding-level: it forms mean / variance / covariance in fp32 with the two-pass form mean((f - mu)^2); here they come from
+ * float64 sums.  Weights are supplied by the caller (nothing is fetched, none ship).
+ * Inputs: two u8 images of equal shape, cn 1 (gray repeated), 3, or 4 (alpha dropped).  Any h, w >= 1 is valid.
+ *   stage 0   x = u8 / 255, three channels, not normalised.
+ *   input     (x - mean_c) / std_c in fp32, in that order, tabulated per channel and u8 value; mean = (0.485, 0.456, 0.406),
+ *             std = (0.229, 0.224, 0.225) unless given.  Convolution zero padding acts on this normalised value.
+ *   stages    1 .. 5: torchvision VGG16's convolutions, 2, 2, 3, 3, 3 of 3 x 3, pad 1, + bias + ReLU; 64, 128, 256, 512, 512
+ *             channels; a stage's feature map is its last ReLU.  Each convolution sums in the order csrc/sr_conv_mfma.h
+ *             documents (the first: bias, then channels, then taps ascending, as fmaf).
+ *   L2 pool   in front of stages 2 .. 5 in place of the max pooling: y(Y, X) = sqrtf(sum_{j,i} g_j g_i x(2Y - 1 + j,
+ *             2X - 1 + i)^2 + 1e-12f), g = (1/4, 1/2, 1/4) (hanning(5)[1:-1], outer product, normalised), stride 2, zero
+ *             padding 1: the output side is ceil(n / 2).  All fp32: x * x rounded once, the nine terms g_j g_i (x * x) -- exact
+ *             products by powers of two -- added in row-major tap order onto 0, then + 1e-12f, then a correctly rounded sqrtf.
+ *   sums      per stage and channel (3 + 64 + 128 + 256 + 512 + 512 = 1475, stage 0 first) five float64 sums over the whole
+ *             feature map: a, b, a^2, b^2, a b.  Stage 0: exact integers of the u8 values (the / 255 and / 255^2 happen in
+ *             sr_dists_score).  Other stages: fp32 features converted to double, products in double, fixed order (inside a
+ *             block, blocks ascending, tiles ascending; no floating-point atomics): equal inputs give equal bits.
+ *   score     float64, n_k the pixel count of stage k: mu = sum / n, var = sum_sq / n - mu^2, cov = sum_ab / n - mu_a mu_b,
+ *             S1 = (2 mu_a mu_b + c1) / (mu_a^2 + mu_b^2 + c1), S2 = (2 cov + c2) / (var_a + var_b + c2), c1 = c2 = 1e-6;
+ *             DISTS = 1 - sum_ch (alpha_ch S1_ch + beta_ch S2_ch) / (sum alpha + sum beta).  For a == b every S1 and S2 is
+ *             exactly 1 and the value is 1 minus the rounded sum of the normalised weights: |DISTS(a, a)| <= 1e-12, not
+ *             necessarily 0.
+ * sr_dists_create: h_conv_w[i] = i-th of the 13 convolutions, dense OIHW fp32, h_conv_b[i] its bias; h_mean / h_std: 3 values
+ * or NULL for the defaults.  sr_dists_u8 streams the pair in `tile` x `tile` input tiles (multiple of 16; <= 0: one tile),
+ * each recomputing its receptive-field halo, zero padding at the true image border only, over tiles [tile_begin, tile_end)
+ * of the row-major tile grid (tile_end < 0: all); h_sums (1475 x 5) receives the sums over the tiles' own disjoint parts of
+ * every feature map, additive over disjoint tile ranges.  Synchronous.  Refused before any device call: null pointers, cn not
+ * 1, 3 or 4, a side below 1, a tile that is no multiple of 16 (SR_ERR_INVALID_ARG), a stride shorter than a row
+ * (SR_ERR_SHAPE), a null or destroyed model.
+ * sr_dists_l2pool_f32 (inspection): the pooling kernel on a dense planar [C][H][W] fp32 device tensor -> [C][ceil(H / 2)]
+ * [ceil(W / 2)].
+ * Host only, no context: sr_dists_layer_sizes gives the six (H, W) (stage 0 = the image, stage 1 the same, then ceil
+ * halving) as h_hw[12]; sr_dists_score gives the score from sums, those sizes and alpha / beta (1475 each, stage 0 first;
+ * finite with a positive total), and S1 / S2 per channel when s1 / s2 are not NULL. */
+typedef struct sr_dists_model sr_dists_model;
+SR_API int sr_dists_create(sr_ctx *ctx, const float *const *h_conv_w, const float *const *h_conv_b, const float *h_mean,
+                           const float *h_std, sr_dists_model **out);
+SR_API int sr_dists_destroy(sr_dists_model *model);
+SR_API int sr_dists_tile_count(int h, int w, int tile, int *n_tiles);
+SR_API int sr_dists_u8(sr_dists_model *model, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b,
+                       int h, int w, int cn, int tile, int tile_begin, int tile_end, double *h_sums);
+SR_API int sr_dists_l2pool_f32(sr_ctx *ctx, const float *d_in, int C, int H, int W, float *d_out);
+SR_API int sr_dists_layer_sizes(int h, int w, int *h_hw);
+SR_API int sr_dists_score(const double *sums, const int *hw, const float *alpha, const float *beta, double *score, double *s1,
+                          double *s2);
+
 /* ---- local SR backend: compact "VGG-style" SR network (csrc/sr_srnet.hip) ------------------------------------------------
  * Stage 2 of the reference is a remote API client (main.py:194-267); this is a local learned upscaler of the family
  * Real-ESRGAN ships as SRVGGNetCompact, restated (parity with that package is unpinned: neither it nor a checkpoint exists

@@ -249,6 +249,13 @@ SIGNATURES = {
     "sr_lpips_layer_sizes": (_i, [_i, _i, _i, _pi]),
     "sr_lpips_tile_count": (_i, [_i, _i, _i, _pi]),
     "sr_lpips_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(_dbl)]),
+    "sr_dists_create": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp)]),
+    "sr_dists_destroy": (_i, [_vp]),
+    "sr_dists_tile_count": (_i, [_i, _i, _i, _pi]),
+    "sr_dists_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
+    "sr_dists_l2pool_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "sr_dists_layer_sizes": (_i, [_i, _i, _pi]),
+    "sr_dists_score": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_dbl), _vp, _vp]),
     "sr_srnet_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "sr_srnet_destroy": (_i, [_vp]),
     "sr_srnet_plan": (_i, [_i, _i, _i, _i, _i, _i, _pi, _pi, C.POINTER(_sz)]),
@@ -1485,6 +1492,172 @@ class LpipsModel:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+# ------------------------------------------------------------------------------------------
+# DISTS (sr_dists_*): caller-supplied weights, state-dict names of DISTS_pytorch.DISTS()
+# ------------------------------------------------------------------------------------------
+# the 13 convolutions in forward order: "stage<S>.<index in torchvision's VGG16 features>"; the published weights.pt holds
+# only alpha and beta, so torchvision's own "features.<index>" is accepted for each
+DISTS_CONV_KEYS = ["stage1.0", "stage1.2", "stage2.5", "stage2.7", "stage3.10", "stage3.12", "stage3.14", "stage4.17",
+                   "stage4.19", "stage4.21", "stage5.24", "stage5.26", "stage5.28"]
+DISTS_CONV_SHAPES = LPIPS_CONV_SHAPES["vgg"]
+DISTS_CHANNELS = (3, 64, 128, 256, 512, 512)
+DISTS_TOTAL = sum(DISTS_CHANNELS)        # 1475
+_DISTS_HANN = np.outer([0.25, 0.5, 0.25], [0.25, 0.5, 0.25])
+
+
+def load_dists_weights(path: str) -> dict:
+    """Reads a flat .npz holding the VGG16 convolutions (``stageN.K.weight`` / ``.bias`` or ``features.K.*``) and ``alpha`` /
+    ``beta`` (numpy.load with allow_pickle=False: nothing in the file is executed).  Returns {name: ndarray}."""
+    with np.load(path, allow_pickle=False) as z:
+        return {k: np.asarray(z[k]) for k in z.files}
+
+
+def dists_pack_weights(weights: dict):
+    """Validates a dict of arrays -> (conv weights, conv biases, alpha, beta, mean or None, std or None) as contiguous fp32
+    arrays.  Every refusal is a ValueError that names the key.  Host only."""
+    convs_w, convs_b = [], []
+    for key, (co, ci, k) in zip(DISTS_CONV_KEYS, DISTS_CONV_SHAPES):
+        alt = "features." + key.split(".")[1]
+        arrs = []
+        for suffix, shape in ((".weight", (co, ci, k, k)), (".bias", (co,))):
+            name = next((n for n in (key + suffix, alt + suffix) if n in weights), None)
+            if name is None:
+                raise ValueError(f"DISTS weights lack {key}{suffix} (or {alt}{suffix})")
+            a = np.ascontiguousarray(weights[name], dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"DISTS weight {name}: expected {shape}, got {a.shape}")
+            arrs.append(a)
+        convs_w.append(arrs[0])
+        convs_b.append(arrs[1])
+    ab = []
+    for name in ("alpha", "beta"):
+        if name not in weights:
+            raise ValueError(f"DISTS weights lack {name}")
+        v = np.ascontiguousarray(np.asarray(weights[name], dtype=np.float32).reshape(-1))
+        if v.shape != (DISTS_TOTAL,):
+            raise ValueError(f"DISTS weight {name}: expected {DISTS_TOTAL} values, got {np.asarray(weights[name]).shape}")
+        if not np.all(np.isfinite(v)):
+            raise ValueError(f"DISTS weight {name}: not finite")
+        ab.append(v)
+    if not float(ab[0].astype(np.float64).sum() + ab[1].astype(np.float64).sum()) > 0.0:
+        raise ValueError("DISTS weights alpha / beta: the total must be positive")
+    ms = []
+    for name in ("mean", "std"):
+        if name not in weights:
+            ms.append(None)
+            continue
+        v = np.ascontiguousarray(np.asarray(weights[name], dtype=np.float32).reshape(-1))
+        if v.shape != (3,) or not np.all(np.isfinite(v)) or (name == "std" and np.any(v == 0)):
+            raise ValueError(f"DISTS weight {name}: expected 3 finite values (std non-zero), got {np.asarray(weights[name]).shape}")
+        ms.append(v)
+    for name, v in weights.items():
+        if name.startswith("stage") and name.endswith(".filter"):     # L2pooling's buffer: fixed here, so it must be the Hann one
+            f = np.asarray(v, dtype=np.float64)
+            if f.ndim != 4 or f.shape[1:] != (1, 3, 3) or not np.allclose(f, _DISTS_HANN[None, None], rtol=0, atol=1e-7):
+                raise ValueError(f"DISTS weight {name}: not the 3 x 3 Hann filter outer((1/4, 1/2, 1/4)) the L2 pooling here is fixed to")
+    return convs_w, convs_b, ab[0], ab[1], ms[0], ms[1]
+
+
+def dists_synthetic_weights(seed: int = 20260519) -> dict:
+    """Seeded random weights of the real shapes (He-scaled convolutions, alpha, beta ~ U(0, 1)) for timing and structural
+    tests.  NOT the published weights: those cannot be fetched offline."""
+    rng = np.random.default_rng(seed)
+    w = {}
+    for key, (co, ci, k) in zip(DISTS_CONV_KEYS, DISTS_CONV_SHAPES):
+        w[key + ".weight"] = (rng.standard_normal((co, ci, k, k)) * np.sqrt(2.0 / (ci * k * k))).astype(np.float32)
+        w[key + ".bias"] = rng.uniform(0, 0.1, co).astype(np.float32)
+    w["alpha"] = rng.uniform(0, 1, (1, DISTS_TOTAL, 1, 1)).astype(np.float32)
+    w["beta"] = rng.uniform(0, 1, (1, DISTS_TOTAL, 1, 1)).astype(np.float32)
+    return w
+
+
+def dists_layer_sizes(h: int, w: int):
+    """Host only: the six (H, W) of DISTS's feature maps (stage 0 = the image, then ceil halving from stage 2 on)."""
+    out = (C.c_int * 12)()
+    check(load().sr_dists_layer_sizes(int(h), int(w), out))
+    return [(out[2 * i], out[2 * i + 1]) for i in range(6)]
+
+
+def dists_score(sums, hw, alpha, beta, per_channel: bool = False):
+    """Host only: the DISTS value from 1475 x 5 float64 sums, the six sizes and alpha / beta (sr_dists_score)."""
+    sums = _f64(sums, (DISTS_TOTAL, 5), "sums")
+    hw_a = np.ascontiguousarray(np.asarray(hw, dtype=np.int32).reshape(-1))
+    if hw_a.shape != (12,):
+        raise ValueError("dists_score: hw must hold six (H, W)")
+    al = np.ascontiguousarray(np.asarray(alpha, dtype=np.float32).reshape(-1))
+    be = np.ascontiguousarray(np.asarray(beta, dtype=np.float32).reshape(-1))
+    if al.shape != (DISTS_TOTAL,) or be.shape != (DISTS_TOTAL,):
+        raise ValueError(f"dists_score: alpha and beta must hold {DISTS_TOTAL} values")
+    score = C.c_double(0.0)
+    s1, s2 = np.empty(DISTS_TOTAL, np.float64), np.empty(DISTS_TOTAL, np.float64)
+    check(load().sr_dists_score(sums.ctypes.data, hw_a.ctypes.data, al.ctypes.data, be.ctypes.data, C.byref(score),
+                                s1.ctypes.data if per_channel else None, s2.ctypes.data if per_channel else None))
+    return (score.value, s1, s2) if per_channel else score.value
+
+
+class DistsModel:
+    """sr_dists_model: the VGG16 convolutions resident on the GPU, alpha / beta on the host."""
+
+    def __init__(self, ctx: Context, weights: dict):
+        convs_w, convs_b, self.alpha, self.beta, mean, std = dists_pack_weights(weights)
+        self.ctx = ctx
+        pw = (C.c_void_p * 13)(*[a.ctypes.data for a in convs_w])
+        pb = (C.c_void_p * 13)(*[a.ctypes.data for a in convs_b])
+        h = C.c_void_p()
+        check(ctx.lib.sr_dists_create(ctx.handle, pw, pb, mean.ctypes.data if mean is not None else None,
+                                      std.ctypes.data if std is not None else None, C.byref(h)))
+        self.handle = h
+
+    def layer_sizes(self, h: int, w: int):
+        return dists_layer_sizes(h, w)
+
+    def tile_count(self, h: int, w: int, tile: int) -> int:
+        n = C.c_int(0)
+        check(self.ctx.lib.sr_dists_tile_count(int(h), int(w), int(tile), C.byref(n)))
+        return n.value
+
+    def sums(self, d_a: int, stride_a: int, d_b: int, stride_b: int, h: int, w: int, cn: int, tile: int = 4096,
+             tile_begin: int = 0, tile_end: int = -1) -> np.ndarray:
+        """The 1475 x 5 float64 sums (a, b, a^2, b^2, a b per channel, stage 0 first) over tiles [tile_begin, tile_end):
+        additive across disjoint tile ranges."""
+        out = np.zeros((DISTS_TOTAL, 5), np.float64)
+        check(self.ctx.lib.sr_dists_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h),
+                                       int(w), int(cn), int(tile), int(tile_begin), int(tile_end), out.ctypes.data))
+        return out
+
+    def value(self, d_a: int, stride_a: int, d_b: int, stride_b: int, h: int, w: int, cn: int, tile: int = 4096,
+              per_channel: bool = False):
+        """DISTS of the pair; with per_channel also S1 and S2 (1475 each)."""
+        sums = self.sums(d_a, stride_a, d_b, stride_b, h, w, cn, tile)
+        return dists_score(sums, self.layer_sizes(h, w), self.alpha, self.beta, per_channel)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.sr_dists_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def dists_l2pool(ctx, x: np.ndarray) -> np.ndarray:
+    """The L2 pooling kernel on a dense [C][H][W] fp32 array (inspection: sr_dists_l2pool_f32)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 3:
+        raise ValueError("dists_l2pool: a [C][H][W] array")
+    c, h, w = x.shape
+    ho, wo = (h + 1) // 2, (w + 1) // 2
+    d_in, d_out = ctx.upload(x), ctx.alloc(c * ho * wo * 4)
+    try:
+        check(ctx.lib.sr_dists_l2pool_f32(ctx.handle, C.c_void_p(d_in.ptr), c, h, w, C.c_void_p(d_out.ptr)))
+        return ctx.download(d_out.ptr, (c, ho, wo), np.float32)
+    finally:
+        d_in.free(); d_out.free()
 
 
 # ------------------------------------------------------------------------------------------

@@ -20,106 +20,21 @@
 #include <cstring>
 #include <vector>
 
-#include "sr_conv_mfma.h"
+#include "sr_vgg_stream.h"
 
 namespace {
 
-enum { LP_CONV = 0, LP_POOL = 1, LP_TAP = 2 };
-
-struct LpLayer {
-    int kind;
-    int cout, cin, k, s, p;   // conv / pool geometry
-    int tap;                  // LP_TAP: LPIPS layer index 0..4
-    int widx;                 // LP_CONV: index into the weight arrays
-};
-
-// ---------------------------------------------------------------------------------------------------------------
-// Stem convolution (Cin = 3) straight from the u8 image: one thread = one output pixel x 64 output channels.
-// value(c, y, x) = ((u8 / 255) * 2 - 1 - shift_c) / scale_c inside the image, 0 outside (Conv2d zero padding acts on
-// the ScalingLayer output).  The 3 x 256 possible values are tabulated in LDS once per block with exactly those fp32
-// operations.  Weights are laid out [c][tap][64] so the 64 multipliers of one input value are wave-uniform
-// (scalar loads), the inner loop is 64 v_fmac with an SGPR operand.
-// ---------------------------------------------------------------------------------------------------------------
-template <int KS, int S, int P>
-__global__ __launch_bounds__(256) void k_lp_conv_stem(const unsigned char *__restrict__ img, long long stride, int cn,
-                                                      int H, int W, const float *__restrict__ wt,
-                                                      const float *__restrict__ bias, float sh0, float sh1, float sh2,
-                                                      float sc0, float sc1, float sc2, float *__restrict__ out, int ya,
-                                                      int xa, int rows, int cols, int pitch, long long plane)
-{
-    __shared__ float lut[3][256];
-    const int tid = threadIdx.y * 64 + threadIdx.x;
-    for (int i = tid; i < 768; i += 256) {
-        const int c = i >> 8, v = i & 255;
+// The stem table of LPIPS: ((u8 / 255) * 2 - 1 - shift_c) / scale_c, the ScalingLayer output, in these fp32 operations.
+struct LpipsTable {
+    float sh0, sh1, sh2, sc0, sc1, sc2;
+    __device__ float operator()(int c, int v) const
+    {
         const float t = (float)v / 255.0f;
         const float u = t * 2.0f - 1.0f;
         const float sh = c == 0 ? sh0 : (c == 1 ? sh1 : sh2), sc = c == 0 ? sc0 : (c == 1 ? sc1 : sc2);
-        lut[c][v] = (u - sh) / sc;
+        return (u - sh) / sc;
     }
-    __syncthreads();
-    const int lx = blockIdx.x * 64 + threadIdx.x, ly = blockIdx.y * 4 + threadIdx.y;
-    if (lx >= cols || ly >= rows) return;
-    const int oy = ya + ly, ox = xa + lx;
-    float acc[64];
-#pragma unroll
-    for (int co = 0; co < 64; ++co) acc[co] = bias[co];
-    constexpr int T = KS * KS;
-#pragma unroll 1
-    for (int c = 0; c < 3; ++c) {
-        const int cs = cn == 1 ? 0 : c;              // gray is repeated, alpha (cn == 4) is dropped
-#pragma unroll 1
-        for (int ky = 0; ky < KS; ++ky) {
-            const int gy = oy * S - P + ky;
-            const bool yok = gy >= 0 && gy < H;
-            const unsigned char *row = img + (size_t)(yok ? gy : 0) * stride;
-#pragma unroll 1
-            for (int kx = 0; kx < KS; ++kx) {
-                const int gx = ox * S - P + kx;
-                float v = 0.0f;
-                if (yok && gx >= 0 && gx < W) v = lut[c][row[(size_t)gx * cn + cs]];
-                const float *wp = wt + ((size_t)c * T + ky * KS + kx) * 64;
-#pragma unroll
-                for (int co = 0; co < 64; ++co) acc[co] = fmaf(wp[co], v, acc[co]);
-            }
-        }
-    }
-    float *o = out + (size_t)ly * pitch + lx;
-#pragma unroll
-    for (int co = 0; co < 64; ++co) o[(size_t)co * plane] = fmaxf(acc[co], 0.0f);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Implicit-GEMM convolution + bias + ReLU on v_mfma_f32_32x32x2_f32, stride 1, KS x KS, zero padding P = KS / 2:
-// conv_mfma_mainloop<KS, CC, 2, false> (sr_conv_mfma.h states the GEMM view, the block shape, the LDS staging and the
-// summation order) plus a ReLU epilogue.  Block = 4 waves = 8 output rows x 32 columns x 64 couts.  GUARD is off: this
-// kernel is not told how many rows and columns its input buffer holds.
-// ---------------------------------------------------------------------------------------------------------------
-template <int KS, int CC>
-__global__ __launch_bounds__(256) void k_lp_conv_mfma(const float *__restrict__ in, long long in_plane, int in_pitch,
-                                                      int in_ya, int in_xa, int H_in, int W_in, int cin,
-                                                      const float *__restrict__ wslab, const float *__restrict__ bias,
-                                                      float *__restrict__ out, long long out_plane, int out_pitch,
-                                                      int out_ya, int out_xa, int rows, int cols)
-{
-    const MfmaLane ln = mfma_lane();
-    f32x16 acc[2][2];
-    conv_mfma_mainloop<KS, CC, 2, false>(ln, in, in_plane, in_pitch, in_ya, in_xa, 0, 0, H_in, W_in, cin, wslab, bias, out_ya, out_xa, acc);
-    // epilogue: ReLU, masked store
-    const int col = ln.ox0 + ln.l32;
-    if (col >= cols) return;
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr) {
-        const int row = ln.oy0 + 2 * ln.wave + pr;
-        if (row >= rows) continue;
-#pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = ln.ct * 64 + mfma_cout(c2, r, ln.half);
-                out[(size_t)co * out_plane + (size_t)row * out_pitch + col] = fmaxf(acc[c2][pr][r], 0.0f);
-            }
-    }
-}
+};
 
 // MaxPool2d(K, S), no padding, floor mode: every window lies inside the input range by construction.
 template <int K, int S>
@@ -136,13 +51,6 @@ __global__ __launch_bounds__(256) void k_lp_pool(const float *__restrict__ in, l
 #pragma unroll
         for (int i = 0; i < K; ++i) m = fmaxf(m, p[(size_t)j * in_pitch + i]);
     out[(size_t)c * out_plane + (size_t)y * out_pitch + x] = m;
-}
-
-__device__ __forceinline__ double lp_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
 }
 
 // One LPIPS tap over the tile's own part of the feature map: per pixel
@@ -177,37 +85,6 @@ __global__ __launch_bounds__(256) void k_lp_tap(const float *__restrict__ fa, co
     if ((tid & 63) == 0) ws[tid >> 6] = v;
     __syncthreads();
     if (tid == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-
-// acc += sum(part[0..n)) in a fixed order (one block)
-__global__ __launch_bounds__(256) void k_lp_accum(const double *__restrict__ part, long long n, double *__restrict__ acc)
-{
-    __shared__ double sh[256];
-    double s = 0.0;
-    for (long long i = threadIdx.x; i < n; i += 256) s += part[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *acc += sh[0];
-}
-
-struct Range {
-    int a = 0, b = 0;                 // [a, b)
-    bool empty() const { return a >= b; }
-    int n() const { return b > a ? b - a : 0; }
-};
-
-Range hull(Range p, Range q)
-{
-    if (p.empty()) return q;
-    if (q.empty()) return p;
-    Range r;
-    r.a = std::min(p.a, q.a);
-    r.b = std::max(p.b, q.b);
-    return r;
 }
 
 }  // namespace
@@ -250,57 +127,6 @@ static void lp_arch(int net, std::vector<LpLayer> &L)
         pool(2, 2); conv(256, 128, 3, 1, 1); conv(256, 256, 3, 1, 1); conv(256, 256, 3, 1, 1); tap(2);
         pool(2, 2); conv(512, 256, 3, 1, 1); conv(512, 512, 3, 1, 1); conv(512, 512, 3, 1, 1); tap(3);
         pool(2, 2); conv(512, 512, 3, 1, 1); conv(512, 512, 3, 1, 1); conv(512, 512, 3, 1, 1); tap(4);
-    }
-}
-
-// Per-activation geometry of an h x w input: activation 0 is the image, activation j the output of the j-th conv / pool.
-struct LpGeom {
-    std::vector<int> H, W, C, S;      // extent, channels and cumulative stride per activation
-    std::vector<int> act_of_layer;    // activation a layer reads (conv / pool) or taps
-};
-
-static bool lp_geometry(const std::vector<LpLayer> &L, int h, int w, LpGeom &G)
-{
-    G.H = {h}; G.W = {w}; G.C = {3}; G.S = {1};
-    G.act_of_layer.clear();
-    for (auto &l : L) {
-        G.act_of_layer.push_back((int)G.H.size() - 1);
-        if (l.kind == LP_TAP) continue;
-        const int hi = G.H.back(), wi = G.W.back();
-        const int ho = (hi + 2 * l.p - l.k) / l.s + 1, wo = (wi + 2 * l.p - l.k) / l.s + 1;
-        if (hi + 2 * l.p < l.k || wi + 2 * l.p < l.k || ho < 1 || wo < 1) return false;
-        G.H.push_back(ho); G.W.push_back(wo);
-        G.C.push_back(l.kind == LP_CONV ? l.cout : G.C.back());
-        G.S.push_back(G.S.back() * l.s);
-    }
-    return true;
-}
-
-// Ranges (one axis) every activation of a tile must cover: its own part of every tapped activation plus what the
-// deeper layers need of it.  t0 / t1: the tile's span in input pixels (t1 < 0: to the end).
-static void lp_ranges(const std::vector<LpLayer> &L, const LpGeom &G, const std::vector<int> &ext, int t0, int t1,
-                      std::vector<Range> &need, std::vector<Range> &own)
-{
-    const int na = (int)ext.size();
-    need.assign(na, Range());
-    own.assign(na, Range());
-    for (int j = 0; j < na; ++j) {
-        own[j].a = std::min(t0 / G.S[j], ext[j]);
-        own[j].b = t1 < 0 ? ext[j] : std::min(t1 / G.S[j], ext[j]);
-    }
-    for (int li = (int)L.size() - 1; li >= 0; --li) {
-        const LpLayer &l = L[li];
-        const int ai = G.act_of_layer[li];
-        if (l.kind == LP_TAP) {
-            need[ai] = hull(need[ai], own[ai]);
-            continue;
-        }
-        const Range o = need[ai + 1];
-        if (o.empty()) continue;
-        Range r;
-        r.a = std::max(o.a * l.s - l.p, 0);
-        r.b = std::min((o.b - 1) * l.s - l.p + l.k, ext[ai]);
-        need[ai] = hull(need[ai], r);
     }
 }
 
@@ -499,10 +325,10 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
                     const uint8_t *img = im == 0 ? d_a : d_b;
                     const long long st = im == 0 ? stride_a : stride_b;
                     const dim3 grid((cols + 63) / 64, (rows + 3) / 4);
-#define STEM_ARGS img, st, cn, h, w, m->d_w[l.widx], m->d_b[l.widx], m->shift[0], m->shift[1], m->shift[2], m->scale[0], \
-                  m->scale[1], m->scale[2], dst, ny[ao].a, nx[ao].a, rows, cols, pitch[ao], plane[ao]
-                    if (l.k == 3) hipLaunchKernelGGL((k_lp_conv_stem<3, 1, 1>), grid, blk, 0, ctx->stream, STEM_ARGS);
-                    else hipLaunchKernelGGL((k_lp_conv_stem<11, 4, 2>), grid, blk, 0, ctx->stream, STEM_ARGS);
+                    const LpipsTable tab{m->shift[0], m->shift[1], m->shift[2], m->scale[0], m->scale[1], m->scale[2]};
+#define STEM_ARGS img, st, cn, h, w, m->d_w[l.widx], m->d_b[l.widx], tab, dst, ny[ao].a, nx[ao].a, rows, cols, pitch[ao], plane[ao]
+                    if (l.k == 3) hipLaunchKernelGGL((k_lp_conv_stem<3, 1, 1, LpipsTable>), grid, blk, 0, ctx->stream, STEM_ARGS);
+                    else hipLaunchKernelGGL((k_lp_conv_stem<11, 4, 2, LpipsTable>), grid, blk, 0, ctx->stream, STEM_ARGS);
 #undef STEM_ARGS
                 } else {
                     ProfScope ps(ctx, "lpips_conv_mfma");

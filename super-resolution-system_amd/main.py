@@ -68,6 +68,8 @@ class PipelineConfig:
                                # resize of the source ('ms_ssim_5scale'; the 'ms_ssim' key keeps the reference's single-scale value)
     qa_benchmark: bool = False # (with enable_qa): stage 4 also reports the SR-benchmark PSNR / SSIM (Y channel and RGB, a border of
                                # sr_scale pixels cropped) of the canvas against the INTER_CUBIC resize of the source ('sr_benchmark')
+    qa_dists_weights: str = "" # (with enable_qa): path of DISTS weights (.npz: the VGG16 convolutions and alpha / beta): stage 4 also reports
+                               # the DISTS of the canvas against the INTER_CUBIC resize of the source ('dists')
     qa_niqe_params: str = ""   # (with enable_qa): path of NIQE's pristine parameters (.npz with BasicSR's keys, or .mat): stage 4 also
                                # reports the NIQE of the canvas ('niqe_model'; the 'niqe' key keeps the reference's stand-in heuristic)
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
@@ -118,6 +120,7 @@ class SuperResolutionPipeline:
         self.blending_module = BlendingModule(method=config.blend_method, num_levels=config.num_pyramid_levels)
         self.quality_module = QualityAssessmentModule(device=config.qa_device)
         self._niqe_params = None       # qa_niqe_params, read at the first use
+        self._dists_model = None       # qa_dists_weights, loaded at the first use
         self.sr_net = None
         if config.sr_ensemble != 1:
             from sr_network import ensemble_mask
@@ -243,6 +246,24 @@ class SuperResolutionPipeline:
             ctx.sync()
             ref.free()
         out.update(psnr_y=y['psnr'], ssim_y=y['ssim'], psnr_rgb=rgb['psnr'], ssim_rgb=rgb['ssim'])
+
+    def _dists(self, ctx, report: Dict[str, Any], d_src: int, src_shape, d_canvas: int, canvas_shape) -> None:
+        """Stage 4's optional 'dists' entry (qa_dists_weights): DISTS of the canvas against the INTER_CUBIC resize of the
+        source to the canvas size (the pair of 'sr_benchmark'), both in HBM, under the weights of the configured file.  One
+        helper for the device-resident, the host-array and the sharded path."""
+        import _native
+        if self._dists_model is None:
+            self._dists_model = _native.DistsModel(ctx, _native.load_dists_weights(self.config.qa_dists_weights))
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        ih, iw = int(src_shape[0]), int(src_shape[1])
+        ref = ctx.alloc(H * W * cn)
+        try:
+            ctx.resize_cubic_u8(d_src, iw * cn, ih, iw, cn, ref.ptr, W * cn, H, W)
+            report['dists'] = float(self._dists_model.value(ref.ptr, W * cn, d_canvas, W * cn, H, W, cn,
+                                                            tile=self.quality_module.dists_tile))
+        finally:
+            ctx.sync()
+            ref.free()
 
     def _niqe_model(self, ctx, report: Dict[str, Any], d_canvas: int, canvas_shape) -> None:
         """Stage 4's optional 'niqe_model' entry (qa_niqe_params): the NIQE of the canvas in HBM (no crop) under the pristine
@@ -391,6 +412,8 @@ class SuperResolutionPipeline:
                     self._sr_benchmark(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_niqe_params:
                     self._niqe_model(ctx, report, canvas.ptr, (H, W, 3))
+                if self.config.qa_dists_weights:
+                    self._dists(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 score = qa.get('overall_score', 0)
             lap("assess")
             # Stage 5: the one download, then the writer
@@ -490,6 +513,8 @@ class SuperResolutionPipeline:
                         self._sr_benchmark(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_niqe_params:
                         self._niqe_model(qctx, report, canvas.data_ptr(), (H, W, 3))
+                    if self.config.qa_dists_weights:
+                        self._dists(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     score = qa.get('overall_score', 0)
                 fused = qctx.download(canvas.data_ptr(), (H, W, 3), np.uint8)
                 self._write_outputs(fused, output_path, report)
@@ -591,6 +616,13 @@ class SuperResolutionPipeline:
                         self._niqe_model(qctx, report, d_fused.ptr, fused.shape)
                     finally:
                         d_fused.free()
+                if self.config.qa_dists_weights:
+                    qctx = self.quality_module._ctx()
+                    d_src, d_fused = qctx.upload(original), qctx.upload(fused)
+                    try:
+                        self._dists(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
+                    finally:
+                        d_src.free(); d_fused.free()
                 score = qa.get('overall_score', 0)
             # Stage 5: output
             self._write_outputs(fused, output_path, report)
@@ -639,6 +671,10 @@ async def main() -> int:
     ap.add_argument("--qa-niqe-params", default="", metavar="PATH",
                     help="NIQE's pristine parameters (.npz with the keys mu_pris_param / cov_pris_param, or .mat): stage 4 also "
                          "reports the NIQE of the result (report key niqe_model; the key niqe stays the stand-in heuristic)")
+    ap.add_argument("--qa-dists-weights", default="", metavar="PATH",
+                    help="DISTS weights (.npz with the VGG16 convolutions stageN.K.weight / .bias, or features.K.*, and alpha / "
+                         "beta): stage 4 also reports the DISTS of the result against the bicubic resize of the input (report "
+                         "key dists)")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node to use: N > 1 starts one process per GPU (RCCL)")
     ap.add_argument("--deadline-s", type=float, default=1800.0,
                     help="--gpus N: ranks still running after this many seconds are terminated (status 124)")
@@ -660,7 +696,7 @@ async def main() -> int:
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act, sr_ensemble=args.sr_ensemble,
                          qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark,
-                         qa_niqe_params=args.qa_niqe_params)
+                         qa_niqe_params=args.qa_niqe_params, qa_dists_weights=args.qa_dists_weights)
     if args.plan_only:
         from PIL import Image
         with Image.open(args.input) as im:

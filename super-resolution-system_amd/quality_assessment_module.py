@@ -126,7 +126,8 @@ class _DevImage:
 class QualityAssessmentModule:
     def __init__(self, device: str = 'cpu', thresholds: Optional[QualityThresholds] = None,
                  scale_config: Optional[ScaleConfig] = None, gpu_index: int = 0, ssim_branch: str = 'A',
-                 gray_shift: int = 15, lpips_weights: Optional[Dict[str, Any]] = None, lpips_tile: int = 4096):
+                 gray_shift: int = 15, lpips_weights: Optional[Dict[str, Any]] = None, lpips_tile: int = 4096,
+                 dists_weights: Any = None, dists_tile: int = 4096):
         # the reference's `device` only places the LPIPS networks; the metrics here always run on the GPU
         self.device = device
         self.thresholds = thresholds or QualityThresholds()
@@ -140,6 +141,9 @@ class QualityAssessmentModule:
         self.lpips_model_vgg = None      # stay None without caller-supplied weights (nothing is fetched)
         self.lpips_model_alex = None
         self._init_lpips_models(lpips_weights)
+        self.dists_tile = int(dists_tile)
+        self.dists_model = None          # stays None without caller-supplied weights (nothing is fetched)
+        self._init_dists_model(dists_weights)
         self._niqe_available = False
         self._brisque_available = False
 
@@ -159,6 +163,16 @@ class QualityAssessmentModule:
             if isinstance(w, (str, os.PathLike)):
                 w = _native.load_lpips_weights(os.fspath(w))
             setattr(self, f"lpips_model_{net}", _native.LpipsModel(self._ctx(), net, w))
+
+    def _init_dists_model(self, dists_weights: Any = None) -> None:
+        """DISTS from caller-supplied arrays: a flat .npz path or a dict (env SR_DISTS_WEIGHTS as a default) holding the VGG16
+        convolutions and alpha / beta under the names _native.dists_pack_weights documents."""
+        w = dists_weights if dists_weights is not None else (os.environ.get("SR_DISTS_WEIGHTS") or None)
+        if w is None:
+            return
+        if isinstance(w, (str, os.PathLike)):
+            w = _native.load_dists_weights(os.fspath(w))
+        self.dists_model = _native.DistsModel(self._ctx(), w)
 
     # -- preprocessing (quality_assessment_module.py:169-195, 304-308) --------------------------------
     def _preprocess_image(self, image: Any, to_tensor: bool = False) -> np.ndarray:
@@ -532,6 +546,42 @@ class QualityAssessmentModule:
         finally:
             da.free(); db.free()
 
+    # -- DISTS (no reference counterpart; include/sr_hip.h holds the definition, parity with DISTS_pytorch unpinned) -----------
+    def _dists_dev(self, a: _DevImage, b: _DevImage) -> float:
+        if self.dists_model is None:
+            raise RuntimeError("DISTS needs caller-supplied weights (dists_weights= or SR_DISTS_WEIGHTS); none were given")
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"calculate_dists: images differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")
+        if a.cn not in (1, 3, 4):
+            raise ValueError(f"calculate_dists: 1, 3 or 4 channels, got {tuple(a.shape)}")
+        return float(self.dists_model.value(a.ptr, a.stride, b.ptr, b.stride, a.h, a.w, a.cn, tile=self.dists_tile))
+
+    def calculate_dists(self, img1: np.ndarray, img2: np.ndarray) -> float:
+        """DISTS (Ding et al. 2020) of two u8 images of equal shape, lower is better, 0 for equal images (up to 1e-12)."""
+        if self.dists_model is None:
+            raise RuntimeError("DISTS needs caller-supplied weights (dists_weights= or SR_DISTS_WEIGHTS); none were given")
+        a = self._require_u8(np.asarray(img1), "calculate_dists")
+        b = self._require_u8(np.asarray(img2), "calculate_dists")
+        if a.shape != b.shape:
+            raise ValueError(f"calculate_dists: images differ in shape: {a.shape} vs {b.shape}")
+        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3, 4)):
+            raise ValueError(f"calculate_dists: 1, 3 or 4 channels, got {a.shape}")
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._dists_dev(da, db)
+        finally:
+            da.free(); db.free()
+
+    def calculate_dists_device(self, d_img1: int, shape1, d_img2: int, shape2) -> float:
+        """calculate_dists on two dense u8 images that already live in HBM (device addresses + shapes)."""
+        if self.dists_model is None:
+            raise RuntimeError("DISTS needs caller-supplied weights (dists_weights= or SR_DISTS_WEIGHTS); none were given")
+        if not d_img1 or not d_img2:
+            raise ValueError("calculate_dists: null device pointer")
+        ctx = self._ctx()
+        return self._dists_dev(_DevImage(ctx, shape=tuple(shape1), ptr=d_img1), _DevImage(ctx, shape=tuple(shape2), ptr=d_img2))
+
     # -- full-reference evaluation (quality_assessment_module.py:467-609) ------------------------------------
     def evaluate_full_reference(self, original: np.ndarray, upscaled: np.ndarray, scale_factor: int = 4) -> Dict[str, float]:
         o, u = self._pair(original, upscaled, "evaluate_full_reference")
@@ -578,6 +628,8 @@ class QualityAssessmentModule:
                     metrics['lpips_alex'] = float(self._lpips_dev(d_o, d_u, 'alex'))
                 metrics['lpips_level'] = self._assess_lpips(metrics['lpips_vgg'])
             metrics['overall_score'] = self._calculate_overall_score(metrics)
+            if self.dists_model is not None and d_o.shape == d_u.shape:   # only with weights; takes no part in the overall score
+                metrics['dists'] = self._dists_dev(d_o, d_u)
             return metrics
         finally:
             d_o.free(); d_u.free()
