@@ -38,7 +38,7 @@ enum sr_status {
     SR_OK = 0,
     SR_ERR_INVALID_ARG = -1, /* -> ValueError in the Python mirror                    */
     SR_ERR_SHAPE = -2,       /* shape / size mismatch (cv2.error in the reference)    */
-    SR_ERR_OOM = -3,
+    SR_ERR_OOM = -3,         /* a failed device allocation, from every entry point    */
     SR_ERR_HIP = -4,         /* any HIP runtime failure, incl. "no device"            */
     SR_ERR_COMM = -5,
     SR_ERR_UNSUPPORTED = -6

@@ -1374,6 +1374,23 @@ __global__ __launch_bounds__(256) void k_cc_map(const unsigned char *__restrict_
     }
 }
 
+// The fused radius-8 kernels as the host launches them: k[cn - 1] is the instance for cn channels, Tab the element of its table.
+template <typename Tab>
+using FusedKernel = void (*)(const unsigned char *, long long, int, int, const Tab *, float, unsigned char *, long long);
+
+template <typename Tab>
+int launch_fused8(sr_ctx *ctx, const char *name, const FusedKernel<Tab> (&k)[4], size_t lds, const uint8_t *d_img, int64_t stride, int h,
+                  int w, int cn, const Tab *d_tab, float eps, uint8_t *d_out, int64_t out_stride)
+{
+    (void)hipFuncSetAttribute((const void *)k[cn - 1], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    {
+        ProfScope ps(ctx, name);
+        const dim3 grid((w + FG_TW - 1) / FG_TW, (h + FG_TH - 1) / FG_TH);
+        hipLaunchKernelGGL(k[cn - 1], grid, dim3(FG_NT), lds, ctx->stream, d_img, (long long)stride, h, w, d_tab, eps, d_out, (long long)out_stride);
+    }
+    return check_launch(name);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1476,10 +1493,9 @@ int sr_color_correct_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h
             if (whole) {
                 unsigned char *d_glutb = (unsigned char *)scr + tab_bytes;
                 HIPCHK(upload_small(ctx, d_glutb, tabb, sizeof(tabb)));
-                float *ab2 = nullptr;
-                hipError_t e = hipMalloc((void **)&ab2, (size_t)12 * plane * sizeof(float));
-                if (e != hipSuccess)
-                    return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "sr_color_correct_u8: %s", hipGetErrorString(e));
+                DevTemp ab_planes(ctx);
+                SRCHK(ab_planes.alloc("sr_color_correct_u8", (size_t)12 * plane * sizeof(float)));
+                float *ab2 = ab_planes.as<float>();
                 const double sc = 1.0 / ((double)R * (double)R);
                 {
                     ProfScope ps(ctx, "guided_ximgproc");
@@ -1491,23 +1507,16 @@ int sr_color_correct_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h
                                            3 * c, 9 + c, h, w, sc, c, d_out, (long long)out_stride, d_img, (long long)stride,
                                            (const float *)d_glut);
                 }
-                int rcf = check_launch("guided_ximgproc");
-                hipError_t esf = stream_sync(ctx);
-                (void)hipFree(ab2);
-                if (rcf) return rcf;
-                if (esf != hipSuccess) return sr_set_error(SR_ERR_HIP, "sr_color_correct_u8: %s", hipGetErrorString(esf));
+                SRCHK(check_launch("guided_ximgproc"));
+                HIPCHK(stream_sync(ctx));
                 return SR_OK;
             }
         }
-        float *buf = nullptr;
-        {
-            // (the fused second stage of the 3-channel radius-8 case never writes the mean planes of a / b)
-            const int nmab = (cn == 3 && R == GB_R) ? 0 : nab;
-            hipError_t e = hipMalloc((void **)&buf, (size_t)(2 * cn + nmean + nab + nmab) * plane * sizeof(float));
-            if (e != hipSuccess)
-                return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "sr_color_correct_u8: %s", hipGetErrorString(e));
-        }
-        float *planes = buf, *means = planes + 2 * cn * plane, *ab = means + (size_t)nmean * plane, *mab = ab + (size_t)nab * plane;
+        // (the fused second stage of the 3-channel radius-8 case never writes the mean planes of a / b)
+        const int nmab = (cn == 3 && R == GB_R) ? 0 : nab;
+        DevTemp buf(ctx);
+        SRCHK(buf.alloc("sr_color_correct_u8", (size_t)(2 * cn + nmean + nab + nmab) * plane * sizeof(float)));
+        float *planes = buf.as<float>(), *means = planes + 2 * cn * plane, *ab = means + (size_t)nmean * plane, *mab = ab + (size_t)nab * plane;
         const int PH = CC_TH + R - 1, PW = CC_TW + R - 1;
         const size_t lds = ((((size_t)PH * PW * sizeof(float)) + 15) & ~(size_t)15) + (size_t)PH * CC_TW * sizeof(double);
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)k_gf_box, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1550,11 +1559,8 @@ int sr_color_correct_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h
                                    (long long)out_stride);
             }
         }
-        int rc2 = check_launch("guided_ximgproc");
-        hipError_t es2 = stream_sync(ctx);
-        (void)hipFree(buf);
-        if (rc2) return rc2;
-        if (es2 != hipSuccess) return sr_set_error(SR_ERR_HIP, "sr_color_correct_u8: %s", hipGetErrorString(es2));
+        SRCHK(check_launch("guided_ximgproc"));
+        HIPCHK(stream_sync(ctx));
         return SR_OK;
     }
     // (the fused kernel's division leaves out v_div_scale / v_div_fixup, the identity while var + eps stays in [0.006, 65026]:
@@ -1574,55 +1580,19 @@ int sr_color_correct_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h
             unsigned char *d_glutb = (unsigned char *)scr + tab_bytes;
             HIPCHK(upload_small(ctx, d_glutb, tabb, (size_t)cn * 256));
             const size_t lds = (size_t)FG_Y_BYTES + FG_X_BYTES + 1024 + (size_t)FG_IH * ((cn * FG_IW + 3) & ~3);
-            const void *kf = cn == 1 ? (const void *)k_cc_fused8<1> : cn == 2 ? (const void *)k_cc_fused8<2>
-                             : cn == 3 ? (const void *)k_cc_fused8<3> : (const void *)k_cc_fused8<4>;
-            (void)hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            {
-                ProfScope ps(ctx, "guided_fused");
-                const dim3 grid((w + FG_TW - 1) / FG_TW, (h + FG_TH - 1) / FG_TH);
-                const unsigned char *lb = d_glutb;
-#define FG_LAUNCH(N) hipLaunchKernelGGL(k_cc_fused8<N>, grid, dim3(FG_NT), lds, ctx->stream, d_img, (long long)stride, h, w, lb, eps, \
-                                        d_out, (long long)out_stride)
-                switch (cn) {
-                case 1: FG_LAUNCH(1); break;
-                case 2: FG_LAUNCH(2); break;
-                case 3: FG_LAUNCH(3); break;
-                default: FG_LAUNCH(4); break;
-                }
-#undef FG_LAUNCH
-            }
-            return check_launch("guided_fused");
+            static const FusedKernel<unsigned char> k[4] = {k_cc_fused8<1>, k_cc_fused8<2>, k_cc_fused8<3>, k_cc_fused8<4>};
+            return launch_fused8(ctx, "guided_fused", k, lds, d_img, stride, h, w, cn, (const unsigned char *)d_glutb, eps, d_out, out_stride);
         }
         if (cls == 2) {
             const size_t lds = (size_t)FG_Y_BYTES + FG_X_BYTES + (size_t)cn * 1024 + (size_t)FG_IH * ((cn * FG_IW + 3) & ~3);
-            const void *kf = cn == 1 ? (const void *)k_cc_fused8f<1> : cn == 2 ? (const void *)k_cc_fused8f<2>
-                             : cn == 3 ? (const void *)k_cc_fused8f<3> : (const void *)k_cc_fused8f<4>;
-            (void)hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            {
-                ProfScope ps(ctx, "guided_fused_f");
-                const dim3 grid((w + FG_TW - 1) / FG_TW, (h + FG_TH - 1) / FG_TH);
-                const float *lf = d_glut;
-#define FG_LAUNCH(N) hipLaunchKernelGGL(k_cc_fused8f<N>, grid, dim3(FG_NT), lds, ctx->stream, d_img, (long long)stride, h, w, lf, eps, \
-                                        d_out, (long long)out_stride)
-                switch (cn) {
-                case 1: FG_LAUNCH(1); break;
-                case 2: FG_LAUNCH(2); break;
-                case 3: FG_LAUNCH(3); break;
-                default: FG_LAUNCH(4); break;
-                }
-#undef FG_LAUNCH
-            }
-            return check_launch("guided_fused_f");
+            static const FusedKernel<float> k[4] = {k_cc_fused8f<1>, k_cc_fused8f<2>, k_cc_fused8f<3>, k_cc_fused8f<4>};
+            return launch_fused8(ctx, "guided_fused_f", k, lds, d_img, stride, h, w, cn, (const float *)d_glut, eps, d_out, out_stride);
         }
     }
     // a / b planes (8 bytes per sample): an allocation of their own, released when the call is done
-    float *d_a = nullptr;
-    {
-        hipError_t e = hipMalloc((void **)&d_a, 2 * npx * sizeof(float));
-        if (e != hipSuccess)
-            return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "sr_color_correct_u8: %s", hipGetErrorString(e));
-    }
-    float *d_b = d_a + npx;
+    DevTemp ab_planes(ctx);
+    SRCHK(ab_planes.alloc("sr_color_correct_u8", 2 * npx * sizeof(float)));
+    float *d_a = ab_planes.as<float>(), *d_b = d_a + npx;
     const int PH = CC_TH + radius - 1, PW = CC_TW + radius - 1;
     const size_t patch = (((size_t)2 * PH * PW * sizeof(float)) + 15) & ~(size_t)15;
     const size_t lds1 = patch + (size_t)PH * CC_TW * 4 * sizeof(double), lds2 = patch + (size_t)PH * CC_TW * 2 * sizeof(double);
@@ -1655,11 +1625,8 @@ int sr_color_correct_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h
                                radius, scale, (const float *)d_a, (const float *)d_b, d_out, (long long)out_stride);
         }
     }
-    rc = check_launch("color_correct");
-    hipError_t es = stream_sync(ctx);
-    (void)hipFree(d_a);
-    if (rc) return rc;
-    if (es != hipSuccess) return sr_set_error(SR_ERR_HIP, "sr_color_correct_u8: %s", hipGetErrorString(es));
+    SRCHK(check_launch("color_correct"));
+    HIPCHK(stream_sync(ctx));
     return SR_OK;
 }
 

@@ -1193,6 +1193,19 @@ const double *reduce_partials(sr_ctx *ctx, const double *part, long long n, int 
     }
 }
 
+// The blocking form of an assessment: run(d_res) enqueues it into a one-call result word, which is then copied to *h_out.
+// The caller holds the context's Guard.
+template <typename Run>
+static int assess_to_host(sr_ctx *ctx, const char *who, sr_assess_sums *h_out, Run &&run)
+{
+    DevTemp res(ctx);
+    SRCHK(res.alloc(who, sizeof(sr_assess_sums)));
+    SRCHK(run(res.as<sr_assess_sums>()));
+    HIPCHK(hipMemcpyAsync(h_out, res.d, sizeof(sr_assess_sums), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(stream_sync(ctx));
+    return SR_OK;
+}
+
 extern "C" {
 
 // ---- metrics ------------------------------------------------------------------------------------------
@@ -1377,8 +1390,8 @@ int sr_assess_resized_u8_async(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a
     cubic_table(w, dst_w, xt);
     cubic_table(h, dst_h, yt);
     xt.insert(xt.end(), yt.begin(), yt.end());
-    HIPCHK(upload_cached(ctx, ctx->resize_tab, xt.data(), sizeof(CubicTab) * xt.size()));
-    const CubicTab *d_xt = (const CubicTab *)ctx->resize_tab.d, *d_yt = d_xt + dst_w;
+    SRCHK(upload_cached(ctx, ctx->resize_tab, xt.data(), sizeof(CubicTab) * xt.size()));
+    const CubicTab *d_xt = ctx->resize_tab.buf.as<const CubicTab>(), *d_yt = d_xt + dst_w;
     const int64_t pitch = ((int64_t)dst_w + 63) / 64 * 64;
     // down-sampling RGB: the LDS-staged kernel when its source window (64 destination columns wide) fits
     int lds_pitch = 0, march_cols = 0, march_pitch = 0;
@@ -1407,18 +1420,9 @@ int sr_assess_resized_u8_async(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a
                                  march ? (unsigned)((dst_h + 4 * RGM_SEG - 1) / (4 * RGM_SEG)) : (unsigned)((dst_h + 3) / 4));
     const size_t nblk = (size_t)grid.x * grid.y, plane = (size_t)pitch * dst_h;
     const size_t off_part = (2 * plane + 255) / 256 * 256, need = off_part + (nblk + 2 * (nblk / 1024 + 2)) * sizeof(double);
-    if (need > ctx->gray_planes_bytes) {
-        if (ctx->gray_planes) {
-            HIPCHK(stream_sync(ctx));
-            HIPCHK(hipFree(ctx->gray_planes));
-            ctx->gray_planes = nullptr;
-            ctx->gray_planes_bytes = 0;
-        }
-        HIPCHK(hipMalloc(&ctx->gray_planes, need));
-        ctx->gray_planes_bytes = need;
-    }
-    uint8_t *ga = (uint8_t *)ctx->gray_planes, *gb = ga + plane;
-    double *part = (double *)((char *)ctx->gray_planes + off_part), *buf0 = part + nblk, *buf1 = buf0 + nblk / 1024 + 2;
+    SRCHK(ctx->gray_planes.reserve(ctx, "sr_assess_resized_u8", need));
+    uint8_t *ga = ctx->gray_planes.as<uint8_t>(), *gb = ga + plane;
+    double *part = ctx->gray_planes.as<double>(off_part), *buf0 = part + nblk, *buf1 = buf0 + nblk / 1024 + 2;
     const bool want_sse = (flags & ASSESS_SSE) != 0;
     const double *sse_ptr = nullptr;
     {
@@ -1461,17 +1465,9 @@ int sr_assess_resized_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, cons
 {
     CTX_ENTER(ctx);
     if (!h_out) return sr_set_error(SR_ERR_INVALID_ARG, "sr_assess_resized_u8: null result");
-    void *res = nullptr;
-    HIPCHK(hipMalloc(&res, sizeof(sr_assess_sums)));
-    int rc = sr_assess_resized_u8_async(ctx, d_a, stride_a, d_b, stride_b, h, w, cn, dst_h, dst_w, gray_shift,
-                                        data_range, flags, (sr_assess_sums *)res);
-    if (rc == SR_OK) {
-        hipError_t e = hipMemcpyAsync(h_out, res, sizeof(sr_assess_sums), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = stream_sync(ctx);
-        if (e != hipSuccess) rc = sr_set_error(SR_ERR_HIP, "sr_assess_resized_u8: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(res);
-    return rc;
+    return assess_to_host(ctx, "sr_assess_resized_u8", h_out, [&](sr_assess_sums *d_res) {
+        return sr_assess_resized_u8_async(ctx, d_a, stride_a, d_b, stride_b, h, w, cn, dst_h, dst_w, gray_shift, data_range, flags, d_res);
+    });
 }
 
 int sr_assess_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
@@ -1479,18 +1475,9 @@ int sr_assess_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_
 {
     CTX_ENTER(ctx);
     if (!h_out) return sr_set_error(SR_ERR_INVALID_ARG, "sr_assess_u8: null result");
-    void *res = nullptr;
-    HIPCHK(hipMalloc(&res, sizeof(sr_assess_sums)));
-    int rc = sr_assess_u8_async(ctx, d_a, stride_a, d_b, stride_b, h, w, cn, gray_shift, data_range, row_begin, row_end,
-                                flags, (sr_assess_sums *)res);
-    if (rc == SR_OK) {
-        hipError_t e = hipMemcpyAsync(h_out, res, sizeof(sr_assess_sums), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = stream_sync(ctx);
-        if (e != hipSuccess) rc = sr_set_error(SR_ERR_HIP, "sr_assess_u8: D2H: %s", hipGetErrorString(e));
-    }
-    (void)stream_sync(ctx);
-    (void)hipFree(res);
-    return rc;
+    return assess_to_host(ctx, "sr_assess_u8", h_out, [&](sr_assess_sums *d_res) {
+        return sr_assess_u8_async(ctx, d_a, stride_a, d_b, stride_b, h, w, cn, gray_shift, data_range, row_begin, row_end, flags, d_res);
+    });
 }
 
 static int ssim_mode_check(int h, int w, int mode, int *flag, size_t *field_off)
@@ -1521,10 +1508,10 @@ int sr_ssim_u8_async(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const ui
     rc = ctx_scratch(ctx, (size_t)8 << 20, &scr);
     if (rc) return rc;
     // the result record lives in the last 256 bytes of the (>= 8 MiB) scratch, clear of the partial buffers
-    sr_assess_sums *rec = (sr_assess_sums *)((char *)ctx->scratch + ctx->scratch_bytes - 256);
+    sr_assess_sums *rec = ctx->scratch.as<sr_assess_sums>(ctx->scratch.cap - 256);
     rc = sr_assess_u8_async(ctx, d_a, stride_a, d_b, stride_b, h, w, cn, gray_shift, data_range, row_begin, row_end, flag, rec);
     if (rc) return rc;
-    rec = (sr_assess_sums *)((char *)ctx->scratch + ctx->scratch_bytes - 256);    // scratch may have grown
+    rec = ctx->scratch.as<sr_assess_sums>(ctx->scratch.cap - 256);    // scratch may have grown
     HIPCHK(hipMemcpyAsync(d_sum, (const char *)rec + off, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     return SR_OK;
 }
@@ -1586,11 +1573,9 @@ int sr_ssim_float(sr_ctx *ctx, int dtype, const void *d_a, int64_t stride_a, con
     const size_t plane = (size_t)h * w;
     const dim3 block(64, 4), grid((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4));
     const size_t nblk = (size_t)grid.x * grid.y;
-    double *buf = nullptr;
-    {
-        hipError_t e = hipMalloc((void **)&buf, (7 * plane + nblk + 2 * (nblk / 1024 + 2)) * sizeof(double));
-        if (e != hipSuccess) return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "sr_ssim_float: %s", hipGetErrorString(e));
-    }
+    DevTemp tmp_planes(ctx);
+    SRCHK(tmp_planes.alloc("sr_ssim_float", (7 * plane + nblk + 2 * (nblk / 1024 + 2)) * sizeof(double)));
+    double *buf = tmp_planes.as<double>();
     double *ga = buf, *gb = buf + plane, *tmp = buf + 2 * plane, *part = buf + 7 * plane, *b0 = part + nblk, *b1 = b0 + nblk / 1024 + 2;
     {
         ProfScope ps(ctx, "ssim_float");
@@ -1605,12 +1590,9 @@ int sr_ssim_float(sr_ctx *ctx, int dtype, const void *d_a, int64_t stride_a, con
         hipLaunchKernelGGL(k_ssimf_cols, grid, block, 0, ctx->stream, (const double *)tmp, P, part);
     }
     const double *res = reduce_partials(ctx, part, (long long)nblk, 1, b0, b1);
-    rc = check_launch("ssim_float");
-    hipError_t e = hipMemcpyAsync(h_sum, res, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t es2 = stream_sync(ctx);
-    (void)hipFree(buf);
-    if (rc) return rc;
-    if (e != hipSuccess || es2 != hipSuccess) return sr_set_error(SR_ERR_HIP, "sr_ssim_float: %s", hipGetErrorString(e != hipSuccess ? e : es2));
+    SRCHK(check_launch("ssim_float"));
+    HIPCHK(hipMemcpyAsync(h_sum, res, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(stream_sync(ctx));
     return SR_OK;
 }
 
@@ -1641,8 +1623,8 @@ int sr_resize_cubic_window_u8(sr_ctx *ctx, const uint8_t *d_src, int64_t src_str
     cubic_table(w, dw, xt);
     cubic_table(h, dh, yt);
     xt.insert(xt.end(), yt.begin(), yt.end());          // both axes in one cached device table (re-used per geometry)
-    HIPCHK(upload_cached(ctx, ctx->cubic_tab, xt.data(), sizeof(CubicTab) * xt.size()));
-    CubicTab *dx = (CubicTab *)ctx->cubic_tab.d, *dy = dx + dw;
+    SRCHK(upload_cached(ctx, ctx->cubic_tab, xt.data(), sizeof(CubicTab) * xt.size()));
+    CubicTab *dx = ctx->cubic_tab.buf.as<CubicTab>(), *dy = dx + dw;
     {
         ProfScope ps(ctx, "resize_cubic");
         dim3 grid((ww + 63) / 64, (wh + 3) / 4), block(64, 4);

@@ -740,21 +740,10 @@ Gauss7 gauss7()
 
 int cm_workspace(sr_ctx *ctx, size_t bytes, char **out)
 {
-    if (bytes > ctx->cm_ws_bytes) {
-        if (ctx->cm_ws) {
-            HIPCHK(stream_sync(ctx));
-            HIPCHK(hipFree(ctx->cm_ws));
-            ctx->cm_ws = nullptr;
-            ctx->cm_ws_bytes = 0;
-        }
-        HIPCHK(hipMalloc(&ctx->cm_ws, bytes));
-        ctx->cm_ws_bytes = bytes;
-    }
-    *out = (char *)ctx->cm_ws;
+    SRCHK(ctx->cm_ws.reserve(ctx, "commercial / FFT workspace", bytes));
+    *out = ctx->cm_ws.as<char>();
     return SR_OK;
 }
-
-size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -774,11 +763,10 @@ int sr_fft_c2c(sr_ctx *ctx, const void *d_in, void *d_out, int64_t lines, int n)
     CTX_ENTER(ctx);
     if (!d_in || !d_out || lines < 1 || n < 1) return sr_set_error(SR_ERR_INVALID_ARG, "sr_fft_c2c: bad arguments");
     if (n > CM_MAX_LEN) return sr_set_error(SR_ERR_UNSUPPORTED, "sr_fft_c2c: length %d above %d", n, CM_MAX_LEN);
-    const size_t xb = al256((size_t)lines * n * 8), wb = al256((size_t)lines * fft_work_len(n) * 8),
-                 tb = al256(fft_tab_elems(n) * 8);
+    const size_t xb = up256((size_t)lines * n * 8), wb = up256((size_t)lines * fft_work_len(n) * 8),
+                 tb = up256(fft_tab_elems(n) * 8);
     char *ws = nullptr;
-    int rc = cm_workspace(ctx, xb + 2 * wb + tb, &ws);
-    if (rc) return rc;
+    SRCHK(cm_workspace(ctx, xb + 2 * wb + tb, &ws));
     float2 *X = (float2 *)ws, *P = (float2 *)(ws + xb), *Q = (float2 *)(ws + xb + wb), *T = (float2 *)(ws + xb + 2 * wb);
     HIPCHK(hipMemcpyAsync(X, d_in, (size_t)lines * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
     float2 *r;
@@ -786,8 +774,7 @@ int sr_fft_c2c(sr_ctx *ctx, const void *d_in, void *d_out, int64_t lines, int n)
         ProfScope ps(ctx, "cm_fft");
         r = fft_lines(ctx, X, P, Q, T, lines, n);
     }
-    rc = check_launch("fft_c2c");
-    if (rc) return rc;
+    SRCHK(check_launch("fft_c2c"));
     HIPCHK(hipMemcpyAsync(d_out, r, (size_t)lines * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(stream_sync(ctx));
     return SR_OK;
@@ -830,11 +817,11 @@ int sr_commercial_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, i
         fft_buf = std::max((size_t)lines_r * fft_work_len(w), (size_t)Wh * fft_work_len(h));
         fft_tab = std::max(fft_tab_elems(w), fft_tab_elems(h));
     }
-    const size_t b_ints = al256((size_t)nr * NI * 8), b_part = al256((size_t)nr * CM_NBLK * NF * 8),
-                 b_rect = al256(sizeof(CmRect) * nr), b_lab = al256((256 + 3072) * 4), b_hf = al256((size_t)CM_NBLK * 2 * 8),
-                 b_flag = 256, b_gray = colour ? al256((size_t)npx) : 0,
-                 b_mag = (flags & CMF_CANNY) ? al256((size_t)npx * 2) : 0, b_st = (flags & CMF_CANNY) ? al256((size_t)npx) : 0,
-                 b_fft = al256(fft_buf * 8), b_tab = al256(fft_tab * 8);
+    const size_t b_ints = up256((size_t)nr * NI * 8), b_part = up256((size_t)nr * CM_NBLK * NF * 8),
+                 b_rect = up256(sizeof(CmRect) * nr), b_lab = up256((256 + 3072) * 4), b_hf = up256((size_t)CM_NBLK * 2 * 8),
+                 b_flag = 256, b_gray = colour ? up256((size_t)npx) : 0,
+                 b_mag = (flags & CMF_CANNY) ? up256((size_t)npx * 2) : 0, b_st = (flags & CMF_CANNY) ? up256((size_t)npx) : 0,
+                 b_fft = up256(fft_buf * 8), b_tab = up256(fft_tab * 8);
     char *ws = nullptr;
     int rc = cm_workspace(ctx, b_ints + b_part + b_rect + b_lab + b_hf + b_flag + b_gray + b_mag + b_st + 3 * b_fft + b_tab, &ws);
     if (rc) return rc;

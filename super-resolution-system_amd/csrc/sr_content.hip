@@ -296,8 +296,6 @@ unsigned grid1(long long n, int per = 256, long long cap = 1 << 16)
     return (unsigned)std::max(1LL, std::min((n + per - 1) / per, cap));
 }
 
-size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-
 bool bad_image(const void *d_img, int64_t stride, int h, int w, int cn)
 {
     return !d_img || h < 1 || w < 1 || (cn != 1 && cn != 3 && cn != 4) || stride < (int64_t)w * cn;
@@ -326,8 +324,8 @@ int sr_saliency_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int
         return sr_set_error(SR_ERR_UNSUPPORTED, "sr_saliency_u8: DFT side above %d", sr_fft_max_len());
     const long long npx = (long long)h * w;
     const size_t buf = std::max((size_t)h * sr_fft_work_len(w), (size_t)w * sr_fft_work_len(h));
-    const size_t b_fft = al256(buf * 8), b_tab = al256(std::max(sr_fft_tab_elems(w), sr_fft_tab_elems(h)) * 8),
-                 b_part = al256((size_t)CT_NBLK * 2 * 4 + 2 * 4);
+    const size_t b_fft = up256(buf * 8), b_tab = up256(std::max(sr_fft_tab_elems(w), sr_fft_tab_elems(h)) * 8),
+                 b_part = up256((size_t)CT_NBLK * 2 * 4 + 2 * 4);
     char *ws = nullptr;
     int rc = sr_fft_workspace(ctx, 3 * b_fft + b_tab + b_part, &ws);
     if (rc) return rc;
@@ -435,7 +433,7 @@ int sr_rect_counts_u8(sr_ctx *ctx, const uint8_t *d_map, int64_t stride, int h, 
         if (h_rects[i].w < 0 || h_rects[i].h < 0) return sr_set_error(SR_ERR_INVALID_ARG, "sr_rect_counts_u8: rectangle %d has a negative size", i);
     if (n == 0) return SR_OK;
     const std::vector<CtRect> rects = clip_rects(h_rects, n, h, w, true);
-    const size_t b_cnt = al256((size_t)n * 8), b_tab = (size_t)n * sizeof(CtRect);
+    const size_t b_cnt = up256((size_t)n * 8), b_tab = (size_t)n * sizeof(CtRect);
     void *d_s = nullptr;
     int rc = ctx_scratch(ctx, b_cnt + b_tab, &d_s);
     if (rc) return rc;

@@ -205,13 +205,13 @@ inline MfmaWeights arrange_mfma_weights(const float *w, const float *b, int cout
     return m;
 }
 
-// Device copy of v, appended to dst (so a failed create frees it with the rest); SR_OK, SR_ERR_OOM or SR_ERR_HIP.
-inline int upload_floats(const std::vector<float> &v, std::vector<float *> &dst)
+// Device copy of n floats, appended to dst (so a failed create releases it with the rest); on failure the error is set.
+inline int upload_floats(sr_ctx *ctx, const char *who, const float *src, size_t n, std::vector<DevBuf> &dst)
 {
-    float *d = nullptr;
-    if (hipMalloc((void **)&d, v.size() * sizeof(float)) != hipSuccess) return SR_ERR_OOM;
-    dst.push_back(d);
-    return hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? SR_OK : SR_ERR_HIP;
+    dst.emplace_back();
+    SRCHK(dst.back().reserve(ctx, who, n * sizeof(float)));
+    HIPCHK(hipMemcpy(dst.back().d, src, n * sizeof(float), hipMemcpyHostToDevice));
+    return SR_OK;
 }
 
 // The models of one kind that exist: a handle is checked against it before it is dereferenced.
@@ -237,23 +237,14 @@ public:
     }
 };
 
-// Grow a model's n activation buffers to need_floats each (never shrinks): sync, free all, allocate all.
-inline int ensure_activation_buffers(sr_ctx *ctx, float **bufs, int n, size_t &buf_floats, size_t need_floats, const char *who)
+// Grow a model's n activation buffers to need_floats each (never shrinks): sync, free all, allocate all.  The n grow together
+// and the last is allocated last, so its capacity tells whether all of them are large enough.
+inline int ensure_activation_buffers(sr_ctx *ctx, DevBuf *bufs, int n, size_t need_floats, const char *who)
 {
-    if (need_floats <= buf_floats) return SR_OK;
+    if (need_floats * sizeof(float) <= bufs[n - 1].cap) return SR_OK;
     HIPCHK(stream_sync(ctx));
-    for (int i = 0; i < n; ++i) {
-        if (bufs[i]) (void)hipFree(bufs[i]);
-        bufs[i] = nullptr;
-    }
-    buf_floats = 0;
-    for (int i = 0; i < n; ++i) {
-        hipError_t e = hipMalloc((void **)&bufs[i], need_floats * sizeof(float));
-        if (e != hipSuccess)
-            return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "%s: activation buffers (%d x %zu MB; use a smaller tile): %s",
-                                who, n, need_floats * 4 >> 20, hipGetErrorString(e));
-    }
-    buf_floats = need_floats;
+    for (int i = 0; i < n; ++i) bufs[i].release();
+    for (int i = 0; i < n; ++i) SRCHK(bufs[i].reserve(ctx, who, need_floats * sizeof(float)));
     return SR_OK;
 }
 

@@ -1,7 +1,7 @@
 // sr_ctx.h -- the device context shared by the .hip translation units of libsrhip.so (sr_runtime.hip owns the
 // definitions, except plan_describe and destroy_plans_of: sr_engine.hip, and reduce_partials: sr_assess.hip; every
-// other .hip file and sr_comm.cpp use them, the convolution networks through sr_conv_mfma.h, the SSIM column march and its
-// workspace growth through sr_ssim11.h).
+// other .hip file and sr_comm.cpp use them, the convolution networks through sr_conv_mfma.h, the SSIM column march through
+// sr_ssim11.h).  Device memory is owned here: DevBuf (grow-only, released by its owner) and DevTemp (one call).
 // Internal: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,6 +12,12 @@
 
 #include "sr_internal.h"
 
+#define SRCHK(expr)                                                                                \
+    do {                                                                                           \
+        const int rc_ = (expr);                                                                    \
+        if (rc_ != SR_OK) return rc_;                                                              \
+    } while (0)
+
 #define HIPCHK(expr)                                                                               \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
@@ -19,6 +25,43 @@
             return sr_set_error(SR_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
                                 __LINE__);                                                         \
     } while (0)
+
+struct sr_ctx;
+
+// The error of a failed device allocation: SR_ERR_OOM when the device is out of memory, SR_ERR_HIP otherwise.
+int dev_alloc_error(const char *who, const char *what, size_t bytes, hipError_t e);
+
+// An owned device buffer that only grows.  It has no destructor: its owner calls release() with the stream drained and the
+// buffer's device current (sr_ctx_destroy and the model destroys do, under their Guard).
+struct DevBuf {
+    void *d = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : d(o.d), cap(o.cap) { o.d = nullptr; o.cap = 0; }
+    // bytes <= cap: nothing.  Otherwise the stream is drained, the old buffer freed (its contents are lost) and
+    // max(bytes, floor) rounded up to a multiple of page allocated; *regrown tells.  On failure d == nullptr, cap == 0.
+    int reserve(sr_ctx *c, const char *who, size_t bytes, size_t floor = 0, size_t page = 1, bool *regrown = nullptr);
+    void release();
+    template <class T>
+    T *as(size_t byte_off = 0) const { return (T *)((char *)d + byte_off); }
+};
+
+// A device temporary of one call.  Declared after CTX_ENTER, so it goes before the Guard does: every return path drains the
+// context's stream and frees it, with the context's device current.
+struct DevTemp {
+    sr_ctx *c;
+    void *d = nullptr;
+    explicit DevTemp(sr_ctx *ctx) : c(ctx) {}
+    DevTemp(const DevTemp &) = delete;
+    DevTemp &operator=(const DevTemp &) = delete;
+    DevTemp(DevTemp &&o) noexcept : c(o.c), d(o.d) { o.d = nullptr; }
+    ~DevTemp();
+    int alloc(const char *who, size_t bytes);
+    template <class T>
+    T *as(size_t byte_off = 0) const { return (T *)((char *)d + byte_off); }
+};
 
 struct ProfPair {
     int name_id;
@@ -29,8 +72,7 @@ struct ProfPair {
 // pointers, strides, rectangles) rarely change between calls, and a host->device copy between two kernels costs a
 // stream bubble of several microseconds -- identical content is not uploaded again.
 struct CachedTable {
-    void *d = nullptr;
-    size_t cap = 0;
+    DevBuf buf;
     std::vector<char> shadow;
 };
 
@@ -46,26 +88,26 @@ struct sr_ctx {
     std::vector<ProfPair> prof_pairs;
     std::vector<hipEvent_t> ev_pool;
     // small reusable device scratch (resize tables, reduction partials, result words)
-    void *scratch = nullptr;
-    size_t scratch_bytes = 0;
+    DevBuf scratch;
     // host copies of small tables handed to hipMemcpyAsync; released at the next stream sync
     std::vector<std::vector<char>> pending_host;
     size_t pending_bytes = 0;
     CachedTable extract_tab;                            // tile-extract descriptors
     CachedTable resize_tab;                             // cubic tables of the resized assessment
     CachedTable cubic_tab;                              // cubic tables of sr_resize_cubic_u8
-    void *gray_planes = nullptr;                        // resized gray planes + SSE partials of the resized assessment
-    size_t gray_planes_bytes = 0;
-    void *cm_ws = nullptr;                              // commercial / no-reference metrics: planes, FFT buffers, partials
-    size_t cm_ws_bytes = 0;
-    void *msssim_ws = nullptr;                          // MS-SSIM: level planes (x | y << 16 sums), partials, per-level results
-    size_t msssim_ws_bytes = 0;
+    DevBuf gray_planes;                                 // resized gray planes + SSE partials of the resized assessment
+    DevBuf cm_ws;                                       // commercial / no-reference metrics: planes, FFT buffers, partials
+    DevBuf msssim_ws;                                   // MS-SSIM: level planes (x | y << 16 sums), partials, per-level results
     int msssim_h = 0, msssim_w = 0, msssim_levels = 0;  // what the planes hold (levels == 0: nothing valid)
-    void *bench_ws = nullptr;                           // SR-benchmark PSNR / SSIM: per-block partials
-    size_t bench_ws_bytes = 0;
-    void *niqe_ws = nullptr;                            // NIQE: the int32 half plane, then the block records
-    size_t niqe_ws_bytes = 0;
+    DevBuf bench_ws;                                    // SR-benchmark PSNR / SSIM: per-block partials
+    DevBuf niqe_ws;                                     // NIQE: the int32 half plane, then the block records
     int niqe_H = 0, niqe_W = 0;                         // the kept plane whose half plane the scratch holds (0: nothing valid)
+    // Frees every device buffer above; sr_ctx_destroy calls it with the stream drained and the device current.
+    void release_device()
+    {
+        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws})
+            b->release();
+    }
 };
 
 // Enqueue a small host->device table upload whose source stays alive until the next sync.
@@ -73,8 +115,8 @@ hipError_t upload_small(sr_ctx *c, void *d_dst, const void *h_src, size_t bytes)
 hipError_t stream_sync(sr_ctx *c);
 // Upload into a fixed destination unless `shadow` shows the same bytes are already there.
 hipError_t upload_if_changed(sr_ctx *c, void *d_dst, const void *h_src, size_t bytes, std::vector<char> &shadow);
-// Same with a table that owns (and grows) its device buffer.
-hipError_t upload_cached(sr_ctx *c, CachedTable &t, const void *h_src, size_t bytes);
+// Same with a table that owns (and grows, in 4 KiB pages) its device buffer; an SR_* code.
+int upload_cached(sr_ctx *c, CachedTable &t, const void *h_src, size_t bytes);
 bool ctx_is_live(const sr_ctx *c);
 // What a blend plan was made for (sr_comm.cpp cross-checks the arguments of the sharded blend); false when the plan is
 // null or destroyed.

@@ -135,13 +135,20 @@ __global__ __launch_bounds__(256) void k_ds_stats_u8(const unsigned char *__rest
 struct sr_dists_model {
     sr_ctx *ctx = nullptr;
     std::vector<LpLayer> layers;
-    std::vector<float *> d_w, d_b;    // per convolution: weights in the kernel's layout, bias
+    std::vector<DevBuf> d_w, d_b;     // per convolution: weights in the kernel's layout, bias
     float mean[3], stdv[3];
-    float *buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [image][ping-pong] activation buffers
-    size_t buf_floats = 0;
-    double *d_acc = nullptr;          // 1475 x 5 sums
-    double *d_part = nullptr;         // per-block partials of one stats launch
-    size_t part_cap = 0;
+    DevBuf buf[2][2];                 // [image][ping-pong] activation buffers
+    DevBuf d_acc;                     // 1475 x 5 sums
+    DevBuf d_part;                    // per-block partials of one stats launch
+    void release_device()
+    {
+        for (auto *v : {&d_w, &d_b})
+            for (auto &p : *v) p.release();
+        for (auto &im : buf)
+            for (auto &p : im) p.release();
+        d_acc.release();
+        d_part.release();
+    }
 };
 
 static LiveSet g_ds_live;
@@ -198,10 +205,9 @@ int sr_dists_create(sr_ctx *ctx, const float *const *h_conv_w, const float *cons
         M->stdv[c] = h_std ? h_std[c] : def_std[c];
     }
     g_ds_live.insert(M);
-    auto fail = [&](int code, const char *what) {
-        sr_set_error(code, "sr_dists_create: %s", what);
+    auto drop = [&](int rc) {                               // the error is set
         sr_dists_destroy(M);
-        return code;
+        return rc;
     };
     for (auto &l : M->layers) {
         if (l.kind != LP_CONV) continue;
@@ -215,12 +221,12 @@ int sr_dists_create(sr_ctx *ctx, const float *const *h_conv_w, const float *cons
         } else {                                            // MFMA: [cout tile][chunk][c in chunk][tap][64]
             arranged = arrange_mfma_weights(w, b, l.cout, l.cin, 9, 8, 64).w;     // cout % 64 == 0: the bias needs no padding
         }
-        int rc = upload_floats(arranged, M->d_w);
-        if (rc) return fail(rc, "weights");
-        rc = upload_floats(std::vector<float>(b, b + l.cout), M->d_b);
-        if (rc) return fail(rc, "bias");
+        int rc;
+        if ((rc = upload_floats(ctx, "sr_dists_create: weights", arranged.data(), arranged.size(), M->d_w)) ||
+            (rc = upload_floats(ctx, "sr_dists_create: bias", b, (size_t)l.cout, M->d_b)))
+            return drop(rc);
     }
-    if (hipMalloc((void **)&M->d_acc, (size_t)DS_TOTAL * 5 * sizeof(double)) != hipSuccess) return fail(SR_ERR_OOM, "accumulators");
+    if (int rc = M->d_acc.reserve(ctx, "sr_dists_create: accumulators", (size_t)DS_TOTAL * 5 * sizeof(double))) return drop(rc);
     *out = M;
     return SR_OK;
 }
@@ -232,11 +238,7 @@ int sr_dists_destroy(sr_dists_model *m)
     if (ctx_is_live(m->ctx)) {
         Guard g(m->ctx);
         (void)hipStreamSynchronize(m->ctx->stream);
-        for (auto p : m->d_w) if (p) (void)hipFree(p);
-        for (auto p : m->d_b) if (p) (void)hipFree(p);
-        for (auto &im : m->buf) for (auto p : im) if (p) (void)hipFree(p);
-        if (m->d_acc) (void)hipFree(m->d_acc);
-        if (m->d_part) (void)hipFree(m->d_part);
+        m->release_device();
     }
     delete m;
     return SR_OK;
@@ -271,7 +273,7 @@ int sr_dists_u8(sr_dists_model *m, const uint8_t *d_a, int64_t stride_a, const u
     ntiles = tiles_x * tiles_y;
     if (tile_end < 0 || tile_end > ntiles) tile_end = ntiles;
     tile_begin = std::max(tile_begin, 0);
-    HIPCHK(hipMemsetAsync(m->d_acc, 0, (size_t)DS_TOTAL * 5 * sizeof(double), ctx->stream));
+    HIPCHK(hipMemsetAsync(m->d_acc.d, 0, (size_t)DS_TOTAL * 5 * sizeof(double), ctx->stream));
     const std::vector<LpLayer> &L = m->layers;
     const int na = (int)G.H.size();
     const dim3 blk(64, 4);
@@ -293,7 +295,7 @@ int sr_dists_u8(sr_dists_model *m, const uint8_t *d_a, int64_t stride_a, const u
             // + 8 rows and 32 columns: the unguarded convolution stages whole 8 x 32 blocks of what lies inside the image
             need_floats = std::max(need_floats, (size_t)plane[j] * G.C[j] + (size_t)8 * pitch[j] + 32);
         }
-        rc = ensure_activation_buffers(ctx, &m->buf[0][0], 4, m->buf_floats, need_floats, "sr_dists_u8");
+        rc = ensure_activation_buffers(ctx, &m->buf[0][0], 4, need_floats, "sr_dists_u8");
         if (rc) return rc;
         int cur = 0;                       // ping-pong index of the current activation (both images in step)
         for (size_t li = 0; li < L.size(); ++li) {
@@ -305,23 +307,16 @@ int sr_dists_u8(sr_dists_model *m, const uint8_t *d_a, int64_t stride_a, const u
                 const int C = DS_CH[l.tap];
                 const dim3 grid((rx.n() + 63) / 64, (ry.n() + DS_BR - 1) / DS_BR, C);
                 const size_t nblk = (size_t)grid.x * grid.y, npart = nblk * C * 5;
-                if (npart > m->part_cap) {
-                    HIPCHK(stream_sync(ctx));
-                    if (m->d_part) (void)hipFree(m->d_part);
-                    m->d_part = nullptr;
-                    m->part_cap = 0;
-                    HIPCHK(hipMalloc((void **)&m->d_part, npart * sizeof(double)));
-                    m->part_cap = npart;
-                }
+                SRCHK(m->d_part.reserve(ctx, "sr_dists_u8", npart * sizeof(double)));
                 ProfScope ps(ctx, "dists_stats");
                 if (ai == 0)
                     hipLaunchKernelGGL(k_ds_stats_u8, grid, blk, 0, ctx->stream, d_a, (long long)stride_a, d_b, (long long)stride_b, cn,
-                                       ry.a, rx.a, ry.n(), rx.n(), m->d_part);
+                                       ry.a, rx.a, ry.n(), rx.n(), m->d_part.as<double>());
                 else
-                    hipLaunchKernelGGL(k_ds_stats, grid, blk, 0, ctx->stream, m->buf[0][cur], m->buf[1][cur], plane[ai], pitch[ai],
-                                       ry.a - ny[ai].a, rx.a - nx[ai].a, ry.n(), rx.n(), m->d_part);
-                hipLaunchKernelGGL(k_lp_accum, dim3(C * 5), dim3(256), 0, ctx->stream, m->d_part, (long long)nblk,
-                                   m->d_acc + (size_t)ch0[l.tap] * 5);
+                    hipLaunchKernelGGL(k_ds_stats, grid, blk, 0, ctx->stream, m->buf[0][cur].as<float>(), m->buf[1][cur].as<float>(), plane[ai], pitch[ai],
+                                       ry.a - ny[ai].a, rx.a - nx[ai].a, ry.n(), rx.n(), m->d_part.as<double>());
+                hipLaunchKernelGGL(k_lp_accum, dim3(C * 5), dim3(256), 0, ctx->stream, m->d_part.as<double>(), (long long)nblk,
+                                   m->d_acc.as<double>() + (size_t)ch0[l.tap] * 5);
                 continue;
             }
             const int ao = ai + 1;
@@ -329,8 +324,8 @@ int sr_dists_u8(sr_dists_model *m, const uint8_t *d_a, int64_t stride_a, const u
             if (rows <= 0 || cols <= 0) { cur ^= (ai > 0); continue; }
             const int nxt = ai == 0 ? 0 : cur ^ 1;
             for (int im = 0; im < 2; ++im) {
-                const float *src = ai == 0 ? nullptr : m->buf[im][cur];
-                float *dst = m->buf[im][nxt];
+                const float *src = ai == 0 ? nullptr : m->buf[im][cur].as<float>();
+                float *dst = m->buf[im][nxt].as<float>();
                 if (l.kind == LP_L2POOL) {
                     ProfScope ps(ctx, "dists_l2pool");
                     ds_launch_l2pool(ctx->stream, src, plane[ai], pitch[ai], ny[ai].a, nx[ai].a, G.H[ai], G.W[ai], dst, plane[ao],
@@ -340,13 +335,13 @@ int sr_dists_u8(sr_dists_model *m, const uint8_t *d_a, int64_t stride_a, const u
                     const uint8_t *img = im == 0 ? d_a : d_b;
                     const long long st = im == 0 ? stride_a : stride_b;
                     const dim3 grid((cols + 63) / 64, (rows + 3) / 4);
-                    hipLaunchKernelGGL((k_lp_conv_stem<3, 1, 1, DistsTable>), grid, blk, 0, ctx->stream, img, st, cn, h, w, m->d_w[l.widx],
-                                       m->d_b[l.widx], tab, dst, ny[ao].a, nx[ao].a, rows, cols, pitch[ao], plane[ao]);
+                    hipLaunchKernelGGL((k_lp_conv_stem<3, 1, 1, DistsTable>), grid, blk, 0, ctx->stream, img, st, cn, h, w, m->d_w[l.widx].as<const float>(),
+                                       m->d_b[l.widx].as<const float>(), tab, dst, ny[ao].a, nx[ao].a, rows, cols, pitch[ao], plane[ao]);
                 } else {
                     ProfScope ps(ctx, "dists_conv_mfma");
                     const dim3 grid((cols + 31) / 32, (rows + 7) / 8, l.cout / 64);
                     hipLaunchKernelGGL((k_lp_conv_mfma<3, 8>), grid, dim3(256), 0, ctx->stream, src, plane[ai], pitch[ai], ny[ai].a,
-                                       nx[ai].a, G.H[ai], G.W[ai], l.cin, m->d_w[l.widx], m->d_b[l.widx], dst, plane[ao], pitch[ao],
+                                       nx[ai].a, G.H[ai], G.W[ai], l.cin, m->d_w[l.widx].as<const float>(), m->d_b[l.widx].as<const float>(), dst, plane[ao], pitch[ao],
                                        ny[ao].a, nx[ao].a, rows, cols);
                 }
             }
@@ -355,7 +350,7 @@ int sr_dists_u8(sr_dists_model *m, const uint8_t *d_a, int64_t stride_a, const u
         rc = check_launch("dists");
         if (rc) return rc;
     }
-    HIPCHK(hipMemcpyAsync(h_sums, m->d_acc, (size_t)DS_TOTAL * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_sums, m->d_acc.d, (size_t)DS_TOTAL * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(stream_sync(ctx));
     return SR_OK;
 }

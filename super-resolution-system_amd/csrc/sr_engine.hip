@@ -1601,7 +1601,7 @@ struct sr_blend_plan : BlendTables {
     ~sr_blend_plan()                                    // under the context's Guard
     {
         for (void *p : owned) (void)hipFree(p);
-        for (auto &t : subset_tabs) (void)hipFree(t.d);
+        for (auto &t : subset_tabs) t.buf.release();
     }
 };
 static_assert(sizeof(int4) == sizeof(EdgeBlock), "the kernels read an EdgeBlock as one int4");
@@ -1677,18 +1677,20 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
     if (rc) return rc;
     // One table onto the device: an allocation of its own of max(count, 1) elements, owned by the plan, `count` elements copied
     // into it (src == nullptr: none -- the table is written per call).  The first failure sticks: the calls after it do nothing.
-    hipError_t err = hipSuccess;
-    const char *what = "";
+    int up_rc = SR_OK;
     auto up = [&](auto *&d, const void *src, size_t count, const char *name) {
-        if (err != hipSuccess) return;
+        if (up_rc != SR_OK) return;
         const size_t es = sizeof(*d);
         void *p = nullptr;
-        what = name;
-        if ((err = hipMalloc(&p, es * std::max<size_t>(count, 1))) != hipSuccess) return;
+        hipError_t e = hipMalloc(&p, es * std::max<size_t>(count, 1));
+        if (e != hipSuccess) {
+            up_rc = dev_alloc_error("sr_blend_plan_create", name, es * std::max<size_t>(count, 1), e);
+            return;
+        }
         P->owned.push_back(p);
         d = static_cast<std::remove_reference_t<decltype(d)>>(p);
-        what = "upload";
-        if (src && count) err = hipMemcpy(p, src, es * count, hipMemcpyHostToDevice);
+        if (src && count && (e = hipMemcpy(p, src, es * count, hipMemcpyHostToDevice)) != hipSuccess)
+            up_rc = sr_set_error(SR_ERR_HIP, "sr_blend_plan_create: upload: %s", hipGetErrorString(e));
     };
     up(P->d_arena, nullptr, std::max<size_t>(P->arena_floats, 4), "arena");
     up(P->d_tiles, P->tiles.data(), P->tiles.size(), "tile table");
@@ -1714,10 +1716,7 @@ int sr_blend_plan_create(sr_ctx *ctx, const sr_tile_rect *h_tiles, int n, int cn
         for (int k = 1; k <= MARCH_NT; ++k)
             if (P->n_march_items[k] > 0) up(P->d_march_items[k], P->march_items[k].data(), P->march_items[k].size(), "march items");
     }
-    if (err != hipSuccess) {
-        const int code = (err == hipErrorOutOfMemory) ? SR_ERR_OOM : SR_ERR_HIP;
-        return sr_set_error(code, "sr_blend_plan_create: %s: %s", what, hipGetErrorString(err));
-    }
+    if (up_rc) return up_rc;
     {
         std::lock_guard<std::mutex> lk(g_reg_mu);
         g_live_plan.insert(P.get());
@@ -1841,8 +1840,7 @@ static int blend_pyramids(sr_blend_plan *P, int dtype, void *const *h_d_tiles, c
     } else {
         sub_t.resize(n_idx);
         for (int k = 0; k < n_idx; ++k) sub_t[k] = P->tiles[idx[k]];
-        auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-        const size_t o_src = al(sizeof(TileDev) * n_idx), total = o_src + al(sizeof(TileSrc) * n_idx);
+        const size_t o_src = up256(sizeof(TileDev) * n_idx), total = o_src + up256(sizeof(TileSrc) * n_idx);
         std::vector<char> packed(total, 0);
         memcpy(packed.data(), sub_t.data(), sizeof(TileDev) * n_idx);
         memcpy(packed.data() + o_src, sub_s.data(), sizeof(TileSrc) * n_idx);
@@ -1854,9 +1852,9 @@ static int blend_pyramids(sr_blend_plan *P, int dtype, void *const *h_d_tiles, c
             slot = &P->subset_tabs[P->subset_next];
             P->subset_next = (P->subset_next + 1) % 4;
         }
-        HIPCHK(upload_cached(ctx, *slot, packed.data(), total));
-        d_tiles = (const TileDev *)slot->d;
-        d_srcs = (const TileSrc *)((const char *)slot->d + o_src);
+        SRCHK(upload_cached(ctx, *slot, packed.data(), total));
+        d_tiles = slot->buf.as<const TileDev>();
+        d_srcs = slot->buf.as<const TileSrc>(o_src);
     }
     // tiles whose levels 1 and 2 come out of one march (u8 RGB, 32-bit offsets inside a tile and the arena; a strip's row
     // windows included)
@@ -2147,45 +2145,29 @@ static int fusion_host_impl(sr_ctx *ctx, bool lap, int dtype, const void *const 
     sr_blend_plan *plan = nullptr;
     int rc = sr_blend_plan_create(ctx, h_rects, n, cn, canvas_h, canvas_w, levels, weight_type, 0, canvas_h, &plan);
     if (rc) return rc;
+    std::unique_ptr<sr_blend_plan, int (*)(sr_blend_plan *)> plan_owner(plan, sr_blend_plan_destroy);
     const int es = dtype == SR_U8 ? 1 : 4;
+    std::vector<DevTemp> tiles;
+    tiles.reserve(n);
     std::vector<void *> d_tiles(n, nullptr);
     std::vector<int64_t> strides(n);
-    void *d_canvas = nullptr, *d_f32 = nullptr;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (auto p : d_tiles)
-            if (p) (void)hipFree(p);
-        if (d_canvas) (void)hipFree(d_canvas);
-        if (d_f32) (void)hipFree(d_f32);
-        sr_blend_plan_destroy(plan);
-    };
-    for (int t = 0; t < n && rc == SR_OK; ++t) {
+    for (int t = 0; t < n; ++t) {
         const size_t bytes = (size_t)h_rects[t].h * h_rects[t].w * cn * es;
         strides[t] = (int64_t)h_rects[t].w * cn * es;
-        hipError_t e = hipMalloc(&d_tiles[t], bytes);
-        if (e != hipSuccess) rc = sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "fusion_host: hipMalloc: %s", hipGetErrorString(e));
-        else if ((e = hipMemcpyAsync(d_tiles[t], h_tiles[t], bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-            rc = sr_set_error(SR_ERR_HIP, "fusion_host: H2D: %s", hipGetErrorString(e));
+        tiles.emplace_back(ctx);
+        SRCHK(tiles[t].alloc("fusion_host", bytes));
+        d_tiles[t] = tiles[t].d;
+        HIPCHK(hipMemcpyAsync(d_tiles[t], h_tiles[t], bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     const size_t cbytes = (size_t)canvas_h * canvas_w * cn;
-    if (rc == SR_OK) {
-        hipError_t e = hipMalloc(&d_canvas, cbytes);
-        if (e != hipSuccess) rc = sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "fusion_host: hipMalloc: %s", hipGetErrorString(e));
-    }
-    if (rc == SR_OK && h_canvas_f32) {
-        hipError_t e = hipMalloc(&d_f32, cbytes * sizeof(float));
-        if (e != hipSuccess) rc = sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "fusion_host: hipMalloc: %s", hipGetErrorString(e));
-    }
-    if (rc == SR_OK)
-        rc = blend_impl(plan, lap, dtype, d_tiles.data(), strides.data(), (uint8_t *)d_canvas, (int64_t)canvas_w * cn, (float *)d_f32);
-    if (rc == SR_OK) {
-        hipError_t e = hipMemcpyAsync(h_canvas, d_canvas, cbytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && h_canvas_f32) e = hipMemcpyAsync(h_canvas_f32, d_f32, cbytes * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = sr_set_error(SR_ERR_HIP, "fusion_host: D2H: %s", hipGetErrorString(e));
-    }
-    cleanup();
-    return rc;
+    DevTemp canvas(ctx), canvas_f32(ctx);
+    SRCHK(canvas.alloc("fusion_host", cbytes));
+    if (h_canvas_f32) SRCHK(canvas_f32.alloc("fusion_host", cbytes * sizeof(float)));
+    SRCHK(blend_impl(plan, lap, dtype, d_tiles.data(), strides.data(), canvas.as<uint8_t>(), (int64_t)canvas_w * cn, canvas_f32.as<float>()));
+    HIPCHK(hipMemcpyAsync(h_canvas, canvas.d, cbytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_canvas_f32) HIPCHK(hipMemcpyAsync(h_canvas_f32, canvas_f32.d, cbytes * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(stream_sync(ctx));
+    return SR_OK;
 }
 
 int sr_laplacian_fusion_host(sr_ctx *ctx, int dtype, const void *const *h_tiles, const sr_tile_rect *h_rects, int n,

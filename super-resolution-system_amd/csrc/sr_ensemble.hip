@@ -158,8 +158,8 @@ int ens_run(const char *who, SrModelBase &m, int scale, const EnsForward &fwd, c
     if (rc) return rc;
     if ((rc = check_image(who, "source", d_src, src_stride, (long long)w * 3, false))) return rc;
     if ((rc = check_image(who, "destination", d_dst, dst_stride, (long long)w * scale * (u8 ? 3 : 12), !u8))) return rc;
-    if ((rc = ensure_activation_buffers(ctx, m.ens_ws, 1, m.ens_floats, (L.total + 3) / 4, who))) return rc;
-    char *ws = (char *)m.ens_ws[0];
+    if ((rc = ensure_activation_buffers(ctx, &m.ens_ws, 1, (L.total + 3) / 4, who))) return rc;
+    char *ws = m.ens_ws.as<char>();
     float *acc = (float *)(ws + L.acc_off), *y = (float *)(ws + L.y_off);
     uint8_t *in = (uint8_t *)(ws + L.in_off);
     const int H = h * scale, W = w * scale;

@@ -365,11 +365,10 @@ int sr_gradient_fusion(sr_ctx *ctx, int dtype, void *const *h_d_tiles, const int
         }
     }
     const size_t b0 = sizeof(GradTile) * (size_t)n, b1 = sizeof(float) * luts.size();
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     void *scr = nullptr;
-    int rc = ctx_scratch(ctx, al(b0) + al(b1), &scr);
+    int rc = ctx_scratch(ctx, up256(b0) + up256(b1), &scr);
     if (rc) return rc;
-    char *p0 = (char *)scr, *p1 = p0 + al(b0);
+    char *p0 = (char *)scr, *p1 = p0 + up256(b0);
     HIPCHK(upload_small(ctx, p0, gt.data(), b0));
     HIPCHK(upload_small(ctx, p1, luts.data(), b1));
     const GradTile *d_gt = (const GradTile *)p0;
@@ -475,11 +474,10 @@ int sr_tile_ssim_sums_u8(sr_ctx *ctx, const uint8_t *d_canvas, int64_t canvas_st
         max_ow = std::max(max_ow, S.ow);
     }
     const size_t b0 = sizeof(SsimTile) * (size_t)n, b1 = sizeof(LinTab) * tabs.size(), b2 = sizeof(uint64_t) * 5 * (size_t)n;
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     void *scr = nullptr;
-    int rc = ctx_scratch(ctx, al(b0) + al(b1) + al(b2), &scr);
+    int rc = ctx_scratch(ctx, up256(b0) + up256(b1) + up256(b2), &scr);
     if (rc) return rc;
-    char *p0 = (char *)scr, *p1 = p0 + al(b0), *p2 = p1 + al(b1);
+    char *p0 = (char *)scr, *p1 = p0 + up256(b0), *p2 = p1 + up256(b1);
     HIPCHK(upload_small(ctx, p0, st.data(), b0));
     if (b1) HIPCHK(upload_small(ctx, p1, tabs.data(), b1));
     HIPCHK(hipMemsetAsync(p2, 0, b2, ctx->stream));

@@ -11,6 +11,9 @@
 
 int sr_set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// Sections of a device workspace start at multiples of 256 bytes.
+inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
 struct SrWin {
     int a, b;  // [a, b)
     bool empty() const { return a >= b; }

@@ -93,15 +93,22 @@ struct sr_lpips_model {
     sr_ctx *ctx = nullptr;
     int net = 0;
     std::vector<LpLayer> layers;
-    std::vector<float *> d_w, d_b;    // per convolution: weights in the kernel's layout, bias
-    float *d_lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<DevBuf> d_w, d_b;     // per convolution: weights in the kernel's layout, bias
+    std::vector<DevBuf> d_lin;        // per tap
     int tap_c[5] = {0, 0, 0, 0, 0};
     float shift[3], scale[3];
-    float *buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [image][ping-pong] activation buffers
-    size_t buf_floats = 0;
-    double *d_acc = nullptr;          // 5 layer sums
-    double *d_part = nullptr;         // per-block partials of one tap launch
-    size_t part_cap = 0;
+    DevBuf buf[2][2];                 // [image][ping-pong] activation buffers
+    DevBuf d_acc;                     // 5 layer sums
+    DevBuf d_part;                    // per-block partials of one tap launch
+    void release_device()
+    {
+        for (auto *v : {&d_w, &d_b, &d_lin})
+            for (auto &p : *v) p.release();
+        for (auto &im : buf)
+            for (auto &p : im) p.release();
+        d_acc.release();
+        d_part.release();
+    }
 };
 
 static LiveSet g_lp_live;
@@ -156,11 +163,11 @@ int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, const fl
         M->scale[c] = h_scale ? h_scale[c] : def_scale[c];
     }
     g_lp_live.insert(M);
-    auto fail = [&](int code, const char *what) {
-        sr_set_error(code, "sr_lpips_create: %s", what);
+    auto drop = [&](int rc) {                               // the error is set
         sr_lpips_destroy(M);
-        return code;
+        return rc;
     };
+    auto fail = [&](int code, const char *what) { return drop(sr_set_error(code, "sr_lpips_create: %s", what)); };
     int tapc = 3, ti = 0;
     for (auto &l : M->layers) {
         if (l.kind == LP_CONV) tapc = l.cout;
@@ -184,22 +191,16 @@ int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, const fl
                 return fail(SR_ERR_UNSUPPORTED, "convolution shape outside the MFMA kernel's cases");
             arranged = arrange_mfma_weights(w, b, l.cout, l.cin, T, CC, 64).w;     // cout % 64 == 0: the bias needs no padding
         }
-        float *dw = nullptr, *db = nullptr;
-        if (hipMalloc((void **)&dw, arranged.size() * sizeof(float)) != hipSuccess) return fail(SR_ERR_OOM, "weights");
-        M->d_w.push_back(dw);
-        if (hipMalloc((void **)&db, (size_t)l.cout * sizeof(float)) != hipSuccess) { M->d_b.push_back(nullptr); return fail(SR_ERR_OOM, "bias"); }
-        M->d_b.push_back(db);
-        if (hipMemcpy(dw, arranged.data(), arranged.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(db, b, (size_t)l.cout * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-            return fail(SR_ERR_HIP, "weight upload");
+        int rc;
+        if ((rc = upload_floats(ctx, "sr_lpips_create: weights", arranged.data(), arranged.size(), M->d_w)) ||
+            (rc = upload_floats(ctx, "sr_lpips_create: bias", b, (size_t)l.cout, M->d_b)))
+            return drop(rc);
     }
     for (int i = 0; i < 5; ++i) {
         if (!h_lin_w[i]) return fail(SR_ERR_INVALID_ARG, "null lin array");
-        if (hipMalloc((void **)&M->d_lin[i], (size_t)M->tap_c[i] * sizeof(float)) != hipSuccess) return fail(SR_ERR_OOM, "lin");
-        if (hipMemcpy(M->d_lin[i], h_lin_w[i], (size_t)M->tap_c[i] * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-            return fail(SR_ERR_HIP, "lin upload");
+        if (int rc = upload_floats(ctx, "sr_lpips_create: lin", h_lin_w[i], (size_t)M->tap_c[i], M->d_lin)) return drop(rc);
     }
-    if (hipMalloc((void **)&M->d_acc, 5 * sizeof(double)) != hipSuccess) return fail(SR_ERR_OOM, "accumulators");
+    if (int rc = M->d_acc.reserve(ctx, "sr_lpips_create: accumulators", 5 * sizeof(double))) return drop(rc);
     *out = M;
     return SR_OK;
 }
@@ -211,12 +212,7 @@ int sr_lpips_destroy(sr_lpips_model *m)
     if (ctx_is_live(m->ctx)) {
         Guard g(m->ctx);
         (void)hipStreamSynchronize(m->ctx->stream);
-        for (auto p : m->d_w) if (p) (void)hipFree(p);
-        for (auto p : m->d_b) if (p) (void)hipFree(p);
-        for (auto p : m->d_lin) if (p) (void)hipFree(p);
-        for (auto &im : m->buf) for (auto p : im) if (p) (void)hipFree(p);
-        if (m->d_acc) (void)hipFree(m->d_acc);
-        if (m->d_part) (void)hipFree(m->d_part);
+        m->release_device();
     }
     delete m;
     return SR_OK;
@@ -265,7 +261,7 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
     ntiles = tiles_x * tiles_y;
     if (tile_end < 0 || tile_end > ntiles) tile_end = ntiles;
     tile_begin = std::max(tile_begin, 0);
-    HIPCHK(hipMemsetAsync(m->d_acc, 0, 5 * sizeof(double), ctx->stream));
+    HIPCHK(hipMemsetAsync(m->d_acc.d, 0, 5 * sizeof(double), ctx->stream));
     const std::vector<LpLayer> &L = m->layers;
     const int na = (int)G.H.size();
     const dim3 blk(64, 4);
@@ -283,7 +279,7 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
             plane[j] = (long long)ny[j].n() * pitch[j];
             need_floats = std::max(need_floats, (size_t)plane[j] * G.C[j]);
         }
-        rc = ensure_activation_buffers(ctx, &m->buf[0][0], 4, m->buf_floats, need_floats, "sr_lpips_u8");
+        rc = ensure_activation_buffers(ctx, &m->buf[0][0], 4, need_floats, "sr_lpips_u8");
         if (rc) return rc;
         int cur = 0;                       // ping-pong index of the current activation (both images in step)
         for (size_t li = 0; li < L.size(); ++li) {
@@ -294,18 +290,11 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
                 if (ry.empty() || rx.empty()) continue;
                 const dim3 grid((rx.n() + 63) / 64, (ry.n() + 3) / 4);
                 const size_t nblk = (size_t)grid.x * grid.y;
-                if (nblk > m->part_cap) {
-                    HIPCHK(stream_sync(ctx));
-                    if (m->d_part) (void)hipFree(m->d_part);
-                    m->d_part = nullptr;
-                    m->part_cap = 0;
-                    HIPCHK(hipMalloc((void **)&m->d_part, nblk * sizeof(double)));
-                    m->part_cap = nblk;
-                }
+                SRCHK(m->d_part.reserve(ctx, "sr_lpips_u8", nblk * sizeof(double)));
                 ProfScope ps(ctx, "lpips_tap");
-                hipLaunchKernelGGL(k_lp_tap, grid, blk, 0, ctx->stream, m->buf[0][cur], m->buf[1][cur], plane[ai], pitch[ai],
-                                   G.C[ai], m->d_lin[l.tap], ry.a - ny[ai].a, rx.a - nx[ai].a, ry.n(), rx.n(), m->d_part);
-                hipLaunchKernelGGL(k_lp_accum, dim3(1), dim3(256), 0, ctx->stream, m->d_part, (long long)nblk, m->d_acc + l.tap);
+                hipLaunchKernelGGL(k_lp_tap, grid, blk, 0, ctx->stream, m->buf[0][cur].as<float>(), m->buf[1][cur].as<float>(), plane[ai], pitch[ai],
+                                   G.C[ai], m->d_lin[l.tap].as<const float>(), ry.a - ny[ai].a, rx.a - nx[ai].a, ry.n(), rx.n(), m->d_part.as<double>());
+                hipLaunchKernelGGL(k_lp_accum, dim3(1), dim3(256), 0, ctx->stream, m->d_part.as<double>(), (long long)nblk, m->d_acc.as<double>() + l.tap);
                 continue;
             }
             const int ao = ai + 1;
@@ -313,8 +302,8 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
             if (rows <= 0 || cols <= 0) { cur ^= (ai > 0); continue; }
             const int nxt = ai == 0 ? 0 : cur ^ 1;
             for (int im = 0; im < 2; ++im) {
-                const float *src = ai == 0 ? nullptr : m->buf[im][cur];
-                float *dst = m->buf[im][nxt];
+                const float *src = ai == 0 ? nullptr : m->buf[im][cur].as<float>();
+                float *dst = m->buf[im][nxt].as<float>();
                 if (l.kind == LP_POOL) {
                     ProfScope ps(ctx, "lpips_pool");
                     const dim3 grid((cols + 63) / 64, (rows + 3) / 4, G.C[ao]);
@@ -326,14 +315,14 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
                     const long long st = im == 0 ? stride_a : stride_b;
                     const dim3 grid((cols + 63) / 64, (rows + 3) / 4);
                     const LpipsTable tab{m->shift[0], m->shift[1], m->shift[2], m->scale[0], m->scale[1], m->scale[2]};
-#define STEM_ARGS img, st, cn, h, w, m->d_w[l.widx], m->d_b[l.widx], tab, dst, ny[ao].a, nx[ao].a, rows, cols, pitch[ao], plane[ao]
+#define STEM_ARGS img, st, cn, h, w, m->d_w[l.widx].as<const float>(), m->d_b[l.widx].as<const float>(), tab, dst, ny[ao].a, nx[ao].a, rows, cols, pitch[ao], plane[ao]
                     if (l.k == 3) hipLaunchKernelGGL((k_lp_conv_stem<3, 1, 1, LpipsTable>), grid, blk, 0, ctx->stream, STEM_ARGS);
                     else hipLaunchKernelGGL((k_lp_conv_stem<11, 4, 2, LpipsTable>), grid, blk, 0, ctx->stream, STEM_ARGS);
 #undef STEM_ARGS
                 } else {
                     ProfScope ps(ctx, "lpips_conv_mfma");
                     const dim3 grid((cols + 31) / 32, (rows + 7) / 8, l.cout / 64);
-#define CONV_ARGS src, plane[ai], pitch[ai], ny[ai].a, nx[ai].a, G.H[ai], G.W[ai], l.cin, m->d_w[l.widx], m->d_b[l.widx], dst, \
+#define CONV_ARGS src, plane[ai], pitch[ai], ny[ai].a, nx[ai].a, G.H[ai], G.W[ai], l.cin, m->d_w[l.widx].as<const float>(), m->d_b[l.widx].as<const float>(), dst, \
                   plane[ao], pitch[ao], ny[ao].a, nx[ao].a, rows, cols
                     if (l.k == 3) hipLaunchKernelGGL((k_lp_conv_mfma<3, 8>), grid, dim3(256), 0, ctx->stream, CONV_ARGS);
                     else hipLaunchKernelGGL((k_lp_conv_mfma<5, 4>), grid, dim3(256), 0, ctx->stream, CONV_ARGS);
@@ -345,7 +334,7 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
         rc = check_launch("lpips");
         if (rc) return rc;
     }
-    HIPCHK(hipMemcpyAsync(h_layer_sums, m->d_acc, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_layer_sums, m->d_acc.d, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(stream_sync(ctx));
     return SR_OK;
 }

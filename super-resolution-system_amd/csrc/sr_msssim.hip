@@ -219,9 +219,8 @@ int sr_ms_ssim_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8
     if (stride_a < min_stride || stride_b < min_stride) return sr_set_error(SR_ERR_SHAPE, "sr_ms_ssim_u8: stride smaller than a row");
     CTX_ENTER(ctx);
     ctx->msssim_levels = 0;                                              // the planes are about to be overwritten
-    rc = ctx_grow_ws(ctx, "sr_ms_ssim_u8", &ctx->msssim_ws, &ctx->msssim_ws_bytes, p.total);
-    if (rc) return rc;
-    char *ws = (char *)ctx->msssim_ws;
+    SRCHK(ctx->msssim_ws.reserve(ctx, "sr_ms_ssim_u8", p.total));
+    char *ws = ctx->msssim_ws.as<char>();
     double *part = (double *)(ws + p.red.off_part), *buf0 = (double *)(ws + p.red.off_buf0), *buf1 = (double *)(ws + p.red.off_buf1),
            *res = (double *)(ws + p.off_res);
     static const char *const names[MS_MAX_LEVELS] = {"msssim_l0", "msssim_l1", "msssim_l2", "msssim_l3", "msssim_l4"};
@@ -299,7 +298,7 @@ int sr_ms_ssim_planes(sr_ctx *ctx, int level, uint16_t *h_x, uint16_t *h_y)
     if (rc) return rc;
     const size_t n = (size_t)p.lh[level] * (size_t)p.lw[level];
     std::vector<unsigned> host(n);
-    HIPCHK(hipMemcpyAsync(host.data(), (char *)ctx->msssim_ws + p.off_plane[level], n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(host.data(), ctx->msssim_ws.as<char>(p.off_plane[level]), n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(stream_sync(ctx));
     for (size_t i = 0; i < n; ++i) {
         h_x[i] = (uint16_t)(host[i] & 0xFFFFu);

@@ -119,9 +119,17 @@ inline int check_sr_geometry(const char *who, int h, int w, int scale, bool nega
 // What every model holds.
 struct SrModelBase {
     sr_ctx *ctx = nullptr;
-    std::vector<float *> d_w, d_b;            // per convolution
-    float *ens_ws[1] = {nullptr};             // workspace of the geometric self-ensemble (sr_ensemble.hip), grown on demand
-    size_t ens_floats = 0;
+    std::vector<DevBuf> d_w, d_b;             // per convolution
+    DevBuf ens_ws;                            // workspace of the geometric self-ensemble (sr_ensemble.hip), grown on demand
+    const float *w(int i) const { return d_w[i].as<const float>(); }
+    const float *b(int i) const { return d_b[i].as<const float>(); }
+    // Every model adds a release_device() of its own that ends with this one (destroy_model calls it).
+    void release_base()
+    {
+        for (auto &p : d_w) p.release();
+        for (auto &p : d_b) p.release();
+        ens_ws.release();
+    }
 };
 
 // The geometric self-ensemble over one family's forward (sr_ensemble.hip; the definition is in include/sr_hip.h).
@@ -144,26 +152,22 @@ inline int check_weight_tables(const char *who, const char *what, int n, int n_g
 // Appends one convolution's arranged weights and bias to the model; on failure the error is set and the caller destroys m.
 inline int upload_conv(const char *who, SrModelBase &m, const MfmaWeights &a)
 {
-    int rc;
-    if ((rc = upload_floats(a.w, m.d_w)) != SR_OK) return sr_set_error(rc, "%s: weight upload", who);
-    if ((rc = upload_floats(a.b, m.d_b)) != SR_OK) return sr_set_error(rc, "%s: bias upload", who);
+    SRCHK(upload_floats(m.ctx, who, a.w.data(), a.w.size(), m.d_w));
+    SRCHK(upload_floats(m.ctx, who, a.b.data(), a.b.size(), m.d_b));
     return SR_OK;
 }
 
-// The body of every *_destroy.  extra(*m): the device buffers the model owns beside d_w and d_b, asked for only once m is known
-// to be live.
-template <typename Model, typename Extra>
-inline int destroy_model(Model *m, LiveSet &live, Extra &&extra)
+// The body of every *_destroy: m->release_device() with the stream drained and the context's device current.  A model that
+// outlives its context only goes: the context's device memory is no longer this library's to free.
+template <typename Model>
+inline int destroy_model(Model *m, LiveSet &live)
 {
     if (!m) return SR_OK;
     if (!live.erase(m)) return SR_OK;
     if (ctx_is_live(m->ctx)) {
         Guard g(m->ctx);
         (void)hipStreamSynchronize(m->ctx->stream);
-        for (auto p : m->d_w) if (p) (void)hipFree(p);
-        for (auto p : m->d_b) if (p) (void)hipFree(p);
-        for (float *p : extra(*m)) if (p) (void)hipFree(p);
-        if (m->ens_ws[0]) (void)hipFree(m->ens_ws[0]);
+        m->release_device();
     }
     delete m;
     return SR_OK;

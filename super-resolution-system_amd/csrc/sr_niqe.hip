@@ -203,9 +203,8 @@ int sr_niqe_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, 
     if (stride < (int64_t)w * cn) return sr_set_error(SR_ERR_SHAPE, "sr_niqe_u8: stride smaller than a row");
     CTX_ENTER(ctx);
     ctx->niqe_H = ctx->niqe_W = 0;                                      // the scratch holds nothing valid until this call completes
-    rc = ctx_grow_ws(ctx, "sr_niqe_u8", &ctx->niqe_ws, &ctx->niqe_ws_bytes, p.total);
-    if (rc) return rc;
-    char *ws = (char *)ctx->niqe_ws;
+    SRCHK(ctx->niqe_ws.reserve(ctx, "sr_niqe_u8", p.total));
+    char *ws = ctx->niqe_ws.as<char>();
     int *half = (int *)(ws + p.off_half);
     sr_niqe_block *rec = (sr_niqe_block *)(ws + p.off_rec);
     NqWindow Kw;
@@ -249,7 +248,7 @@ int sr_niqe_half_plane(sr_ctx *ctx, int32_t *h_out)
     CTX_ENTER(ctx);
     if (ctx->niqe_H < 1) return sr_set_error(SR_ERR_INVALID_ARG, "sr_niqe_half_plane: no sr_niqe_u8 call has completed on this context");
     const size_t n = (size_t)(ctx->niqe_H / 2) * (size_t)(ctx->niqe_W / 2);
-    HIPCHK(hipMemcpyAsync(h_out, ctx->niqe_ws, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_out, ctx->niqe_ws.d, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(stream_sync(ctx));
     return SR_OK;
 }

@@ -15,7 +15,6 @@ constexpr int F = NQ_FEAT;
 constexpr int GAM_N = 9801;                 // gam = 0.2 + 0.001 t, t = 0 .. 9800
 constexpr int MIN_FIT_ROWS = F + 1;         // a sample covariance of 36 features has full rank from 37 rows on
 
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 double gam_at(int t) { return 0.2 + 0.001 * (double)t; }
 

@@ -38,7 +38,6 @@ namespace {
 
 #define PS_THREADS 256
 
-size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 __device__ __forceinline__ int ps_refl101(int p, int n)
 {
@@ -319,8 +318,8 @@ int sr_poisson_clone_u8(sr_ctx *ctx, const uint8_t *d_dest, int64_t dest_stride,
     }
     const int wi = w - 2, hi = h - 2, Lw = 2 * (wi + 1), Lh = 2 * (hi + 1);
     const size_t buf = std::max((size_t)2 * hi * sr_fft_work_len(Lw), (size_t)2 * wi * sr_fft_work_len(Lh));
-    const size_t b_fft = al256(buf * 8), b_tab = al256(std::max(sr_fft_tab_elems(Lw), sr_fft_tab_elems(Lh)) * 8),
-                 b_lam = al256((size_t)(wi + hi) * 8), b_em = al256((size_t)h * w);
+    const size_t b_fft = up256(buf * 8), b_tab = up256(std::max(sr_fft_tab_elems(Lw), sr_fft_tab_elems(Lh)) * 8),
+                 b_lam = up256((size_t)(wi + hi) * 8), b_em = up256((size_t)h * w);
     char *ws = nullptr;
     int rc = sr_fft_workspace(ctx, 3 * b_fft + b_tab + b_lam + b_em, &ws);
     if (rc) return rc;

@@ -309,16 +309,13 @@ int sr_quality_map_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const u
                  off_xe = off_cstart + up256(cstart.size() * sizeof(int)),
                  off_out = off_xe + up256(((size_t)gw + 1) * sizeof(int)), off_ws = off_out + up256(ncell * sizeof(QmapRecord)),
                  total = off_ws + (size_t)nsel * (size_t)P.plane * 8;
-    char *dev = nullptr;
-    hipError_t e = hipMalloc((void **)&dev, total);
-    if (e != hipSuccess)
-        return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "sr_quality_map_u8: workspace of %zu bytes: %s", total,
-                            hipGetErrorString(e));
-    // the host tables live until the synchronisation below
-    e = hipMemcpyAsync(dev + off_chunks, chunks.data(), chunks.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dev + off_cstart, cstart.data(), cstart.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dev + off_xe, h_xedges, ((size_t)gw + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
+    DevTemp ws(ctx);                                    // chunks and cstart are older: they outlive the sync of its destructor
+    SRCHK(ws.alloc("sr_quality_map_u8", total));
+    char *dev = ws.as<char>();
+    HIPCHK(hipMemcpyAsync(dev + off_chunks, chunks.data(), chunks.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dev + off_cstart, cstart.data(), cstart.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dev + off_xe, h_xedges, ((size_t)gw + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    {
         ProfScope ps(ctx, "qmap");
         const dim3 grid((unsigned)nchunk, (unsigned)((w + S11_OUT - 1) / S11_OUT)), block(S11_TX);
         if (cn == 3)
@@ -330,15 +327,10 @@ int sr_quality_map_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const u
         hipLaunchKernelGGL(k_qmap_cells, dim3((unsigned)ncell), dim3(256), 0, ctx->stream, (const unsigned long long *)(dev + off_ws), P,
                            (const int *)(dev + off_xe), gw, (const int *)(dev + off_cstart), (QmapRecord *)(dev + off_out));
     }
-    rc = e == hipSuccess ? check_launch("qmap") : sr_set_error(SR_ERR_HIP, "sr_quality_map_u8: H2D: %s", hipGetErrorString(e));
-    if (rc == SR_OK) {
-        e = hipMemcpyAsync(h_out, dev + off_out, ncell * sizeof(QmapRecord), hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) rc = sr_set_error(SR_ERR_HIP, "sr_quality_map_u8: D2H: %s", hipGetErrorString(e));
-    }
-    e = stream_sync(ctx);
-    if (e != hipSuccess && rc == SR_OK) rc = sr_set_error(SR_ERR_HIP, "sr_quality_map_u8: %s", hipGetErrorString(e));
-    (void)hipFree(dev);
-    return rc;
+    SRCHK(check_launch("qmap"));
+    HIPCHK(hipMemcpyAsync(h_out, dev + off_out, ncell * sizeof(QmapRecord), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(stream_sync(ctx));
+    return SR_OK;
 }
 
 }  // extern "C"

@@ -288,8 +288,12 @@ struct RnTen : PlanarTen {
 struct sr_resnet_model : SrModelBase {         // d_w, d_b: per op
     sr_resnet_desc d{};
     std::vector<RnOp> ops;
-    float *buf[3] = {nullptr, nullptr, nullptr};
-    size_t buf_floats = 0;
+    DevBuf buf[3];
+    void release_device()
+    {
+        for (auto &b : buf) b.release();
+        release_base();
+    }
 };
 
 static LiveSet g_rn_live;
@@ -306,7 +310,7 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
     RnGeom g;
     rc = rn_geometry(who, m->d, m->ops, h, w, tile, g);
     if (rc) return rc;
-    rc = ensure_activation_buffers(ctx, m->buf, 3, m->buf_floats, (size_t)g.plane * F, who);
+    rc = ensure_activation_buffers(ctx, m->buf, 3, (size_t)g.plane * F, who);
     if (rc) return rc;
     const std::vector<RnOp> &ops = m->ops;
     const size_t n = ops.size();
@@ -344,7 +348,7 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
                 // where a freshly laid out result goes: r x the convolution's own extent
                 auto fresh = [&](int b) {
                     RnTen o;
-                    static_cast<PlanarTen &>(o) = planar_tensor(m->buf[b], oya * op.r, oxa * op.r, rows * op.r, cols * op.r);
+                    static_cast<PlanarTen &>(o) = planar_tensor(m->buf[b].as<float>(), oya * op.r, oxa * op.r, rows * op.r, cols * op.r);
                     o.buf = b;
                     return o;
                 };
@@ -354,7 +358,7 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
                     ProfScope ps(ctx, "resnet_head");
                     t = fresh(0);
                     hipLaunchKernelGGL(k_rn_head, dim3((cols + 63) / 64, (rows + 3) / 4, F / 64), dim3(64, 4), 0, ctx->stream, d_src,
-                                       (long long)src_stride, h, w, m->d_w[i], m->d_b[i], op.slope, af, t.p, oya, oxa, rows, cols, t.pitch,
+                                       (long long)src_stride, h, w, m->w(i), m->b(i), op.slope, af, t.p, oya, oxa, rows, cols, t.pitch,
                                        t.plane);
                     if (m->d.long_skip) {
                         hten = t;
@@ -365,7 +369,7 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
                     ProfScope ps(ctx, op.lvl == 0 ? "resnet_body" : "resnet_hr");
                     blk = t;                               // a block's first convolution: its input is the block's skip
                     RnTen o = fresh(other(t.buf, h_buf));
-                    launch_conv(k_rn_conv<2, RN_SLOPE>, ctx->stream, t, H_in, W_in, F, F / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa, rows,
+                    launch_conv(k_rn_conv<2, RN_SLOPE>, ctx->stream, t, H_in, W_in, F, F / 64, m->w(i), m->b(i), o.p, o.plane, o.pitch, oya, oxa, rows,
                                            cols, ep);
                     t = o;
                 } else if (op.kind == OP_SKIP) {
@@ -385,7 +389,7 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
                     ep.skip_pitch = sk.pitch;
                     ep.skip_ya = sk.ya;
                     ep.skip_xa = sk.xa;
-                    launch_conv(k_rn_conv<2, RN_SKIP>, ctx->stream, t, H_in, W_in, F, F / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa, rows,
+                    launch_conv(k_rn_conv<2, RN_SKIP>, ctx->stream, t, H_in, W_in, F, F / 64, m->w(i), m->b(i), o.p, o.plane, o.pitch, oya, oxa, rows,
                                           cols, ep);
                     t = o;
                     if (op.skip == 2) h_buf = -1;
@@ -393,18 +397,18 @@ static int rn_forward(sr_resnet_model *m, const uint8_t *d_src, int64_t src_stri
                     ProfScope ps(ctx, "resnet_up");
                     RnTen o = fresh(other(t.buf, -1));
                     if (op.r == 2)
-                        launch_conv(k_rn_conv<2, RN_SHUF2>, ctx->stream, t, H_in, W_in, F, F * 4 / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa,
+                        launch_conv(k_rn_conv<2, RN_SHUF2>, ctx->stream, t, H_in, W_in, F, F * 4 / 64, m->w(i), m->b(i), o.p, o.plane, o.pitch, oya, oxa,
                                                rows, cols, ep);
                     else
-                        launch_conv(k_rn_conv<2, RN_SHUF3>, ctx->stream, t, H_in, W_in, F, F * 9 / 64, m->d_w[i], m->d_b[i], o.p, o.plane, o.pitch, oya, oxa,
+                        launch_conv(k_rn_conv<2, RN_SHUF3>, ctx->stream, t, H_in, W_in, F, F * 9 / 64, m->w(i), m->b(i), o.p, o.plane, o.pitch, oya, oxa,
                                                rows, cols, ep);
                     t = o;
                 } else {
                     ProfScope ps(ctx, "resnet_last");
                     if (u8)
-                        launch_conv(k_rn_conv<1, RN_LAST_U8>, ctx->stream, t, H_in, W_in, F, 1, m->d_w[i], m->d_b[i], nullptr, 0LL, 0, oya, oxa, rows, cols, ep);
+                        launch_conv(k_rn_conv<1, RN_LAST_U8>, ctx->stream, t, H_in, W_in, F, 1, m->w(i), m->b(i), nullptr, 0LL, 0, oya, oxa, rows, cols, ep);
                     else
-                        launch_conv(k_rn_conv<1, RN_LAST_F32>, ctx->stream, t, H_in, W_in, F, 1, m->d_w[i], m->d_b[i], nullptr, 0LL, 0, oya, oxa, rows, cols, ep);
+                        launch_conv(k_rn_conv<1, RN_LAST_F32>, ctx->stream, t, H_in, W_in, F, 1, m->w(i), m->b(i), nullptr, 0LL, 0, oya, oxa, rows, cols, ep);
                 }
             }
             rc = check_launch(who);
@@ -460,7 +464,7 @@ int sr_resnet_create(sr_ctx *ctx, const sr_resnet_desc *desc, const float *const
 
 int sr_resnet_destroy(sr_resnet_model *m)
 {
-    return destroy_model(m, g_rn_live, [](const sr_resnet_model &m) { return std::vector<float *>(m.buf, m.buf + 3); });
+    return destroy_model(m, g_rn_live);
 }
 
 int sr_resnet_plan(const sr_resnet_desc *desc, int h, int w, int tile, int *halo, int *n_tiles, size_t *workspace_bytes)

@@ -284,11 +284,15 @@ int rr_geometry(const char *who, const sr_rrdb_desc &d, int h, int w, int tile, 
 
 struct sr_rrdb_model : SrModelBase {
     sr_rrdb_desc d{};
-    float *dense[3] = {nullptr, nullptr, nullptr};
-    float *hbuf[1] = {nullptr};               // h, until conv_body has added it
-    float *f2[1] = {nullptr};                 // f replicated to 2 x: what the trunk phase leaves to the tail phase
-    float *tailbuf[2] = {nullptr, nullptr};
-    size_t dense_floats = 0, h_floats = 0, f2_floats = 0, tail_floats = 0;
+    DevBuf dense[3];
+    DevBuf hbuf;                              // h, until conv_body has added it
+    DevBuf f2;                                // f replicated to 2 x: what the trunk phase leaves to the tail phase
+    DevBuf tailbuf[2];
+    void release_device()
+    {
+        for (DevBuf *b : {&dense[0], &dense[1], &dense[2], &hbuf, &f2, &tailbuf[0], &tailbuf[1]}) b->release();
+        release_base();
+    }
 };
 
 static LiveSet g_rr_live;
@@ -305,10 +309,10 @@ static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride
     RrGeom g;
     rc = rr_geometry(who, m->d, h, w, tile, tail, g);
     if (rc) return rc;
-    if ((rc = ensure_activation_buffers(ctx, m->dense, 3, m->dense_floats, (size_t)g.plane0 * DP, who))) return rc;
-    if ((rc = ensure_activation_buffers(ctx, m->hbuf, 1, m->h_floats, (size_t)g.plane0 * F, who))) return rc;
-    if ((rc = ensure_activation_buffers(ctx, m->f2, 1, m->f2_floats, (size_t)g.plane2 * F, who))) return rc;
-    if ((rc = ensure_activation_buffers(ctx, m->tailbuf, 2, m->tail_floats, (size_t)g.plane4 * F, who))) return rc;
+    if ((rc = ensure_activation_buffers(ctx, m->dense, 3, (size_t)g.plane0 * DP, who))) return rc;
+    if ((rc = ensure_activation_buffers(ctx, &m->hbuf, 1, (size_t)g.plane0 * F, who))) return rc;
+    if ((rc = ensure_activation_buffers(ctx, &m->f2, 1, (size_t)g.plane2 * F, who))) return rc;
+    if ((rc = ensure_activation_buffers(ctx, m->tailbuf, 2, (size_t)g.plane4 * F, who))) return rc;
     hipStream_t st = ctx->stream;
     const std::vector<ExtStep> steps = rr_steps(n);
     RrEpi ep0{};
@@ -336,15 +340,15 @@ static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride
                 ProfScope ps(ctx, "rrdb_head");
                 // h goes to planes [0, F) of dense buffer 0 (the first dense block's x) and, where an RRDB will overwrite that in
                 // place, to its own buffer as well (conv_body adds it)
-                for (float *o : {m->dense[0], B > 0 ? m->hbuf[0] : (float *)nullptr})
+                for (float *o : {m->dense[0].as<float>(), B > 0 ? m->hbuf.as<float>() : (float *)nullptr})
                     if (o)
                         hipLaunchKernelGGL(k_rr_head, dim3((L.cols + 63) / 64, (L.rows + 3) / 4, F / 64), dim3(64, 4), 0, st, d_src,
-                                           (long long)src_stride, h, w, m->d_w[0], m->d_b[0], o, L.ya, L.xa, L.rows, L.cols, L.pitch, L.plane);
+                                           (long long)src_stride, h, w, m->w(0), m->b(0), o, L.ya, L.xa, L.rows, L.cols, L.pitch, L.plane);
             }
             int i = 1;
             for (int blk = 0; blk < B; ++blk)
                 for (int db = 0; db < 3; ++db) {
-                    float *D = m->dense[db];
+                    float *D = m->dense[db].as<float>();
                     // The guard is the buffer's stored extent (the head's).  Planes of x_j hold stale values outside convolution
                     // j's extent; by the extent rule (each extent is the next one grown by one, clipped) these reach only masked
                     // outputs, and an output depends on its own pixel's patch alone.
@@ -354,29 +358,29 @@ static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride
                         const int cin = F + (k - 1) * G, rows = yb[i] - ya[i], cols = xb[i] - xa[i];
                         float *o = at(D + (size_t)cin * L.plane, i);
                         if (G == 32)
-                            launch_conv(k_rr_conv<1, RR_ACT>, st, in, h, w, cin, 1, m->d_w[i], m->d_b[i], o, L.plane, L.pitch, ya[i], xa[i], rows, cols, ep);
+                            launch_conv(k_rr_conv<1, RR_ACT>, st, in, h, w, cin, 1, m->w(i), m->b(i), o, L.plane, L.pitch, ya[i], xa[i], rows, cols, ep);
                         else
-                            launch_conv(k_rr_conv<2, RR_ACT>, st, in, h, w, cin, 1, m->d_w[i], m->d_b[i], o, L.plane, L.pitch, ya[i], xa[i], rows, cols, ep);
+                            launch_conv(k_rr_conv<2, RR_ACT>, st, in, h, w, cin, 1, m->w(i), m->b(i), o, L.plane, L.pitch, ya[i], xa[i], rows, cols, ep);
                     }
                     ProfScope ps(ctx, "rrdb_blockout");
                     const int rows = yb[i] - ya[i], cols = xb[i] - xa[i];
                     ep.skip = D;
                     if (db < 2) {
-                        launch_conv(k_rr_conv<2, RR_SKIP>, st, in, h, w, DP, F / 64, m->d_w[i], m->d_b[i], at(m->dense[db + 1], i), L.plane, L.pitch, ya[i],
+                        launch_conv(k_rr_conv<2, RR_SKIP>, st, in, h, w, DP, F / 64, m->w(i), m->b(i), at(m->dense[db + 1].as<float>(), i), L.plane, L.pitch, ya[i],
                                               xa[i], rows, cols, ep);
                     } else {                               // in place over the RRDB's input r
-                        ep.skip2 = m->dense[0];
-                        launch_conv(k_rr_conv<2, RR_SKIP2>, st, in, h, w, DP, F / 64, m->d_w[i], m->d_b[i], at(m->dense[0], i), L.plane, L.pitch, ya[i],
+                        ep.skip2 = m->dense[0].as<float>();
+                        launch_conv(k_rr_conv<2, RR_SKIP2>, st, in, h, w, DP, F / 64, m->w(i), m->b(i), at(m->dense[0].as<float>(), i), L.plane, L.pitch, ya[i],
                                                xa[i], rows, cols, ep);
                     }
                     ++i;
                 }
             // conv_body + h, replicated to 2 x
-            const PlanarTen f2 = planar_tensor(m->f2[0], 2 * ya[i], 2 * xa[i], 2 * (yb[i] - ya[i]), 2 * (xb[i] - xa[i]));
+            const PlanarTen f2 = planar_tensor(m->f2.as<float>(), 2 * ya[i], 2 * xa[i], 2 * (yb[i] - ya[i]), 2 * (xb[i] - xa[i]));
             {
                 ProfScope ps(ctx, "rrdb_bodyup");
-                ep.skip = B > 0 ? m->hbuf[0] : m->dense[0];
-                launch_conv(k_rr_conv<2, RR_REP_SKIP>, st, ten(m->dense[0]), h, w, F, F / 64, m->d_w[i], m->d_b[i], f2.p, f2.plane, f2.pitch, ya[i], xa[i],
+                ep.skip = B > 0 ? m->hbuf.as<float>() : m->dense[0].as<float>();
+                launch_conv(k_rr_conv<2, RR_REP_SKIP>, st, ten(m->dense[0].as<float>()), h, w, F, F / 64, m->w(i), m->b(i), f2.p, f2.plane, f2.pitch, ya[i], xa[i],
                                           yb[i] - ya[i], xb[i] - xa[i], ep);
             }
             rc = check_launch(who);
@@ -389,28 +393,28 @@ static int rr_forward(sr_rrdb_model *m, const uint8_t *d_src, int64_t src_stride
                     rr_extents(steps, sx, (int)std::min<long long>((long long)sx + g.tail, px1), w, sxa, sxb);
                     auto rows = [&](int k) { return syb[k] - sya[k]; };
                     auto cols = [&](int k) { return sxb[k] - sxa[k]; };
-                    const PlanarTen a = planar_tensor(m->tailbuf[0], 2 * sya[u1], 2 * sxa[u1], 2 * rows(u1), 2 * cols(u1));
-                    const PlanarTen b = planar_tensor(m->tailbuf[1], sya[u2], sxa[u2], rows(u2), cols(u2));
-                    const PlanarTen c = planar_tensor(m->tailbuf[0], sya[hr], sxa[hr], rows(hr), cols(hr));
+                    const PlanarTen a = planar_tensor(m->tailbuf[0].as<float>(), 2 * sya[u1], 2 * sxa[u1], 2 * rows(u1), 2 * cols(u1));
+                    const PlanarTen b = planar_tensor(m->tailbuf[1].as<float>(), sya[u2], sxa[u2], rows(u2), cols(u2));
+                    const PlanarTen c = planar_tensor(m->tailbuf[0].as<float>(), sya[hr], sxa[hr], rows(hr), cols(hr));
                     {
                         ProfScope ps(ctx, "rrdb_bodyup");
-                        launch_conv(k_rr_conv<2, RR_REP_ACT>, st, f2, 2 * h, 2 * w, F, F / 64, m->d_w[u1], m->d_b[u1], a.p, a.plane, a.pitch, sya[u1], sxa[u1],
+                        launch_conv(k_rr_conv<2, RR_REP_ACT>, st, f2, 2 * h, 2 * w, F, F / 64, m->w(u1), m->b(u1), a.p, a.plane, a.pitch, sya[u1], sxa[u1],
                                                  rows(u1), cols(u1), ep);
-                        launch_conv(k_rr_conv<2, RR_ACT>, st, a, 4 * h, 4 * w, F, F / 64, m->d_w[u2], m->d_b[u2], b.p, b.plane, b.pitch, sya[u2], sxa[u2],
+                        launch_conv(k_rr_conv<2, RR_ACT>, st, a, 4 * h, 4 * w, F, F / 64, m->w(u2), m->b(u2), b.p, b.plane, b.pitch, sya[u2], sxa[u2],
                                              rows(u2), cols(u2), ep);
                     }
                     {
                         ProfScope ps(ctx, "rrdb_hr");
-                        launch_conv(k_rr_conv<2, RR_ACT>, st, b, 4 * h, 4 * w, F, F / 64, m->d_w[hr], m->d_b[hr], c.p, c.plane, c.pitch, sya[hr], sxa[hr],
+                        launch_conv(k_rr_conv<2, RR_ACT>, st, b, 4 * h, 4 * w, F, F / 64, m->w(hr), m->b(hr), c.p, c.plane, c.pitch, sya[hr], sxa[hr],
                                              rows(hr), cols(hr), ep);
                     }
                     {
                         ProfScope ps(ctx, "rrdb_last");
                         if (u8)
-                            launch_conv(k_rr_conv<1, RR_LAST_U8>, st, c, 4 * h, 4 * w, F, 1, m->d_w[la], m->d_b[la], nullptr, 0LL, 0, sya[la], sxa[la], rows(la),
+                            launch_conv(k_rr_conv<1, RR_LAST_U8>, st, c, 4 * h, 4 * w, F, 1, m->w(la), m->b(la), nullptr, 0LL, 0, sya[la], sxa[la], rows(la),
                                                      cols(la), ep);
                         else
-                            launch_conv(k_rr_conv<1, RR_LAST_F32>, st, c, 4 * h, 4 * w, F, 1, m->d_w[la], m->d_b[la], nullptr, 0LL, 0, sya[la], sxa[la], rows(la),
+                            launch_conv(k_rr_conv<1, RR_LAST_F32>, st, c, 4 * h, 4 * w, F, 1, m->w(la), m->b(la), nullptr, 0LL, 0, sya[la], sxa[la], rows(la),
                                                       cols(la), ep);
                     }
                     rc = check_launch(who);
@@ -472,9 +476,7 @@ int sr_rrdb_create(sr_ctx *ctx, const sr_rrdb_desc *desc, const float *const *h_
 
 int sr_rrdb_destroy(sr_rrdb_model *m)
 {
-    return destroy_model(m, g_rr_live, [](const sr_rrdb_model &m) {
-        return std::vector<float *>{m.dense[0], m.dense[1], m.dense[2], m.hbuf[0], m.f2[0], m.tailbuf[0], m.tailbuf[1]};
-    });
+    return destroy_model(m, g_rr_live);
 }
 
 int sr_rrdb_plan(const sr_rrdb_desc *desc, int h, int w, int tile, int tail, int *halo, int *n_tiles, int *n_tail_tiles,

@@ -36,22 +36,59 @@ hipError_t upload_if_changed(sr_ctx *c, void *d_dst, const void *h_src, size_t b
     return upload_small(c, d_dst, h_src, bytes);
 }
 
-hipError_t upload_cached(sr_ctx *c, CachedTable &t, const void *h_src, size_t bytes)
+int upload_cached(sr_ctx *c, CachedTable &t, const void *h_src, size_t bytes)
 {
-    if (bytes > t.cap) {
-        if (t.d) {
-            hipError_t e = stream_sync(c);
-            if (e != hipSuccess) return e;
-            (void)hipFree(t.d);
-            t.d = nullptr;
-        }
-        const size_t nb = std::max<size_t>((bytes + 4095) / 4096 * 4096, 4096);
-        hipError_t e = hipMalloc(&t.d, nb);
-        if (e != hipSuccess) { t.cap = 0; return e; }
-        t.cap = nb;
-        t.shadow.clear();
+    bool regrown = false;
+    SRCHK(t.buf.reserve(c, "upload_cached", bytes, 0, 4096, &regrown));
+    if (regrown) t.shadow.clear();
+    HIPCHK(upload_if_changed(c, t.buf.d, h_src, bytes, t.shadow));
+    return SR_OK;
+}
+
+int dev_alloc_error(const char *who, const char *what, size_t bytes, hipError_t e)
+{
+    return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "%s: %s of %zu bytes: %s", who, what, bytes,
+                        hipGetErrorString(e));
+}
+
+int DevBuf::reserve(sr_ctx *c, const char *who, size_t bytes, size_t floor, size_t page, bool *regrown)
+{
+    if (bytes <= cap) return SR_OK;
+    if (d) {
+        HIPCHK(stream_sync(c));
+        release();
     }
-    return upload_if_changed(c, t.d, h_src, bytes, t.shadow);
+    const size_t nb = (std::max(bytes, floor) + page - 1) / page * page;
+    const hipError_t e = hipMalloc(&d, nb);
+    if (e != hipSuccess) {
+        d = nullptr;
+        return dev_alloc_error(who, "device buffer", nb, e);
+    }
+    cap = nb;
+    if (regrown) *regrown = true;
+    return SR_OK;
+}
+
+void DevBuf::release()
+{
+    if (d) (void)hipFree(d);
+    d = nullptr;
+    cap = 0;
+}
+
+DevTemp::~DevTemp()
+{
+    if (!d) return;
+    (void)stream_sync(c);
+    (void)hipFree(d);
+}
+
+int DevTemp::alloc(const char *who, size_t bytes)
+{
+    const hipError_t e = hipMalloc(&d, bytes);
+    if (e == hipSuccess) return SR_OK;
+    d = nullptr;
+    return dev_alloc_error(who, "temporary", bytes, e);
 }
 
 hipError_t stream_sync(sr_ctx *c)
@@ -77,18 +114,8 @@ bool ctx_is_live(const sr_ctx *c)
 
 int ctx_scratch(sr_ctx *c, size_t bytes, void **out)
 {
-    if (bytes > c->scratch_bytes) {
-        if (c->scratch) {
-            HIPCHK(stream_sync(c));
-            HIPCHK(hipFree(c->scratch));
-            c->scratch = nullptr;
-            c->scratch_bytes = 0;
-        }
-        size_t nb = std::max(bytes, (size_t)1 << 20);
-        HIPCHK(hipMalloc(&c->scratch, nb));
-        c->scratch_bytes = nb;
-    }
-    *out = c->scratch;
+    SRCHK(c->scratch.reserve(c, "ctx_scratch", bytes, (size_t)1 << 20));
+    *out = c->scratch.d;
     return SR_OK;
 }
 
@@ -189,15 +216,7 @@ int sr_ctx_destroy(sr_ctx *ctx)
             (void)hipEventDestroy(p.b);
         }
         for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
-        if (ctx->scratch) (void)hipFree(ctx->scratch);
-        if (ctx->gray_planes) (void)hipFree(ctx->gray_planes);
-        if (ctx->cm_ws) (void)hipFree(ctx->cm_ws);
-        if (ctx->msssim_ws) (void)hipFree(ctx->msssim_ws);
-        if (ctx->bench_ws) (void)hipFree(ctx->bench_ws);
-        if (ctx->niqe_ws) (void)hipFree(ctx->niqe_ws);
-        if (ctx->extract_tab.d) (void)hipFree(ctx->extract_tab.d);
-        if (ctx->resize_tab.d) (void)hipFree(ctx->resize_tab.d);
-        if (ctx->cubic_tab.d) (void)hipFree(ctx->cubic_tab.d);
+        ctx->release_device();
         if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     }
     delete ctx;
@@ -226,8 +245,7 @@ int sr_dev_alloc(sr_ctx *ctx, size_t bytes, void **d_ptr)
     *d_ptr = nullptr;
     if (bytes == 0) bytes = 16;
     hipError_t e = hipMalloc(d_ptr, bytes);
-    if (e == hipErrorOutOfMemory) return sr_set_error(SR_ERR_OOM, "sr_dev_alloc: out of device memory (%zu B)", bytes);
-    if (e != hipSuccess) return sr_set_error(SR_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return dev_alloc_error("sr_dev_alloc", "device memory", bytes, e);
     return SR_OK;
 }
 

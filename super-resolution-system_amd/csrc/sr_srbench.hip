@@ -199,9 +199,8 @@ int sr_bench_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t
     const int64_t min_stride = (int64_t)w * cn;
     if (stride_a < min_stride || stride_b < min_stride) return sr_set_error(SR_ERR_SHAPE, "sr_bench_u8: stride smaller than a row");
     CTX_ENTER(ctx);
-    rc = ctx_grow_ws(ctx, "sr_bench_u8", &ctx->bench_ws, &ctx->bench_ws_bytes, p.total);
-    if (rc) return rc;
-    char *ws = (char *)ctx->bench_ws;
+    SRCHK(ctx->bench_ws.reserve(ctx, "sr_bench_u8", p.total));
+    char *ws = ctx->bench_ws.as<char>();
     double *part = (double *)(ws + p.red.off_part), *buf0 = (double *)(ws + p.red.off_buf0), *buf1 = (double *)(ws + p.red.off_buf1);
     SbParams P;
     memset(&P, 0, sizeof(P));

@@ -154,9 +154,14 @@ int sn_geometry(const char *who, int h, int w, int n_body, int scale, int tile, 
 
 struct sr_srnet_model : SrModelBase {
     int F = 0, D = 0, S = 0;
-    std::vector<float *> d_slope;             // per layer 0 .. D (d_w, d_b: 0 .. D + 1; no slope for the tail)
-    float *buf[2] = {nullptr, nullptr};       // ping-pong activation buffers
-    size_t buf_floats = 0;
+    std::vector<DevBuf> d_slope;              // per layer 0 .. D (d_w, d_b: 0 .. D + 1; no slope for the tail)
+    DevBuf buf[2];                            // ping-pong activation buffers
+    void release_device()
+    {
+        for (auto &p : d_slope) p.release();
+        for (auto &b : buf) b.release();
+        release_base();
+    }
 };
 
 static LiveSet g_sn_live;
@@ -182,7 +187,7 @@ static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_strid
     SnGeom g;
     rc = sn_geometry(who, h, w, D, S, tile, g);
     if (rc) return rc;
-    rc = ensure_activation_buffers(ctx, m->buf, 2, m->buf_floats, (size_t)g.plane * F, who);
+    rc = ensure_activation_buffers(ctx, m->buf, 2, (size_t)g.plane * F, who);
     if (rc) return rc;
     const SnTail tail = {d_src, (long long)src_stride, d_dst, (long long)dst_stride};
     const std::vector<ExtStep> steps = sn_steps(D);
@@ -201,7 +206,7 @@ static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_strid
             {
                 ProfScope ps(ctx, "srnet_head");
                 hipLaunchKernelGGL(k_sn_head, dim3((cols + 63) / 64, (rows + 3) / 4, F / 64), dim3(64, 4), 0, ctx->stream, d_src,
-                                   (long long)src_stride, h, w, m->d_w[0], m->d_b[0], m->d_slope[0], m->buf[0], ya, xa, rows,
+                                   (long long)src_stride, h, w, m->w(0), m->b(0), m->d_slope[0].as<const float>(), m->buf[0].as<float>(), ya, xa, rows,
                                    cols, pitch, plane);
             }
             int in_ya = ya, in_xa = xa, in_rows = rows, in_cols = cols;
@@ -209,8 +214,8 @@ static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_strid
                 ext(k);
                 ProfScope ps(ctx, "srnet_body");
                 hipLaunchKernelGGL((k_sn_conv<2, 0, false>), dim3((cols + 31) / 32, (rows + 7) / 8, F / 64), dim3(256), 0, ctx->stream,
-                                   m->buf[cur], plane, pitch, in_ya, in_xa, in_rows, in_cols, h, w, F, m->d_w[k], m->d_b[k], m->d_slope[k],
-                                   m->buf[cur ^ 1], plane, pitch, ya, xa, rows, cols, SnTail{nullptr, 0, nullptr, 0});
+                                   m->buf[cur].as<float>(), plane, pitch, in_ya, in_xa, in_rows, in_cols, h, w, F, m->w(k), m->b(k), m->d_slope[k].as<const float>(),
+                                   m->buf[cur ^ 1].as<float>(), plane, pitch, ya, xa, rows, cols, SnTail{nullptr, 0, nullptr, 0});
                 cur ^= 1;
                 in_ya = ya; in_xa = xa; in_rows = rows; in_cols = cols;
             }
@@ -223,8 +228,8 @@ static int sn_forward(sr_srnet_model *m, const uint8_t *d_src, int64_t src_strid
                                                     {sn_launch_tail<2, false>, sn_launch_tail<2, true>},
                                                     {sn_launch_tail<3, false>, sn_launch_tail<3, true>},
                                                     {sn_launch_tail<4, false>, sn_launch_tail<4, true>}};
-                launch[S - 1][u8 ? 1 : 0](grid, ctx->stream, m->buf[cur], plane, pitch, in_ya, in_xa, in_rows, in_cols, h, w, F, m->d_w[D + 1],
-                                  m->d_b[D + 1], ya, xa, rows, cols, tail);
+                launch[S - 1][u8 ? 1 : 0](grid, ctx->stream, m->buf[cur].as<float>(), plane, pitch, in_ya, in_xa, in_rows, in_cols, h, w, F, m->w(D + 1),
+                                  m->b(D + 1), ya, xa, rows, cols, tail);
             }
             rc = check_launch(who);
             if (rc) return rc;
@@ -267,8 +272,7 @@ int sr_srnet_create(sr_ctx *ctx, int n_feat, int n_body, int scale, const float 
         if (k == 0) a = {arrange_head_weights(h_w[k], F), std::vector<float>(h_b[k], h_b[k] + F)};
         else a = arrange_mfma_weights(h_w[k], h_b[k], k <= D ? F : tail_c, F, 9, 8, k <= D ? 64 : tail_nc);
         rc = upload_conv("sr_srnet_create", *M, a);
-        if (!rc && k <= D && (rc = upload_floats(std::vector<float>(h_slope[k], h_slope[k] + F), M->d_slope)) != SR_OK)
-            sr_set_error(rc, "sr_srnet_create: slope upload");
+        if (!rc && k <= D) rc = upload_floats(ctx, "sr_srnet_create", h_slope[k], F, M->d_slope);
         if (rc) {
             sr_srnet_destroy(M);
             return rc;
@@ -280,11 +284,7 @@ int sr_srnet_create(sr_ctx *ctx, int n_feat, int n_body, int scale, const float 
 
 int sr_srnet_destroy(sr_srnet_model *m)
 {
-    return destroy_model(m, g_sn_live, [](const sr_srnet_model &m) {
-        std::vector<float *> v(m.d_slope);
-        v.insert(v.end(), m.buf, m.buf + 2);
-        return v;
-    });
+    return destroy_model(m, g_sn_live);
 }
 
 int sr_srnet_plan(int h, int w, int n_feat, int n_body, int scale, int tile, int *halo, int *n_tiles, size_t *workspace_bytes)

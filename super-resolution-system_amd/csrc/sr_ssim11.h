@@ -15,7 +15,7 @@
 //   ssim_terms        the terms of the SSIM quotient: l cs, and cs beside it from the same reciprocal.
 //   s11_block_sum2    the block's S11_TX column sums of two components through a fixed tree: no floating-point atomics.
 // Every expression is evaluated in the order written (the build has -ffp-contract=off): equal inputs give equal bits.
-// Host side: the normalised taps, the chunk cut, the scratch layout of the per-block partials and the workspace growth.
+// Host side: the normalised taps, the chunk cut, the scratch layout of the per-block partials.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -193,8 +193,6 @@ inline void gauss_taps(double *k6)
     for (int j = 0; j <= 5; ++j) k6[j] = k[5 + j] / sum;
 }
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 // Chunks of at most S11_ROWS map rows; a small map takes shorter ones (down to S11_ROWS_MIN) until it has S11_BLOCKS blocks:
 // a block walks its rows one after the other, so a small map cut into a few long chunks would take as long as a chunk takes
 // on an empty chip.  The cut depends on the size alone, never on the device: equal bits everywhere.
@@ -223,24 +221,4 @@ inline PartialsLayout s11_partials_layout(size_t off, size_t nblk)
 {
     const size_t part = up256(nblk * 2 * sizeof(double)), buf = up256((nblk / 1024 + 2) * 2 * sizeof(double));
     return {off, off + part, off + part + buf, off + part + 2 * buf};
-}
-
-// Grows a workspace of the context to `need` bytes (the old one is freed after the stream has drained; contents are lost).
-inline int ctx_grow_ws(sr_ctx *ctx, const char *scope, void **ws, size_t *have, size_t need)
-{
-    if (need <= *have) return SR_OK;
-    if (*ws) {
-        HIPCHK(stream_sync(ctx));
-        HIPCHK(hipFree(*ws));
-        *ws = nullptr;
-        *have = 0;
-    }
-    const hipError_t e = hipMalloc(ws, need);
-    if (e != hipSuccess) {
-        *ws = nullptr;
-        return sr_set_error(e == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, "%s: scratch of %zu bytes: %s", scope, need,
-                            hipGetErrorString(e));
-    }
-    *have = need;
-    return SR_OK;
 }

@@ -461,8 +461,8 @@ static int extract_impl(sr_ctx *ctx, const uint8_t *d_img, int img_h, int img_w,
         mw = std::max(mw, d.out_w);
         mh = std::max(mh, d.out_h);
     }
-    HIPCHK(upload_cached(ctx, ctx->extract_tab, descs.data(), sizeof(ExtractDesc) * n));
-    const void *scr = ctx->extract_tab.d;
+    SRCHK(upload_cached(ctx, ctx->extract_tab, descs.data(), sizeof(ExtractDesc) * n));
+    const void *scr = ctx->extract_tab.buf.d;
     {
         ProfScope ps(ctx, name);
         const long long chunks = ((long long)mw * cn + 15) / 16;
@@ -613,11 +613,10 @@ int sr_feather_merge_dt(sr_ctx *ctx, int dtype, const sr_merge_tile *h_tiles, in
         if (h_strides[t] < (int64_t)m.src_w * 3 * es) return sr_set_error(SR_ERR_SHAPE, "sr_feather_merge: tile %d stride too small", t);
     }
     const size_t b0 = sizeof(MergeDev) * (size_t)n, b1 = sizeof(TileSrc) * (size_t)n, b2 = sizeof(LinTab) * tabs.size();
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     void *scr = nullptr;
-    int rc = ctx_scratch(ctx, al(b0) + al(b1) + al(b2) + 256, &scr);
+    int rc = ctx_scratch(ctx, up256(b0) + up256(b1) + up256(b2) + 256, &scr);
     if (rc) return rc;
-    char *p0 = (char *)scr, *p1 = p0 + al(b0), *p2 = p1 + al(b1);
+    char *p0 = (char *)scr, *p1 = p0 + up256(b0), *p2 = p1 + up256(b1);
     if (n > 0) {
         HIPCHK(upload_small(ctx, p0, md.data(), b0));
         HIPCHK(upload_small(ctx, p1, srcs.data(), b1));
