@@ -695,6 +695,65 @@ SR_API int sr_niqe_fit(const double *feat, const double *sharp, const int64_t *i
 /* Host only.  The score of nblocks feature rows under (mu_pris[36], cov_pris[36 x 36]); NaN (and sr_last_error) for null
  * pointers or fewer than two NaN-free rows. */
 SR_API double sr_niqe_score(const double *feat, int64_t nblocks, const double *mu_pris, const double *cov_pris);
+/* ---- BRISQUE, the no-reference quality model (csrc/sr_brisque.hip, csrc/sr_brisque_host.cpp) ----------------------------------
+ * Mittal, Moorthy, Bovik 2012, in the arithmetic of MATLAB's brisque_feature.m / brisquescore.m and pyiqa's brisque, made
+ * exact wherever it can be.  The reference's calculate_brisque asks pyiqa for this model first; the 'brisque' key of the
+ * reports is its fallback heuristic and is NOT this number.  The model is an RBF epsilon-SVR over 36 scaled features: the
+ * caller supplies it (nothing is fetched and none ships).
+ * PARITY UNPINNED with MATLAB, pyiqa and piq: none of them is available offline, and neither are allmodel / allrange.  Known
+ * distances, unmeasured here: pyiqa scales by / 255 ... * 255 around the resize where the plane here is exact; the 2-D window
+ * is applied in one pass elsewhere and is separable here; an implementation that replicates the border instead of
+ * zero-padding differs in a 3-pixel rim.  OpenCV's QualityBRISQUE (non-antialiased bicubic, non-circular shifts) is a
+ * different definition and out of scope.  The flat-neighbourhood caveat of NIQE applies unchanged: where a 7 x 7
+ * neighbourhood is exactly flat, G * I^2 - mu^2 is rounding noise of either sign and m with it.
+ * All arithmetic is float64 without contraction.
+ *   plane    cn = 3: NIQE's luma (SR_BENCH_Y_ROUND's formula); cn = 1: the plane as it is.  crop_border pixels per side are
+ *            cropped by pointer arithmetic, giving H x W; the whole crop is used (no multiple-of-96 rule).  H < 16 or W < 16
+ *            after the crop is SR_ERR_SHAPE: scale 2 (at least 8 x 8) still holds a whole 7-tap window.
+ *   scale 2  NIQE's imresize(., 0.5): taps {-3, -9, 29, 111, 111, 29, -9, -3} / 256, output i reads inputs 2 i - 3 .. 2 i + 4,
+ *            symmetric reflection (one reflection reaches every index once a side is >= 16), rows first, then columns.  The
+ *            output is H2 = ceil(H / 2) by W2 = ceil(W / 2), MATLAB's output size; it is kept as int32 = 65536 x the value,
+ *            exact.
+ *   MSCN     NIQE's window k_i, separable: horizontal pass, then vertical pass, taps added in ascending index order.  The
+ *            border is ZERO, as in MATLAB's filter2(window, I, 'same'): a tap outside the plane contributes an exact 0.
+ *            mu, sigma = sqrt(|G * I^2 - mu^2|), m = (I - mu) / (sigma + 1) as for NIQE.
+ *   products X_0 = m and X_s = m * roll(m, shift_s) for the shifts (0, 1), (1, 0), (1, 1), (1, -1), NIQE's order and roll
+ *            convention, but circular over the WHOLE plane of that scale.  MATLAB's fourth shift is (-1, 1); under a circular
+ *            roll m * roll(m, (-1, 1)) is roll(m * roll(m, (1, -1)), (-1, 1)): the same multiset of products, the same moments.
+ *   record   per scale n = H_s W_s and five sr_niqe_moments.  Counts are exact.  Sums: per-workgroup partials into context
+ *            scratch, then one fixed tree over them whose shape depends on the call shape only.  No floating-point atomics:
+ *            equal inputs give equal bits.
+ *   features 18 per scale, scale 1 then scale 2.  X_0, a GGD fit: s2 = (ssq_neg + ssq_pos) / n, E = sabs / n, alpha = the
+ *            entry of gam = 0.2 + 0.001 t, t = 0 .. 9800, that minimises |Gamma(1 / gam) Gamma(3 / gam) / Gamma(2 / gam)^2 -
+ *            s2 / E^2| (the first on a tie): [alpha, s2], NaN for sabs = 0.  Each shift: NIQE's AGGD fit (same table, same
+ *            argmin; n counts every element, zeros included; ls, rs as there): [alpha, (rs - ls) (Gamma(2 / alpha) /
+ *            Gamma(1 / alpha)) (sqrt(Gamma(1 / alpha)) / sqrt(Gamma(3 / alpha))), ls^2, rs^2], NaN for n_neg = 0 or n_pos = 0.
+ *   score    x_k = lower + (upper - lower)(f_k - min_k) / (max_k - min_k), not clamped; x_k = 0 where max_k = min_k (svm-scale
+ *            drops such a feature).  score = sum_i coef_i exp(-gamma sum_k (sv_ik - x_k)^2) - rho, support vectors and
+ *            features ascending.  NaN for any NaN feature. */
+typedef struct sr_brisque_record {
+    uint64_t n;                 /* H_s * W_s */
+    sr_niqe_moments x[5];       /* X_0 = m, then the four shifted products in the order above */
+} sr_brisque_record;
+/* Host only, no context: the cropped size, the half plane's size and the bytes of context scratch a call will hold (each
+ * output may be NULL).  Carries every shape refusal: SR_ERR_INVALID_ARG for cn not 1 or 3, crop_border < 0, h or w < 1;
+ * SR_ERR_SHAPE for a side below 16 after the crop. */
+SR_API int sr_brisque_plan(int h, int w, int cn, int crop_border, int *H, int *W, int *H2, int *W2, size_t *scratch_bytes);
+/* One read of the image for the half plane, then one launch per scale: a workgroup owns a 64 x 64 tile of m.  h_out: two
+ * records, scale 1 then scale 2.  Strides in bytes, arbitrary (>= a row).  Synchronous; the half plane and the partials are
+ * context scratch, grown on demand.  Refused before any device call: null pointers, everything sr_brisque_plan refuses, a
+ * stride shorter than a row of the uncropped image (SR_ERR_SHAPE). */
+SR_API int sr_brisque_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, int cn, int crop_border,
+                         sr_brisque_record *h_out);
+/* The half plane (65536 x the scale-2 plane, dense H2 x W2) the context's last completed sr_brisque_u8 call left in its
+ * scratch, for inspection. */
+SR_API int sr_brisque_half_plane(sr_ctx *ctx, int32_t *h_out);
+/* Host only.  records: the two records of sr_brisque_u8; feat36: 36 values. */
+SR_API int sr_brisque_features(const sr_brisque_record *records, double *feat36);
+/* Host only.  sv: n_sv x 36 row-major, coef: n_sv, fmin / fmax: 36.  NaN (and sr_last_error) for null pointers, n_sv < 1, a
+ * gamma that is not finite and positive; NaN for any NaN feature. */
+SR_API double sr_brisque_score(const double *feat36, const double *sv, const double *coef, int64_t n_sv, double gamma, double rho,
+                               const double *fmin, const double *fmax, double lower, double upper);
 /* cv2.cvtColor(RGB2GRAY) on u8 (quality_assessment_module.py:359-360) */
 SR_API int sr_rgb2gray_u8(sr_ctx *ctx, const uint8_t *d_rgb, int64_t stride, int h, int w,
                           int gray_shift, uint8_t *d_gray, int64_t gray_stride);

@@ -91,6 +91,9 @@ class NiqeBlock(C.Structure):
 NIQE_MOMENTS = np.dtype([("n_neg", "<u8"), ("n_pos", "<u8"), ("ssq_neg", "<f8"), ("ssq_pos", "<f8"), ("sabs", "<f8")])
 NIQE_RECORD = np.dtype([("x", NIQE_MOMENTS, (5,)), ("sum_sigma", "<f8")])
 NIQE_BLOCK, NIQE_FEATURES = 96, 36
+# sr_brisque_record (include/sr_hip.h): one per scale
+BRISQUE_RECORD = np.dtype([("n", "<u8"), ("x", NIQE_MOMENTS, (5,))])
+BRISQUE_FEATURES, BRISQUE_MIN_SIDE = 36, 16
 
 MS_SSIM_MAX_LEVELS = 5
 MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
@@ -234,6 +237,11 @@ SIGNATURES = {
     "sr_niqe_features": (_i, [_vp, _i64, _vp]),
     "sr_niqe_fit": (_i, [_vp, _vp, _vp, _i, _dbl, _vp, _vp, C.POINTER(_i64)]),
     "sr_niqe_score": (_dbl, [_vp, _i64, _vp, _vp]),
+    "sr_brisque_plan": (_i, [_i, _i, _i, _i, _pi, _pi, _pi, _pi, C.POINTER(_sz)]),
+    "sr_brisque_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sr_brisque_half_plane": (_i, [_vp, _vp]),
+    "sr_brisque_features": (_i, [_vp, _vp]),
+    "sr_brisque_score": (_dbl, [_vp, _vp, _vp, _i64, _dbl, _dbl, _vp, _vp, _dbl, _dbl]),
     "sr_rgb2gray_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
     "sr_resize_cubic_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i]),
     "sr_resize_cubic_window_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64]),
@@ -665,6 +673,139 @@ def niqe_score(feat, mu_pris, cov_pris) -> float:
                                       cov.ctypes.data_as(C.c_void_p)))
 
 
+def brisque_plan(h: int, w: int, cn: int, crop_border: int = 0) -> dict:
+    """Host only (sr_brisque_plan): the cropped size, the half plane's size (sides rounded up) and the bytes of context scratch
+    of a BRISQUE call.  ValueError for cn not 1 or 3 or a negative crop_border; SrShapeError (a ValueError) naming the minimum
+    for a side below 16 after the crop."""
+    h, w, cn, crop_border = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn"), (crop_border, "crop_border")))
+    H, W, H2, W2, nbytes = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    check(load().sr_brisque_plan(h, w, cn, crop_border, C.byref(H), C.byref(W), C.byref(H2), C.byref(W2), C.byref(nbytes)))
+    return {"size": (H.value, W.value), "half_size": (H2.value, W2.value), "scratch_bytes": int(nbytes.value)}
+
+
+def brisque_features(records: np.ndarray) -> np.ndarray:
+    """Host only (sr_brisque_features): records[2] (BRISQUE_RECORD, scale 1 then scale 2) -> feat[36]."""
+    rec = np.ascontiguousarray(records, dtype=BRISQUE_RECORD)
+    if rec.shape != (2,):
+        raise ValueError(f"brisque_features: records must be [2], got shape {rec.shape}")
+    feat = np.zeros(BRISQUE_FEATURES, dtype=np.float64)
+    check(load().sr_brisque_features(rec.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p)))
+    return feat
+
+
+_BRISQUE_KEYS = ("sv", "sv_coef", "gamma", "rho", "feature_min", "feature_max")
+
+
+def check_brisque_model(model) -> dict:
+    """-> {'sv': float64 (n_sv, 36), 'sv_coef': (n_sv,), 'gamma', 'rho': float, 'feature_min', 'feature_max': (36,), 'lower',
+    'upper': float (default -1, 1)}; ValueError for missing keys, other shapes, n_sv < 1 or a gamma that is not finite and
+    positive (sv_coef may come as (n_sv,) or (1, n_sv), libsvm's dual_coef_)."""
+    try:
+        got = {k: model[k] for k in _BRISQUE_KEYS}
+        lower = model["lower"] if "lower" in model else -1.0
+        upper = model["upper"] if "upper" in model else 1.0
+    except (KeyError, TypeError, IndexError) as exc:
+        raise ValueError("a BRISQUE model needs the keys " + ", ".join(repr(k) for k in _BRISQUE_KEYS)) from exc
+    sv = np.asarray(got["sv"], dtype=np.float64)
+    if sv.ndim != 2 or sv.shape[1] != BRISQUE_FEATURES or sv.shape[0] < 1:
+        raise ValueError(f"BRISQUE model: sv must have shape (n_sv >= 1, 36), got {sv.shape}")
+    coef = np.asarray(got["sv_coef"], dtype=np.float64)
+    if coef.shape not in ((sv.shape[0],), (1, sv.shape[0])):
+        raise ValueError(f"BRISQUE model: sv_coef must have shape ({sv.shape[0]},) or (1, {sv.shape[0]}), got {coef.shape}")
+    out = {"sv": np.ascontiguousarray(sv), "sv_coef": np.ascontiguousarray(coef.reshape(-1))}
+    for k in ("gamma", "rho", "lower", "upper"):
+        v = np.asarray({"lower": lower, "upper": upper}.get(k, got.get(k)), dtype=np.float64)
+        if v.size != 1 or not np.isfinite(v).all():
+            raise ValueError(f"BRISQUE model: {k} must be one finite number")
+        out[k] = float(v.reshape(-1)[0])
+    if not out["gamma"] > 0.0:
+        raise ValueError(f"BRISQUE model: gamma must be positive (got {out['gamma']})")
+    for k in ("feature_min", "feature_max"):
+        v = np.asarray(got[k], dtype=np.float64)
+        if v.shape not in ((BRISQUE_FEATURES,), (1, BRISQUE_FEATURES)):
+            raise ValueError(f"BRISQUE model: {k} must have shape (36,) or (1, 36), got {v.shape}")
+        out[k] = np.ascontiguousarray(v.reshape(-1))
+    return out
+
+
+def brisque_score(feat, model) -> float:
+    """Host only (sr_brisque_score): the score of feat[36] under a model (check_brisque_model's form); NaN for any NaN
+    feature.  ValueError for wrong shapes."""
+    m = check_brisque_model(model)
+    f = _f64(np.asarray(feat, dtype=np.float64).reshape(-1), (BRISQUE_FEATURES,), "brisque_score: features")
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    return float(load().sr_brisque_score(p(f), p(m["sv"]), p(m["sv_coef"]), m["sv"].shape[0], m["gamma"], m["rho"],
+                                         p(m["feature_min"]), p(m["feature_max"]), m["lower"], m["upper"]))
+
+
+def save_brisque_model(path: str, model) -> None:
+    """A flat .npz: sv, sv_coef, gamma, rho, feature_min, feature_max, lower, upper."""
+    m = check_brisque_model(model)
+    if not str(path).lower().endswith(".npz"):
+        raise ValueError(f"BRISQUE model files are .npz, got {path!r}")
+    with open(str(path), "wb") as f:
+        np.savez(f, **{k: np.asarray(v, dtype=np.float64) for k, v in m.items()})
+
+
+def load_brisque_model(path: str) -> dict:
+    """Reads what save_brisque_model writes (lower / upper optional, default -1 / 1); nothing is unpickled."""
+    if not str(path).lower().endswith(".npz"):
+        raise ValueError(f"BRISQUE model files are .npz, got {path!r}")
+    with np.load(str(path), allow_pickle=False) as z:
+        missing = [k for k in _BRISQUE_KEYS if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: no {' / '.join(missing)}")
+        return check_brisque_model({k: z[k] for k in z.files if k in _BRISQUE_KEYS + ("lower", "upper")})
+
+
+def brisque_model_from_libsvm(model_path: str, range_path: str) -> dict:
+    """A model from libsvm's text model file (svm-train's output) and svm-scale's range file.  Only svm_type epsilon_svr with
+    kernel_type rbf is BRISQUE's regressor: anything else is refused by name.  Support vectors are sparse index:value lists
+    (1-based, absent = 0); a feature absent from the range file was constant in training (feature_min = feature_max)."""
+    header, sv, coef = {}, [], []
+    with open(str(model_path)) as f:
+        lines = [ln.strip() for ln in f if ln.strip()]
+    if "SV" not in lines:
+        raise ValueError(f"{model_path}: no SV section")
+    at = lines.index("SV")
+    for ln in lines[:at]:
+        key, _, val = ln.partition(" ")
+        header[key] = val.strip()
+    if header.get("svm_type") != "epsilon_svr":
+        raise ValueError(f"{model_path}: svm_type {header.get('svm_type')!r} is not supported (need epsilon_svr)")
+    if header.get("kernel_type") != "rbf":
+        raise ValueError(f"{model_path}: kernel_type {header.get('kernel_type')!r} is not supported (need rbf)")
+    for key in ("gamma", "rho"):
+        if key not in header:
+            raise ValueError(f"{model_path}: no {key}")
+    for ln in lines[at + 1:]:
+        parts = ln.split()
+        row = np.zeros(BRISQUE_FEATURES)
+        for item in parts[1:]:
+            idx, _, val = item.partition(":")
+            k = int(idx)
+            if not 1 <= k <= BRISQUE_FEATURES:
+                raise ValueError(f"{model_path}: feature index {k} outside 1 .. 36")
+            row[k - 1] = float(val)
+        coef.append(float(parts[0]))
+        sv.append(row)
+    if "total_sv" in header and int(header["total_sv"]) != len(sv):
+        raise ValueError(f"{model_path}: total_sv {header['total_sv']} but {len(sv)} support vectors")
+    with open(str(range_path)) as f:
+        rl = [ln.split() for ln in f if ln.strip()]
+    if len(rl) < 2 or rl[0] != ["x"] or len(rl[1]) != 2:
+        raise ValueError(f"{range_path}: not an svm-scale range file of the features ('x', then 'lower upper')")
+    fmin, fmax = np.zeros(BRISQUE_FEATURES), np.zeros(BRISQUE_FEATURES)
+    for parts in rl[2:]:
+        k = int(parts[0])
+        if len(parts) != 3 or not 1 <= k <= BRISQUE_FEATURES:
+            raise ValueError(f"{range_path}: bad line {' '.join(parts)!r}")
+        fmin[k - 1], fmax[k - 1] = float(parts[1]), float(parts[2])
+    return check_brisque_model({"sv": np.array(sv).reshape(-1, BRISQUE_FEATURES), "sv_coef": np.array(coef),
+                                "gamma": float(header["gamma"]), "rho": float(header["rho"]), "feature_min": fmin,
+                                "feature_max": fmax, "lower": float(rl[1][0]), "upper": float(rl[1][1])})
+
+
 def psnr_from_sse(sse: int, count: int, data_range: float = 255.0) -> float:
     return float(load().sr_psnr_from_sse(C.c_uint64(sse), C.c_uint64(count), data_range))
 
@@ -929,6 +1070,25 @@ class Context:
         scratch; shape = (H / 2, W / 2) of that call's niqe_plan size."""
         out = np.zeros(shape, dtype=np.int32)
         check(self.lib.sr_niqe_half_plane(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def brisque_u8(self, d_img, stride, h, w, cn, crop_border=0) -> np.ndarray:
+        """sr_brisque_u8 -> records[2] (BRISQUE_RECORD, scale 1 then scale 2) of the image cropped by crop_border (finish with
+        brisque_features and brisque_score).  Every argument is checked before the device is touched: ValueError, or its
+        subclass SrShapeError for a short stride or a side below 16 after the crop."""
+        if not d_img:
+            raise ValueError("brisque_u8: null image pointer")
+        brisque_plan(h, w, cn, crop_border)
+        rec = np.zeros(2, dtype=BRISQUE_RECORD)
+        check(self.lib.sr_brisque_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w), int(cn), int(crop_border),
+                                     rec.ctypes.data_as(C.c_void_p)))
+        return rec
+
+    def brisque_half_plane(self, shape) -> np.ndarray:
+        """sr_brisque_half_plane: 65536 x the scale-2 plane (int32, exact) that the last brisque_u8 call of this context left
+        in its scratch; shape = that call's brisque_plan half_size."""
+        out = np.zeros(shape, dtype=np.int32)
+        check(self.lib.sr_brisque_half_plane(self.handle, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def ms_ssim_planes(self, level: int, shape) -> Tuple[np.ndarray, np.ndarray]:

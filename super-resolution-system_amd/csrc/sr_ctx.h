@@ -102,10 +102,12 @@ struct sr_ctx {
     DevBuf bench_ws;                                    // SR-benchmark PSNR / SSIM: per-block partials
     DevBuf niqe_ws;                                     // NIQE: the int32 half plane, then the block records
     int niqe_H = 0, niqe_W = 0;                         // the kept plane whose half plane the scratch holds (0: nothing valid)
+    DevBuf brisque_ws;                                  // BRISQUE: the int32 half plane, then the per-tile partials
+    int brisque_H2 = 0, brisque_W2 = 0;                 // the half plane the scratch holds (0: nothing valid)
     // Frees every device buffer above; sr_ctx_destroy calls it with the stream drained and the device current.
     void release_device()
     {
-        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws})
+        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws, &brisque_ws})
             b->release();
     }
 };

@@ -37,15 +37,6 @@ struct NqWindow {
 };
 
 template <int PX>
-__device__ __forceinline__ unsigned nq_luma(const unsigned char *p)
-{
-    if constexpr (PX == 3)                  // MATLAB's uint8 rgb2ycbcr (SR_BENCH_Y_ROUND): half up, 16 .. 235
-        return (2u * (65481u * p[0] + 128553u * p[1] + 24966u * p[2] + 4080000u) + 255000u) / 510000u;
-    else
-        return p[0];
-}
-
-template <int PX>
 __global__ __launch_bounds__(NH_T) void k_niqe_half(const unsigned char *__restrict__ img, long long stride, int H, int W,
                                                     int *__restrict__ out)
 {

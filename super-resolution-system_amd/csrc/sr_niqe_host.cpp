@@ -12,54 +12,9 @@
 namespace {
 
 constexpr int F = NQ_FEAT;
-constexpr int GAM_N = 9801;                 // gam = 0.2 + 0.001 t, t = 0 .. 9800
 constexpr int MIN_FIT_ROWS = F + 1;         // a sample covariance of 36 features has full rank from 37 rows on
 
-
-double gam_at(int t) { return 0.2 + 0.001 * (double)t; }
-
-// Gamma(2 / gam)^2 / (Gamma(1 / gam) Gamma(3 / gam)) over the grid, built once
-struct GamTable {
-    std::vector<double> r;
-    bool ascending = true;
-    GamTable() : r(GAM_N)
-    {
-        for (int t = 0; t < GAM_N; ++t) {
-            const double g = gam_at(t), g2 = std::tgamma(2.0 / g);
-            r[t] = g2 * g2 / (std::tgamma(1.0 / g) * std::tgamma(3.0 / g));
-            if (t && !(r[t] > r[t - 1])) ascending = false;
-        }
-    }
-};
-
-const GamTable &gam_table()
-{
-    static const GamTable T;
-    return T;
-}
-
-// argmin_t (r[t] - R)^2, the first on a tie.  The table ascends strictly, so the minimum lies beside R's insertion point: the
-// same squared differences are compared there as a scan of the whole table would compare (which is what runs if it did not).
-int gam_argmin(double R)
-{
-    const GamTable &T = gam_table();
-    int lo = 0, hi = GAM_N - 1;
-    if (T.ascending) {
-        const int p = (int)(std::lower_bound(T.r.begin(), T.r.end(), R) - T.r.begin());
-        lo = std::max(p - 2, 0);
-        hi = std::min(p + 2, GAM_N - 1);
-    }
-    int best = lo;
-    double bd = (T.r[lo] - R) * (T.r[lo] - R);
-    for (int t = lo + 1; t <= hi; ++t) {
-        const double d = (T.r[t] - R) * (T.r[t] - R);
-        if (d < bd) {
-            bd = d;
-            best = t;
-        }
-    }
-    return best;
-}
+// the Gamma-ratio table and its argmin are sr_niqe.h's (BRISQUE's fits read the same table)
 
 struct Aggd {
     double alpha, beta_l, beta_r;
@@ -76,7 +31,7 @@ Aggd aggd_fit(const sr_niqe_moments &m, double n)
     const double g2 = g * g;
     const double R = rhat * (g2 * g + 1.0) * (g + 1.0) / ((g2 + 1.0) * (g2 + 1.0));
     if (!(R == R)) return {nan, nan, nan};
-    const double alpha = gam_at(gam_argmin(R));
+    const double alpha = nq_gam_at(nq_gam_argmin(R));
     const double s = std::sqrt(std::tgamma(1.0 / alpha) / std::tgamma(3.0 / alpha));
     return {alpha, ls * s, rs * s};
 }

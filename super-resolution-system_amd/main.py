@@ -72,6 +72,8 @@ class PipelineConfig:
                                # the DISTS of the canvas against the INTER_CUBIC resize of the source ('dists')
     qa_niqe_params: str = ""   # (with enable_qa): path of NIQE's pristine parameters (.npz with BasicSR's keys, or .mat): stage 4 also
                                # reports the NIQE of the canvas ('niqe_model'; the 'niqe' key keeps the reference's stand-in heuristic)
+    qa_brisque_model: str = "" # (with enable_qa): path of a BRISQUE regressor (.npz: sv, sv_coef, gamma, rho, feature_min, feature_max): stage 4
+                               # also reports the BRISQUE of the canvas ('brisque_model'; the 'brisque' key keeps the reference's stand-in)
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
                                    # only the canvas comes back for the writer (a custom sr_backend gets host arrays)
     sr_weights: str = ""       # path of an SR network's weights (.npz, or .pth / .pt where torch imports): stage 2 runs the
@@ -120,6 +122,7 @@ class SuperResolutionPipeline:
         self.blending_module = BlendingModule(method=config.blend_method, num_levels=config.num_pyramid_levels)
         self.quality_module = QualityAssessmentModule(device=config.qa_device)
         self._niqe_params = None       # qa_niqe_params, read at the first use
+        self._brisque_model = None     # qa_brisque_model, read at the first use
         self._dists_model = None       # qa_dists_weights, loaded at the first use
         self.sr_net = None
         if config.sr_ensemble != 1:
@@ -282,6 +285,23 @@ class SuperResolutionPipeline:
         finally:
             ctx.sync()
 
+    def _brisque_model_entry(self, ctx, report: Dict[str, Any], d_canvas: int, canvas_shape) -> None:
+        """Stage 4's optional 'brisque_model' entry (qa_brisque_model): the BRISQUE of the canvas in HBM (no crop) under the
+        regressor of the configured file.  Not the 'brisque' key of the commercial section, which is the reference's
+        stand-in.  A canvas with a side below 16, or with a NaN feature, has no score: the entry is None and
+        'brisque_model_note' says why (the run does not fail).  One helper for the device-resident, the host-array and the
+        sharded path."""
+        import quality_assessment_module as qam
+        if self._brisque_model is None:
+            self._brisque_model = qam.load_brisque_model(self.config.qa_brisque_model)
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        try:
+            report['brisque_model'] = float(self.quality_module.calculate_brisque_model_device(d_canvas, (H, W, cn), self._brisque_model))
+        except ValueError as exc:
+            report['brisque_model'], report['brisque_model_note'] = None, str(exc)
+        finally:
+            ctx.sync()
+
     def _quality_map(self, ctx, d_src: int, src_shape, d_canvas: int, canvas_shape, tiles: List[Tile],
                      output_path: str) -> Dict[str, Any]:
         """Stage 4's optional 'quality_map' section (qa_map_cell > 0): where the canvas differs from the INTER_CUBIC resize
@@ -412,6 +432,8 @@ class SuperResolutionPipeline:
                     self._sr_benchmark(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_niqe_params:
                     self._niqe_model(ctx, report, canvas.ptr, (H, W, 3))
+                if self.config.qa_brisque_model:
+                    self._brisque_model_entry(ctx, report, canvas.ptr, (H, W, 3))
                 if self.config.qa_dists_weights:
                     self._dists(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 score = qa.get('overall_score', 0)
@@ -513,6 +535,8 @@ class SuperResolutionPipeline:
                         self._sr_benchmark(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_niqe_params:
                         self._niqe_model(qctx, report, canvas.data_ptr(), (H, W, 3))
+                    if self.config.qa_brisque_model:
+                        self._brisque_model_entry(qctx, report, canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_dists_weights:
                         self._dists(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     score = qa.get('overall_score', 0)
@@ -616,6 +640,13 @@ class SuperResolutionPipeline:
                         self._niqe_model(qctx, report, d_fused.ptr, fused.shape)
                     finally:
                         d_fused.free()
+                if self.config.qa_brisque_model:
+                    qctx = self.quality_module._ctx()
+                    d_fused = qctx.upload(fused)
+                    try:
+                        self._brisque_model_entry(qctx, report, d_fused.ptr, fused.shape)
+                    finally:
+                        d_fused.free()
                 if self.config.qa_dists_weights:
                     qctx = self.quality_module._ctx()
                     d_src, d_fused = qctx.upload(original), qctx.upload(fused)
@@ -671,6 +702,9 @@ async def main() -> int:
     ap.add_argument("--qa-niqe-params", default="", metavar="PATH",
                     help="NIQE's pristine parameters (.npz with the keys mu_pris_param / cov_pris_param, or .mat): stage 4 also "
                          "reports the NIQE of the result (report key niqe_model; the key niqe stays the stand-in heuristic)")
+    ap.add_argument("--qa-brisque-model", default="", metavar="PATH",
+                    help="a BRISQUE regressor (.npz with the keys sv, sv_coef, gamma, rho, feature_min, feature_max): stage 4 also "
+                         "reports the BRISQUE of the result (report key brisque_model; the key brisque stays the stand-in heuristic)")
     ap.add_argument("--qa-dists-weights", default="", metavar="PATH",
                     help="DISTS weights (.npz with the VGG16 convolutions stageN.K.weight / .bias, or features.K.*, and alpha / "
                          "beta): stage 4 also reports the DISTS of the result against the bicubic resize of the input (report "
@@ -696,7 +730,7 @@ async def main() -> int:
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act, sr_ensemble=args.sr_ensemble,
                          qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark,
-                         qa_niqe_params=args.qa_niqe_params, qa_dists_weights=args.qa_dists_weights)
+                         qa_niqe_params=args.qa_niqe_params, qa_brisque_model=args.qa_brisque_model, qa_dists_weights=args.qa_dists_weights)
     if args.plan_only:
         from PIL import Image
         with Image.open(args.input) as im:

@@ -30,6 +30,10 @@ NIQE proper (no reference counterpart in code: the reference asks pyiqa for it):
 ``niqe_features`` / ``fit_niqe_model`` run the model of Mittal et al. as include/sr_hip.h defines it (csrc/sr_niqe.hip), with
 pristine parameters the caller supplies or fits.  ``calculate_niqe`` and the 'niqe' report key stay the reference's MSCN
 stand-in: another number under a similar name.
+
+BRISQUE proper, likewise: ``calculate_brisque_model`` / ``brisque_features`` run the model of Mittal, Moorthy and Bovik as
+include/sr_hip.h defines it (csrc/sr_brisque.hip) under an RBF epsilon-SVR the caller supplies (``load_brisque_model``,
+``brisque_model_from_libsvm``; none ships).  ``calculate_brisque`` and the 'brisque' report key stay the reference's stand-in.
 u8 HxW, HxWx3 and HxWx4 (alpha ignored) images only; an image side above the FFT's longest line (32768) raises
 NotImplementedError before any device work.
 """
@@ -497,6 +501,59 @@ class QualityAssessmentModule:
             raise ValueError("calculate_niqe_model: null device pointer")
         feat, _ = self._niqe_features_dev(self._ctx(), int(d_image), args)
         return self._niqe_value(feat, params)
+
+    # -- BRISQUE, the model (no reference counterpart in code: the reference delegates to pyiqa.create_metric('brisque')) ----
+    @staticmethod
+    def _brisque_args(shape, crop_border) -> Tuple[int, int, int, int]:
+        """Every refusal of the BRISQUE methods, on the host: ValueError (SrShapeError for a side below 16 after the crop).
+        -> (h, w, cn, crop_border)."""
+        shape = tuple(int(v) for v in shape)
+        if len(shape) not in (2, 3):
+            raise ValueError(f"brisque: need an H x W or H x W x C image, got shape {shape}")
+        cn = shape[2] if len(shape) == 3 else 1
+        if cn not in (1, 3):
+            raise ValueError("brisque: colour images must have 3 channels (RGB)")
+        _native.brisque_plan(shape[0], shape[1], cn, crop_border)                 # crop_border < 0, a too-small crop
+        return shape[0], shape[1], cn, int(crop_border)
+
+    @staticmethod
+    def _brisque_features_dev(ctx, d_img: int, args) -> np.ndarray:
+        h, w, cn, cb = args
+        return _native.brisque_features(ctx.brisque_u8(d_img, w * cn, h, w, cn, crop_border=cb))
+
+    def brisque_features(self, image: np.ndarray, crop_border: int = 0) -> np.ndarray:
+        """The 36 BRISQUE features of a u8 image (RGB: on MATLAB's rounded u8 luma), as include/sr_hip.h defines them: 18 per
+        scale over the whole cropped plane.  -> feat[36]; a fit without samples on one side is NaN."""
+        a = self._require_u8(np.asarray(image), "brisque_features")
+        args = self._brisque_args(a.shape, crop_border)
+        ctx = self._ctx()
+        d = _DevImage(ctx, a)
+        try:
+            return self._brisque_features_dev(ctx, d.ptr, args)
+        finally:
+            d.free()
+
+    @staticmethod
+    def _brisque_value(feat: np.ndarray, model) -> float:
+        if np.isnan(feat).any():
+            raise _native.SrShapeError("brisque: a feature is NaN (a fit without samples on one side of 0): the image has no score")
+        return _native.brisque_score(feat, model)
+
+    def calculate_brisque_model(self, image: np.ndarray, model, crop_border: int = 0) -> float:
+        """BRISQUE (Mittal, Moorthy, Bovik 2012; the arithmetic of MATLAB's brisquescore and pyiqa's brisque) of a u8 image
+        under the caller's RBF epsilon-SVR (load_brisque_model / brisque_model_from_libsvm; nothing is fetched, none ships).
+        Lower is better.  NOT calculate_brisque, which is the reference's stand-in.  A side below 16 after the crop, or a
+        NaN feature, is a ValueError (SrShapeError)."""
+        model = _native.check_brisque_model(model)
+        return self._brisque_value(self.brisque_features(image, crop_border), model)
+
+    def calculate_brisque_model_device(self, d_image: int, shape, model, crop_border: int = 0) -> float:
+        """calculate_brisque_model on a dense u8 image that already lives in HBM (device address + shape)."""
+        model = _native.check_brisque_model(model)
+        args = self._brisque_args(shape, crop_border)
+        if not d_image:
+            raise ValueError("calculate_brisque_model: null device pointer")
+        return self._brisque_value(self._brisque_features_dev(self._ctx(), int(d_image), args), model)
 
     def _calculate_ssim_simple(self, img1: np.ndarray, img2: np.ndarray) -> float:
         """quality_assessment_module.py:391-417 on already-gray u8 images."""
@@ -1212,6 +1269,13 @@ def load_niqe_params(path: str) -> Dict[str, np.ndarray]:
                 raise ValueError(f"{path}: no mu_pris_param / cov_pris_param")
             return check_niqe_params({"mu_pris_param": z["mu_pris_param"], "cov_pris_param": z["cov_pris_param"]})
     raise ValueError(f"NIQE parameter files are .npz or .mat, got {path!r}")
+
+
+# -- the regressor of BRISQUE: check, save, load, read libsvm's files (the code is _native's) -------------------------------------
+check_brisque_model = _native.check_brisque_model
+save_brisque_model = _native.save_brisque_model
+load_brisque_model = _native.load_brisque_model
+brisque_model_from_libsvm = _native.brisque_model_from_libsvm
 
 
 def _lab_tables_b() -> Tuple[np.ndarray, np.ndarray]:
