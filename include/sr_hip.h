@@ -1019,6 +1019,81 @@ SR_API int sr_rrdb_u8(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_st
 SR_API int sr_rrdb_f32(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
                        int64_t dst_stride, int tile, int tail);
 
+/* ---- local SR backend: RCAN, residual channel attention (csrc/sr_rcan.hip) --------------------------------------------------
+ * BasicSR's RCAN (Zhang et al., ECCV 2018) at scales 1 .. 4, restated (parity with the BasicSR package is unpinned: neither it
+ * nor a checkpoint exists offline).  Convolutions are fp32 in, fp32 accumulate, 3 x 3, stride 1, zero padding 1 at the true image
+ * border, with bias; the channel attention is float64.  A model is an sr_rcan_desc:
+ *     F = n_feat in {64, 128, 192, 256};  R = n_squeeze, 1 <= R <= F (BasicSR: F / 16);  G = n_groups, 1 <= G <= 16;
+ *     B = n_blocks per group, 0 <= B <= 32;  s = scale in {1, 2, 3, 4};  res_scale;  mean[3], range.
+ *  1. input      x[c] = (u8 / 255 - mean[c]) * range (fp32: one division, one subtraction, one product); zero is padded
+ *                after this step.
+ *  2. head       h = conv_first(x), 3 -> F, no activation.
+ *  3. groups     t_0 = h;  group g = 1 .. G takes u = t_{g-1} through its B blocks (RCABs), then t_g = conv_g(u_B) + u_0 (one
+ *                fp32 add, u_0 the group's input).  An RCAB on input u:
+ *                    y1 = relu(conv_a(u)), relu(y) = y > 0 ? y : +0;   y2 = conv_b(y1);
+ *                    m[c]  = (float)(S[c] / (double)(h w)),  S[c] = the float64 sum of y2[c] over exactly the h w pixels of the
+ *                            image, in the order below;
+ *                    z1[j] = max(b1[j] + sum_c w1[j][c] m[c], 0),  j < R;     z[c] = b2[c] + sum_j w2[c][j] z1[j]
+ *                            (float64 from the fp32 tables and the fp32 m, index ascending, every term one rounded float64
+ *                            product and one rounded float64 add; the first layer's products are exact);
+ *                    s[c]  = (float)(1 / (1 + exp(-z[c])))  (float64 exp; a restatement's libm may differ from the device's in
+ *                            the last place of s);
+ *                    out   = fmaf(res_scale, (float)(y2 * s[c]), u)  (the product rounded to fp32, then one fmaf).
+ *                The order of S[c]: the rows are cut into chunks of 32.  Inside a chunk, 256 lane sums: lane t adds rows ascending
+ *                and, within a row, columns t, t + 256, .. ascending; the lane sums are folded a[t] += a[t + k] for
+ *                k = 128, 64, .. 1; the chunks' sums are added in ascending order.  All float64, no atomics: the order depends on
+ *                (h, w) alone.
+ *  4. long skip  f = conv_after_body(t_G) + h  (one fp32 add).
+ *  5. upsampling s = 4: two stages with r = 2;  s in {2, 3}: one stage with r = s;  s = 1: none.  A stage is conv F -> F r^2,
+ *                PixelShuffle(r):  u[c, Y, X] = v[c r^2 + (Y % r) r + (X % r), Y / r, X / r]  (no activation).
+ *  6. last conv  y = conv_last(.), F -> 3 at full resolution.
+ *  7. output     o[c] = y[c] / range + mean[c]  (one division, one add).  Stored as HWC fp32 unclamped (sr_rcan_f32) or as HWC u8
+ *                rintf(fminf(fmaxf(o, 0), 1) * 255) (sr_rcan_u8).
+ * BasicSR's defaults, which a state dict does not hold: res_scale 1, range 255, mean (0.4488, 0.4371, 0.4040).
+ * Anything outside the ranges above (non-finite values, range 0, and x8 with its three shuffle stages included) is
+ * SR_ERR_UNSUPPORTED, decided on the host before any device call.  Out of scope: fp16 / bf16, x8, the original repository's key
+ * names.
+ * Summation order of the 3 x 3 convolutions: bias, then channel pairs (2p, 2p + 1) ascending, then taps ascending, one two-term
+ * MFMA step each (even channel, then odd); head: bias, then channels, then taps, as fmaf.  Equal inputs give equal bits.
+ * The mean makes an output depend on the whole image: the trunk (steps 2 .. 4) runs on the image in ONE piece, in five planar
+ * fp32 buffers of F planes of P0 = h x (w padded to 4) floats (h / f, the group input, t, y1, y2); it is not streamed and there
+ * is no tile argument.  After f nothing is global: steps 5 .. 7 run in tail x tail sub-pieces of the input, every layer's extent
+ * derived backwards from the sub-piece's output rectangle (divided by r rounded outwards across a shuffle, grown by one per
+ * convolution, clipped to the layer's image), in two F-plane buffers of P4 = the largest shuffled extent of a sub-piece.
+ * sr_rcan_create: h_w[k] / h_b[k] = the tables in forward order: conv_first; per group, per RCAB conv_a, conv_b (dense OIHW
+ * fp32), the first 1 x 1 layer (w1 dense [R][F], b1 [R]), the second (w2 dense [F][R], b2 [F]), then the group's convolution;
+ * conv_after_body; the upsampling stages; conv_last.  n_tables must be 1 + G (4 B + 1) + 1 + stages + 1.
+ * sr_rcan_plan (host only, no context, no GPU): *halo = input pixels a tail sub-piece reads beyond its edge (1 at s = 1, 2 at
+ * every other scale); *n_tail_tiles = ceil(h / tail) ceil(w / tail); *workspace_bytes = 4 (5 F P0 + 2 F P4) + 8 F
+ * ceil(h / 32) + 4 F (the buffers, the chunk sums, s).  tail 0: 256.  Outputs may be NULL.
+ * sr_rcan_u8 / sr_rcan_f32: d_src h x w x 3 u8, d_dst (h s) x (w s) x 3; strides in bytes (fp32: a multiple of 4).
+ * sr_rcan_attention_f32 (for inspection; synchronous): the mean and the attention of step 3 on any planar fp32 tensor on the
+ * device, element (c, y, x) at d_x + c plane_stride + y row_stride + 4 x bytes, 1 <= R <= F <= 256; the four tables and the two
+ * results h_mean[F], h_s[F] are host arrays.
+ * SR_ERR_INVALID_ARG for null pointers, a wrong n_tables, a destroyed model and a tail < 0, SR_ERR_SHAPE for h or w < 1, a stride
+ * shorter than a row, an output size beyond int, more than 262140 rows, P0 or P4 above INT_MAX / 8 floats (the convolution's
+ * 32-bit offsets), and trunk buffers 20 F P0 bytes above SR_RCAN_TRUNK_CAP = 16 GiB -- a policy, as SR_RRDB_TRUNK_CAP; the
+ * message names the largest input that fits (F = 64: 1280 bytes per pixel, about 13.4 MP) -- all before any launch.  Every tail
+ * gives the same bits.  Asynchronous, except sr_rcan_attention_f32. */
+#define SR_RCAN_TRUNK_CAP ((size_t)16 << 30)
+typedef struct sr_rcan_desc {
+    int n_feat, n_squeeze, n_groups, n_blocks, scale;
+    float res_scale;
+    float mean[3], range;
+} sr_rcan_desc;
+typedef struct sr_rcan_model sr_rcan_model;
+SR_API int sr_rcan_create(sr_ctx *ctx, const sr_rcan_desc *desc, const float *const *h_w, const float *const *h_b, int n_tables,
+                          sr_rcan_model **out);
+SR_API int sr_rcan_destroy(sr_rcan_model *model);
+SR_API int sr_rcan_plan(const sr_rcan_desc *desc, int h, int w, int tail, int *halo, int *n_tail_tiles, size_t *workspace_bytes);
+SR_API int sr_rcan_u8(sr_rcan_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                      int64_t dst_stride, int tail);
+SR_API int sr_rcan_f32(sr_rcan_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                       int64_t dst_stride, int tail);
+SR_API int sr_rcan_attention_f32(sr_ctx *ctx, const float *d_x, int64_t plane_stride, int64_t row_stride, int n_feat, int n_squeeze,
+                                 int h, int w, const float *h_w1, const float *h_b1, const float *h_w2, const float *h_b2,
+                                 float *h_mean, float *h_s);
+
 /* ---- geometric self-ensemble of the local SR backends (csrc/sr_ensemble.hip) ------------------------------------------------
  * The "+" results of the SR literature (EDSR+, RCAN+: Timofte et al., Lim et al.): the network runs on the eight flips and
  * rotations of the input, each output is mapped back and the eight are averaged.  No new weights; the forwards are the
@@ -1068,6 +1143,12 @@ SR_API int sr_rrdb_ens_u8(sr_rrdb_model *model, const uint8_t *d_src, int64_t sr
                           int64_t dst_stride, int tile, int tail, int mask);
 SR_API int sr_rrdb_ens_f32(sr_rrdb_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
                            int64_t dst_stride, int tile, int tail, int mask);
+/* RCAN+: a flip or a transpose permutes the pixels of every plane, so each member pools over its own planes and nothing else
+ * changes. */
+SR_API int sr_rcan_ens_u8(sr_rcan_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                          int64_t dst_stride, int tail, int mask);
+SR_API int sr_rcan_ens_f32(sr_rcan_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                           int64_t dst_stride, int tail, int mask);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,12 @@ class RrdbDesc(C.Structure):
                 ("res_scale", C.c_float)]
 
 
+class RcanDesc(C.Structure):
+    """sr_rcan_desc (include/sr_hip.h)."""
+    _fields_ = [("n_feat", C.c_int), ("n_squeeze", C.c_int), ("n_groups", C.c_int), ("n_blocks", C.c_int), ("scale", C.c_int),
+                ("res_scale", C.c_float), ("mean", C.c_float * 3), ("range", C.c_float)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("launches", C.c_int64)]
 
@@ -279,6 +285,12 @@ SIGNATURES = {
     "sr_rrdb_plan": (_i, [C.POINTER(RrdbDesc), _i, _i, _i, _i, _pi, _pi, _pi, C.POINTER(_sz)]),
     "sr_rrdb_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
     "sr_rrdb_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_rcan_create": (_i, [_vp, C.POINTER(RcanDesc), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_vp)]),
+    "sr_rcan_destroy": (_i, [_vp]),
+    "sr_rcan_plan": (_i, [C.POINTER(RcanDesc), _i, _i, _i, _pi, _pi, C.POINTER(_sz)]),
+    "sr_rcan_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_rcan_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_rcan_attention_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_d4_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
     "sr_d4_acc_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i64]),
     "sr_ens_finish_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
@@ -290,6 +302,8 @@ SIGNATURES = {
     "sr_resnet_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
     "sr_rrdb_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i, _i]),
     "sr_rrdb_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i, _i]),
+    "sr_rcan_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_rcan_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
 }
 
 
@@ -1869,7 +1883,7 @@ def ens_finish(ctx, d_acc: int, acc_stride: int, H: int, W: int, n: int, d_dst: 
 
 
 class _SrModel:
-    """What SrNetModel, ResNetModel and RrdbModel share: the caller's tables as checked fp32 arrays, the create call, the two
+    """What SrNetModel, ResNetModel, RrdbModel and RcanModel share: the caller's tables as checked fp32 arrays, the create call, the two
     forwards, close.  ``_kind`` names the sr_<kind>_* entry points, ``_run_args`` what their forwards take after the
     destination stride."""
     _kind = ""
@@ -1902,8 +1916,8 @@ class _SrModel:
                                                                 C.c_void_p(d_dst), int(dst_stride), *ints))
 
     def upscale_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, *args, **named):
-        """sr_<kind>_u8: h x w x 3 u8 -> (h s) x (w s) x 3 u8, HBM -> HBM; then ``tile = 0`` (RrdbModel: and ``tail = 0``), by
-        position or by name.  Asynchronous."""
+        """sr_<kind>_u8: h x w x 3 u8 -> (h s) x (w s) x 3 u8, HBM -> HBM; then ``tile = 0`` (RrdbModel: and ``tail = 0``; RcanModel:
+        ``tail = 0`` alone), by position or by name.  Asynchronous."""
         self._run("u8", d_src, src_stride, h, w, d_dst, dst_stride, args, named)
 
     def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, *args, **named):
@@ -2038,6 +2052,75 @@ class RrdbModel(_SrModel):
 
     def plan(self, h: int, w: int, tile: int = 0, tail: int = 0) -> Tuple[int, int, int, int]:
         return rrdb_plan(self.desc, h, w, tile, tail)
+
+
+# ------------------------------------------------------------------------------------------
+# local SR network, RCAN (sr_rcan_*): sr_network.RCANSRNet parses BasicSR state dicts into these arrays
+# ------------------------------------------------------------------------------------------
+def rcan_desc(n_feat: int, n_squeeze: int, n_groups: int, n_blocks: int, scale: int, res_scale: float = 1.0, mean=(0.0, 0.0, 0.0),
+              range: float = 1.0) -> RcanDesc:  # noqa: A002 (the header's name)
+    mean = [float(v) for v in np.asarray(mean, dtype=np.float64).reshape(-1)]
+    if len(mean) != 3:
+        raise ValueError(f"mean holds 3 values, got {len(mean)}")
+    return RcanDesc(int(n_feat), int(n_squeeze), int(n_groups), int(n_blocks), int(scale), float(res_scale), (C.c_float * 3)(*mean),
+                    float(range))
+
+
+def rcan_conv_shapes(desc: RcanDesc) -> List[Tuple[int, int, int]]:
+    """(cout, cin, kernel side) of every table in sr_rcan_create's order: 3 for a 3 x 3 convolution, 1 for one of the two 1 x 1
+    layers of an RCAB's attention."""
+    F, R, s = desc.n_feat, desc.n_squeeze, desc.scale
+    ups = {1: [], 2: [2], 3: [3], 4: [2, 2]}.get(s, [])
+    group = [(F, F, 3), (F, F, 3), (R, F, 1), (F, R, 1)] * desc.n_blocks + [(F, F, 3)]
+    return [(F, 3, 3)] + group * desc.n_groups + [(F, F, 3)] + [(F * r * r, F, 3) for r in ups] + [(3, F, 3)]
+
+
+def rcan_plan(desc: RcanDesc, h: int, w: int, tail: int = 0) -> Tuple[int, int, int]:
+    """sr_rcan_plan (host only) -> (the tail's halo, tail sub-pieces, workspace bytes)."""
+    halo, nt, ws = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check_unsupported(load().sr_rcan_plan(C.byref(desc), int(h), int(w), int(tail), C.byref(halo), C.byref(nt), C.byref(ws)))
+    return halo.value, nt.value, int(ws.value)
+
+
+class RcanModel(_SrModel):
+    """sr_rcan_model: an RCAN resident on the GPU.  weights / biases: one fp32 array and one bias vector per table in forward
+    order (rcan_conv_shapes): OIHW for the 3 x 3 convolutions, (out, in) or (out, in, 1, 1) for the 1 x 1 layers.  The trunk is
+    one piece (the channel mean is global), so the forwards take ``tail`` alone."""
+    _kind = "rcan"
+    _run_args = ("tail",)
+
+    def __init__(self, ctx: Context, desc: RcanDesc, weights, biases):
+        rcan_plan(desc, 1, 1)                                    # the supported range, refused before any array is touched
+        shapes = rcan_conv_shapes(desc)
+        if len(weights) != len(shapes) or len(biases) != len(shapes):
+            raise ValueError(f"this RCAN has {len(shapes)} tables, got {len(weights)} weight / {len(biases)} bias arrays")
+        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
+        bs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in biases]
+        for k, (w, b, (co, ci, ks)) in enumerate(zip(ws, bs, shapes)):
+            ok = w.shape == (co, ci, ks, ks) or (ks == 1 and w.shape == (co, ci))
+            if not ok or b.shape != (co,):
+                raise ValueError(f"RCAN table {k}: expected {(co, ci, ks, ks)} / {(co,)}, got {w.shape} / {b.shape}")
+        self.desc, self.scale = desc, desc.scale
+        self._create(ctx, (C.byref(desc),), ws, bs, count=True)
+
+    def plan(self, h: int, w: int, tail: int = 0) -> Tuple[int, int, int]:
+        return rcan_plan(self.desc, h, w, tail)
+
+
+def rcan_attention(ctx, d_x: int, plane_stride: int, row_stride: int, n_feat: int, n_squeeze: int, h: int, w: int, w1, b1, w2, b2):
+    """sr_rcan_attention_f32: the channel mean and the attention of one RCAB on a planar fp32 tensor on the device (element
+    (c, y, x) at d_x + c plane_stride + y row_stride + 4 x bytes) -> (mean[F], s[F]) as fp32 arrays.  Arguments are refused
+    before the context is looked at, so ``ctx`` may be None where only the refusal matters.  Synchronous."""
+    F, R = int(n_feat), int(n_squeeze)
+    tabs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (w1, b1, w2, b2)]
+    for a, n, name in zip(tabs, (R * F, R, F * R, F), ("w1", "b1", "w2", "b2")):
+        if 1 <= R <= F <= 256 and a.size != n:                   # outside that range the library refuses by name
+            raise ValueError(f"{name} holds {a.size} values, expected {n}")
+    mean, s = np.empty(max(F, 1), np.float32), np.empty(max(F, 1), np.float32)
+    _check_unsupported(load().sr_rcan_attention_f32(_ctx_handle(ctx), C.c_void_p(d_x), int(plane_stride), int(row_stride), F, R, int(h), int(w),
+                                                    *[a.ctypes.data_as(C.c_void_p) for a in tabs], mean.ctypes.data_as(C.c_void_p),
+                                                    s.ctypes.data_as(C.c_void_p)))
+    return mean, s
 
 
 _default_ctx = {}

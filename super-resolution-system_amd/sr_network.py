@@ -240,7 +240,9 @@ def parse_residual_state(state: Mapping, res_scale: float = 1.0, img_range: floa
     keys = {str(k) for k in state}
     if "conv_first.weight" not in keys:
         raise ValueError("conv_first.weight: not in the state (not a residual SR network)")
-    convs = []                                                   # (key, cout or None for 'any multiple', cin)
+    if RCAN_KEY in keys:                                         # its body.{g}.* keys would read as an EDSR of zero blocks
+        raise ValueError(f"{RCAN_KEY}: this is an RCAN state (parse_rcan_state), not a residual SR network")
+    convs = []                                                 # (key, cout or None for 'any multiple', cin)
 
     def conv(name: str, cin: int, cout=None):
         convs.append(_read_conv(state, keys, name, cin, cout, " but the layer before it gives {}"))
@@ -390,13 +392,140 @@ def _rrdb_extras(state: Mapping) -> dict:
     return _scalar_extras(state, (("slope", 1), ("res_scale", 1)))
 
 
+# ------------------------------------------------------------------------------------------
+# RCAN: BasicSR's residual channel attention network (Zhang et al., ECCV 2018), run by csrc/sr_rcan.hip.  PARITY UNPINNED here
+# too: neither the BasicSR package nor a checkpoint exists offline; the arithmetic is written out in include/sr_hip.h and held
+# against a torch-CPU restatement (tests/_rcan_ref.py).
+# ------------------------------------------------------------------------------------------
+RCAN_KEY = "body.0.residual_group.0.rcab.0.weight"              # what tells an RCAN state from the residual family
+_RCAN_BLOCK_KEY = re.compile(r"^body\.(\d+)\.residual_group\.(\d+)\.rcab\.")
+_RCAN_GROUP_KEY = re.compile(r"^body\.(\d+)\.")
+
+
+def _read_1x1(state: Mapping, keys, name: str, cout: int, cin: int):
+    """-> (weight (cout, cin), bias) of the 1 x 1 convolution ``name`` as contiguous fp32; a ValueError names the offending key."""
+    for part in ("weight", "bias"):
+        if f"{name}.{part}" not in keys:
+            raise ValueError(f"{name}.{part}: not in the state")
+    w = np.ascontiguousarray(_array(state, f"{name}.weight"), dtype=np.float32)
+    b = np.ascontiguousarray(_array(state, f"{name}.bias"), dtype=np.float32).reshape(-1)
+    if w.shape != (cout, cin, 1, 1):
+        raise ValueError(f"{name}.weight: expected the 1x1 convolution {(cout, cin, 1, 1)}, got shape {w.shape}")
+    if b.shape != (cout,):
+        raise ValueError(f"{name}.bias: expected {cout} values, got {b.shape}")
+    return np.ascontiguousarray(w.reshape(cout, cin)), b
+
+
+def parse_rcan_state(state: Mapping, res_scale: float = 1.0, img_range: float = EDSR_IMG_RANGE, rgb_mean=EDSR_RGB_MEAN):
+    """-> (_native.RcanDesc, weights, biases) in sr_rcan_create's order, contiguous fp32 (the 1 x 1 layers as (out, in)).
+
+    BasicSR key names: ``conv_first``, per group g and block b ``body.{g}.residual_group.{b}.rcab.0`` / ``.rcab.2`` (3 x 3) and
+    ``.rcab.3.attention.1`` / ``.attention.3`` (1 x 1, F -> F / r -> F), ``body.{g}.conv``, then ``conv_after_body``,
+    ``upsample.{k}``, ``conv_last``.  The squeeze width is read off ``attention.1``.  Groups and blocks are numbered from 0
+    without gaps and every group has the same number of blocks.  res_scale, img_range and rgb_mean are not in a state dict.
+    Every shape is checked; a ValueError names the offending key; what the kernels do not cover (F, more than 16 groups, x8) is
+    a NotImplementedError."""
+    state = _unwrap(state)
+    keys = {str(k) for k in state}
+    if "conv_first.weight" not in keys:
+        raise ValueError("conv_first.weight: not in the state (not an RCAN)")
+    tables = []
+
+    def conv(name: str, cin: int, cout=None):
+        tables.append(_read_conv(state, keys, name, cin, cout, ", expected {}"))
+        return tables[-1][0]
+
+    F = int(conv("conv_first", 3).shape[0])
+    groups = sorted({int(m.group(1)) for m in map(_RCAN_GROUP_KEY.match, keys) if m})
+    if not groups or groups != list(range(len(groups))):
+        gap = next(i for i in range(len(groups) + 1) if i not in groups)
+        raise ValueError(f"body.{gap}.conv.weight: residual groups must be numbered 0 .. G - 1, got {groups}")
+    B = R = None
+    for g in groups:
+        blocks = sorted({int(m.group(2)) for m in map(_RCAN_BLOCK_KEY.match, keys) if m and int(m.group(1)) == g})
+        if blocks != list(range(len(blocks))):
+            gap = next(i for i in range(len(blocks) + 1) if i not in blocks)
+            raise ValueError(f"body.{g}.residual_group.{gap}.rcab.0.weight: a group's blocks must be numbered 0 .. B - 1, got {blocks}")
+        if B is None:
+            B = len(blocks)
+        elif len(blocks) != B:
+            raise ValueError(f"body.{g}.residual_group.{min(len(blocks), B)}.rcab.0.weight: every group must have the same number of "
+                             f"blocks, group 0 has {B} and group {g} has {len(blocks)}")
+        for b in blocks:
+            name = f"body.{g}.residual_group.{b}.rcab"
+            conv(f"{name}.0", F, F)
+            conv(f"{name}.2", F, F)
+            if R is None:
+                if f"{name}.3.attention.1.weight" not in keys:
+                    raise ValueError(f"{name}.3.attention.1.weight: not in the state")
+                R = int(np.shape(_array(state, f"{name}.3.attention.1.weight"))[0])
+            tables.append(_read_1x1(state, keys, f"{name}.3.attention.1", R, F))
+            tables.append(_read_1x1(state, keys, f"{name}.3.attention.3", F, R))
+        conv(f"body.{g}.conv", F, F)
+    conv("conv_after_body", F, F)
+    ups = [f"upsample.{k}" for k in sorted(int(m.group(1)) for m in map(_UPSAMPLE_KEY.match, keys) if m)
+           if _array(state, f"upsample.{k}.weight").ndim == 4]
+    scale = 1
+    for name in ups:
+        cout = int(np.shape(_array(state, f"{name}.weight"))[0])
+        r = {4 * F: 2, 9 * F: 3}.get(cout)
+        if r is None or (len(ups) >= 2 and r != 2):
+            want = f"{4 * F}" if len(ups) >= 2 else f"{4 * F} or {9 * F}"
+            raise ValueError(f"{name}.weight gives {cout} channels, expected F r^2 = {want}")
+        scale *= r
+    if len(ups) <= 2:                                            # beyond that the plan call below refuses the scale by name
+        for name in ups:
+            conv(name, F, None)
+        conv("conv_last", F, 3)
+    desc = _native.rcan_desc(F, max(1, F // 16) if R is None else R, len(groups), B, scale, float(res_scale), rgb_mean, float(img_range))
+    _native.rcan_plan(desc, 1, 1)                                # NotImplementedError outside the kernels' range (host only)
+    return desc, [w for w, _ in tables], [b for _, b in tables]
+
+
+class RCANSRNet(CompactSRNet):
+    """RCAN on the GPU, with CompactSRNet's surface (from_file, model, upscale, upscale_device, close).  ``state``: a BasicSR
+    state dict (see parse_rcan_state).
+
+    Every RCAB pools each channel over the whole image it is given, so the image is not streamed through the trunk: there is
+    no ``tile`` (anything but 0 is refused), only the ``tail`` of the upsampling phase, which changes no bit.  It also means
+    that an image cut into tiles before the network (as the pipeline does with ``block_size``) pools over each tile on its own
+    -- as every tiled inference of RCAN does -- so the tile size affects the values, not only the speed."""
+
+    def __init__(self, state: Mapping, res_scale: float = 1.0, img_range: float = EDSR_IMG_RANGE, rgb_mean=EDSR_RGB_MEAN, device: int = 0):
+        self.desc, self._w, self._b = parse_rcan_state(state, res_scale, img_range, rgb_mean)
+        d = self.desc
+        self.n_feat, self.n_squeeze, self.n_groups, self.n_blocks, self.scale = d.n_feat, d.n_squeeze, d.n_groups, d.n_blocks, d.scale
+        self.device = int(device)
+        self._models = {}
+
+    @classmethod
+    def from_file(cls, path: str, device: int = 0, **extras) -> "RCANSRNet":
+        """A .npz may hold the constants a state dict lacks as 0-d ``res_scale`` / ``img_range`` and 3-vector ``rgb_mean``
+        entries; keyword arguments win over them, BasicSR's defaults (1, 255, the DIV2K mean) stand in for the rest."""
+        state = load_state(path)
+        return cls(state, device=device, **{**_residual_extras(state), **extras})
+
+    def _make_model(self, ctx: "_native.Context"):
+        return _native.RcanModel(ctx, self.desc, self._w, self._b)
+
+    def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
+                       ctx: Optional["_native.Context"] = None, ensemble: int = 1, tail: int = 0):
+        if tile:
+            raise ValueError(f"RCAN's trunk is one piece (the channel mean is global): there is no tile, got tile={tile!r}; see tail")
+        # the one argument after the strides of sr_rcan_* is tail, and CompactSRNet hands its first one on by position
+        super().upscale_device(d_src, shape, d_dst, dst_stride, src_stride, tail, ctx, ensemble)
+
+
 def load_network(path: str, act: str = "prelu", device: int = 0):
-    """The network a weights file holds: a ``body.0.rdb1.conv1.weight`` entry makes it an RRDBSRNet, otherwise a
-    ``conv_first.weight`` entry a ResidualSRNet (``act`` is ignored for these two families), ``body.{i}.weight`` entries a
-    CompactSRNet exactly as CompactSRNet.from_file."""
+    """The network a weights file holds: a ``body.0.rdb1.conv1.weight`` entry makes it an RRDBSRNet, a
+    ``body.0.residual_group.0.rcab.0.weight`` entry an RCANSRNet, otherwise a ``conv_first.weight`` entry a ResidualSRNet
+    (``act`` is ignored for these three families), ``body.{i}.weight`` entries a CompactSRNet exactly as
+    CompactSRNet.from_file."""
     state = load_state(path)
     if RRDB_KEY in {str(k) for k in _unwrap(state)}:
         return RRDBSRNet(state, device=device, **_rrdb_extras(state))
+    if RCAN_KEY in {str(k) for k in _unwrap(state)}:
+        return RCANSRNet(state, device=device, **_residual_extras(state))
     if "conv_first.weight" in {str(k) for k in _unwrap(state)}:
         return ResidualSRNet(state, device=device, **_residual_extras(state))
     return CompactSRNet(state, act=act, device=device)
