@@ -1094,6 +1094,116 @@ SR_API int sr_rcan_attention_f32(sr_ctx *ctx, const float *d_x, int64_t plane_st
                                  int h, int w, const float *h_w1, const float *h_b1, const float *h_w2, const float *h_b2,
                                  float *h_mean, float *h_s);
 
+/* ---- local SR backend: SwinIR, shifted-window attention (csrc/sr_swinir.hip, csrc/sr_swinir_host.cpp) -----------------------
+ * BasicSR's SwinIR (Liang et al., ICCVW 2021) with resi_connection '1conv', ape False, patch_norm True, qkv_bias True,
+ * patch_size 1, in_chans 3, window 8, restated (parity with BasicSR and the official repository is unpinned: neither package nor
+ * a checkpoint exists offline).  Everything is fp32 (fp32 in, fp32 accumulate) except the LayerNorm statistics (float64).  A
+ * model is an sr_swinir_desc:
+ *     C = n_feat (embed_dim), 4 <= C <= 256, a multiple of 4;  n_heads dividing C with d = C / n_heads <= 32;
+ *     n_hidden = the MLP's hidden width (rows of fc1), 1 <= n_hidden <= 4 C;  L = n_groups RSTBs, 1 <= L <= 12;
+ *     D = depth, Swin layers per RSTB (the same in every RSTB), 1 <= D <= 12;  s = scale;  upsampler = SR_SWINIR_PIXELSHUFFLE
+ *     (s in 2, 3, 4), SR_SWINIR_PIXELSHUFFLEDIRECT (s in 1 .. 4) or SR_SWINIR_NEAREST_CONV (s = 4);  mean[3], range.
+ *  1. input      the u8 h x w x 3 image is extended to Hp x Wp, the next multiples of 8, by symmetric reflection: padded index
+ *                i reads m = i mod 2 n, m < n ? m : 2 n - 1 - m (np.pad mode 'symmetric': the edge pixel repeated, period 2 n;
+ *                the official test script's flip-concatenate whenever the pad is not larger than the side).  Then
+ *                x[c] = (u8 / 255 - mean[c]) * range (fp32: one division, one subtraction, one product).
+ *  2. head       h = conv_first(x), 3 x 3, 3 -> C, zero padding 1 at the border of the PADDED image (as every 3 x 3 here).
+ *  3. deep       r_0 = LN(h) (patch_embed.norm);  RSTB i = 1 .. L:  x = r_{i-1}, D Swin layers, r_i = conv_i(x) + r_{i-1};
+ *                then g = LN(r_L) (norm).  Swin layer j = 0 .. D - 1, shift = 0 for even j, 4 for odd j:
+ *                    y   = LN1(x);   [q k v] = W y + b  (qkv: rows 0 .. C - 1 are q, then k, then v; head n owns the channels
+ *                          n d .. n d + d - 1 of each);   q = q * (float)(1 / sqrtf(d))  (one fp32 multiply after the sum);
+ *                    the tokens are the pixels of the image rolled by (-shift, -shift) and cut into 8 x 8 windows: token
+ *                          (wy, wx) of window (by, bx) is pixel ((8 by + wy + shift) mod Hp, (8 bx + wx + shift) mod Wp);
+ *                    a[i][j] = (sum_dd q_i[dd] k_j[dd]  +  B[rel(i, j)][head])  +  (region(i) != region(j) ? -100 : nothing)
+ *                          for the 64 tokens of a window, rel(i, j) = (iy - jy + 7) * 15 + (ix - jx + 7) -- computed, the
+ *                          state dict's relative_position_index and attn_mask buffers are ignored -- and, with shift 4 only,
+ *                          region = 3 ry + rx of the token's coordinates (v) in the rolled image: 0 for v < L - 8, 1 for
+ *                          v < L - 4, else 2 (calculate_mask's slices; L = Hp or Wp);
+ *                    p[i][j] = e_j / sum_j e_j,  e_j = expf(a[i][j] - max_j a[i][j]);   o_i[dd] = sum_j p[i][j] v_j[dd];
+ *                    x = x + (proj o + b)  at the token's own pixel (the roll back);
+ *                    x = x + fc2(gelu(fc1(LN2(x)))),   gelu(t) = 0.5 t (1 + erff(t * 0.70710678f))  (fp32, left to right).
+ *                LayerNorm (eps 1e-5, population variance), float64 from the fp32 values, channels ascending, two passes:
+ *                    mean = (sum_c x[c]) / C;   var = (sum_c (x[c] - mean)^2) / C  (the square rounded, then added);
+ *                    y[c] = (float)((x[c] - mean) * (1 / sqrt(var + 1e-5)) * gamma[c] + beta[c])
+ *                every operation one rounded float64 operation, left to right, one rounding to fp32 at the end.
+ *  4. long skip  f = conv_after_body(g) + h  (one fp32 add).
+ *  5. reconstruction
+ *       pixelshuffle        conv_before_upsample C -> 64, LeakyReLU 0.01;  upsample: s = 4 two stages with r = 2, else one with
+ *                           r = s, a stage = conv 64 -> 64 r^2 + PixelShuffle(r);  conv_last 64 -> 3.
+ *       pixelshuffledirect  upsample.0: conv C -> 3 s^2 + PixelShuffle(s); nothing else.
+ *       nearest+conv (x4)   conv_before_upsample (LeakyReLU 0.01);  conv_up1 on the nearest x2 (LeakyReLU 0.2);  conv_up2 on
+ *                           the nearest x2 of that (0.2);  conv_hr (0.2);  conv_last.
+ *       PixelShuffle(r): u[c, Y, X] = v[c r^2 + (Y % r) r + (X % r), Y / r, X / r];  LeakyReLU: y >= 0 ? y : slope * y.
+ *  6. output     o[c] = y[c] / range + mean[c] (one division, one add), cropped to (h s) x (w s).  Stored as HWC fp32 unclamped
+ *                (sr_swinir_f32) or as HWC u8 rintf(fminf(fmaxf(o, 0), 1) * 255) (sr_swinir_u8).
+ * SwinIR's defaults, which a state dict does not hold: range 1, mean (0.4488, 0.4371, 0.4040).
+ * Summation orders.  3 x 3 convolutions and linear layers: bias, then channel pairs (2p, 2p + 1) ascending, then taps ascending,
+ * one two-term MFMA step each (even channel, then odd); head: bias, then channels, then taps, as fmaf; a skip is one add after
+ * the sum.  Attention: the dot product is an fmaf chain from +0 over dd ascending; then + B, then + the mask (two adds); the sum
+ * of e_j runs over the keys j ascending from +0; the division by the sum comes BEFORE the a v sum (p is formed, as torch's
+ * softmax does); the a v sum is an fmaf chain from +0 over j ascending.  No atomics.  Equal inputs give equal bits.
+ * Anything outside the ranges above (a non-finite mean or range, range 0) is SR_ERR_UNSUPPORTED, decided on the host before any
+ * device call.  Out of scope: window sizes other than 8, resi_connection '3conv', the absolute position embedding, the JPEG /
+ * denoising variants (no upsampler), Swin2SR, fp16 / bf16.
+ * Shifted windows let a pixel see farther with every layer pair, so the trunk (steps 1 .. 4) runs on the padded image in ONE
+ * piece: four planar fp32 buffers of Cp = C rounded up to 64 planes of P0 = Hp Wp floats (h / f, the RSTB input, x, LN / attention
+ * output) and one of Qp = max(3 C, n_hidden each rounded up to 64) planes (qkv, then the MLP's hidden tensor): 4 (4 Cp + Qp)
+ * bytes per pixel, 5376 at C = 180, hidden 360.  There is no tile argument.  After f nothing is global: step 5 runs in tail x tail
+ * sub-pieces of the h x w input, every layer's extent derived backwards from the sub-piece's output rectangle (divided by r
+ * rounded outwards across a shuffle or a replication, grown by one per convolution, clipped to the padded image), in two 64-plane
+ * buffers of P4 = the largest stored extent of a sub-piece (none for pixelshuffledirect).  Every tail gives the same bits.
+ * sr_swinir_create: h_w[k] / h_b[k] = the tables in forward order (dense fp32, weight then bias):
+ *     conv_first [C][3][3][3];  patch_embed.norm (gamma[C], beta[C]);
+ *     per RSTB i, per layer j:  norm1 (gamma, beta);  attn.qkv [3 C][C], [3 C];  attn.relative_position_bias_table [225][heads]
+ *         (its h_b entry is ignored and may be NULL);  attn.proj [C][C], [C];  norm2;  mlp.fc1 [hidden][C];  mlp.fc2 [C][hidden];
+ *     then the RSTB's conv [C][C][3][3];
+ *     norm;  conv_after_body;  then pixelshuffle: conv_before_upsample.0 [64][C][3][3], upsample.0 (and .2) [64 r^2][64][3][3],
+ *     conv_last [3][64][3][3];  pixelshuffledirect: upsample.0 [3 s^2][C][3][3];  nearest+conv: conv_before_upsample.0, conv_up1,
+ *     conv_up2, conv_hr, conv_last.  n_tables must be 2 + L (7 D + 1) + 2 + (3 or 4 | 1 | 5).
+ * sr_swinir_plan (host only, no context, no GPU): *hp, *wp = the padded size;  *halo = input pixels a tail sub-piece reads beyond
+ * its edge;  *n_tail_tiles = ceil(h / tail) ceil(w / tail);  *workspace_bytes = 4 (4 Cp + Qp) P0 + 4 * 2 * 64 P4 + 3 P0 (the
+ * trunk, the tail buffers, the reflected u8 image).  tail 0: 256.  Outputs may be NULL.
+ * sr_swinir_rel_index (host only): rel[i * 64 + j] = rel(i, j); n must be 4096.
+ * sr_swinir_u8 / sr_swinir_f32: d_src h x w x 3 u8, d_dst (h s) x (w s) x 3; strides in bytes (fp32: a multiple of 4).
+ * sr_swinir_layernorm_f32 (for inspection; synchronous): the LayerNorm above on any planar fp32 tensor on the device, element
+ * (c, y, x) at d_x + c plane_stride + y row_stride + 4 x bytes, into d_out likewise; gamma / beta are host arrays; C <= 256.
+ * sr_swinir_attention_f32 (for inspection; synchronous): the window attention above (from a[i][j] to o, before proj) on a planar
+ * qkv tensor of 3 C planes of hp x wp (multiples of 8) whose q planes are already scaled, h_table the [225][heads] host table,
+ * shift 0 or 4, into the C planes of d_out.
+ * sr_swinir_fill_workspace (for tests): grows the model's buffers to what an h x w forward needs and fills them with `byte`; a
+ * forward must not depend on what its workspace held.
+ * SR_ERR_INVALID_ARG for null pointers, a wrong n_tables, a destroyed model and a tail < 0, SR_ERR_SHAPE for h or w < 1, a stride
+ * shorter than a row, an output size beyond int, more than 262140 rows, P0 above INT_MAX / 32 or P4 above INT_MAX / 8 floats
+ * (the mainloop's 32-bit offsets inside a cin chunk), and trunk buffers above SR_SWINIR_TRUNK_CAP = 32 GiB -- a policy, as
+ * SR_RCAN_TRUNK_CAP, so that one 2048 x 2048 pipeline block fits at C = 180; the message names the cap and the largest input
+ * that fits -- all before any launch.  Asynchronous, except the two inspection entry points. */
+#define SR_SWINIR_TRUNK_CAP ((size_t)32 << 30)
+#define SR_SWINIR_PIXELSHUFFLE 0
+#define SR_SWINIR_PIXELSHUFFLEDIRECT 1
+#define SR_SWINIR_NEAREST_CONV 2
+typedef struct sr_swinir_desc {
+    int n_feat, n_heads, n_hidden, n_groups, depth, scale, upsampler;
+    float mean[3], range;
+} sr_swinir_desc;
+typedef struct sr_swinir_model sr_swinir_model;
+SR_API int sr_swinir_create(sr_ctx *ctx, const sr_swinir_desc *desc, const float *const *h_w, const float *const *h_b, int n_tables,
+                            sr_swinir_model **out);
+SR_API int sr_swinir_destroy(sr_swinir_model *model);
+SR_API int sr_swinir_plan(const sr_swinir_desc *desc, int h, int w, int tail, int *hp, int *wp, int *halo, int *n_tail_tiles,
+                          size_t *workspace_bytes);
+SR_API int sr_swinir_rel_index(int *rel, int n);
+SR_API int sr_swinir_u8(sr_swinir_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                        int64_t dst_stride, int tail);
+SR_API int sr_swinir_f32(sr_swinir_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                         int64_t dst_stride, int tail);
+SR_API int sr_swinir_fill_workspace(sr_swinir_model *model, int h, int w, int tail, int byte);
+SR_API int sr_swinir_layernorm_f32(sr_ctx *ctx, const float *d_x, int64_t plane_stride, int64_t row_stride, int n_feat, int h, int w,
+                                   const float *h_gamma, const float *h_beta, float *d_out, int64_t out_plane_stride,
+                                   int64_t out_row_stride);
+SR_API int sr_swinir_attention_f32(sr_ctx *ctx, const float *d_qkv, int64_t plane_stride, int64_t row_stride, int n_feat, int n_heads,
+                                   int hp, int wp, int shift, const float *h_table, float *d_out, int64_t out_plane_stride,
+                                   int64_t out_row_stride);
+
 /* ---- geometric self-ensemble of the local SR backends (csrc/sr_ensemble.hip) ------------------------------------------------
  * The "+" results of the SR literature (EDSR+, RCAN+: Timofte et al., Lim et al.): the network runs on the eight flips and
  * rotations of the input, each output is mapped back and the eight are averaged.  No new weights; the forwards are the
@@ -1149,6 +1259,11 @@ SR_API int sr_rcan_ens_u8(sr_rcan_model *model, const uint8_t *d_src, int64_t sr
                           int64_t dst_stride, int tail, int mask);
 SR_API int sr_rcan_ens_f32(sr_rcan_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
                            int64_t dst_stride, int tail, int mask);
+/* SwinIR+: every member is reflected, padded and windowed on its own. */
+SR_API int sr_swinir_ens_u8(sr_swinir_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                            int64_t dst_stride, int tail, int mask);
+SR_API int sr_swinir_ens_f32(sr_swinir_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                             int64_t dst_stride, int tail, int mask);
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,12 @@ class RcanDesc(C.Structure):
                 ("res_scale", C.c_float), ("mean", C.c_float * 3), ("range", C.c_float)]
 
 
+class SwinirDesc(C.Structure):
+    """sr_swinir_desc (include/sr_hip.h)."""
+    _fields_ = [("n_feat", C.c_int), ("n_heads", C.c_int), ("n_hidden", C.c_int), ("n_groups", C.c_int), ("depth", C.c_int),
+                ("scale", C.c_int), ("upsampler", C.c_int), ("mean", C.c_float * 3), ("range", C.c_float)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("launches", C.c_int64)]
 
@@ -291,6 +297,15 @@ SIGNATURES = {
     "sr_rcan_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
     "sr_rcan_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
     "sr_rcan_attention_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sr_swinir_create": (_i, [_vp, C.POINTER(SwinirDesc), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_vp)]),
+    "sr_swinir_destroy": (_i, [_vp]),
+    "sr_swinir_plan": (_i, [C.POINTER(SwinirDesc), _i, _i, _i, _pi, _pi, _pi, _pi, C.POINTER(_sz)]),
+    "sr_swinir_rel_index": (_i, [_vp, _i]),
+    "sr_swinir_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_swinir_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_swinir_fill_workspace": (_i, [_vp, _i, _i, _i, _i]),
+    "sr_swinir_layernorm_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i64]),
+    "sr_swinir_attention_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i64, _i64]),
     "sr_d4_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
     "sr_d4_acc_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i64]),
     "sr_ens_finish_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
@@ -304,6 +319,8 @@ SIGNATURES = {
     "sr_rrdb_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i, _i]),
     "sr_rcan_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
     "sr_rcan_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_swinir_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_swinir_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
 }
 
 
@@ -1883,7 +1900,7 @@ def ens_finish(ctx, d_acc: int, acc_stride: int, H: int, W: int, n: int, d_dst: 
 
 
 class _SrModel:
-    """What SrNetModel, ResNetModel, RrdbModel and RcanModel share: the caller's tables as checked fp32 arrays, the create call, the two
+    """What SrNetModel, ResNetModel, RrdbModel, RcanModel and SwinirModel share: the caller's tables as checked fp32 arrays, the create call, the two
     forwards, close.  ``_kind`` names the sr_<kind>_* entry points, ``_run_args`` what their forwards take after the
     destination stride."""
     _kind = ""
@@ -1917,7 +1934,7 @@ class _SrModel:
 
     def upscale_u8(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, *args, **named):
         """sr_<kind>_u8: h x w x 3 u8 -> (h s) x (w s) x 3 u8, HBM -> HBM; then ``tile = 0`` (RrdbModel: and ``tail = 0``; RcanModel:
-        ``tail = 0`` alone), by position or by name.  Asynchronous."""
+        and SwinirModel: ``tail = 0`` alone), by position or by name.  Asynchronous."""
         self._run("u8", d_src, src_stride, h, w, d_dst, dst_stride, args, named)
 
     def forward_f32(self, d_src: int, src_stride: int, h: int, w: int, d_dst: int, dst_stride: int, *args, **named):
@@ -2121,6 +2138,130 @@ def rcan_attention(ctx, d_x: int, plane_stride: int, row_stride: int, n_feat: in
                                                     *[a.ctypes.data_as(C.c_void_p) for a in tabs], mean.ctypes.data_as(C.c_void_p),
                                                     s.ctypes.data_as(C.c_void_p)))
     return mean, s
+
+
+# ------------------------------------------------------------------------------------------
+# local SR network, SwinIR (sr_swinir_*): sr_network.SwinIRSRNet parses BasicSR state dicts into these arrays
+# ------------------------------------------------------------------------------------------
+SWINIR_UPSAMPLERS = {"pixelshuffle": 0, "pixelshuffledirect": 1, "nearest+conv": 2}
+SWINIR_WINDOW = 8
+
+
+def swinir_desc(n_feat: int, n_heads: int, n_hidden: int, n_groups: int, depth: int, scale: int, upsampler="pixelshuffle",
+                mean=(0.0, 0.0, 0.0), range: float = 1.0) -> SwinirDesc:  # noqa: A002 (the header's name)
+    mean = [float(v) for v in np.asarray(mean, dtype=np.float64).reshape(-1)]
+    if len(mean) != 3:
+        raise ValueError(f"mean holds 3 values, got {len(mean)}")
+    kind = SWINIR_UPSAMPLERS.get(upsampler, upsampler)
+    return SwinirDesc(int(n_feat), int(n_heads), int(n_hidden), int(n_groups), int(depth), int(scale), int(kind), (C.c_float * 3)(*mean),
+                      float(range))
+
+
+def swinir_table_names(desc: SwinirDesc) -> List[str]:
+    """BasicSR's name of every table in sr_swinir_create's order (weight key = name + '.weight', bias key = name + '.bias';
+    the bias table's key is the name itself and it has no bias)."""
+    names = ["conv_first", "patch_embed.norm"]
+    for i in range(desc.n_groups):
+        for j in range(desc.depth):
+            b = f"layers.{i}.residual_group.blocks.{j}"
+            names += [f"{b}.norm1", f"{b}.attn.qkv", f"{b}.attn.relative_position_bias_table", f"{b}.attn.proj", f"{b}.norm2",
+                      f"{b}.mlp.fc1", f"{b}.mlp.fc2"]
+        names.append(f"layers.{i}.conv")
+    names += ["norm", "conv_after_body"]
+    if desc.upsampler == 0:
+        names += ["conv_before_upsample.0"] + [f"upsample.{2 * k}" for k in range(2 if desc.scale == 4 else 1)] + ["conv_last"]
+    elif desc.upsampler == 1:
+        names += ["upsample.0"]
+    else:
+        names += ["conv_before_upsample.0", "conv_up1", "conv_up2", "conv_hr", "conv_last"]
+    return names
+
+
+def swinir_table_shapes(desc: SwinirDesc) -> List[Tuple[tuple, Optional[tuple]]]:
+    """(weight shape, bias shape) of every table in sr_swinir_create's order; the bias table has no bias (None)."""
+    Cn, nh, hid, s = desc.n_feat, desc.n_heads, desc.n_hidden, desc.scale
+    ln = ((Cn,), (Cn,))
+    layer = [ln, ((3 * Cn, Cn), (3 * Cn,)), (((2 * SWINIR_WINDOW - 1) ** 2, nh), None), ((Cn, Cn), (Cn,)), ln, ((hid, Cn), (hid,)),
+             ((Cn, hid), (Cn,))]
+
+    def conv(co, ci):
+        return ((co, ci, 3, 3), (co,))
+
+    shapes = [conv(Cn, 3), ln] + (layer * desc.depth + [conv(Cn, Cn)]) * desc.n_groups + [ln, conv(Cn, Cn)]
+    if desc.upsampler == 0:
+        shapes += [conv(64, Cn)] + [conv(64 * r * r, 64) for r in ([2, 2] if s == 4 else [s])] + [conv(3, 64)]
+    elif desc.upsampler == 1:
+        shapes += [conv(3 * s * s, Cn)]
+    else:
+        shapes += [conv(64, Cn), conv(64, 64), conv(64, 64), conv(64, 64), conv(3, 64)]
+    return shapes
+
+
+def swinir_plan(desc: SwinirDesc, h: int, w: int, tail: int = 0) -> Tuple[int, int, int, int, int]:
+    """sr_swinir_plan (host only) -> (padded rows, padded columns, the tail's halo, tail sub-pieces, workspace bytes)."""
+    hp, wp, halo, nt, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check_unsupported(load().sr_swinir_plan(C.byref(desc), int(h), int(w), int(tail), C.byref(hp), C.byref(wp), C.byref(halo), C.byref(nt),
+                                             C.byref(ws)))
+    return hp.value, wp.value, halo.value, nt.value, int(ws.value)
+
+
+def swinir_rel_index() -> np.ndarray:
+    """sr_swinir_rel_index (host only) -> (64, 64) int32: the bias-table row of (query token, key token)."""
+    rel = np.empty((64, 64), np.int32)
+    check(load().sr_swinir_rel_index(rel.ctypes.data_as(C.c_void_p), rel.size))
+    return rel
+
+
+class SwinirModel(_SrModel):
+    """sr_swinir_model: a SwinIR resident on the GPU.  weights / biases: one fp32 array each per table in forward order
+    (swinir_table_shapes / swinir_table_names); the bias entry of a relative-position table is ignored (None is fine).  The
+    trunk is one piece, so the forwards take ``tail`` alone."""
+    _kind = "swinir"
+    _run_args = ("tail",)
+
+    def __init__(self, ctx: Context, desc: SwinirDesc, weights, biases):
+        swinir_plan(desc, 1, 1)                                  # the supported range, refused before any array is touched
+        shapes = swinir_table_shapes(desc)
+        if len(weights) != len(shapes) or len(biases) != len(shapes):
+            raise ValueError(f"this SwinIR has {len(shapes)} tables, got {len(weights)} weight / {len(biases)} bias arrays")
+        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
+        bs = [np.zeros(1, np.float32) if sb is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a, (_, sb) in zip(biases, shapes)]
+        for k, (w, b, (sw, sb)) in enumerate(zip(ws, bs, shapes)):
+            if w.shape != sw or (sb is not None and b.shape != sb):
+                raise ValueError(f"SwinIR table {k}: expected {sw} / {sb}, got {w.shape} / {b.shape}")
+        self.desc, self.scale = desc, desc.scale
+        self._create(ctx, (C.byref(desc),), ws, bs, count=True)
+
+    def plan(self, h: int, w: int, tail: int = 0):
+        return swinir_plan(self.desc, h, w, tail)
+
+    def fill_workspace(self, h: int, w: int, byte: int, tail: int = 0):
+        """sr_swinir_fill_workspace: the buffers of an h x w forward, grown and filled with ``byte`` (for tests)."""
+        check(self.ctx.lib.sr_swinir_fill_workspace(self.handle, int(h), int(w), int(tail), int(byte)))
+
+
+def swinir_layernorm(ctx, d_x: int, plane_stride: int, row_stride: int, n_feat: int, h: int, w: int, gamma, beta, d_out: int,
+                     out_plane_stride: int, out_row_stride: int):
+    """sr_swinir_layernorm_f32: the backend's LayerNorm over the channels of a planar fp32 tensor on the device (element
+    (c, y, x) at d_x + c plane_stride + y row_stride + 4 x bytes) into d_out, laid out likewise.  Synchronous."""
+    g, b = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (gamma, beta))
+    if 1 <= int(n_feat) <= 256 and (g.size != n_feat or b.size != n_feat):
+        raise ValueError(f"gamma / beta hold {g.size} / {b.size} values, expected {n_feat}")
+    _check_unsupported(load().sr_swinir_layernorm_f32(_ctx_handle(ctx), C.c_void_p(d_x), int(plane_stride), int(row_stride), int(n_feat), int(h),
+                                                      int(w), g.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.c_void_p(d_out),
+                                                      int(out_plane_stride), int(out_row_stride)))
+
+
+def swinir_attention(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat: int, n_heads: int, hp: int, wp: int, shift: int, table,
+                     d_out: int, out_plane_stride: int, out_row_stride: int):
+    """sr_swinir_attention_f32: the window attention (before proj) on a planar qkv tensor of 3 C planes whose q planes are
+    already scaled; ``table``: the (225, heads) relative-position bias table; into the C planes of d_out.  Synchronous."""
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    if 1 <= int(n_heads) <= 256 and t.shape != ((2 * SWINIR_WINDOW - 1) ** 2, int(n_heads)):
+        raise ValueError(f"the bias table is {((2 * SWINIR_WINDOW - 1) ** 2, int(n_heads))}, got {t.shape}")
+    _check_unsupported(load().sr_swinir_attention_f32(_ctx_handle(ctx), C.c_void_p(d_qkv), int(plane_stride), int(row_stride), int(n_feat),
+                                                      int(n_heads), int(hp), int(wp), int(shift), t.ctypes.data_as(C.c_void_p), C.c_void_p(d_out),
+                                                      int(out_plane_stride), int(out_row_stride)))
 
 
 _default_ctx = {}

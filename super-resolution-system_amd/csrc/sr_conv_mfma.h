@@ -1,4 +1,4 @@
-// sr_conv_mfma.h -- the fp32 implicit-GEMM convolution shared by sr_lpips.hip, sr_srnet.hip, sr_resnet.hip, sr_rrdb.hip and sr_rcan.hip: one device
+// sr_conv_mfma.h -- the fp32 implicit-GEMM convolution shared by sr_lpips.hip, sr_srnet.hip, sr_resnet.hip, sr_rrdb.hip, sr_rcan.hip and sr_swinir.hip: one device
 // mainloop, one 3 -> F head accumulate, and the host helpers around them (weight layouts, upload, the live-model set, the
 // activation buffers, the forward calls' argument checks).  Internal: nothing here is part of the C ABI.
 #pragma once

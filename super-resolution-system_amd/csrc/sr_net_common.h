@@ -1,4 +1,4 @@
-// sr_net_common.h -- what the four local SR backends (sr_srnet.hip, sr_resnet.hip, sr_rrdb.hip, sr_rcan.hip) share around the convolution
+// sr_net_common.h -- what the five local SR backends (sr_srnet.hip, sr_resnet.hip, sr_rrdb.hip, sr_rcan.hip, sr_swinir.hip) share around the convolution
 // mainloop of sr_conv_mfma.h: the head frame and the per-element pieces of their epilogues, the planar-tensor and
 // backward-extent geometry of their layer walks, and the lifetime of their models.  sr_lpips.hip needs none of it and includes
 // the mainloop header alone.  Internal: nothing here is part of the C ABI.
@@ -96,7 +96,7 @@ inline int backward_halo(const ExtStep *steps, int n)
     return g;
 }
 
-// The convolution launch of sr_resnet.hip, sr_rrdb.hip and sr_rcan.hip.  in: the tensor read (its first cin planes); out: pointer to the
+// The convolution launch of sr_resnet.hip, sr_rrdb.hip, sr_rcan.hip and sr_swinir.hip.  in: the tensor read (its first cin planes); out: pointer to the
 // element (cout 0, ya, xa) of the output -- or, for a replicating or shuffling epilogue, of the output at its own resolution.
 template <typename Kernel, typename Epi>
 inline void launch_conv(Kernel kernel, hipStream_t st, const PlanarTen &in, int H_in, int W_in, int cin, int ncout_tiles, const float *dw,

@@ -6,9 +6,10 @@ Keeps the reference's names, config fields and defaults, result record and five-
 through tiling_module / blending_module / quality_assessment_module.  Stage 2 of the reference is a
 remote vendor API (out of scope): here it is a pluggable ``sr_backend`` whose default
 is the bicubic stub of BASELINE.json's configs, executed on the GPU with the resize kernel; with
-``PipelineConfig.sr_weights`` set it is a local SR network of sr_network.py (compact, MSRResNet / EDSR, RRDBNet x4 or
-RCAN; caller-supplied weights).  RCAN pools every channel over the image it is given, so each tile pools over itself -- as
-every tiled inference of RCAN does -- and ``block_size`` then affects the SR values.
+``PipelineConfig.sr_weights`` set it is a local SR network of sr_network.py (compact, MSRResNet / EDSR, RRDBNet x4, RCAN
+or SwinIR; caller-supplied weights).  RCAN pools every channel over the image it is given, so each tile pools over itself -- as
+every tiled inference of RCAN does -- and ``block_size`` then affects the SR values.  SwinIR likewise: each tile is reflected,
+padded to a multiple of 8 and cut into shifted windows on its own, as in every tiled SwinIR inference.
 
 What is wired differently from the reference, because the reference's own wiring cannot run
 (SURVEY.md 0.3): tiles are read from ``tile.data``; ``TileInfo(image, x, y, row, col)`` is built with
@@ -78,8 +79,9 @@ class PipelineConfig:
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
                                    # only the canvas comes back for the writer (a custom sr_backend gets host arrays)
     sr_weights: str = ""       # path of an SR network's weights (.npz, or .pth / .pt where torch imports): stage 2 runs the
-                               # network (sr_network.load_network: compact, MSRResNet / EDSR, RRDBNet x4 or RCAN) instead of the bicubic
-                               # stub, device-resident too (RCAN: each tile pools its channel means over itself)
+                               # network (sr_network.load_network: compact, MSRResNet / EDSR, RRDBNet x4, RCAN or SwinIR) instead of the
+                               # bicubic stub, device-resident too (RCAN: each tile pools its channel means over itself; SwinIR: each
+                               # tile is padded and windowed on its own)
     sr_act: str = "prelu"      # activation of a compact network whose weights hold no PReLU slopes: 'relu' or 'leakyrelu'
                                # (ignored for the residual family)
     sr_ensemble: int = 1       # (with sr_weights) geometric self-ensemble of the network: 1 off, 2 identity + horizontal flip, 4 the
@@ -688,7 +690,7 @@ async def main() -> int:
     ap.add_argument("--block-size", type=int, default=2048)
     ap.add_argument("--sr-scale", type=int, default=2)
     ap.add_argument("--sr-weights", default="", metavar="PATH",
-                    help="weights of an SR network (.npz / .pth: compact, MSRResNet / EDSR, RCAN, or RRDBNet x4 with --sr-scale 4): stage 2 runs it "
+                    help="weights of an SR network (.npz / .pth: compact, MSRResNet / EDSR, RCAN, SwinIR, or RRDBNet x4 with --sr-scale 4): stage 2 runs it "
                          "instead of the bicubic stub")
     ap.add_argument("--sr-act", default="prelu", metavar="NAME", help="prelu (slopes in the weights), relu or leakyrelu")
     ap.add_argument("--sr-ensemble", type=int, choices=(1, 2, 4, 8), default=1,

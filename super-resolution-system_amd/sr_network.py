@@ -242,6 +242,8 @@ def parse_residual_state(state: Mapping, res_scale: float = 1.0, img_range: floa
         raise ValueError("conv_first.weight: not in the state (not a residual SR network)")
     if RCAN_KEY in keys:                                         # its body.{g}.* keys would read as an EDSR of zero blocks
         raise ValueError(f"{RCAN_KEY}: this is an RCAN state (parse_rcan_state), not a residual SR network")
+    if SWINIR_KEY in keys:
+        raise ValueError(f"{SWINIR_KEY}: this is a SwinIR state (parse_swinir_state), not a residual SR network")
     convs = []                                                 # (key, cout or None for 'any multiple', cin)
 
     def conv(name: str, cin: int, cout=None):
@@ -516,16 +518,204 @@ class RCANSRNet(CompactSRNet):
         super().upscale_device(d_src, shape, d_dst, dst_stride, src_stride, tail, ctx, ensemble)
 
 
+# ------------------------------------------------------------------------------------------
+# SwinIR: BasicSR's shifted-window transformer for image restoration (Liang et al., ICCVW 2021), run by csrc/sr_swinir.hip.
+# PARITY UNPINNED here too: neither the BasicSR package, the official repository nor a checkpoint exists offline; the arithmetic
+# is written out in include/sr_hip.h and held against a torch-CPU restatement (tests/_swinir_ref.py).
+# ------------------------------------------------------------------------------------------
+SWINIR_KEY = "layers.0.residual_group.blocks.0.attn.qkv.weight"  # what tells a SwinIR state from the residual family
+SWINIR_RGB_MEAN = EDSR_RGB_MEAN                                  # SwinIR's defaults: the DIV2K mean, img_range 1
+SWINIR_IMG_RANGE = 1.0
+_SWINIR_LAYER_KEY = re.compile(r"^layers\.(\d+)\.")
+_SWINIR_BLOCK_KEY = re.compile(r"^layers\.(\d+)\.residual_group\.blocks\.(\d+)\.")
+
+
+def _read_dense(state: Mapping, keys, name: str, w_shape, b_shape, part_w: str = "weight"):
+    """-> (weight, bias) of ``name`` as contiguous fp32 with exactly these shapes; a ValueError names the offending key."""
+    out = []
+    for part, shape in ((part_w, w_shape), ("bias", b_shape)):
+        if shape is None:
+            out.append(None)
+            continue
+        key = f"{name}.{part}" if part else name
+        if key not in keys:
+            raise ValueError(f"{key}: not in the state")
+        a = np.ascontiguousarray(_array(state, key), dtype=np.float32)
+        if a.shape != tuple(shape):
+            raise ValueError(f"{key}: expected shape {tuple(shape)}, got {a.shape}")
+        out.append(a)
+    return out[0], out[1]
+
+
+def parse_swinir_state(state: Mapping, img_range: float = SWINIR_IMG_RANGE, rgb_mean=SWINIR_RGB_MEAN):
+    """-> (_native.SwinirDesc, weights, biases) in sr_swinir_create's order (_native.swinir_table_names), contiguous fp32; the
+    bias entry of a relative-position table is None.
+
+    BasicSR key names.  The whole description is read off the shapes: embed_dim from ``conv_first``, the heads from the second
+    axis of ``relative_position_bias_table``, the hidden width from ``mlp.fc1``, the RSTBs and their depth from the numbering
+    (from 0 without gaps, the same depth and head count everywhere), the upsampler from which keys exist
+    (``conv_up1`` -> nearest+conv, ``conv_before_upsample.0`` -> pixelshuffle, ``upsample.0`` alone -> pixelshuffledirect) and
+    the scale from the upsampling convolutions' widths.  The ``relative_position_index`` and ``attn_mask`` buffers are
+    ignored.  A ValueError names the offending key for a wrong shape and for everything out of scope: resi_connection '3conv',
+    the absolute position embedding, a window other than 8, the JPEG / denoising variants (no upsampler), Swin2SR, fp16 / bf16;
+    what only the kernels' ranges exclude is a NotImplementedError."""
+    state = _unwrap(state)
+    keys = {str(k) for k in state}
+    if SWINIR_KEY not in keys:
+        raise ValueError(f"{SWINIR_KEY}: not in the state (not a SwinIR)")
+    if "absolute_pos_embed" in keys:
+        raise ValueError("absolute_pos_embed: the absolute position embedding (ape=True) is not supported")
+    if "layers.0.conv.0.weight" in keys:
+        raise ValueError("layers.0.conv.0.weight: resi_connection '3conv' is not supported (only '1conv')")
+    for k in sorted(keys):
+        if k.endswith((".attn.logit_scale", ".attn.cpb_mlp.0.weight", ".attn.q_bias")):
+            raise ValueError(f"{k}: this is a Swin2SR state (SwinV2 attention), not a SwinIR")
+    for k in sorted(keys):
+        a = state[k]
+        name = str(getattr(a, "dtype", ""))
+        if "float16" in name or "bfloat16" in name:
+            raise ValueError(f"{k}: {name} weights are not supported (fp32 only)")
+    tables = []
+
+    def conv(name: str, cin: int, cout=None):
+        tables.append(_read_conv(state, keys, name, cin, cout, ", expected {}"))
+        return tables[-1][0]
+
+    def dense(name: str, w_shape, b_shape, part_w: str = "weight"):
+        tables.append(_read_dense(state, keys, name, w_shape, b_shape, part_w))
+
+    Cn = int(conv("conv_first", 3).shape[0])
+    dense("patch_embed.norm", (Cn,), (Cn,))
+    groups = sorted({int(m.group(1)) for m in map(_SWINIR_LAYER_KEY.match, keys) if m})
+    if not groups or groups != list(range(len(groups))):
+        gap = next(i for i in range(len(groups) + 1) if i not in groups)
+        raise ValueError(f"layers.{gap}.conv.weight: the RSTBs must be numbered 0 .. L - 1, got {groups}")
+    tkey = "layers.0.residual_group.blocks.0.attn.relative_position_bias_table"
+    if tkey not in keys:
+        raise ValueError(f"{tkey}: not in the state")
+    tshape = np.shape(_array(state, tkey))
+    rows = (2 * _native.SWINIR_WINDOW - 1) ** 2
+    if len(tshape) != 2 or tshape[0] != rows:
+        raise ValueError(f"{tkey}: shape {tuple(tshape)} is not a window of 8 ({rows} rows): only window_size 8 is supported")
+    heads = int(tshape[1])
+    fkey = "layers.0.residual_group.blocks.0.mlp.fc1.weight"
+    if fkey not in keys:
+        raise ValueError(f"{fkey}: not in the state")
+    hidden = int(np.shape(_array(state, fkey))[0])
+    depth = None
+    for g in groups:
+        blocks = sorted({int(m.group(2)) for m in map(_SWINIR_BLOCK_KEY.match, keys) if m and int(m.group(1)) == g})
+        if not blocks or blocks != list(range(len(blocks))):
+            gap = next(i for i in range(len(blocks) + 1) if i not in blocks)
+            raise ValueError(f"layers.{g}.residual_group.blocks.{gap}.attn.qkv.weight: an RSTB's layers must be numbered 0 .. D - 1, got {blocks}")
+        if depth is None:
+            depth = len(blocks)
+        elif len(blocks) != depth:
+            raise ValueError(f"layers.{g}.residual_group.blocks.{min(len(blocks), depth)}.attn.qkv.weight: every RSTB must have the same "
+                             f"depth, RSTB 0 has {depth} layers and RSTB {g} has {len(blocks)}")
+        for j in blocks:
+            b = f"layers.{g}.residual_group.blocks.{j}"
+            t = f"{b}.attn.relative_position_bias_table"
+            if t in keys and np.shape(_array(state, t)) != (rows, heads):
+                got = np.shape(_array(state, t))
+                what = "every layer must have the same number of heads" if len(got) == 2 and got[0] == rows else "only window_size 8 is supported"
+                raise ValueError(f"{t}: expected shape {(rows, heads)}, got {tuple(got)}: {what}")
+            dense(f"{b}.norm1", (Cn,), (Cn,))
+            dense(f"{b}.attn.qkv", (3 * Cn, Cn), (3 * Cn,))
+            dense(t, (rows, heads), None, "")
+            dense(f"{b}.attn.proj", (Cn, Cn), (Cn,))
+            dense(f"{b}.norm2", (Cn,), (Cn,))
+            dense(f"{b}.mlp.fc1", (hidden, Cn), (hidden,))
+            dense(f"{b}.mlp.fc2", (Cn, hidden), (Cn,))
+        conv(f"layers.{g}.conv", Cn, Cn)
+    dense("norm", (Cn,), (Cn,))
+    conv("conv_after_body", Cn, Cn)
+    scale = 1
+    if "conv_up1.weight" in keys:
+        kind, scale = "nearest+conv", 4
+        conv("conv_before_upsample.0", Cn, 64)
+        for name in ("conv_up1", "conv_up2", "conv_hr"):
+            conv(name, 64, 64)
+        conv("conv_last", 64, 3)
+    elif "conv_before_upsample.0.weight" in keys:
+        kind = "pixelshuffle"
+        conv("conv_before_upsample.0", Cn, 64)
+        ups = [f"upsample.{k}" for k in sorted(int(m.group(1)) for m in map(_UPSAMPLE_KEY.match, keys) if m)]
+        for name in ups:
+            cout = int(np.shape(_array(state, f"{name}.weight"))[0])
+            r = {256: 2, 576: 3}.get(cout)
+            if r is None or (len(ups) >= 2 and r != 2) or len(ups) > 2:
+                raise ValueError(f"{name}.weight gives {cout} channels in {len(ups)} stage(s), expected 64 r^2 = 256 (x2, x4) or 576 (x3)")
+            scale *= r
+            conv(name, 64, cout)
+        if not ups:
+            raise ValueError("upsample.0.weight: not in the state (pixelshuffle at scale 1 has no upsampling stage and is not supported)")
+        conv("conv_last", 64, 3)
+    elif "upsample.0.weight" in keys:
+        kind = "pixelshuffledirect"
+        cout = int(np.shape(_array(state, "upsample.0.weight"))[0])
+        scale = {3: 1, 12: 2, 27: 3, 48: 4}.get(cout)
+        if scale is None:
+            raise ValueError(f"upsample.0.weight gives {cout} channels, expected 3 s^2 with s in 1 .. 4")
+        conv("upsample.0", Cn, cout)
+    else:
+        raise ValueError("conv_last.weight: no upsampler keys (conv_before_upsample, upsample, conv_up1): the JPEG / denoising variants "
+                         "of SwinIR are not supported")
+    desc = _native.swinir_desc(Cn, heads, hidden, len(groups), depth, scale, kind, rgb_mean, float(img_range))
+    _native.swinir_plan(desc, 1, 1)                              # NotImplementedError outside the kernels' range (host only)
+    return desc, [w for w, _ in tables], [b for _, b in tables]
+
+
+class SwinIRSRNet(CompactSRNet):
+    """SwinIR on the GPU, with CompactSRNet's surface (from_file, model, upscale, upscale_device, close).  ``state``: a BasicSR
+    state dict (see parse_swinir_state).
+
+    Shifted windows let a pixel see farther with every layer, so the image is not streamed through the trunk: there is no
+    ``tile`` (anything but 0 is refused), only the ``tail`` of the reconstruction, which changes no bit.  An image cut into
+    tiles before the network (as the pipeline does with ``block_size``) is reflected, padded and windowed tile by tile -- as
+    every tiled inference of SwinIR does -- so the tile size affects the values, not only the speed."""
+
+    def __init__(self, state: Mapping, img_range: float = SWINIR_IMG_RANGE, rgb_mean=SWINIR_RGB_MEAN, device: int = 0):
+        self.desc, self._w, self._b = parse_swinir_state(state, img_range, rgb_mean)
+        d = self.desc
+        self.n_feat, self.n_heads, self.n_hidden, self.n_groups, self.depth, self.scale = d.n_feat, d.n_heads, d.n_hidden, d.n_groups, d.depth, d.scale
+        self.device = int(device)
+        self._models = {}
+
+    @classmethod
+    def from_file(cls, path: str, device: int = 0, **extras) -> "SwinIRSRNet":
+        """A .npz may hold the constants a state dict lacks as a 0-d ``img_range`` and a 3-vector ``rgb_mean`` entry; keyword
+        arguments win over them, SwinIR's defaults (1, the DIV2K mean) stand in for the rest."""
+        state = load_state(path)
+        return cls(state, device=device, **{**_swinir_extras(state), **extras})
+
+    def _make_model(self, ctx: "_native.Context"):
+        return _native.SwinirModel(ctx, self.desc, self._w, self._b)
+
+    def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
+                       ctx: Optional["_native.Context"] = None, ensemble: int = 1, tail: int = 0):
+        if tile:
+            raise ValueError(f"SwinIR's trunk is one piece (shifted windows reach across any tile): there is no tile, got tile={tile!r}; see tail")
+        # the one argument after the strides of sr_swinir_* is tail, and CompactSRNet hands its first one on by position
+        super().upscale_device(d_src, shape, d_dst, dst_stride, src_stride, tail, ctx, ensemble)
+
+
+def _swinir_extras(state: Mapping) -> dict:
+    return _scalar_extras(state, (("img_range", 1), ("rgb_mean", 3)))
+
+
 def load_network(path: str, act: str = "prelu", device: int = 0):
     """The network a weights file holds: a ``body.0.rdb1.conv1.weight`` entry makes it an RRDBSRNet, a
-    ``body.0.residual_group.0.rcab.0.weight`` entry an RCANSRNet, otherwise a ``conv_first.weight`` entry a ResidualSRNet
-    (``act`` is ignored for these three families), ``body.{i}.weight`` entries a CompactSRNet exactly as
+    ``body.0.residual_group.0.rcab.0.weight`` entry an RCANSRNet, a ``layers.0.residual_group.blocks.0.attn.qkv.weight`` entry a
+    SwinIRSRNet, otherwise a ``conv_first.weight`` entry a ResidualSRNet (``act`` is ignored for these four families), ``body.{i}.weight`` entries a CompactSRNet exactly as
     CompactSRNet.from_file."""
     state = load_state(path)
     if RRDB_KEY in {str(k) for k in _unwrap(state)}:
         return RRDBSRNet(state, device=device, **_rrdb_extras(state))
     if RCAN_KEY in {str(k) for k in _unwrap(state)}:
         return RCANSRNet(state, device=device, **_residual_extras(state))
+    if SWINIR_KEY in {str(k) for k in _unwrap(state)}:
+        return SwinIRSRNet(state, device=device, **_swinir_extras(state))
     if "conv_first.weight" in {str(k) for k in _unwrap(state)}:
         return ResidualSRNet(state, device=device, **_residual_extras(state))
     return CompactSRNet(state, act=act, device=device)
