@@ -1204,6 +1204,112 @@ SR_API int sr_swinir_attention_f32(sr_ctx *ctx, const float *d_qkv, int64_t plan
                                    int hp, int wp, int shift, const float *h_table, float *d_out, int64_t out_plane_stride,
                                    int64_t out_row_stride);
 
+/* ---- local SR backend: HAT, hybrid attention (csrc/sr_hat.hip, csrc/sr_hat_host.cpp) -----------------------------------------
+ * HAT (Chen et al., "Activating More Pixels in Image Super-Resolution Transformer", CVPR 2023) with resi_connection '1conv',
+ * ape False, patch_norm True, qkv_bias True, patch_size 1, in_chans 3, window_size 16, overlap_ratio 0.5, upsampler
+ * pixelshuffle, restated (parity with the official repository is unpinned: neither the package nor a checkpoint exists offline;
+ * the forward is written from the published architecture).  Everything is fp32 except the LayerNorm statistics and the CAB's
+ * channel attention (float64).  A model is an sr_hat_desc:
+ *     C = n_feat (embed_dim), 4 <= C <= 256, a multiple of 4;  n_heads dividing C with d = C / n_heads <= 32;
+ *     n_hidden = the MLP's hidden width, 1 <= n_hidden <= 4 C, the same in every HAB and OCAB;  n_mid = the CAB's compressed
+ *     width (rows of cab.0), 1 <= n_mid <= C;  n_squeeze = rows of cab.3.attention.1, 1 <= n_squeeze <= C;  L = n_groups RHAGs,
+ *     1 <= L <= 12;  D = depth, HABs per RHAG, 1 <= D <= 12;  s = scale in 2, 3, 4;  conv_scale;  mean[3], range.
+ *  1. input      the u8 h x w x 3 image is extended to Hp x Wp, the next multiples of 16, by reflection WITHOUT the edge pixel
+ *                (F.pad mode 'reflect', which HAT's pre_process uses; not SwinIR's symmetric form): padded index i reads
+ *                m = i mod (2 n - 2), m < n ? m : 2 n - 2 - m; for n = 1 the single pixel is repeated.  Then
+ *                x[c] = (u8 / 255 - mean[c]) * range, as SwinIR.
+ *  2. head, 4. long skip, 5. reconstruction (pixelshuffle only), 6. output: exactly SwinIR's steps of those numbers.
+ *  3. deep       r_0 = LN(h) (patch_embed.norm);  RHAG i = 1 .. L:  x = r_{i-1}, D HABs, one OCAB, r_i = conv_i(x) + r_{i-1};
+ *                then g = LN(r_L) (norm).  LayerNorm, the linear layers and gelu are SwinIR's.
+ *                HAB j = 0 .. D - 1, shift = 0 for even j, 8 for odd j:
+ *                    y   = LN1(x);
+ *                    window attention on y: SwinIR's with 16 in place of 8 -- 256 tokens per window, token (wy, wx) of window
+ *                          (by, bx) is pixel ((16 by + wy + shift) mod Hp, (16 bx + wx + shift) mod Wp);  rel(i, j) =
+ *                          (iy - jy + 15) * 31 + (ix - jx + 15), the table is [961][heads];  regions per axis: 0 for v < L - 16,
+ *                          1 for v < L - 8, else 2;  the mask is -100;  q = q * (float)(1 / sqrtf(d));  a = proj(o) + b;
+ *                    CAB on the same y (unshifted, not windowed; zero padding 1 at the border of the padded image):
+ *                          t = gelu(conv3x3 C -> n_mid (y));  u = conv3x3 n_mid -> C (t);  m[c] = the mean of u[c] over the whole
+ *                          Hp x Wp PADDED image, float64 in sr_rcan's fixed order (row chunks of 32, no atomics);
+ *                          sc = sigmoid(W2 relu(W1 m + b1) + b2) in float64, as sr_rcan_attention_f32;
+ *                    x = fmaf(conv_scale, u * sc, x + a):  x + a is one rounded add (proj's skip), u * sc one rounded fp32
+ *                          product, and the scaled add ONE fmaf (as RCAN's res_scale) -- not a rounded product and an add;
+ *                    x = x + fc2(gelu(fc1(LN2(x)))).
+ *                OCAB (no shift, no mask):
+ *                    y = LN1(x);  [q k v] = W y + b as above;  q scaled as above;  the queries of window (by, bx) are its 256
+ *                    pixels;  the keys are the 576 positions (16 by - 4 + ky, 16 bx - 4 + kx), 0 <= ky, kx < 24;  a key position
+ *                    outside the padded image has k = v = 0 EXACTLY (nn.Unfold zero-pads after the projection: the bias does not
+ *                    enter) and is NOT masked: its score is 0 + bias, it takes its share of the softmax and adds nothing;
+ *                    a[i][j] = q_i . k_j + B_oca[rpi_oca[i][j]][head], B_oca [1521][heads], rpi_oca [256][576];  softmax over the
+ *                    576 keys;  x = x + (proj o + b);  x = x + fc2(gelu(fc1(LN2(x)))).
+ *                rpi_oca: when the caller supplies an index (HAT's persistent buffer relative_position_index_OCA), THAT index is
+ *                used: every value must lie in [-1521, 1520] and a negative one is wrapped once by + 1521 (torch's indexing).
+ *                Without one, the default is the formula as recalled from calculate_rpi_oca -- unverified against the official
+ *                code: (ky - qy - 7) * 39 + (kx - qx - 7), wrapped the same way.  The window attention's index is computed; a
+ *                state's relative_position_index_SA must equal it; attn_mask buffers are ignored.  Where the keys sit: HAT
+ *                registers both buffers once, on the top-level module, so a checkpoint holds the bare keys
+ *                relative_position_index_SA and relative_position_index_OCA; sr_network.parse_hat_state reads every key that
+ *                ends in one of the two names (top level or nested), never ignores one, and wants all OCA copies equal.
+ * HAT's defaults, which a state dict does not hold: conv_scale 0.01, range 1, mean (0.4488, 0.4371, 0.4040).
+ * Summation orders.  Convolutions, linear layers, head, skips: as SwinIR.  Both attention kernels make three sweeps over the
+ * keys and recompute the score in each by the same instruction sequence (equal bits): the dot product is an fmaf chain from +0
+ * over dd ascending; then + B, then (window attention, shift 8) + the mask (two adds); sweep 1 takes the exact maximum; sweep 2
+ * sums e_j = expf(a_j - max) over the keys j ascending from +0; sweep 3 forms p_j = e_j / sum (the division comes BEFORE the p v
+ * sum) and adds p_j v_j[dd] as an fmaf chain from +0 over j ascending.  No atomics.  Nothing depends on tail.  Equal inputs
+ * give equal bits.
+ * Anything outside the ranges above (a window other than 16, an overlap window other than 24, a non-finite constant, range 0) is
+ * SR_ERR_UNSUPPORTED, decided on the host before any device call.  Out of scope: other windows and overlap ratios,
+ * resi_connection 'identity', ape, upsamplers other than pixelshuffle, x1 and x8, fp16 / bf16, the ImageNet-pretraining heads.
+ * The trunk (steps 1 .. 4) runs on the padded image in ONE piece: five planar fp32 buffers of Cp = C rounded up to 64 planes of
+ * P0 = Hp Wp floats (h / f, the RHAG input, x, LN / attention output, the CAB's output), one of Tp = n_mid rounded up to 64 (the
+ * CAB's middle tensor) and one of Qp = max(3 C, n_hidden each rounded up to 64) (qkv, then the MLP's hidden tensor):
+ * 4 (5 Cp + Tp + Qp) bytes per pixel, 6400 at C = 180, n_mid 60, hidden 360.  The reconstruction runs in tail x tail sub-pieces as
+ * SwinIR's.  Every tail gives the same bits.
+ * sr_hat_create: h_w[k] / h_b[k] = the tables in forward order (dense fp32, weight then bias):
+ *     conv_first [C][3][3][3];  patch_embed.norm (gamma[C], beta[C]);
+ *     per RHAG i, per HAB j (residual_group.blocks.j):  norm1;  attn.qkv [3 C][C];  attn.relative_position_bias_table [961][heads]
+ *         (its h_b entry is ignored and may be NULL);  attn.proj [C][C];  conv_block.cab.0 [n_mid][C][3][3];  conv_block.cab.2
+ *         [C][n_mid][3][3];  conv_block.cab.3.attention.1 [n_squeeze][C];  conv_block.cab.3.attention.3 [C][n_squeeze];  norm2;
+ *         mlp.fc1 [hidden][C];  mlp.fc2 [C][hidden];
+ *     then the OCAB (residual_group.overlap_attn):  norm1;  qkv [3 C][C];  relative_position_bias_table [1521][heads] (no bias);
+ *         proj;  norm2;  mlp.fc1;  mlp.fc2;  then the RHAG's conv [C][C][3][3];
+ *     norm;  conv_after_body;  conv_before_upsample.0 [64][C][3][3];  upsample.0 (and .2) [64 r^2][64][3][3];  conv_last.
+ *     n_tables must be 2 + L (11 D + 8) + 2 + (3 or 4).  h_rpi_oca: NULL for the default formula, else [256][576] ints.
+ * sr_hat_plan (host only): as sr_swinir_plan;  *workspace_bytes = 4 (5 Cp + Tp + Qp) P0 + 4 * 2 * 64 P4 + 3 P0 + 8 C ceil(Hp / 32)
+ * + 4 C (the trunk, the tail buffers, the reflected u8 image, the chunk sums and the attention vector).  tail 0: 256.
+ * sr_hat_rel_index (host only): rel[i * 256 + j] = rel(i, j); n must be 65536.
+ * sr_hat_oca_index (host only): idx[i * 576 + j] = the default rpi_oca, wrapped; n must be 147456.
+ * sr_hat_attention_f32 / sr_hat_oca_f32 (for inspection; synchronous): the window attention (shift 0 or 8, h_table [961][heads])
+ * and the overlapping cross-attention (h_table [1521][heads], h_index NULL or [256][576]) from a[i][j] to o, before proj, on a
+ * planar qkv tensor of 3 C planes of hp x wp (multiples of 16) whose q planes are already scaled, into the C planes of d_out.
+ * sr_hat_fill_workspace (for tests): as sr_swinir_fill_workspace.
+ * Errors as SwinIR's, the row limit taken on the padded image (Hp above 262140 rows): SR_ERR_SHAPE for P0 above INT_MAX / 32, P4 above INT_MAX / 8 and a trunk above SR_HAT_TRUNK_CAP = 32 GiB
+ * (the same policy as SR_SWINIR_TRUNK_CAP; the message names the cap and the largest input that fits), SR_ERR_INVALID_ARG for an
+ * index value outside [-1521, 1520] -- all before any launch.  Asynchronous, except the two inspection entry points. */
+#define SR_HAT_TRUNK_CAP ((size_t)32 << 30)
+typedef struct sr_hat_desc {
+    int n_feat, n_heads, n_hidden, n_mid, n_squeeze, n_groups, depth, scale;
+    float conv_scale, mean[3], range;
+} sr_hat_desc;
+typedef struct sr_hat_model sr_hat_model;
+SR_API int sr_hat_create(sr_ctx *ctx, const sr_hat_desc *desc, const float *const *h_w, const float *const *h_b, int n_tables,
+                         const int *h_rpi_oca, sr_hat_model **out);
+SR_API int sr_hat_destroy(sr_hat_model *model);
+SR_API int sr_hat_plan(const sr_hat_desc *desc, int h, int w, int tail, int *hp, int *wp, int *halo, int *n_tail_tiles,
+                       size_t *workspace_bytes);
+SR_API int sr_hat_rel_index(int *rel, int n);
+SR_API int sr_hat_oca_index(int *idx, int n);
+SR_API int sr_hat_u8(sr_hat_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst, int64_t dst_stride,
+                     int tail);
+SR_API int sr_hat_f32(sr_hat_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst, int64_t dst_stride,
+                      int tail);
+SR_API int sr_hat_fill_workspace(sr_hat_model *model, int h, int w, int tail, int byte);
+SR_API int sr_hat_attention_f32(sr_ctx *ctx, const float *d_qkv, int64_t plane_stride, int64_t row_stride, int n_feat, int n_heads,
+                                int hp, int wp, int shift, const float *h_table, float *d_out, int64_t out_plane_stride,
+                                int64_t out_row_stride);
+SR_API int sr_hat_oca_f32(sr_ctx *ctx, const float *d_qkv, int64_t plane_stride, int64_t row_stride, int n_feat, int n_heads, int hp,
+                          int wp, const float *h_table, const int *h_index, float *d_out, int64_t out_plane_stride,
+                          int64_t out_row_stride);
+
 /* ---- geometric self-ensemble of the local SR backends (csrc/sr_ensemble.hip) ------------------------------------------------
  * The "+" results of the SR literature (EDSR+, RCAN+: Timofte et al., Lim et al.): the network runs on the eight flips and
  * rotations of the input, each output is mapped back and the eight are averaged.  No new weights; the forwards are the
@@ -1264,6 +1370,11 @@ SR_API int sr_swinir_ens_u8(sr_swinir_model *model, const uint8_t *d_src, int64_
                             int64_t dst_stride, int tail, int mask);
 SR_API int sr_swinir_ens_f32(sr_swinir_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
                              int64_t dst_stride, int tail, int mask);
+/* HAT+: as SwinIR+; each member also pools the CAB's mean over its own padded planes. */
+SR_API int sr_hat_ens_u8(sr_hat_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                         int64_t dst_stride, int tail, int mask);
+SR_API int sr_hat_ens_f32(sr_hat_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                          int64_t dst_stride, int tail, int mask);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,13 @@ class SwinirDesc(C.Structure):
                 ("scale", C.c_int), ("upsampler", C.c_int), ("mean", C.c_float * 3), ("range", C.c_float)]
 
 
+class HatDesc(C.Structure):
+    """sr_hat_desc (include/sr_hip.h)."""
+    _fields_ = [("n_feat", C.c_int), ("n_heads", C.c_int), ("n_hidden", C.c_int), ("n_mid", C.c_int), ("n_squeeze", C.c_int),
+                ("n_groups", C.c_int), ("depth", C.c_int), ("scale", C.c_int), ("conv_scale", C.c_float), ("mean", C.c_float * 3),
+                ("range", C.c_float)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("launches", C.c_int64)]
 
@@ -321,6 +328,18 @@ SIGNATURES = {
     "sr_rcan_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
     "sr_swinir_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
     "sr_swinir_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_hat_create": (_i, [_vp, C.POINTER(HatDesc), C.POINTER(_vp), C.POINTER(_vp), _i, _vp, C.POINTER(_vp)]),
+    "sr_hat_destroy": (_i, [_vp]),
+    "sr_hat_plan": (_i, [C.POINTER(HatDesc), _i, _i, _i, _pi, _pi, _pi, _pi, C.POINTER(_sz)]),
+    "sr_hat_rel_index": (_i, [_vp, _i]),
+    "sr_hat_oca_index": (_i, [_vp, _i]),
+    "sr_hat_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_hat_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_hat_fill_workspace": (_i, [_vp, _i, _i, _i, _i]),
+    "sr_hat_attention_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i64, _i64]),
+    "sr_hat_oca_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _i64]),
+    "sr_hat_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_hat_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
 }
 
 
@@ -1900,7 +1919,7 @@ def ens_finish(ctx, d_acc: int, acc_stride: int, H: int, W: int, n: int, d_dst: 
 
 
 class _SrModel:
-    """What SrNetModel, ResNetModel, RrdbModel, RcanModel and SwinirModel share: the caller's tables as checked fp32 arrays, the create call, the two
+    """What SrNetModel, ResNetModel, RrdbModel, RcanModel, SwinirModel and HatModel share: the caller's tables as checked fp32 arrays, the create call, the two
     forwards, close.  ``_kind`` names the sr_<kind>_* entry points, ``_run_args`` what their forwards take after the
     destination stride."""
     _kind = ""
@@ -2262,6 +2281,157 @@ def swinir_attention(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat
     _check_unsupported(load().sr_swinir_attention_f32(_ctx_handle(ctx), C.c_void_p(d_qkv), int(plane_stride), int(row_stride), int(n_feat),
                                                       int(n_heads), int(hp), int(wp), int(shift), t.ctypes.data_as(C.c_void_p), C.c_void_p(d_out),
                                                       int(out_plane_stride), int(out_row_stride)))
+
+
+# ------------------------------------------------------------------------------------------
+# local SR network, HAT (sr_hat_*): sr_network.HATSRNet parses HAT state dicts into these arrays
+# ------------------------------------------------------------------------------------------
+HAT_WINDOW, HAT_OVERLAP_WINDOW = 16, 24
+HAT_REL_ROWS = (2 * HAT_WINDOW - 1) ** 2                          # 961
+HAT_OCA_ROWS = (HAT_WINDOW + HAT_OVERLAP_WINDOW - 1) ** 2         # 1521
+
+
+def hat_desc(n_feat: int, n_heads: int, n_hidden: int, n_mid: int, n_squeeze: int, n_groups: int, depth: int, scale: int,
+             conv_scale: float = 0.01, mean=(0.0, 0.0, 0.0), range: float = 1.0) -> HatDesc:  # noqa: A002 (the header's name)
+    mean = [float(v) for v in np.asarray(mean, dtype=np.float64).reshape(-1)]
+    if len(mean) != 3:
+        raise ValueError(f"mean holds 3 values, got {len(mean)}")
+    return HatDesc(int(n_feat), int(n_heads), int(n_hidden), int(n_mid), int(n_squeeze), int(n_groups), int(depth), int(scale),
+                   float(conv_scale), (C.c_float * 3)(*mean), float(range))
+
+
+def hat_table_names(desc: HatDesc) -> List[str]:
+    """HAT's name of every table in sr_hat_create's order (weight key = name + '.weight', bias key = name + '.bias'; a bias
+    table's key is the name itself and it has no bias)."""
+    names = ["conv_first", "patch_embed.norm"]
+    for i in range(desc.n_groups):
+        for j in range(desc.depth):
+            b = f"layers.{i}.residual_group.blocks.{j}"
+            names += [f"{b}.norm1", f"{b}.attn.qkv", f"{b}.attn.relative_position_bias_table", f"{b}.attn.proj", f"{b}.conv_block.cab.0",
+                      f"{b}.conv_block.cab.2", f"{b}.conv_block.cab.3.attention.1", f"{b}.conv_block.cab.3.attention.3", f"{b}.norm2",
+                      f"{b}.mlp.fc1", f"{b}.mlp.fc2"]
+        o = f"layers.{i}.residual_group.overlap_attn"
+        names += [f"{o}.norm1", f"{o}.qkv", f"{o}.relative_position_bias_table", f"{o}.proj", f"{o}.norm2", f"{o}.mlp.fc1", f"{o}.mlp.fc2",
+                  f"layers.{i}.conv"]
+    names += ["norm", "conv_after_body", "conv_before_upsample.0"]
+    return names + [f"upsample.{2 * k}" for k in range(2 if desc.scale == 4 else 1)] + ["conv_last"]
+
+
+def hat_table_shapes(desc: HatDesc) -> List[Tuple[tuple, Optional[tuple]]]:
+    """(weight shape, bias shape) of every table in sr_hat_create's order; a bias table has no bias (None).  The two 1 x 1
+    layers of a CAB's attention are (out, in); (out, in, 1, 1) arrays are accepted for them."""
+    Cn, nh, hid, mid, sq, s = desc.n_feat, desc.n_heads, desc.n_hidden, desc.n_mid, desc.n_squeeze, desc.scale
+    ln = ((Cn,), (Cn,))
+
+    def conv(co, ci):
+        return ((co, ci, 3, 3), (co,))
+
+    mlp = [ln, ((hid, Cn), (hid,)), ((Cn, hid), (Cn,))]
+    hab = [ln, ((3 * Cn, Cn), (3 * Cn,)), ((HAT_REL_ROWS, nh), None), ((Cn, Cn), (Cn,)), conv(mid, Cn), conv(Cn, mid), ((sq, Cn), (sq,)),
+           ((Cn, sq), (Cn,))] + mlp
+    ocab = [ln, ((3 * Cn, Cn), (3 * Cn,)), ((HAT_OCA_ROWS, nh), None), ((Cn, Cn), (Cn,))] + mlp
+    shapes = [conv(Cn, 3), ln] + (hab * desc.depth + ocab + [conv(Cn, Cn)]) * desc.n_groups + [ln, conv(Cn, Cn)]
+    return shapes + [conv(64, Cn)] + [conv(64 * r * r, 64) for r in ([2, 2] if s == 4 else [s])] + [conv(3, 64)]
+
+
+def hat_plan(desc: HatDesc, h: int, w: int, tail: int = 0) -> Tuple[int, int, int, int, int]:
+    """sr_hat_plan (host only) -> (padded rows, padded columns, the tail's halo, tail sub-pieces, workspace bytes)."""
+    hp, wp, halo, nt, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check_unsupported(load().sr_hat_plan(C.byref(desc), int(h), int(w), int(tail), C.byref(hp), C.byref(wp), C.byref(halo), C.byref(nt),
+                                          C.byref(ws)))
+    return hp.value, wp.value, halo.value, nt.value, int(ws.value)
+
+
+def hat_rel_index() -> np.ndarray:
+    """sr_hat_rel_index (host only) -> (256, 256) int32: the bias-table row of (query token, key token) of a 16 x 16 window."""
+    rel = np.empty((256, 256), np.int32)
+    check(load().sr_hat_rel_index(rel.ctypes.data_as(C.c_void_p), rel.size))
+    return rel
+
+
+def hat_oca_index() -> np.ndarray:
+    """sr_hat_oca_index (host only) -> (256, 576) int32: the default index of the overlapping cross-attention, wrapped."""
+    idx = np.empty((256, 576), np.int32)
+    check(load().sr_hat_oca_index(idx.ctypes.data_as(C.c_void_p), idx.size))
+    return idx
+
+
+def _hat_index(index, name: str = "relative_position_index_OCA") -> Optional[np.ndarray]:
+    """A caller's relative_position_index_OCA as contiguous int32 (256, 576), every value in [-1521, 1520]; None stays None.
+    ``name``: what a ValueError calls it (a state dict's key)."""
+    if index is None:
+        return None
+    a = np.asarray(index)
+    if a.shape != (256, 576) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name}: expected an integer array of shape (256, 576), got {a.dtype} {a.shape}")
+    if a.min() < -HAT_OCA_ROWS or a.max() >= HAT_OCA_ROWS:
+        raise ValueError(f"{name}: values must lie in [-{HAT_OCA_ROWS}, {HAT_OCA_ROWS - 1}], got [{int(a.min())}, {int(a.max())}]")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class HatModel(_SrModel):
+    """sr_hat_model: a HAT resident on the GPU.  weights / biases: one fp32 array each per table in forward order
+    (hat_table_shapes / hat_table_names); the bias entry of a relative-position table is ignored (None is fine).  ``rpi_oca``:
+    the state's relative_position_index_OCA (256, 576), or None for the default formula.  The trunk is one piece, so the
+    forwards take ``tail`` alone."""
+    _kind = "hat"
+    _run_args = ("tail",)
+
+    def __init__(self, ctx: Context, desc: HatDesc, weights, biases, rpi_oca=None):
+        hat_plan(desc, 1, 1)                                     # the supported range, refused before any array is touched
+        shapes = hat_table_shapes(desc)
+        if len(weights) != len(shapes) or len(biases) != len(shapes):
+            raise ValueError(f"this HAT has {len(shapes)} tables, got {len(weights)} weight / {len(biases)} bias arrays")
+        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
+        bs = [np.zeros(1, np.float32) if sb is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a, (_, sb) in zip(biases, shapes)]
+        for k, (w, b, (sw, sb)) in enumerate(zip(ws, bs, shapes)):
+            ok = w.shape == sw or (len(sw) == 2 and w.shape == sw + (1, 1))
+            if not ok or (sb is not None and b.shape != sb):
+                raise ValueError(f"HAT table {k}: expected {sw} / {sb}, got {w.shape} / {b.shape}")
+        self.desc, self.scale = desc, desc.scale
+        self._rpi = _hat_index(rpi_oca)
+        self._create(ctx, (C.byref(desc),), ws, bs)
+
+    def _create(self, ctx: Context, args, ws, bs):
+        ptrs = [(C.c_void_p * len(t))(*[a.ctypes.data for a in t]) for t in (ws, bs)]
+        h = C.c_void_p()
+        rpi = None if self._rpi is None else self._rpi.ctypes.data_as(C.c_void_p)
+        _check_unsupported(ctx.lib.sr_hat_create(ctx.handle, *args, *ptrs, len(ws), rpi, C.byref(h)))
+        self.ctx, self.handle = ctx, h
+
+    def plan(self, h: int, w: int, tail: int = 0):
+        return hat_plan(self.desc, h, w, tail)
+
+    def fill_workspace(self, h: int, w: int, byte: int, tail: int = 0):
+        """sr_hat_fill_workspace: the buffers of an h x w forward, grown and filled with ``byte`` (for tests)."""
+        check(self.ctx.lib.sr_hat_fill_workspace(self.handle, int(h), int(w), int(tail), int(byte)))
+
+
+def hat_attention(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat: int, n_heads: int, hp: int, wp: int, shift: int, table,
+                  d_out: int, out_plane_stride: int, out_row_stride: int):
+    """sr_hat_attention_f32: the 16 x 16 window attention (before proj) on a planar qkv tensor of 3 C planes whose q planes are
+    already scaled; ``table``: the (961, heads) relative-position bias table; into the C planes of d_out.  Synchronous."""
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    if 1 <= int(n_heads) <= 256 and t.shape != (HAT_REL_ROWS, int(n_heads)):
+        raise ValueError(f"the bias table is {(HAT_REL_ROWS, int(n_heads))}, got {t.shape}")
+    _check_unsupported(load().sr_hat_attention_f32(_ctx_handle(ctx), C.c_void_p(d_qkv), int(plane_stride), int(row_stride), int(n_feat),
+                                                   int(n_heads), int(hp), int(wp), int(shift), t.ctypes.data_as(C.c_void_p), C.c_void_p(d_out),
+                                                   int(out_plane_stride), int(out_row_stride)))
+
+
+def hat_oca(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat: int, n_heads: int, hp: int, wp: int, table, index, d_out: int,
+            out_plane_stride: int, out_row_stride: int):
+    """sr_hat_oca_f32: the overlapping cross-attention (before proj) on a planar qkv tensor of 3 C planes whose q planes are
+    already scaled; ``table``: the (1521, heads) bias table; ``index``: (256, 576) integers in [-1521, 1520] or None for the
+    default formula; into the C planes of d_out.  Synchronous."""
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    if 1 <= int(n_heads) <= 256 and t.shape != (HAT_OCA_ROWS, int(n_heads)):
+        raise ValueError(f"the bias table is {(HAT_OCA_ROWS, int(n_heads))}, got {t.shape}")
+    idx = _hat_index(index)
+    _check_unsupported(load().sr_hat_oca_f32(_ctx_handle(ctx), C.c_void_p(d_qkv), int(plane_stride), int(row_stride), int(n_feat),
+                                             int(n_heads), int(hp), int(wp), t.ctypes.data_as(C.c_void_p),
+                                             None if idx is None else idx.ctypes.data_as(C.c_void_p), C.c_void_p(d_out),
+                                             int(out_plane_stride), int(out_row_stride)))
 
 
 _default_ctx = {}

@@ -96,7 +96,7 @@ inline int backward_halo(const ExtStep *steps, int n)
     return g;
 }
 
-// The convolution launch of sr_resnet.hip, sr_rrdb.hip, sr_rcan.hip and sr_swinir.hip.  in: the tensor read (its first cin planes); out: pointer to the
+// The convolution launch of sr_resnet.hip, sr_rrdb.hip, sr_rcan.hip, sr_swinir.hip and sr_hat.hip.  in: the tensor read (its first cin planes); out: pointer to the
 // element (cout 0, ya, xa) of the output -- or, for a replicating or shuffling epilogue, of the output at its own resolution.
 template <typename Kernel, typename Epi>
 inline void launch_conv(Kernel kernel, hipStream_t st, const PlanarTen &in, int H_in, int W_in, int cin, int ncout_tiles, const float *dw,

@@ -26,6 +26,8 @@
 //   tail phase   after f nothing is global: the upsampling stages and conv_last run in tail x tail sub-pieces of the input over
 //                their backward extents (backward_extents, as sr_rrdb.hip's tail phase), two F-plane ping-pong buffers.
 //
+// The three kernels of the channel attention (k_rc_rowsum, k_rc_attention, k_rc_scale) are sr_chan_attn.h, shared with
+// sr_hat.hip's CAB.
 // The channel mean (the order every restatement follows): the image's rows are cut into chunks of RC_ROWS = 32.  One block of
 // 256 threads per (channel, chunk): thread t adds, in float64, rows ascending and within a row the columns t, t + 256, ..
 // ascending -- valid pixels only, never a padded column; the 256 sums are then folded in LDS, a[t] += a[t + k] for
@@ -42,12 +44,13 @@
 #include <cstring>
 #include <vector>
 
+#include "sr_chan_attn.h"
 #include "sr_net_common.h"
 
 namespace {
 
 constexpr size_t RC_TRUNK_CAP = SR_RCAN_TRUNK_CAP;     // the five trunk buffers of one image stay under 16 GiB (a policy)
-constexpr int RC_TRUNK_BUFS = 5, RC_DEFAULT_TAIL = 256, RC_ROWS = 32;
+constexpr int RC_TRUNK_BUFS = 5, RC_DEFAULT_TAIL = 256;         // RC_ROWS: sr_chan_attn.h
 constexpr int RC_MAX_ROWS = 65535 * 4;                 // rows of one launch: the head's grid is rows / 4 blocks high
 constexpr int RC_MAX_G = 16, RC_MAX_B = 32;
 
@@ -161,87 +164,6 @@ __global__ __launch_bounds__(256) void k_rc_conv(const float *__restrict__ in, l
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Row-chunk sums of a planar tensor, float64.  grid (chunks, F), block 256: block (k, c) sums plane c over the rows
-// [k RC_ROWS, min((k + 1) RC_ROWS, h)) and the columns [0, w) in the order written at the top of this file and stores
-// part[c * chunks + k].  plane / pitch in floats.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_rc_rowsum(const float *__restrict__ x, long long plane, long long pitch, int h, int w,
-                                                   double *__restrict__ part)
-{
-    __shared__ double a[256];
-    const int t = threadIdx.x, k = blockIdx.x, c = blockIdx.y;
-    const int r0 = k * RC_ROWS, r1 = min(r0 + RC_ROWS, h);
-    const float *p = x + (size_t)c * plane;
-    double s = 0.0;
-    for (int r = r0; r < r1; ++r) {
-        const float *row = p + (size_t)r * pitch;
-        for (int col = t; col < w; col += 256) s += (double)row[col];
-    }
-    a[t] = s;
-    __syncthreads();
-#pragma unroll
-    for (int k2 = 128; k2 >= 1; k2 >>= 1) {
-        if (t < k2) a[t] += a[t + k2];
-        __syncthreads();
-    }
-    if (t == 0) part[(size_t)c * gridDim.x + k] = a[0];
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The channel attention of one RCAB, one block of 256 threads (F <= 256, R <= F): the ordered sum of a channel's chunk sums,
-// the mean, the two 1 x 1 layers and the sigmoid in float64; s[F] (and mean[F] where asked) to device memory.
-// w1 [R][F], w2 [F][R] dense fp32.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_rc_attention(const double *__restrict__ part, int chunks, double count, int F, int R,
-                                                      const float *__restrict__ w1, const float *__restrict__ b1,
-                                                      const float *__restrict__ w2, const float *__restrict__ b2,
-                                                      float *__restrict__ s_out, float *__restrict__ mean_out)
-{
-    __shared__ float m[256];
-    __shared__ double z1[256];
-    const int t = threadIdx.x;
-    if (t < F) {
-        const double *p = part + (size_t)t * chunks;
-        double S = 0.0;
-        for (int k = 0; k < chunks; ++k) S += p[k];
-        m[t] = (float)(S / count);
-        if (mean_out) mean_out[t] = m[t];
-    }
-    __syncthreads();
-    if (t < R) {
-        double z = (double)b1[t];
-        for (int c = 0; c < F; ++c) z += (double)w1[(size_t)t * F + c] * (double)m[c];
-        z1[t] = z > 0.0 ? z : 0.0;
-    }
-    __syncthreads();
-    if (t < F) {
-        double z = (double)b2[t];
-        for (int j = 0; j < R; ++j) z += (double)w2[(size_t)t * R + j] * z1[j];
-        s_out[t] = (float)(1.0 / (1.0 + exp(-z)));
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Scale-and-skip: out[c] = fmaf(res_scale, y2[c] * s[c], t[c]) over whole planes (padded columns included: they are never
-// read as pixels), four floats per thread; the product is rounded to fp32 first.  grid (ceil(plane4 / 256), F); out may be t.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_rc_scale(const float4 *__restrict__ y2, const float *__restrict__ s, const float4 *t, float4 *out,
-                                                  long long plane4, float res_scale)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= plane4) return;
-    const size_t e = (size_t)blockIdx.y * plane4 + i;
-    const float sc = s[blockIdx.y];
-    const float4 y = y2[e], v = t[e];
-    float4 o;
-    o.x = fmaf(res_scale, y.x * sc, v.x);
-    o.y = fmaf(res_scale, y.y * sc, v.y);
-    o.z = fmaf(res_scale, y.z * sc, v.z);
-    o.w = fmaf(res_scale, y.w * sc, v.w);
-    out[e] = o;
-}
-
 int rc_check_desc(const char *who, const sr_rcan_desc *d)
 {
     if (!d) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null description", who);
@@ -349,19 +271,6 @@ int rc_geometry(const char *who, const sr_rcan_desc &d, int h, int w, int tail, 
     g.workspace_bytes = ((size_t)RC_TRUNK_BUFS * F * (size_t)g.plane0 + (size_t)2 * F * (size_t)g.plane_t) * sizeof(float) +
                         (size_t)F * g.chunks * sizeof(double) + (size_t)F * sizeof(float);
     return SR_OK;
-}
-
-// The reduction and the attention of one RCAB on x (F planes): part gets F x chunks doubles, s (and mean, if not null) F floats.
-void rc_attention(hipStream_t st, sr_ctx *ctx, const float *x, long long plane, long long pitch, int h, int w, int F, int R, const float *w1,
-                  const float *b1, const float *w2, const float *b2, double *part, float *s, float *mean)
-{
-    const int chunks = (h + RC_ROWS - 1) / RC_ROWS;
-    {
-        ProfScope ps(ctx, "rcan_reduce");
-        hipLaunchKernelGGL(k_rc_rowsum, dim3(chunks, F), dim3(256), 0, st, x, plane, pitch, h, w, part);
-    }
-    ProfScope ps(ctx, "rcan_attention");
-    hipLaunchKernelGGL(k_rc_attention, dim3(1), dim3(256), 0, st, part, chunks, (double)h * (double)w, F, R, w1, b1, w2, b2, s, mean);
 }
 
 }  // namespace

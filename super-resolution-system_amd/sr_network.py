@@ -704,16 +704,225 @@ def _swinir_extras(state: Mapping) -> dict:
     return _scalar_extras(state, (("img_range", 1), ("rgb_mean", 3)))
 
 
+# ------------------------------------------------------------------------------------------
+# HAT: the hybrid attention transformer (Chen et al., CVPR 2023), run by csrc/sr_hat.hip: a Swin trunk with 16 x 16 windows, a
+# channel-attention convolution branch (CAB) beside every window attention and an overlapping cross-attention block (OCAB) at
+# the end of every group.  PARITY UNPINNED here too: neither the HAT package nor a checkpoint exists offline; the arithmetic is
+# written out in include/sr_hip.h and held against a torch-CPU restatement (tests/_hat_ref.py).  The one piece restated from
+# memory with the least confidence is the index of the overlapping cross-attention: a state's own
+# ``relative_position_index_OCA`` buffer is used when it is there, the recalled formula only when it is not.
+# ------------------------------------------------------------------------------------------
+HAT_KEY = "layers.0.residual_group.overlap_attn.qkv.weight"      # what tells a HAT state from a SwinIR one
+HAT_RGB_MEAN = EDSR_RGB_MEAN                                     # HAT's defaults: the DIV2K mean, img_range 1, conv_scale 0.01
+HAT_IMG_RANGE = 1.0
+HAT_CONV_SCALE = 0.01
+
+
+def parse_hat_state(state: Mapping, img_range: float = HAT_IMG_RANGE, rgb_mean=HAT_RGB_MEAN, conv_scale: float = HAT_CONV_SCALE):
+    """-> (_native.HatDesc, weights, biases, rpi_oca) in sr_hat_create's order (_native.hat_table_names), contiguous fp32; the
+    bias entry of a relative-position table is None; rpi_oca is the state's ``relative_position_index_OCA`` as int32
+    (256, 576) -- negative values allowed, the library wraps them -- or None where the state holds none (the default formula).
+
+    HAT's key names.  The whole description is read off the shapes: embed_dim from ``conv_first``, the heads from the second
+    axis of ``relative_position_bias_table``, window 16 from its 961 rows, the overlap window 24 from the 1521 rows of the
+    OCAB's table, the hidden width from ``mlp.fc1``, the CAB's widths from ``conv_block.cab.0`` and
+    ``conv_block.cab.3.attention.1``, the groups and their depth from the numbering, the scale from the upsampling
+    convolutions' widths.  The two index buffers are looked for under every key that ends in their name: HAT registers them once
+    on the top-level module, so a checkpoint holds the bare keys ``relative_position_index_SA`` and
+    ``relative_position_index_OCA``; nested copies are read the same way.  Every ``relative_position_index_SA`` must equal the
+    computed index, every ``relative_position_index_OCA`` must agree with the others and is the index used; ``attn_mask``
+    buffers are ignored.  A ValueError names the offending key for a wrong shape and for everything out of scope (other
+    windows, other overlap ratios, resi_connection 'identity', the absolute position embedding, upsamplers other than
+    pixelshuffle, fp16 / bf16); what only the kernels' ranges exclude is a NotImplementedError."""
+    state = _unwrap(state)
+    keys = {str(k) for k in state}
+    if HAT_KEY not in keys:
+        raise ValueError(f"{HAT_KEY}: not in the state (not a HAT)")
+    if "absolute_pos_embed" in keys:
+        raise ValueError("absolute_pos_embed: the absolute position embedding (ape=True) is not supported")
+    if "layers.0.conv.0.weight" in keys:
+        raise ValueError("layers.0.conv.0.weight: only resi_connection '1conv' is supported")
+    if "layers.0.conv.weight" not in keys:
+        raise ValueError("layers.0.conv.weight: not in the state (resi_connection 'identity' is not supported, only '1conv')")
+    for k in sorted(keys):
+        name = str(getattr(state[k], "dtype", ""))
+        if "float16" in name or "bfloat16" in name:
+            raise ValueError(f"{k}: {name} weights are not supported (fp32 only)")
+    tables = []
+
+    def conv(name: str, cin: int, cout=None):
+        tables.append(_read_conv(state, keys, name, cin, cout, ", expected {}"))
+        return tables[-1][0]
+
+    def dense(name: str, w_shape, b_shape, part_w: str = "weight"):
+        tables.append(_read_dense(state, keys, name, w_shape, b_shape, part_w))
+
+    def pointwise(name: str, cout: int, cin: int):              # a 1 x 1 convolution: (out, in, 1, 1) or (out, in)
+        for part in ("weight", "bias"):
+            if f"{name}.{part}" not in keys:
+                raise ValueError(f"{name}.{part}: not in the state")
+        w = np.ascontiguousarray(_array(state, f"{name}.weight"), dtype=np.float32)
+        b = np.ascontiguousarray(_array(state, f"{name}.bias"), dtype=np.float32).reshape(-1)
+        if w.shape not in ((cout, cin), (cout, cin, 1, 1)):
+            raise ValueError(f"{name}.weight: expected shape {(cout, cin, 1, 1)}, got {w.shape}")
+        if b.shape != (cout,):
+            raise ValueError(f"{name}.bias: expected {cout} values, got {b.shape}")
+        tables.append((w.reshape(cout, cin), b))
+
+    def shape_of(key: str):
+        if key not in keys:
+            raise ValueError(f"{key}: not in the state")
+        return tuple(np.shape(_array(state, key)))
+
+    Cn = int(conv("conv_first", 3).shape[0])
+    dense("patch_embed.norm", (Cn,), (Cn,))
+    groups = sorted({int(m.group(1)) for m in map(_SWINIR_LAYER_KEY.match, keys) if m})
+    if not groups or groups != list(range(len(groups))):
+        gap = next(i for i in range(len(groups) + 1) if i not in groups)
+        raise ValueError(f"layers.{gap}.conv.weight: the groups must be numbered 0 .. L - 1, got {groups}")
+    rows, orows = _native.HAT_REL_ROWS, _native.HAT_OCA_ROWS
+    tkey = "layers.0.residual_group.blocks.0.attn.relative_position_bias_table"
+    tshape = shape_of(tkey)
+    if len(tshape) != 2 or tshape[0] != rows:
+        raise ValueError(f"{tkey}: shape {tshape} is not a window of 16 ({rows} rows): only window_size 16 is supported")
+    heads = int(tshape[1])
+    okey = "layers.0.residual_group.overlap_attn.relative_position_bias_table"
+    oshape = shape_of(okey)
+    if len(oshape) != 2 or oshape[0] != orows:
+        raise ValueError(f"{okey}: shape {oshape} is not an overlap window of 24 ({orows} rows): only overlap_ratio 0.5 of window 16 is supported")
+    hidden = int(shape_of("layers.0.residual_group.blocks.0.mlp.fc1.weight")[0])
+    mid = int(shape_of("layers.0.residual_group.blocks.0.conv_block.cab.0.weight")[0])
+    squeeze = int(shape_of("layers.0.residual_group.blocks.0.conv_block.cab.3.attention.1.weight")[0])
+    # The two index buffers, wherever the state holds them: HAT registers them once on the top-level module (the bare keys
+    # ``relative_position_index_SA`` / ``relative_position_index_OCA``); a nested copy (``...attn.relative_position_index_SA``,
+    # ``...overlap_attn.relative_position_index_OCA``) is read the same way.  None is ever ignored.
+    rpi_oca, first = None, None
+    for ikey in sorted(k for k in keys if k.endswith("relative_position_index_SA")):
+        got, rel = np.asarray(_array(state, ikey)), _native.hat_rel_index()
+        if got.shape != rel.shape or not np.array_equal(got, rel):
+            raise ValueError(f"{ikey}: differs from the relative-position index of a 16 x 16 window that the kernels compute")
+    for ikey in sorted(k for k in keys if k.endswith("relative_position_index_OCA")):
+        got = _native._hat_index(np.asarray(_array(state, ikey)), ikey)
+        if rpi_oca is not None and not np.array_equal(got, rpi_oca):
+            raise ValueError(f"{ikey}: differs from {first} (one index serves every OCAB)")
+        if rpi_oca is None:
+            rpi_oca, first = got, ikey
+    depth = None
+    for g in groups:
+        blocks = sorted({int(m.group(2)) for m in map(_SWINIR_BLOCK_KEY.match, keys) if m and int(m.group(1)) == g})
+        if not blocks or blocks != list(range(len(blocks))):
+            gap = next(i for i in range(len(blocks) + 1) if i not in blocks)
+            raise ValueError(f"layers.{g}.residual_group.blocks.{gap}.attn.qkv.weight: a group's HABs must be numbered 0 .. D - 1, got {blocks}")
+        if depth is None:
+            depth = len(blocks)
+        elif len(blocks) != depth:
+            raise ValueError(f"layers.{g}.residual_group.blocks.{min(len(blocks), depth)}.attn.qkv.weight: every group must have the same "
+                             f"depth, group 0 has {depth} HABs and group {g} has {len(blocks)}")
+        for j in blocks:
+            b = f"layers.{g}.residual_group.blocks.{j}"
+            t = f"{b}.attn.relative_position_bias_table"
+            if t in keys and shape_of(t) != (rows, heads):
+                got = shape_of(t)
+                what = "every layer must have the same number of heads" if len(got) == 2 and got[0] == rows else "only window_size 16 is supported"
+                raise ValueError(f"{t}: expected shape {(rows, heads)}, got {got}: {what}")
+            dense(f"{b}.norm1", (Cn,), (Cn,))
+            dense(f"{b}.attn.qkv", (3 * Cn, Cn), (3 * Cn,))
+            dense(t, (rows, heads), None, "")
+            dense(f"{b}.attn.proj", (Cn, Cn), (Cn,))
+            conv(f"{b}.conv_block.cab.0", Cn, mid)
+            conv(f"{b}.conv_block.cab.2", mid, Cn)
+            pointwise(f"{b}.conv_block.cab.3.attention.1", squeeze, Cn)
+            pointwise(f"{b}.conv_block.cab.3.attention.3", Cn, squeeze)
+            dense(f"{b}.norm2", (Cn,), (Cn,))
+            dense(f"{b}.mlp.fc1", (hidden, Cn), (hidden,))
+            dense(f"{b}.mlp.fc2", (Cn, hidden), (Cn,))
+        o = f"layers.{g}.residual_group.overlap_attn"
+        t = f"{o}.relative_position_bias_table"
+        if t in keys and shape_of(t) != (orows, heads):
+            got = shape_of(t)
+            what = "every layer must have the same number of heads" if len(got) == 2 and got[0] == orows else "only overlap_ratio 0.5 of window 16 is supported"
+            raise ValueError(f"{t}: expected shape {(orows, heads)}, got {got}: {what}")
+        dense(f"{o}.norm1", (Cn,), (Cn,))
+        dense(f"{o}.qkv", (3 * Cn, Cn), (3 * Cn,))
+        dense(t, (orows, heads), None, "")
+        dense(f"{o}.proj", (Cn, Cn), (Cn,))
+        dense(f"{o}.norm2", (Cn,), (Cn,))
+        dense(f"{o}.mlp.fc1", (hidden, Cn), (hidden,))
+        dense(f"{o}.mlp.fc2", (Cn, hidden), (Cn,))
+        conv(f"layers.{g}.conv", Cn, Cn)
+    dense("norm", (Cn,), (Cn,))
+    conv("conv_after_body", Cn, Cn)
+    if "conv_up1.weight" in keys:
+        raise ValueError("conv_up1.weight: upsampler nearest+conv is not supported (only pixelshuffle)")
+    if "conv_before_upsample.0.weight" not in keys:
+        raise ValueError("conv_before_upsample.0.weight: not in the state (only upsampler pixelshuffle is supported)")
+    conv("conv_before_upsample.0", Cn, 64)
+    ups = [f"upsample.{k}" for k in sorted(int(m.group(1)) for m in map(_UPSAMPLE_KEY.match, keys) if m)]
+    scale = 1
+    for name in ups:
+        cout = int(np.shape(_array(state, f"{name}.weight"))[0])
+        r = {256: 2, 576: 3}.get(cout)
+        if r is None or (len(ups) >= 2 and r != 2) or len(ups) > 2:
+            raise ValueError(f"{name}.weight gives {cout} channels in {len(ups)} stage(s), expected 64 r^2 = 256 (x2, x4) or 576 (x3): x1 and x8 "
+                             "are not supported")
+        scale *= r
+        conv(name, 64, cout)
+    if not ups:
+        raise ValueError("upsample.0.weight: not in the state (scale 1 is not supported)")
+    conv("conv_last", 64, 3)
+    desc = _native.hat_desc(Cn, heads, hidden, mid, squeeze, len(groups), depth, scale, float(conv_scale), rgb_mean, float(img_range))
+    _native.hat_plan(desc, 1, 1)                                 # NotImplementedError outside the kernels' range (host only)
+    return desc, [w for w, _ in tables], [b for _, b in tables], rpi_oca
+
+
+class HATSRNet(CompactSRNet):
+    """HAT on the GPU, with CompactSRNet's surface (from_file, model, upscale, upscale_device, close).  ``state``: a HAT state
+    dict (see parse_hat_state).  As SwinIRSRNet there is no ``tile`` (anything but 0 is refused), only the ``tail`` of the
+    reconstruction, which changes no bit; an image cut into tiles before the network is reflected, padded, windowed -- and its
+    CAB means pooled -- tile by tile."""
+
+    def __init__(self, state: Mapping, img_range: float = HAT_IMG_RANGE, rgb_mean=HAT_RGB_MEAN, conv_scale: float = HAT_CONV_SCALE,
+                 device: int = 0):
+        self.desc, self._w, self._b, self._rpi = parse_hat_state(state, img_range, rgb_mean, conv_scale)
+        d = self.desc
+        self.n_feat, self.n_heads, self.n_hidden, self.n_groups, self.depth, self.scale = d.n_feat, d.n_heads, d.n_hidden, d.n_groups, d.depth, d.scale
+        self.device = int(device)
+        self._models = {}
+
+    @classmethod
+    def from_file(cls, path: str, device: int = 0, **extras) -> "HATSRNet":
+        """A .npz may hold the constants a state dict lacks as 0-d ``img_range`` and ``conv_scale`` and a 3-vector ``rgb_mean``
+        entry; keyword arguments win over them, HAT's defaults (1, 0.01, the DIV2K mean) stand in for the rest."""
+        state = load_state(path)
+        return cls(state, device=device, **{**_hat_extras(state), **extras})
+
+    def _make_model(self, ctx: "_native.Context"):
+        return _native.HatModel(ctx, self.desc, self._w, self._b, self._rpi)
+
+    def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
+                       ctx: Optional["_native.Context"] = None, ensemble: int = 1, tail: int = 0):
+        if tile:
+            raise ValueError(f"HAT's trunk is one piece (windows, overlaps and the CAB's mean reach across any tile): there is no tile, got tile={tile!r}; see tail")
+        # the one argument after the strides of sr_hat_* is tail, and CompactSRNet hands its first one on by position
+        super().upscale_device(d_src, shape, d_dst, dst_stride, src_stride, tail, ctx, ensemble)
+
+
+def _hat_extras(state: Mapping) -> dict:
+    return _scalar_extras(state, (("img_range", 1), ("rgb_mean", 3), ("conv_scale", 1)))
+
+
 def load_network(path: str, act: str = "prelu", device: int = 0):
     """The network a weights file holds: a ``body.0.rdb1.conv1.weight`` entry makes it an RRDBSRNet, a
-    ``body.0.residual_group.0.rcab.0.weight`` entry an RCANSRNet, a ``layers.0.residual_group.blocks.0.attn.qkv.weight`` entry a
-    SwinIRSRNet, otherwise a ``conv_first.weight`` entry a ResidualSRNet (``act`` is ignored for these four families), ``body.{i}.weight`` entries a CompactSRNet exactly as
+    ``body.0.residual_group.0.rcab.0.weight`` entry an RCANSRNet, a ``layers.0.residual_group.overlap_attn.qkv.weight`` entry a
+    HATSRNet, a ``layers.0.residual_group.blocks.0.attn.qkv.weight`` entry a SwinIRSRNet, otherwise a ``conv_first.weight`` entry a ResidualSRNet (``act`` is ignored for these five families), ``body.{i}.weight`` entries a CompactSRNet exactly as
     CompactSRNet.from_file."""
     state = load_state(path)
     if RRDB_KEY in {str(k) for k in _unwrap(state)}:
         return RRDBSRNet(state, device=device, **_rrdb_extras(state))
     if RCAN_KEY in {str(k) for k in _unwrap(state)}:
         return RCANSRNet(state, device=device, **_residual_extras(state))
+    if HAT_KEY in {str(k) for k in _unwrap(state)}:                # before SwinIR's key, which a HAT state carries too
+        return HATSRNet(state, device=device, **_hat_extras(state))
     if SWINIR_KEY in {str(k) for k in _unwrap(state)}:
         return SwinIRSRNet(state, device=device, **_swinir_extras(state))
     if "conv_first.weight" in {str(k) for k in _unwrap(state)}:
