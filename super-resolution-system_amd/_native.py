@@ -2160,6 +2160,93 @@ def rcan_attention(ctx, d_x: int, plane_stride: int, row_stride: int, n_feat: in
 
 
 # ------------------------------------------------------------------------------------------
+# What the two window-attention families (SwinIR, HAT) share on this side: the names and shapes of an attention block, an
+# MLP and the pixelshuffle reconstruction, the plan and index calls, the model base and the inspection call.
+# ------------------------------------------------------------------------------------------
+def _sw_conv(co, ci):
+    return ((co, ci, 3, 3), (co,))
+
+
+def _sw_block_names(b: str, attn: str = "attn."):
+    """-> (the names of block b's attention tables, of its MLP's); attn: '' where the attention is the block itself (HAT's OCAB)."""
+    return ([f"{b}.norm1", f"{b}.{attn}qkv", f"{b}.{attn}relative_position_bias_table", f"{b}.{attn}proj"],
+            [f"{b}.norm2", f"{b}.mlp.fc1", f"{b}.mlp.fc2"])
+
+
+def _sw_block_shapes(Cn: int, nh: int, hid: int, rows: int):
+    """-> (the shapes of an attention's tables, its bias table of ``rows`` rows, and of an MLP's)."""
+    ln = ((Cn,), (Cn,))
+    return [ln, ((3 * Cn, Cn), (3 * Cn,)), ((rows, nh), None), ((Cn, Cn), (Cn,))], [ln, ((hid, Cn), (hid,)), ((Cn, hid), (Cn,))]
+
+
+def _sw_shuffle_tail(Cn: int, s: int):
+    """-> (names, shapes) of the pixelshuffle reconstruction at scale s."""
+    rs = [2, 2] if s == 4 else [s]
+    return (["conv_before_upsample.0"] + [f"upsample.{2 * k}" for k in range(len(rs))] + ["conv_last"],
+            [_sw_conv(64, Cn)] + [_sw_conv(64 * r * r, 64) for r in rs] + [_sw_conv(3, 64)])
+
+
+def _sw_plan(entry: str, desc, h: int, w: int, tail: int) -> Tuple[int, int, int, int, int]:
+    hp, wp, halo, nt, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check_unsupported(getattr(load(), entry)(C.byref(desc), int(h), int(w), int(tail), C.byref(hp), C.byref(wp), C.byref(halo), C.byref(nt),
+                                              C.byref(ws)))
+    return hp.value, wp.value, halo.value, nt.value, int(ws.value)
+
+
+def _sw_index(entry: str, shape) -> np.ndarray:
+    idx = np.empty(shape, np.int32)
+    check(getattr(load(), entry)(idx.ctypes.data_as(C.c_void_p), idx.size))
+    return idx
+
+
+class _SwModel(_SrModel):
+    """What SwinirModel and HatModel share: the checked tables, plan, fill_workspace.  ``_name``: what a ValueError calls the
+    family; ``_shapes`` / ``_plan``: its *_table_shapes / *_plan; ``_conv1x1``: whether an (out, in) table may come as
+    (out, in, 1, 1).  The trunk is one piece, so the forwards take ``tail`` alone."""
+    _run_args = ("tail",)
+    _name = ""
+    _conv1x1 = False
+    _shapes = _plan = None
+
+    def _tables(self, desc, weights, biases):
+        """-> (weights, biases) as contiguous fp32, checked against the family's shapes."""
+        self._plan(desc, 1, 1)                                   # the supported range, refused before any array is touched
+        shapes = self._shapes(desc)
+        if len(weights) != len(shapes) or len(biases) != len(shapes):
+            raise ValueError(f"this {self._name} has {len(shapes)} tables, got {len(weights)} weight / {len(biases)} bias arrays")
+        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
+        bs = [np.zeros(1, np.float32) if sb is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a, (_, sb) in zip(biases, shapes)]
+        for k, (w, b, (sw, sb)) in enumerate(zip(ws, bs, shapes)):
+            ok = w.shape == sw or (self._conv1x1 and len(sw) == 2 and w.shape == sw + (1, 1))
+            if not ok or (sb is not None and b.shape != sb):
+                raise ValueError(f"{self._name} table {k}: expected {sw} / {sb}, got {w.shape} / {b.shape}")
+        self.desc, self.scale = desc, desc.scale
+        return ws, bs
+
+    def plan(self, h: int, w: int, tail: int = 0):
+        return self._plan(self.desc, h, w, tail)
+
+    def fill_workspace(self, h: int, w: int, byte: int, tail: int = 0):
+        """sr_<kind>_fill_workspace: the buffers of an h x w forward, grown and filled with ``byte`` (for tests)."""
+        check(getattr(self.ctx.lib, f"sr_{self._kind}_fill_workspace")(self.handle, int(h), int(w), int(tail), int(byte)))
+
+
+def _sw_bias_table(table, rows: int, n_heads: int) -> np.ndarray:
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    if 1 <= int(n_heads) <= 256 and t.shape != (rows, int(n_heads)):
+        raise ValueError(f"the bias table is {(rows, int(n_heads))}, got {t.shape}")
+    return t
+
+
+def _sw_attention(entry: str, ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat: int, n_heads: int, hp: int, wp: int, args,
+                  d_out: int, out_plane_stride: int, out_row_stride: int):
+    """sr_<entry>(ctx, the qkv view, C, heads, hp, wp, *args, the output view); ``args``: what the entry takes between them."""
+    _check_unsupported(getattr(load(), entry)(_ctx_handle(ctx), C.c_void_p(d_qkv), int(plane_stride), int(row_stride), int(n_feat),
+                                              int(n_heads), int(hp), int(wp), *args, C.c_void_p(d_out), int(out_plane_stride),
+                                              int(out_row_stride)))
+
+
+# ------------------------------------------------------------------------------------------
 # local SR network, SwinIR (sr_swinir_*): sr_network.SwinIRSRNet parses BasicSR state dicts into these arrays
 # ------------------------------------------------------------------------------------------
 SWINIR_UPSAMPLERS = {"pixelshuffle": 0, "pixelshuffledirect": 1, "nearest+conv": 2}
@@ -2183,12 +2270,11 @@ def swinir_table_names(desc: SwinirDesc) -> List[str]:
     for i in range(desc.n_groups):
         for j in range(desc.depth):
             b = f"layers.{i}.residual_group.blocks.{j}"
-            names += [f"{b}.norm1", f"{b}.attn.qkv", f"{b}.attn.relative_position_bias_table", f"{b}.attn.proj", f"{b}.norm2",
-                      f"{b}.mlp.fc1", f"{b}.mlp.fc2"]
+            names += sum(_sw_block_names(b), [])
         names.append(f"layers.{i}.conv")
     names += ["norm", "conv_after_body"]
     if desc.upsampler == 0:
-        names += ["conv_before_upsample.0"] + [f"upsample.{2 * k}" for k in range(2 if desc.scale == 4 else 1)] + ["conv_last"]
+        names += _sw_shuffle_tail(desc.n_feat, desc.scale)[0]
     elif desc.upsampler == 1:
         names += ["upsample.0"]
     else:
@@ -2198,17 +2284,11 @@ def swinir_table_names(desc: SwinirDesc) -> List[str]:
 
 def swinir_table_shapes(desc: SwinirDesc) -> List[Tuple[tuple, Optional[tuple]]]:
     """(weight shape, bias shape) of every table in sr_swinir_create's order; the bias table has no bias (None)."""
-    Cn, nh, hid, s = desc.n_feat, desc.n_heads, desc.n_hidden, desc.scale
-    ln = ((Cn,), (Cn,))
-    layer = [ln, ((3 * Cn, Cn), (3 * Cn,)), (((2 * SWINIR_WINDOW - 1) ** 2, nh), None), ((Cn, Cn), (Cn,)), ln, ((hid, Cn), (hid,)),
-             ((Cn, hid), (Cn,))]
-
-    def conv(co, ci):
-        return ((co, ci, 3, 3), (co,))
-
+    Cn, s, conv, ln = desc.n_feat, desc.scale, _sw_conv, ((desc.n_feat,), (desc.n_feat,))
+    layer = sum(_sw_block_shapes(Cn, desc.n_heads, desc.n_hidden, (2 * SWINIR_WINDOW - 1) ** 2), [])
     shapes = [conv(Cn, 3), ln] + (layer * desc.depth + [conv(Cn, Cn)]) * desc.n_groups + [ln, conv(Cn, Cn)]
     if desc.upsampler == 0:
-        shapes += [conv(64, Cn)] + [conv(64 * r * r, 64) for r in ([2, 2] if s == 4 else [s])] + [conv(3, 64)]
+        shapes += _sw_shuffle_tail(Cn, s)[1]
     elif desc.upsampler == 1:
         shapes += [conv(3 * s * s, Cn)]
     else:
@@ -2218,45 +2298,24 @@ def swinir_table_shapes(desc: SwinirDesc) -> List[Tuple[tuple, Optional[tuple]]]
 
 def swinir_plan(desc: SwinirDesc, h: int, w: int, tail: int = 0) -> Tuple[int, int, int, int, int]:
     """sr_swinir_plan (host only) -> (padded rows, padded columns, the tail's halo, tail sub-pieces, workspace bytes)."""
-    hp, wp, halo, nt, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
-    _check_unsupported(load().sr_swinir_plan(C.byref(desc), int(h), int(w), int(tail), C.byref(hp), C.byref(wp), C.byref(halo), C.byref(nt),
-                                             C.byref(ws)))
-    return hp.value, wp.value, halo.value, nt.value, int(ws.value)
+    return _sw_plan("sr_swinir_plan", desc, h, w, tail)
 
 
 def swinir_rel_index() -> np.ndarray:
     """sr_swinir_rel_index (host only) -> (64, 64) int32: the bias-table row of (query token, key token)."""
-    rel = np.empty((64, 64), np.int32)
-    check(load().sr_swinir_rel_index(rel.ctypes.data_as(C.c_void_p), rel.size))
-    return rel
+    return _sw_index("sr_swinir_rel_index", (64, 64))
 
 
-class SwinirModel(_SrModel):
+class SwinirModel(_SwModel):
     """sr_swinir_model: a SwinIR resident on the GPU.  weights / biases: one fp32 array each per table in forward order
     (swinir_table_shapes / swinir_table_names); the bias entry of a relative-position table is ignored (None is fine).  The
     trunk is one piece, so the forwards take ``tail`` alone."""
-    _kind = "swinir"
-    _run_args = ("tail",)
+    _kind, _name = "swinir", "SwinIR"
+    _shapes, _plan = staticmethod(swinir_table_shapes), staticmethod(swinir_plan)
 
     def __init__(self, ctx: Context, desc: SwinirDesc, weights, biases):
-        swinir_plan(desc, 1, 1)                                  # the supported range, refused before any array is touched
-        shapes = swinir_table_shapes(desc)
-        if len(weights) != len(shapes) or len(biases) != len(shapes):
-            raise ValueError(f"this SwinIR has {len(shapes)} tables, got {len(weights)} weight / {len(biases)} bias arrays")
-        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
-        bs = [np.zeros(1, np.float32) if sb is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a, (_, sb) in zip(biases, shapes)]
-        for k, (w, b, (sw, sb)) in enumerate(zip(ws, bs, shapes)):
-            if w.shape != sw or (sb is not None and b.shape != sb):
-                raise ValueError(f"SwinIR table {k}: expected {sw} / {sb}, got {w.shape} / {b.shape}")
-        self.desc, self.scale = desc, desc.scale
+        ws, bs = self._tables(desc, weights, biases)
         self._create(ctx, (C.byref(desc),), ws, bs, count=True)
-
-    def plan(self, h: int, w: int, tail: int = 0):
-        return swinir_plan(self.desc, h, w, tail)
-
-    def fill_workspace(self, h: int, w: int, byte: int, tail: int = 0):
-        """sr_swinir_fill_workspace: the buffers of an h x w forward, grown and filled with ``byte`` (for tests)."""
-        check(self.ctx.lib.sr_swinir_fill_workspace(self.handle, int(h), int(w), int(tail), int(byte)))
 
 
 def swinir_layernorm(ctx, d_x: int, plane_stride: int, row_stride: int, n_feat: int, h: int, w: int, gamma, beta, d_out: int,
@@ -2275,12 +2334,9 @@ def swinir_attention(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat
                      d_out: int, out_plane_stride: int, out_row_stride: int):
     """sr_swinir_attention_f32: the window attention (before proj) on a planar qkv tensor of 3 C planes whose q planes are
     already scaled; ``table``: the (225, heads) relative-position bias table; into the C planes of d_out.  Synchronous."""
-    t = np.ascontiguousarray(table, dtype=np.float32)
-    if 1 <= int(n_heads) <= 256 and t.shape != ((2 * SWINIR_WINDOW - 1) ** 2, int(n_heads)):
-        raise ValueError(f"the bias table is {((2 * SWINIR_WINDOW - 1) ** 2, int(n_heads))}, got {t.shape}")
-    _check_unsupported(load().sr_swinir_attention_f32(_ctx_handle(ctx), C.c_void_p(d_qkv), int(plane_stride), int(row_stride), int(n_feat),
-                                                      int(n_heads), int(hp), int(wp), int(shift), t.ctypes.data_as(C.c_void_p), C.c_void_p(d_out),
-                                                      int(out_plane_stride), int(out_row_stride)))
+    t = _sw_bias_table(table, (2 * SWINIR_WINDOW - 1) ** 2, n_heads)
+    _sw_attention("sr_swinir_attention_f32", ctx, d_qkv, plane_stride, row_stride, n_feat, n_heads, hp, wp,
+                  (int(shift), t.ctypes.data_as(C.c_void_p)), d_out, out_plane_stride, out_row_stride)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2307,53 +2363,37 @@ def hat_table_names(desc: HatDesc) -> List[str]:
     for i in range(desc.n_groups):
         for j in range(desc.depth):
             b = f"layers.{i}.residual_group.blocks.{j}"
-            names += [f"{b}.norm1", f"{b}.attn.qkv", f"{b}.attn.relative_position_bias_table", f"{b}.attn.proj", f"{b}.conv_block.cab.0",
-                      f"{b}.conv_block.cab.2", f"{b}.conv_block.cab.3.attention.1", f"{b}.conv_block.cab.3.attention.3", f"{b}.norm2",
-                      f"{b}.mlp.fc1", f"{b}.mlp.fc2"]
-        o = f"layers.{i}.residual_group.overlap_attn"
-        names += [f"{o}.norm1", f"{o}.qkv", f"{o}.relative_position_bias_table", f"{o}.proj", f"{o}.norm2", f"{o}.mlp.fc1", f"{o}.mlp.fc2",
-                  f"layers.{i}.conv"]
-    names += ["norm", "conv_after_body", "conv_before_upsample.0"]
-    return names + [f"upsample.{2 * k}" for k in range(2 if desc.scale == 4 else 1)] + ["conv_last"]
+            attn, mlp = _sw_block_names(b)
+            names += attn + [f"{b}.conv_block.cab.0", f"{b}.conv_block.cab.2", f"{b}.conv_block.cab.3.attention.1",
+                             f"{b}.conv_block.cab.3.attention.3"] + mlp
+        names += sum(_sw_block_names(f"layers.{i}.residual_group.overlap_attn", ""), []) + [f"layers.{i}.conv"]
+    return names + ["norm", "conv_after_body"] + _sw_shuffle_tail(desc.n_feat, desc.scale)[0]
 
 
 def hat_table_shapes(desc: HatDesc) -> List[Tuple[tuple, Optional[tuple]]]:
     """(weight shape, bias shape) of every table in sr_hat_create's order; a bias table has no bias (None).  The two 1 x 1
     layers of a CAB's attention are (out, in); (out, in, 1, 1) arrays are accepted for them."""
-    Cn, nh, hid, mid, sq, s = desc.n_feat, desc.n_heads, desc.n_hidden, desc.n_mid, desc.n_squeeze, desc.scale
-    ln = ((Cn,), (Cn,))
-
-    def conv(co, ci):
-        return ((co, ci, 3, 3), (co,))
-
-    mlp = [ln, ((hid, Cn), (hid,)), ((Cn, hid), (Cn,))]
-    hab = [ln, ((3 * Cn, Cn), (3 * Cn,)), ((HAT_REL_ROWS, nh), None), ((Cn, Cn), (Cn,)), conv(mid, Cn), conv(Cn, mid), ((sq, Cn), (sq,)),
-           ((Cn, sq), (Cn,))] + mlp
-    ocab = [ln, ((3 * Cn, Cn), (3 * Cn,)), ((HAT_OCA_ROWS, nh), None), ((Cn, Cn), (Cn,))] + mlp
+    Cn, nh, mid, sq, conv, ln = desc.n_feat, desc.n_heads, desc.n_mid, desc.n_squeeze, _sw_conv, ((desc.n_feat,), (desc.n_feat,))
+    attn, mlp = _sw_block_shapes(Cn, nh, desc.n_hidden, HAT_REL_ROWS)
+    hab = attn + [conv(mid, Cn), conv(Cn, mid), ((sq, Cn), (sq,)), ((Cn, sq), (Cn,))] + mlp
+    ocab = sum(_sw_block_shapes(Cn, nh, desc.n_hidden, HAT_OCA_ROWS), [])
     shapes = [conv(Cn, 3), ln] + (hab * desc.depth + ocab + [conv(Cn, Cn)]) * desc.n_groups + [ln, conv(Cn, Cn)]
-    return shapes + [conv(64, Cn)] + [conv(64 * r * r, 64) for r in ([2, 2] if s == 4 else [s])] + [conv(3, 64)]
+    return shapes + _sw_shuffle_tail(Cn, desc.scale)[1]
 
 
 def hat_plan(desc: HatDesc, h: int, w: int, tail: int = 0) -> Tuple[int, int, int, int, int]:
     """sr_hat_plan (host only) -> (padded rows, padded columns, the tail's halo, tail sub-pieces, workspace bytes)."""
-    hp, wp, halo, nt, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
-    _check_unsupported(load().sr_hat_plan(C.byref(desc), int(h), int(w), int(tail), C.byref(hp), C.byref(wp), C.byref(halo), C.byref(nt),
-                                          C.byref(ws)))
-    return hp.value, wp.value, halo.value, nt.value, int(ws.value)
+    return _sw_plan("sr_hat_plan", desc, h, w, tail)
 
 
 def hat_rel_index() -> np.ndarray:
     """sr_hat_rel_index (host only) -> (256, 256) int32: the bias-table row of (query token, key token) of a 16 x 16 window."""
-    rel = np.empty((256, 256), np.int32)
-    check(load().sr_hat_rel_index(rel.ctypes.data_as(C.c_void_p), rel.size))
-    return rel
+    return _sw_index("sr_hat_rel_index", (256, 256))
 
 
 def hat_oca_index() -> np.ndarray:
     """sr_hat_oca_index (host only) -> (256, 576) int32: the default index of the overlapping cross-attention, wrapped."""
-    idx = np.empty((256, 576), np.int32)
-    check(load().sr_hat_oca_index(idx.ctypes.data_as(C.c_void_p), idx.size))
-    return idx
+    return _sw_index("sr_hat_oca_index", (256, 576))
 
 
 def _hat_index(index, name: str = "relative_position_index_OCA") -> Optional[np.ndarray]:
@@ -2369,26 +2409,16 @@ def _hat_index(index, name: str = "relative_position_index_OCA") -> Optional[np.
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-class HatModel(_SrModel):
+class HatModel(_SwModel):
     """sr_hat_model: a HAT resident on the GPU.  weights / biases: one fp32 array each per table in forward order
     (hat_table_shapes / hat_table_names); the bias entry of a relative-position table is ignored (None is fine).  ``rpi_oca``:
     the state's relative_position_index_OCA (256, 576), or None for the default formula.  The trunk is one piece, so the
     forwards take ``tail`` alone."""
-    _kind = "hat"
-    _run_args = ("tail",)
+    _kind, _name, _conv1x1 = "hat", "HAT", True
+    _shapes, _plan = staticmethod(hat_table_shapes), staticmethod(hat_plan)
 
     def __init__(self, ctx: Context, desc: HatDesc, weights, biases, rpi_oca=None):
-        hat_plan(desc, 1, 1)                                     # the supported range, refused before any array is touched
-        shapes = hat_table_shapes(desc)
-        if len(weights) != len(shapes) or len(biases) != len(shapes):
-            raise ValueError(f"this HAT has {len(shapes)} tables, got {len(weights)} weight / {len(biases)} bias arrays")
-        ws = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
-        bs = [np.zeros(1, np.float32) if sb is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a, (_, sb) in zip(biases, shapes)]
-        for k, (w, b, (sw, sb)) in enumerate(zip(ws, bs, shapes)):
-            ok = w.shape == sw or (len(sw) == 2 and w.shape == sw + (1, 1))
-            if not ok or (sb is not None and b.shape != sb):
-                raise ValueError(f"HAT table {k}: expected {sw} / {sb}, got {w.shape} / {b.shape}")
-        self.desc, self.scale = desc, desc.scale
+        ws, bs = self._tables(desc, weights, biases)
         self._rpi = _hat_index(rpi_oca)
         self._create(ctx, (C.byref(desc),), ws, bs)
 
@@ -2399,24 +2429,14 @@ class HatModel(_SrModel):
         _check_unsupported(ctx.lib.sr_hat_create(ctx.handle, *args, *ptrs, len(ws), rpi, C.byref(h)))
         self.ctx, self.handle = ctx, h
 
-    def plan(self, h: int, w: int, tail: int = 0):
-        return hat_plan(self.desc, h, w, tail)
-
-    def fill_workspace(self, h: int, w: int, byte: int, tail: int = 0):
-        """sr_hat_fill_workspace: the buffers of an h x w forward, grown and filled with ``byte`` (for tests)."""
-        check(self.ctx.lib.sr_hat_fill_workspace(self.handle, int(h), int(w), int(tail), int(byte)))
-
 
 def hat_attention(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat: int, n_heads: int, hp: int, wp: int, shift: int, table,
                   d_out: int, out_plane_stride: int, out_row_stride: int):
     """sr_hat_attention_f32: the 16 x 16 window attention (before proj) on a planar qkv tensor of 3 C planes whose q planes are
     already scaled; ``table``: the (961, heads) relative-position bias table; into the C planes of d_out.  Synchronous."""
-    t = np.ascontiguousarray(table, dtype=np.float32)
-    if 1 <= int(n_heads) <= 256 and t.shape != (HAT_REL_ROWS, int(n_heads)):
-        raise ValueError(f"the bias table is {(HAT_REL_ROWS, int(n_heads))}, got {t.shape}")
-    _check_unsupported(load().sr_hat_attention_f32(_ctx_handle(ctx), C.c_void_p(d_qkv), int(plane_stride), int(row_stride), int(n_feat),
-                                                   int(n_heads), int(hp), int(wp), int(shift), t.ctypes.data_as(C.c_void_p), C.c_void_p(d_out),
-                                                   int(out_plane_stride), int(out_row_stride)))
+    t = _sw_bias_table(table, HAT_REL_ROWS, n_heads)
+    _sw_attention("sr_hat_attention_f32", ctx, d_qkv, plane_stride, row_stride, n_feat, n_heads, hp, wp,
+                  (int(shift), t.ctypes.data_as(C.c_void_p)), d_out, out_plane_stride, out_row_stride)
 
 
 def hat_oca(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat: int, n_heads: int, hp: int, wp: int, table, index, d_out: int,
@@ -2424,14 +2444,11 @@ def hat_oca(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat: int, n_
     """sr_hat_oca_f32: the overlapping cross-attention (before proj) on a planar qkv tensor of 3 C planes whose q planes are
     already scaled; ``table``: the (1521, heads) bias table; ``index``: (256, 576) integers in [-1521, 1520] or None for the
     default formula; into the C planes of d_out.  Synchronous."""
-    t = np.ascontiguousarray(table, dtype=np.float32)
-    if 1 <= int(n_heads) <= 256 and t.shape != (HAT_OCA_ROWS, int(n_heads)):
-        raise ValueError(f"the bias table is {(HAT_OCA_ROWS, int(n_heads))}, got {t.shape}")
+    t = _sw_bias_table(table, HAT_OCA_ROWS, n_heads)
     idx = _hat_index(index)
-    _check_unsupported(load().sr_hat_oca_f32(_ctx_handle(ctx), C.c_void_p(d_qkv), int(plane_stride), int(row_stride), int(n_feat),
-                                             int(n_heads), int(hp), int(wp), t.ctypes.data_as(C.c_void_p),
-                                             None if idx is None else idx.ctypes.data_as(C.c_void_p), C.c_void_p(d_out),
-                                             int(out_plane_stride), int(out_row_stride)))
+    _sw_attention("sr_hat_oca_f32", ctx, d_qkv, plane_stride, row_stride, n_feat, n_heads, hp, wp,
+                  (t.ctypes.data_as(C.c_void_p), None if idx is None else idx.ctypes.data_as(C.c_void_p)), d_out, out_plane_stride,
+                  out_row_stride)
 
 
 _default_ctx = {}

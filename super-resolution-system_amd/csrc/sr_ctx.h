@@ -150,10 +150,12 @@ struct Guard {
     }
 };
 
-#define CTX_ENTER(ctx)                                                               \
-    if (!ctx_is_live(ctx)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed context", __func__); \
+// fn: the name the two messages carry (a frame shared by several entry points passes its caller's).
+#define CTX_ENTER_AS(ctx, fn)                                                        \
+    if (!ctx_is_live(ctx)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed context", fn); \
     Guard guard_(ctx);                                                               \
-    if (!guard_.ok) return sr_set_error(SR_ERR_HIP, "%s: hipSetDevice(%d) failed", __func__, (ctx)->device)
+    if (!guard_.ok) return sr_set_error(SR_ERR_HIP, "%s: hipSetDevice(%d) failed", fn, (ctx)->device)
+#define CTX_ENTER(ctx) CTX_ENTER_AS(ctx, __func__)
 
 struct ProfScope {
     sr_ctx *c;

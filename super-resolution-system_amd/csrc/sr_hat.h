@@ -1,7 +1,8 @@
-// sr_hat.h -- what sr_hat_host.cpp (host only: the description checks, the table list, the two relative-position indices, the
+// sr_hat.h -- what sr_hat_host.cpp (host only: the description checks, the table list, the overlapping attention's index, the
 // plan) hands to sr_hat.hip (the kernels and the forward).  Internal: nothing here is part of the C ABI.  It includes no HIP
-// header, so that the host unit compiles with a plain C++ compiler (tools/sanitize/hat_driver.cpp).  The reconstruction is
-// SwinIR's pixelshuffle tail, so the step list and the extent rule are sr_swinir.h's.
+// header, so that the host unit compiles with a plain C++ compiler (tools/sanitize/hat_driver.cpp).  The geometry (SwGeom), the
+// window's relative-position index (sw_rel_index at HT_WIN), the step list of the pixelshuffle tail and the extent rule are
+// sr_swinir.h's.
 #pragma once
 #include <cstddef>
 #include <vector>
@@ -24,23 +25,13 @@ enum {
     HT_T_ATT3          // conv_block.cab.3.attention.3, [C][n_squeeze]
 };
 
-struct HtGeom {
-    int hp = 0, wp = 0;                                 // the padded image
-    int cp = 0, qp = 0, tp = 0;                         // planes of a C buffer, of the qkv / hidden buffer, of the CAB's middle
-    int tail = 0, halo = 0, chunks = 0;
-    long long tail_tiles = 0;
-    long long plane0 = 0, plane_t = 0;                  // a trunk plane, the largest plane of a tail buffer
-    size_t trunk_bytes = 0, workspace_bytes = 0;
-};
-
 int ht_check_desc(const char *who, const sr_hat_desc *d);
 std::vector<SwTable> ht_tables(const sr_hat_desc &d);
 std::vector<SwStep> ht_tail_steps(const sr_hat_desc &d);
-// rel[i * 256 + j]: the row of a window attention's bias table that query token i and key token j share.
-void ht_rel_index(int *rel);
 // idx[i * 576 + j]: the row of an OCAB's bias table that query i and key j of the enlarged window share (the default formula,
 // negative values wrapped).
 void ht_oca_index(int *idx);
 // A caller's index [256][576]: every value in [-1521, 1520], negatives wrapped once into out.
 int ht_wrap_oca_index(const char *who, const int *in, int *out);
-int ht_geometry(const char *who, const sr_hat_desc &d, int h, int w, int tail, HtGeom &g);
+// sw_plan_geometry with HAT's SwFamily: g.tp, g.chunks and g.red_bytes are set.
+int ht_geometry(const char *who, const sr_hat_desc &d, int h, int w, int tail, SwGeom &g);

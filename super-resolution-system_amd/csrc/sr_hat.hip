@@ -14,8 +14,10 @@
 //
 // Everything is fp32 except the LayerNorm statistics and the CAB's channel attention (float64).  The head, the LayerNorm, the
 // linear layers, the 3 x 3 convolutions and the weight arrangement are sr_swin_common.h (shared with sr_swinir.hip); the
-// channel mean, the attention and the scale-and-skip pass are sr_chan_attn.h (shared with sr_rcan.hip); the reconstruction
-// runs in tail x tail sub-pieces exactly as sr_swinir.hip's.  New here: the two attention kernels and the reflection.
+// channel mean, the attention and the scale-and-skip pass are sr_chan_attn.h (shared with sr_rcan.hip).  The frame around the
+// blocks is sr_swin_common.h's too: the model's buffers, the trunk phase's steps, the tail phase (sw_run_tail: SwinIR's
+// pixelshuffle reconstruction in tail x tail sub-pieces), the create, the ensemble and the inspection calls.  This file keeps
+// the two attention kernels, the reflection, the body of one RHAG, HAT's own table kinds and the entry points.
 //
 // Trunk phase: the padded image is ONE piece in seven planar fp32 buffers of Hp x Wp planes: H (h, then f in place), R (the
 // RHAG's input, then its output in place), X (the running x), A (LayerNorm output, then the attention output in place of it),
@@ -267,224 +269,87 @@ void ht_launch(hipStream_t st, const float *qkv, long long plane, int pitch, int
 {
     const int d = C / heads;
     const dim3 grid((hp / HT_WIN) * (wp / HT_WIN), heads), block(HT_TOK);
-    auto go = [&](auto window, auto overlap) {
-        if constexpr (A::OCA) hipLaunchKernelGGL(overlap, grid, block, 0, st, qkv, plane, pitch, hp, wp, C, d, shift, bias, out, oplane, opitch, Cp);
-        else hipLaunchKernelGGL(window, grid, block, 0, st, qkv, plane, pitch, hp, wp, C, d, shift, bias, out, oplane, opitch, Cp);
-    };
-    if (d <= 8) go(k_hat_attention<8>, k_hat_oca<8>);
-    else if (d <= 16) go(k_hat_attention<16>, k_hat_oca<16>);
-    else if (d <= 24) go(k_hat_attention<24>, k_hat_oca<24>);
-    else go(k_hat_attention<32>, k_hat_oca<32>);
+    if constexpr (A::OCA)
+        sw_launch_by_d(d, k_hat_oca<8>, k_hat_oca<16>, k_hat_oca<24>, k_hat_oca<32>, grid, block, st, qkv, plane, pitch, hp, wp, C, d, shift, bias, out,
+                       oplane, opitch, Cp);
+    else
+        sw_launch_by_d(d, k_hat_attention<8>, k_hat_attention<16>, k_hat_attention<24>, k_hat_attention<32>, grid, block, st, qkv, plane, pitch, hp,
+                       wp, C, d, shift, bias, out, oplane, opitch, Cp);
 }
 
-// A bias table [rows][heads] gathered through idx [256][nk] to [head][key j][query i].
-std::vector<float> ht_gather_bias(const float *table, const int *idx, int nk, int heads)
+// The index of an OCAB's bias table: the caller's (checked and wrapped) or the default formula.
+int ht_oca_index_of(const char *who, const int *h_index, int *idx)
 {
-    std::vector<float> g((size_t)heads * nk * HT_TOK);
-    for (int hd = 0; hd < heads; ++hd)
-        for (int j = 0; j < nk; ++j)
-            for (int i = 0; i < HT_TOK; ++i) g[((size_t)hd * nk + j) * HT_TOK + i] = table[(size_t)idx[i * nk + j] * heads + hd];
-    return g;
+    if (h_index) return ht_wrap_oca_index(who, h_index, idx);
+    ht_oca_index(idx);
+    return SR_OK;
 }
 
 }  // namespace
 
-struct sr_hat_model : SrModelBase {            // d_w, d_b: per table (ht_tables)
+struct sr_hat_model : SwModelBase {            // trunk[4] is U (the CAB's output); tbuf and red are in use
     sr_hat_desc d{};
-    std::vector<SwTable> tables;
-    DevBuf trunk[5];                          // H, R, X, A, U
-    DevBuf tbuf;                              // the CAB's middle tensor
-    DevBuf qbuf;                              // qkv / hidden
-    DevBuf tailbuf[2];
-    DevBuf img;                               // the reflected u8 image
-    DevBuf red;                               // C x chunks float64 chunk sums, then s[C]
-    void release_device()
-    {
-        for (auto &b : trunk) b.release();
-        for (DevBuf *b : {&tailbuf[0], &tailbuf[1], &tbuf, &qbuf, &img, &red}) b->release();
-        release_base();
-    }
+    static constexpr bool SHUFFLE_ONLY = true;
+    static int check_desc(const char *who, const sr_hat_desc *desc) { return ht_check_desc(who, desc); }
+    static std::vector<SwTable> table_list(const sr_hat_desc &desc) { return ht_tables(desc); }
+    static bool bias_table(int kind) { return kind == SW_T_RPB || kind == HT_T_RPB_OCA; }
+    int geometry(const char *who, int h, int w, int tail, SwGeom &g) const { return ht_geometry(who, d, h, w, tail, g); }
+    std::vector<SwStep> tail_steps() const { return ht_tail_steps(d); }
 };
 
 static LiveSet g_ht_live;
 
-static int ht_reserve(sr_hat_model *m, const HtGeom &g, const char *who)
-{
-    sr_ctx *ctx = m->ctx;
-    int rc;
-    if ((rc = ensure_activation_buffers(ctx, m->trunk, 5, (size_t)g.plane0 * g.cp, who))) return rc;
-    if ((rc = ensure_activation_buffers(ctx, &m->tbuf, 1, (size_t)g.plane0 * g.tp, who))) return rc;
-    if ((rc = ensure_activation_buffers(ctx, &m->qbuf, 1, (size_t)g.plane0 * g.qp, who))) return rc;
-    if (g.plane_t && (rc = ensure_activation_buffers(ctx, m->tailbuf, 2, (size_t)g.plane_t * SW_MID, who))) return rc;
-    SRCHK(m->img.reserve(ctx, who, (size_t)g.plane0 * 3));
-    SRCHK(m->red.reserve(ctx, who, (size_t)m->d.n_feat * g.chunks * sizeof(double) + (size_t)m->d.n_feat * sizeof(float)));
-    return SR_OK;
-}
-
 static int ht_forward(sr_hat_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride, int tail,
                       bool u8, const char *who)
 {
-    if (!g_ht_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
-    sr_ctx *ctx = m->ctx;
-    CTX_ENTER(ctx);
-    const sr_hat_desc &D = m->d;
-    const int C = D.n_feat, heads = D.n_heads, S = D.scale, R = D.n_squeeze;
-    int rc = check_sr_forward_args(who, d_src, src_stride, w, d_dst, dst_stride, S, u8);
-    if (rc) return rc;
-    HtGeom g;
-    if ((rc = ht_geometry(who, D, h, w, tail, g))) return rc;
-    if ((rc = ht_reserve(m, g, who))) return rc;
-    const int hp = g.hp, wp = g.wp, Cp = g.cp, Tp = g.tp, hidp = sw_pad64(D.n_hidden), qkvp = sw_pad64(3 * C);
-    hipStream_t st = ctx->stream;
-    SwEpi ep{};
-    ep.af = {{D.mean[0], D.mean[1], D.mean[2]}, D.range};
-    ep.dst = d_dst;
-    ep.dst_stride = (long long)dst_stride;
-    ep.s = 1;
-    ep.nq = C;
-    ep.qscale = 1.0f / sqrtf((float)(C / heads));
-    // ---- trunk phase: the whole padded image, every tensor in one layout ----
-    const PlanarTen L = planar_tensor(nullptr, 0, 0, hp, wp);
-    auto ten = [&](float *base) { PlanarTen t = L; t.p = base; return t; };
-    ep.skip_plane = L.plane;
-    ep.skip_pitch = L.pitch;
-    float *Hb = m->trunk[0].as<float>(), *Rb = m->trunk[1].as<float>(), *Xb = m->trunk[2].as<float>(), *Ab = m->trunk[3].as<float>();
-    float *Ub = m->trunk[4].as<float>(), *Tb = m->tbuf.as<float>(), *Qb = m->qbuf.as<float>();
-    unsigned char *img = m->img.as<unsigned char>();
-    const size_t part_bytes = (size_t)C * g.chunks * sizeof(double);
-    double *part = m->red.as<double>();
-    float *sc = m->red.as<float>(part_bytes);
-    const long long plane4 = L.plane / 4;
-    auto lin = [&](auto kernel, float *in, int cin, int k, int cout_planes, float *out, const float *skip) {
-        ProfScope ps(ctx, "hat_linear");
-        SwEpi e = ep;
-        e.skip = skip;
-        launch_conv(kernel, st, ten(in), hp, wp, cin, cout_planes / 64, m->w(k), m->b(k), out, L.plane, L.pitch, 0, 0, hp, wp, e);
-    };
-    auto conv = [&](float *in, int k, float *out, const float *skip) {
-        ProfScope ps(ctx, "hat_conv");
-        SwEpi e = ep;
-        e.skip = skip;
-        launch_conv(k_sw_conv<2, SW_ADD>, st, ten(in), hp, wp, Cp, Cp / 64, m->w(k), m->b(k), out, L.plane, L.pitch, 0, 0, hp, wp, e);
-    };
-    auto norm = [&](float *in, int k, float *out) {
-        ProfScope ps(ctx, "hat_ln");
-        sw_launch_layernorm(st, in, L.plane, L.pitch, hp, wp, C, Cp, m->w(k), m->b(k), out, L.plane, L.pitch);
-    };
-    auto mlp = [&](int k) {                                // x = x + fc2(gelu(fc1(LN2(x)))) on X; tables k, k + 1, k + 2
-        norm(Xb, k, Ab);
-        lin(k_sw_lin<SL_GELU>, Ab, Cp, k + 1, hidp, Qb, nullptr);
-        lin(k_sw_lin<SL_ADD>, Qb, hidp, k + 2, Cp, Xb, Xb);
-    };
-    {
-        ProfScope ps(ctx, "hat_head");
-        const long long n = (long long)g.plane0 * 3;
-        hipLaunchKernelGGL(k_hat_reflect, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_src, (long long)src_stride, h, w, img, hp, wp);
-        hipLaunchKernelGGL(k_sw_head, dim3((wp + 63) / 64, (hp + 3) / 4, Cp / 64), dim3(64, 4), 0, st, img, (long long)wp * 3, hp, wp, m->w(0), m->b(0),
-                           ep.af, Hb, hp, wp, L.pitch, L.plane);
-    }
-    int k = 1;
-    norm(Hb, k++, Rb);
-    for (int gi = 0; gi < D.n_groups; ++gi) {
-        float *x = Rb;                                     // the first layer reads the RHAG's input and writes X
+    static const SwNames names{"hat_head", "hat_ln", "hat_linear", "hat_conv", "hat_tail"};
+    return sw_forward_frame(__func__, g_ht_live, m, names, k_hat_reflect, d_src, src_stride, h, w, d_dst, dst_stride, tail, u8, who,
+                            [m](const SwTrunk &T, const SwGeom &g, int &k) {      // one RHAG: D HABs of 11 tables, one OCAB of 7
+        const sr_hat_desc &D = m->d;
+        const int hp = T.hp, wp = T.wp, C = T.C, Cp = T.Cp, heads = D.n_heads;
+        const PlanarTen &L = T.L;
+        float *Ub = m->trunk[4].as<float>(), *Tb = m->tbuf.as<float>();
+        double *part = m->red.as<double>();
+        float *sc = m->red.as<float>((size_t)C * g.chunks * sizeof(double));
+        const long long plane4 = L.plane / 4;
+        float *x = T.Rb;                                   // the first layer reads the RHAG's input and writes X
         for (int j = 0; j < D.depth; ++j, k += 11) {
-            norm(x, k, Ab);
+            T.norm(x, k, T.Ab);
             {                                              // the CAB on LN1's output, before the attention takes A
-                ProfScope ps(ctx, "hat_cab_conv");
-                launch_conv(k_sw_conv<2, SW_GELU>, st, ten(Ab), hp, wp, Cp, Tp / 64, m->w(k + 4), m->b(k + 4), Tb, L.plane, L.pitch, 0, 0, hp, wp, ep);
-                launch_conv(k_sw_conv<2, SW_PLAIN>, st, ten(Tb), hp, wp, Tp, Cp / 64, m->w(k + 5), m->b(k + 5), Ub, L.plane, L.pitch, 0, 0, hp, wp, ep);
+                ProfScope ps(T.ctx, "hat_cab_conv");
+                launch_conv(k_sw_conv<2, SW_GELU>, T.st, T.ten(T.Ab), hp, wp, Cp, g.tp / 64, m->w(k + 4), m->b(k + 4), Tb, L.plane, L.pitch, 0, 0, hp, wp,
+                            T.ep);
+                launch_conv(k_sw_conv<2, SW_PLAIN>, T.st, T.ten(Tb), hp, wp, g.tp, Cp / 64, m->w(k + 5), m->b(k + 5), Ub, L.plane, L.pitch, 0, 0, hp, wp,
+                            T.ep);
             }
-            rc_attention(st, ctx, Ub, L.plane, L.pitch, hp, wp, C, R, m->w(k + 6), m->b(k + 6), m->w(k + 7), m->b(k + 7), part, sc, nullptr,
-                         "hat_cab_reduce", "hat_cab_attention");
-            lin(k_sw_lin<SL_QKV>, Ab, Cp, k + 1, qkvp, Qb, nullptr);
+            rc_attention(T.st, T.ctx, Ub, L.plane, L.pitch, hp, wp, C, D.n_squeeze, m->w(k + 6), m->b(k + 6), m->w(k + 7), m->b(k + 7), part, sc,
+                         nullptr, "hat_cab_reduce", "hat_cab_attention");
+            T.qkv(k + 1);
             {
-                ProfScope ps(ctx, "hat_attention");
-                ht_launch<HtWindow>(st, Qb, L.plane, L.pitch, hp, wp, C, heads, j % 2 ? HT_SHIFT : 0, m->w(k + 2), Ab, L.plane, L.pitch, Cp);
+                ProfScope ps(T.ctx, "hat_attention");
+                ht_launch<HtWindow>(T.st, T.Qb, L.plane, L.pitch, hp, wp, C, heads, j % 2 ? HT_SHIFT : 0, m->w(k + 2), T.Ab, L.plane, L.pitch, Cp);
             }
-            lin(k_sw_lin<SL_ADD>, Ab, Cp, k + 3, Cp, Xb, x);
-            x = Xb;
+            T.proj(k + 3, x);
+            x = T.Xb;
             {
-                ProfScope ps(ctx, "hat_cab_scale");
-                hipLaunchKernelGGL(k_rc_scale, dim3((unsigned)((plane4 + 255) / 256), C), dim3(256), 0, st, (const float4 *)Ub, sc, (const float4 *)Xb,
-                                   (float4 *)Xb, plane4, D.conv_scale);
+                ProfScope ps(T.ctx, "hat_cab_scale");
+                hipLaunchKernelGGL(k_rc_scale, dim3((unsigned)((plane4 + 255) / 256), C), dim3(256), 0, T.st, (const float4 *)Ub, sc,
+                                   (const float4 *)T.Xb, (float4 *)T.Xb, plane4, D.conv_scale);
             }
-            mlp(k + 8);
+            T.mlp(k + 8);
         }
-        norm(x, k, Ab);                                    // the OCAB
-        lin(k_sw_lin<SL_QKV>, Ab, Cp, k + 1, qkvp, Qb, nullptr);
+        T.norm(x, k, T.Ab);                                // the OCAB
+        T.qkv(k + 1);
         {
-            ProfScope ps(ctx, "hat_oca");
-            ht_launch<HtOverlap>(st, Qb, L.plane, L.pitch, hp, wp, C, heads, 0, m->w(k + 2), Ab, L.plane, L.pitch, Cp);
+            ProfScope ps(T.ctx, "hat_oca");
+            ht_launch<HtOverlap>(T.st, T.Qb, L.plane, L.pitch, hp, wp, C, heads, 0, m->w(k + 2), T.Ab, L.plane, L.pitch, Cp);
         }
-        lin(k_sw_lin<SL_ADD>, Ab, Cp, k + 3, Cp, Xb, x);
-        x = Xb;
-        mlp(k + 4);
+        T.proj(k + 3, x);
+        x = T.Xb;
+        T.mlp(k + 4);
         k += 7;
-        conv(x, k++, Rb, Rb);                              // in place over the RHAG's input
-    }
-    norm(Rb, k++, Ab);
-    conv(Ab, k++, Hb, Hb);                                 // f = conv_after_body(.) + h, in place over h
-    if ((rc = check_launch(who))) return rc;
-    // ---- tail phase: sub-pieces of the input over their own backward extents (as sr_swinir.hip's pixelshuffle tail) ----
-    const std::vector<SwStep> steps = ht_tail_steps(D);
-    const int n = (int)steps.size();
-    const PlanarTen f = ten(Hb);
-    std::vector<int> ya, yb, xa, xb;
-    for (int sy = 0; sy < h; sy = (int)std::min<long long>((long long)sy + g.tail, h))
-        for (int sx = 0; sx < w; sx = (int)std::min<long long>((long long)sx + g.tail, w)) {
-            sw_backward_extents(steps.data(), n, S, sy, (int)std::min<long long>((long long)sy + g.tail, h), hp, ya, yb);
-            sw_backward_extents(steps.data(), n, S, sx, (int)std::min<long long>((long long)sx + g.tail, w), wp, xa, xb);
-            PlanarTen t = f;
-            ProfScope ps(ctx, "hat_tail");
-            for (int i = 0; i < n; ++i) {
-                const int rows = yb[i] - ya[i], cols = xb[i] - xa[i], mult = steps[i].mult, r = steps[i].r, kt = k + i;
-                const int kind = m->tables[kt].kind, cin = i == 0 ? Cp : SW_MID;
-                SwEpi e = ep;
-                e.slope = 0.01f;
-                e.s = r;
-                if (i + 1 < n) {
-                    const PlanarTen o = planar_tensor(m->tailbuf[i & 1].as<float>(), ya[i] * r, xa[i] * r, rows * r, cols * r);
-                    auto go = [&](auto kernel, int tiles) {
-                        launch_conv(kernel, st, t, hp * mult, wp * mult, cin, tiles, m->w(kt), m->b(kt), o.p, o.plane, o.pitch, ya[i], xa[i], rows, cols, e);
-                    };
-                    if (kind == SW_T_UP && r == 2) go(k_sw_conv<2, SW_SHUF2>, 4);
-                    else if (kind == SW_T_UP) go(k_sw_conv<2, SW_SHUF3>, 9);
-                    else go(k_sw_conv<2, SW_ACT>, 1);
-                    t = o;
-                } else {
-                    auto go = [&](auto kernel) {
-                        launch_conv(kernel, st, t, hp * mult, wp * mult, cin, 1, m->w(kt), m->b(kt), nullptr, 0LL, 0, ya[i], xa[i], rows, cols, e);
-                    };
-                    if (u8) go(k_sw_conv<1, SW_LAST_U8>);
-                    else go(k_sw_conv<1, SW_LAST_F32>);
-                }
-            }
-            if ((rc = check_launch(who))) return rc;
-        }
-    return SR_OK;
-}
-
-// The self-ensemble over ht_forward (driver: sr_ensemble.hip): every member is reflected, padded and windowed on its own.
-static int ht_ensemble(sr_hat_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride, int tail,
-                       int mask, bool u8, const char *who)
-{
-    const int rc = sr_ens_check_mask(who, mask);
-    if (rc) return rc;
-    if (tail < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: %s must be >= 1, or 0 for the library's choice", who, "tail");
-    if (!g_ht_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
-    return ens_run(who, *m, m->d.scale, [&](const uint8_t *s, int64_t ss, int hh, int ww, float *d, int64_t ds) {
-        return ht_forward(m, s, ss, hh, ww, d, ds, tail, false, who);
-    }, d_src, src_stride, h, w, d_dst, dst_stride, mask, u8);
-}
-
-// What the two inspection entry points share: the checks of the description of one attention call.
-static int ht_check_attention(const char *who, int C, int n_heads, int hp, int wp)
-{
-    if (C < 1 || C > 256 || n_heads < 1 || C % n_heads || C / n_heads > 32)
-        return sr_set_error(SR_ERR_UNSUPPORTED, "%s: %d channels in %d heads is outside C <= 256, heads of at most 32 channels", who, C, n_heads);
-    if (hp < HT_WIN || wp < HT_WIN || hp % HT_WIN || wp % HT_WIN)
-        return sr_set_error(SR_ERR_SHAPE, "%s: a %dx%d tensor is not made of %d x %d windows", who, wp, hp, HT_WIN, HT_WIN);
-    return SR_OK;
+        return x;
+    });
 }
 
 extern "C" {
@@ -493,84 +358,19 @@ int sr_hat_create(sr_ctx *ctx, const sr_hat_desc *desc, const float *const *h_w,
                   sr_hat_model **out)
 {
     const char *who = "sr_hat_create";
-    if (!out) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null out", who);
-    *out = nullptr;
-    int rc = ht_check_desc(who, desc);                                      // host decision, before any device call
-    if (rc) return rc;
-    const std::vector<SwTable> tables = ht_tables(*desc);
-    if (!h_w || !h_b) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null weight table", who);
-    if (n_tables != (int)tables.size())
-        return sr_set_error(SR_ERR_INVALID_ARG, "%s: this description has %d tables, %d given", who, (int)tables.size(), n_tables);
-    for (int k = 0; k < n_tables; ++k) {
-        const bool rpb = tables[k].kind == SW_T_RPB || tables[k].kind == HT_T_RPB_OCA;
-        if (!h_w[k] || (!h_b[k] && !rpb)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null array of table %d", who, k);
-    }
-    std::vector<int> rel(HT_TOK * HT_TOK), oca(HT_TOK * HT_KEYS);
-    ht_rel_index(rel.data());
-    if (h_rpi_oca) {
-        if ((rc = ht_wrap_oca_index(who, h_rpi_oca, oca.data()))) return rc;
-    } else {
-        ht_oca_index(oca.data());
-    }
-    CTX_ENTER(ctx);
-    sr_hat_model *M = new sr_hat_model();
-    M->ctx = ctx;
-    M->d = *desc;
-    M->tables = tables;
-    g_ht_live.insert(M);
-    const int C = desc->n_feat, Cp = sw_pad64(C), hidp = sw_pad64(desc->n_hidden), Tp = sw_pad64(desc->n_mid), R = desc->n_squeeze;
-    for (int k = 0; k < n_tables; ++k) {
-        const SwTable &t = tables[k];
-        MfmaWeights a;
-        switch (t.kind) {
-        case SW_T_HEAD: {
-            std::vector<float> wpad((size_t)Cp * 27, 0.0f);
-            std::memcpy(wpad.data(), h_w[k], (size_t)C * 27 * sizeof(float));
-            a.w = arrange_head_weights(wpad.data(), Cp);
-            a.b.assign(Cp, 0.0f);
-            std::memcpy(a.b.data(), h_b[k], (size_t)C * sizeof(float));
-            break;
-        }
-        case SW_T_LN:
-            a = {std::vector<float>(h_w[k], h_w[k] + C), std::vector<float>(h_b[k], h_b[k] + C)};
-            break;
-        case SW_T_RPB:
-            a = {ht_gather_bias(h_w[k], rel.data(), HT_TOK, desc->n_heads), std::vector<float>(1, 0.0f)};
-            break;
-        case HT_T_RPB_OCA:
-            a = {ht_gather_bias(h_w[k], oca.data(), HT_KEYS, desc->n_heads), std::vector<float>(1, 0.0f)};
-            break;
-        case SW_T_QKV: case SW_T_PROJ: case SW_T_FC1:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 1, Cp, SW_LIN_CC, 64);
-            break;
-        case SW_T_FC2:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 1, hidp, SW_LIN_CC, 64);
-            break;
-        case SW_T_CONV: case SW_T_CBU: case HT_T_CAB0:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 9, Cp, 8, 64);
-            break;
-        case HT_T_CAB2:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 9, Tp, 8, 64);
-            break;
-        case HT_T_ATT1:
-            a = {std::vector<float>(h_w[k], h_w[k] + (size_t)R * C), std::vector<float>(h_b[k], h_b[k] + R)};
-            break;
-        case HT_T_ATT3:
-            a = {std::vector<float>(h_w[k], h_w[k] + (size_t)C * R), std::vector<float>(h_b[k], h_b[k] + C)};
-            break;
-        case SW_T_LAST:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 9, SW_MID, 8, 32);
-            break;
-        default:                                                            // SW_T_UP
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 9, SW_MID, 8, 64);
-        }
-        if ((rc = upload_conv(who, *M, a))) {
-            sr_hat_destroy(M);
-            return rc;
-        }
-    }
-    *out = M;
-    return SR_OK;
+    std::vector<int> oca(HT_TOK * HT_KEYS);
+    return sw_create(who, ctx, desc, h_w, h_b, n_tables, g_ht_live, out, [&] { return ht_oca_index_of(who, h_rpi_oca, oca.data()); },
+                     [&](const SwTable &t, const float *w, const float *b, MfmaWeights &a) {
+        const int C = desc->n_feat, R = desc->n_squeeze;
+        if (t.kind == SW_T_RPB) a = {sw_gather_window_bias(w, HT_WIN, desc->n_heads), std::vector<float>(1, 0.0f)};
+        else if (t.kind == HT_T_RPB_OCA) a = {sw_gather_bias(w, oca.data(), HT_KEYS, HT_TOK, desc->n_heads), std::vector<float>(1, 0.0f)};
+        else if (t.kind == HT_T_CAB0) a = sw_arrange(w, b, t.cout, t.cin, 9, sw_pad64(C), 8, 64);
+        else if (t.kind == HT_T_CAB2) a = sw_arrange(w, b, t.cout, t.cin, 9, sw_pad64(desc->n_mid), 8, 64);
+        else if (t.kind == HT_T_ATT1) a = {std::vector<float>(w, w + (size_t)R * C), std::vector<float>(b, b + R)};
+        else if (t.kind == HT_T_ATT3) a = {std::vector<float>(w, w + (size_t)C * R), std::vector<float>(b, b + C)};
+        else return false;
+        return true;
+    });
 }
 
 int sr_hat_destroy(sr_hat_model *m)
@@ -591,80 +391,47 @@ int sr_hat_f32(sr_hat_model *model, const uint8_t *d_src, int64_t src_stride, in
 int sr_hat_ens_u8(sr_hat_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst, int64_t dst_stride, int tail,
                   int mask)
 {
-    return ht_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tail, mask, true, "sr_hat_ens_u8");
+    return sw_ensemble(g_ht_live, model, ht_forward, d_src, src_stride, h, w, d_dst, dst_stride, tail, mask, true, "sr_hat_ens_u8");
 }
 
 int sr_hat_ens_f32(sr_hat_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst, int64_t dst_stride, int tail,
                    int mask)
 {
-    return ht_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tail, mask, false, "sr_hat_ens_f32");
+    return sw_ensemble(g_ht_live, model, ht_forward, d_src, src_stride, h, w, d_dst, dst_stride, tail, mask, false, "sr_hat_ens_f32");
 }
 
 int sr_hat_fill_workspace(sr_hat_model *m, int h, int w, int tail, int byte)
 {
-    const char *who = "sr_hat_fill_workspace";
-    if (!g_ht_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
-    sr_ctx *ctx = m->ctx;
-    CTX_ENTER(ctx);
-    HtGeom g;
-    int rc = ht_geometry(who, m->d, h, w, tail, g);
-    if (rc) return rc;
-    if ((rc = ht_reserve(m, g, who))) return rc;
-    for (DevBuf *b : {&m->trunk[0], &m->trunk[1], &m->trunk[2], &m->trunk[3], &m->trunk[4], &m->tbuf, &m->qbuf, &m->tailbuf[0], &m->tailbuf[1],
-                      &m->img, &m->red})
-        if (b->d) HIPCHK(hipMemsetAsync(b->d, byte, b->cap, ctx->stream));
-    return SR_OK;
+    return sw_fill_workspace("sr_hat_fill_workspace", g_ht_live, m, h, w, tail, byte);
 }
 
 int sr_hat_attention_f32(sr_ctx *ctx, const float *d_qkv, int64_t plane_stride, int64_t row_stride, int n_feat, int n_heads, int hp, int wp,
                          int shift, const float *h_table, float *d_out, int64_t out_plane_stride, int64_t out_row_stride)
 {
     const char *who = "sr_hat_attention_f32";
-    if (!d_qkv || !h_table || !d_out) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    if ((rc = ht_check_attention(who, n_feat, n_heads, hp, wp))) return rc;
+    if ((rc = sw_check_attention_args(who, d_qkv, h_table, d_out, n_feat, n_heads))) return rc;
+    if ((rc = sw_check_windows(who, hp, wp, HT_WIN))) return rc;
     if (shift != 0 && shift != HT_SHIFT) return sr_set_error(SR_ERR_UNSUPPORTED, "%s: shift %d (supported: 0, %d)", who, shift, HT_SHIFT);
-    if ((rc = sw_check_view(who, d_qkv, plane_stride, row_stride, hp, wp))) return rc;
-    if ((rc = sw_check_view(who, d_out, out_plane_stride, out_row_stride, hp, wp))) return rc;
-    CTX_ENTER(ctx);
-    std::vector<int> rel(HT_TOK * HT_TOK);
-    ht_rel_index(rel.data());
-    const std::vector<float> g = ht_gather_bias(h_table, rel.data(), HT_TOK, n_heads);
-    DevTemp tmp(ctx);
-    SRCHK(tmp.alloc(who, g.size() * sizeof(float)));
-    HIPCHK(hipMemcpyAsync(tmp.d, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    ht_launch<HtWindow>(ctx->stream, d_qkv, plane_stride / 4, (int)(row_stride / 4), hp, wp, n_feat, n_heads, shift, tmp.as<float>(), d_out,
-                        out_plane_stride / 4, (int)(out_row_stride / 4), n_feat);
-    SRCHK(check_launch(who));
-    HIPCHK(stream_sync(ctx));
-    return SR_OK;
+    return sw_run_attention(who, ctx, d_qkv, plane_stride, row_stride, n_heads, hp, wp, h_table, HT_TOK, HT_TOK, d_out, out_plane_stride,
+                            out_row_stride, [](int *idx) { sw_rel_index(HT_WIN, idx); return SR_OK; },
+                            [&](hipStream_t st, const float *qkv, long long plane, int pitch, const float *bias, float *out, long long oplane, int opitch) {
+        ht_launch<HtWindow>(st, qkv, plane, pitch, hp, wp, n_feat, n_heads, shift, bias, out, oplane, opitch, n_feat);
+    });
 }
 
 int sr_hat_oca_f32(sr_ctx *ctx, const float *d_qkv, int64_t plane_stride, int64_t row_stride, int n_feat, int n_heads, int hp, int wp,
                    const float *h_table, const int *h_index, float *d_out, int64_t out_plane_stride, int64_t out_row_stride)
 {
     const char *who = "sr_hat_oca_f32";
-    if (!d_qkv || !h_table || !d_out) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    if ((rc = ht_check_attention(who, n_feat, n_heads, hp, wp))) return rc;
-    if ((rc = sw_check_view(who, d_qkv, plane_stride, row_stride, hp, wp))) return rc;
-    if ((rc = sw_check_view(who, d_out, out_plane_stride, out_row_stride, hp, wp))) return rc;
-    std::vector<int> oca(HT_TOK * HT_KEYS);
-    if (h_index) {
-        if ((rc = ht_wrap_oca_index(who, h_index, oca.data()))) return rc;
-    } else {
-        ht_oca_index(oca.data());
-    }
-    CTX_ENTER(ctx);
-    const std::vector<float> g = ht_gather_bias(h_table, oca.data(), HT_KEYS, n_heads);
-    DevTemp tmp(ctx);
-    SRCHK(tmp.alloc(who, g.size() * sizeof(float)));
-    HIPCHK(hipMemcpyAsync(tmp.d, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    ht_launch<HtOverlap>(ctx->stream, d_qkv, plane_stride / 4, (int)(row_stride / 4), hp, wp, n_feat, n_heads, 0, tmp.as<float>(), d_out,
-                  out_plane_stride / 4, (int)(out_row_stride / 4), n_feat);
-    SRCHK(check_launch(who));
-    HIPCHK(stream_sync(ctx));
-    return SR_OK;
+    if ((rc = sw_check_attention_args(who, d_qkv, h_table, d_out, n_feat, n_heads))) return rc;
+    if ((rc = sw_check_windows(who, hp, wp, HT_WIN))) return rc;
+    return sw_run_attention(who, ctx, d_qkv, plane_stride, row_stride, n_heads, hp, wp, h_table, HT_KEYS, HT_TOK, d_out, out_plane_stride,
+                            out_row_stride, [&](int *idx) { return ht_oca_index_of(who, h_index, idx); },
+                            [&](hipStream_t st, const float *qkv, long long plane, int pitch, const float *bias, float *out, long long oplane, int opitch) {
+        ht_launch<HtOverlap>(st, qkv, plane, pitch, hp, wp, n_feat, n_heads, 0, bias, out, oplane, opitch, n_feat);
+    });
 }
 
 }  // extern "C"

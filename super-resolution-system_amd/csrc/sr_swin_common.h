@@ -1,8 +1,13 @@
 // sr_swin_common.h -- what the Swin-trunk backends (sr_swinir.hip, sr_hat.hip) share on the device side: the head from a padded
 // u8 image, the LayerNorm, the linear layers and the 3 x 3 convolutions (sr_conv_mfma.h's mainloop behind their epilogues) and
-// the weight arrangement.  Everything sits in an anonymous namespace: every unit that includes this header gets its own copy of
+// the weight arrangement -- and, below them, the frame of a family around its own blocks: the model base and its workspace
+// (SwModelBase, sw_reserve, sw_fill_workspace), the trunk phase's steps (SwTrunk), the forward (sw_forward_frame), the tail phase
+// (sw_run_tail), the create (sw_create, sw_arrange_shared), the ensemble wrapper, the bias gather, the launch by head width and
+// the inspection calls of the attention kernels.  A family keeps its kernels, the body of one group, its own table kinds and
+// its entry points.  Everything sits in an anonymous namespace: every unit that includes this header gets its own copy of
 // the kernels, exactly as if they were written there.  Internal: nothing here is part of the C ABI.
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -244,6 +249,365 @@ inline int sw_check_view(const char *who, const void *p, int64_t plane_stride, i
     if (row_stride % 4 || plane_stride % 4 || (uintptr_t)p % 4)
         return sr_set_error(SR_ERR_INVALID_ARG, "%s: the pointers and the strides must be multiples of 4 bytes", who);
     if (row_stride / 4 > INT_MAX) return sr_set_error(SR_ERR_SHAPE, "%s: a row stride beyond int", who);
+    return SR_OK;
+}
+
+// ===============================================================================================================
+// The frame of a family: the model, the workspace, the trunk phase around the family's own blocks, the tail phase, the
+// create, the ensemble and the inspection calls.  A family's model derives from SwModelBase and adds
+//   d                                       its description (n_feat, n_heads, n_hidden, n_groups, depth, scale, mean, range)
+//   SHUFFLE_ONLY                            whether its reconstruction is always the pixelshuffle one
+//   check_desc, table_list, bias_table      (static) its description check, its tables, the kinds whose bias entry is ignored
+//   geometry, tail_steps                    its plan
+// Everything is resolved at compile time: no std::function and no virtual call on the launch path.
+// ===============================================================================================================
+struct SwModelBase : SrModelBase {             // d_w, d_b: per table
+    std::vector<SwTable> tables;
+    DevBuf trunk[5];                          // H, R, X, A and (HAT) U: the first SwGeom::trunk_bufs are in use
+    DevBuf tbuf;                              // HAT: the CAB's middle tensor
+    DevBuf qbuf;                              // qkv / hidden
+    DevBuf tailbuf[2];
+    DevBuf img;                               // the reflected u8 image
+    DevBuf red;                               // HAT: C x chunks float64 chunk sums, then s[C]
+    std::array<DevBuf *, 11> buffers()
+    {
+        return {&trunk[0], &trunk[1], &trunk[2], &trunk[3], &trunk[4], &tbuf, &qbuf, &tailbuf[0], &tailbuf[1], &img, &red};
+    }
+    void release_device()
+    {
+        for (DevBuf *b : buffers()) b->release();
+        release_base();
+    }
+};
+
+inline int sw_reserve(SwModelBase *m, const SwGeom &g, const char *who)
+{
+    sr_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = ensure_activation_buffers(ctx, m->trunk, g.trunk_bufs, (size_t)g.plane0 * g.cp, who))) return rc;
+    if (g.tp && (rc = ensure_activation_buffers(ctx, &m->tbuf, 1, (size_t)g.plane0 * g.tp, who))) return rc;
+    if ((rc = ensure_activation_buffers(ctx, &m->qbuf, 1, (size_t)g.plane0 * g.qp, who))) return rc;
+    if (g.plane_t && (rc = ensure_activation_buffers(ctx, m->tailbuf, 2, (size_t)g.plane_t * SW_MID, who))) return rc;
+    SRCHK(m->img.reserve(ctx, who, (size_t)g.plane0 * 3));
+    if (g.red_bytes) SRCHK(m->red.reserve(ctx, who, g.red_bytes));
+    return SR_OK;
+}
+
+template <typename Model>
+int sw_fill_workspace(const char *who, LiveSet &live, Model *m, int h, int w, int tail, int byte)
+{
+    if (!live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
+    sr_ctx *ctx = m->ctx;
+    CTX_ENTER_AS(ctx, who);
+    SwGeom g;
+    int rc = m->geometry(who, h, w, tail, g);
+    if (rc) return rc;
+    if ((rc = sw_reserve(m, g, who))) return rc;
+    for (DevBuf *b : m->buffers())
+        if (b->d) HIPCHK(hipMemsetAsync(b->d, byte, b->cap, ctx->stream));
+    return SR_OK;
+}
+
+struct SwNames {                               // a family's profile scopes
+    const char *head, *ln, *linear, *conv, *tail;
+};
+
+// The trunk phase: the whole padded image, every tensor in one layout L; table k's arrays are m->w(k), m->b(k).
+struct SwTrunk {
+    sr_ctx *ctx;
+    hipStream_t st;
+    SwModelBase *m;
+    SwNames nm;
+    PlanarTen L;
+    SwEpi ep;
+    int hp, wp, C, Cp, hidp, qkvp;
+    float *Hb, *Rb, *Xb, *Ab, *Qb;             // h then f;  the group's input then output;  the running x;  LN / attention output;  qkv / hidden
+    PlanarTen ten(float *base) const
+    {
+        PlanarTen t = L;
+        t.p = base;
+        return t;
+    }
+    template <typename Kernel>
+    void lin(Kernel kernel, float *in, int cin, int k, int cout_planes, float *out, const float *skip) const
+    {
+        ProfScope ps(ctx, nm.linear);
+        SwEpi e = ep;
+        e.skip = skip;
+        launch_conv(kernel, st, ten(in), hp, wp, cin, cout_planes / 64, m->w(k), m->b(k), out, L.plane, L.pitch, 0, 0, hp, wp, e);
+    }
+    void conv(float *in, int k, float *out, const float *skip) const
+    {
+        ProfScope ps(ctx, nm.conv);
+        SwEpi e = ep;
+        e.skip = skip;
+        launch_conv(k_sw_conv<2, SW_ADD>, st, ten(in), hp, wp, Cp, Cp / 64, m->w(k), m->b(k), out, L.plane, L.pitch, 0, 0, hp, wp, e);
+    }
+    void norm(float *in, int k, float *out) const
+    {
+        ProfScope ps(ctx, nm.ln);
+        sw_launch_layernorm(st, in, L.plane, L.pitch, hp, wp, C, Cp, m->w(k), m->b(k), out, L.plane, L.pitch);
+    }
+    void qkv(int k) const { lin(k_sw_lin<SL_QKV>, Ab, Cp, k, qkvp, Qb, nullptr); }            // A -> Q
+    void proj(int k, const float *x) const { lin(k_sw_lin<SL_ADD>, Ab, Cp, k, Cp, Xb, x); }   // X = x + proj(A)
+    void mlp(int k) const                                  // x = x + fc2(gelu(fc1(LN2(x)))) on X; tables k, k + 1, k + 2
+    {
+        norm(Xb, k, Ab);
+        lin(k_sw_lin<SL_GELU>, Ab, Cp, k + 1, hidp, Qb, nullptr);
+        lin(k_sw_lin<SL_ADD>, Qb, hidp, k + 2, Cp, Xb, Xb);
+    }
+    template <typename Reflect>
+    void head(Reflect reflect, const uint8_t *d_src, int64_t src_stride, int h, int w) const   // the family's reflection, then table 0 -> H
+    {
+        ProfScope ps(ctx, nm.head);
+        unsigned char *img = m->img.as<unsigned char>();
+        const long long n = (long long)hp * wp * 3;
+        hipLaunchKernelGGL(reflect, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_src, (long long)src_stride, h, w, img, hp, wp);
+        hipLaunchKernelGGL(k_sw_head, dim3((wp + 63) / 64, (hp + 3) / 4, Cp / 64), dim3(64, 4), 0, st, img, (long long)wp * 3, hp, wp, m->w(0), m->b(0),
+                           ep.af, Hb, hp, wp, L.pitch, L.plane);
+    }
+};
+
+// The tail phase: sub-pieces of the input over their own backward extents; the tables from k on.  SHUFFLE_ONLY leaves out the
+// launches only the other two reconstructions have (a unit that never runs them does not carry their kernels).
+template <bool SHUFFLE_ONLY>
+int sw_run_tail(const SwTrunk &T, const std::vector<SwStep> &steps, int k, int S, int h, int w, int tail, bool u8, const char *who)
+{
+    SwModelBase *m = T.m;
+    const int n = (int)steps.size(), hp = T.hp, wp = T.wp;
+    const PlanarTen f = T.ten(T.Hb);
+    std::vector<int> ya, yb, xa, xb;
+    int rc;
+    for (int sy = 0; sy < h; sy = (int)std::min<long long>((long long)sy + tail, h))
+        for (int sx = 0; sx < w; sx = (int)std::min<long long>((long long)sx + tail, w)) {
+            sw_backward_extents(steps.data(), n, S, sy, (int)std::min<long long>((long long)sy + tail, h), hp, ya, yb);
+            sw_backward_extents(steps.data(), n, S, sx, (int)std::min<long long>((long long)sx + tail, w), wp, xa, xb);
+            PlanarTen t = f;
+            ProfScope ps(T.ctx, T.nm.tail);
+            for (int i = 0; i < n; ++i) {
+                const int rows = yb[i] - ya[i], cols = xb[i] - xa[i], mult = steps[i].mult, r = steps[i].r, kt = k + i;
+                const int kind = m->tables[kt].kind, cin = i == 0 ? T.Cp : SW_MID;
+                SwEpi e = T.ep;
+                e.slope = kind == SW_T_CBU ? 0.01f : 0.2f;  // read by SW_ACT and SW_REP_ACT alone
+                e.s = r;
+                if (i + 1 < n) {
+                    const PlanarTen o = planar_tensor(m->tailbuf[i & 1].as<float>(), ya[i] * r, xa[i] * r, rows * r, cols * r);
+                    auto go = [&](auto kernel, int tiles) {
+                        launch_conv(kernel, T.st, t, hp * mult, wp * mult, cin, tiles, m->w(kt), m->b(kt), o.p, o.plane, o.pitch, ya[i], xa[i], rows, cols, e);
+                    };
+                    if (kind == SW_T_UP && r == 2) go(k_sw_conv<2, SW_SHUF2>, 4);
+                    else if (kind == SW_T_UP) go(k_sw_conv<2, SW_SHUF3>, 9);
+                    else if constexpr (SHUFFLE_ONLY) go(k_sw_conv<2, SW_ACT>, 1);
+                    else r == 2 ? go(k_sw_conv<2, SW_REP_ACT>, 1) : go(k_sw_conv<2, SW_ACT>, 1);
+                    t = o;
+                } else {
+                    auto go = [&](auto kernel) {
+                        launch_conv(kernel, T.st, t, hp * mult, wp * mult, cin, 1, m->w(kt), m->b(kt), nullptr, 0LL, 0, ya[i], xa[i], rows, cols, e);
+                    };
+                    bool wide = false;                     // more than 32 couts: pixelshuffledirect at scale 4
+                    if constexpr (!SHUFFLE_ONLY) wide = 3 * r * r > 32;
+                    if (!wide) u8 ? go(k_sw_conv<1, SW_LAST_U8>) : go(k_sw_conv<1, SW_LAST_F32>);
+                    else if constexpr (!SHUFFLE_ONLY) u8 ? go(k_sw_conv<2, SW_LAST_U8>) : go(k_sw_conv<2, SW_LAST_F32>);
+                }
+            }
+            if ((rc = check_launch(who))) return rc;
+        }
+    return SR_OK;
+}
+
+// A family's forward: everything but its groups.  group(T, g, k) runs the blocks of one group from the group's input T.Rb,
+// advances k past their tables and returns where the group's x lies; fn: the name a dead context is reported under.
+template <typename Model, typename Reflect, typename Group>
+int sw_forward_frame(const char *fn, LiveSet &live, Model *m, const SwNames &nm, Reflect reflect, const uint8_t *d_src, int64_t src_stride, int h,
+                     int w, void *d_dst, int64_t dst_stride, int tail, bool u8, const char *who, Group group)
+{
+    if (!live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
+    sr_ctx *ctx = m->ctx;
+    CTX_ENTER_AS(ctx, fn);
+    const auto &D = m->d;
+    const int C = D.n_feat, S = D.scale;
+    int rc = check_sr_forward_args(who, d_src, src_stride, w, d_dst, dst_stride, S, u8);
+    if (rc) return rc;
+    SwGeom g;
+    if ((rc = m->geometry(who, h, w, tail, g))) return rc;
+    if ((rc = sw_reserve(m, g, who))) return rc;
+    SwTrunk T{};
+    T.ctx = ctx;
+    T.st = ctx->stream;
+    T.m = m;
+    T.nm = nm;
+    T.L = planar_tensor(nullptr, 0, 0, g.hp, g.wp);
+    T.ep.af = {{D.mean[0], D.mean[1], D.mean[2]}, D.range};
+    T.ep.dst = d_dst;
+    T.ep.dst_stride = (long long)dst_stride;
+    T.ep.s = 1;
+    T.ep.nq = C;
+    T.ep.qscale = 1.0f / sqrtf((float)(C / D.n_heads));
+    T.ep.skip_plane = T.L.plane;
+    T.ep.skip_pitch = T.L.pitch;
+    T.hp = g.hp, T.wp = g.wp, T.C = C, T.Cp = g.cp, T.hidp = sw_pad64(D.n_hidden), T.qkvp = sw_pad64(3 * C);
+    T.Hb = m->trunk[0].template as<float>(), T.Rb = m->trunk[1].template as<float>(), T.Xb = m->trunk[2].template as<float>();
+    T.Ab = m->trunk[3].template as<float>(), T.Qb = m->qbuf.template as<float>();
+    T.head(reflect, d_src, src_stride, h, w);
+    int k = 1;
+    T.norm(T.Hb, k++, T.Rb);
+    for (int gi = 0; gi < D.n_groups; ++gi) {
+        float *x = group(T, g, k);
+        T.conv(x, k++, T.Rb, T.Rb);                        // in place over the group's input
+    }
+    T.norm(T.Rb, k++, T.Ab);
+    T.conv(T.Ab, k++, T.Hb, T.Hb);                         // f = conv_after_body(.) + h, in place over h
+    if ((rc = check_launch(who))) return rc;
+    return sw_run_tail<Model::SHUFFLE_ONLY>(T, m->tail_steps(), k, S, h, w, g.tail, u8, who);
+}
+
+// The self-ensemble over a family's forward fwd (driver: sr_ensemble.hip): every member is padded and windowed on its own.
+template <typename Model, typename Forward>
+int sw_ensemble(LiveSet &live, Model *m, Forward fwd, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride,
+                int tail, int mask, bool u8, const char *who)
+{
+    const int rc = sr_ens_check_mask(who, mask);
+    if (rc) return rc;
+    if (tail < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: %s must be >= 1, or 0 for the library's choice", who, "tail");
+    if (!live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
+    return ens_run(who, *m, m->d.scale, [&](const uint8_t *s, int64_t ss, int hh, int ww, float *d, int64_t ds) {
+        return fwd(m, s, ss, hh, ww, d, ds, tail, false, who);
+    }, d_src, src_stride, h, w, d_dst, dst_stride, mask, u8);
+}
+
+// The tables of the kinds both families have -> the kernels' layouts; false: the kind is the family's own.
+inline bool sw_arrange_shared(const SwTable &t, const float *w, const float *b, int C, int hidden, MfmaWeights &a)
+{
+    const int Cp = sw_pad64(C);
+    switch (t.kind) {
+    case SW_T_HEAD: {
+        std::vector<float> wpad((size_t)Cp * 27, 0.0f);
+        std::memcpy(wpad.data(), w, (size_t)C * 27 * sizeof(float));
+        a.w = arrange_head_weights(wpad.data(), Cp);
+        a.b.assign(Cp, 0.0f);
+        std::memcpy(a.b.data(), b, (size_t)C * sizeof(float));
+        return true;
+    }
+    case SW_T_LN:
+        a = {std::vector<float>(w, w + C), std::vector<float>(b, b + C)};
+        return true;
+    case SW_T_QKV: case SW_T_PROJ: case SW_T_FC1:
+        a = sw_arrange(w, b, t.cout, t.cin, 1, Cp, SW_LIN_CC, 64);
+        return true;
+    case SW_T_FC2:
+        a = sw_arrange(w, b, t.cout, t.cin, 1, sw_pad64(hidden), SW_LIN_CC, 64);
+        return true;
+    case SW_T_CONV: case SW_T_CBU:
+        a = sw_arrange(w, b, t.cout, t.cin, 9, Cp, 8, 64);
+        return true;
+    case SW_T_UP:
+        a = sw_arrange(w, b, t.cout, t.cin, 9, SW_MID, 8, 64);
+        return true;
+    case SW_T_LAST:
+        a = sw_arrange(w, b, t.cout, t.cin, 9, SW_MID, 8, 32);
+        return true;
+    }
+    return false;
+}
+
+// The body of a family's create.  pre(): what the family checks of its further arguments before the context is entered;
+// own(t, w, b, a): arranges a table of one of the family's own kinds and returns true, or returns false.
+template <typename Model, typename Desc, typename Pre, typename Own>
+int sw_create(const char *who, sr_ctx *ctx, const Desc *desc, const float *const *h_w, const float *const *h_b, int n_tables, LiveSet &live,
+              Model **out, Pre pre, Own own)
+{
+    if (!out) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null out", who);
+    *out = nullptr;
+    int rc = Model::check_desc(who, desc);                                  // host decision, before any device call
+    if (rc) return rc;
+    const std::vector<SwTable> tables = Model::table_list(*desc);
+    if (!h_w || !h_b) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null weight table", who);
+    if (n_tables != (int)tables.size())
+        return sr_set_error(SR_ERR_INVALID_ARG, "%s: this description has %d tables, %d given", who, (int)tables.size(), n_tables);
+    for (int k = 0; k < n_tables; ++k)
+        if (!h_w[k] || (!h_b[k] && !Model::bias_table(tables[k].kind))) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null array of table %d", who, k);
+    if ((rc = pre())) return rc;
+    CTX_ENTER_AS(ctx, who);
+    Model *M = new Model();
+    M->ctx = ctx;
+    M->d = *desc;
+    M->tables = tables;
+    live.insert(M);
+    for (int k = 0; k < n_tables; ++k) {
+        MfmaWeights a;
+        if (!own(tables[k], h_w[k], h_b[k], a)) sw_arrange_shared(tables[k], h_w[k], h_b[k], desc->n_feat, desc->n_hidden, a);
+        if ((rc = upload_conv(who, *M, a))) {
+            destroy_model(M, live);
+            return rc;
+        }
+    }
+    *out = M;
+    return SR_OK;
+}
+
+// A bias table [rows][heads] gathered through idx [nq][nk] to [head][key j][query i].
+inline std::vector<float> sw_gather_bias(const float *table, const int *idx, int nk, int nq, int heads)
+{
+    std::vector<float> g((size_t)heads * nk * nq);
+    for (int hd = 0; hd < heads; ++hd)
+        for (int j = 0; j < nk; ++j)
+            for (int i = 0; i < nq; ++i) g[((size_t)hd * nk + j) * nq + i] = table[(size_t)idx[i * nk + j] * heads + hd];
+    return g;
+}
+
+inline std::vector<float> sw_gather_window_bias(const float *table, int win, int heads)     // through sw_rel_index(win)
+{
+    std::vector<int> rel((size_t)win * win * win * win);
+    sw_rel_index(win, rel.data());
+    return sw_gather_bias(table, rel.data(), win * win, win * win, heads);
+}
+
+// One of four instantiations of an attention kernel by the head width d (their LDS holds d rounded up to a multiple of 8).
+template <typename Kernel, typename... Args>
+void sw_launch_by_d(int d, Kernel k8, Kernel k16, Kernel k24, Kernel k32, dim3 grid, dim3 block, hipStream_t st, Args... args)
+{
+    const Kernel kernel = d <= 8 ? k8 : d <= 16 ? k16 : d <= 24 ? k24 : k32;
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+}
+
+// The inspection entry points of the attention kernels: first the arguments every one of them checks first ...
+inline int sw_check_attention_args(const char *who, const void *d_qkv, const void *h_table, const void *d_out, int C, int n_heads)
+{
+    if (!d_qkv || !h_table || !d_out) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null argument", who);
+    if (C < 1 || C > 256 || n_heads < 1 || C % n_heads || C / n_heads > 32)
+        return sr_set_error(SR_ERR_UNSUPPORTED, "%s: %d channels in %d heads is outside C <= 256, heads of at most 32 channels", who, C, n_heads);
+    return SR_OK;
+}
+
+inline int sw_check_windows(const char *who, int hp, int wp, int win)
+{
+    if (hp < win || wp < win || hp % win || wp % win)
+        return sr_set_error(SR_ERR_SHAPE, "%s: a %dx%d tensor is not made of %d x %d windows", who, wp, hp, win, win);
+    return SR_OK;
+}
+
+// ... then, once the family's own checks have passed: the two views, the index [nq][nk] of the bias table (index(idx) -> rc),
+// the upload of the gathered table, launch(stream, qkv, plane, pitch, bias, out, oplane, opitch) with the strides in floats,
+// and the sync.
+template <typename Index, typename Launch>
+int sw_run_attention(const char *who, sr_ctx *ctx, const float *d_qkv, int64_t plane_stride, int64_t row_stride, int n_heads, int hp, int wp,
+                     const float *h_table, int nk, int nq, float *d_out, int64_t out_plane_stride, int64_t out_row_stride, Index index,
+                     Launch launch)
+{
+    int rc;
+    if ((rc = sw_check_view(who, d_qkv, plane_stride, row_stride, hp, wp))) return rc;
+    if ((rc = sw_check_view(who, d_out, out_plane_stride, out_row_stride, hp, wp))) return rc;
+    std::vector<int> idx((size_t)nq * nk);
+    if ((rc = index(idx.data()))) return rc;
+    CTX_ENTER_AS(ctx, who);
+    const std::vector<float> g = sw_gather_bias(h_table, idx.data(), nk, nq, n_heads);
+    DevTemp tmp(ctx);
+    SRCHK(tmp.alloc(who, g.size() * sizeof(float)));
+    HIPCHK(hipMemcpyAsync(tmp.d, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    launch(ctx->stream, d_qkv, (long long)(plane_stride / 4), (int)(row_stride / 4), tmp.as<float>(), d_out, (long long)(out_plane_stride / 4),
+           (int)(out_row_stride / 4));
+    SRCHK(check_launch(who));
+    HIPCHK(stream_sync(ctx));
     return SR_OK;
 }
 

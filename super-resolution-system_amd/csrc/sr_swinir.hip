@@ -48,9 +48,10 @@
 // keys ascending from +0, p_j = e_j / sum (the division comes BEFORE the a v sum, as torch's softmax), and the a v sum is an
 // fmaf chain over keys ascending from +0.  No atomics.  Nothing depends on tail.  Equal inputs give equal bits.
 //
-// The head, the LayerNorm, the linear layers, the 3 x 3 convolutions (k_sw_head, k_sw_layernorm, k_sw_lin, k_sw_conv) and the
-// weight arrangement are sr_swin_common.h, shared with sr_hat.hip; this file keeps the reflection, the window attention, the
-// model and the forward.
+// The head, the LayerNorm, the linear layers, the 3 x 3 convolutions (k_sw_head, k_sw_layernorm, k_sw_lin, k_sw_conv), the
+// weight arrangement and the whole frame around a family's blocks (the model's buffers, the trunk and the tail phase, the
+// create, the ensemble, the inspection calls) are sr_swin_common.h, shared with sr_hat.hip; this file keeps the reflection, the
+// window attention, the body of one RSTB, SwinIR's own table kinds and the entry points.
 //
 // Weights are caller-supplied (sr_swinir_create); nothing is fetched.
 #include <cmath>
@@ -177,182 +178,45 @@ void sw_launch_attention(hipStream_t st, const float *qkv, long long plane, int 
                          const float *bias, float *out, long long oplane, int opitch, int Cp)
 {
     const int d = C / heads;
-    const dim3 grid((hp / SW_WIN) * (wp / SW_WIN), heads), block(SW_TOK);
-    if (d <= 8) hipLaunchKernelGGL(k_sw_attention<8>, grid, block, 0, st, qkv, plane, pitch, hp, wp, C, d, shift, bias, out, oplane, opitch, Cp);
-    else if (d <= 16) hipLaunchKernelGGL(k_sw_attention<16>, grid, block, 0, st, qkv, plane, pitch, hp, wp, C, d, shift, bias, out, oplane, opitch, Cp);
-    else if (d <= 24) hipLaunchKernelGGL(k_sw_attention<24>, grid, block, 0, st, qkv, plane, pitch, hp, wp, C, d, shift, bias, out, oplane, opitch, Cp);
-    else hipLaunchKernelGGL(k_sw_attention<32>, grid, block, 0, st, qkv, plane, pitch, hp, wp, C, d, shift, bias, out, oplane, opitch, Cp);
-}
-
-// The bias table [225][heads] gathered to [head][key j][query i].
-std::vector<float> sw_gather_bias(const float *table, int heads)
-{
-    std::vector<int> rel(SW_TOK * SW_TOK);
-    sw_rel_index(rel.data());
-    std::vector<float> g((size_t)heads * SW_TOK * SW_TOK);
-    for (int hd = 0; hd < heads; ++hd)
-        for (int j = 0; j < SW_TOK; ++j)
-            for (int i = 0; i < SW_TOK; ++i) g[((size_t)hd * SW_TOK + j) * SW_TOK + i] = table[(size_t)rel[i * SW_TOK + j] * heads + hd];
-    return g;
+    sw_launch_by_d(d, k_sw_attention<8>, k_sw_attention<16>, k_sw_attention<24>, k_sw_attention<32>, dim3((hp / SW_WIN) * (wp / SW_WIN), heads),
+                   dim3(SW_TOK), st, qkv, plane, pitch, hp, wp, C, d, shift, bias, out, oplane, opitch, Cp);
 }
 
 }  // namespace
 
-struct sr_swinir_model : SrModelBase {         // d_w, d_b: per table (sw_tables)
+struct sr_swinir_model : SwModelBase {
     sr_swinir_desc d{};
-    std::vector<SwTable> tables;
-    DevBuf trunk[4];                          // H, R, X, A
-    DevBuf qbuf;                              // qkv / hidden
-    DevBuf tailbuf[2];
-    DevBuf img;                               // the reflected u8 image
-    void release_device()
-    {
-        for (auto &b : trunk) b.release();
-        for (DevBuf *b : {&tailbuf[0], &tailbuf[1], &qbuf, &img}) b->release();
-        release_base();
-    }
+    static constexpr bool SHUFFLE_ONLY = false;
+    static int check_desc(const char *who, const sr_swinir_desc *desc) { return sw_check_desc(who, desc); }
+    static std::vector<SwTable> table_list(const sr_swinir_desc &desc) { return sw_tables(desc); }
+    static bool bias_table(int kind) { return kind == SW_T_RPB; }
+    int geometry(const char *who, int h, int w, int tail, SwGeom &g) const { return sw_geometry(who, d, h, w, tail, g); }
+    std::vector<SwStep> tail_steps() const { return sw_tail_steps(d); }
 };
 
 static LiveSet g_sw_live;
 
-static int sw_reserve(sr_swinir_model *m, const SwGeom &g, const char *who)
-{
-    sr_ctx *ctx = m->ctx;
-    int rc;
-    if ((rc = ensure_activation_buffers(ctx, m->trunk, 4, (size_t)g.plane0 * g.cp, who))) return rc;
-    if ((rc = ensure_activation_buffers(ctx, &m->qbuf, 1, (size_t)g.plane0 * g.qp, who))) return rc;
-    if (g.plane_t && (rc = ensure_activation_buffers(ctx, m->tailbuf, 2, (size_t)g.plane_t * SW_MID, who))) return rc;
-    SRCHK(m->img.reserve(ctx, who, (size_t)g.plane0 * 3));
-    return SR_OK;
-}
-
 static int sw_forward(sr_swinir_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride, int tail,
                       bool u8, const char *who)
 {
-    if (!g_sw_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
-    sr_ctx *ctx = m->ctx;
-    CTX_ENTER(ctx);
-    const sr_swinir_desc &D = m->d;
-    const int C = D.n_feat, heads = D.n_heads, S = D.scale;
-    int rc = check_sr_forward_args(who, d_src, src_stride, w, d_dst, dst_stride, S, u8);
-    if (rc) return rc;
-    SwGeom g;
-    if ((rc = sw_geometry(who, D, h, w, tail, g))) return rc;
-    if ((rc = sw_reserve(m, g, who))) return rc;
-    const int hp = g.hp, wp = g.wp, Cp = g.cp, hidp = sw_pad64(D.n_hidden), qkvp = sw_pad64(3 * C);
-    hipStream_t st = ctx->stream;
-    SwEpi ep{};
-    ep.af = {{D.mean[0], D.mean[1], D.mean[2]}, D.range};
-    ep.dst = d_dst;
-    ep.dst_stride = (long long)dst_stride;
-    ep.s = 1;
-    ep.nq = C;
-    ep.qscale = 1.0f / sqrtf((float)(C / heads));
-    // ---- trunk phase: the whole padded image, every tensor in one layout ----
-    const PlanarTen L = planar_tensor(nullptr, 0, 0, hp, wp);
-    auto ten = [&](float *base) { PlanarTen t = L; t.p = base; return t; };
-    ep.skip_plane = L.plane;
-    ep.skip_pitch = L.pitch;
-    float *Hb = m->trunk[0].as<float>(), *Rb = m->trunk[1].as<float>(), *Xb = m->trunk[2].as<float>(), *Ab = m->trunk[3].as<float>();
-    float *Qb = m->qbuf.as<float>();
-    unsigned char *img = m->img.as<unsigned char>();
-    auto lin = [&](auto kernel, float *in, int cin, int k, int cout_planes, float *out, const float *skip) {
-        ProfScope ps(ctx, "swinir_linear");
-        SwEpi e = ep;
-        e.skip = skip;
-        launch_conv(kernel, st, ten(in), hp, wp, cin, cout_planes / 64, m->w(k), m->b(k), out, L.plane, L.pitch, 0, 0, hp, wp, e);
-    };
-    auto conv = [&](float *in, int k, float *out, const float *skip) {
-        ProfScope ps(ctx, "swinir_conv");
-        SwEpi e = ep;
-        e.skip = skip;
-        launch_conv(k_sw_conv<2, SW_ADD>, st, ten(in), hp, wp, Cp, Cp / 64, m->w(k), m->b(k), out, L.plane, L.pitch, 0, 0, hp, wp, e);
-    };
-    auto norm = [&](float *in, int k, float *out) {
-        ProfScope ps(ctx, "swinir_ln");
-        sw_launch_layernorm(st, in, L.plane, L.pitch, hp, wp, C, Cp, m->w(k), m->b(k), out, L.plane, L.pitch);
-    };
-    {
-        ProfScope ps(ctx, "swinir_head");
-        const long long n = (long long)g.plane0 * 3;
-        hipLaunchKernelGGL(k_sw_reflect, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_src, (long long)src_stride, h, w, img, hp, wp);
-        hipLaunchKernelGGL(k_sw_head, dim3((wp + 63) / 64, (hp + 3) / 4, Cp / 64), dim3(64, 4), 0, st, img, (long long)wp * 3, hp, wp, m->w(0), m->b(0),
-                           ep.af, Hb, hp, wp, L.pitch, L.plane);
-    }
-    int k = 1;
-    norm(Hb, k++, Rb);
-    for (int gi = 0; gi < D.n_groups; ++gi) {
-        float *x = Rb;                                     // the first layer reads the RSTB's input and writes X
-        for (int j = 0; j < D.depth; ++j, k += 7) {
-            norm(x, k, Ab);
-            lin(k_sw_lin<SL_QKV>, Ab, Cp, k + 1, qkvp, Qb, nullptr);
+    static const SwNames names{"swinir_head", "swinir_ln", "swinir_linear", "swinir_conv", "swinir_tail"};
+    return sw_forward_frame(__func__, g_sw_live, m, names, k_sw_reflect, d_src, src_stride, h, w, d_dst, dst_stride, tail, u8, who,
+                            [m](const SwTrunk &T, const SwGeom &, int &k) {       // one RSTB: D Swin layers, 7 tables each
+        float *x = T.Rb;                                   // the first layer reads the RSTB's input and writes X
+        for (int j = 0; j < m->d.depth; ++j, k += 7) {
+            T.norm(x, k, T.Ab);
+            T.qkv(k + 1);
             {
-                ProfScope ps(ctx, "swinir_attention");
-                sw_launch_attention(st, Qb, L.plane, L.pitch, hp, wp, C, heads, j % 2 ? SW_SHIFT : 0, m->w(k + 2), Ab, L.plane, L.pitch, Cp);
+                ProfScope ps(T.ctx, "swinir_attention");
+                sw_launch_attention(T.st, T.Qb, T.L.plane, T.L.pitch, T.hp, T.wp, T.C, m->d.n_heads, j % 2 ? SW_SHIFT : 0, m->w(k + 2), T.Ab,
+                                    T.L.plane, T.L.pitch, T.Cp);
             }
-            lin(k_sw_lin<SL_ADD>, Ab, Cp, k + 3, Cp, Xb, x);
-            x = Xb;
-            norm(x, k + 4, Ab);
-            lin(k_sw_lin<SL_GELU>, Ab, Cp, k + 5, hidp, Qb, nullptr);
-            lin(k_sw_lin<SL_ADD>, Qb, hidp, k + 6, Cp, Xb, Xb);
+            T.proj(k + 3, x);
+            x = T.Xb;
+            T.mlp(k + 4);
         }
-        conv(x, k++, Rb, Rb);                              // in place over the RSTB's input
-    }
-    norm(Rb, k++, Ab);
-    conv(Ab, k++, Hb, Hb);                                 // f = conv_after_body(.) + h, in place over h
-    if ((rc = check_launch(who))) return rc;
-    // ---- tail phase: sub-pieces of the input over their own backward extents ----
-    const std::vector<SwStep> steps = sw_tail_steps(D);
-    const int n = (int)steps.size();
-    const PlanarTen f = ten(Hb);
-    std::vector<int> ya, yb, xa, xb;
-    for (int sy = 0; sy < h; sy = (int)std::min<long long>((long long)sy + g.tail, h))
-        for (int sx = 0; sx < w; sx = (int)std::min<long long>((long long)sx + g.tail, w)) {
-            sw_backward_extents(steps.data(), n, S, sy, (int)std::min<long long>((long long)sy + g.tail, h), hp, ya, yb);
-            sw_backward_extents(steps.data(), n, S, sx, (int)std::min<long long>((long long)sx + g.tail, w), wp, xa, xb);
-            PlanarTen t = f;
-            ProfScope ps(ctx, "swinir_tail");
-            for (int i = 0; i < n; ++i) {
-                const int rows = yb[i] - ya[i], cols = xb[i] - xa[i], mult = steps[i].mult, r = steps[i].r, kt = k + i;
-                const int kind = m->tables[kt].kind, cin = i == 0 ? Cp : SW_MID;
-                SwEpi e = ep;
-                e.slope = kind == SW_T_CBU ? 0.01f : 0.2f;
-                e.s = r;
-                if (i + 1 < n) {
-                    const PlanarTen o = planar_tensor(m->tailbuf[i & 1].as<float>(), ya[i] * r, xa[i] * r, rows * r, cols * r);
-                    auto go = [&](auto kernel, int tiles) {
-                        launch_conv(kernel, st, t, hp * mult, wp * mult, cin, tiles, m->w(kt), m->b(kt), o.p, o.plane, o.pitch, ya[i], xa[i], rows, cols, e);
-                    };
-                    if (kind == SW_T_UP && r == 2) go(k_sw_conv<2, SW_SHUF2>, 4);
-                    else if (kind == SW_T_UP) go(k_sw_conv<2, SW_SHUF3>, 9);
-                    else if (r == 2) go(k_sw_conv<2, SW_REP_ACT>, 1);
-                    else go(k_sw_conv<2, SW_ACT>, 1);
-                    t = o;
-                } else {
-                    auto go = [&](auto kernel) {
-                        launch_conv(kernel, st, t, hp * mult, wp * mult, cin, 1, m->w(kt), m->b(kt), nullptr, 0LL, 0, ya[i], xa[i], rows, cols, e);
-                    };
-                    const bool wide = 3 * r * r > 32;
-                    if (u8) wide ? go(k_sw_conv<2, SW_LAST_U8>) : go(k_sw_conv<1, SW_LAST_U8>);
-                    else wide ? go(k_sw_conv<2, SW_LAST_F32>) : go(k_sw_conv<1, SW_LAST_F32>);
-                }
-            }
-            if ((rc = check_launch(who))) return rc;
-        }
-    return SR_OK;
-}
-
-// The self-ensemble over sw_forward (driver: sr_ensemble.hip): every member is padded and windowed on its own.
-static int sw_ensemble(sr_swinir_model *m, const uint8_t *d_src, int64_t src_stride, int h, int w, void *d_dst, int64_t dst_stride, int tail,
-                       int mask, bool u8, const char *who)
-{
-    const int rc = sr_ens_check_mask(who, mask);
-    if (rc) return rc;
-    if (tail < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: %s must be >= 1, or 0 for the library's choice", who, "tail");
-    if (!g_sw_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
-    return ens_run(who, *m, m->d.scale, [&](const uint8_t *s, int64_t ss, int hh, int ww, float *d, int64_t ds) {
-        return sw_forward(m, s, ss, hh, ww, d, ds, tail, false, who);
-    }, d_src, src_stride, h, w, d_dst, dst_stride, mask, u8);
+        return x;
+    });
 }
 
 extern "C" {
@@ -360,67 +224,14 @@ extern "C" {
 int sr_swinir_create(sr_ctx *ctx, const sr_swinir_desc *desc, const float *const *h_w, const float *const *h_b, int n_tables,
                      sr_swinir_model **out)
 {
-    const char *who = "sr_swinir_create";
-    if (!out) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null out", who);
-    *out = nullptr;
-    int rc = sw_check_desc(who, desc);                                      // host decision, before any device call
-    if (rc) return rc;
-    const std::vector<SwTable> tables = sw_tables(*desc);
-    if (!h_w || !h_b) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null weight table", who);
-    if (n_tables != (int)tables.size())
-        return sr_set_error(SR_ERR_INVALID_ARG, "%s: this description has %d tables, %d given", who, (int)tables.size(), n_tables);
-    for (int k = 0; k < n_tables; ++k)
-        if (!h_w[k] || (!h_b[k] && tables[k].kind != SW_T_RPB)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null array of table %d", who, k);
-    CTX_ENTER(ctx);
-    sr_swinir_model *M = new sr_swinir_model();
-    M->ctx = ctx;
-    M->d = *desc;
-    M->tables = tables;
-    g_sw_live.insert(M);
-    const int C = desc->n_feat, Cp = sw_pad64(C), hidp = sw_pad64(desc->n_hidden);
-    for (int k = 0; k < n_tables; ++k) {
-        const SwTable &t = tables[k];
-        MfmaWeights a;
-        switch (t.kind) {
-        case SW_T_HEAD: {
-            std::vector<float> wpad((size_t)Cp * 27, 0.0f);
-            std::memcpy(wpad.data(), h_w[k], (size_t)C * 27 * sizeof(float));
-            a.w = arrange_head_weights(wpad.data(), Cp);
-            a.b.assign(Cp, 0.0f);
-            std::memcpy(a.b.data(), h_b[k], (size_t)C * sizeof(float));
-            break;
-        }
-        case SW_T_LN:
-            a = {std::vector<float>(h_w[k], h_w[k] + C), std::vector<float>(h_b[k], h_b[k] + C)};
-            break;
-        case SW_T_RPB:
-            a = {sw_gather_bias(h_w[k], desc->n_heads), std::vector<float>(1, 0.0f)};
-            break;
-        case SW_T_QKV: case SW_T_PROJ: case SW_T_FC1:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 1, Cp, SW_LIN_CC, 64);
-            break;
-        case SW_T_FC2:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 1, hidp, SW_LIN_CC, 64);
-            break;
-        case SW_T_CONV: case SW_T_CBU:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 9, Cp, 8, 64);
-            break;
-        case SW_T_UPD:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 9, Cp, 8, t.cout > 32 ? 64 : 32);
-            break;
-        case SW_T_LAST:
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 9, SW_MID, 8, 32);
-            break;
-        default:                                                            // SW_T_UP, SW_T_C64
-            a = sw_arrange(h_w[k], h_b[k], t.cout, t.cin, 9, SW_MID, 8, 64);
-        }
-        if ((rc = upload_conv(who, *M, a))) {
-            sr_swinir_destroy(M);
-            return rc;
-        }
-    }
-    *out = M;
-    return SR_OK;
+    return sw_create("sr_swinir_create", ctx, desc, h_w, h_b, n_tables, g_sw_live, out, [] { return SR_OK; },
+                     [&](const SwTable &t, const float *w, const float *b, MfmaWeights &a) {
+        if (t.kind == SW_T_RPB) a = {sw_gather_window_bias(w, SW_WIN, desc->n_heads), std::vector<float>(1, 0.0f)};
+        else if (t.kind == SW_T_UPD) a = sw_arrange(w, b, t.cout, t.cin, 9, sw_pad64(desc->n_feat), 8, t.cout > 32 ? 64 : 32);
+        else if (t.kind == SW_T_C64) a = sw_arrange(w, b, t.cout, t.cin, 9, SW_MID, 8, 64);
+        else return false;
+        return true;
+    });
 }
 
 int sr_swinir_destroy(sr_swinir_model *m)
@@ -441,28 +252,18 @@ int sr_swinir_f32(sr_swinir_model *model, const uint8_t *d_src, int64_t src_stri
 int sr_swinir_ens_u8(sr_swinir_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst, int64_t dst_stride,
                      int tail, int mask)
 {
-    return sw_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tail, mask, true, "sr_swinir_ens_u8");
+    return sw_ensemble(g_sw_live, model, sw_forward, d_src, src_stride, h, w, d_dst, dst_stride, tail, mask, true, "sr_swinir_ens_u8");
 }
 
 int sr_swinir_ens_f32(sr_swinir_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst, int64_t dst_stride,
                       int tail, int mask)
 {
-    return sw_ensemble(model, d_src, src_stride, h, w, d_dst, dst_stride, tail, mask, false, "sr_swinir_ens_f32");
+    return sw_ensemble(g_sw_live, model, sw_forward, d_src, src_stride, h, w, d_dst, dst_stride, tail, mask, false, "sr_swinir_ens_f32");
 }
 
 int sr_swinir_fill_workspace(sr_swinir_model *m, int h, int w, int tail, int byte)
 {
-    const char *who = "sr_swinir_fill_workspace";
-    if (!g_sw_live.contains(m)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null or destroyed model", who);
-    sr_ctx *ctx = m->ctx;
-    CTX_ENTER(ctx);
-    SwGeom g;
-    int rc = sw_geometry(who, m->d, h, w, tail, g);
-    if (rc) return rc;
-    if ((rc = sw_reserve(m, g, who))) return rc;
-    for (DevBuf *b : {&m->trunk[0], &m->trunk[1], &m->trunk[2], &m->trunk[3], &m->qbuf, &m->tailbuf[0], &m->tailbuf[1], &m->img})
-        if (b->d) HIPCHK(hipMemsetAsync(b->d, byte, b->cap, ctx->stream));
-    return SR_OK;
+    return sw_fill_workspace("sr_swinir_fill_workspace", g_sw_live, m, h, w, tail, byte);
 }
 
 int sr_swinir_layernorm_f32(sr_ctx *ctx, const float *d_x, int64_t plane_stride, int64_t row_stride, int n_feat, int h, int w,
@@ -492,26 +293,15 @@ int sr_swinir_attention_f32(sr_ctx *ctx, const float *d_qkv, int64_t plane_strid
                             int shift, const float *h_table, float *d_out, int64_t out_plane_stride, int64_t out_row_stride)
 {
     const char *who = "sr_swinir_attention_f32";
-    if (!d_qkv || !h_table || !d_out) return sr_set_error(SR_ERR_INVALID_ARG, "%s: null argument", who);
-    const int C = n_feat;
-    if (C < 1 || C > 256 || n_heads < 1 || C % n_heads || C / n_heads > 32)
-        return sr_set_error(SR_ERR_UNSUPPORTED, "%s: %d channels in %d heads is outside C <= 256, heads of at most 32 channels", who, C, n_heads);
-    if (shift != 0 && shift != SW_SHIFT) return sr_set_error(SR_ERR_UNSUPPORTED, "%s: shift %d (supported: 0, %d)", who, shift, SW_SHIFT);
-    if (hp < SW_WIN || wp < SW_WIN || hp % SW_WIN || wp % SW_WIN)
-        return sr_set_error(SR_ERR_SHAPE, "%s: a %dx%d tensor is not made of %d x %d windows", who, wp, hp, SW_WIN, SW_WIN);
     int rc;
-    if ((rc = sw_check_view(who, d_qkv, plane_stride, row_stride, hp, wp))) return rc;
-    if ((rc = sw_check_view(who, d_out, out_plane_stride, out_row_stride, hp, wp))) return rc;
-    CTX_ENTER(ctx);
-    const std::vector<float> g = sw_gather_bias(h_table, n_heads);
-    DevTemp tmp(ctx);
-    SRCHK(tmp.alloc(who, g.size() * sizeof(float)));
-    HIPCHK(hipMemcpyAsync(tmp.d, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    sw_launch_attention(ctx->stream, d_qkv, plane_stride / 4, (int)(row_stride / 4), hp, wp, C, n_heads, shift, tmp.as<float>(), d_out,
-                        out_plane_stride / 4, (int)(out_row_stride / 4), C);
-    SRCHK(check_launch(who));
-    HIPCHK(stream_sync(ctx));
-    return SR_OK;
+    if ((rc = sw_check_attention_args(who, d_qkv, h_table, d_out, n_feat, n_heads))) return rc;
+    if (shift != 0 && shift != SW_SHIFT) return sr_set_error(SR_ERR_UNSUPPORTED, "%s: shift %d (supported: 0, %d)", who, shift, SW_SHIFT);
+    if ((rc = sw_check_windows(who, hp, wp, SW_WIN))) return rc;
+    return sw_run_attention(who, ctx, d_qkv, plane_stride, row_stride, n_heads, hp, wp, h_table, SW_TOK, SW_TOK, d_out, out_plane_stride,
+                            out_row_stride, [](int *idx) { sw_rel_index(SW_WIN, idx); return SR_OK; },
+                            [&](hipStream_t st, const float *qkv, long long plane, int pitch, const float *bias, float *out, long long oplane, int opitch) {
+        sw_launch_attention(st, qkv, plane, pitch, hp, wp, n_feat, n_heads, shift, bias, out, oplane, opitch, n_feat);
+    });
 }
 
 }  // extern "C"

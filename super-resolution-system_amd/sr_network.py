@@ -484,7 +484,20 @@ def parse_rcan_state(state: Mapping, res_scale: float = 1.0, img_range: float = 
     return desc, [w for w, _ in tables], [b for _, b in tables]
 
 
-class RCANSRNet(CompactSRNet):
+class _OnePieceSRNet(CompactSRNet):
+    """What RCANSRNet, SwinIRSRNet and HATSRNet share: the trunk is one piece, so there is no ``tile``, only ``tail``.
+    ``_one_piece``: the family's sentence about it, with which a tile is refused."""
+    _one_piece = ""
+
+    def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
+                       ctx: Optional["_native.Context"] = None, ensemble: int = 1, tail: int = 0):
+        if tile:
+            raise ValueError(f"{self._one_piece}: there is no tile, got tile={tile!r}; see tail")
+        # the one argument after the strides of sr_<kind>_* is tail, and CompactSRNet hands its first one on by position
+        super().upscale_device(d_src, shape, d_dst, dst_stride, src_stride, tail, ctx, ensemble)
+
+
+class RCANSRNet(_OnePieceSRNet):
     """RCAN on the GPU, with CompactSRNet's surface (from_file, model, upscale, upscale_device, close).  ``state``: a BasicSR
     state dict (see parse_rcan_state).
 
@@ -492,6 +505,8 @@ class RCANSRNet(CompactSRNet):
     no ``tile`` (anything but 0 is refused), only the ``tail`` of the upsampling phase, which changes no bit.  It also means
     that an image cut into tiles before the network (as the pipeline does with ``block_size``) pools over each tile on its own
     -- as every tiled inference of RCAN does -- so the tile size affects the values, not only the speed."""
+
+    _one_piece = "RCAN's trunk is one piece (the channel mean is global)"
 
     def __init__(self, state: Mapping, res_scale: float = 1.0, img_range: float = EDSR_IMG_RANGE, rgb_mean=EDSR_RGB_MEAN, device: int = 0):
         self.desc, self._w, self._b = parse_rcan_state(state, res_scale, img_range, rgb_mean)
@@ -509,13 +524,6 @@ class RCANSRNet(CompactSRNet):
 
     def _make_model(self, ctx: "_native.Context"):
         return _native.RcanModel(ctx, self.desc, self._w, self._b)
-
-    def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
-                       ctx: Optional["_native.Context"] = None, ensemble: int = 1, tail: int = 0):
-        if tile:
-            raise ValueError(f"RCAN's trunk is one piece (the channel mean is global): there is no tile, got tile={tile!r}; see tail")
-        # the one argument after the strides of sr_rcan_* is tail, and CompactSRNet hands its first one on by position
-        super().upscale_device(d_src, shape, d_dst, dst_stride, src_stride, tail, ctx, ensemble)
 
 
 # ------------------------------------------------------------------------------------------
@@ -547,6 +555,90 @@ def _read_dense(state: Mapping, keys, name: str, w_shape, b_shape, part_w: str =
     return out[0], out[1]
 
 
+class _SwinStateReader:
+    """What parse_swinir_state and parse_hat_state share: the tables read so far in create order, the numbering of the groups
+    and of their blocks, the tables of an attention and of an MLP, and the pixelshuffle reconstruction.  The nouns of a message
+    are the caller's."""
+
+    def __init__(self, state: Mapping):
+        self.state = _unwrap(state)
+        self.keys = {str(k) for k in self.state}
+        self.tables = []
+
+    def refuse_half(self):
+        for k in sorted(self.keys):
+            name = str(getattr(self.state[k], "dtype", ""))
+            if "float16" in name or "bfloat16" in name:
+                raise ValueError(f"{k}: {name} weights are not supported (fp32 only)")
+
+    def conv(self, name: str, cin: int, cout=None):
+        self.tables.append(_read_conv(self.state, self.keys, name, cin, cout, ", expected {}"))
+        return self.tables[-1][0]
+
+    def dense(self, name: str, w_shape, b_shape, part_w: str = "weight"):
+        self.tables.append(_read_dense(self.state, self.keys, name, w_shape, b_shape, part_w))
+
+    def shape_of(self, key: str):
+        if key not in self.keys:
+            raise ValueError(f"{key}: not in the state")
+        return tuple(np.shape(_array(self.state, key)))
+
+    def groups(self, noun: str):
+        groups = sorted({int(m.group(1)) for m in map(_SWINIR_LAYER_KEY.match, self.keys) if m})
+        if not groups or groups != list(range(len(groups))):
+            gap = next(i for i in range(len(groups) + 1) if i not in groups)
+            raise ValueError(f"layers.{gap}.conv.weight: the {noun} must be numbered 0 .. L - 1, got {groups}")
+        return groups
+
+    def blocks(self, g: int, depth, a_group: str, group: str, layers: str):
+        """The block numbers of group g, which has as many as the groups before it (``depth``, None for the first)."""
+        blocks = sorted({int(m.group(2)) for m in map(_SWINIR_BLOCK_KEY.match, self.keys) if m and int(m.group(1)) == g})
+        if not blocks or blocks != list(range(len(blocks))):
+            gap = next(i for i in range(len(blocks) + 1) if i not in blocks)
+            raise ValueError(f"layers.{g}.residual_group.blocks.{gap}.attn.qkv.weight: {a_group} {layers} must be numbered 0 .. D - 1, got {blocks}")
+        if depth is not None and len(blocks) != depth:
+            raise ValueError(f"layers.{g}.residual_group.blocks.{min(len(blocks), depth)}.attn.qkv.weight: every {group} must have the same "
+                             f"depth, {group} 0 has {depth} {layers} and {group} {g} has {len(blocks)}")
+        return blocks
+
+    def attention(self, b: str, attn: str, Cn: int, rows: int, heads: int, only: str):
+        """norm1, qkv, the bias table (``rows`` x heads, else ``only`` is what is supported) and proj of block b."""
+        t = f"{b}.{attn}relative_position_bias_table"
+        if t in self.keys and self.shape_of(t) != (rows, heads):
+            got = self.shape_of(t)
+            what = "every layer must have the same number of heads" if len(got) == 2 and got[0] == rows else only
+            raise ValueError(f"{t}: expected shape {(rows, heads)}, got {got}: {what}")
+        self.dense(f"{b}.norm1", (Cn,), (Cn,))
+        self.dense(f"{b}.{attn}qkv", (3 * Cn, Cn), (3 * Cn,))
+        self.dense(t, (rows, heads), None, "")
+        self.dense(f"{b}.{attn}proj", (Cn, Cn), (Cn,))
+
+    def mlp(self, b: str, Cn: int, hidden: int):
+        self.dense(f"{b}.norm2", (Cn,), (Cn,))
+        self.dense(f"{b}.mlp.fc1", (hidden, Cn), (hidden,))
+        self.dense(f"{b}.mlp.fc2", (Cn, hidden), (Cn,))
+
+    def shuffle_tail(self, Cn: int, not_these: str, none: str) -> int:
+        """conv_before_upsample, the upsampling stages and conv_last -> the scale."""
+        self.conv("conv_before_upsample.0", Cn, 64)
+        ups = [f"upsample.{k}" for k in sorted(int(m.group(1)) for m in map(_UPSAMPLE_KEY.match, self.keys) if m)]
+        scale = 1
+        for name in ups:
+            cout = int(np.shape(_array(self.state, f"{name}.weight"))[0])
+            r = {256: 2, 576: 3}.get(cout)
+            if r is None or (len(ups) >= 2 and r != 2) or len(ups) > 2:
+                raise ValueError(f"{name}.weight gives {cout} channels in {len(ups)} stage(s), expected 64 r^2 = 256 (x2, x4) or 576 (x3){not_these}")
+            scale *= r
+            self.conv(name, 64, cout)
+        if not ups:
+            raise ValueError(f"upsample.0.weight: not in the state ({none})")
+        self.conv("conv_last", 64, 3)
+        return scale
+
+    def arrays(self):
+        return [w for w, _ in self.tables], [b for _, b in self.tables]
+
+
 def parse_swinir_state(state: Mapping, img_range: float = SWINIR_IMG_RANGE, rgb_mean=SWINIR_RGB_MEAN):
     """-> (_native.SwinirDesc, weights, biases) in sr_swinir_create's order (_native.swinir_table_names), contiguous fp32; the
     bias entry of a relative-position table is None.
@@ -559,8 +651,8 @@ def parse_swinir_state(state: Mapping, img_range: float = SWINIR_IMG_RANGE, rgb_
     ignored.  A ValueError names the offending key for a wrong shape and for everything out of scope: resi_connection '3conv',
     the absolute position embedding, a window other than 8, the JPEG / denoising variants (no upsampler), Swin2SR, fp16 / bf16;
     what only the kernels' ranges exclude is a NotImplementedError."""
-    state = _unwrap(state)
-    keys = {str(k) for k in state}
+    rd = _SwinStateReader(state)
+    state, keys, conv, dense = rd.state, rd.keys, rd.conv, rd.dense
     if SWINIR_KEY not in keys:
         raise ValueError(f"{SWINIR_KEY}: not in the state (not a SwinIR)")
     if "absolute_pos_embed" in keys:
@@ -570,63 +662,25 @@ def parse_swinir_state(state: Mapping, img_range: float = SWINIR_IMG_RANGE, rgb_
     for k in sorted(keys):
         if k.endswith((".attn.logit_scale", ".attn.cpb_mlp.0.weight", ".attn.q_bias")):
             raise ValueError(f"{k}: this is a Swin2SR state (SwinV2 attention), not a SwinIR")
-    for k in sorted(keys):
-        a = state[k]
-        name = str(getattr(a, "dtype", ""))
-        if "float16" in name or "bfloat16" in name:
-            raise ValueError(f"{k}: {name} weights are not supported (fp32 only)")
-    tables = []
-
-    def conv(name: str, cin: int, cout=None):
-        tables.append(_read_conv(state, keys, name, cin, cout, ", expected {}"))
-        return tables[-1][0]
-
-    def dense(name: str, w_shape, b_shape, part_w: str = "weight"):
-        tables.append(_read_dense(state, keys, name, w_shape, b_shape, part_w))
-
+    rd.refuse_half()
     Cn = int(conv("conv_first", 3).shape[0])
     dense("patch_embed.norm", (Cn,), (Cn,))
-    groups = sorted({int(m.group(1)) for m in map(_SWINIR_LAYER_KEY.match, keys) if m})
-    if not groups or groups != list(range(len(groups))):
-        gap = next(i for i in range(len(groups) + 1) if i not in groups)
-        raise ValueError(f"layers.{gap}.conv.weight: the RSTBs must be numbered 0 .. L - 1, got {groups}")
+    groups = rd.groups("RSTBs")
     tkey = "layers.0.residual_group.blocks.0.attn.relative_position_bias_table"
-    if tkey not in keys:
-        raise ValueError(f"{tkey}: not in the state")
-    tshape = np.shape(_array(state, tkey))
+    tshape = rd.shape_of(tkey)
     rows = (2 * _native.SWINIR_WINDOW - 1) ** 2
     if len(tshape) != 2 or tshape[0] != rows:
-        raise ValueError(f"{tkey}: shape {tuple(tshape)} is not a window of 8 ({rows} rows): only window_size 8 is supported")
+        raise ValueError(f"{tkey}: shape {tshape} is not a window of 8 ({rows} rows): only window_size 8 is supported")
     heads = int(tshape[1])
-    fkey = "layers.0.residual_group.blocks.0.mlp.fc1.weight"
-    if fkey not in keys:
-        raise ValueError(f"{fkey}: not in the state")
-    hidden = int(np.shape(_array(state, fkey))[0])
+    hidden = int(rd.shape_of("layers.0.residual_group.blocks.0.mlp.fc1.weight")[0])
     depth = None
     for g in groups:
-        blocks = sorted({int(m.group(2)) for m in map(_SWINIR_BLOCK_KEY.match, keys) if m and int(m.group(1)) == g})
-        if not blocks or blocks != list(range(len(blocks))):
-            gap = next(i for i in range(len(blocks) + 1) if i not in blocks)
-            raise ValueError(f"layers.{g}.residual_group.blocks.{gap}.attn.qkv.weight: an RSTB's layers must be numbered 0 .. D - 1, got {blocks}")
-        if depth is None:
-            depth = len(blocks)
-        elif len(blocks) != depth:
-            raise ValueError(f"layers.{g}.residual_group.blocks.{min(len(blocks), depth)}.attn.qkv.weight: every RSTB must have the same "
-                             f"depth, RSTB 0 has {depth} layers and RSTB {g} has {len(blocks)}")
+        blocks = rd.blocks(g, depth, "an RSTB's", "RSTB", "layers")
+        depth = len(blocks)
         for j in blocks:
             b = f"layers.{g}.residual_group.blocks.{j}"
-            t = f"{b}.attn.relative_position_bias_table"
-            if t in keys and np.shape(_array(state, t)) != (rows, heads):
-                got = np.shape(_array(state, t))
-                what = "every layer must have the same number of heads" if len(got) == 2 and got[0] == rows else "only window_size 8 is supported"
-                raise ValueError(f"{t}: expected shape {(rows, heads)}, got {tuple(got)}: {what}")
-            dense(f"{b}.norm1", (Cn,), (Cn,))
-            dense(f"{b}.attn.qkv", (3 * Cn, Cn), (3 * Cn,))
-            dense(t, (rows, heads), None, "")
-            dense(f"{b}.attn.proj", (Cn, Cn), (Cn,))
-            dense(f"{b}.norm2", (Cn,), (Cn,))
-            dense(f"{b}.mlp.fc1", (hidden, Cn), (hidden,))
-            dense(f"{b}.mlp.fc2", (Cn, hidden), (Cn,))
+            rd.attention(b, "attn.", Cn, rows, heads, "only window_size 8 is supported")
+            rd.mlp(b, Cn, hidden)
         conv(f"layers.{g}.conv", Cn, Cn)
     dense("norm", (Cn,), (Cn,))
     conv("conv_after_body", Cn, Cn)
@@ -639,18 +693,7 @@ def parse_swinir_state(state: Mapping, img_range: float = SWINIR_IMG_RANGE, rgb_
         conv("conv_last", 64, 3)
     elif "conv_before_upsample.0.weight" in keys:
         kind = "pixelshuffle"
-        conv("conv_before_upsample.0", Cn, 64)
-        ups = [f"upsample.{k}" for k in sorted(int(m.group(1)) for m in map(_UPSAMPLE_KEY.match, keys) if m)]
-        for name in ups:
-            cout = int(np.shape(_array(state, f"{name}.weight"))[0])
-            r = {256: 2, 576: 3}.get(cout)
-            if r is None or (len(ups) >= 2 and r != 2) or len(ups) > 2:
-                raise ValueError(f"{name}.weight gives {cout} channels in {len(ups)} stage(s), expected 64 r^2 = 256 (x2, x4) or 576 (x3)")
-            scale *= r
-            conv(name, 64, cout)
-        if not ups:
-            raise ValueError("upsample.0.weight: not in the state (pixelshuffle at scale 1 has no upsampling stage and is not supported)")
-        conv("conv_last", 64, 3)
+        scale = rd.shuffle_tail(Cn, "", "pixelshuffle at scale 1 has no upsampling stage and is not supported")
     elif "upsample.0.weight" in keys:
         kind = "pixelshuffledirect"
         cout = int(np.shape(_array(state, "upsample.0.weight"))[0])
@@ -663,10 +706,10 @@ def parse_swinir_state(state: Mapping, img_range: float = SWINIR_IMG_RANGE, rgb_
                          "of SwinIR are not supported")
     desc = _native.swinir_desc(Cn, heads, hidden, len(groups), depth, scale, kind, rgb_mean, float(img_range))
     _native.swinir_plan(desc, 1, 1)                              # NotImplementedError outside the kernels' range (host only)
-    return desc, [w for w, _ in tables], [b for _, b in tables]
+    return (desc,) + rd.arrays()
 
 
-class SwinIRSRNet(CompactSRNet):
+class SwinIRSRNet(_OnePieceSRNet):
     """SwinIR on the GPU, with CompactSRNet's surface (from_file, model, upscale, upscale_device, close).  ``state``: a BasicSR
     state dict (see parse_swinir_state).
 
@@ -674,6 +717,8 @@ class SwinIRSRNet(CompactSRNet):
     ``tile`` (anything but 0 is refused), only the ``tail`` of the reconstruction, which changes no bit.  An image cut into
     tiles before the network (as the pipeline does with ``block_size``) is reflected, padded and windowed tile by tile -- as
     every tiled inference of SwinIR does -- so the tile size affects the values, not only the speed."""
+
+    _one_piece = "SwinIR's trunk is one piece (shifted windows reach across any tile)"
 
     def __init__(self, state: Mapping, img_range: float = SWINIR_IMG_RANGE, rgb_mean=SWINIR_RGB_MEAN, device: int = 0):
         self.desc, self._w, self._b = parse_swinir_state(state, img_range, rgb_mean)
@@ -691,13 +736,6 @@ class SwinIRSRNet(CompactSRNet):
 
     def _make_model(self, ctx: "_native.Context"):
         return _native.SwinirModel(ctx, self.desc, self._w, self._b)
-
-    def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
-                       ctx: Optional["_native.Context"] = None, ensemble: int = 1, tail: int = 0):
-        if tile:
-            raise ValueError(f"SwinIR's trunk is one piece (shifted windows reach across any tile): there is no tile, got tile={tile!r}; see tail")
-        # the one argument after the strides of sr_swinir_* is tail, and CompactSRNet hands its first one on by position
-        super().upscale_device(d_src, shape, d_dst, dst_stride, src_stride, tail, ctx, ensemble)
 
 
 def _swinir_extras(state: Mapping) -> dict:
@@ -734,8 +772,8 @@ def parse_hat_state(state: Mapping, img_range: float = HAT_IMG_RANGE, rgb_mean=H
     buffers are ignored.  A ValueError names the offending key for a wrong shape and for everything out of scope (other
     windows, other overlap ratios, resi_connection 'identity', the absolute position embedding, upsamplers other than
     pixelshuffle, fp16 / bf16); what only the kernels' ranges exclude is a NotImplementedError."""
-    state = _unwrap(state)
-    keys = {str(k) for k in state}
+    rd = _SwinStateReader(state)
+    state, keys, conv, dense, shape_of = rd.state, rd.keys, rd.conv, rd.dense, rd.shape_of
     if HAT_KEY not in keys:
         raise ValueError(f"{HAT_KEY}: not in the state (not a HAT)")
     if "absolute_pos_embed" in keys:
@@ -744,18 +782,7 @@ def parse_hat_state(state: Mapping, img_range: float = HAT_IMG_RANGE, rgb_mean=H
         raise ValueError("layers.0.conv.0.weight: only resi_connection '1conv' is supported")
     if "layers.0.conv.weight" not in keys:
         raise ValueError("layers.0.conv.weight: not in the state (resi_connection 'identity' is not supported, only '1conv')")
-    for k in sorted(keys):
-        name = str(getattr(state[k], "dtype", ""))
-        if "float16" in name or "bfloat16" in name:
-            raise ValueError(f"{k}: {name} weights are not supported (fp32 only)")
-    tables = []
-
-    def conv(name: str, cin: int, cout=None):
-        tables.append(_read_conv(state, keys, name, cin, cout, ", expected {}"))
-        return tables[-1][0]
-
-    def dense(name: str, w_shape, b_shape, part_w: str = "weight"):
-        tables.append(_read_dense(state, keys, name, w_shape, b_shape, part_w))
+    rd.refuse_half()
 
     def pointwise(name: str, cout: int, cin: int):              # a 1 x 1 convolution: (out, in, 1, 1) or (out, in)
         for part in ("weight", "bias"):
@@ -767,19 +794,11 @@ def parse_hat_state(state: Mapping, img_range: float = HAT_IMG_RANGE, rgb_mean=H
             raise ValueError(f"{name}.weight: expected shape {(cout, cin, 1, 1)}, got {w.shape}")
         if b.shape != (cout,):
             raise ValueError(f"{name}.bias: expected {cout} values, got {b.shape}")
-        tables.append((w.reshape(cout, cin), b))
-
-    def shape_of(key: str):
-        if key not in keys:
-            raise ValueError(f"{key}: not in the state")
-        return tuple(np.shape(_array(state, key)))
+        rd.tables.append((w.reshape(cout, cin), b))
 
     Cn = int(conv("conv_first", 3).shape[0])
     dense("patch_embed.norm", (Cn,), (Cn,))
-    groups = sorted({int(m.group(1)) for m in map(_SWINIR_LAYER_KEY.match, keys) if m})
-    if not groups or groups != list(range(len(groups))):
-        gap = next(i for i in range(len(groups) + 1) if i not in groups)
-        raise ValueError(f"layers.{gap}.conv.weight: the groups must be numbered 0 .. L - 1, got {groups}")
+    groups = rd.groups("groups")
     rows, orows = _native.HAT_REL_ROWS, _native.HAT_OCA_ROWS
     tkey = "layers.0.residual_group.blocks.0.attn.relative_position_bias_table"
     tshape = shape_of(tkey)
@@ -809,46 +828,19 @@ def parse_hat_state(state: Mapping, img_range: float = HAT_IMG_RANGE, rgb_mean=H
             rpi_oca, first = got, ikey
     depth = None
     for g in groups:
-        blocks = sorted({int(m.group(2)) for m in map(_SWINIR_BLOCK_KEY.match, keys) if m and int(m.group(1)) == g})
-        if not blocks or blocks != list(range(len(blocks))):
-            gap = next(i for i in range(len(blocks) + 1) if i not in blocks)
-            raise ValueError(f"layers.{g}.residual_group.blocks.{gap}.attn.qkv.weight: a group's HABs must be numbered 0 .. D - 1, got {blocks}")
-        if depth is None:
-            depth = len(blocks)
-        elif len(blocks) != depth:
-            raise ValueError(f"layers.{g}.residual_group.blocks.{min(len(blocks), depth)}.attn.qkv.weight: every group must have the same "
-                             f"depth, group 0 has {depth} HABs and group {g} has {len(blocks)}")
+        blocks = rd.blocks(g, depth, "a group's", "group", "HABs")
+        depth = len(blocks)
         for j in blocks:
             b = f"layers.{g}.residual_group.blocks.{j}"
-            t = f"{b}.attn.relative_position_bias_table"
-            if t in keys and shape_of(t) != (rows, heads):
-                got = shape_of(t)
-                what = "every layer must have the same number of heads" if len(got) == 2 and got[0] == rows else "only window_size 16 is supported"
-                raise ValueError(f"{t}: expected shape {(rows, heads)}, got {got}: {what}")
-            dense(f"{b}.norm1", (Cn,), (Cn,))
-            dense(f"{b}.attn.qkv", (3 * Cn, Cn), (3 * Cn,))
-            dense(t, (rows, heads), None, "")
-            dense(f"{b}.attn.proj", (Cn, Cn), (Cn,))
+            rd.attention(b, "attn.", Cn, rows, heads, "only window_size 16 is supported")
             conv(f"{b}.conv_block.cab.0", Cn, mid)
             conv(f"{b}.conv_block.cab.2", mid, Cn)
             pointwise(f"{b}.conv_block.cab.3.attention.1", squeeze, Cn)
             pointwise(f"{b}.conv_block.cab.3.attention.3", Cn, squeeze)
-            dense(f"{b}.norm2", (Cn,), (Cn,))
-            dense(f"{b}.mlp.fc1", (hidden, Cn), (hidden,))
-            dense(f"{b}.mlp.fc2", (Cn, hidden), (Cn,))
+            rd.mlp(b, Cn, hidden)
         o = f"layers.{g}.residual_group.overlap_attn"
-        t = f"{o}.relative_position_bias_table"
-        if t in keys and shape_of(t) != (orows, heads):
-            got = shape_of(t)
-            what = "every layer must have the same number of heads" if len(got) == 2 and got[0] == orows else "only overlap_ratio 0.5 of window 16 is supported"
-            raise ValueError(f"{t}: expected shape {(orows, heads)}, got {got}: {what}")
-        dense(f"{o}.norm1", (Cn,), (Cn,))
-        dense(f"{o}.qkv", (3 * Cn, Cn), (3 * Cn,))
-        dense(t, (orows, heads), None, "")
-        dense(f"{o}.proj", (Cn, Cn), (Cn,))
-        dense(f"{o}.norm2", (Cn,), (Cn,))
-        dense(f"{o}.mlp.fc1", (hidden, Cn), (hidden,))
-        dense(f"{o}.mlp.fc2", (Cn, hidden), (Cn,))
+        rd.attention(o, "", Cn, orows, heads, "only overlap_ratio 0.5 of window 16 is supported")
+        rd.mlp(o, Cn, hidden)
         conv(f"layers.{g}.conv", Cn, Cn)
     dense("norm", (Cn,), (Cn,))
     conv("conv_after_body", Cn, Cn)
@@ -856,30 +848,19 @@ def parse_hat_state(state: Mapping, img_range: float = HAT_IMG_RANGE, rgb_mean=H
         raise ValueError("conv_up1.weight: upsampler nearest+conv is not supported (only pixelshuffle)")
     if "conv_before_upsample.0.weight" not in keys:
         raise ValueError("conv_before_upsample.0.weight: not in the state (only upsampler pixelshuffle is supported)")
-    conv("conv_before_upsample.0", Cn, 64)
-    ups = [f"upsample.{k}" for k in sorted(int(m.group(1)) for m in map(_UPSAMPLE_KEY.match, keys) if m)]
-    scale = 1
-    for name in ups:
-        cout = int(np.shape(_array(state, f"{name}.weight"))[0])
-        r = {256: 2, 576: 3}.get(cout)
-        if r is None or (len(ups) >= 2 and r != 2) or len(ups) > 2:
-            raise ValueError(f"{name}.weight gives {cout} channels in {len(ups)} stage(s), expected 64 r^2 = 256 (x2, x4) or 576 (x3): x1 and x8 "
-                             "are not supported")
-        scale *= r
-        conv(name, 64, cout)
-    if not ups:
-        raise ValueError("upsample.0.weight: not in the state (scale 1 is not supported)")
-    conv("conv_last", 64, 3)
+    scale = rd.shuffle_tail(Cn, ": x1 and x8 are not supported", "scale 1 is not supported")
     desc = _native.hat_desc(Cn, heads, hidden, mid, squeeze, len(groups), depth, scale, float(conv_scale), rgb_mean, float(img_range))
     _native.hat_plan(desc, 1, 1)                                 # NotImplementedError outside the kernels' range (host only)
-    return desc, [w for w, _ in tables], [b for _, b in tables], rpi_oca
+    return (desc,) + rd.arrays() + (rpi_oca,)
 
 
-class HATSRNet(CompactSRNet):
+class HATSRNet(_OnePieceSRNet):
     """HAT on the GPU, with CompactSRNet's surface (from_file, model, upscale, upscale_device, close).  ``state``: a HAT state
     dict (see parse_hat_state).  As SwinIRSRNet there is no ``tile`` (anything but 0 is refused), only the ``tail`` of the
     reconstruction, which changes no bit; an image cut into tiles before the network is reflected, padded, windowed -- and its
     CAB means pooled -- tile by tile."""
+
+    _one_piece = "HAT's trunk is one piece (windows, overlaps and the CAB's mean reach across any tile)"
 
     def __init__(self, state: Mapping, img_range: float = HAT_IMG_RANGE, rgb_mean=HAT_RGB_MEAN, conv_scale: float = HAT_CONV_SCALE,
                  device: int = 0):
@@ -898,13 +879,6 @@ class HATSRNet(CompactSRNet):
 
     def _make_model(self, ctx: "_native.Context"):
         return _native.HatModel(ctx, self.desc, self._w, self._b, self._rpi)
-
-    def upscale_device(self, d_src: int, shape, d_dst: int, dst_stride: int, src_stride: Optional[int] = None, tile: int = 0,
-                       ctx: Optional["_native.Context"] = None, ensemble: int = 1, tail: int = 0):
-        if tile:
-            raise ValueError(f"HAT's trunk is one piece (windows, overlaps and the CAB's mean reach across any tile): there is no tile, got tile={tile!r}; see tail")
-        # the one argument after the strides of sr_hat_* is tail, and CompactSRNet hands its first one on by position
-        super().upscale_device(d_src, shape, d_dst, dst_stride, src_stride, tail, ctx, ensemble)
 
 
 def _hat_extras(state: Mapping) -> dict:
