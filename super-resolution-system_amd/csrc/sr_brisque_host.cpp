@@ -1,12 +1,12 @@
 // sr_brisque_host.cpp -- the host side of BRISQUE: the plan, the GGD / AGGD features of the two scale records, the feature
 // scaler and the RBF epsilon-SVR.  Pure host code: no device call, no context -- sr_brisque.hip plans with bq_plan;
 // tools/sanitize/brisque_driver.cpp runs this file under the sanitizers.  The definition is in include/sr_hip.h; the
-// Gamma-ratio table and its argmin are NIQE's (sr_niqe.h).
+// crop refusals, the Gamma-ratio table with its argmin and the AGGD fit are sr_mscn.h's, shared with NIQE.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
-#include "sr_niqe.h"
+#include "sr_mscn.h"
 
 namespace {
 
@@ -35,20 +35,14 @@ void ggd_fit(const sr_niqe_moments &m, double n, double *o)
     o[1] = s2;
 }
 
-// a shift: [alpha, mean, ls^2, rs^2]; R as in NIQE's fit
+// a shift: [alpha, mean, ls^2, rs^2] from sr_mscn.h's fit (shared with NIQE)
 void aggd_fit(const sr_niqe_moments &m, double n, double *o)
 {
     const double nan = std::nan("");
     o[0] = o[1] = o[2] = o[3] = nan;
-    if (m.n_neg == 0 || m.n_pos == 0) return;
-    const double ls = std::sqrt(m.ssq_neg / (double)m.n_neg), rs = std::sqrt(m.ssq_pos / (double)m.n_pos);
-    const double g = ls / rs;
-    const double ma = m.sabs / n;
-    const double rhat = ma * ma / ((m.ssq_neg + m.ssq_pos) / n);
-    const double g2 = g * g;
-    const double R = rhat * (g2 * g + 1.0) * (g + 1.0) / ((g2 + 1.0) * (g2 + 1.0));
-    if (!(R == R)) return;
-    const double alpha = nq_gam_at(nq_gam_argmin(R));
+    const MscnAggd a = mscn_aggd(m, n);
+    if (!(a.alpha == a.alpha)) return;
+    const double alpha = a.alpha, ls = a.ls, rs = a.rs;
     const double G1 = std::tgamma(1.0 / alpha), G2 = std::tgamma(2.0 / alpha), G3 = std::tgamma(3.0 / alpha);
     o[0] = alpha;
     o[1] = (rs - ls) * (G2 / G1) * (std::sqrt(G1) / std::sqrt(G3));
@@ -60,13 +54,9 @@ void aggd_fit(const sr_niqe_moments &m, double n, double *o)
 
 int bq_plan(const char *scope, int h, int w, int cn, int crop_border, BqPlan *p)
 {
-    if (cn != 1 && cn != 3) return sr_set_error(SR_ERR_INVALID_ARG, "%s: need 1 or 3 channels (got %d)", scope, cn);
-    if (crop_border < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: crop_border must be >= 0 (got %d)", scope, crop_border);
-    if (h < 1 || w < 1) return sr_set_error(SR_ERR_INVALID_ARG, "%s: need h, w >= 1", scope);
-    const long long ch = (long long)h - 2LL * crop_border, cw = (long long)w - 2LL * crop_border;
-    if (ch < BQ_MIN || cw < BQ_MIN)
-        return sr_set_error(SR_ERR_SHAPE, "%s: image %dx%d with crop_border %d leaves %lldx%lld: both sides must be at least %d "
-                            "after the crop", scope, w, h, crop_border, std::max(cw, 0LL), std::max(ch, 0LL), BQ_MIN);
+    long long ch, cw;
+    const int rc = mscn_crop(scope, h, w, cn, crop_border, BQ_MIN, &ch, &cw);
+    if (rc) return rc;
     memset(p, 0, sizeof(*p));
     p->H = (int)ch;
     p->W = (int)cw;

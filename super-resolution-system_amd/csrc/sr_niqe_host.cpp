@@ -7,33 +7,24 @@
 #include <cstring>
 #include <vector>
 
-#include "sr_niqe.h"
+#include "sr_mscn.h"
 
 namespace {
 
 constexpr int F = NQ_FEAT;
 constexpr int MIN_FIT_ROWS = F + 1;         // a sample covariance of 36 features has full rank from 37 rows on
 
-// the Gamma-ratio table and its argmin are sr_niqe.h's (BRISQUE's fits read the same table)
-
 struct Aggd {
     double alpha, beta_l, beta_r;
 };
 
+// sr_mscn.h's fit (shared with BRISQUE) with NIQE's scales: beta = the side's root mean square * sqrt(G1 / G3)
 Aggd aggd_fit(const sr_niqe_moments &m, double n)
 {
-    const double nan = std::nan("");
-    if (m.n_neg == 0 || m.n_pos == 0) return {nan, nan, nan};
-    const double ls = std::sqrt(m.ssq_neg / (double)m.n_neg), rs = std::sqrt(m.ssq_pos / (double)m.n_pos);
-    const double g = ls / rs;
-    const double ma = m.sabs / n;
-    const double rhat = ma * ma / ((m.ssq_neg + m.ssq_pos) / n);
-    const double g2 = g * g;
-    const double R = rhat * (g2 * g + 1.0) * (g + 1.0) / ((g2 + 1.0) * (g2 + 1.0));
-    if (!(R == R)) return {nan, nan, nan};
-    const double alpha = nq_gam_at(nq_gam_argmin(R));
-    const double s = std::sqrt(std::tgamma(1.0 / alpha) / std::tgamma(3.0 / alpha));
-    return {alpha, ls * s, rs * s};
+    const MscnAggd a = mscn_aggd(m, n);
+    if (!(a.alpha == a.alpha)) return {a.alpha, a.ls, a.rs};            // all NaN
+    const double s = std::sqrt(std::tgamma(1.0 / a.alpha) / std::tgamma(3.0 / a.alpha));
+    return {a.alpha, a.ls * s, a.rs * s};
 }
 
 void scale_features(const sr_niqe_block &rec, double n, double *f)
@@ -120,13 +111,9 @@ void jacobi_eig(double *A, double *V, int n)
 
 int nq_plan(const char *scope, int h, int w, int cn, int crop_border, NqPlan *p)
 {
-    if (cn != 1 && cn != 3) return sr_set_error(SR_ERR_INVALID_ARG, "%s: need 1 or 3 channels (got %d)", scope, cn);
-    if (crop_border < 0) return sr_set_error(SR_ERR_INVALID_ARG, "%s: crop_border must be >= 0 (got %d)", scope, crop_border);
-    if (h < 1 || w < 1) return sr_set_error(SR_ERR_INVALID_ARG, "%s: need h, w >= 1", scope);
-    const long long ch = (long long)h - 2LL * crop_border, cw = (long long)w - 2LL * crop_border;
-    if (ch < NQ_BLOCK || cw < NQ_BLOCK)
-        return sr_set_error(SR_ERR_SHAPE, "%s: image %dx%d with crop_border %d leaves %lldx%lld: both sides must be at least %d "
-                            "after the crop", scope, w, h, crop_border, std::max(cw, 0LL), std::max(ch, 0LL), NQ_BLOCK);
+    long long ch, cw;
+    const int rc = mscn_crop(scope, h, w, cn, crop_border, NQ_BLOCK, &ch, &cw);
+    if (rc) return rc;
     memset(p, 0, sizeof(*p));
     p->nby = (int)(ch / NQ_BLOCK);
     p->nbx = (int)(cw / NQ_BLOCK);

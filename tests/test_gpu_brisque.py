@@ -5,7 +5,8 @@ tests/_brisque_ref.py.  T = 64 is the moment kernel's tile side.
   padding; 64 x 64 -- one full tile; 65 x 127 -- 2 x 2 tiles with one-pixel and T - 1 remainders, odd sides (H2, W2 round up,
   both reflect sides of the 8-tap pass); 192 x 192 -- an interior tile with no wrap and no padding; 200 x 301 with crop_border
   3 -- an odd byte offset and an odd width;
-* the half plane is equal as integers;
+* the half plane is equal as integers, and equal to NIQE's on shapes that are multiples of 96 after the crop (one kernel, two
+  instantiations);
 * per scale and per X the ten counts are equal and the sums are within 1e-9 relative (all-positive fp64 sums: the suite's bar,
   the one of tests/test_gpu_niqe.py); a failure names scale and shift;
 * a wrap probe: an image whose last row and column are far from the first ones; the restatement's counts for the shifts
@@ -95,6 +96,27 @@ def test_the_roll_wraps_over_the_whole_plane(ctx):
             counts = [(int(r[s]["x"][i]["n_neg"]), int(r[s]["x"][i]["n_pos"])) for r in (want, replicate, zero)]
             assert counts[0] != counts[1] and counts[0] != counts[2], (s, i, counts)
     _check_records(_run(ctx, img), want, "wrap probe")
+
+
+@pytest.mark.parametrize("cn", [1, 3])
+def test_niqe_and_brisque_keep_the_same_half_plane(ctx, cn):
+    """One half-plane kernel (k_mscn_half) serves both metrics: NIQE's instantiation without the clamp and the store guard,
+    BRISQUE's with them.  On shapes that are multiples of 96 after the crop both keep the same plane: equal integers.
+    (200 x 301 with crop_border 3 is not among them: NIQE trims it to 192 x 288 and reflects at another edge.)"""
+    import _niqe_ref
+    for h, w, cb in ((96, 96, 0), (96, 192, 0), (288, 288, 0), (102, 198, 3)):
+        img = _niqe_ref.image(_niqe_ref.case_seed(h, w, cn), h, w, cn)
+        shape = ((h - 2 * cb) // 2, (w - 2 * cb) // 2)
+        d = ctx.upload(img)
+        try:
+            ctx.niqe_u8(d.ptr, w * cn, h, w, cn, crop_border=cb)
+            ctx.brisque_u8(d.ptr, w * cn, h, w, cn, crop_border=cb)
+        finally:
+            d.free()
+        niqe_half, brisque_half = ctx.niqe_half_plane(shape), ctx.brisque_half_plane(shape)
+        assert niqe_half.dtype == brisque_half.dtype == np.int32 and niqe_half.any()
+        bad = np.argwhere(niqe_half != brisque_half)
+        assert bad.size == 0, f"{h}x{w} cb {cb}: half planes differ at {bad[:4].tolist()}"
 
 
 def test_score_matches_the_restatement(ctx):
