@@ -765,6 +765,58 @@ SR_API int sr_resize_cubic_u8(sr_ctx *ctx, const uint8_t *d_src, int64_t src_str
 SR_API int sr_resize_cubic_window_u8(sr_ctx *ctx, const uint8_t *d_src, int64_t src_stride, int h,
                                      int w, int cn, int dh, int dw, int x0, int y0, int ww, int wh,
                                      uint8_t *d_dst, int64_t dst_stride);
+/* ---- MATLAB imresize, bicubic (csrc/sr_imresize.hip, csrc/sr_imresize_host.cpp) -----------------------------------------------
+ * imresize(A, scale) / imresize(A, [dh dw]) with the 'bicubic' kernel: MATLAB's imresize.m / contributions, the form BasicSR's
+ * matlab_functions.imresize restates -- the degradation every classical SR benchmark is defined on ("HR, downscaled by
+ * imresize(hr, 1 / s), run through the network, compared with the HR").  NOT sr_resize_cubic_u8, which is OpenCV's INTER_CUBIC
+ * (a = -0.75, four taps whatever the scale, no antialiasing).  No reference counterpart.  PARITY UNPINNED with MATLAB and BasicSR:
+ * neither is available offline.  Anchors: at scale 1/2 the definition is NIQE's exact half plane above; away from the border
+ * it agrees with torch's F.interpolate(mode='bicubic', antialias=True, align_corners=False) in float64 (torch clamps at the
+ * border, MATLAB reflects); tests/_imresize_ref.py restates it in NumPy.  Known distance: BasicSR scales by / 255 ... * 255
+ * around the resize where v here is in gray levels, a rounding-level difference.
+ * Per axis of input length n and output length m:
+ *   sizes    scalar scale: m = ceil(n * scale) evaluated in double exactly as written (MATLAB's answer, its floating-point
+ *            trap included: ceil(100 * 0.07) is 8) and both axes use `scale` itself; output size: the axis scale is m / n in
+ *            double.
+ *   kernel   cubic(x), a = -0.5: 1.5 |x|^3 - 2.5 |x|^2 + 1 for |x| <= 1, -0.5 |x|^3 + 2.5 |x|^2 - 4 |x| + 2 for 1 < |x| <= 2,
+ *            else 0.  Kernel width kw = 4 / scale when scale < 1 and antialiasing is on, else 4; P = ceil(kw) + 2 taps.
+ *   output i (0-based): u = (i + 1) / scale + 0.5 (1 - 1 / scale), left = floor(u - kw / 2); tap k = 0 .. P - 1 reads the
+ *            1-based index left + k with weight scale * cubic(scale * (u - left - k)) when antialiased below 1, else
+ *            cubic(u - left - k); the weights of an output are divided by their sum, taken in ascending k, in float64.
+ *   border   symmetric reflection as MATLAB writes it: 0-based j = (idx - 1) mod 2 n, then j >= n -> 2 n - 1 - j; an image
+ *            shorter than the kernel wraps more than once.
+ *   order    the axis with the smaller scale goes first, on a tie the vertical pass (along the height), as in MATLAB and
+ *            BasicSR.  Both passes are float64 without contraction, taps added in ascending k; the first pass's result stays
+ *            float64 (the im2double -> imresize -> im2uint8 protocol of the dataset scripts: no intermediate u8 rounding).
+ *   outputs  v in gray levels.  SR_IMRESIZE_U8: min(255, max(0, floor(v + 0.5))); SR_IMRESIZE_F32: v rounded to float32, not
+ *            clamped; SR_IMRESIZE_F64: v itself, not clamped (inspection and tests).
+ * Ranges: u8 input, cn 1, 3 or 4, sides >= 1, each axis scale in [1/16, 16] (so P <= 66; outside: SR_ERR_UNSUPPORTED naming
+ * the range).  Out of scope: the 'bilinear' / 'lanczos' / 'box' kernels, uint16 / float inputs, and MATLAB's uint8-class path
+ * with a rounded intermediate (imresize called on a uint8 array directly), which differs from this by +-1 level in places. */
+enum sr_imresize_out { SR_IMRESIZE_U8 = 0, SR_IMRESIZE_F32 = 1, SR_IMRESIZE_F64 = 2 };
+/* Host only: ceil(n * scale), or a negative SR_ERR_* (n < 1: SR_ERR_INVALID_ARG; a scale outside [1/16, 16] or not finite:
+ * SR_ERR_UNSUPPORTED). */
+SR_API int sr_imresize_size(int n, double scale);
+/* Host only: the normalised weights and the reflected 0-based indices of one axis.  Leading and trailing taps whose weight is
+ * zero for every output are dropped (no value changes): *taps is what is left, and w / idx (both or neither may be NULL) are
+ * dense n_out x *taps, room for n_out x cap.  n_out must be ceil(n_in * scale) or scale must be n_out / n_in, else
+ * SR_ERR_INVALID_ARG; as is cap < *taps (with *taps set). */
+SR_API int sr_imresize_weights(int n_in, int n_out, double scale, int antialias, int cap, int *taps, double *w, int32_t *idx);
+/* Host only, no context: the pass order (*order 0: vertical pass first, 1: horizontal first), the tap counts, the output tile
+ * of one workgroup (tile_h x tile_w), its LDS bytes and the bytes of context scratch (the tables) a call will hold; each
+ * output may be NULL.  Carries every shape refusal of sr_imresize_u8: SR_ERR_INVALID_ARG for h, w, dh or dw < 1, cn not 1, 3
+ * or 4, an axis whose (scale, output length) pair is neither form above; SR_ERR_UNSUPPORTED for a scale outside [1/16, 16]. */
+SR_API int sr_imresize_plan(int h, int w, int cn, double scale_y, double scale_x, int dh, int dw, int antialias, int *order,
+                            int *taps_y, int *taps_x, int *tile_h, int *tile_w, size_t *lds_bytes, size_t *scratch_bytes);
+/* One launch: a workgroup owns tile_h x tile_w outputs, runs the first pass for exactly the input span they need into LDS
+ * (float64) and the second pass out of LDS; no float64 intermediate goes through HBM.  Every output's sum has a fixed order:
+ * the result depends neither on the tile geometry nor on strides.  Strides in bytes, arbitrary (>= a row); pixels are read
+ * byte by byte and offsets are 64-bit; nothing outside dh x dw x cn elements of the destination is written.  d_dst holds
+ * uint8_t, float or double by out_type.  Synchronous; the tables are context scratch, grown on demand.  Refused before any
+ * device call: null pointers, everything sr_imresize_plan refuses, an unknown out_type, a stride shorter than a row
+ * (SR_ERR_SHAPE), a float / double destination or stride that is not a multiple of the element size. */
+SR_API int sr_imresize_u8(sr_ctx *ctx, const uint8_t *d_src, int64_t src_stride, int h, int w, int cn, double scale_y,
+                          double scale_x, int antialias, int out_type, void *d_dst, int64_t dst_stride, int dh, int dw);
 
 /* ---- BlendingModule.color_correction (blending_module.py:969-1146) ---------------------------------
  * sr_histogram_u8: per-channel 256-bin histogram (np.histogram(ch, 256, [0, 256]) of u8 data), h_hist = cn x 256 counts.

@@ -75,6 +75,10 @@ class BenchSums(C.Structure):
 
 # enum sr_bench_mode (include/sr_hip.h)
 BENCH_CHANNELS, BENCH_Y, BENCH_Y_ROUND = 0, 1, 2
+# enum sr_imresize_out (include/sr_hip.h) and the element type each writes
+IMRESIZE_U8, IMRESIZE_F32, IMRESIZE_F64 = 0, 1, 2
+IMRESIZE_DTYPES = {IMRESIZE_U8: np.uint8, IMRESIZE_F32: np.float32, IMRESIZE_F64: np.float64}
+IMRESIZE_MAX_TAPS = 66
 
 
 class NiqeMoments(C.Structure):
@@ -262,6 +266,10 @@ SIGNATURES = {
     "sr_brisque_features": (_i, [_vp, _vp]),
     "sr_brisque_score": (_dbl, [_vp, _vp, _vp, _i64, _dbl, _dbl, _vp, _vp, _dbl, _dbl]),
     "sr_rgb2gray_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64]),
+    "sr_imresize_size": (_i, [_i, _dbl]),
+    "sr_imresize_weights": (_i, [_i, _i, _dbl, _i, _i, _pi, _vp, _vp]),
+    "sr_imresize_plan": (_i, [_i, _i, _i, _dbl, _dbl, _i, _i, _i, _pi, _pi, _pi, _pi, _pi, C.POINTER(_sz), C.POINTER(_sz)]),
+    "sr_imresize_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _dbl, _dbl, _i, _i, _vp, _i64, _i, _i]),
     "sr_resize_cubic_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i]),
     "sr_resize_cubic_window_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64]),
     "sr_gray_moments_u8": (_i, [_vp, _vp, _i, _i64, _i64, _i, _i, _i, _i, C.POINTER(C.c_uint64)]),
@@ -653,6 +661,58 @@ def bench_values(sums: dict, data_range: float = 255.0) -> Tuple[float, float]:
     sse = sums["sse"]
     psnr = float("inf") if sse == 0 else 10.0 * math.log10(float(data_range) * float(data_range) / (sse / sums["n_elems"]))
     return psnr, sums["ssim_sum"] / sums["n_map"]
+
+
+def imresize_size(n: int, scale: float) -> int:
+    """Host only (sr_imresize_size): MATLAB's output length ceil(n * scale), evaluated in double as written.  ValueError for
+    n < 1, SrNativeError (SR_ERR_UNSUPPORTED) naming the range for a scale outside [1/16, 16]."""
+    m = load().sr_imresize_size(_whole(n, "n"), float(scale))
+    if m < 0:
+        check(m)
+    return int(m)
+
+
+def imresize_geometry(h: int, w: int, scale=None, output_shape=None) -> Tuple[float, float, int, int]:
+    """The two forms of imresize's size argument -> (scale_y, scale_x, dh, dw): a scalar `scale` (both axes use it, sides
+    ceil(n * scale)) or `output_shape` = (dh, dw) (the axis scales are dh / h and dw / w).  ValueError for both or neither."""
+    if (scale is None) == (output_shape is None):
+        raise ValueError("imresize: give exactly one of scale and output_shape")
+    h, w = _whole(h, "h"), _whole(w, "w")
+    if h < 1 or w < 1:
+        raise ValueError(f"imresize: sides must be >= 1 (got {h} x {w})")
+    if scale is not None:
+        scale = float(scale)
+        return scale, scale, imresize_size(h, scale), imresize_size(w, scale)
+    if len(output_shape) != 2:
+        raise ValueError(f"imresize: output_shape must be (dh, dw), got {output_shape!r}")
+    dh, dw = _whole(output_shape[0], "dh"), _whole(output_shape[1], "dw")
+    if dh < 1 or dw < 1:
+        raise ValueError(f"imresize: sides must be >= 1 (got {dh} x {dw})")
+    return dh / h, dw / w, dh, dw
+
+
+def imresize_weights(n_in: int, n_out: int, scale: float, antialias: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """Host only (sr_imresize_weights): (w[n_out, taps] float64, idx[n_out, taps] int32) of one axis -- the normalised weights
+    and the reflected 0-based indices, without the taps that are zero for every output."""
+    n_in, n_out = _whole(n_in, "n_in"), _whole(n_out, "n_out")
+    taps = C.c_int(0)
+    check(load().sr_imresize_weights(n_in, n_out, float(scale), 1 if antialias else 0, 0, C.byref(taps), None, None))
+    w, idx = np.zeros((n_out, taps.value), dtype=np.float64), np.zeros((n_out, taps.value), dtype=np.int32)
+    check(load().sr_imresize_weights(n_in, n_out, float(scale), 1 if antialias else 0, taps.value, C.byref(taps),
+                                     w.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p)))
+    return w, idx
+
+
+def imresize_plan(h: int, w: int, cn: int, scale_y: float, scale_x: float, dh: int, dw: int, antialias: bool = True) -> dict:
+    """Host only (sr_imresize_plan): the pass order ('vertical' or 'horizontal' first), the tap counts, the output tile of one
+    workgroup, its LDS bytes and the bytes of context scratch of an imresize call.  Carries every shape refusal: ValueError,
+    or SrNativeError (SR_ERR_UNSUPPORTED) naming the range for a scale outside [1/16, 16]."""
+    h, w, cn, dh, dw = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn"), (dh, "dh"), (dw, "dw")))
+    order, ty, tx, th, tw, lds, nbytes = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+    check(load().sr_imresize_plan(h, w, cn, float(scale_y), float(scale_x), dh, dw, 1 if antialias else 0, C.byref(order),
+                                  C.byref(ty), C.byref(tx), C.byref(th), C.byref(tw), C.byref(lds), C.byref(nbytes)))
+    return {"first": "vertical" if order.value == 0 else "horizontal", "taps": (ty.value, tx.value), "tile": (th.value, tw.value),
+            "lds_bytes": int(lds.value), "scratch_bytes": int(nbytes.value)}
 
 
 def niqe_plan(h: int, w: int, cn: int, crop_border: int = 0) -> dict:
@@ -1191,6 +1251,18 @@ class Context:
     def rgb2gray_u8(self, d_rgb, stride, h, w, d_gray, gray_stride, gray_shift=15):
         check(self.lib.sr_rgb2gray_u8(self.handle, C.c_void_p(d_rgb), stride, h, w, gray_shift, C.c_void_p(d_gray),
                                       gray_stride))
+
+    def imresize(self, d_src, src_stride, h, w, cn, scale_y, scale_x, d_dst, dst_stride, dh, dw, antialias=True,
+                 out_type=IMRESIZE_U8):
+        """sr_imresize_u8: MATLAB's bicubic imresize of a u8 image in HBM into d_dst (uint8, float32 or float64 by out_type;
+        strides in bytes).  Synchronous.  Every argument is checked before the device is touched: ValueError, its subclass
+        SrShapeError for a short stride, SrNativeError (SR_ERR_UNSUPPORTED) for a scale outside [1/16, 16]."""
+        if not d_src or not d_dst:
+            raise ValueError("imresize: null image pointer")
+        imresize_plan(h, w, cn, scale_y, scale_x, dh, dw, antialias)
+        check(self.lib.sr_imresize_u8(self.handle, C.c_void_p(d_src), int(src_stride), int(h), int(w), int(cn), float(scale_y),
+                                      float(scale_x), 1 if antialias else 0, _whole(out_type, "out_type"), C.c_void_p(d_dst),
+                                      int(dst_stride), int(dh), int(dw)))
 
     def resize_cubic_u8(self, d_src, src_stride, h, w, cn, d_dst, dst_stride, dh, dw):
         check(self.lib.sr_resize_cubic_u8(self.handle, C.c_void_p(d_src), src_stride, h, w, cn, C.c_void_p(d_dst),

@@ -86,6 +86,10 @@ class PipelineConfig:
                                # (ignored for the residual family)
     sr_ensemble: int = 1       # (with sr_weights) geometric self-ensemble of the network: 1 off, 2 identity + horizontal flip, 4 the
                                # four flips, 8 all eight flips / rotations, averaged on the device (the "+" results of SR papers)
+    benchmark_degrade: bool = False  # the input file is the GROUND TRUTH: it is mod-cropped to sr_scale and brought down by MATLAB's
+                               # bicubic imresize(1 / sr_scale) on the GPU, that low-resolution image is the source of stages 1 - 3
+                               # exactly as if it had been the input file, and stage 4 adds 'benchmark_hr': the SR-benchmark PSNR / SSIM
+                               # of the canvas against the ground truth.  Device-resident path, built-in backends, one GPU only
 
 
 @dataclass
@@ -128,6 +132,15 @@ class SuperResolutionPipeline:
         self._brisque_model = None     # qa_brisque_model, read at the first use
         self._dists_model = None       # qa_dists_weights, loaded at the first use
         self.sr_net = None
+        if config.benchmark_degrade:
+            import _launch
+            if sr_backend is not None:
+                raise ValueError("benchmark_degrade needs a built-in backend (the stub or sr_weights): a custom sr_backend gets host "
+                                 "arrays, and the ground truth stays in HBM")
+            if not config.device_resident:
+                raise ValueError("benchmark_degrade runs on the device-resident path only (device_resident=False was asked for)")
+            if _launch.dist_env()[1] > 1:
+                raise ValueError("benchmark_degrade runs on one GPU: the sharded pipeline (WORLD_SIZE > 1) is out of its scope")
         if config.sr_ensemble != 1:
             from sr_network import ensemble_mask
             ensemble_mask(config.sr_ensemble)                                                # ValueError outside {1, 2, 4, 8}
@@ -252,6 +265,54 @@ class SuperResolutionPipeline:
             ctx.sync()
             ref.free()
         out.update(psnr_y=y['psnr'], ssim_y=y['ssim'], psnr_rgb=rgb['psnr'], ssim_rgb=rgb['ssim'])
+
+    def _degrade(self, ctx, hr: np.ndarray):
+        """benchmark_degrade's stage 0: the ground truth goes up once and stays in HBM; its mod-crop to sr_scale (a view: the
+        same address, the full stride) is brought down by MATLAB's bicubic imresize(1 / sr_scale) on the GPU, and the
+        low-resolution image -- 1 / sr_scale^2 of the ground truth -- comes down once to feed split_array.
+        -> (the device buffer of the ground truth, its row stride in bytes, the cropped shape, the low-resolution array)."""
+        s = int(self.config.sr_scale)
+        H, W = hr.shape[0] - hr.shape[0] % s, hr.shape[1] - hr.shape[1] % s
+        if H < s or W < s:
+            raise ValueError(f"benchmark_degrade: the image {hr.shape[:2]} is smaller than sr_scale {s}")
+        d_hr, d_lr = ctx.upload(hr), None
+        try:
+            lh, lw = H // s, W // s
+            d_lr = ctx.alloc(lh * lw * 3)
+            shape = self.quality_module.imresize_device(d_hr.ptr, (H, W, 3), d_lr.ptr, scale=1.0 / s, src_stride=hr.shape[1] * 3)
+            if shape != (lh, lw, 3):
+                raise ValueError(f"benchmark_degrade: imresize gave {shape}, not {(lh, lw, 3)}")
+            lr = ctx.download(d_lr.ptr, (lh, lw, 3), np.uint8)
+        except Exception:
+            d_hr.free()
+            raise
+        finally:
+            if d_lr is not None:
+                d_lr.free()
+        return d_hr, hr.shape[1] * 3, (H, W, 3), lr
+
+    def _benchmark_hr(self, ctx, report: Dict[str, Any], d_hr: int, hr_stride: int, d_canvas: int, canvas_shape, lr_shape) -> None:
+        """Stage 4's 'benchmark_hr' entry (benchmark_degrade): the SR-benchmark PSNR / SSIM -- a border of sr_scale pixels
+        cropped, on the BT.601 luma and on the RGB channels -- of the canvas against the mod-cropped ground truth, both in
+        HBM: the keys of QualityAssessmentModule.evaluate_sr_network.  A side below 11 after the crop has no SSIM window:
+        the entry is None and 'benchmark_hr_note' says why (the run does not fail)."""
+        import _native
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        cb = int(self.config.sr_scale)
+        try:
+            _native.bench_plan(H, W, cn, cb, _native.BENCH_Y)
+        except ValueError as exc:
+            report['benchmark_hr'], report['benchmark_hr_note'] = None, str(exc)
+            return
+        out = {}
+        try:
+            for key, mode in (("y", _native.BENCH_Y), ("rgb", _native.BENCH_CHANNELS)):
+                sums = ctx.bench_u8(d_canvas, W * cn, d_hr, hr_stride, H, W, cn, crop_border=cb, mode=mode, data_range=255.0)
+                out["psnr_" + key], out["ssim_" + key] = _native.bench_values(sums, 255.0)
+        finally:
+            ctx.sync()
+        out.update(crop_border=cb, scale=cb, hr_shape=[H, W, cn], lr_shape=[int(v) for v in lr_shape])
+        report['benchmark_hr'] = out
 
     def _dists(self, ctx, report: Dict[str, Any], d_src: int, src_shape, d_canvas: int, canvas_shape) -> None:
         """Stage 4's optional 'dists' entry (qa_dists_weights): DISTS of the canvas against the INTER_CUBIC resize of the
@@ -394,18 +455,23 @@ class SuperResolutionPipeline:
             t_mark = now
 
         original = _load_rgb(input_path)
-        ih, iw = original.shape[:2]
         ctx = self.quality_module._ctx()
         h2d0, d2h0 = ctx.h2d_bytes, ctx.d2h_bytes
         lap("decode")
-        # Stage 1: tiling (metadata on the host, pixels stay on the GPU)
-        tiles = tm.split_array(original, image_hash=tm._compute_image_hash(input_path), image_path=input_path,
-                               device_resident=True)
-        ts = tm.device_tiles
-        block, out_block = tm.block_size, tm.block_size * s
+        d_hr = None
+        if self.config.benchmark_degrade:
+            # the file is the ground truth: from here on `original` is its imresize(1 / s), as if that had been the input file
+            d_hr, hr_stride, hr_shape, original = self._degrade(ctx, original)
+            lap("degrade")
+        ih, iw = original.shape[:2]
         sr_bufs, canvas = [], None
-        lap("upload+tile")
         try:
+            # Stage 1: tiling (metadata on the host, pixels stay on the GPU)
+            tiles = tm.split_array(original, image_hash=tm._compute_image_hash(input_path), image_path=input_path,
+                                   device_resident=True)
+            ts = tm.device_tiles
+            block, out_block = tm.block_size, tm.block_size * s
+            lap("upload+tile")
             # Stage 2: SR (the network, or the bicubic stand-in), tile by tile, HBM -> HBM
             for i in range(len(tiles)):
                 buf = ctx.alloc(out_block * out_block * 3)
@@ -439,6 +505,9 @@ class SuperResolutionPipeline:
                     self._brisque_model_entry(ctx, report, canvas.ptr, (H, W, 3))
                 if self.config.qa_dists_weights:
                     self._dists(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
+                if d_hr is not None:
+                    assert hr_shape == (H, W, 3)
+                    self._benchmark_hr(ctx, report, d_hr.ptr, hr_stride, canvas.ptr, (H, W, 3), (ih, iw, 3))
                 score = qa.get('overall_score', 0)
             lap("assess")
             # Stage 5: the one download, then the writer
@@ -446,7 +515,7 @@ class SuperResolutionPipeline:
             lap("download")
         finally:
             ctx.sync()
-            for b in sr_bufs + ([canvas] if canvas is not None else []):
+            for b in sr_bufs + ([canvas] if canvas is not None else []) + ([d_hr] if d_hr is not None else []):
                 b.free()
             tm.release_device_tiles()
         self.transfers = {"h2d_bytes": ctx.h2d_bytes - h2d0, "d2h_bytes": ctx.d2h_bytes - d2h0,
@@ -712,6 +781,10 @@ async def main() -> int:
                     help="DISTS weights (.npz with the VGG16 convolutions stageN.K.weight / .bias, or features.K.*, and alpha / "
                          "beta): stage 4 also reports the DISTS of the result against the bicubic resize of the input (report "
                          "key dists)")
+    ap.add_argument("--benchmark-degrade", action="store_true",
+                    help="the input is the ground truth: it is mod-cropped to --sr-scale, brought down by MATLAB's bicubic "
+                         "imresize(1 / scale) on the GPU, upscaled, and stage 4 also reports the SR-benchmark PSNR / SSIM of the "
+                         "result against the input (report key benchmark_hr); one GPU only")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node to use: N > 1 starts one process per GPU (RCCL)")
     ap.add_argument("--deadline-s", type=float, default=1800.0,
                     help="--gpus N: ranks still running after this many seconds are terminated (status 124)")
@@ -723,6 +796,9 @@ async def main() -> int:
     if args.gpus < 1:
         print("main.py: --gpus must be >= 1", file=sys.stderr)
         return 2
+    if args.benchmark_degrade and args.gpus > 1:
+        print("main.py: --benchmark-degrade runs on one GPU (--gpus 1)", file=sys.stderr)
+        return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # children only: this process never touches torch or the GPU (and nothing that has is ever exec'ed)
         return _launch.launch_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:], args.deadline_s, who="main.py")
@@ -733,7 +809,8 @@ async def main() -> int:
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act, sr_ensemble=args.sr_ensemble,
                          qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark,
-                         qa_niqe_params=args.qa_niqe_params, qa_brisque_model=args.qa_brisque_model, qa_dists_weights=args.qa_dists_weights)
+                         qa_niqe_params=args.qa_niqe_params, qa_brisque_model=args.qa_brisque_model, qa_dists_weights=args.qa_dists_weights,
+                         benchmark_degrade=args.benchmark_degrade)
     if args.plan_only:
         from PIL import Image
         with Image.open(args.input) as im:

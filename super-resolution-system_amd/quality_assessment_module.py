@@ -228,6 +228,112 @@ class QualityAssessmentModule:
         src.free(); dst.free()
         return out
 
+    # -- MATLAB's bicubic imresize (no reference counterpart: the degradation of the classical SR benchmarks) ------------------
+    _IMRESIZE_OUT = {np.dtype(np.uint8): _native.IMRESIZE_U8, np.dtype(np.float32): _native.IMRESIZE_F32,
+                     np.dtype(np.float64): _native.IMRESIZE_F64}
+
+    @classmethod
+    def _imresize_args(cls, shape, scale, output_shape, antialiasing, dtype):
+        """Every refusal of the imresize methods, on the host: ValueError, or SrNativeError naming the range for a scale
+        outside [1/16, 16].  -> (h, w, cn, scale_y, scale_x, dh, dw, out_type, element size, output shape)."""
+        shape = tuple(int(v) for v in shape)
+        if len(shape) not in (2, 3):
+            raise ValueError(f"imresize: need an H x W or H x W x C image, got shape {shape}")
+        cn = shape[2] if len(shape) == 3 else 1
+        try:
+            out_type = cls._IMRESIZE_OUT[np.dtype(dtype)]
+        except (KeyError, TypeError) as exc:
+            raise ValueError(f"imresize: dtype must be uint8, float32 or float64, got {dtype!r}") from exc
+        sy, sx, dh, dw = _native.imresize_geometry(shape[0], shape[1], scale, output_shape)
+        _native.imresize_plan(shape[0], shape[1], cn, sy, sx, dh, dw, bool(antialiasing))      # cn, the scale range
+        out_shape = (dh, dw, cn) if len(shape) == 3 else (dh, dw)
+        return shape[0], shape[1], cn, sy, sx, dh, dw, out_type, np.dtype(dtype).itemsize, out_shape
+
+    def imresize(self, image: np.ndarray, scale: Optional[float] = None, output_shape: Optional[Tuple[int, int]] = None,
+                 antialiasing: bool = True, dtype=np.uint8) -> np.ndarray:
+        """MATLAB's imresize(image, scale) / imresize(image, [dh dw]) with the bicubic kernel (a = -0.5, antialiased below 1,
+        symmetric border), as include/sr_hip.h defines it and BasicSR's matlab_functions.imresize restates it: the resize
+        the SR benchmarks make their low-resolution inputs with.  NOT downsample_bicubic / upsample_bicubic, which stay
+        OpenCV's INTER_CUBIC.  Give exactly one of `scale` (both axes use it, sides ceil(n * scale)) and `output_shape`.
+        u8 image H x W or H x W x C (C 1, 3 or 4), each axis scale in [1/16, 16].  dtype uint8: rounded half up and
+        saturated; float32 / float64: the unclamped value in gray levels."""
+        img = self._require_u8(np.asarray(image), "imresize")
+        args = self._imresize_args(img.shape, scale, output_shape, antialiasing, dtype)
+        h, w, cn, sy, sx, dh, dw, out_type, item, out_shape = args
+        ctx = self._ctx()
+        src, dst = _DevImage(ctx, img), None
+        try:
+            dst = ctx.alloc(dh * dw * cn * item)
+            ctx.imresize(src.ptr, w * cn, h, w, cn, sy, sx, dst.ptr, dw * cn * item, dh, dw, antialias=bool(antialiasing),
+                         out_type=out_type)
+            return ctx.download(dst.ptr, out_shape, np.dtype(dtype).type)
+        finally:
+            src.free()
+            if dst is not None:
+                dst.free()
+
+    def imresize_device(self, d_src: int, shape, d_dst: int, scale: Optional[float] = None,
+                        output_shape: Optional[Tuple[int, int]] = None, antialiasing: bool = True, dtype=np.uint8,
+                        src_stride: Optional[int] = None, dst_stride: Optional[int] = None) -> Tuple[int, ...]:
+        """imresize on a u8 image that already lives in HBM, into d_dst (device addresses; dense unless the strides, in
+        bytes, are given).  -> the output's shape.  Synchronous."""
+        args = self._imresize_args(shape, scale, output_shape, antialiasing, dtype)
+        h, w, cn, sy, sx, dh, dw, out_type, item, out_shape = args
+        if not d_src or not d_dst:
+            raise ValueError("imresize: null device pointer")
+        ss = w * cn if src_stride is None else int(src_stride)
+        ds = dw * cn * item if dst_stride is None else int(dst_stride)
+        if ss < w * cn or ds < dw * cn * item:
+            raise ValueError("imresize: a stride is shorter than a row")
+        self._ctx().imresize(int(d_src), ss, h, w, cn, sy, sx, int(d_dst), ds, dh, dw, antialias=bool(antialiasing),
+                             out_type=out_type)
+        return out_shape
+
+    def evaluate_sr_network(self, net, hr: np.ndarray, crop_border: Optional[int] = None, ensemble: int = 1, y_round: bool = False,
+                            return_sr: bool = False) -> Dict[str, Any]:
+        """The ground-truth benchmark of an SR network (sr_network.py) on one image, the protocol of the SR papers: the u8 RGB
+        image `hr` is mod-cropped to net.scale, brought down by imresize(1 / net.scale) (MATLAB's bicubic), run through the
+        network and compared with the cropped HR by the SR-benchmark PSNR / SSIM on Y (y_round: MATLAB's rounded u8 luma) and
+        on RGB, a border of crop_border (default net.scale) pixels cropped.  Everything stays in HBM; only the numbers come
+        down, and with return_sr the SR image ('sr').  -> {'psnr_y', 'ssim_y', 'psnr_rgb', 'ssim_rgb', 'crop_border',
+        'scale', 'hr_shape', 'lr_shape'}."""
+        from sr_network import ensemble_mask
+        ensemble_mask(ensemble)
+        img = self._require_u8(np.asarray(hr), "evaluate_sr_network")
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"evaluate_sr_network: need an H x W x 3 RGB image, got shape {img.shape}")
+        s = int(net.scale)
+        cb = s if crop_border is None else _native._whole(crop_border, "crop_border")
+        H, W = img.shape[0] - img.shape[0] % s, img.shape[1] - img.shape[1] % s
+        if H < s or W < s:
+            raise ValueError(f"evaluate_sr_network: the image {img.shape[:2]} is smaller than the scale {s}")
+        lr_args = self._imresize_args((H, W, 3), 1.0 / s, None, True, np.uint8)
+        lh, lw = lr_args[5], lr_args[6]
+        if (lh * s, lw * s) != (H, W):
+            raise ValueError(f"evaluate_sr_network: ceil({H, W} / {s}) gave {lh, lw}")
+        y_args = self._sr_benchmark_args((H, W, 3), (H, W, 3), cb, True, bool(y_round), 255.0)
+        rgb_args = self._sr_benchmark_args((H, W, 3), (H, W, 3), cb, False, False, 255.0)
+        ctx = self._ctx()
+        full_stride = img.shape[1] * 3                                  # the mod-crop is a view: the same address, the full stride
+        d_hr, d_lr, d_sr = _DevImage(ctx, img), None, None
+        try:
+            d_lr, d_sr = ctx.alloc(lh * lw * 3), ctx.alloc(H * W * 3)
+            ctx.imresize(d_hr.ptr, full_stride, H, W, 3, 1.0 / s, 1.0 / s, d_lr.ptr, lw * 3, lh, lw)
+            net.upscale_device(d_lr.ptr, (lh, lw, 3), d_sr.ptr, W * 3, ctx=ctx, ensemble=ensemble)
+            out = {}
+            for key, a in (("y", y_args), ("rgb", rgb_args)):
+                sums = ctx.bench_u8(d_sr.ptr, W * 3, d_hr.ptr, full_stride, H, W, 3, crop_border=cb, mode=a[4], data_range=255.0)
+                out["psnr_" + key], out["ssim_" + key] = _native.bench_values(sums, 255.0)
+            out.update(crop_border=cb, scale=s, hr_shape=(H, W, 3), lr_shape=(lh, lw, 3))
+            if return_sr:
+                out["sr"] = ctx.download(d_sr.ptr, (H, W, 3), np.uint8)
+            return out
+        finally:
+            ctx.sync()
+            for b in (d_hr, d_lr, d_sr):
+                if b is not None:
+                    b.free()
+
     # -- device-level metrics ---------------------------------------------------------------------------
     def _psnr_dev(self, a: _DevImage, b: _DevImage, data_range: float) -> float:
         h, w = min(a.h, b.h), min(a.w, b.w)
@@ -1205,6 +1311,17 @@ _FFT_MAX_LEN = 32768          # sr_fft_max_len(): longest DFT line of the hand-w
 
 
 # -- the pristine model of NIQE: check, fit, save, load ---------------------------------------------------------------------
+def mod_crop(image: np.ndarray, scale: int) -> np.ndarray:
+    """The top-left (h - h % scale) x (w - w % scale) of an image, as a view: what the SR benchmarks do to a ground-truth
+    image before they degrade it, so that the upscaled result has its size."""
+    s = _native._whole(scale, "scale")
+    if s < 1:
+        raise ValueError(f"mod_crop: scale must be >= 1, got {s}")
+    image = np.asarray(image)
+    h, w = image.shape[:2]
+    return image[:h - h % s, :w - w % s]
+
+
 def check_niqe_params(params) -> Dict[str, np.ndarray]:
     """-> {'mu_pris_param': float64 (36,), 'cov_pris_param': float64 (36, 36)}; ValueError for missing keys or other shapes
     (mu may come as (36,) or (1, 36))."""
