@@ -272,7 +272,11 @@ SR_API int sr_weighted_blend(sr_blend_plan *plan, int dtype, void *const *h_d_ti
                              float *d_canvas_f32);
 
 /* weighted_average_fusion with caller-supplied weight maps (blending_module.py:729-751): h_d_weights[i] is an
- * h_i x w_i fp32 map in HBM (row stride in bytes).  Same accumulate / normalise / clip / truncate. */
+ * h_i x w_i fp32 map in HBM (row stride in bytes, at least w_i * 4; address and stride multiples of 4).  Same accumulate /
+ * normalise / clip / truncate, rows [row_begin, row_end) only; a pixel no tile covers is 0 in both canvases.
+ * A tile whose sr_blend_plan_tile_rows window is empty (a row-window plan that does not reach it) is never read: both its
+ * tile pointer and its weight pointer may be NULL (its strides are still checked).  A NULL weight pointer for a tile that has
+ * rows is SR_ERR_INVALID_ARG.  Every refusal happens before anything is launched: the canvases are untouched. */
 SR_API int sr_weighted_blend_custom(sr_blend_plan *plan, int dtype, void *const *h_d_tiles,
                                     const int64_t *h_strides, const float *const *h_d_weights,
                                     const int64_t *h_weight_strides, uint8_t *d_canvas, int64_t canvas_stride,

@@ -2203,7 +2203,8 @@ int sr_weighted_blend_custom(sr_blend_plan *plan, int dtype, void *const *h_d_ti
     std::vector<TileSrc> srcs(P->n);
     std::vector<CustomW> wts(P->n);
     for (int t = 0; t < P->n; ++t) {
-        if (!h_d_weights[t]) return sr_set_error(SR_ERR_INVALID_ARG, "sr_weighted_blend_custom: weight map %d is null", t);
+        // like the tile itself (blend_check_tiles): a tile none of whose rows the plan reads needs no map
+        if (!h_d_weights[t] && !P->tile_rows[t].empty()) return sr_set_error(SR_ERR_INVALID_ARG, "sr_weighted_blend_custom: weight map %d is null", t);
         if (h_weight_strides[t] < (int64_t)P->tiles[t].w * 4) return sr_set_error(SR_ERR_SHAPE, "sr_weighted_blend_custom: weight map %d stride too small", t);
         srcs[t].p = h_d_tiles[t];
         srcs[t].stride = h_strides[t];

@@ -1,5 +1,7 @@
 """GPU: every strided entry point of include/sr_hip.h on padded, offset, guarded views (tests/_views.py).
 
+(sr_weighted_blend_custom included: tiles, fp32 weight maps and the canvas are three kinds of views.)
+
 Each test lays its inputs and outputs into parents full of a fill byte -- base residues 0..3, 7, 12 mod 16, stride residues
 0..3 mod 4 and a 64-byte gap, input and output layouts chosen independently -- and asserts (a) the result: the reference and
 tolerance of the entry point's own test where that is a few lines (the C oracle, oracle_np, the tests/_*_ref.py
@@ -220,6 +222,59 @@ def test_blend_row_window_views(ctx, rng, march, env, fill, monkeypatch):
                 assert np.array_equal(fl[a:b], ref_f[a:b]) and np.array_equal(u8[a:b], ref_u8[a:b]), f"rows [{a}, {b}): {tag}"
         finally:
             plan.close()
+
+
+def _custom_case(rng, cn, f32):
+    """Four tiles of 40 x 67 at overlaps 12 / 13 on a 68 x 121 canvas, weight maps uniform in [0.1, 1) with one box where every
+    covering weight is 0 and one where the four weights sum to 3e-7, below the 1e-6 floor."""
+    th, tw = 40, 67
+    rects = [((i % 2) * (tw - 13), (i // 2) * (th - 12), tw, th) for i in range(4)]
+    tiles = [_scene(rng, th, tw, cn, i) for i in range(4)]
+    if f32:
+        tiles = [t.astype(np.float32) * np.float32(0.75) + np.float32(3.25) for t in tiles]
+    maps = [rng.uniform(0.1, 1.0, (th, tw)).astype(np.float32) for _ in range(4)]
+    for m, (x, y, _, _) in zip(maps, rects):
+        m[30 - y:34 - y, 56 - x:60 - x] = 0.0                          # canvas rows 30..33, columns 56..59: under all four tiles
+        m[35 - y:38 - y, 58 - x:64 - x] = np.float32(7.5e-8)
+    return tiles, maps, rects, 2 * th - 12, 2 * tw - 13
+
+
+@FILL
+@pytest.mark.parametrize("cn,f32", [(3, False), (1, True), (4, False), (3, True)], ids=["cn3-u8", "cn1-f32", "cn4-u8", "cn3-f32"])
+def test_weighted_blend_custom_views(ctx, rng, cn, f32, fill):
+    """sr_weighted_blend_custom takes three kinds of (pointer, stride) pairs: tiles (LAYOUTS_U8 / LAYOUTS_F32 by their type),
+    fp32 weight maps (LAYOUTS_F32: base and stride multiples of 4, what a const float * needs) and the u8 canvas (a guarded
+    view); the fp32 canvas is dense by the ABI.  Both canvases bit for bit oracle_np's AND the dense call's; one plan, the
+    layouts change from call to call."""
+    tiles, maps, rects, H, W = _custom_case(rng, cn, f32)
+    ref_u8, ref_f = onp.weighted_average_fusion(tiles, [(r[1], r[0]) for r in rects], (H, W), weights=maps, return_float=True)
+    shape = (H, W, cn) if cn > 1 else (H, W)
+    dt = _native.SR_F32 if f32 else _native.SR_U8
+    plan = _native.BlendPlan(ctx, rects, cn, H, W, 1, "linear")
+    try:
+        tb, wb = [ctx.upload(t) for t in tiles], [ctx.upload(m) for m in maps]
+        cu, cf = ctx.alloc(H * W * cn), ctx.alloc(H * W * cn * 4)
+        plan.blend_custom_weights([b.ptr for b in tb], [_rb(t) for t in tiles], [b.ptr for b in wb], [_rb(m) for m in maps],
+                                  cu.ptr, W * cn, dtype=dt, d_canvas_f32=cf.ptr)
+        dense_u8, dense_f = ctx.download(cu.ptr, shape, np.uint8), ctx.download(cf.ptr, shape, np.float32)
+        _free(cu, cf, *tb, *wb)
+        assert np.array_equal(dense_f, ref_f) and np.array_equal(dense_u8, ref_u8), "dense call differs from the oracle"
+        for k in range(NL):
+            ins = [_in(ctx, t, k + 1 + 5 * j, fill) for j, t in enumerate(tiles)]
+            wts = [_in(ctx, m, k + 2 + j, fill) for j, m in enumerate(maps)]
+            pc, cp, cst, ctag = _out(ctx, H, W * cn, _ok(k), fill)
+            pf, fp, _, ftag = _out(ctx, H, W * cn * 4, k, fill, f32=True, dense=True)
+            plan.blend_custom_weights([i[1] for i in ins], [i[2] for i in ins], [i[1] for i in wts], [i[2] for i in wts],
+                                      cp, cst, dtype=dt, d_canvas_f32=fp)
+            tag = f"tiles {[i[3] for i in ins]} weights {[i[3] for i in wts]} canvas {ctag} fp32 canvas {ftag}"
+            u8 = V.check_guard(ctx, pc, np.uint8, shape, what=f"custom blend canvas ({tag})")
+            fl = V.check_guard(ctx, pf, np.float32, shape, what=f"custom blend fp32 canvas ({tag})")
+            _free(pc, pf, *[i[0] for i in ins], *[i[0] for i in wts])
+            assert np.array_equal(fl, ref_f), f"fp32 canvas differs from the oracle: {tag}"
+            assert np.array_equal(u8, ref_u8), f"u8 canvas differs from the oracle: {tag}"
+            assert np.array_equal(fl.view(np.uint32), dense_f.view(np.uint32)) and np.array_equal(u8, dense_u8), f"differs from the dense call: {tag}"
+    finally:
+        plan.close()
 
 
 def _merge_case(rng, f32):
@@ -480,10 +535,17 @@ def test_rgb2gray_resize_and_histogram_views(ctx, rng, k, fill):
 
 
 # ---- colour correction ----------------------------------------------------------------------------------------------------
+# radius 8 keeps its ids; 5 and 12 are an odd radius and an even one above the 64 KiB LDS threshold of the generic kernels
+# (k_cc_coeff / k_cc_apply, k_gf_box / k_gf_out), which the radius-8 cases never launch
+CC_CASES = [pytest.param(0, 8, id="lut"), pytest.param(1, 8, id="guided"), pytest.param(2, 8, id="ximgproc")] + \
+           [pytest.param(lf, r, id=f"{name}-r{r}") for lf, name in ((1, "guided"), (2, "ximgproc")) for r in (5, 12)]
+
+
 @FILL
-@pytest.mark.parametrize("local_filter", [0, 1, 2], ids=["lut", "guided", "ximgproc"])
-def test_color_correct_views(ctx, rng, local_filter, fill):
-    """Out of place and in place; an integer table (the fused kernels out of place) and a float table (branches 0 and 1)."""
+@pytest.mark.parametrize("local_filter,radius", CC_CASES)
+def test_color_correct_views(ctx, rng, local_filter, radius, fill):
+    """Out of place and in place; an integer table (the fused kernels out of place at radius 8) and a float table (branches
+    0 and 1; branch 2 away from radius 8, where no kernel depends on the table's class)."""
     h, w = 46, 75
     img = _scene(rng, h, w, 3)
     src = img.astype(np.float32)
@@ -491,22 +553,22 @@ def test_color_correct_views(ctx, rng, local_filter, fill):
     lut_i[1] = np.clip(np.arange(256) * 0.5 + 40, 0, 255).astype(np.int32)
     lut_f = (np.arange(256, dtype=np.float32)[None, :] - np.float32(140.25)) * np.float32(1.5) + np.float32(100.5)
     lut_f = np.ascontiguousarray(np.repeat(lut_f, 3, 0))
-    for lut in ((lut_i,) if local_filter == 2 else (lut_i, lut_f)):
+    for lut in ((lut_i,) if local_filter == 2 and radius == 8 else (lut_i, lut_f)):
         corrected = np.stack([lut[c][img[..., c]] for c in range(3)], axis=-1).astype(np.float32)
         if local_filter == 0:
             want = np.clip(corrected, 0, 255).astype(np.uint8)
         else:
             f = onp.simple_guided_filter if local_filter == 1 else onp.guided_filter_ximgproc
-            want = np.clip(f(corrected, src, 8, 0.01), 0, 255).astype(np.uint8)
+            want = np.clip(f(corrected, src, radius, 0.01), 0, 255).astype(np.uint8)
         for k in range(NL):
             pi, ip, ist, itag = _in(ctx, img, k, fill)
             po, op, ost, otag = _out(ctx, h, w * 3, _ok(k), fill)
-            ctx.color_correct_u8(ip, ist, h, w, 3, lut, local_filter, 8, 0.01, op, ost)
-            what = f"sr_color_correct_u8 filter {local_filter} {itag} -> {otag}"
+            ctx.color_correct_u8(ip, ist, h, w, 3, lut, local_filter, radius, 0.01, op, ost)
+            what = f"sr_color_correct_u8 filter {local_filter} radius {radius} {itag} -> {otag}"
             got = V.check_guard(ctx, po, np.uint8, (h, w, 3), what=what)
             assert np.array_equal(got, want), (what, int((got != want).sum()))
-            ctx.color_correct_u8(ip, ist, h, w, 3, lut, local_filter, 8, 0.01, ip, ist)
-            what = f"sr_color_correct_u8 filter {local_filter} in place {itag}"
+            ctx.color_correct_u8(ip, ist, h, w, 3, lut, local_filter, radius, 0.01, ip, ist)
+            what = f"sr_color_correct_u8 filter {local_filter} radius {radius} in place {itag}"
             got = V.check_guard(ctx, pi, np.uint8, (h, w, 3), what=what)
             assert np.array_equal(got, want), (what, int((got != want).sum()))
             _free(pi, po)
