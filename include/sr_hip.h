@@ -1200,7 +1200,7 @@ SR_API int sr_rcan_attention_f32(sr_ctx *ctx, const float *d_x, int64_t plane_st
  * softmax does); the a v sum is an fmaf chain from +0 over j ascending.  No atomics.  Equal inputs give equal bits.
  * Anything outside the ranges above (a non-finite mean or range, range 0) is SR_ERR_UNSUPPORTED, decided on the host before any
  * device call.  Out of scope: window sizes other than 8, resi_connection '3conv', the absolute position embedding, the JPEG /
- * denoising variants (no upsampler), Swin2SR, fp16 / bf16.
+ * denoising variants (no upsampler), fp16 / bf16; Swin2SR is a backend of its own (below).
  * Shifted windows let a pixel see farther with every layer pair, so the trunk (steps 1 .. 4) runs on the padded image in ONE
  * piece: four planar fp32 buffers of Cp = C rounded up to 64 planes of P0 = Hp Wp floats (h / f, the RSTB input, x, LN / attention
  * output) and one of Qp = max(3 C, n_hidden each rounded up to 64) planes (qkv, then the MLP's hidden tensor): 4 (4 Cp + Qp)
@@ -1366,6 +1366,90 @@ SR_API int sr_hat_oca_f32(sr_ctx *ctx, const float *d_qkv, int64_t plane_stride,
                           int wp, const float *h_table, const int *h_index, float *d_out, int64_t out_plane_stride,
                           int64_t out_row_stride);
 
+/* ---- local SR backend: Swin2SR, SwinV2 cosine attention and post-norm (csrc/sr_swin2sr.hip, csrc/sr_swin2sr_host.cpp) ---------
+ * Swin2SR (Conde et al., "Swin2SR: SwinV2 Transformer for Compressed Image Super-Resolution and Restoration", ECCVW 2022) with
+ * resi_connection '1conv', no absolute position embedding, patch size 1, window 8, shift 4 on odd layers, as the `transformers`
+ * package's Swin2SRForImageSuperResolution computes it (modeling_swin2sr.py; the official repository's names in brackets).  The
+ * package layout is held against `transformers` 5.15.0 (tests/golden/swin2sr_*.npz); the official layout and its mask value rest
+ * on the restatement (tests/_swin2sr_ref.py); no published checkpoint was ever run.  Everything is fp32 except the LayerNorm
+ * statistics (float64), as SwinIR.  A model is an sr_swin2sr_desc: SwinIR's fields with SwinIR's ranges (C <= 256 and a multiple
+ * of 4, d = C / n_heads <= 32, n_hidden <= 4 C, L <= 12 stages, D <= 12 layers per stage, the three upsamplers
+ * SR_SWINIR_PIXELSHUFFLE / _PIXELSHUFFLEDIRECT / _NEAREST_CONV at SwinIR's scales) and mask_value, finite.
+ *  1. input      SwinIR's step 1 unchanged: the u8 image extended on the bottom and right to multiples of 8 by SYMMETRIC
+ *                reflection (the package's image processor pads 'symmetric', the official test script by flip; the model's own
+ *                'reflect' pad is then a no-op), x[c] = (u8 / 255 - mean[c]) * range.  Defaults: the DIV2K mean, range 1.
+ *  2. head       h = conv3x3(x)  (first_convolution / conv_first).
+ *  3. embedding  e = P_0 h + b, a 1 x 1 convolution C -> C (embeddings.patch_embeddings.projection / patch_embed.proj; SwinIR has
+ *                none);  r_0 = LN(e)  (embeddings.patch_embeddings.layernorm / patch_embed.norm).
+ *  4. stage i = 1 .. L (RSTB):  x = r_{i-1};  D layers;  r_i = P_i(conv3x3_i(x)) + r_{i-1}, P_i a 1 x 1 convolution with bias
+ *                (stages.i.patch_embed.projection / layers.i.patch_embed.proj), the skip one fp32 add after the sum.
+ *                Layer j = 0 .. D - 1, shift = 0 for even j, 4 for odd j:
+ *                    [q k v] = W x + b on x ITSELF (there is no pre-norm); the k third has no bias (q_bias, 0, v_bias): a k bias
+ *                          that is not zero is refused; q is NOT scaled by d^-1/2;
+ *                    cosine window attention, per window and head (windows, roll, regions and rel(i, j) as SwinIR's):
+ *                          ss = sum_dd q[dd]^2, an fmaf chain over dd ascending from +0;  n = sqrtf(ss);
+ *                          qn[dd] = q[dd] / fmaxf(n, 1e-12f)  (a division);  k likewise;
+ *                          a[i][j] = ((sum_dd qn_i[dd] kn_j[dd]) * scale_h  +  B[head][rel(i, j)])  +  (region(i) != region(j) ?
+ *                          mask_value : nothing)  -- the sum an fmaf chain from +0, the scale one multiply, then two adds;
+ *                          exact maximum, e_j = expf(a - max), the sum over keys ascending, p = e / sum, then the p v fmaf
+ *                          chain: SwinIR's order;
+ *                    x = x + LN1(proj(o) + b)   (layernorm_before / norm1, applied AFTER the attention);
+ *                    x = x + LN2(fc2(gelu(fc1(x))))   (layernorm_after / norm2).
+ *                LayerNorm as SwinIR's (eps 1e-5, float64);  LN(.) is rounded to fp32, then one fp32 add.
+ *  5. long skip  f = conv_after_body(LN(r_L)) + h  (the skip is h, not e).
+ *  6. reconstruction and output: SwinIR's steps 5 and 6 unchanged (pixelshuffle with 64 middle features and LeakyReLU 0.01).
+ * Host-side tables (sr_swin2sr_cpb_bias; float64 from the fp32 weights, rounded once to fp32):
+ *     scale_h = (float)exp(min((double)logit_scale_h, ln 100));
+ *     B[t][head], t = (dy + 7) * 15 + dx + 7:  c = (g(8 dy / 7), g(8 dx / 7)), g(v) = sign(v) log2(|v| + 1) / 3;
+ *     u = relu(W1 c + b1)  (Linear(2, 512));  z = W2 u  (Linear(512, heads), no bias; sums ascending);  B = 16 / (1 + exp(-z)).
+ *     The package evaluates this in fp32; the distance is rounding-level.  The state's relative_coords_table,
+ *     relative_position_index and attn_mask buffers are recomputed, never read.
+ * mask_value.  The package adds the shifted-window mask twice, so its effective value is -200; the official code adds -100 once.
+ * sr_network.parse_swin2sr_state sets -200 for the package's key layout and -100 for the official one (a 0-d `mask_value` entry
+ * of a .npz overrides it).  With scale_h up to 100 a masked score can lie 200 + 16 above an unmasked one before the mask, so
+ * the two values are not always equivalent.
+ * The package's own model fails on a side that is not a multiple of 8 (its patch_unembed is given the unpadded size): at such
+ * sizes the result is defined by step 1 alone.
+ * Buffers: SwinIR's five (qkv X -> Q; attention -> A; proj A -> Q's first Cp planes; LN + skip -> X; fc1 X -> Q; fc2 Q -> A;
+ * LN + skip -> X), the same bytes per pixel, SR_SWIN2SR_TRUNK_CAP = SR_SWINIR_TRUNK_CAP, the same tail phase.
+ * sr_swin2sr_create: h_w[k] / h_b[k] = the tables in forward order (dense fp32):
+ *     first_convolution [C][3][3][3];  P_0 [C][C], [C];  the embedding LayerNorm (gamma, beta);
+ *     per stage, per layer:  qkv [3 C][C], [3 C] (rows q, k, v; bias entries C .. 2 C - 1 zero);  logit_scale [heads] (no bias);
+ *         cpb_mlp.0 [512][2], [512];  cpb_mlp.2 [heads][512] (no bias);  proj [C][C], [C];  norm1;  fc1 [hidden][C];  fc2 [C][hidden];
+ *         norm2;   then the stage's conv [C][C][3][3] and P_i [C][C], [C];
+ *     norm;  conv_after_body;  the reconstruction's tables as sr_swinir_create's.  n_tables = 3 + L (9 D + 2) + 2 + (3 or 4 | 1 | 5).
+ * sr_swin2sr_plan: as sr_swinir_plan.  sr_swin2sr_cpb_bias (host only): table [225][heads] and / or scale [heads] (either output
+ * may be NULL, and with it the inputs only it needs).  sr_swin2sr_attention_f32 (inspection; synchronous): the attention above
+ * on a planar qkv tensor (3 C planes of hp x wp), h_table [225][heads] = B, h_scale [heads], into the C planes of d_out.
+ * sr_swin2sr_layernorm_add_f32 (inspection; synchronous): d_out = d_skip + (float)LN(d_x); d_out may be d_skip itself.
+ * Errors as SwinIR's; SR_ERR_UNSUPPORTED also for a non-finite mask_value or logit_scale and for a k bias that is not zero.  Out
+ * of scope, refused by name: upsampler pixelshuffle_aux, no upsampler (JPEG / denoising), '3conv', the absolute position
+ * embedding, windows other than 8, unequal depths or head counts between stages, fp16 / bf16 weights. */
+#define SR_SWIN2SR_TRUNK_CAP SR_SWINIR_TRUNK_CAP
+typedef struct sr_swin2sr_desc {
+    int n_feat, n_heads, n_hidden, n_groups, depth, scale, upsampler;
+    float mean[3], range, mask_value;
+} sr_swin2sr_desc;
+typedef struct sr_swin2sr_model sr_swin2sr_model;
+SR_API int sr_swin2sr_create(sr_ctx *ctx, const sr_swin2sr_desc *desc, const float *const *h_w, const float *const *h_b, int n_tables,
+                             sr_swin2sr_model **out);
+SR_API int sr_swin2sr_destroy(sr_swin2sr_model *model);
+SR_API int sr_swin2sr_plan(const sr_swin2sr_desc *desc, int h, int w, int tail, int *hp, int *wp, int *halo, int *n_tail_tiles,
+                           size_t *workspace_bytes);
+SR_API int sr_swin2sr_cpb_bias(const float *h_w1, const float *h_b1, const float *h_w2, const float *h_logit_scale, int n_heads,
+                               float *h_table, float *h_scale);
+SR_API int sr_swin2sr_u8(sr_swin2sr_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                         int64_t dst_stride, int tail);
+SR_API int sr_swin2sr_f32(sr_swin2sr_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                          int64_t dst_stride, int tail);
+SR_API int sr_swin2sr_fill_workspace(sr_swin2sr_model *model, int h, int w, int tail, int byte);
+SR_API int sr_swin2sr_attention_f32(sr_ctx *ctx, const float *d_qkv, int64_t plane_stride, int64_t row_stride, int n_feat, int n_heads,
+                                    int hp, int wp, int shift, const float *h_table, const float *h_scale, float mask_value,
+                                    float *d_out, int64_t out_plane_stride, int64_t out_row_stride);
+SR_API int sr_swin2sr_layernorm_add_f32(sr_ctx *ctx, const float *d_x, int64_t plane_stride, int64_t row_stride, int n_feat, int h, int w,
+                                        const float *h_gamma, const float *h_beta, const float *d_skip, int64_t skip_plane_stride,
+                                        int64_t skip_row_stride, float *d_out, int64_t out_plane_stride, int64_t out_row_stride);
+
 /* ---- geometric self-ensemble of the local SR backends (csrc/sr_ensemble.hip) ------------------------------------------------
  * The "+" results of the SR literature (EDSR+, RCAN+: Timofte et al., Lim et al.): the network runs on the eight flips and
  * rotations of the input, each output is mapped back and the eight are averaged.  No new weights; the forwards are the
@@ -1431,6 +1515,11 @@ SR_API int sr_hat_ens_u8(sr_hat_model *model, const uint8_t *d_src, int64_t src_
                          int64_t dst_stride, int tail, int mask);
 SR_API int sr_hat_ens_f32(sr_hat_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
                           int64_t dst_stride, int tail, int mask);
+/* Swin2SR+: as SwinIR+. */
+SR_API int sr_swin2sr_ens_u8(sr_swin2sr_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, uint8_t *d_dst,
+                             int64_t dst_stride, int tail, int mask);
+SR_API int sr_swin2sr_ens_f32(sr_swin2sr_model *model, const uint8_t *d_src, int64_t src_stride, int h, int w, float *d_dst,
+                              int64_t dst_stride, int tail, int mask);
 
 #ifdef __cplusplus
 }

@@ -133,6 +133,12 @@ class SwinirDesc(C.Structure):
                 ("scale", C.c_int), ("upsampler", C.c_int), ("mean", C.c_float * 3), ("range", C.c_float)]
 
 
+class Swin2srDesc(C.Structure):
+    """sr_swin2sr_desc (include/sr_hip.h)."""
+    _fields_ = [("n_feat", C.c_int), ("n_heads", C.c_int), ("n_hidden", C.c_int), ("n_groups", C.c_int), ("depth", C.c_int),
+                ("scale", C.c_int), ("upsampler", C.c_int), ("mean", C.c_float * 3), ("range", C.c_float), ("mask_value", C.c_float)]
+
+
 class HatDesc(C.Structure):
     """sr_hat_desc (include/sr_hip.h)."""
     _fields_ = [("n_feat", C.c_int), ("n_heads", C.c_int), ("n_hidden", C.c_int), ("n_mid", C.c_int), ("n_squeeze", C.c_int),
@@ -348,6 +354,17 @@ SIGNATURES = {
     "sr_hat_oca_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _i64]),
     "sr_hat_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
     "sr_hat_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_swin2sr_create": (_i, [_vp, C.POINTER(Swin2srDesc), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_vp)]),
+    "sr_swin2sr_destroy": (_i, [_vp]),
+    "sr_swin2sr_plan": (_i, [C.POINTER(Swin2srDesc), _i, _i, _i, _pi, _pi, _pi, _pi, C.POINTER(_sz)]),
+    "sr_swin2sr_cpb_bias": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "sr_swin2sr_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_swin2sr_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i]),
+    "sr_swin2sr_fill_workspace": (_i, [_vp, _i, _i, _i, _i]),
+    "sr_swin2sr_attention_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i64, _i64]),
+    "sr_swin2sr_layernorm_add_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64]),
+    "sr_swin2sr_ens_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
+    "sr_swin2sr_ens_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i]),
 }
 
 
@@ -2521,6 +2538,130 @@ def hat_oca(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat: int, n_
     _sw_attention("sr_hat_oca_f32", ctx, d_qkv, plane_stride, row_stride, n_feat, n_heads, hp, wp,
                   (t.ctypes.data_as(C.c_void_p), None if idx is None else idx.ctypes.data_as(C.c_void_p)), d_out, out_plane_stride,
                   out_row_stride)
+
+
+# ------------------------------------------------------------------------------------------
+# local SR network, Swin2SR (sr_swin2sr_*): sr_network.Swin2SRNet parses `transformers` / official state dicts into these arrays
+# ------------------------------------------------------------------------------------------
+SWIN2SR_CPB_HIDDEN = 512
+SWIN2SR_MASK_PACKAGE, SWIN2SR_MASK_OFFICIAL = -200.0, -100.0     # the package adds the shifted-window mask twice
+
+
+def swin2sr_desc(n_feat: int, n_heads: int, n_hidden: int, n_groups: int, depth: int, scale: int, upsampler="pixelshuffle",
+                 mean=(0.0, 0.0, 0.0), range: float = 1.0, mask_value: float = SWIN2SR_MASK_PACKAGE) -> Swin2srDesc:  # noqa: A002
+    mean = [float(v) for v in np.asarray(mean, dtype=np.float64).reshape(-1)]
+    if len(mean) != 3:
+        raise ValueError(f"mean holds 3 values, got {len(mean)}")
+    kind = SWINIR_UPSAMPLERS.get(upsampler, upsampler)
+    return Swin2srDesc(int(n_feat), int(n_heads), int(n_hidden), int(n_groups), int(depth), int(scale), int(kind), (C.c_float * 3)(*mean),
+                       float(range), float(mask_value))
+
+
+def _s2_tail_names(desc) -> List[str]:
+    if desc.upsampler == 0:
+        ups = ["upsample.upsample.convolution"] if desc.scale == 3 else [f"upsample.upsample.convolution_{k}" for k in (0, 1)[:desc.scale // 2]]
+        return ["upsample.conv_before_upsample"] + ups + ["upsample.final_convolution"]
+    if desc.upsampler == 1:
+        return ["upsample.conv"]
+    return ["upsample.conv_before_upsample", "upsample.conv_up1", "upsample.conv_up2", "upsample.conv_hr", "upsample.final_convolution"]
+
+
+def swin2sr_table_names(desc: Swin2srDesc) -> List[str]:
+    """The `transformers` package's name of every table in sr_swin2sr_create's order (weight key = name + '.weight', bias key =
+    name + '.bias'), except: the qkv table is the package's query / key / value stacked (named '<...>.attention.self.qkv'), and
+    the logit_scale table's key is the name itself."""
+    names = ["swin2sr.first_convolution", "swin2sr.embeddings.patch_embeddings.projection", "swin2sr.embeddings.patch_embeddings.layernorm"]
+    for i in range(desc.n_groups):
+        for j in range(desc.depth):
+            b = f"swin2sr.encoder.stages.{i}.layers.{j}"
+            a = f"{b}.attention.self"
+            names += [f"{a}.qkv", f"{a}.logit_scale", f"{a}.continuous_position_bias_mlp.0", f"{a}.continuous_position_bias_mlp.2",
+                      f"{b}.attention.output.dense", f"{b}.layernorm_before", f"{b}.intermediate.dense", f"{b}.output.dense",
+                      f"{b}.layernorm_after"]
+        names += [f"swin2sr.encoder.stages.{i}.conv", f"swin2sr.encoder.stages.{i}.patch_embed.projection"]
+    return names + ["swin2sr.layernorm", "swin2sr.conv_after_body"] + _s2_tail_names(desc)
+
+
+def swin2sr_table_shapes(desc: Swin2srDesc) -> List[Tuple[tuple, Optional[tuple]]]:
+    """(weight shape, bias shape) of every table in sr_swin2sr_create's order; logit_scale and cpb_mlp.2 have no bias (None).  The
+    1 x 1 projections are (out, in); (out, in, 1, 1) arrays are accepted for them."""
+    Cn, nh, hid, s, conv, ln = desc.n_feat, desc.n_heads, desc.n_hidden, desc.scale, _sw_conv, ((desc.n_feat,), (desc.n_feat,))
+    lin = ((Cn, Cn), (Cn,))
+    layer = [((3 * Cn, Cn), (3 * Cn,)), ((nh,), None), ((SWIN2SR_CPB_HIDDEN, 2), (SWIN2SR_CPB_HIDDEN,)), ((nh, SWIN2SR_CPB_HIDDEN), None), lin, ln,
+             ((hid, Cn), (hid,)), ((Cn, hid), (Cn,)), ln]
+    shapes = [conv(Cn, 3), lin, ln] + (layer * desc.depth + [conv(Cn, Cn), lin]) * desc.n_groups + [ln, conv(Cn, Cn)]
+    if desc.upsampler == 0:
+        shapes += _sw_shuffle_tail(Cn, s)[1]
+    elif desc.upsampler == 1:
+        shapes += [conv(3 * s * s, Cn)]
+    else:
+        shapes += [conv(64, Cn), conv(64, 64), conv(64, 64), conv(64, 64), conv(3, 64)]
+    return shapes
+
+
+def swin2sr_plan(desc: Swin2srDesc, h: int, w: int, tail: int = 0) -> Tuple[int, int, int, int, int]:
+    """sr_swin2sr_plan (host only) -> (padded rows, padded columns, the tail's halo, tail sub-pieces, workspace bytes)."""
+    return _sw_plan("sr_swin2sr_plan", desc, h, w, tail)
+
+
+def swin2sr_cpb_bias(w1, b1, w2, logit_scale=None):
+    """sr_swin2sr_cpb_bias (host only): the continuous position bias 16 sigmoid(cpb_mlp(coords)) as a (225, heads) fp32 table
+    (float64 from the fp32 weights, rounded once); with ``logit_scale`` (heads values) -> (table, scale), scale[h] =
+    (float)exp(min(logit_scale[h], ln 100))."""
+    w1, b1, w2 = (np.ascontiguousarray(a, dtype=np.float32) for a in (w1, b1, w2))
+    if w2.ndim != 2 or w2.shape[1] != SWIN2SR_CPB_HIDDEN or w1.shape != (SWIN2SR_CPB_HIDDEN, 2) or b1.reshape(-1).shape != (SWIN2SR_CPB_HIDDEN,):
+        raise ValueError(f"the cpb MLP is (512, 2), (512,), (heads, 512), got {w1.shape}, {b1.shape}, {w2.shape}")
+    heads = int(w2.shape[0])
+    table = np.empty(((2 * SWINIR_WINDOW - 1) ** 2, heads), np.float32)
+    ls = sc = None
+    if logit_scale is not None:
+        ls = np.ascontiguousarray(logit_scale, dtype=np.float32).reshape(-1)
+        if ls.size != heads:
+            raise ValueError(f"logit_scale holds {ls.size} values, expected {heads}")
+        sc = np.empty(heads, np.float32)
+    _check_unsupported(load().sr_swin2sr_cpb_bias(w1.ctypes.data_as(C.c_void_p), b1.ctypes.data_as(C.c_void_p), w2.ctypes.data_as(C.c_void_p),
+                                                  None if ls is None else ls.ctypes.data_as(C.c_void_p), heads,
+                                                  table.ctypes.data_as(C.c_void_p), None if sc is None else sc.ctypes.data_as(C.c_void_p)))
+    return table if sc is None else (table, sc)
+
+
+class Swin2srModel(_SwModel):
+    """sr_swin2sr_model: a Swin2SR resident on the GPU.  weights / biases: one fp32 array each per table in forward order
+    (swin2sr_table_shapes / swin2sr_table_names); the bias entries of logit_scale and cpb_mlp.2 are ignored (None is fine).  The
+    trunk is one piece, so the forwards take ``tail`` alone."""
+    _kind, _name, _conv1x1 = "swin2sr", "Swin2SR", True
+    _shapes, _plan = staticmethod(swin2sr_table_shapes), staticmethod(swin2sr_plan)
+
+    def __init__(self, ctx: Context, desc: Swin2srDesc, weights, biases):
+        ws, bs = self._tables(desc, weights, biases)
+        self._create(ctx, (C.byref(desc),), ws, bs, count=True)
+
+
+def swin2sr_attention(ctx, d_qkv: int, plane_stride: int, row_stride: int, n_feat: int, n_heads: int, hp: int, wp: int, shift: int, table,
+                      scale, mask_value: float, d_out: int, out_plane_stride: int, out_row_stride: int):
+    """sr_swin2sr_attention_f32: the cosine window attention (before proj) on a planar qkv tensor of 3 C planes; ``table``: the
+    (225, heads) position bias (swin2sr_cpb_bias); ``scale``: heads values (the clamped exp of logit_scale); into the C planes of
+    d_out.  Synchronous."""
+    t = _sw_bias_table(table, (2 * SWINIR_WINDOW - 1) ** 2, n_heads)
+    sc = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+    if 1 <= int(n_heads) <= 256 and sc.size != int(n_heads):
+        raise ValueError(f"scale holds {sc.size} values, expected {int(n_heads)}")
+    _sw_attention("sr_swin2sr_attention_f32", ctx, d_qkv, plane_stride, row_stride, n_feat, n_heads, hp, wp,
+                  (int(shift), t.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), C.c_float(float(mask_value))), d_out,
+                  out_plane_stride, out_row_stride)
+
+
+def swin2sr_layernorm_add(ctx, d_x: int, plane_stride: int, row_stride: int, n_feat: int, h: int, w: int, gamma, beta, d_skip: int,
+                          skip_plane_stride: int, skip_row_stride: int, d_out: int, out_plane_stride: int, out_row_stride: int):
+    """sr_swin2sr_layernorm_add_f32: d_out = d_skip + (float)LayerNorm(d_x) over the channels of planar fp32 tensors on the device;
+    d_out may be d_skip itself.  Synchronous."""
+    g, b = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (gamma, beta))
+    if 1 <= int(n_feat) <= 256 and (g.size != n_feat or b.size != n_feat):
+        raise ValueError(f"gamma / beta hold {g.size} / {b.size} values, expected {n_feat}")
+    _check_unsupported(load().sr_swin2sr_layernorm_add_f32(_ctx_handle(ctx), C.c_void_p(d_x), int(plane_stride), int(row_stride), int(n_feat),
+                                                           int(h), int(w), g.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
+                                                           C.c_void_p(d_skip), int(skip_plane_stride), int(skip_row_stride), C.c_void_p(d_out),
+                                                           int(out_plane_stride), int(out_row_stride)))
 
 
 _default_ctx = {}

@@ -290,6 +290,7 @@ int ht_oca_index_of(const char *who, const int *h_index, int *idx)
 struct sr_hat_model : SwModelBase {            // trunk[4] is U (the CAB's output); tbuf and red are in use
     sr_hat_desc d{};
     static constexpr bool SHUFFLE_ONLY = true;
+    static constexpr bool PROJECTED = false;
     static int check_desc(const char *who, const sr_hat_desc *desc) { return ht_check_desc(who, desc); }
     static std::vector<SwTable> table_list(const sr_hat_desc &desc) { return ht_tables(desc); }
     static bool bias_table(int kind) { return kind == SW_T_RPB || kind == HT_T_RPB_OCA; }

@@ -1,6 +1,7 @@
-// sr_swin_common.h -- what the Swin-trunk backends (sr_swinir.hip, sr_hat.hip) share on the device side: the head from a padded
-// u8 image, the LayerNorm, the linear layers and the 3 x 3 convolutions (sr_conv_mfma.h's mainloop behind their epilogues) and
-// the weight arrangement -- and, below them, the frame of a family around its own blocks: the model base and its workspace
+// sr_swin_common.h -- what the Swin-trunk backends (sr_swinir.hip, sr_hat.hip, sr_swin2sr.hip) share on the device side: the
+// symmetric reflection (SwinIR, Swin2SR), the head from a padded u8 image, the LayerNorm -- and the LayerNorm behind a skip
+// (Swin2SR) --, the linear layers and the 3 x 3 convolutions (sr_conv_mfma.h's mainloop behind their epilogues) and the weight
+// arrangement -- and, below them, the frame of a family around its own blocks: the model base and its workspace
 // (SwModelBase, sw_reserve, sw_fill_workspace), the trunk phase's steps (SwTrunk), the forward (sw_forward_frame), the tail phase
 // (sw_run_tail), the create (sw_create, sw_arrange_shared), the ensemble wrapper, the bias gather, the launch by head width and
 // the inspection calls of the attention kernels.  A family keeps its kernels, the body of one group, its own table kinds and
@@ -39,6 +40,24 @@ __global__ __launch_bounds__(256) void k_sw_head(const unsigned char *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Symmetric reflection of the u8 image to Hp x Wp (dense, 3 Wp bytes per row): padded index i reads m = i mod 2 n,
+// m < n ? m : 2 n - 1 - m (np.pad mode 'symmetric': the edge pixel repeated, period 2 n).  One thread per output byte.  A
+// template (launched as k_sw_reflect<>) so that only a unit that launches it carries it: SwinIR and Swin2SR, not HAT.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename Px = unsigned char>
+__global__ __launch_bounds__(256) void k_sw_reflect(const Px *__restrict__ img, long long stride, int h, int w, Px *__restrict__ out, int hp,
+                                                    int wp)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)hp * wp * 3) return;
+    const int c = (int)(i % 3), x = (int)((i / 3) % wp), y = (int)(i / (3LL * wp));
+    int my = y % (2 * h), mx = x % (2 * w);
+    if (my >= h) my = 2 * h - 1 - my;
+    if (mx >= w) mx = 2 * w - 1 - mx;
+    out[i] = img[(size_t)my * stride + (size_t)mx * 3 + c];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // LayerNorm over the C channels of every token of a planar tensor, one thread per token (coalesced across tokens):
 //   mean = (sum_c (double)x[c]) / C;  var = (sum_c ((double)x[c] - mean)^2) / C   (float64, channels ascending, two passes,
 //   the square rounded before it is added);  y[c] = (float)(((double)x[c] - mean) * (1 / sqrt(var + 1e-5)) * gamma[c] + beta[c])
@@ -63,6 +82,37 @@ __global__ __launch_bounds__(256) void k_sw_layernorm(const float *__restrict__ 
     }
     const double rstd = 1.0 / sqrt(v / (double)C + 1e-5);
     for (int c = 0; c < C; ++c) o[(size_t)c * oplane] = (float)(((double)p[(size_t)c * plane] - mean) * rstd * (double)gamma[c] + (double)beta[c]);
+    for (int c = C; c < Cp; ++c) o[(size_t)c * oplane] = 0.0f;
+}
+
+// The same LayerNorm behind a skip (Swin2SR's post-norm): out[c] = skip[c] + (float)LN(x)[c] -- LN(.) rounded to fp32, then one
+// fp32 add.  out may be skip itself (a thread reads exactly the element it then writes); x must be neither.  Planes C .. Cp - 1
+// of out get +0.  A template (launched as k_sw_layernorm_add<>) so that only a unit that launches it carries it.
+template <typename Skip = float>
+__global__ __launch_bounds__(256) void k_sw_layernorm_add(const float *__restrict__ x, long long plane, long long pitch, int rows, int cols, int C,
+                                                          int Cp, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                          const Skip *skip, long long splane, long long spitch, float *out,
+                                                          long long oplane, long long opitch)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)rows * cols) return;
+    const int y = (int)(idx / cols), xx = (int)(idx % cols);
+    const float *p = x + (size_t)y * pitch + xx;
+    const Skip *sk = skip + (size_t)y * spitch + xx;
+    float *o = out + (size_t)y * opitch + xx;
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += (double)p[(size_t)c * plane];
+    const double mean = s / (double)C;
+    double v = 0.0;
+    for (int c = 0; c < C; ++c) {
+        const double d = (double)p[(size_t)c * plane] - mean;
+        v += d * d;
+    }
+    const double rstd = 1.0 / sqrt(v / (double)C + 1e-5);
+    for (int c = 0; c < C; ++c) {
+        const float ln = (float)(((double)p[(size_t)c * plane] - mean) * rstd * (double)gamma[c] + (double)beta[c]);
+        o[(size_t)c * oplane] = sk[(size_t)c * splane] + ln;
+    }
     for (int c = C; c < Cp; ++c) o[(size_t)c * oplane] = 0.0f;
 }
 
@@ -257,6 +307,7 @@ inline int sw_check_view(const char *who, const void *p, int64_t plane_stride, i
 // create, the ensemble and the inspection calls.  A family's model derives from SwModelBase and adds
 //   d                                       its description (n_feat, n_heads, n_hidden, n_groups, depth, scale, mean, range)
 //   SHUFFLE_ONLY                            whether its reconstruction is always the pixelshuffle one
+//   PROJECTED                               whether a 1 x 1 projection follows the head and every group's convolution (Swin2SR)
 //   check_desc, table_list, bias_table      (static) its description check, its tables, the kinds whose bias entry is ignored
 //   geometry, tail_steps                    its plan
 // Everything is resolved at compile time: no std::function and no virtual call on the launch path.
@@ -347,6 +398,14 @@ struct SwTrunk {
     {
         ProfScope ps(ctx, nm.ln);
         sw_launch_layernorm(st, in, L.plane, L.pitch, hp, wp, C, Cp, m->w(k), m->b(k), out, L.plane, L.pitch);
+    }
+    template <typename Kernel>
+    void conv_with(Kernel kernel, float *in, int k, float *out, const float *skip) const   // a C -> C convolution behind another epilogue
+    {
+        ProfScope ps(ctx, nm.conv);
+        SwEpi e = ep;
+        e.skip = skip;
+        launch_conv(kernel, st, ten(in), hp, wp, Cp, Cp / 64, m->w(k), m->b(k), out, L.plane, L.pitch, 0, 0, hp, wp, e);
     }
     void qkv(int k) const { lin(k_sw_lin<SL_QKV>, Ab, Cp, k, qkvp, Qb, nullptr); }            // A -> Q
     void proj(int k, const float *x) const { lin(k_sw_lin<SL_ADD>, Ab, Cp, k, Cp, Xb, x); }   // X = x + proj(A)
@@ -450,10 +509,20 @@ int sw_forward_frame(const char *fn, LiveSet &live, Model *m, const SwNames &nm,
     T.Ab = m->trunk[3].template as<float>(), T.Qb = m->qbuf.template as<float>();
     T.head(reflect, d_src, src_stride, h, w);
     int k = 1;
-    T.norm(T.Hb, k++, T.Rb);
+    if constexpr (Model::PROJECTED) {                      // Swin2SR: e = P_0 h + b, a 1 x 1 convolution, ahead of the first LayerNorm
+        T.lin(k_sw_lin<SL_PLAIN>, T.Hb, T.Cp, k++, T.Cp, T.Ab, nullptr);
+        T.norm(T.Ab, k++, T.Rb);
+    } else {
+        T.norm(T.Hb, k++, T.Rb);
+    }
     for (int gi = 0; gi < D.n_groups; ++gi) {
         float *x = group(T, g, k);
-        T.conv(x, k++, T.Rb, T.Rb);                        // in place over the group's input
+        if constexpr (Model::PROJECTED) {                  // r = P_i(conv(x)) + r: the convolution into A, the projection in place over r
+            T.conv_with(k_sw_conv<2, SW_PLAIN>, x, k++, T.Ab, nullptr);
+            T.lin(k_sw_lin<SL_ADD>, T.Ab, T.Cp, k++, T.Cp, T.Rb, T.Rb);
+        } else {
+            T.conv(x, k++, T.Rb, T.Rb);                    // in place over the group's input
+        }
     }
     T.norm(T.Rb, k++, T.Ab);
     T.conv(T.Ab, k++, T.Hb, T.Hb);                         // f = conv_after_body(.) + h, in place over h

@@ -78,6 +78,8 @@ int sw_check_affine(const char *who, const char *what, const float *mean, float 
 void sw_emit_attention(std::vector<SwTable> &t, int C, int heads, int rpb_kind, int rpb_rows);
 void sw_emit_mlp(std::vector<SwTable> &t, int C, int hidden);
 void sw_emit_shuffle_tail(std::vector<SwTable> &t, int C, int s);
+// The tables of any of the three reconstructions (SR_SWINIR_PIXELSHUFFLE / _PIXELSHUFFLEDIRECT / _NEAREST_CONV), appended to t.
+void sw_emit_tail(std::vector<SwTable> &t, int C, int s, int upsampler);
 std::vector<SwStep> sw_shuffle_steps(int s);
 int sw_check_desc(const char *who, const sr_swinir_desc *d);
 std::vector<SwTable> sw_tables(const sr_swinir_desc &d);

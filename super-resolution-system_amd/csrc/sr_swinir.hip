@@ -48,10 +48,10 @@
 // keys ascending from +0, p_j = e_j / sum (the division comes BEFORE the a v sum, as torch's softmax), and the a v sum is an
 // fmaf chain over keys ascending from +0.  No atomics.  Nothing depends on tail.  Equal inputs give equal bits.
 //
-// The head, the LayerNorm, the linear layers, the 3 x 3 convolutions (k_sw_head, k_sw_layernorm, k_sw_lin, k_sw_conv), the
-// weight arrangement and the whole frame around a family's blocks (the model's buffers, the trunk and the tail phase, the
-// create, the ensemble, the inspection calls) are sr_swin_common.h, shared with sr_hat.hip; this file keeps the reflection, the
-// window attention, the body of one RSTB, SwinIR's own table kinds and the entry points.
+// The reflection, the head, the LayerNorm, the linear layers, the 3 x 3 convolutions (k_sw_reflect, k_sw_head, k_sw_layernorm,
+// k_sw_lin, k_sw_conv), the weight arrangement and the whole frame around a family's blocks (the model's buffers, the trunk and
+// the tail phase, the create, the ensemble, the inspection calls) are sr_swin_common.h, shared with sr_hat.hip and
+// sr_swin2sr.hip; this file keeps the window attention, the body of one RSTB, SwinIR's own table kinds and the entry points.
 //
 // Weights are caller-supplied (sr_swinir_create); nothing is fetched.
 #include <cmath>
@@ -62,22 +62,6 @@
 #include "sr_swin_common.h"
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------------------------
-// Symmetric reflection of the u8 image to Hp x Wp (dense, 3 Wp bytes per row): padded index i reads m = i mod 2 n,
-// m < n ? m : 2 n - 1 - m (np.pad mode 'symmetric': the edge pixel repeated, period 2 n).  One thread per output byte.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sw_reflect(const unsigned char *__restrict__ img, long long stride, int h, int w,
-                                                    unsigned char *__restrict__ out, int hp, int wp)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)hp * wp * 3) return;
-    const int c = (int)(i % 3), x = (int)((i / 3) % wp), y = (int)(i / (3LL * wp));
-    int my = y % (2 * h), mx = x % (2 * w);
-    if (my >= h) my = 2 * h - 1 - my;
-    if (mx >= w) mx = 2 * w - 1 - mx;
-    out[i] = img[(size_t)my * stride + (size_t)mx * 3 + c];
-}
 
 // Region of coordinate v of the shifted image along an axis of length L (calculate_mask's three slices).
 __device__ __forceinline__ int sw_region(int v, int L) { return v < L - SW_WIN ? 0 : (v < L - SW_SHIFT ? 1 : 2); }
@@ -187,6 +171,7 @@ void sw_launch_attention(hipStream_t st, const float *qkv, long long plane, int 
 struct sr_swinir_model : SwModelBase {
     sr_swinir_desc d{};
     static constexpr bool SHUFFLE_ONLY = false;
+    static constexpr bool PROJECTED = false;
     static int check_desc(const char *who, const sr_swinir_desc *desc) { return sw_check_desc(who, desc); }
     static std::vector<SwTable> table_list(const sr_swinir_desc &desc) { return sw_tables(desc); }
     static bool bias_table(int kind) { return kind == SW_T_RPB; }
@@ -200,7 +185,7 @@ static int sw_forward(sr_swinir_model *m, const uint8_t *d_src, int64_t src_stri
                       bool u8, const char *who)
 {
     static const SwNames names{"swinir_head", "swinir_ln", "swinir_linear", "swinir_conv", "swinir_tail"};
-    return sw_forward_frame(__func__, g_sw_live, m, names, k_sw_reflect, d_src, src_stride, h, w, d_dst, dst_stride, tail, u8, who,
+    return sw_forward_frame(__func__, g_sw_live, m, names, k_sw_reflect<>, d_src, src_stride, h, w, d_dst, dst_stride, tail, u8, who,
                             [m](const SwTrunk &T, const SwGeom &, int &k) {       // one RSTB: D Swin layers, 7 tables each
         float *x = T.Rb;                                   // the first layer reads the RSTB's input and writes X
         for (int j = 0; j < m->d.depth; ++j, k += 7) {

@@ -113,16 +113,21 @@ std::vector<SwTable> sw_tables(const sr_swinir_desc &d)
     }
     t.push_back({SW_T_LN, 1, C, 0, 0});
     t.push_back({SW_T_CONV, 1, C, C, 3});
-    if (d.upsampler == SR_SWINIR_PIXELSHUFFLE) {
+    sw_emit_tail(t, C, s, d.upsampler);
+    return t;
+}
+
+void sw_emit_tail(std::vector<SwTable> &t, int C, int s, int upsampler)
+{
+    if (upsampler == SR_SWINIR_PIXELSHUFFLE) {
         sw_emit_shuffle_tail(t, C, s);
-    } else if (d.upsampler == SR_SWINIR_PIXELSHUFFLEDIRECT) {
+    } else if (upsampler == SR_SWINIR_PIXELSHUFFLEDIRECT) {
         t.push_back({SW_T_UPD, s, 3 * s * s, C, 3});
     } else {
         t.push_back({SW_T_CBU, 1, SW_MID, C, 3});
         for (int k = 0; k < 3; ++k) t.push_back({SW_T_C64, 1, SW_MID, SW_MID, 3});
         t.push_back({SW_T_LAST, 1, 3, SW_MID, 3});
     }
-    return t;
 }
 
 // The tail phase's convolutions: {factor by which the stored output is replicated or shuffled, multiplier of the resolution

@@ -79,7 +79,7 @@ class PipelineConfig:
     device_resident: bool = True   # with the built-in SR stub: source uploaded once, every stage on device pointers,
                                    # only the canvas comes back for the writer (a custom sr_backend gets host arrays)
     sr_weights: str = ""       # path of an SR network's weights (.npz, or .pth / .pt where torch imports): stage 2 runs the
-                               # network (sr_network.load_network: compact, MSRResNet / EDSR, RRDBNet x4, RCAN or SwinIR) instead of the
+                               # network (sr_network.load_network: compact, MSRResNet / EDSR, RRDBNet x4, RCAN, SwinIR, HAT or Swin2SR) instead of the
                                # bicubic stub, device-resident too (RCAN: each tile pools its channel means over itself; SwinIR: each
                                # tile is padded and windowed on its own)
     sr_act: str = "prelu"      # activation of a compact network whose weights hold no PReLU slopes: 'relu' or 'leakyrelu'

@@ -87,8 +87,15 @@ def parse_state(state: Mapping, act: str = "prelu"):
 
 def load_state(path: str) -> Mapping:
     """A flat .npz through numpy (allow_pickle=False: nothing in the file is executed); .pth / .pt through
-    torch.load(weights_only=True, map_location='cpu') where torch imports."""
+    torch.load(weights_only=True, map_location='cpu') where torch imports; .safetensors through safetensors.numpy.load_file
+    where safetensors imports (a local file: nothing is fetched)."""
     p = str(path)
+    if p.endswith(".safetensors"):
+        try:
+            from safetensors.numpy import load_file
+        except ImportError as exc:
+            raise RuntimeError(f"{p}: loading a .safetensors checkpoint needs the safetensors package; convert it to a flat .npz instead") from exc
+        return dict(load_file(p))
     if p.endswith((".pth", ".pt")):
         try:
             import torch
@@ -885,16 +892,234 @@ def _hat_extras(state: Mapping) -> dict:
     return _scalar_extras(state, (("img_range", 1), ("rgb_mean", 3), ("conv_scale", 1)))
 
 
+# ------------------------------------------------------------------------------------------
+# Swin2SR: SwinV2 cosine attention with a continuous position bias, post-norm (Conde et al., ECCVW 2022), run by
+# csrc/sr_swin2sr.hip.  The `transformers` package's key layout is PINNED against `transformers` 5.15.0 (random-weight float64
+# goldens under tests/golden/); the official repository's layout and its -100 mask rest on the restatement
+# (tests/_swin2sr_ref.py); no published checkpoint was ever run.
+# ------------------------------------------------------------------------------------------
+SWIN2SR_PACKAGE_KEY = "swin2sr.encoder.stages.0.layers.0.attention.self.logit_scale"   # the `transformers` layout
+SWIN2SR_OFFICIAL_KEY = "layers.0.residual_group.blocks.0.attn.logit_scale"             # the official repository's layout
+SWIN2SR_RGB_MEAN = EDSR_RGB_MEAN                                 # Swin2SR's defaults: the DIV2K mean, img_range 1
+SWIN2SR_IMG_RANGE = 1.0
+_S2_STAGE_KEY = {True: re.compile(r"^swin2sr\.encoder\.stages\.(\d+)\."), False: re.compile(r"^layers\.(\d+)\.")}
+_S2_LAYER_KEY = {True: re.compile(r"^swin2sr\.encoder\.stages\.(\d+)\.layers\.(\d+)\."),
+                 False: re.compile(r"^layers\.(\d+)\.residual_group\.blocks\.(\d+)\.")}
+
+
+def swin2sr_layout(keys) -> Optional[str]:
+    """'package', 'official' or None: which Swin2SR key layout a state's keys are."""
+    keys = {str(k) for k in keys}
+    return "package" if SWIN2SR_PACKAGE_KEY in keys else "official" if SWIN2SR_OFFICIAL_KEY in keys else None
+
+
+def parse_swin2sr_state(state: Mapping, img_range: float = SWIN2SR_IMG_RANGE, rgb_mean=SWIN2SR_RGB_MEAN, mask_value: Optional[float] = None):
+    """-> (_native.Swin2srDesc, weights, biases) in sr_swin2sr_create's order (_native.swin2sr_table_names), contiguous fp32; the
+    bias entries of logit_scale and cpb_mlp.2 are None.
+
+    Both key layouts are read: the `transformers` package's (``swin2sr.encoder.stages.{i}.layers.{j}.attention.self.{query, key,
+    value, logit_scale, continuous_position_bias_mlp.0 / .2}``, ``...attention.output.dense``, ``layernorm_before / _after``,
+    ``intermediate.dense``, ``output.dense``, ``stages.{i}.conv``, ``stages.{i}.patch_embed.projection``, ``upsample.*``) and the
+    official repository's (``layers.{i}.residual_group.blocks.{j}.attn.{qkv.weight, q_bias, v_bias, logit_scale, cpb_mlp.*,
+    proj}``, ``patch_embed.proj``, ``layers.{i}.patch_embed.proj``, ...).  query / key / value are stacked into one qkv table whose
+    k bias is zero.  ``mask_value``: None takes the layout's own, -200 for the package (it adds the shifted-window mask twice),
+    -100 for the official code.  The whole description is read off the shapes; the buffers ``relative_coords_table``,
+    ``relative_position_index`` and ``attn_mask`` are recomputed, never read.  A ValueError names the offending key for a wrong
+    shape and for everything out of scope: upsampler pixelshuffle_aux, no upsampler (JPEG / denoising), resi_connection '3conv',
+    the absolute position embedding, a window other than 8, a k bias that is not zero, unequal depths or head counts between
+    stages, fp16 / bf16; what only the kernels' ranges exclude is a NotImplementedError."""
+    rd = _SwinStateReader(state)
+    state, keys, conv, dense = rd.state, rd.keys, rd.conv, rd.dense
+    layout = swin2sr_layout(keys)
+    if layout is None:
+        raise ValueError(f"{SWIN2SR_PACKAGE_KEY}: not in the state, nor {SWIN2SR_OFFICIAL_KEY} (not a Swin2SR)")
+    pk = layout == "package"
+    if mask_value is None:
+        mask_value = _native.SWIN2SR_MASK_PACKAGE if pk else _native.SWIN2SR_MASK_OFFICIAL
+    root = "swin2sr." if pk else ""
+    up = "upsample." if pk else ""
+    for k in ("swin2sr.embeddings.position_embeddings", "absolute_pos_embed"):
+        if k in keys:
+            raise ValueError(f"{k}: the absolute position embedding is not supported")
+    c3 = "swin2sr.encoder.stages.0.conv.0.weight" if pk else "layers.0.conv.0.weight"
+    if c3 in keys:
+        raise ValueError(f"{c3}: resi_connection '3conv' is not supported (only '1conv')")
+    aux = f"{up}conv_bicubic.weight"
+    if aux in keys:
+        raise ValueError(f"{aux}: upsampler pixelshuffle_aux is not supported")
+    rd.refuse_half()
+
+    def stage(i):
+        return f"swin2sr.encoder.stages.{i}" if pk else f"layers.{i}"
+
+    def block(i, j):
+        return f"{stage(i)}.layers.{j}" if pk else f"{stage(i)}.residual_group.blocks.{j}"
+
+    def pointwise(name: str, Cn: int):                           # a 1 x 1 convolution C -> C: (C, C, 1, 1) or (C, C)
+        for part in ("weight", "bias"):
+            if f"{name}.{part}" not in keys:
+                raise ValueError(f"{name}.{part}: not in the state")
+        w = np.ascontiguousarray(_array(state, f"{name}.weight"), dtype=np.float32)
+        b = np.ascontiguousarray(_array(state, f"{name}.bias"), dtype=np.float32).reshape(-1)
+        if w.shape not in ((Cn, Cn), (Cn, Cn, 1, 1)):
+            raise ValueError(f"{name}.weight: expected shape {(Cn, Cn, 1, 1)}, got {w.shape}: only patch_size 1 is supported")
+        if b.shape != (Cn,):
+            raise ValueError(f"{name}.bias: expected {Cn} values, got {b.shape}")
+        rd.tables.append((w.reshape(Cn, Cn), b))
+
+    def vector(key: str, n: int, what: str = ""):
+        if key not in keys:
+            raise ValueError(f"{key}: not in the state")
+        a = np.ascontiguousarray(_array(state, key), dtype=np.float32)
+        if a.size != n or a.reshape(-1).shape != (n,):
+            raise ValueError(f"{key}: expected {n} values, got shape {a.shape}{what}")
+        return a.reshape(-1)
+
+    Cn = int(conv(f"{root}first_convolution" if pk else "conv_first", 3).shape[0])
+    pointwise("swin2sr.embeddings.patch_embeddings.projection" if pk else "patch_embed.proj", Cn)
+    dense("swin2sr.embeddings.patch_embeddings.layernorm" if pk else "patch_embed.norm", (Cn,), (Cn,))
+    stages = sorted({int(m.group(1)) for m in map(_S2_STAGE_KEY[pk].match, keys) if m})
+    if not stages or stages != list(range(len(stages))):
+        gap = next(i for i in range(len(stages) + 1) if i not in stages)
+        raise ValueError(f"{stage(gap)}.conv.weight: the stages must be numbered 0 .. L - 1, got {stages}")
+    heads = int(np.size(_array(state, SWIN2SR_PACKAGE_KEY if pk else SWIN2SR_OFFICIAL_KEY)))
+    hidden = int(rd.shape_of(f"{block(0, 0)}.{'intermediate.dense' if pk else 'mlp.fc1'}.weight")[0])
+    hid_cpb = _native.SWIN2SR_CPB_HIDDEN
+    depth = None
+    for i in stages:
+        blocks = sorted({int(m.group(2)) for m in map(_S2_LAYER_KEY[pk].match, keys) if m and int(m.group(1)) == i})
+        if not blocks or blocks != list(range(len(blocks))):
+            gap = next(j for j in range(len(blocks) + 1) if j not in blocks)
+            raise ValueError(f"{block(i, gap)}: a stage's layers must be numbered 0 .. D - 1, got {blocks}")
+        if depth is not None and len(blocks) != depth:
+            raise ValueError(f"{block(i, min(len(blocks), depth))}: every stage must have the same depth, stage 0 has {depth} layers and "
+                             f"stage {i} has {len(blocks)}")
+        depth = len(blocks)
+        for j in blocks:
+            b = block(i, j)
+            a = f"{b}.attention.self" if pk else f"{b}.attn"
+            if pk:
+                if f"{a}.key.bias" in keys and np.any(np.asarray(_array(state, f"{a}.key.bias"), dtype=np.float32) != 0):
+                    raise ValueError(f"{a}.key.bias: a k bias that is not zero is not supported (Swin2SR's key has none)")
+                parts = [_read_dense(state, keys, f"{a}.{n}", (Cn, Cn), (Cn,) if n != "key" else None) for n in ("query", "key", "value")]
+                w = np.concatenate([p[0] for p in parts])
+                qb, vb = parts[0][1], parts[2][1]
+            else:
+                w = _read_dense(state, keys, f"{a}.qkv", (3 * Cn, Cn), None)[0]
+                if f"{a}.qkv.bias" in keys:
+                    full = vector(f"{a}.qkv.bias", 3 * Cn)
+                    if np.any(full[Cn:2 * Cn] != 0):
+                        raise ValueError(f"{a}.qkv.bias: a k bias that is not zero is not supported (Swin2SR's is q_bias, 0, v_bias)")
+                    qb, vb = full[:Cn], full[2 * Cn:]
+                else:
+                    qb, vb = vector(f"{a}.q_bias", Cn), vector(f"{a}.v_bias", Cn)
+            rd.tables.append((np.ascontiguousarray(w), np.ascontiguousarray(np.concatenate([qb, np.zeros(Cn, np.float32), vb]))))
+            rd.tables.append((vector(f"{a}.logit_scale", heads, ": every layer must have the same number of heads"), None))
+            mlp = f"{a}.continuous_position_bias_mlp" if pk else f"{a}.cpb_mlp"
+            dense(f"{mlp}.0", (hid_cpb, 2), (hid_cpb,))
+            got = rd.shape_of(f"{mlp}.2.weight")
+            if got != (heads, hid_cpb):
+                raise ValueError(f"{mlp}.2.weight: expected shape {(heads, hid_cpb)}, got {got}: every layer must have the same number of heads")
+            dense(f"{mlp}.2", (heads, hid_cpb), None)
+            dense(f"{b}.attention.output.dense" if pk else f"{a}.proj", (Cn, Cn), (Cn,))
+            dense(f"{b}.layernorm_before" if pk else f"{b}.norm1", (Cn,), (Cn,))
+            dense(f"{b}.intermediate.dense" if pk else f"{b}.mlp.fc1", (hidden, Cn), (hidden,))
+            dense(f"{b}.output.dense" if pk else f"{b}.mlp.fc2", (Cn, hidden), (Cn,))
+            dense(f"{b}.layernorm_after" if pk else f"{b}.norm2", (Cn,), (Cn,))
+            for buf, want in ((f"{a}.relative_position_index", (64, 64)), (f"{a}.relative_coords_table", (1, 15, 15, 2))):
+                if buf in keys and rd.shape_of(buf) != want:       # recomputed, never read -- but its shape tells the window
+                    raise ValueError(f"{buf}: shape {rd.shape_of(buf)} is not a window of 8 {want}: only window_size 8 is supported")
+        conv(f"{stage(i)}.conv", Cn, Cn)
+        pointwise(f"{stage(i)}.patch_embed.{'projection' if pk else 'proj'}", Cn)
+    dense("swin2sr.layernorm" if pk else "norm", (Cn,), (Cn,))
+    conv(f"{root}conv_after_body", Cn, Cn)
+    last = f"{up}final_convolution" if pk else "conv_last"
+    cbu = f"{up}conv_before_upsample" if pk else "conv_before_upsample.0"
+    scale = 1
+    if f"{up}conv_up1.weight" in keys:
+        kind, scale = "nearest+conv", 4
+        conv(cbu, Cn, 64)
+        for name in ("conv_up1", "conv_up2", "conv_hr"):
+            conv(f"{up}{name}", 64, 64)
+        conv(last, 64, 3)
+    elif f"{cbu}.weight" in keys:
+        kind = "pixelshuffle"
+        conv(cbu, Cn, 64)
+        if pk:
+            ups = sorted(k[:-len(".weight")] for k in keys if k.startswith("upsample.upsample.convolution") and k.endswith(".weight"))
+        else:
+            ups = [f"upsample.{n}" for n in sorted(int(m.group(1)) for m in map(_UPSAMPLE_KEY.match, keys) if m)]
+        if not ups:
+            raise ValueError(f"{'upsample.upsample.convolution_0' if pk else 'upsample.0'}.weight: not in the state (pixelshuffle at scale 1 has no "
+                             "upsampling stage and is not supported)")
+        for name in ups:
+            cout = int(np.shape(_array(state, f"{name}.weight"))[0])
+            r = {256: 2, 576: 3}.get(cout)
+            if r is None or (len(ups) >= 2 and r != 2) or len(ups) > 2:
+                raise ValueError(f"{name}.weight gives {cout} channels in {len(ups)} stage(s), expected 64 r^2 = 256 (x2, x4) or 576 (x3)")
+            scale *= r
+            conv(name, 64, cout)
+        conv(last, 64, 3)
+    elif ("upsample.conv.weight" if pk else "upsample.0.weight") in keys:
+        kind = "pixelshuffledirect"
+        name = "upsample.conv" if pk else "upsample.0"
+        cout = int(np.shape(_array(state, f"{name}.weight"))[0])
+        scale = {3: 1, 12: 2, 27: 3, 48: 4}.get(cout)
+        if scale is None:
+            raise ValueError(f"{name}.weight gives {cout} channels, expected 3 s^2 with s in 1 .. 4")
+        conv(name, Cn, cout)
+    else:
+        raise ValueError(f"{'final_convolution' if pk else 'conv_last'}.weight: no upsampler keys (conv_before_upsample, upsample, conv_up1): the "
+                         "JPEG / denoising variants of Swin2SR are not supported")
+    desc = _native.swin2sr_desc(Cn, heads, hidden, len(stages), depth, scale, kind, rgb_mean, float(img_range), float(mask_value))
+    _native.swin2sr_plan(desc, 1, 1)                             # NotImplementedError outside the kernels' range (host only)
+    return (desc,) + rd.arrays()
+
+
+class Swin2SRNet(_OnePieceSRNet):
+    """Swin2SR on the GPU, with CompactSRNet's surface (from_file, model, upscale, upscale_device, close).  ``state``: a state dict
+    in the `transformers` package's or the official repository's key layout (see parse_swin2sr_state).  As SwinIRSRNet there is no
+    ``tile`` (anything but 0 is refused), only the ``tail`` of the reconstruction, which changes no bit; an image cut into tiles
+    before the network is reflected, padded and windowed tile by tile."""
+
+    _one_piece = "Swin2SR's trunk is one piece (shifted windows reach across any tile)"
+
+    def __init__(self, state: Mapping, img_range: float = SWIN2SR_IMG_RANGE, rgb_mean=SWIN2SR_RGB_MEAN, mask_value: Optional[float] = None,
+                 device: int = 0):
+        self.desc, self._w, self._b = parse_swin2sr_state(state, img_range, rgb_mean, mask_value)
+        d = self.desc
+        self.n_feat, self.n_heads, self.n_hidden, self.n_groups, self.depth, self.scale = d.n_feat, d.n_heads, d.n_hidden, d.n_groups, d.depth, d.scale
+        self.mask_value = float(d.mask_value)
+        self.device = int(device)
+        self._models = {}
+
+    @classmethod
+    def from_file(cls, path: str, device: int = 0, **extras) -> "Swin2SRNet":
+        """A .npz may hold the constants a state dict lacks as 0-d ``img_range`` and ``mask_value`` and a 3-vector ``rgb_mean``
+        entry; keyword arguments win over them, Swin2SR's defaults (1, the layout's mask, the DIV2K mean) stand in for the rest."""
+        state = load_state(path)
+        return cls(state, device=device, **{**_swin2sr_extras(state), **extras})
+
+    def _make_model(self, ctx: "_native.Context"):
+        return _native.Swin2srModel(ctx, self.desc, self._w, self._b)
+
+
+def _swin2sr_extras(state: Mapping) -> dict:
+    return _scalar_extras(state, (("img_range", 1), ("rgb_mean", 3), ("mask_value", 1)))
+
+
 def load_network(path: str, act: str = "prelu", device: int = 0):
     """The network a weights file holds: a ``body.0.rdb1.conv1.weight`` entry makes it an RRDBSRNet, a
     ``body.0.residual_group.0.rcab.0.weight`` entry an RCANSRNet, a ``layers.0.residual_group.overlap_attn.qkv.weight`` entry a
-    HATSRNet, a ``layers.0.residual_group.blocks.0.attn.qkv.weight`` entry a SwinIRSRNet, otherwise a ``conv_first.weight`` entry a ResidualSRNet (``act`` is ignored for these five families), ``body.{i}.weight`` entries a CompactSRNet exactly as
+    HATSRNet, a ``...attention.self.logit_scale`` / ``...attn.logit_scale`` entry of layer 0 a Swin2SRNet (either key layout), a ``layers.0.residual_group.blocks.0.attn.qkv.weight`` entry a SwinIRSRNet, otherwise a ``conv_first.weight`` entry a ResidualSRNet (``act`` is ignored for these families), ``body.{i}.weight`` entries a CompactSRNet exactly as
     CompactSRNet.from_file."""
     state = load_state(path)
     if RRDB_KEY in {str(k) for k in _unwrap(state)}:
         return RRDBSRNet(state, device=device, **_rrdb_extras(state))
     if RCAN_KEY in {str(k) for k in _unwrap(state)}:
         return RCANSRNet(state, device=device, **_residual_extras(state))
+    if swin2sr_layout(_unwrap(state)) is not None:                 # before SwinIR's key, which an official-layout Swin2SR state carries too
+        return Swin2SRNet(state, device=device, **_swin2sr_extras(state))
     if HAT_KEY in {str(k) for k in _unwrap(state)}:                # before SwinIR's key, which a HAT state carries too
         return HATSRNet(state, device=device, **_hat_extras(state))
     if SWINIR_KEY in {str(k) for k in _unwrap(state)}:
