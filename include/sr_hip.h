@@ -627,6 +627,77 @@ SR_API int sr_bench_plan(int h, int w, int cn, int crop_border, int mode, int *c
  * uncropped image (SR_ERR_SHAPE). */
 SR_API int sr_bench_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
                        int cn, int crop_border, int mode, double data_range, sr_bench_sums *h_out);
+/* ---- VIF and GMSD, two classical full-reference metrics (csrc/sr_vif.hip, csrc/sr_gmsd.hip, csrc/sr_vif_host.cpp) -----------
+ * VIF: Sheikh and Bovik's visual information fidelity in the pixel-domain multi-scale form of MATLAB's vifp_mscale.m ("VIFp").
+ * GMSD: Xue, Zhang, Mou and Bovik's gradient magnitude similarity deviation, the authors' GMSD.m.  No reference counterpart.
+ * PARITY UNPINNED for both: MATLAB, piq and pyiqa are not available offline, and both definitions below are recalled from the
+ * published scripts; they are pinned by the NumPy / SciPy restatements tests/_vif_ref.py and tests/_gmsd_ref.py alone.  Known
+ * distances: piq and pyiqa feed a differently rounded Y; for GMSD they divide by N where GMSD.m's std2 divides by N - 1; the
+ * widely copied Python port of vifp_mscale filters with ndimage.gaussian_filter and reflection instead of valid windows,
+ * which is a different definition.
+ * Inputs and planes (both metrics): two u8 images of h x w x cn, strides in bytes, and crop_border = cb >= 0: rows [cb, h - cb),
+ * columns [cb, w - cb), as sr_bench_u8.  One plane per image, in gray-level units 0 .. 255 (both metrics hold absolute
+ * constants in those units: unlike SSIM neither is scale-free):
+ *   cn = 1, SR_BENCH_CHANNELS   the plane as it is
+ *   cn = 3, SR_BENCH_Y          X / 255000 with X = 65481 R + 128553 G + 24966 B + 4080000, an exact integer below 2^26
+ *   cn = 3, SR_BENCH_Y_ROUND    floor((2 X + 255000) / 510000)
+ * Anything else is SR_ERR_INVALID_ARG, cn = 3 with SR_BENCH_CHANNELS included.
+ * VIF.  a is the reference and b the distorted image: the metric is not symmetric.  For scale s = 1 .. 4, N = 2^(5 - s) + 1 =
+ * 17, 9, 5, 3 and the window W is fspecial('gaussian', N, N / 5): the outer product of the 1-D taps exp(-(k - c)^2 /
+ * (2 sigma^2)), c = (N - 1) / 2, sigma = N / 5, normalised by their sum (fspecial's eps truncation never bites for these four).
+ * For s > 1 both planes are first filtered with THAT scale's window over the valid region only and every second sample is
+ * kept, from index 0 on both axes.  On the scale's planes x, y, all over the valid region: mu1 = W*x, mu2 = W*y,
+ * s1 = W*(x x) - mu1^2, s2 = W*(y y) - mu2^2, s12 = W*(x y) - mu1 mu2; then, in this order: s1, s2 < 0 -> 0;
+ * g = s12 / (s1 + 1e-10); sv = s2 - g s12; where s1 < 1e-10: g = 0, sv = s2, s1 = 0; where s2 < 1e-10: g = 0, sv = 0; where
+ * g < 0: sv = s2, g = 0; sv <= 1e-10 -> 1e-10.  num_s = sum log10(1 + g^2 s1 / (sv + 2)), den_s = sum log10(1 + s1 / 2)
+ * (sigma_nsq = 2); the value is sum_s num_s / sum_s den_s, NaN when the denominators sum to 0 (a flat reference: MATLAB's
+ * 0 / 0).  Identical images give a value within 1e-11 of 1, not 1, because of the 1e-10 terms.  Sizes: the scale-1 map is
+ * (H - 16) x (W - 16); the scale-2 plane is ceil((H - 8) / 2) on a side and its map 8 less; scale 3: ceil((h2 - 4) / 2), map 4
+ * less; scale 4: ceil((h3 - 2) / 2), map 2 less.  Both cropped sides must be at least 41 (one sample at scale 4), else
+ * SR_ERR_SHAPE naming the minimum; the scale count is never reduced.  Everything is float64; the filter is evaluated
+ * separably, columns first (against the 2-D window that moves num_s by up to 1.9e-12 and den_s by up to 3.5e-12 relative over
+ * the shapes of tests/test_gpu_vif.py, measured on an MI355X).
+ * GMSD.  avg = conv2(P, ones(2) / 4, 'same'): the mean of P(i .. i + 1, j .. j + 1) with ZERO beyond the last row and column;
+ * avg(1:2:end, 1:2:end) is kept, ceil(H / 2) x ceil(W / 2).  Prewitt gradients dx = [1 0 -1; 1 0 -1; 1 0 -1] / 3, dy = dx',
+ * conv2(., ., 'same') with a zero border; m = sqrt(Ix^2 + Iy^2); q = (2 m1 m2 + 170) / (m1^2 + m2^2 + 170); the score is
+ * std2(q), the standard deviation with the N - 1 divisor.  The record carries d = 1 - q = (m1 - m2)^2 / (m1^2 + m2^2 + 170):
+ * the deviation of d is that of q, and summing d avoids the cancellation of a mean near 1.  The 2 x 2 sums and the Prewitt
+ * sums are exact integers in every mode; m^2 = (Sx^2 + Sy^2) / 144 rounds once in the plane and Y_ROUND modes and twice in
+ * SR_BENCH_Y (the 64-bit integer can pass 2^53 on its way to float64, then the division).  Identical images give exactly 0.  Both cropped sides must be
+ * at least 4, else SR_ERR_SHAPE. */
+typedef struct sr_vif_scale {
+    double num, den;    /* num_s, den_s */
+    uint64_t count;     /* samples of the scale's map */
+} sr_vif_scale;
+typedef struct sr_gmsd_sums {
+    double sum_d, sum_d2;   /* sum of d and of d^2 over the half-size map */
+    uint64_t count;         /* ceil(ch / 2) * ceil(cw / 2) */
+} sr_gmsd_sums;
+/* Host only, no context: the plane sizes and map sample counts of the four scales and the bytes of context scratch a call
+ * will hold (each output may be NULL; the arrays take 4 entries).  Carries every shape and argument refusal above. */
+SR_API int sr_vif_plan(int h, int w, int cn, int crop_border, int mode, int *scale_h, int *scale_w, uint64_t *counts,
+                       size_t *scratch_bytes);
+/* Host only: the N normalised 1-D taps of scale 1 .. 4 (N = 17, 9, 5, 3). */
+SR_API int sr_vif_window(int scale, double *taps);
+/* The four scales' sums, h_out[4].  The crop is pointer arithmetic; pixels are read byte by byte, so no alignment is assumed;
+ * strides are arbitrary (at least a row).  Per-block partial sums are added in a fixed order, no floating-point atomics: equal
+ * inputs give equal bits.  Synchronous; the planes of scales 2 .. 4 and the partials are context scratch, grown on demand.
+ * Refused before any device call: null pointers, everything sr_vif_plan refuses, a stride shorter than a row of the uncropped
+ * image (SR_ERR_SHAPE). */
+SR_API int sr_vif_u8(sr_ctx *ctx, const uint8_t *d_ref, int64_t stride_ref, const uint8_t *d_dist, int64_t stride_dist, int h,
+                     int w, int cn, int crop_border, int mode, sr_vif_scale *h_out);
+/* sum num_s / sum den_s of the 4 records (host only); NaN for a flat reference, and NaN with sr_last_error for a null list
+ * or scales != 4. */
+SR_API double sr_vif_value(const sr_vif_scale *out, int scales);
+/* Host only: the half-size map, its sample count and the scratch bytes of a GMSD call; every shape and argument refusal. */
+SR_API int sr_gmsd_plan(int h, int w, int cn, int crop_border, int mode, int *map_h, int *map_w, uint64_t *count,
+                        size_t *scratch_bytes);
+/* One launch, one pass over both images; conventions and refusals as sr_vif_u8. */
+SR_API int sr_gmsd_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
+                      int cn, int crop_border, int mode, sr_gmsd_sums *h_out);
+/* sqrt((sum_d2 - sum_d^2 / n) / (n - 1)), 0 when rounding takes the variance below 0 (host only); NaN with sr_last_error for
+ * a null record or fewer than 2 samples. */
+SR_API double sr_gmsd_value(const sr_gmsd_sums *sums);
 /* ---- NIQE, the no-reference quality model (csrc/sr_niqe.hip, csrc/sr_niqe_host.cpp) -------------------------------------------
  * Mittal, Soundararajan, Bovik 2013, in the arithmetic of MATLAB's computequality / estimatemodelparam and BasicSR's
  * calculate_niqe, made exact wherever it can be.  The reference's calculate_niqe asks pyiqa for this model first; the 'niqe'

@@ -73,6 +73,17 @@ class BenchSums(C.Structure):
     _fields_ = [("sse", C.c_double), ("ssim_sum", C.c_double), ("n_elems", C.c_uint64), ("n_map", C.c_uint64)]
 
 
+class VifScale(C.Structure):
+    """sr_vif_scale (include/sr_hip.h)."""
+    _fields_ = [("num", C.c_double), ("den", C.c_double), ("count", C.c_uint64)]
+
+
+class GmsdSums(C.Structure):
+    """sr_gmsd_sums (include/sr_hip.h)."""
+    _fields_ = [("sum_d", C.c_double), ("sum_d2", C.c_double), ("count", C.c_uint64)]
+
+
+VIF_SCALES = 4
 # enum sr_bench_mode (include/sr_hip.h)
 BENCH_CHANNELS, BENCH_Y, BENCH_Y_ROUND = 0, 1, 2
 # enum sr_imresize_out (include/sr_hip.h) and the element type each writes
@@ -260,6 +271,13 @@ SIGNATURES = {
     "sr_ms_ssim_planes": (_i, [_vp, _i, _vp, _vp]),
     "sr_bench_plan": (_i, [_i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_sz)]),
     "sr_bench_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _dbl, C.POINTER(BenchSums)]),
+    "sr_vif_plan": (_i, [_i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), C.POINTER(_sz)]),
+    "sr_vif_window": (_i, [_i, C.POINTER(_dbl)]),
+    "sr_vif_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, C.POINTER(VifScale)]),
+    "sr_vif_value": (_dbl, [C.POINTER(VifScale), _i]),
+    "sr_gmsd_plan": (_i, [_i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), C.POINTER(_sz)]),
+    "sr_gmsd_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, C.POINTER(GmsdSums)]),
+    "sr_gmsd_value": (_dbl, [C.POINTER(GmsdSums)]),
     "sr_niqe_plan": (_i, [_i, _i, _i, _i, _pi, _pi, _pi, _pi, C.POINTER(_sz)]),
     "sr_niqe_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sr_niqe_half_plane": (_i, [_vp, _vp]),
@@ -678,6 +696,56 @@ def bench_values(sums: dict, data_range: float = 255.0) -> Tuple[float, float]:
     sse = sums["sse"]
     psnr = float("inf") if sse == 0 else 10.0 * math.log10(float(data_range) * float(data_range) / (sse / sums["n_elems"]))
     return psnr, sums["ssim_sum"] / sums["n_map"]
+
+
+def vif_plan(h: int, w: int, cn: int, crop_border: int = 0, mode: int = BENCH_Y) -> dict:
+    """Host only (sr_vif_plan): the plane sizes [(h_s, w_s)] and map sample counts of VIF's four scales and the bytes of context
+    scratch of a call.  ValueError for cn not 1 or 3, an unknown mode, a Y mode on one channel, SR_BENCH_CHANNELS on three or a
+    negative crop_border; SrShapeError (a ValueError) naming the minimum for a side below 41 after the crop."""
+    h, w, cn, crop_border, mode = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn"), (crop_border, "crop_border"),
+                                                             (mode, "mode")))
+    sh, sw, cnt, nbytes = (C.c_int * VIF_SCALES)(), (C.c_int * VIF_SCALES)(), (C.c_uint64 * VIF_SCALES)(), C.c_size_t(0)
+    check(load().sr_vif_plan(h, w, cn, crop_border, mode, sh, sw, cnt, C.byref(nbytes)))
+    return {"sizes": [(sh[s], sw[s]) for s in range(VIF_SCALES)], "counts": [int(cnt[s]) for s in range(VIF_SCALES)],
+            "scratch_bytes": int(nbytes.value)}
+
+
+def vif_window(scale: int) -> np.ndarray:
+    """Host only (sr_vif_window): the N = 17, 9, 5, 3 normalised 1-D taps of scale 1 .. 4.  ValueError for another scale."""
+    scale = _whole(scale, "scale")
+    taps = (C.c_double * 17)()
+    check(load().sr_vif_window(scale, taps))
+    return np.array(taps[:(16 >> (scale - 1)) + 1], np.float64)
+
+
+def vif_value(scales) -> float:
+    """Host only (sr_vif_value): sum num_s / sum den_s of the four (num, den, count) records of vif_u8; NaN for a flat
+    reference (every den 0).  ValueError for anything but four records."""
+    scales = list(scales)
+    if len(scales) != VIF_SCALES:
+        raise ValueError(f"vif_value: need the {VIF_SCALES} scale records of vif_u8 (got {len(scales)})")
+    arr = (VifScale * VIF_SCALES)(*[VifScale(float(n), float(d), int(c)) for n, d, c in scales])
+    return float(load().sr_vif_value(arr, VIF_SCALES))
+
+
+def gmsd_plan(h: int, w: int, cn: int, crop_border: int = 0, mode: int = BENCH_Y) -> dict:
+    """Host only (sr_gmsd_plan): the half-size map, its sample count and the bytes of context scratch of a GMSD call.
+    ValueError as vif_plan; SrShapeError naming the minimum for a side below 4 after the crop."""
+    h, w, cn, crop_border, mode = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn"), (crop_border, "crop_border"),
+                                                             (mode, "mode")))
+    mh, mw, cnt, nbytes = C.c_int(0), C.c_int(0), C.c_uint64(0), C.c_size_t(0)
+    check(load().sr_gmsd_plan(h, w, cn, crop_border, mode, C.byref(mh), C.byref(mw), C.byref(cnt), C.byref(nbytes)))
+    return {"size": (mh.value, mw.value), "count": int(cnt.value), "scratch_bytes": int(nbytes.value)}
+
+
+def gmsd_value(sums: dict) -> float:
+    """Host only (sr_gmsd_value): the deviation sqrt((sum_d2 - sum_d^2 / n) / (n - 1)) of a gmsd_u8 record.  ValueError for
+    fewer than 2 samples."""
+    rec = GmsdSums(float(sums["sum_d"]), float(sums["sum_d2"]), int(sums["count"]))
+    v = float(load().sr_gmsd_value(C.byref(rec)))
+    if v != v:
+        raise ValueError(last_error())
+    return v
 
 
 def imresize_size(n: int, scale: float) -> int:
@@ -1179,6 +1247,30 @@ class Context:
         check(self.lib.sr_bench_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
                                    int(cn), crop_border, mode, float(data_range), C.byref(out)))
         return {"sse": out.sse, "ssim_sum": out.ssim_sum, "n_elems": int(out.n_elems), "n_map": int(out.n_map)}
+
+    def vif_u8(self, d_ref, stride_ref, d_dist, stride_dist, h, w, cn, crop_border=0, mode=BENCH_Y) -> list:
+        """sr_vif_u8 -> [(num_s, den_s, count)] of the four scales, d_ref the reference and d_dist the distorted image, both
+        cropped by crop_border (finish with vif_value).  Every argument is checked before the device is touched: ValueError,
+        or its subclass SrShapeError for a short stride or a crop that leaves a side below 41."""
+        crop_border, mode = _whole(crop_border, "crop_border"), _whole(mode, "mode")
+        if not d_ref or not d_dist:
+            raise ValueError("vif_u8: null image pointer")
+        out = (VifScale * VIF_SCALES)()
+        check(self.lib.sr_vif_u8(self.handle, C.c_void_p(d_ref), int(stride_ref), C.c_void_p(d_dist), int(stride_dist), int(h), int(w),
+                                 int(cn), crop_border, mode, out))
+        return [(out[s].num, out[s].den, int(out[s].count)) for s in range(VIF_SCALES)]
+
+    def gmsd_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, crop_border=0, mode=BENCH_Y) -> dict:
+        """sr_gmsd_u8 -> {'sum_d', 'sum_d2', 'count'} of the two images cropped by crop_border (finish with gmsd_value).  Every
+        argument is checked before the device is touched: ValueError, or its subclass SrShapeError for a short stride or a
+        crop that leaves a side below 4."""
+        crop_border, mode = _whole(crop_border, "crop_border"), _whole(mode, "mode")
+        if not d_a or not d_b:
+            raise ValueError("gmsd_u8: null image pointer")
+        out = GmsdSums()
+        check(self.lib.sr_gmsd_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
+                                  int(cn), crop_border, mode, C.byref(out)))
+        return {"sum_d": out.sum_d, "sum_d2": out.sum_d2, "count": int(out.count)}
 
     def niqe_u8(self, d_img, stride, h, w, cn, crop_border=0) -> np.ndarray:
         """sr_niqe_u8 -> records[2, nby * nbx] (NIQE_RECORD, scale-major) of the image cropped by crop_border (finish with

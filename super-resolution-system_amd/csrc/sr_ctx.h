@@ -104,11 +104,13 @@ struct sr_ctx {
     int niqe_H = 0, niqe_W = 0;                         // the kept plane whose half plane the scratch holds (0: nothing valid)
     DevBuf brisque_ws;                                  // BRISQUE: the int32 half plane, then the per-tile partials
     int brisque_H2 = 0, brisque_W2 = 0;                 // the half plane the scratch holds (0: nothing valid)
+    DevBuf vif_ws;                                      // VIF: the float64 planes of scales 2 .. 4, then the per-block partials
+    DevBuf gmsd_ws;                                     // GMSD: per-block partials
     CachedTable imresize_tab;                           // imresize: both axes' weights, indices and starts of the last geometry
     // Frees every device buffer above; sr_ctx_destroy calls it with the stream drained and the device current.
     void release_device()
     {
-        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws, &brisque_ws, &imresize_tab.buf})
+        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws, &brisque_ws, &vif_ws, &gmsd_ws, &imresize_tab.buf})
             b->release();
     }
 };

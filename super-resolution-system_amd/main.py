@@ -72,6 +72,9 @@ class PipelineConfig:
                                # sr_scale pixels cropped) of the canvas against the INTER_CUBIC resize of the source ('sr_benchmark')
     qa_dists_weights: str = "" # (with enable_qa): path of DISTS weights (.npz: the VGG16 convolutions and alpha / beta): stage 4 also reports
                                # the DISTS of the canvas against the INTER_CUBIC resize of the source ('dists')
+    qa_vif: bool = False       # (with enable_qa): stage 4 also reports the 4-scale pixel-domain VIF of the canvas against the INTER_CUBIC
+                               # resize of the source (the reference), on the exact luma ('vifp', 'vifp_scales')
+    qa_gmsd: bool = False      # (with enable_qa): ... and the gradient magnitude similarity deviation of the same pair ('gmsd')
     qa_niqe_params: str = ""   # (with enable_qa): path of NIQE's pristine parameters (.npz with BasicSR's keys, or .mat): stage 4 also
                                # reports the NIQE of the canvas ('niqe_model'; the 'niqe' key keeps the reference's stand-in heuristic)
     qa_brisque_model: str = "" # (with enable_qa): path of a BRISQUE regressor (.npz: sv, sv_coef, gamma, rho, feature_min, feature_max): stage 4
@@ -265,6 +268,49 @@ class SuperResolutionPipeline:
             ctx.sync()
             ref.free()
         out.update(psnr_y=y['psnr'], ssim_y=y['ssim'], psnr_rgb=rgb['psnr'], ssim_rgb=rgb['ssim'])
+
+    def _vif_gmsd(self, ctx, report: Dict[str, Any], d_src: int, src_shape, d_canvas: int, canvas_shape) -> None:
+        """Stage 4's optional 'vifp' / 'vifp_scales' (qa_vif) and 'gmsd' (qa_gmsd) entries: the 4-scale pixel-domain VIF and
+        the gradient magnitude similarity deviation of the canvas against the INTER_CUBIC resize of the source to the canvas
+        size (the reference), both in HBM, on the exact BT.601 luma, no crop.  A canvas too small (a side below 41 for VIF,
+        below 4 for GMSD) or a NaN value (VIF of a flat reference; GMSD has none) gives None and 'vifp_note' / 'gmsd_note' says why (the run
+        does not fail).  One helper for the device-resident, the host-array and the sharded path."""
+        import _native
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        ih, iw = int(src_shape[0]), int(src_shape[1])
+        todo = []
+        if self.config.qa_vif:
+            report['vifp'], report['vifp_scales'] = None, None
+            try:
+                _native.vif_plan(H, W, cn, 0, _native.BENCH_Y)
+                todo.append('vif')
+            except ValueError as exc:
+                report['vifp_note'] = str(exc)
+        if self.config.qa_gmsd:
+            report['gmsd'] = None
+            try:
+                _native.gmsd_plan(H, W, cn, 0, _native.BENCH_Y)
+                todo.append('gmsd')
+            except ValueError as exc:
+                report['gmsd_note'] = str(exc)
+        if not todo:
+            return
+        ref = ctx.alloc(H * W * cn)
+        try:
+            ctx.resize_cubic_u8(d_src, iw * cn, ih, iw, cn, ref.ptr, W * cn, H, W)
+            q = self.quality_module
+            if 'vif' in todo:
+                v, scales = q.calculate_vif_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn), return_scales=True)
+                report['vifp_scales'] = [{'num': n, 'den': d, 'count': c} for n, d, c in scales]
+                if v == v:
+                    report['vifp'] = float(v)
+                else:
+                    report['vifp_note'] = "the reference is flat at every scale: VIF is 0 / 0"
+            if 'gmsd' in todo:
+                report['gmsd'] = float(q.calculate_gmsd_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn)))
+        finally:
+            ctx.sync()
+            ref.free()
 
     def _degrade(self, ctx, hr: np.ndarray):
         """benchmark_degrade's stage 0: the ground truth goes up once and stays in HBM; its mod-crop to sr_scale (a view: the
@@ -499,6 +545,8 @@ class SuperResolutionPipeline:
                     self._ms_ssim(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_benchmark:
                     self._sr_benchmark(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
+                if self.config.qa_vif or self.config.qa_gmsd:
+                    self._vif_gmsd(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_niqe_params:
                     self._niqe_model(ctx, report, canvas.ptr, (H, W, 3))
                 if self.config.qa_brisque_model:
@@ -605,6 +653,8 @@ class SuperResolutionPipeline:
                         self._ms_ssim(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_benchmark:
                         self._sr_benchmark(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
+                    if self.config.qa_vif or self.config.qa_gmsd:
+                        self._vif_gmsd(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_niqe_params:
                         self._niqe_model(qctx, report, canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_brisque_model:
@@ -705,6 +755,13 @@ class SuperResolutionPipeline:
                         self._sr_benchmark(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
                     finally:
                         d_src.free(); d_fused.free()
+                if self.config.qa_vif or self.config.qa_gmsd:
+                    qctx = self.quality_module._ctx()
+                    d_src, d_fused = qctx.upload(original), qctx.upload(fused)
+                    try:
+                        self._vif_gmsd(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
+                    finally:
+                        d_src.free(); d_fused.free()
                 if self.config.qa_niqe_params:
                     qctx = self.quality_module._ctx()
                     d_fused = qctx.upload(fused)
@@ -771,6 +828,12 @@ async def main() -> int:
     ap.add_argument("--qa-benchmark", action="store_true",
                     help="stage 4 also reports the SR-benchmark PSNR / SSIM (Y channel and RGB, a border of --sr-scale pixels "
                          "cropped) of the result against the bicubic resize of the input (report key sr_benchmark)")
+    ap.add_argument("--qa-vif", action="store_true",
+                    help="stage 4 also reports the 4-scale pixel-domain VIF (vifp_mscale) of the result against the bicubic resize "
+                         "of the input, which is the reference (report keys vifp, vifp_scales)")
+    ap.add_argument("--qa-gmsd", action="store_true",
+                    help="stage 4 also reports the gradient magnitude similarity deviation of the result against the bicubic "
+                         "resize of the input (report key gmsd)")
     ap.add_argument("--qa-niqe-params", default="", metavar="PATH",
                     help="NIQE's pristine parameters (.npz with the keys mu_pris_param / cov_pris_param, or .mat): stage 4 also "
                          "reports the NIQE of the result (report key niqe_model; the key niqe stays the stand-in heuristic)")
@@ -808,7 +871,7 @@ async def main() -> int:
         return 2
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act, sr_ensemble=args.sr_ensemble,
-                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark,
+                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark, qa_vif=args.qa_vif, qa_gmsd=args.qa_gmsd,
                          qa_niqe_params=args.qa_niqe_params, qa_brisque_model=args.qa_brisque_model, qa_dists_weights=args.qa_dists_weights,
                          benchmark_degrade=args.benchmark_degrade)
     if args.plan_only:

@@ -549,6 +549,101 @@ class QualityAssessmentModule:
             raise ValueError("evaluate_sr_benchmark: null device pointer")
         return self._sr_benchmark_dev(self._ctx(), int(d_img1), int(d_img2), args, data_range)
 
+    # -- VIF and GMSD (no reference counterpart: MATLAB's vifp_mscale.m and the authors' GMSD.m) ------------------------------
+    @staticmethod
+    def _plane_metric_args(what: str, plan, shape1, shape2, crop_border, test_y_channel: bool, y_round: bool, stride1, stride2):
+        """Every refusal of the VIF / GMSD methods, on the host: ValueError (SrShapeError for a crop that leaves a side too
+        small or a short stride).  Gray input uses the plane as it is.  -> (h, w, cn, crop_border, mode, stride1, stride2)."""
+        shape1, shape2 = tuple(int(v) for v in shape1), tuple(int(v) for v in shape2)
+        if shape1 != shape2:
+            raise ValueError(f"{what}: images must have the same shape, got {shape1} vs {shape2} "
+                             "(nothing is cropped to a common rectangle)")
+        if len(shape1) not in (2, 3):
+            raise ValueError(f"{what}: need an H x W or H x W x C image, got shape {shape1}")
+        cn = shape1[2] if len(shape1) == 3 else 1
+        if cn not in (1, 3):
+            raise ValueError(f"{what}: colour images must have 3 channels (RGB)")
+        if cn == 3 and not test_y_channel:
+            raise ValueError(f"{what}: a colour image is compared on its luma only (test_y_channel=True)")
+        if y_round and cn != 3:
+            raise ValueError(f"{what}: y_round applies to the luma of an RGB image only")
+        mode = _native.BENCH_CHANNELS if cn == 1 else (_native.BENCH_Y_ROUND if y_round else _native.BENCH_Y)
+        plan(shape1[0], shape1[1], cn, crop_border, mode)                        # crop_border < 0, a too-small crop
+        row = shape1[1] * cn
+        s1, s2 = (row if s is None else int(s) for s in (stride1, stride2))
+        if s1 < row or s2 < row:
+            raise _native.SrShapeError(f"{what}: stride smaller than a row")
+        return shape1[0], shape1[1], cn, int(crop_border), mode, s1, s2
+
+    @staticmethod
+    def _vif_dev(ctx, d_ref: int, d_dist: int, args, return_scales: bool):
+        h, w, cn, cb, mode, s1, s2 = args
+        scales = ctx.vif_u8(d_ref, s1, d_dist, s2, h, w, cn, crop_border=cb, mode=mode)
+        v = _native.vif_value(scales)
+        return (v, scales) if return_scales else v
+
+    def calculate_vif(self, reference: np.ndarray, distorted: np.ndarray, crop_border: int = 0, test_y_channel: bool = True,
+                      y_round: bool = False, return_scales: bool = False):
+        """VIF in the pixel domain over four scales (MATLAB's vifp_mscale, "VIFp"), as include/sr_hip.h defines it: both u8
+        images cropped by crop_border on every side, then on the BT.601 luma carried exactly (y_round: MATLAB's rounded u8
+        luma instead); a gray image is used as it is.  NOT symmetric: `reference` is the reference.  1 for identical images up
+        to 1e-11, NaN for a flat reference.  return_scales: (value, [(num_s, den_s, count)] of the four scales).  u8 images of
+        equal shape only: another shape is a ValueError (nothing is cropped to a common rectangle), as is a crop that leaves
+        a side below 41."""
+        a = self._require_u8(np.asarray(reference), "calculate_vif")
+        b = self._require_u8(np.asarray(distorted), "calculate_vif")
+        args = self._plane_metric_args("calculate_vif", _native.vif_plan, a.shape, b.shape, crop_border, test_y_channel, y_round,
+                                       None, None)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._vif_dev(ctx, da.ptr, db.ptr, args, return_scales)
+        finally:
+            da.free(); db.free()
+
+    def calculate_vif_device(self, d_reference: int, shape1, d_distorted: int, shape2, crop_border: int = 0,
+                             test_y_channel: bool = True, y_round: bool = False, return_scales: bool = False,
+                             stride1: Optional[int] = None, stride2: Optional[int] = None):
+        """calculate_vif on two u8 images that already live in HBM (device addresses + shapes; strides in bytes, dense when
+        None)."""
+        args = self._plane_metric_args("calculate_vif", _native.vif_plan, shape1, shape2, crop_border, test_y_channel, y_round,
+                                       stride1, stride2)
+        if not d_reference or not d_distorted:
+            raise ValueError("calculate_vif: null device pointer")
+        return self._vif_dev(self._ctx(), int(d_reference), int(d_distorted), args, return_scales)
+
+    @staticmethod
+    def _gmsd_dev(ctx, d1: int, d2: int, args) -> float:
+        h, w, cn, cb, mode, s1, s2 = args
+        return _native.gmsd_value(ctx.gmsd_u8(d1, s1, d2, s2, h, w, cn, crop_border=cb, mode=mode))
+
+    def calculate_gmsd(self, img1: np.ndarray, img2: np.ndarray, crop_border: int = 0, test_y_channel: bool = True,
+                       y_round: bool = False) -> float:
+        """The gradient magnitude similarity deviation (the authors' GMSD.m), as include/sr_hip.h defines it: planes as
+        calculate_vif, the 2 x 2 mean and every second sample, Prewitt gradient magnitudes, and the standard deviation (N - 1
+        divisor) of the similarity map.  0 for identical images, larger is worse.  u8 images of equal shape only; a crop that
+        leaves a side below 4 is a ValueError."""
+        a = self._require_u8(np.asarray(img1), "calculate_gmsd")
+        b = self._require_u8(np.asarray(img2), "calculate_gmsd")
+        args = self._plane_metric_args("calculate_gmsd", _native.gmsd_plan, a.shape, b.shape, crop_border, test_y_channel, y_round,
+                                       None, None)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._gmsd_dev(ctx, da.ptr, db.ptr, args)
+        finally:
+            da.free(); db.free()
+
+    def calculate_gmsd_device(self, d_img1: int, shape1, d_img2: int, shape2, crop_border: int = 0, test_y_channel: bool = True,
+                              y_round: bool = False, stride1: Optional[int] = None, stride2: Optional[int] = None) -> float:
+        """calculate_gmsd on two u8 images that already live in HBM (device addresses + shapes; strides in bytes, dense when
+        None)."""
+        args = self._plane_metric_args("calculate_gmsd", _native.gmsd_plan, shape1, shape2, crop_border, test_y_channel, y_round,
+                                       stride1, stride2)
+        if not d_img1 or not d_img2:
+            raise ValueError("calculate_gmsd: null device pointer")
+        return self._gmsd_dev(self._ctx(), int(d_img1), int(d_img2), args)
+
     # -- NIQE, the model (no reference counterpart in code: the reference delegates to pyiqa.create_metric('niqe')) ----------
     @staticmethod
     def _niqe_args(shape, crop_border) -> Tuple[int, int, int, int]:
