@@ -1329,6 +1329,14 @@ static int assess_impl(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const 
             const long long cost = ((blocks + slots - 1) / slots) * (AM_CH * n);
             if (best_cost < 0 || cost <= best_cost) { best_cost = cost; P.nch = n; P.ty = ty; }
         }
+        // SR_ASSESS_NCH=n, an integer in [2, AM_NCH_MAX]: that chunk count instead of the cost rule's choice (anything else
+        // is ignored).  The sums do not depend on it beyond the order of the additions; the suite uses it to run every
+        // block length at small shapes.  Read per call.
+        if (const char *e = std::getenv("SR_ASSESS_NCH")) {
+            char *end = nullptr;
+            const long n = std::strtol(e, &end, 10);
+            if (end != e && *end == '\0' && n >= 2 && n <= AM_NCH_MAX) { P.nch = (int)n; P.ty = AM_CH * (int)n - 2 * AM_R; }
+        }
         const long long gby = (rows + P.ty - 1) / P.ty;
         const size_t nblk = (size_t)(gbx * gby);
         void *scr = nullptr;
