@@ -698,6 +698,83 @@ SR_API int sr_gmsd_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const u
 /* sqrt((sum_d2 - sum_d^2 / n) / (n - 1)), 0 when rounding takes the variance below 0 (host only); NaN with sr_last_error for
  * a null record or fewer than 2 samples. */
 SR_API double sr_gmsd_value(const sr_gmsd_sums *sums);
+/* ---- FSIM and FSIMc, the phase-congruency feature similarity (csrc/sr_fsim.hip, csrc/sr_fsim_host.cpp) ------------------------
+ * Zhang, Zhang, Mou and Zhang, TIP 2011, in the form of the authors' FeatureSIM.m.  No reference counterpart.
+ * PARITY UNPINNED: MATLAB, piq and pyiqa are not available offline; the definition below is recalled from the published
+ * scripts and pinned by the NumPy restatement tests/_fsim_ref.py alone.  Known distance, rounding-level: MATLAB forms Y, I, Q
+ * and the pooling mean in double with a rounding each, here they are exact integers until one division.
+ * Inputs: two u8 images of equal shape h x w x cn, cn = 1, 3 (RGB) or 4 (alpha ignored), strides in bytes.  Both sides must be
+ * at least 16 (SR_ERR_SHAPE).  Nothing is cropped.  The metric is symmetric in its two arguments.
+ *   planes   carried exactly as integers: Y 1000 = 299 R + 587 G + 114 B, I 1000 = 596 R - 274 G - 322 B, Q 1000 = 211 R -
+ *            523 G + 312 B.  cn = 1: Y 1000 = 1000 v and the I and Q records are 0, which gives S_i = S_q = 1 exactly as the
+ *            script's I = Q = 1 does: FSIMc = FSIM.
+ *   pooling  F = max(1, floor(min(h, w) / 256 + 0.5)); each plane is filtered by the F x F mean as conv2(., 'same') with a
+ *            zero border and sampled at 0, F, 2F, ...: rows x cols = ceil(h / F) x ceil(w / F).  0-based, the window of sample
+ *            i along an axis covers the source indices i F + floor(F / 2) - F + 1 .. i F + floor(F / 2); indices outside the
+ *            image contribute 0 and the divisor is always F^2.  The record is the int64 window sum; the division by 1000 F^2
+ *            happens once, in float64.  The pooled long side must be at most 2048 and F at most 256 (SR_ERR_UNSUPPORTED).
+ *   PC       Kovesi's phasecong2 as FSIM ships it, of each pooled Y: 4 scales, 4 orientations, minWaveLength 6, mult 2,
+ *            sigmaOnf 0.55, dThetaOnSigma 1.2, k 2, epsilon 1e-4.  Grid along an axis of length n: odd n (-(n-1)/2 .. (n-1)/2)
+ *            / (n-1), even n (-n/2 .. n/2-1) / n; radius = sqrt(x^2 + y^2), theta = atan2(-y, x), both ifftshifted;
+ *            radius[0,0] = 1 for the log-Gabor only.  lp = 1 / (1 + (r / 0.45)^30) on the radius with 0 at DC;
+ *            logGabor_s = exp(-ln(radius / fo_s)^2 / (2 ln(0.55)^2)) lp, fo_s = 1 / (6 2^s), s = 0..3, logGabor_s[0,0] = 0;
+ *            spread_o = exp(-dtheta^2 / (2 ts^2)), ts = pi / 4 / 1.2, angl = o pi / 4, ds = sin(theta) cos(angl) - cos(theta)
+ *            sin(angl), dc = cos(theta) cos(angl) + sin(theta) sin(angl), dtheta = |atan2(ds, dc)|.  Per orientation o:
+ *            EO_s = ifft2(fft2(Y) logGabor_s spread_o) = E_s + i O_s, An_s = |EO_s|; sumE, sumO, sumAn over s;
+ *            XEnergy = sqrt(sumE^2 + sumO^2) + epsilon, MeanE = sumE / XEnergy, MeanO = sumO / XEnergy;
+ *            Energy = sum_s (E_s MeanE + O_s MeanO - |E_s MeanO - O_s MeanE|); medianE2n = MATLAB's median of |EO_0|^2 over
+ *            the plane (the mean of the two middle values for an even count); noisePower = (-medianE2n / ln 0.5) / EM_n,
+ *            EM_n = sum filter_{0,o}^2; tau = sqrt((2 noisePower S2 + 4 noisePower Sij) / 2); T = (tau sqrt(pi / 2) +
+ *            2 sqrt((2 - pi / 2) tau^2)) / 1.7; EnergyAll += max(Energy - T, 0), AnAll += sumAn; PC = EnergyAll / AnAll.
+ *            S2 = sum_s sum_px a_s^2, Sij = sum_{s<t} sum_px a_s a_t with a_s = real(ifft2(filter_{s,o})) sqrt(rows cols); by
+ *            Parseval sum_px a_s a_t = sum_u g_s(u) g_t(u), g(u) = (f(u) + f(-u)) / 2 with wrap-around, so EM_n, S2 and Sij
+ *            depend on (rows, cols) alone and are host work without a transform.
+ *            The transform is a float64 dense DFT in two passes (products added in ascending index order with fma, against a
+ *            table (cos, sin)(2 pi ((u r) mod n) / n) whose index is reduced in integers); the first sample of the plane is
+ *            subtracted from every sample before it (the filters are 0 at DC), so a flat plane gives AnAll = 0 exactly.
+ *   G        Scharr dx = [3 0 -3; 10 0 -10; 3 0 -3] / 16, dy = dx', on the pooled Y by conv2(., 'same') with a zero border;
+ *            G = sqrt(Ix^2 + Iy^2).
+ *   score    S_pc = (2 PC1 PC2 + 0.85) / (PC1^2 + PC2^2 + 0.85), S_g = (2 G1 G2 + 160) / (G1^2 + G2^2 + 160), PCm =
+ *            max(PC1, PC2); S_i, S_q the same form on the pooled I, Q with 200.  FSIM = sum(S_g S_pc PCm) / sum PCm;
+ *            FSIMc = sum(S_g S_pc Re((S_i S_q)^0.03) PCm) / sum PCm, where a negative S_i S_q = z has the real part
+ *            |z|^0.03 cos(0.03 pi).  Identical images give 1 to 1e-12; a flat image has AnAll = 0 and the value is NaN, as
+ *            MATLAB's is. */
+typedef struct sr_fsim_sums {
+    double sum_s;       /* sum S_g S_pc PCm */
+    double sum_sc;      /* sum S_g S_pc Re((S_i S_q)^0.03) PCm */
+    double sum_pcm;     /* sum PCm */
+    uint64_t count;     /* rows * cols */
+    int32_t F, rows, cols, reserved;
+} sr_fsim_sums;
+/* Host only, no context: F, the pooled size and the bytes of context workspace a call will hold (each output may be NULL).
+ * Carries every refusal that depends on the shape: SR_ERR_INVALID_ARG for cn not 1, 3 or 4 or h, w < 1; SR_ERR_SHAPE for a
+ * side below 16; SR_ERR_UNSUPPORTED, naming the cap, for a pooled side above 2048 or F above 256. */
+SR_API int sr_fsim_plan(int h, int w, int cn, int *F, int *rows, int *cols, size_t *workspace_bytes);
+/* Host only, for inspection: logGabor_s (log_gabor[4][rows * cols]) and spread_o (spread[4][rows * cols]), both as the
+ * transform indexes them (DC first), and EM_n, S2, Sij of the four orientations (em, s2, sij: 4 each).  Each output may be
+ * NULL.  rows, cols outside 16 .. 2048: SR_ERR_SHAPE below, SR_ERR_UNSUPPORTED above. */
+SR_API int sr_fsim_filters(int rows, int cols, double *log_gabor, double *spread, double *em, double *s2, double *sij);
+/* Inspection entry of the pooling with an EXPLICIT F in 1 .. 256 and no minimum side: h_out[2][3][rows * cols] takes the
+ * int64 window sums of Y 1000, I 1000, Q 1000 of a, then of b, rows x cols = ceil(h / F) x ceil(w / F).  One pass: every
+ * source byte is read at most once.  Synchronous.  Refused before any device call: null pointers, cn not 1, 3 or 4, h or
+ * w < 1, F outside 1 .. 256 (SR_ERR_INVALID_ARG), a stride shorter than a row (SR_ERR_SHAPE). */
+SR_API int sr_fsim_pool_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
+                           int cn, int F, int64_t *h_out);
+/* PC of one dense float64 device plane of rows x cols into the dense device plane d_pc, plus the four orientations'
+ * medianE2n (h_median[4]) and thresholds T (h_T[4]; either may be NULL).  Synchronous; equal inputs give equal bits.
+ * Refusals as sr_fsim_filters, and null pointers. */
+SR_API int sr_fsim_pc_f64(sr_ctx *ctx, const double *d_plane, int rows, int cols, double *d_pc, double *h_median, double *h_T);
+/* The record of the three sums of the pair.  Strides are arbitrary (at least a row); pixels are read byte by byte, so no
+ * alignment is assumed.  Integer histograms select the medians and fixed trees add the sums, no floating-point atomics: equal
+ * inputs give equal bits.  Synchronous; the workspace belongs to the context and grows on demand.  Refused before any device
+ * call: null pointers, everything sr_fsim_plan refuses, a stride shorter than a row (SR_ERR_SHAPE). */
+SR_API int sr_fsim_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
+                      int cn, sr_fsim_sums *h_out);
+/* Host only: *fsim = sum_s / sum_pcm, *fsimc = sum_sc / sum_pcm (either may be NULL); NaN for a flat pair (0 / 0) and when a
+ * sum is NaN.  SR_ERR_INVALID_ARG for a null record. */
+SR_API int sr_fsim_value(const sr_fsim_sums *sums, double *fsim, double *fsimc);
+/* Host only: Re((s_i s_q)^0.03), the chroma weight of one sample as the score kernel forms it. */
+SR_API double sr_fsim_chroma_weight(double s_i, double s_q);
 /* ---- NIQE, the no-reference quality model (csrc/sr_niqe.hip, csrc/sr_niqe_host.cpp) -------------------------------------------
  * Mittal, Soundararajan, Bovik 2013, in the arithmetic of MATLAB's computequality / estimatemodelparam and BasicSR's
  * calculate_niqe, made exact wherever it can be.  The reference's calculate_niqe asks pyiqa for this model first; the 'niqe'

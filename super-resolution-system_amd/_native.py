@@ -83,6 +83,12 @@ class GmsdSums(C.Structure):
     _fields_ = [("sum_d", C.c_double), ("sum_d2", C.c_double), ("count", C.c_uint64)]
 
 
+class FsimSums(C.Structure):
+    """sr_fsim_sums (include/sr_hip.h)."""
+    _fields_ = [("sum_s", C.c_double), ("sum_sc", C.c_double), ("sum_pcm", C.c_double), ("count", C.c_uint64),
+                ("F", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32)]
+
+
 VIF_SCALES = 4
 # enum sr_bench_mode (include/sr_hip.h)
 BENCH_CHANNELS, BENCH_Y, BENCH_Y_ROUND = 0, 1, 2
@@ -278,6 +284,13 @@ SIGNATURES = {
     "sr_gmsd_plan": (_i, [_i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), C.POINTER(_sz)]),
     "sr_gmsd_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, C.POINTER(GmsdSums)]),
     "sr_gmsd_value": (_dbl, [C.POINTER(GmsdSums)]),
+    "sr_fsim_plan": (_i, [_i, _i, _i, _pi, _pi, _pi, C.POINTER(_sz)]),
+    "sr_fsim_filters": (_i, [_i, _i, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "sr_fsim_pool_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "sr_fsim_pc_f64": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "sr_fsim_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, C.POINTER(FsimSums)]),
+    "sr_fsim_value": (_i, [C.POINTER(FsimSums), C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "sr_fsim_chroma_weight": (_dbl, [_dbl, _dbl]),
     "sr_niqe_plan": (_i, [_i, _i, _i, _i, _pi, _pi, _pi, _pi, C.POINTER(_sz)]),
     "sr_niqe_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sr_niqe_half_plane": (_i, [_vp, _vp]),
@@ -746,6 +759,44 @@ def gmsd_value(sums: dict) -> float:
     if v != v:
         raise ValueError(last_error())
     return v
+
+
+def fsim_plan(h: int, w: int, cn: int) -> dict:
+    """Host only (sr_fsim_plan): F, the pooled size and the bytes of context workspace of an FSIM call.  ValueError for cn not
+    1, 3 or 4; SrShapeError (a ValueError) naming the minimum for a side below 16; SrNativeError naming the cap for a pooled
+    side above 2048."""
+    h, w, cn = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn")))
+    f, rows, cols, nbytes = C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    check(load().sr_fsim_plan(h, w, cn, C.byref(f), C.byref(rows), C.byref(cols), C.byref(nbytes)))
+    return {"F": f.value, "size": (rows.value, cols.value), "workspace_bytes": int(nbytes.value)}
+
+
+def fsim_filters(rows: int, cols: int) -> dict:
+    """Host only (sr_fsim_filters): {'log_gabor': [4, rows, cols], 'spread': [4, rows, cols], 'em', 's2', 'sij': [4]} of a
+    pooled size, the planes as the transform indexes them (DC first).  SrShapeError for a side below 16, SrNativeError above
+    2048."""
+    rows, cols = _whole(rows, "rows"), _whole(cols, "cols")
+    if rows < 1 or cols < 1:
+        raise ValueError("fsim_filters: need rows, cols >= 1")
+    lg, sp = np.zeros((4, rows, cols), np.float64), np.zeros((4, rows, cols), np.float64)
+    em, s2, sij = np.zeros(4, np.float64), np.zeros(4, np.float64), np.zeros(4, np.float64)
+    dp = C.POINTER(C.c_double)
+    check(load().sr_fsim_filters(rows, cols, lg.ctypes.data_as(dp), sp.ctypes.data_as(dp), em.ctypes.data_as(dp),
+                                 s2.ctypes.data_as(dp), sij.ctypes.data_as(dp)))
+    return {"log_gabor": lg, "spread": sp, "em": em, "s2": s2, "sij": sij}
+
+
+def fsim_value(sums: dict) -> Tuple[float, float]:
+    """Host only (sr_fsim_value): (FSIM, FSIMc) of an fsim_u8 record; NaN for a flat pair."""
+    rec = FsimSums(float(sums["sum_s"]), float(sums["sum_sc"]), float(sums["sum_pcm"]), int(sums.get("count", 0)), 0, 0, 0, 0)
+    a, b = C.c_double(0.0), C.c_double(0.0)
+    check(load().sr_fsim_value(C.byref(rec), C.byref(a), C.byref(b)))
+    return float(a.value), float(b.value)
+
+
+def fsim_chroma_weight(s_i: float, s_q: float) -> float:
+    """Host only (sr_fsim_chroma_weight): Re((s_i s_q)^0.03) as the score kernel forms it."""
+    return float(load().sr_fsim_chroma_weight(float(s_i), float(s_q)))
 
 
 def imresize_size(n: int, scale: float) -> int:
@@ -1271,6 +1322,41 @@ class Context:
         check(self.lib.sr_gmsd_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
                                   int(cn), crop_border, mode, C.byref(out)))
         return {"sum_d": out.sum_d, "sum_d2": out.sum_d2, "count": int(out.count)}
+
+    def fsim_pool_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, F) -> np.ndarray:
+        """sr_fsim_pool_u8 -> int64 [2 images, 3 (Y, I, Q times 1000), rows, cols]: the window sums of FSIM's pooling with an
+        explicit F (1 .. 256), rows x cols = ceil(h / F) x ceil(w / F).  Every argument is checked before the device is touched."""
+        h, w, cn, F = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn"), (F, "F")))
+        if not d_a or not d_b:
+            raise ValueError("fsim_pool_u8: null image pointer")
+        if h < 1 or w < 1 or F < 1:
+            raise ValueError("fsim_pool_u8: need h, w, F >= 1")
+        out = np.zeros((2, 3, (h + F - 1) // F, (w + F - 1) // F), np.int64)
+        check(self.lib.sr_fsim_pool_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), h, w, cn, F,
+                                       out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def fsim_pc_f64(self, d_plane, rows, cols, d_pc) -> dict:
+        """sr_fsim_pc_f64: the phase congruency of the dense float64 device plane d_plane (rows x cols) into the dense device
+        plane d_pc -> {'median': [4], 'T': [4]} of the four orientations."""
+        rows, cols = _whole(rows, "rows"), _whole(cols, "cols")
+        if not d_plane or not d_pc:
+            raise ValueError("fsim_pc_f64: null plane pointer")
+        med, thr = (C.c_double * 4)(), (C.c_double * 4)()
+        check(self.lib.sr_fsim_pc_f64(self.handle, C.c_void_p(d_plane), rows, cols, C.c_void_p(d_pc), med, thr))
+        return {"median": np.array(med[:], np.float64), "T": np.array(thr[:], np.float64)}
+
+    def fsim_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn) -> dict:
+        """sr_fsim_u8 -> {'sum_s', 'sum_sc', 'sum_pcm', 'count', 'F', 'size'} of the pair (finish with fsim_value).  Every argument
+        is checked before the device is touched: ValueError, its subclass SrShapeError for a short stride or a side below 16,
+        SrNativeError for a pooled side above 2048."""
+        if not d_a or not d_b:
+            raise ValueError("fsim_u8: null image pointer")
+        out = FsimSums()
+        check(self.lib.sr_fsim_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
+                                  int(cn), C.byref(out)))
+        return {"sum_s": out.sum_s, "sum_sc": out.sum_sc, "sum_pcm": out.sum_pcm, "count": int(out.count), "F": int(out.F),
+                "size": (int(out.rows), int(out.cols))}
 
     def niqe_u8(self, d_img, stride, h, w, cn, crop_border=0) -> np.ndarray:
         """sr_niqe_u8 -> records[2, nby * nbx] (NIQE_RECORD, scale-major) of the image cropped by crop_border (finish with

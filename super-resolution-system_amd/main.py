@@ -75,6 +75,7 @@ class PipelineConfig:
     qa_vif: bool = False       # (with enable_qa): stage 4 also reports the 4-scale pixel-domain VIF of the canvas against the INTER_CUBIC
                                # resize of the source (the reference), on the exact luma ('vifp', 'vifp_scales')
     qa_gmsd: bool = False      # (with enable_qa): ... and the gradient magnitude similarity deviation of the same pair ('gmsd')
+    qa_fsim: bool = False      # (with enable_qa): ... and the phase-congruency feature similarity of the same pair ('fsim', 'fsimc')
     qa_niqe_params: str = ""   # (with enable_qa): path of NIQE's pristine parameters (.npz with BasicSR's keys, or .mat): stage 4 also
                                # reports the NIQE of the canvas ('niqe_model'; the 'niqe' key keeps the reference's stand-in heuristic)
     qa_brisque_model: str = "" # (with enable_qa): path of a BRISQUE regressor (.npz: sv, sv_coef, gamma, rho, feature_min, feature_max): stage 4
@@ -308,6 +309,32 @@ class SuperResolutionPipeline:
                     report['vifp_note'] = "the reference is flat at every scale: VIF is 0 / 0"
             if 'gmsd' in todo:
                 report['gmsd'] = float(q.calculate_gmsd_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn)))
+        finally:
+            ctx.sync()
+            ref.free()
+
+    def _fsim(self, ctx, report: Dict[str, Any], d_src: int, src_shape, d_canvas: int, canvas_shape) -> None:
+        """Stage 4's optional 'fsim' / 'fsimc' entries (qa_fsim): FSIM and FSIMc of the canvas against the INTER_CUBIC resize of
+        the source to the canvas size, both in HBM.  A refusal of the plan (a side below 16, a pooled long side above 2048) or a
+        NaN value (a flat pair) gives None for both and 'fsim_note' says why (the run does not fail).  Neither value enters
+        overall_score.  One helper for the device-resident, the host-array and the sharded path."""
+        import _native
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        ih, iw = int(src_shape[0]), int(src_shape[1])
+        report['fsim'], report['fsimc'] = None, None
+        try:
+            _native.fsim_plan(H, W, cn)
+        except (ValueError, _native.SrNativeError) as exc:
+            report['fsim_note'] = str(exc)
+            return
+        ref = ctx.alloc(H * W * cn)
+        try:
+            ctx.resize_cubic_u8(d_src, iw * cn, ih, iw, cn, ref.ptr, W * cn, H, W)
+            v = self.quality_module.calculate_fsim_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn))
+            if v['fsim'] == v['fsim'] and v['fsimc'] == v['fsimc']:
+                report['fsim'], report['fsimc'] = float(v['fsim']), float(v['fsimc'])
+            else:
+                report['fsim_note'] = "the pair is flat: FSIM is 0 / 0"
         finally:
             ctx.sync()
             ref.free()
@@ -547,6 +574,8 @@ class SuperResolutionPipeline:
                     self._sr_benchmark(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_vif or self.config.qa_gmsd:
                     self._vif_gmsd(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
+                if self.config.qa_fsim:
+                    self._fsim(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_niqe_params:
                     self._niqe_model(ctx, report, canvas.ptr, (H, W, 3))
                 if self.config.qa_brisque_model:
@@ -655,6 +684,8 @@ class SuperResolutionPipeline:
                         self._sr_benchmark(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_vif or self.config.qa_gmsd:
                         self._vif_gmsd(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
+                    if self.config.qa_fsim:
+                        self._fsim(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_niqe_params:
                         self._niqe_model(qctx, report, canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_brisque_model:
@@ -762,6 +793,13 @@ class SuperResolutionPipeline:
                         self._vif_gmsd(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
                     finally:
                         d_src.free(); d_fused.free()
+                if self.config.qa_fsim:
+                    qctx = self.quality_module._ctx()
+                    d_src, d_fused = qctx.upload(original), qctx.upload(fused)
+                    try:
+                        self._fsim(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
+                    finally:
+                        d_src.free(); d_fused.free()
                 if self.config.qa_niqe_params:
                     qctx = self.quality_module._ctx()
                     d_fused = qctx.upload(fused)
@@ -831,6 +869,9 @@ async def main() -> int:
     ap.add_argument("--qa-vif", action="store_true",
                     help="stage 4 also reports the 4-scale pixel-domain VIF (vifp_mscale) of the result against the bicubic resize "
                          "of the input, which is the reference (report keys vifp, vifp_scales)")
+    ap.add_argument("--qa-fsim", action="store_true",
+                    help="stage 4 also reports FSIM and FSIMc (phase-congruency feature similarity) of the result against the "
+                         "bicubic resize of the input (report keys fsim, fsimc)")
     ap.add_argument("--qa-gmsd", action="store_true",
                     help="stage 4 also reports the gradient magnitude similarity deviation of the result against the bicubic "
                          "resize of the input (report key gmsd)")
@@ -871,7 +912,7 @@ async def main() -> int:
         return 2
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act, sr_ensemble=args.sr_ensemble,
-                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark, qa_vif=args.qa_vif, qa_gmsd=args.qa_gmsd,
+                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark, qa_vif=args.qa_vif, qa_gmsd=args.qa_gmsd, qa_fsim=args.qa_fsim,
                          qa_niqe_params=args.qa_niqe_params, qa_brisque_model=args.qa_brisque_model, qa_dists_weights=args.qa_dists_weights,
                          benchmark_degrade=args.benchmark_degrade)
     if args.plan_only:

@@ -644,6 +644,59 @@ class QualityAssessmentModule:
             raise ValueError("calculate_gmsd: null device pointer")
         return self._gmsd_dev(self._ctx(), int(d_img1), int(d_img2), args)
 
+    # -- FSIM / FSIMc (no reference counterpart: the authors' FeatureSIM.m) ---------------------------------------------------
+    @staticmethod
+    def _fsim_args(shape1, shape2, stride1, stride2) -> Tuple[int, int, int, int, int]:
+        """Every refusal of the FSIM methods, on the host: ValueError (SrShapeError for a side below 16 or a short stride),
+        SrNativeError for a pooled side above 2048.  -> (h, w, cn, stride1, stride2)."""
+        shape1, shape2 = tuple(int(v) for v in shape1), tuple(int(v) for v in shape2)
+        if shape1 != shape2:
+            raise ValueError(f"calculate_fsim: images must have the same shape, got {shape1} vs {shape2} "
+                             "(nothing is cropped to a common rectangle)")
+        if len(shape1) not in (2, 3):
+            raise ValueError(f"calculate_fsim: need an H x W or H x W x C image, got shape {shape1}")
+        cn = shape1[2] if len(shape1) == 3 else 1
+        _native.fsim_plan(shape1[0], shape1[1], cn)
+        row = shape1[1] * cn
+        s1, s2 = (row if s is None else int(s) for s in (stride1, stride2))
+        if s1 < row or s2 < row:
+            raise _native.SrShapeError("calculate_fsim: stride smaller than a row")
+        return shape1[0], shape1[1], cn, s1, s2
+
+    @staticmethod
+    def _fsim_dev(ctx, d1: int, d2: int, args, return_parts: bool) -> Dict[str, Any]:
+        h, w, cn, s1, s2 = args
+        parts = ctx.fsim_u8(d1, s1, d2, s2, h, w, cn)
+        v, vc = _native.fsim_value(parts)
+        out = {'fsim': v, 'fsimc': vc}
+        if return_parts:
+            out['parts'] = parts
+        return out
+
+    def calculate_fsim(self, img1: np.ndarray, img2: np.ndarray, return_parts: bool = False) -> Dict[str, Any]:
+        """FSIM and FSIMc (Zhang et al. 2011, the authors' FeatureSIM.m), as include/sr_hip.h defines them -> {'fsim',
+        'fsimc'}: u8 images of equal shape with 1, 3 (RGB) or 4 channels (alpha ignored), both sides at least 16; a gray
+        pair has fsimc == fsim.  Symmetric; 1 for identical images, NaN for a flat pair.  return_parts adds 'parts', the
+        record of the three sums with F and the pooled size."""
+        a = self._require_u8(np.asarray(img1), "calculate_fsim")
+        b = self._require_u8(np.asarray(img2), "calculate_fsim")
+        args = self._fsim_args(a.shape, b.shape, None, None)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._fsim_dev(ctx, da.ptr, db.ptr, args, return_parts)
+        finally:
+            da.free(); db.free()
+
+    def calculate_fsim_device(self, d_img1: int, shape1, d_img2: int, shape2, return_parts: bool = False,
+                              stride1: Optional[int] = None, stride2: Optional[int] = None) -> Dict[str, Any]:
+        """calculate_fsim on two u8 images that already live in HBM (device addresses + shapes; strides in bytes, dense when
+        None)."""
+        args = self._fsim_args(shape1, shape2, stride1, stride2)
+        if not d_img1 or not d_img2:
+            raise ValueError("calculate_fsim: null device pointer")
+        return self._fsim_dev(self._ctx(), int(d_img1), int(d_img2), args, return_parts)
+
     # -- NIQE, the model (no reference counterpart in code: the reference delegates to pyiqa.create_metric('niqe')) ----------
     @staticmethod
     def _niqe_args(shape, crop_border) -> Tuple[int, int, int, int]:

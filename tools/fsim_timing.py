@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Device time of FSIM / FSIMc (sr_fsim_u8) beside the SR-benchmark PSNR / SSIM (sr_bench_u8, SR_BENCH_Y) on the same buffers
+in the same process, on one 200 MP RGB pair (17320 x 11550 x 3): a noisy image resized on the device and its bicubic partner
+(down to a quarter and back up), the pair stage 4 sees.  The two calls alternate in one run.  Warm-up 2, then 7 repetitions
+timed with HIP events (the library's own per-family event pairs: fsim_pool the one pass over the images, fsim_dft the 34 dense
+transforms, fsim_median the 8 radix selects, fsim_rest the plane, energy, clamp and score kernels with their reduction), median
+and minimum reported, and the wall time of each synchronous call.  Writes profiles/fsim_timing.json (or the path given as the
+third argument).
+usage (GPU box): python tools/fsim_timing.py [W H [out.json]]"""
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "super-resolution-system_amd")):
+    sys.path.insert(0, p)
+import numpy as np            # noqa: E402
+import _native                # noqa: E402
+
+WARM, RUNS = 2, 7
+W, H = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) >= 3 else (17320, 11550)
+OUT = sys.argv[3] if len(sys.argv) >= 4 else os.path.join(ROOT, "profiles", "fsim_timing.json")
+ctx = _native.default_context(0)
+
+
+def pair():
+    rng = np.random.default_rng(1)
+    h, w = max(H // 10, 8), max(W // 10, 8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    small = np.clip((128 + 64 * np.sin(xx / 37.0) + 48 * np.cos(yy / 23.0))[..., None] + rng.integers(-12, 13, (h, w, 3)),
+                    0, 255).astype(np.uint8)
+    src, a, b = ctx.upload(small), ctx.alloc(H * W * 3), ctx.alloc(H * W * 3)
+    q = ctx.alloc((H // 4) * (W // 4) * 3)
+    ctx.resize_cubic_u8(src.ptr, w * 3, h, w, 3, a.ptr, W * 3, H, W)
+    ctx.resize_cubic_u8(a.ptr, W * 3, H, W, 3, q.ptr, (W // 4) * 3, H // 4, W // 4)
+    ctx.resize_cubic_u8(q.ptr, (W // 4) * 3, H // 4, W // 4, 3, b.ptr, W * 3, H, W)
+    ctx.sync()
+    src.free(); q.free()
+    return a, b
+
+
+def med_min(v):
+    return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4)}
+
+
+a, b = pair()
+box = {}
+PARTS = ["fsim_pool", "fsim_dft", "fsim_median", "fsim_rest"]
+CALLS = [("fsim", lambda: box.__setitem__("fsim", ctx.fsim_u8(a.ptr, W * 3, b.ptr, W * 3, H, W, 3)), PARTS),
+         ("bench_y", lambda: box.__setitem__("bench_y", ctx.bench_u8(a.ptr, W * 3, b.ptr, W * 3, H, W, 3, 0, _native.BENCH_Y)),
+          ["srbench"])]
+for _ in range(WARM):
+    for _, fn, _ in CALLS:
+        fn()
+ctx.sync()
+dev = {}
+wall = {n: [] for n, _, _ in CALLS}
+ctx.prof_enable(True)
+for r in range(RUNS):
+    for k in range(len(CALLS)):
+        name, fn, families = CALLS[(k + r) % len(CALLS)]
+        ctx.prof_reset()
+        t0 = time.perf_counter()
+        fn()
+        wall[name].append(1e3 * (time.perf_counter() - t0))
+        ctx.sync()
+        got = ctx.prof_get()
+        for fam in families:
+            dev.setdefault(fam if fam != "srbench" else "bench_y", []).append(got[fam][0])
+        if name == "fsim":
+            dev.setdefault("fsim", []).append(sum(got[fam][0] for fam in PARTS))
+ctx.prof_enable(False)
+bench = statistics.median(dev["bench_y"])
+plan = _native.fsim_plan(H, W, 3)
+res = {"image": [H, W, 3], "F": plan["F"], "pooled": list(plan["size"]), "workspace_bytes": plan["workspace_bytes"],
+       "transform": "float64 dense DFT, plain FMA loop (no MFMA), 16 x 16 outputs per block",
+       "values": dict(zip(("fsim", "fsimc"), _native.fsim_value(box["fsim"])),
+                      bench_y=dict(zip(("psnr", "ssim"), _native.bench_values(box["bench_y"])))),
+       "device": {n: med_min(dev[n]) for n in dev}, "wall": {n: med_min(wall[n]) for n in wall},
+       "ratio_over_bench_y": {n: round(statistics.median(dev[n]) / bench, 3) for n in dev if n != "bench_y"},
+       "pool_input_gb_per_s": round(2 * H * W * 3 / (statistics.median(dev["fsim_pool"]) * 1e-3) / 1e9, 1),
+       "method": f"warm-up {WARM}, {RUNS} alternating repetitions, HIP events (sr_prof) around each family's launches, median and "
+                 "minimum; fsim = the sum of its four families in each repetition; wall = the synchronous call as the host "
+                 "sees it; pool_input_gb_per_s = both images' bytes once over the pooling's median device time"}
+a.free(); b.free()
+os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+with open(OUT, "w") as f:
+    json.dump(res, f, indent=1)
+print(json.dumps(res))
