@@ -775,6 +775,88 @@ SR_API int sr_fsim_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const u
 SR_API int sr_fsim_value(const sr_fsim_sums *sums, double *fsim, double *fsimc);
 /* Host only: Re((s_i s_q)^0.03), the chroma weight of one sample as the score kernel forms it. */
 SR_API double sr_fsim_chroma_weight(double s_i, double s_q);
+/* ---- colour difference: CIEDE2000 and CIE76 per pixel (csrc/sr_deltae.hip, csrc/sr_deltae_host.cpp, csrc/sr_deltae.h) ---------
+ * A full-reference, per-pixel colour difference of two images, in the arithmetic of scikit-image 0.18.3 (rgb2lab of a uint8
+ * image, deltaE_ciede2000 / deltaE_cie76, float64).  PARITY PINNED: tests/golden/deltae_skimage.npz holds scikit-image's own
+ * Lab and both difference maps.  NOT the private brand-colour number of the commercial metrics (brand_color_delta_e_i), which
+ * compares a region MEAN in OpenCV's 8-bit integer Lab with one colour, by CIE76.
+ * Inputs: two u8 images of equal shape h x w x cn, strides in bytes.  cn = 1: gray, used as R = G = B; 3: RGB; 4: RGBA, alpha
+ * ignored.  crop_border = cb >= 0: rows [cb, h - cb), columns [cb, w - cb); both cropped sides must be >= 1 (SR_ERR_SHAPE).
+ * Lab: v = c / 255; linear = ((v + 0.055) / 1.055)^2.4 where v > 0.04045, else v / 12.92 (the 256 values are a table built
+ * once on the host in double); XYZ = M rgb with M = [[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169],
+ * [0.019334, 0.119193, 0.950227]], each row summed left to right; divided by the D65 / 2 degree white (0.95047, 1, 1.08883);
+ * f(t) = cbrt(t) where t > 0.008856, else 7.787 t + 16 / 116; L = 116 f(y) - 16, a = 500 (f(x) - f(y)), b = 200 (f(y) - f(z)).
+ * With this matrix only black has a = b = 0 exactly: a gray pixel keeps a small chroma (about 1e-3), as the definition gives it.
+ * SR_DELTA_E_76: sqrt(dL^2 + da^2 + db^2).
+ * SR_DELTA_E_2000 (kL = kC = kH = 1): Cbar = (hypot(a1, b1) + hypot(a2, b2)) / 2, c7 = Cbar^7,
+ * G = (1 - sqrt(c7 / (c7 + 25^7))) / 2; a' = a (1 + G); C' = hypot(a', b); h = atan2(b, a') moved into [0, 2 pi);
+ * Lbar = (L1 + L2) / 2, SL = 1 + 0.015 (Lbar - 50)^2 / sqrt(20 + (Lbar - 50)^2), L_term = (L2 - L1) / SL;
+ * Cbar' = (C1' + C2') / 2, SC = 1 + 0.045 Cbar', C_term = (C2' - C1') / SC; h_diff = h2 - h1, h_sum = h1 + h2;
+ * dH = h_diff, - 2 pi where h_diff > pi, + 2 pi where h_diff < -pi (STRICT comparisons), 0 where C1' C2' == 0;
+ * dH_term = 2 sqrt(C1' C2') sin(dH / 2); Hbar = h_sum, + 2 pi (h_sum < 2 pi) or - 2 pi (otherwise) only where C1' C2' != 0 and
+ * |h_diff| > pi, then halved -- except where C1' C2' == 0, where Hbar is the SUM of the two hues;
+ * T = 1 - 0.17 cos(Hbar - 30 deg) + 0.24 cos(2 Hbar) + 0.32 cos(3 Hbar + 6 deg) - 0.20 cos(4 Hbar - 63 deg);
+ * SH = 1 + 0.015 Cbar' T, H_term = dH_term / SH; Rc = 2 sqrt(c7' / (c7' + 25^7)) with c7' = Cbar'^7;
+ * dtheta = 30 deg * exp(-((Hbar in degrees - 275) / 25)^2); R = -sin(2 dtheta) Rc C_term H_term;
+ * dE = sqrt(max(L_term^2 + C_term^2 + H_term^2 + R, 0)).  Where scikit-image and Sharma, Wu and Dalal's note differ this
+ * follows scikit-image: the sum (not the mean) of the hues where a chroma is 0, and the strict comparisons at |h_diff| = pi.
+ * hypot is evaluated as sqrt(x^2 + y^2) and the 7th power by multiplication.  A pixel pair with equal bytes gives EXACTLY 0
+ * for both formulas (the arithmetic is skipped).  Out of scope: kL / kC / kH other than 1, CIE94 and CMC (any other formula
+ * value is SR_ERR_UNSUPPORTED), other illuminants, float and 16-bit inputs.
+ * The record over the cropped rectangle: count; sum and sum2 of dE; max; hist: bin min(floor(16 dE), 2047) -- width 1 / 16,
+ * the last bin open (sRGB extremes reach dE00 of about 106.7, so 128 covers them).  No floating-point atomics, integer ones
+ * only (the histogram); partial sums are combined in a fixed order that depends on the size alone: equal inputs give equal
+ * bits. */
+#define SR_DELTA_E_BINS 2048
+enum sr_delta_e_formula { SR_DELTA_E_2000 = 0, SR_DELTA_E_76 = 1 };
+typedef struct sr_delta_e_sums {
+    uint64_t count;
+    double sum, sum2, max;
+    uint64_t hist[SR_DELTA_E_BINS];
+} sr_delta_e_sums;
+typedef struct sr_delta_e_cell {
+    double sum, max;
+} sr_delta_e_cell;
+/* Host only, no context: the cropped size, the pixel count, the blocks of the sums launch and the bytes of context scratch a
+ * call will hold (each output may be NULL).  Carries every refusal that depends on these arguments: SR_ERR_INVALID_ARG for
+ * cn not 1, 3 or 4, crop_border < 0, h or w < 1; SR_ERR_UNSUPPORTED for an unknown formula; SR_ERR_SHAPE for a side below 1
+ * after the crop. */
+SR_API int sr_delta_e_plan(int h, int w, int cn, int crop_border, int formula, int *crop_h, int *crop_w, uint64_t *count,
+                           int *blocks, size_t *scratch_bytes);
+/* Host only: the 256 linear values of the sRGB bytes, as the kernels index them. */
+SR_API int sr_delta_e_table(double *table256);
+/* Host only: the Lab of one sRGB pixel, and the difference of two Labs by `formula`, restating the definition in float64 (the
+ * same expressions the kernels evaluate; arbitrary Lab values are taken as they are, nothing is skipped). */
+SR_API int sr_delta_e_lab_u8(int r, int g, int b, double *lab3);
+SR_API int sr_delta_e_pair(const double *lab1, const double *lab2, int formula, double *out);
+/* The record of the pair.  d_map (may be NULL): float64, map_stride bytes per row (a multiple of 8, at least 8 cw; the pointer
+ * 8-byte aligned), receives the dE of every cropped pixel, ch x cw.  The crop is pointer arithmetic; pixels are read byte by
+ * byte; strides are arbitrary (at least a row).  Synchronous; the table, the histogram and the per-block partials are context
+ * scratch, grown on demand.  Refused before any device call: null pointers, everything sr_delta_e_plan refuses, a stride
+ * shorter than a row of the uncropped image (SR_ERR_SHAPE), a misaligned or short map stride (SR_ERR_INVALID_ARG /
+ * SR_ERR_SHAPE). */
+SR_API int sr_delta_e_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
+                         int cn, int crop_border, int formula, double *d_map, int64_t map_stride, sr_delta_e_sums *h_out);
+/* Per cell of a separable grid, as sr_quality_map_u8 takes it: strictly increasing host edge lists h_xedges[0..gw] (0 .. cw)
+ * and h_yedges[0..gh] (0 .. ch) over the CROPPED rectangle.  h_out: gh * gw records, row-major: the sum and the largest dE of
+ * the cell's pixels.  dE is pointwise, so the cell sums add up to the record's sum within the order of fp64 additions and the
+ * largest cell max equals the record's max exactly; a cell's pixel count is its area.  Refused before any device call:
+ * everything sr_delta_e_u8 refuses, edges that are not strictly increasing or do not span the cropped side
+ * (SR_ERR_INVALID_ARG), and what one launch does not cover (SR_ERR_UNSUPPORTED, naming the cap): more than 2^24 - 1 cells, more
+ * than 2^24 - 1 row chunks (cell rows in pieces of 64 rows), more than 65535 * 256 columns. */
+SR_API int sr_delta_e_cells_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h,
+                               int w, int cn, int crop_border, int formula, const int *h_xedges, int gw, const int *h_yedges,
+                               int gh, sr_delta_e_cell *h_out);
+/* Host only.  mean = sum / count; rms = sqrt(sum2 / count); NaN with sr_last_error for a null record or count 0. */
+SR_API double sr_delta_e_mean(const sr_delta_e_sums *sums);
+SR_API double sr_delta_e_rms(const sr_delta_e_sums *sums);
+/* Host only: for p in (0, 100], k = max(1, ceil(p count / 100)), j = the first bin whose cumulative count reaches k; the
+ * result is the bin's LOWER edge j / 16 (the true percentile lies in [j / 16, (j + 1) / 16); identical images give 0).  NaN
+ * with sr_last_error for a null record, count 0, p outside (0, 100] or a histogram that does not add up to count. */
+SR_API double sr_delta_e_percentile(const sr_delta_e_sums *sums, double p);
+/* Host only: the fraction of pixels with dE >= t, exact from the histogram, for t a multiple of 1 / 16 in [0, 128); any other
+ * t is SR_ERR_INVALID_ARG. */
+SR_API int sr_delta_e_fraction_at_least(const sr_delta_e_sums *sums, double t, double *fraction);
 /* ---- NIQE, the no-reference quality model (csrc/sr_niqe.hip, csrc/sr_niqe_host.cpp) -------------------------------------------
  * Mittal, Soundararajan, Bovik 2013, in the arithmetic of MATLAB's computequality / estimatemodelparam and BasicSR's
  * calculate_niqe, made exact wherever it can be.  The reference's calculate_niqe asks pyiqa for this model first; the 'niqe'

@@ -89,6 +89,23 @@ class FsimSums(C.Structure):
                 ("F", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32)]
 
 
+DELTA_E_BINS = 2048
+
+
+class DeltaESums(C.Structure):
+    """sr_delta_e_sums (include/sr_hip.h)."""
+    _fields_ = [("count", C.c_uint64), ("sum", C.c_double), ("sum2", C.c_double), ("max", C.c_double),
+                ("hist", C.c_uint64 * DELTA_E_BINS)]
+
+
+class DeltaECell(C.Structure):
+    """sr_delta_e_cell (include/sr_hip.h)."""
+    _fields_ = [("sum", C.c_double), ("max", C.c_double)]
+
+
+# enum sr_delta_e_formula (include/sr_hip.h)
+DELTA_E_2000, DELTA_E_76 = 0, 1
+DELTA_E_FORMULAS = {"ciede2000": DELTA_E_2000, "cie76": DELTA_E_76}
 VIF_SCALES = 4
 # enum sr_bench_mode (include/sr_hip.h)
 BENCH_CHANNELS, BENCH_Y, BENCH_Y_ROUND = 0, 1, 2
@@ -291,6 +308,16 @@ SIGNATURES = {
     "sr_fsim_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, C.POINTER(FsimSums)]),
     "sr_fsim_value": (_i, [C.POINTER(FsimSums), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "sr_fsim_chroma_weight": (_dbl, [_dbl, _dbl]),
+    "sr_delta_e_plan": (_i, [_i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), _pi, C.POINTER(_sz)]),
+    "sr_delta_e_table": (_i, [C.POINTER(_dbl)]),
+    "sr_delta_e_lab_u8": (_i, [_i, _i, _i, C.POINTER(_dbl)]),
+    "sr_delta_e_pair": (_i, [C.POINTER(_dbl), C.POINTER(_dbl), _i, C.POINTER(_dbl)]),
+    "sr_delta_e_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i64, C.POINTER(DeltaESums)]),
+    "sr_delta_e_cells_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _pi, _i, _pi, _i, C.POINTER(DeltaECell)]),
+    "sr_delta_e_mean": (_dbl, [C.POINTER(DeltaESums)]),
+    "sr_delta_e_rms": (_dbl, [C.POINTER(DeltaESums)]),
+    "sr_delta_e_percentile": (_dbl, [C.POINTER(DeltaESums), _dbl]),
+    "sr_delta_e_fraction_at_least": (_i, [C.POINTER(DeltaESums), _dbl, C.POINTER(_dbl)]),
     "sr_niqe_plan": (_i, [_i, _i, _i, _i, _pi, _pi, _pi, _pi, C.POINTER(_sz)]),
     "sr_niqe_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sr_niqe_half_plane": (_i, [_vp, _vp]),
@@ -797,6 +824,88 @@ def fsim_value(sums: dict) -> Tuple[float, float]:
 def fsim_chroma_weight(s_i: float, s_q: float) -> float:
     """Host only (sr_fsim_chroma_weight): Re((s_i s_q)^0.03) as the score kernel forms it."""
     return float(load().sr_fsim_chroma_weight(float(s_i), float(s_q)))
+
+
+def delta_e_formula(formula) -> int:
+    """'ciede2000' / 'cie76' (or the enum value) -> enum sr_delta_e_formula.  ValueError for another name; another number goes
+    through to the library, which refuses it (SR_ERR_UNSUPPORTED)."""
+    if isinstance(formula, str):
+        if formula not in DELTA_E_FORMULAS:
+            raise ValueError(f"delta E: unknown formula {formula!r}: {sorted(DELTA_E_FORMULAS)} are built (no CIE94, no CMC)")
+        return DELTA_E_FORMULAS[formula]
+    return _whole(formula, "formula")
+
+
+def delta_e_plan(h: int, w: int, cn: int, crop_border: int = 0, formula=DELTA_E_2000) -> dict:
+    """Host only (sr_delta_e_plan): the cropped size, the pixel count, the blocks of the sums launch and the bytes of context
+    scratch of a call.  ValueError for cn not 1, 3 or 4, a negative crop_border or h, w < 1; SrShapeError (a ValueError) for a
+    crop that leaves nothing; SrNativeError (SR_ERR_UNSUPPORTED) for an unknown formula."""
+    h, w, cn, crop_border = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn"), (crop_border, "crop_border")))
+    ch, cw, cnt, blocks, nbytes = C.c_int(0), C.c_int(0), C.c_uint64(0), C.c_int(0), C.c_size_t(0)
+    check(load().sr_delta_e_plan(h, w, cn, crop_border, delta_e_formula(formula), C.byref(ch), C.byref(cw), C.byref(cnt),
+                                 C.byref(blocks), C.byref(nbytes)))
+    return {"size": (ch.value, cw.value), "count": int(cnt.value), "blocks": blocks.value, "scratch_bytes": int(nbytes.value)}
+
+
+def delta_e_table() -> np.ndarray:
+    """Host only (sr_delta_e_table): the 256 linear values of the sRGB bytes."""
+    out = np.zeros(256, np.float64)
+    check(load().sr_delta_e_table(out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def delta_e_lab(r: int, g: int, b: int) -> np.ndarray:
+    """Host only (sr_delta_e_lab_u8): scikit-image's rgb2lab of one uint8 pixel -> [L, a, b].  ValueError outside 0 .. 255."""
+    out = (C.c_double * 3)()
+    check(load().sr_delta_e_lab_u8(_whole(r, "r"), _whole(g, "g"), _whole(b, "b"), out))
+    return np.array(out[:], np.float64)
+
+
+def delta_e_pair(lab1, lab2, formula=DELTA_E_2000) -> float:
+    """Host only (sr_delta_e_pair): the difference of two Lab triples by `formula`, in float64."""
+    l1, l2 = (np.asarray(v, np.float64).ravel() for v in (lab1, lab2))
+    if l1.size != 3 or l2.size != 3:
+        raise ValueError("delta_e_pair: need two Lab triples")
+    out = C.c_double(0.0)
+    check(load().sr_delta_e_pair((C.c_double * 3)(*l1), (C.c_double * 3)(*l2), delta_e_formula(formula), C.byref(out)))
+    return float(out.value)
+
+
+def _delta_e_record(sums: dict) -> "DeltaESums":
+    hist = np.asarray(sums["hist"])
+    if hist.shape != (DELTA_E_BINS,):
+        raise ValueError(f"delta E record: the histogram must have {DELTA_E_BINS} bins")
+    rec = DeltaESums(int(sums["count"]), float(sums["sum"]), float(sums["sum2"]), float(sums["max"]))
+    C.memmove(rec.hist, np.ascontiguousarray(hist, dtype=np.uint64).ctypes.data, DELTA_E_BINS * 8)
+    return rec
+
+
+def delta_e_mean_rms(sums: dict) -> Tuple[float, float]:
+    """Host only (sr_delta_e_mean, sr_delta_e_rms) of a delta_e_u8 record.  ValueError for an empty record."""
+    rec = _delta_e_record(sums)
+    m, r = float(load().sr_delta_e_mean(C.byref(rec))), float(load().sr_delta_e_rms(C.byref(rec)))
+    if m != m or r != r:
+        raise ValueError(last_error())
+    return m, r
+
+
+def delta_e_percentile(sums: dict, p: float) -> float:
+    """Host only (sr_delta_e_percentile): the LOWER edge j / 16 of the histogram bin that holds the p-th percentile, p in
+    (0, 100]; the true percentile lies in [j / 16, (j + 1) / 16).  ValueError for another p or an empty record."""
+    rec = _delta_e_record(sums)
+    v = float(load().sr_delta_e_percentile(C.byref(rec), float(p)))
+    if v != v:
+        raise ValueError(last_error())
+    return v
+
+
+def delta_e_fraction(sums: dict, t: float) -> float:
+    """Host only (sr_delta_e_fraction_at_least): the fraction of pixels with dE >= t, exact from the histogram, for t a
+    multiple of 1 / 16 in [0, 128).  ValueError for any other t."""
+    rec = _delta_e_record(sums)
+    out = C.c_double(0.0)
+    check(load().sr_delta_e_fraction_at_least(C.byref(rec), float(t), C.byref(out)))
+    return float(out.value)
 
 
 def imresize_size(n: int, scale: float) -> int:
@@ -1357,6 +1466,40 @@ class Context:
                                   int(cn), C.byref(out)))
         return {"sum_s": out.sum_s, "sum_sc": out.sum_sc, "sum_pcm": out.sum_pcm, "count": int(out.count), "F": int(out.F),
                 "size": (int(out.rows), int(out.cols))}
+
+    def delta_e_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, crop_border=0, formula=DELTA_E_2000, d_map=0,
+                   map_stride=0) -> dict:
+        """sr_delta_e_u8 -> {'count', 'sum', 'sum2', 'max', 'hist' (uint64[2048], bins of width 1 / 16)} of the per-pixel colour
+        difference of the two images cropped by crop_border (finish with delta_e_mean_rms / delta_e_percentile /
+        delta_e_fraction).  d_map: a device address that receives the float64 dE of every cropped pixel, map_stride bytes per
+        row (0: dense).  Every argument is checked before the device is touched: ValueError, or its subclass SrShapeError for
+        a short stride or a crop that leaves nothing."""
+        crop_border, formula = _whole(crop_border, "crop_border"), delta_e_formula(formula)
+        if not d_a or not d_b:
+            raise ValueError("delta_e_u8: null image pointer")
+        if d_map and not map_stride:
+            map_stride = 8 * max(int(w) - 2 * crop_border, 0)
+        out = DeltaESums()
+        check(self.lib.sr_delta_e_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
+                                     int(cn), crop_border, formula, C.c_void_p(d_map or None), int(map_stride), C.byref(out)))
+        return {"count": int(out.count), "sum": out.sum, "sum2": out.sum2, "max": out.max,
+                "hist": np.frombuffer(out.hist, dtype=np.uint64).copy()}
+
+    def delta_e_cells_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, x_edges, y_edges, crop_border=0,
+                         formula=DELTA_E_2000) -> dict:
+        """sr_delta_e_cells_u8: the colour difference per cell of the separable grid x_edges x y_edges over the CROPPED
+        rectangle -> (gh, gw) float64 arrays 'sum' and 'max' (a cell's pixel count is its area).  Every argument is checked
+        before the device is touched (ValueError)."""
+        crop_border, formula = _whole(crop_border, "crop_border"), delta_e_formula(formula)
+        if not d_a or not d_b:
+            raise ValueError("delta_e_cells_u8: null image pointer")
+        xe, gw = _edge_array(x_edges, "x_edges")
+        ye, gh = _edge_array(y_edges, "y_edges")
+        recs = (DeltaECell * (gh * gw))()
+        check(self.lib.sr_delta_e_cells_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h),
+                                           int(w), int(cn), crop_border, formula, xe, gw, ye, gh, recs))
+        arr = np.frombuffer(recs, dtype=np.dtype([("sum", "<f8"), ("max", "<f8")])).reshape(gh, gw)
+        return {k: np.ascontiguousarray(arr[k]) for k in ("sum", "max")}
 
     def niqe_u8(self, d_img, stride, h, w, cn, crop_border=0) -> np.ndarray:
         """sr_niqe_u8 -> records[2, nby * nbx] (NIQE_RECORD, scale-major) of the image cropped by crop_border (finish with

@@ -697,6 +697,128 @@ class QualityAssessmentModule:
             raise ValueError("calculate_fsim: null device pointer")
         return self._fsim_dev(self._ctx(), int(d_img1), int(d_img2), args, return_parts)
 
+    # -- colour difference (no reference counterpart: scikit-image's rgb2lab and deltaE_ciede2000 / deltaE_cie76) ------------
+    @staticmethod
+    def _delta_e_args(what: str, shape1, shape2, crop_border, formula, stride1, stride2):
+        """Every refusal of the colour-difference methods, on the host: ValueError (SrShapeError for a crop that leaves
+        nothing or a short stride).  -> (h, w, cn, crop_border, formula, stride1, stride2, plan)."""
+        shape1, shape2 = tuple(int(v) for v in shape1), tuple(int(v) for v in shape2)
+        if shape1 != shape2:
+            raise ValueError(f"{what}: images must have the same shape, got {shape1} vs {shape2} "
+                             "(nothing is cropped to a common rectangle)")
+        if len(shape1) not in (2, 3):
+            raise ValueError(f"{what}: need an H x W or H x W x C image, got shape {shape1}")
+        cn = shape1[2] if len(shape1) == 3 else 1
+        if cn not in (1, 3, 4):
+            raise ValueError(f"{what}: need a gray, RGB or RGBA image (1, 3 or 4 channels), got {cn}")
+        f = _native.delta_e_formula(formula)
+        if f not in (_native.DELTA_E_2000, _native.DELTA_E_76):
+            raise ValueError(f"{what}: unknown formula {formula!r}")
+        plan = _native.delta_e_plan(shape1[0], shape1[1], cn, crop_border, f)    # crop_border < 0, a crop that leaves nothing
+        row = shape1[1] * cn
+        s1, s2 = (row if s is None else int(s) for s in (stride1, stride2))
+        if s1 < row or s2 < row:
+            raise _native.SrShapeError(f"{what}: stride smaller than a row")
+        return shape1[0], shape1[1], cn, int(crop_border), f, s1, s2, plan
+
+    @staticmethod
+    def _delta_e_percentiles(what: str, percentiles) -> Tuple[float, ...]:
+        ps = tuple(float(p) for p in percentiles)
+        for p in ps:
+            if not (0.0 < p <= 100.0):
+                raise ValueError(f"{what}: percentiles must lie in (0, 100], got {p!r}")
+        return ps
+
+    def _delta_e_dev(self, ctx, d1: int, d2: int, args, percentiles, return_map: bool) -> Dict[str, Any]:
+        h, w, cn, cb, f, s1, s2, plan = args
+        ch, cw = plan["size"]
+        dmap = ctx.alloc(ch * cw * 8) if return_map else None
+        try:
+            rec = ctx.delta_e_u8(d1, s1, d2, s2, h, w, cn, crop_border=cb, formula=f, d_map=dmap.ptr if dmap else 0,
+                                 map_stride=cw * 8 if dmap else 0)
+            mean, rms = _native.delta_e_mean_rms(rec)
+            out = {'mean': mean, 'rms': rms, 'max': float(rec['max'])}
+            for p in percentiles:
+                out[f'p{p:g}'] = _native.delta_e_percentile(rec, p)
+            for t in (1, 3, 5):
+                out[f'frac_above_{t}'] = _native.delta_e_fraction(rec, float(t))
+            out.update(level=self._assess_delta_e(mean), formula='ciede2000' if f == _native.DELTA_E_2000 else 'cie76',
+                       count=int(rec['count']))
+            if dmap:
+                out['map'] = ctx.download(dmap.ptr, (ch, cw), np.float64)
+            return out
+        finally:
+            if dmap:
+                dmap.free()
+
+    def calculate_delta_e(self, img1: np.ndarray, img2: np.ndarray, formula: str = 'ciede2000', crop_border: int = 0,
+                          percentiles=(50, 95, 99), return_map: bool = False) -> Dict[str, Any]:
+        """The full-reference, per-pixel colour difference of two u8 images of equal shape (gray, RGB or RGBA with alpha
+        ignored), as include/sr_hip.h defines it: scikit-image's rgb2lab (sRGB, D65 / 2 degrees) and deltaE_ciede2000
+        ('ciede2000', kL = kC = kH = 1) or deltaE_cie76 ('cie76'), in float64, over the image cropped by crop_border.
+        Returns mean, rms, max, p<p> for every p of `percentiles` (the lower edge of the 1/16-wide histogram bin that holds
+        it), frac_above_1 / _3 / _5 (the exact fractions of pixels with dE >= 1, 3, 5), level (the thresholds of
+        QualityThresholds.DELTA_E_* on the mean), formula and count; with return_map also 'map', the float64 dE of every
+        cropped pixel.  0 everywhere for identical images.  NOT the private _calculate_delta_e / brand_color_delta_e_i of the
+        commercial metrics: those compare a region MEAN in OpenCV's 8-bit integer Lab with one brand colour, by CIE76.  A shape
+        mismatch is a ValueError (nothing is cropped to a common rectangle)."""
+        a = self._require_u8(np.asarray(img1), "calculate_delta_e")
+        b = self._require_u8(np.asarray(img2), "calculate_delta_e")
+        ps = self._delta_e_percentiles("calculate_delta_e", percentiles)
+        args = self._delta_e_args("calculate_delta_e", a.shape, b.shape, crop_border, formula, None, None)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._delta_e_dev(ctx, da.ptr, db.ptr, args, ps, return_map)
+        finally:
+            da.free(); db.free()
+
+    def calculate_delta_e_device(self, d_img1: int, shape1, d_img2: int, shape2, formula: str = 'ciede2000', crop_border: int = 0,
+                                 percentiles=(50, 95, 99), return_map: bool = False, stride1: Optional[int] = None,
+                                 stride2: Optional[int] = None) -> Dict[str, Any]:
+        """calculate_delta_e on two u8 images that already live in HBM (device addresses + shapes; strides in bytes, dense when
+        None)."""
+        ps = self._delta_e_percentiles("calculate_delta_e", percentiles)
+        args = self._delta_e_args("calculate_delta_e", shape1, shape2, crop_border, formula, stride1, stride2)
+        if not d_img1 or not d_img2:
+            raise ValueError("calculate_delta_e: null device pointer")
+        return self._delta_e_dev(self._ctx(), int(d_img1), int(d_img2), args, ps, return_map)
+
+    def _delta_e_map_dev(self, ctx, d1: int, d2: int, args, xe: List[int], ye: List[int]) -> Dict[str, Any]:
+        h, w, cn, cb, f, s1, s2, _ = args
+        r = ctx.delta_e_cells_u8(d1, s1, d2, s2, h, w, cn, xe, ye, crop_border=cb, formula=f)
+        area = np.outer(np.diff(ye), np.diff(xe)).astype(np.float64)
+        return {"mean": r["sum"] / area, "max": r["max"], "x_edges": list(xe), "y_edges": list(ye)}
+
+    def evaluate_delta_e_map(self, img1: np.ndarray, img2: np.ndarray, cell: Optional[int] = None, x_edges=None, y_edges=None,
+                             formula: str = 'ciede2000') -> Dict[str, Any]:
+        """Where the colour drifted: the mean and the largest colour difference (calculate_delta_e's, no crop) per cell of a
+        separable grid, with the argument rules of evaluate_quality_map: uniform cells of `cell` pixels (default 256) or the
+        edge lists x_edges (0 .. W) / y_edges (0 .. H).  Returns (gh, gw) arrays 'mean' and 'max' and the two edge lists.
+        The difference is pointwise, so the cell means weighted by their areas give the global mean and the largest cell max
+        is the global max.  Images of different shapes are a ValueError."""
+        a = self._require_u8(np.asarray(img1), "evaluate_delta_e_map")
+        b = self._require_u8(np.asarray(img2), "evaluate_delta_e_map")
+        args = self._delta_e_args("evaluate_delta_e_map", a.shape, b.shape, 0, formula, None, None)
+        xe, ye = self._map_edges(args[0], args[1], cell, x_edges, y_edges)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._delta_e_map_dev(ctx, da.ptr, db.ptr, args, xe, ye)
+        finally:
+            da.free(); db.free()
+
+    def evaluate_delta_e_map_device(self, d_img1: int, shape1, d_img2: int, shape2, cell: Optional[int] = None, x_edges=None,
+                                    y_edges=None, formula: str = 'ciede2000', stride1: Optional[int] = None,
+                                    stride2: Optional[int] = None) -> Dict[str, Any]:
+        """evaluate_delta_e_map on two u8 images that already live in HBM (device addresses + shapes; strides in bytes, dense
+        when None)."""
+        args = self._delta_e_args("evaluate_delta_e_map", shape1, shape2, 0, formula, stride1, stride2)
+        xe, ye = self._map_edges(args[0], args[1], cell, x_edges, y_edges)
+        if not d_img1 or not d_img2:
+            raise ValueError("evaluate_delta_e_map: null device pointer")
+        return self._delta_e_map_dev(self._ctx(), int(d_img1), int(d_img2), args, xe, ye)
+
     # -- NIQE, the model (no reference counterpart in code: the reference delegates to pyiqa.create_metric('niqe')) ----------
     @staticmethod
     def _niqe_args(shape, crop_border) -> Tuple[int, int, int, int]:
