@@ -1094,8 +1094,16 @@ SR_API int sr_encode_jpeg(const uint8_t *h_img, int h, int w, int cn, int64_t st
  * `tile` x `tile` input tiles (multiple of 16; <= 0: one tile) so a 200 MP image fits; tiles [tile_begin, tile_end) of the
  * row-major tile grid are processed (tile_end < 0: all) -- ranks of a multi-GPU job take disjoint tile ranges and add the
  * sums.  h_layer_sums[k] receives the sum of the k-th tap's lin map over those tiles; LPIPS = sum_k sums[k] / (H_k W_k)
- * with the map sizes from sr_lpips_layer_sizes (h_hw: 5 x (H, W)). */
+ * with the map sizes from sr_lpips_layer_sizes (h_hw: 5 x (H, W)).
+ * sr_lpips_tile_plan (host only, no context): what sr_lpips_u8 works on for tile `tile_index` of the row-major tile grid --
+ * the very function the forward calls.  Activation 0 is the image, activation j the output of the j-th convolution / pooling;
+ * *n_act receives their number (at most SR_LPIPS_PLAN_MAX_ACT) and h_plan, n_act x SR_LPIPS_PLAN_FIELDS ints, per activation:
+ * needed rows [a, b), owned rows [a, b), needed columns [a, b), owned columns [a, b) (indices of the activation's own
+ * grid; a tile adds to a tap's sum over its owned ranges and computes its needed ranges), the buffer pitch in floats,
+ * channels, and the activation's full height and width.  *buffer_floats: floats each activation buffer is grown to. */
 enum sr_lpips_net { SR_LPIPS_ALEX = 0, SR_LPIPS_VGG = 1 };
+#define SR_LPIPS_PLAN_MAX_ACT 18
+#define SR_LPIPS_PLAN_FIELDS 12
 typedef struct sr_lpips_model sr_lpips_model;
 SR_API int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, const float *const *h_conv_b, int n_conv,
                            const float *const *h_lin_w, int n_lin, const float *h_shift, const float *h_scale,
@@ -1103,6 +1111,7 @@ SR_API int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, c
 SR_API int sr_lpips_destroy(sr_lpips_model *model);
 SR_API int sr_lpips_layer_sizes(int net, int h, int w, int *h_hw);
 SR_API int sr_lpips_tile_count(int h, int w, int tile, int *n_tiles);
+SR_API int sr_lpips_tile_plan(int net, int h, int w, int tile, int tile_index, int *n_act, int *h_plan, int64_t *buffer_floats);
 SR_API int sr_lpips_u8(sr_lpips_model *model, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b,
                        int h, int w, int cn, int tile, int tile_begin, int tile_end, double *h_layer_sums);
 
@@ -1149,6 +1158,10 @@ SR_API int sr_dists_create(sr_ctx *ctx, const float *const *h_conv_w, const floa
                            const float *h_std, sr_dists_model **out);
 SR_API int sr_dists_destroy(sr_dists_model *model);
 SR_API int sr_dists_tile_count(int h, int w, int tile, int *n_tiles);
+/* sr_dists_tile_plan (host only, no context): sr_lpips_tile_plan for the DISTS stack -- the same records
+ * (SR_LPIPS_PLAN_FIELDS ints per activation, at most SR_LPIPS_PLAN_MAX_ACT activations), the function sr_dists_u8 calls per tile.
+ * Stage 0 is activation 0, the image. */
+SR_API int sr_dists_tile_plan(int h, int w, int tile, int tile_index, int *n_act, int *h_plan, int64_t *buffer_floats);
 SR_API int sr_dists_u8(sr_dists_model *model, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b,
                        int h, int w, int cn, int tile, int tile_begin, int tile_end, double *h_sums);
 SR_API int sr_dists_l2pool_f32(sr_ctx *ctx, const float *d_in, int C, int H, int W, float *d_out);

@@ -347,10 +347,12 @@ SIGNATURES = {
     "sr_lpips_destroy": (_i, [_vp]),
     "sr_lpips_layer_sizes": (_i, [_i, _i, _i, _pi]),
     "sr_lpips_tile_count": (_i, [_i, _i, _i, _pi]),
+    "sr_lpips_tile_plan": (_i, [_i, _i, _i, _i, _i, _pi, _pi, C.POINTER(_i64)]),
     "sr_lpips_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(_dbl)]),
     "sr_dists_create": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp)]),
     "sr_dists_destroy": (_i, [_vp]),
     "sr_dists_tile_count": (_i, [_i, _i, _i, _pi]),
+    "sr_dists_tile_plan": (_i, [_i, _i, _i, _i, _pi, _pi, C.POINTER(_i64)]),
     "sr_dists_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "sr_dists_l2pool_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sr_dists_layer_sizes": (_i, [_i, _i, _pi]),
@@ -2061,6 +2063,27 @@ def lpips_synthetic_weights(net: str, seed: int = 20260313) -> dict:
     for i, c in enumerate(LPIPS_TAP_CHANNELS[net]):
         w[f"lin{i}.model.1.weight"] = rng.uniform(0, 2.0 / c, (1, c, 1, 1)).astype(np.float32)
     return w
+
+
+LPIPS_PLAN_MAX_ACT, LPIPS_PLAN_FIELDS = 18, 12
+
+
+def lpips_tile_plan(net: str, h: int, w: int, tile: int, tile_index: int) -> dict:
+    """sr_lpips_tile_plan (host only, no GPU): what the forward works on for one tile.  Returns {"buffer_floats": int,
+    "acts": [per activation {"need_y", "own_y", "need_x", "own_x": (a, b), "pitch", "C", "H", "W"}]}; activation 0 is the image.  net
+    "dists": sr_dists_tile_plan, the same records for the DISTS stack (stage 0 is activation 0)."""
+    n, floats = C.c_int(0), C.c_int64(0)
+    rec = (C.c_int * (LPIPS_PLAN_MAX_ACT * LPIPS_PLAN_FIELDS))()
+    if net == "dists":
+        check(load().sr_dists_tile_plan(int(h), int(w), int(tile), int(tile_index), C.byref(n), rec, C.byref(floats)))
+    else:
+        check(load().sr_lpips_tile_plan(LPIPS_NETS[net], int(h), int(w), int(tile), int(tile_index), C.byref(n), rec, C.byref(floats)))
+    acts = []
+    for j in range(n.value):
+        r = rec[j * LPIPS_PLAN_FIELDS:(j + 1) * LPIPS_PLAN_FIELDS]
+        acts.append({"need_y": (r[0], r[1]), "own_y": (r[2], r[3]), "need_x": (r[4], r[5]), "own_x": (r[6], r[7]),
+                     "pitch": r[8], "C": r[9], "H": r[10], "W": r[11]})
+    return {"buffer_floats": floats.value, "acts": acts}
 
 
 class LpipsModel:

@@ -155,23 +155,6 @@ static LiveSet g_ds_live;
 
 static const int DS_CH[DS_STAGES] = {3, 64, 128, 256, 512, 512};
 
-static void ds_arch(std::vector<LpLayer> &L)
-{
-    auto conv = [&](int cout, int cin) {
-        int widx = 0;
-        for (auto &l : L) widx += l.kind == LP_CONV;
-        L.push_back({LP_CONV, cout, cin, 3, 1, 1, -1, widx});
-    };
-    auto pool = [&]() { L.push_back({LP_L2POOL, 0, 0, 3, 2, 1, -1, -1}); };
-    auto tap = [&](int i) { L.push_back({LP_TAP, 0, 0, 1, 1, 0, i, -1}); };
-    tap(0);                                               // stage 0: the image itself
-    conv(64, 3); conv(64, 64); tap(1);
-    pool(); conv(128, 64); conv(128, 128); tap(2);
-    pool(); conv(256, 128); conv(256, 256); conv(256, 256); tap(3);
-    pool(); conv(512, 256); conv(512, 512); conv(512, 512); tap(4);
-    pool(); conv(512, 512); conv(512, 512); conv(512, 512); tap(5);
-}
-
 static void ds_launch_l2pool(hipStream_t st, const float *src, long long in_plane, int in_pitch, int in_ya, int in_xa, int H_in,
                              int W_in, float *dst, long long out_plane, int out_pitch, int out_ya, int out_xa, int rows, int cols,
                              int C)
@@ -253,6 +236,24 @@ int sr_dists_tile_count(int h, int w, int tile, int *n_tiles)
     return SR_OK;
 }
 
+int sr_dists_tile_plan(int h, int w, int tile, int tile_index, int *n_act, int *h_plan, int64_t *buffer_floats)
+{
+    if (!n_act || !h_plan || !buffer_floats) return sr_set_error(SR_ERR_INVALID_ARG, "sr_dists_tile_plan: null argument");
+    int ntiles = 0;
+    int rc = sr_dists_tile_count(h, w, tile, &ntiles);
+    if (rc) return rc;
+    if (tile_index < 0 || tile_index >= ntiles) return sr_set_error(SR_ERR_INVALID_ARG, "sr_dists_tile_plan: tile %d of %d", tile_index, ntiles);
+    std::vector<LpLayer> L;
+    ds_arch(L);
+    LpGeom G;
+    if (!lp_geometry(L, h, w, G)) return sr_set_error(SR_ERR_SHAPE, "sr_dists_tile_plan: no geometry for a %dx%d image", w, h);
+    static_assert(LP_PLAN_FIELDS == SR_LPIPS_PLAN_FIELDS, "plan record layout");
+    long long floats = 0;
+    lp_plan_records(L, G, tile, tile_index, n_act, h_plan, &floats);      // 18 activations
+    *buffer_floats = (int64_t)floats;
+    return SR_OK;
+}
+
 int sr_dists_u8(sr_dists_model *m, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
                 int cn, int tile, int tile_begin, int tile_end, double *h_sums)
 {
@@ -268,34 +269,26 @@ int sr_dists_u8(sr_dists_model *m, const uint8_t *d_a, int64_t stride_a, const u
     CTX_ENTER(ctx);
     LpGeom G;
     if (!lp_geometry(m->layers, h, w, G)) return sr_set_error(SR_ERR_SHAPE, "sr_dists_u8: no geometry for a %dx%d image", w, h);
-    if (tile <= 0) tile = (std::max(h, w) + 31) / 16 * 16;
-    const int tiles_x = tile >= w ? 1 : (w + tile - 1) / tile, tiles_y = tile >= h ? 1 : (h + tile - 1) / tile;
+    int tiles_x, tiles_y;
+    lp_tile_grid(h, w, tile, tiles_x, tiles_y);
     ntiles = tiles_x * tiles_y;
     if (tile_end < 0 || tile_end > ntiles) tile_end = ntiles;
     tile_begin = std::max(tile_begin, 0);
     HIPCHK(hipMemsetAsync(m->d_acc.d, 0, (size_t)DS_TOTAL * 5 * sizeof(double), ctx->stream));
     const std::vector<LpLayer> &L = m->layers;
-    const int na = (int)G.H.size();
     const dim3 blk(64, 4);
     int ch0[DS_STAGES];                       // first channel of a stage in the 1475
     for (int k = 0, c = 0; k < DS_STAGES; c += DS_CH[k], ++k) ch0[k] = c;
     const DistsTable tab{m->mean[0], m->mean[1], m->mean[2], m->stdv[0], m->stdv[1], m->stdv[2]};
     for (int ti = tile_begin; ti < tile_end; ++ti) {
-        const int ty = ti / tiles_x, tx = ti % tiles_x;
-        std::vector<Range> ny, oy, nx, ox;
-        lp_ranges(L, G, G.H, ty * tile, ty + 1 < tiles_y ? (ty + 1) * tile : -1, ny, oy);
-        lp_ranges(L, G, G.W, tx * tile, tx + 1 < tiles_x ? (tx + 1) * tile : -1, nx, ox);
-        // buffer geometry per activation (activation 0 is read from the image itself)
-        std::vector<int> pitch(na, 0);
-        std::vector<long long> plane(na, 0);
-        size_t need_floats = 0;
-        for (int j = 1; j < na; ++j) {
-            pitch[j] = (nx[j].n() + 3) / 4 * 4;
-            plane[j] = (long long)ny[j].n() * pitch[j];
-            // + 8 rows and 32 columns: the unguarded convolution stages whole 8 x 32 blocks of what lies inside the image
-            need_floats = std::max(need_floats, (size_t)plane[j] * G.C[j] + (size_t)8 * pitch[j] + 32);
-        }
-        rc = ensure_activation_buffers(ctx, &m->buf[0][0], 4, need_floats, "sr_dists_u8");
+        // ranges and buffer geometry per activation (activation 0 is read from the image itself); the guarded convolution and
+        // the pooling read inside the needed range only, so a buffer holds exactly C * plane floats
+        LpPlan P;
+        lp_plan(L, G, tile, ti, P);
+        const std::vector<Range> &ny = P.ny, &oy = P.oy, &nx = P.nx, &ox = P.ox;
+        const std::vector<int> &pitch = P.pitch;
+        const std::vector<long long> &plane = P.plane;
+        rc = ensure_activation_buffers(ctx, &m->buf[0][0], 4, P.need_floats, "sr_dists_u8");
         if (rc) return rc;
         int cur = 0;                       // ping-pong index of the current activation (both images in step)
         for (size_t li = 0; li < L.size(); ++li) {
@@ -341,7 +334,7 @@ int sr_dists_u8(sr_dists_model *m, const uint8_t *d_a, int64_t stride_a, const u
                     ProfScope ps(ctx, "dists_conv_mfma");
                     const dim3 grid((cols + 31) / 32, (rows + 7) / 8, l.cout / 64);
                     hipLaunchKernelGGL((k_lp_conv_mfma<3, 8>), grid, dim3(256), 0, ctx->stream, src, plane[ai], pitch[ai], ny[ai].a,
-                                       nx[ai].a, G.H[ai], G.W[ai], l.cin, m->d_w[l.widx].as<const float>(), m->d_b[l.widx].as<const float>(), dst, plane[ao], pitch[ao],
+                                       nx[ai].a, ny[ai].n(), nx[ai].n(), G.H[ai], G.W[ai], l.cin, m->d_w[l.widx].as<const float>(), m->d_b[l.widx].as<const float>(), dst, plane[ao], pitch[ao],
                                        ny[ao].a, nx[ao].a, rows, cols);
                 }
             }

@@ -113,30 +113,6 @@ struct sr_lpips_model {
 
 static LiveSet g_lp_live;
 
-static void lp_arch(int net, std::vector<LpLayer> &L)
-{
-    auto conv = [&](int cout, int cin, int k, int s, int p) {
-        int widx = 0;
-        for (auto &l : L) widx += l.kind == LP_CONV;
-        L.push_back({LP_CONV, cout, cin, k, s, p, -1, widx});
-    };
-    auto pool = [&](int k, int s) { L.push_back({LP_POOL, 0, 0, k, s, 0, -1, -1}); };
-    auto tap = [&](int i) { L.push_back({LP_TAP, 0, 0, 1, 1, 0, i, -1}); };
-    if (net == SR_LPIPS_ALEX) {          // torchvision AlexNet.features, lpips/pretrained_networks.py alexnet
-        conv(64, 3, 11, 4, 2); tap(0);
-        pool(3, 2); conv(192, 64, 5, 1, 2); tap(1);
-        pool(3, 2); conv(384, 192, 3, 1, 1); tap(2);
-        conv(256, 384, 3, 1, 1); tap(3);
-        conv(256, 256, 3, 1, 1); tap(4);
-    } else {                             // torchvision VGG16.features, taps relu1_2 .. relu5_3
-        conv(64, 3, 3, 1, 1); conv(64, 64, 3, 1, 1); tap(0);
-        pool(2, 2); conv(128, 64, 3, 1, 1); conv(128, 128, 3, 1, 1); tap(1);
-        pool(2, 2); conv(256, 128, 3, 1, 1); conv(256, 256, 3, 1, 1); conv(256, 256, 3, 1, 1); tap(2);
-        pool(2, 2); conv(512, 256, 3, 1, 1); conv(512, 512, 3, 1, 1); conv(512, 512, 3, 1, 1); tap(3);
-        pool(2, 2); conv(512, 512, 3, 1, 1); conv(512, 512, 3, 1, 1); conv(512, 512, 3, 1, 1); tap(4);
-    }
-}
-
 extern "C" {
 
 int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, const float *const *h_conv_b, int n_conv,
@@ -150,7 +126,7 @@ int sr_lpips_create(sr_ctx *ctx, int net, const float *const *h_conv_w, const fl
     sr_lpips_model *M = new sr_lpips_model();
     M->ctx = ctx;
     M->net = net;
-    lp_arch(net, M->layers);
+    lp_arch(net == SR_LPIPS_ALEX, M->layers);
     int want_conv = 0;
     for (auto &l : M->layers) want_conv += l.kind == LP_CONV;
     if (!h_conv_w || !h_conv_b || !h_lin_w || n_conv != want_conv || n_lin != 5) {
@@ -222,7 +198,7 @@ int sr_lpips_layer_sizes(int net, int h, int w, int *h_hw)
 {
     if (!h_hw || (net != SR_LPIPS_ALEX && net != SR_LPIPS_VGG)) return sr_set_error(SR_ERR_INVALID_ARG, "sr_lpips_layer_sizes: bad arguments");
     std::vector<LpLayer> L;
-    lp_arch(net, L);
+    lp_arch(net == SR_LPIPS_ALEX, L);
     LpGeom G;
     if (h < 1 || w < 1 || !lp_geometry(L, h, w, G)) return sr_set_error(SR_ERR_SHAPE, "sr_lpips: %dx%d image is too small for the network", w, h);
     for (size_t li = 0; li < L.size(); ++li)
@@ -242,6 +218,25 @@ int sr_lpips_tile_count(int h, int w, int tile, int *n_tiles)
     return SR_OK;
 }
 
+int sr_lpips_tile_plan(int net, int h, int w, int tile, int tile_index, int *n_act, int *h_plan, int64_t *buffer_floats)
+{
+    if (!n_act || !h_plan || !buffer_floats || (net != SR_LPIPS_ALEX && net != SR_LPIPS_VGG))
+        return sr_set_error(SR_ERR_INVALID_ARG, "sr_lpips_tile_plan: bad arguments");
+    int ntiles = 0;
+    int rc = sr_lpips_tile_count(h, w, tile, &ntiles);
+    if (rc) return rc;
+    if (tile_index < 0 || tile_index >= ntiles) return sr_set_error(SR_ERR_INVALID_ARG, "sr_lpips_tile_plan: tile %d of %d", tile_index, ntiles);
+    std::vector<LpLayer> L;
+    lp_arch(net == SR_LPIPS_ALEX, L);
+    LpGeom G;
+    if (!lp_geometry(L, h, w, G)) return sr_set_error(SR_ERR_SHAPE, "sr_lpips: %dx%d image is too small for the network", w, h);
+    static_assert(LP_PLAN_FIELDS == SR_LPIPS_PLAN_FIELDS, "plan record layout");
+    long long floats = 0;
+    lp_plan_records(L, G, tile, tile_index, n_act, h_plan, &floats);      // 8 (AlexNet) or 18 (VGG16) activations
+    *buffer_floats = (int64_t)floats;
+    return SR_OK;
+}
+
 int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h,
                 int w, int cn, int tile, int tile_begin, int tile_end, double *h_layer_sums)
 {
@@ -256,30 +251,22 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
     if (rc) return rc;
     LpGeom G;
     if (!lp_geometry(m->layers, h, w, G)) return sr_set_error(SR_ERR_SHAPE, "sr_lpips_u8: %dx%d image is too small for the network", w, h);
-    if (tile <= 0) tile = std::max(h, w) + 16;
-    const int tiles_x = tile >= w ? 1 : (w + tile - 1) / tile, tiles_y = tile >= h ? 1 : (h + tile - 1) / tile;
+    int tiles_x, tiles_y;
+    lp_tile_grid(h, w, tile, tiles_x, tiles_y);
     ntiles = tiles_x * tiles_y;
     if (tile_end < 0 || tile_end > ntiles) tile_end = ntiles;
     tile_begin = std::max(tile_begin, 0);
     HIPCHK(hipMemsetAsync(m->d_acc.d, 0, 5 * sizeof(double), ctx->stream));
     const std::vector<LpLayer> &L = m->layers;
-    const int na = (int)G.H.size();
     const dim3 blk(64, 4);
     for (int ti = tile_begin; ti < tile_end; ++ti) {
-        const int ty = ti / tiles_x, tx = ti % tiles_x;
-        std::vector<Range> ny, oy, nx, ox;
-        lp_ranges(L, G, G.H, ty * tile, ty + 1 < tiles_y ? (ty + 1) * tile : -1, ny, oy);
-        lp_ranges(L, G, G.W, tx * tile, tx + 1 < tiles_x ? (tx + 1) * tile : -1, nx, ox);
-        // buffer geometry per activation (activation 0 is read from the image itself)
-        std::vector<int> pitch(na, 0);
-        std::vector<long long> plane(na, 0);
-        size_t need_floats = 0;
-        for (int j = 1; j < na; ++j) {
-            pitch[j] = (nx[j].n() + 3) / 4 * 4;
-            plane[j] = (long long)ny[j].n() * pitch[j];
-            need_floats = std::max(need_floats, (size_t)plane[j] * G.C[j]);
-        }
-        rc = ensure_activation_buffers(ctx, &m->buf[0][0], 4, need_floats, "sr_lpips_u8");
+        // ranges and buffer geometry per activation (activation 0 is read from the image itself): sr_lpips_tile_plan's
+        LpPlan P;
+        lp_plan(L, G, tile, ti, P);
+        const std::vector<Range> &ny = P.ny, &oy = P.oy, &nx = P.nx, &ox = P.ox;
+        const std::vector<int> &pitch = P.pitch;
+        const std::vector<long long> &plane = P.plane;
+        rc = ensure_activation_buffers(ctx, &m->buf[0][0], 4, P.need_floats, "sr_lpips_u8");
         if (rc) return rc;
         int cur = 0;                       // ping-pong index of the current activation (both images in step)
         for (size_t li = 0; li < L.size(); ++li) {
@@ -322,7 +309,7 @@ int sr_lpips_u8(sr_lpips_model *m, const uint8_t *d_a, int64_t stride_a, const u
                 } else {
                     ProfScope ps(ctx, "lpips_conv_mfma");
                     const dim3 grid((cols + 31) / 32, (rows + 7) / 8, l.cout / 64);
-#define CONV_ARGS src, plane[ai], pitch[ai], ny[ai].a, nx[ai].a, G.H[ai], G.W[ai], l.cin, m->d_w[l.widx].as<const float>(), m->d_b[l.widx].as<const float>(), dst, \
+#define CONV_ARGS src, plane[ai], pitch[ai], ny[ai].a, nx[ai].a, ny[ai].n(), nx[ai].n(), G.H[ai], G.W[ai], l.cin, m->d_w[l.widx].as<const float>(), m->d_b[l.widx].as<const float>(), dst, \
                   plane[ao], pitch[ao], ny[ao].a, nx[ao].a, rows, cols
                     if (l.k == 3) hipLaunchKernelGGL((k_lp_conv_mfma<3, 8>), grid, dim3(256), 0, ctx->stream, CONV_ARGS);
                     else hipLaunchKernelGGL((k_lp_conv_mfma<5, 4>), grid, dim3(256), 0, ctx->stream, CONV_ARGS);

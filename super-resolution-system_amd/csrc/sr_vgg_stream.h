@@ -1,5 +1,5 @@
-// sr_vgg_stream.h -- what the tile-streamed feature-stack metrics (sr_lpips.hip, sr_dists.hip) share: the layer table and its
-// per-tile range algebra, the u8 stem convolution (parameterised by the formula of its 3 x 256 input table), the fp32-MFMA
+// sr_vgg_stream.h -- what the tile-streamed feature-stack metrics (sr_lpips.hip, sr_dists.hip) share: the layer tables and their
+// per-tile range algebra (sr_vgg_ranges.h, host only), the u8 stem convolution (parameterised by the formula of its 3 x 256 input table), the fp32-MFMA
 // convolution + ReLU, and the fixed-order partial accumulate.  Internal: nothing here is part of the C ABI.  Everything sits in
 // an unnamed namespace: each including unit owns its copy of the kernels.
 #pragma once
@@ -7,18 +7,9 @@
 #include <vector>
 
 #include "sr_conv_mfma.h"
+#include "sr_vgg_ranges.h"
 
 namespace {
-
-// LP_L2POOL is DISTS's padded pooling (k 3, s 2, p 1); LP_POOL the unpadded max pooling of the LPIPS backbones.
-enum { LP_CONV = 0, LP_POOL = 1, LP_TAP = 2, LP_L2POOL = 3 };
-
-struct LpLayer {
-    int kind;
-    int cout, cin, k, s, p;   // conv / pool geometry
-    int tap;                  // LP_TAP: tap index
-    int widx;                 // LP_CONV: index into the weight arrays
-};
 
 // ---------------------------------------------------------------------------------------------------------------
 // Stem convolution (Cin = 3) straight from the u8 image: one thread = one output pixel x 64 output channels.
@@ -73,20 +64,22 @@ __global__ __launch_bounds__(256) void k_lp_conv_stem(const unsigned char *__res
 
 // ---------------------------------------------------------------------------------------------------------------
 // Implicit-GEMM convolution + bias + ReLU on v_mfma_f32_32x32x2_f32, stride 1, KS x KS, zero padding P = KS / 2:
-// conv_mfma_mainloop<KS, CC, 2, false> (sr_conv_mfma.h states the GEMM view, the block shape, the LDS staging and the
-// summation order) plus a ReLU epilogue.  Block = 4 waves = 8 output rows x 32 columns x 64 couts.  GUARD is off: this
-// kernel is not told how many rows and columns its input buffer holds.
+// conv_mfma_mainloop<KS, CC, 2, true> (sr_conv_mfma.h states the GEMM view, the block shape, the LDS staging and the
+// summation order) plus a ReLU epilogue.  Block = 4 waves = 8 output rows x 32 columns x 64 couts.  GUARD is on: the input
+// buffer holds in_rows x in_cols (the needed range of the tile), and a partial block at the edge of a tile would otherwise
+// stage elements past it -- past the allocation itself where the activation is the largest of the tile.  Only masked outputs
+// read those elements, so the guard changes no result.
 // ---------------------------------------------------------------------------------------------------------------
 template <int KS, int CC>
 __global__ __launch_bounds__(256) void k_lp_conv_mfma(const float *__restrict__ in, long long in_plane, int in_pitch,
-                                                      int in_ya, int in_xa, int H_in, int W_in, int cin,
+                                                      int in_ya, int in_xa, int in_rows, int in_cols, int H_in, int W_in, int cin,
                                                       const float *__restrict__ wslab, const float *__restrict__ bias,
                                                       float *__restrict__ out, long long out_plane, int out_pitch,
                                                       int out_ya, int out_xa, int rows, int cols)
 {
     const MfmaLane ln = mfma_lane();
     f32x16 acc[2][2];
-    conv_mfma_mainloop<KS, CC, 2, false>(ln, in, in_plane, in_pitch, in_ya, in_xa, 0, 0, H_in, W_in, cin, wslab, bias, out_ya, out_xa, acc);
+    conv_mfma_mainloop<KS, CC, 2, true>(ln, in, in_plane, in_pitch, in_ya, in_xa, in_rows, in_cols, H_in, W_in, cin, wslab, bias, out_ya, out_xa, acc);
     // epilogue: ReLU, masked store
     const int col = ln.ox0 + ln.l32;
     if (col >= cols) return;
@@ -125,73 +118,6 @@ __global__ __launch_bounds__(256) void k_lp_accum(const double *__restrict__ par
         __syncthreads();
     }
     if (threadIdx.x == 0) acc[blockIdx.x] += sh[0];
-}
-
-struct Range {
-    int a = 0, b = 0;                 // [a, b)
-    bool empty() const { return a >= b; }
-    int n() const { return b > a ? b - a : 0; }
-};
-
-inline Range hull(Range p, Range q)
-{
-    if (p.empty()) return q;
-    if (q.empty()) return p;
-    Range r;
-    r.a = std::min(p.a, q.a);
-    r.b = std::max(p.b, q.b);
-    return r;
-}
-
-// Per-activation geometry of an h x w input: activation 0 is the image, activation j the output of the j-th conv / pool.
-struct LpGeom {
-    std::vector<int> H, W, C, S;      // extent, channels and cumulative stride per activation
-    std::vector<int> act_of_layer;    // activation a layer reads (conv / pool) or taps
-};
-
-inline bool lp_geometry(const std::vector<LpLayer> &L, int h, int w, LpGeom &G)
-{
-    G.H = {h}; G.W = {w}; G.C = {3}; G.S = {1};
-    G.act_of_layer.clear();
-    for (auto &l : L) {
-        G.act_of_layer.push_back((int)G.H.size() - 1);
-        if (l.kind == LP_TAP) continue;
-        const int hi = G.H.back(), wi = G.W.back();
-        const int ho = (hi + 2 * l.p - l.k) / l.s + 1, wo = (wi + 2 * l.p - l.k) / l.s + 1;
-        if (hi + 2 * l.p < l.k || wi + 2 * l.p < l.k || ho < 1 || wo < 1) return false;
-        G.H.push_back(ho); G.W.push_back(wo);
-        G.C.push_back(l.kind == LP_CONV ? l.cout : G.C.back());
-        G.S.push_back(G.S.back() * l.s);
-    }
-    return true;
-}
-
-// Ranges (one axis) every activation of a tile must cover: its own part of every tapped activation plus what the
-// deeper layers need of it.  t0 / t1: the tile's span in input pixels (t1 < 0: to the end).
-inline void lp_ranges(const std::vector<LpLayer> &L, const LpGeom &G, const std::vector<int> &ext, int t0, int t1,
-                      std::vector<Range> &need, std::vector<Range> &own)
-{
-    const int na = (int)ext.size();
-    need.assign(na, Range());
-    own.assign(na, Range());
-    for (int j = 0; j < na; ++j) {
-        own[j].a = std::min(t0 / G.S[j], ext[j]);
-        own[j].b = t1 < 0 ? ext[j] : std::min(t1 / G.S[j], ext[j]);
-    }
-    for (int li = (int)L.size() - 1; li >= 0; --li) {
-        const LpLayer &l = L[li];
-        const int ai = G.act_of_layer[li];
-        if (l.kind == LP_TAP) {
-            need[ai] = hull(need[ai], own[ai]);
-            continue;
-        }
-        const Range o = need[ai + 1];
-        if (o.empty()) continue;
-        Range r;
-        r.a = std::max(o.a * l.s - l.p, 0);
-        r.b = std::min((o.b - 1) * l.s - l.p + l.k, ext[ai]);
-        need[ai] = hull(need[ai], r);
-    }
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
 """AddressSanitizer + UBSan over the host side of DISTS: csrc/sr_dists_host.cpp is compiled with g++
 -fsanitize=address,undefined -fno-sanitize-recover=all together with the stand-alone tools/sanitize/dists_driver.cpp, which
-takes seeded sums (dead, constant and equal channels included) through the sizes and the score with exact-size buffers, and run."""
+takes seeded sums (dead, constant and equal channels included) through the sizes and the score with exact-size buffers and walks
+the per-tile plans of csrc/sr_vgg_ranges.h (AlexNet, VGG16 and DISTS stacks, small and odd sizes, every tile), and run."""
 import os
 import shutil
 import subprocess

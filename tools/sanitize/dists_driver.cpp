@@ -1,6 +1,9 @@
 // dists_driver.cpp -- stand-alone driver for the sanitizer run of the host side of DISTS (tests/test_dists_sanitize.py): compiled
 // with csrc/sr_dists_host.cpp alone under -fsanitize=address,undefined, it takes seeded sums through sr_dists_layer_sizes ->
-// sr_dists_score with exact-size heap buffers, dead, constant and equal channels and every refusal included.
+// sr_dists_score with exact-size heap buffers, dead, constant and equal channels and every refusal included.  It also walks the
+// per-tile plan of the three feature stacks (csrc/sr_vgg_ranges.h, host only: lp_geometry, lp_ranges, lp_plan) over small and odd
+// sizes and every tile, checking what the forwards index with: owned inside needed at every tap, the needed input of every
+// layer covering its needed output, pitches and the buffer size.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -8,6 +11,7 @@
 #include <vector>
 
 #include "sr_internal.h"
+#include "sr_vgg_ranges.h"
 
 static char g_err[512] = "";
 
@@ -29,8 +33,55 @@ int sr_set_error(int code, const char *fmt, ...)
         }                                                                                  \
     } while (0)
 
+static bool inside(Range in, Range out) { return in.empty() || (out.a <= in.a && in.b <= out.b); }
+
+// every tile's plan of one stack on an h x w image; false where the forward would index outside a buffer
+static bool plans_hold(const std::vector<LpLayer> &L, int h, int w, int tile)
+{
+    LpGeom G;
+    if (!lp_geometry(L, h, w, G)) return true;                               // refused: nothing is planned
+    int tx, ty;
+    lp_tile_grid(h, w, tile, tx, ty);
+    for (int ti = 0; ti < tx * ty; ++ti) {
+        LpPlan P;
+        lp_plan(L, G, tile, ti, P);
+        const Range *need[2] = {P.ny.data(), P.nx.data()}, *own[2] = {P.oy.data(), P.ox.data()};
+        const int *ext[2] = {G.H.data(), G.W.data()};
+        for (size_t li = 0; li < L.size(); ++li) {
+            const int ai = G.act_of_layer[li];
+            for (int ax = 0; ax < 2; ++ax) {
+                const Range n = need[ax][ai];
+                if (!n.empty() && (n.a < 0 || n.b > ext[ax][ai])) return false;
+                if (L[li].kind == LP_TAP) {
+                    if (!inside(own[ax][ai], n)) return false;
+                    continue;
+                }
+                const Range o = need[ax][ai + 1];
+                if (o.empty()) continue;
+                const Range reads = {std::max(o.a * L[li].s - L[li].p, 0), std::min((o.b - 1) * L[li].s - L[li].p + L[li].k, ext[ax][ai])};
+                if (!inside(reads, n)) return false;
+            }
+        }
+        for (size_t j = 1; j < G.H.size(); ++j)
+            if (P.pitch[j] < P.nx[j].n() || P.pitch[j] % 4 || (size_t)P.plane[j] * G.C[j] > P.need_floats) return false;
+    }
+    return true;
+}
+
 int main()
 {
+    {
+        std::vector<LpLayer> nets[3];
+        lp_arch(true, nets[0]);
+        lp_arch(false, nets[1]);
+        ds_arch(nets[2]);
+        const int sides[] = {1, 2, 16, 17, 31, 33, 35, 47, 53, 64, 67, 99, 131};
+        const int tiles[] = {0, 16, 32, 48, 64, 128};
+        for (auto &L : nets)
+            for (int h : sides)
+                for (int w : sides)
+                    for (int t : tiles) REQUIRE(plans_hold(L, h, w, t));
+    }
     constexpr int TOTAL = 1475;
     const int CH[6] = {3, 64, 128, 256, 512, 512};
     std::mt19937_64 rng(20260519);
