@@ -857,6 +857,73 @@ SR_API double sr_delta_e_percentile(const sr_delta_e_sums *sums, double p);
 /* Host only: the fraction of pixels with dE >= t, exact from the histogram, for t a multiple of 1 / 16 in [0, 128); any other
  * t is SR_ERR_INVALID_ARG. */
 SR_API int sr_delta_e_fraction_at_least(const sr_delta_e_sums *sums, double t, double *fraction);
+/* ---- HaarPSI, the Haar wavelet perceptual similarity index (csrc/sr_haarpsi.hip, csrc/sr_haarpsi_host.cpp, csrc/sr_haarpsi.h) --
+ * Reisenhofer, Bosse, Kutyniok and Wiegand 2018, a full-reference metric; larger is better, 1 for identical images.  No
+ * reference counterpart.  PARITY: the SR_HAARPSI_PYTHON convention is pinned through SciPy's own convolve2d(mode='same'), the
+ * call the authors' Python script makes (tests/_haarpsi_ref.py).  The SR_HAARPSI_MATLAB convention and the constants are
+ * recalled from the published scripts; MATLAB, piq and pyiqa are not available offline: PARITY UNPINNED.  Known distance,
+ * rounding level: the scripts form Y, I and Q in double with a rounding each, here they are exact integers until one division
+ * (measured on the CPU against tests/_haarpsi_ref.py: at most 2.6e-14 relative over the sums and the value).
+ * Inputs: two u8 images of equal shape h x w x cn (ref, dist), strides in bytes.  cn = 1: gray; 3: RGB; 4: RGBA, alpha ignored.
+ * crop_border = cb >= 0: rows [cb, h - cb), columns [cb, w - cb), ch x cw; both cropped sides must be >= 2 (SR_ERR_SHAPE).
+ * Constants: C = 30, alpha = 4.2, three scales (nothing else is built).
+ * Planes, exact integers x 1000: Y = 299 R + 587 G + 114 B, I = 596 R - 274 G - 322 B, Q = 211 R - 523 G + 312 B; gray: Y = 1000 v
+ * and no chroma.
+ * Window-centre convention o: SR_HAARPSI_MATLAB (o = 0) is conv2(., k, 'same'), where an even kernel's window looks forward;
+ * SR_HAARPSI_PYTHON (o = 1) is scipy.signal.convolve2d(., k, mode='same'), whose centre sits one sample earlier.  The two
+ * official scripts differ here and so do their values (1e-3 .. 1e-2 on small images).  Samples outside a plane are ZERO.
+ * Subsampling (subsample = 1): every plane P becomes pool[i, j] = sum P[2 i - o + {0, 1}, 2 j - o + {0, 1}], i < ceil(ch / 2),
+ * j < ceil(cw / 2), unit div = 4000; subsample = 0: the planes as they are, div = 1000.  mh x mw samples either way.
+ * Haar sums of the luma plane, scale s = 1, 2, 3, hf = 2^(s - 1), at sample (i, j):
+ *   V_s = sum over columns j - o - hf + 1 .. j - o + hf of (rows i - o - hf + 1 .. i - o) - (rows i - o + 1 .. i - o + hf),
+ *   H_s the transposed window; both int32 (below 3.4e7 in magnitude); the coefficient is |.| / (div 2^s), rounded once.
+ * Chroma (cn >= 3): c_I = |sum of I over (i - o .. i - o + 1, j - o .. j - o + 1)| / (4 div), c_Q likewise.
+ * Per sample and orientation d in {V, H}, a from ref and b from dist: w_d = max(a_3, b_3),
+ * LS_d = (sim(a_1, b_1) + sim(a_2, b_2)) / 2 with sim(a, b) = (2 a b + C) / (a^2 + b^2 + C).  Colour adds
+ * LS_c = (sim(c_I) + sim(c_Q)) / 2 with w_c = (w_V + w_H) / 2.
+ * Per channel (V, H and, for colour, c): num = sum w / (1 + exp(-alpha LS)), den = sum w, float64.  x = sum num / sum den,
+ * HaarPSI = (ln(x / (1 - x)) / alpha)^2.  Symmetric; 1 within 1e-12 (not exactly) for identical images; NaN when every weight
+ * is 0 (a black pair) -- a flat non-black pair gives 1, the zero border makes the rim coefficients non-zero.
+ * No floating-point atomics; partial sums are combined in a fixed order that depends on the size alone: equal inputs give equal
+ * bits.  Out of scope, refused or absent by name: other C / alpha / scale counts, float and 16-bit inputs, MDSI. */
+enum sr_haarpsi_convention { SR_HAARPSI_MATLAB = 0, SR_HAARPSI_PYTHON = 1 };
+typedef struct sr_haarpsi_sums {
+    double num[3], den[3];      /* V, H, colour (0 for gray) */
+    int32_t channels;           /* 2 (gray) or 3 */
+    int32_t reserved;
+    uint64_t count;             /* samples: mh * mw */
+} sr_haarpsi_sums;
+typedef struct sr_haarpsi_cell {
+    double num, den;            /* summed over the channels */
+} sr_haarpsi_cell;
+/* Host only, no context: the sample map, its count, the blocks of the launch and the bytes of context scratch of an
+ * sr_haarpsi_u8 call (each output may be NULL).  Carries every refusal that depends on these arguments: SR_ERR_INVALID_ARG for
+ * cn not 1, 3 or 4, crop_border < 0, h or w < 1, subsample not 0 or 1, an unknown convention; SR_ERR_SHAPE for a side below 2
+ * after the crop (the message names the minimum) and for more samples than one launch covers. */
+SR_API int sr_haarpsi_plan(int h, int w, int cn, int crop_border, int subsample, int convention, int *map_h, int *map_w,
+                           uint64_t *count, int *blocks, size_t *scratch_bytes);
+/* The record of the pair.  The crop is pointer arithmetic; pixels are read byte by byte; strides are arbitrary (at least a
+ * row) and 64-bit.  Synchronous; the per-block partials are context scratch, grown on demand.  Refused before any device call:
+ * null pointers, everything sr_haarpsi_plan refuses, a stride shorter than a row of the uncropped image (SR_ERR_SHAPE). */
+SR_API int sr_haarpsi_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
+                         int cn, int crop_border, int subsample, int convention, sr_haarpsi_sums *h_out);
+/* Per cell of a separable grid with the argument rules of sr_delta_e_cells_u8: strictly increasing host edge lists
+ * h_xedges[0..gw] (0 .. cw) and h_yedges[0..gh] (0 .. ch) over the CROPPED rectangle, in pixels.  h_out: gh * gw records,
+ * row-major.  A sample belongs to the cell that holds cropped pixel (2 i, 2 j), or (i, j) without subsampling; a cell that
+ * holds no sample has den = 0.  The cells add up to the record's sums over the channels within the order of fp64 additions.
+ * The per-sample (num, den) pairs (16 bytes a sample) are context scratch.  Refused before any device call: everything
+ * sr_haarpsi_u8 refuses, edges that are not strictly increasing or do not span the cropped side (SR_ERR_INVALID_ARG), more than
+ * 2^24 - 1 cells (SR_ERR_UNSUPPORTED). */
+SR_API int sr_haarpsi_cells_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h,
+                               int w, int cn, int crop_border, int subsample, int convention, const int *h_xedges, int gw,
+                               const int *h_yedges, int gh, sr_haarpsi_cell *h_out);
+/* Host only: the value of a record, and of one cell's sums; NaN for den == 0 (and, with sr_last_error, for a null record). */
+SR_API double sr_haarpsi_value(const sr_haarpsi_sums *sums);
+SR_API double sr_haarpsi_cell_value(double num, double den);
+/* Host only: the float64 restatement of the definition on HOST memory (direct window sums, the per-sample expressions the
+ * kernel evaluates, samples added in row-major order).  Same refusals as sr_haarpsi_u8. */
+SR_API int sr_haarpsi_host_u8(const uint8_t *a, int64_t stride_a, const uint8_t *b, int64_t stride_b, int h, int w, int cn,
+                              int crop_border, int subsample, int convention, sr_haarpsi_sums *out);
 /* ---- NIQE, the no-reference quality model (csrc/sr_niqe.hip, csrc/sr_niqe_host.cpp) -------------------------------------------
  * Mittal, Soundararajan, Bovik 2013, in the arithmetic of MATLAB's computequality / estimatemodelparam and BasicSR's
  * calculate_niqe, made exact wherever it can be.  The reference's calculate_niqe asks pyiqa for this model first; the 'niqe'

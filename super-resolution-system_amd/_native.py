@@ -103,6 +103,20 @@ class DeltaECell(C.Structure):
     _fields_ = [("sum", C.c_double), ("max", C.c_double)]
 
 
+class HaarPsiSums(C.Structure):
+    """sr_haarpsi_sums (include/sr_hip.h)."""
+    _fields_ = [("num", C.c_double * 3), ("den", C.c_double * 3), ("channels", C.c_int32), ("reserved", C.c_int32),
+                ("count", C.c_uint64)]
+
+
+class HaarPsiCell(C.Structure):
+    """sr_haarpsi_cell (include/sr_hip.h)."""
+    _fields_ = [("num", C.c_double), ("den", C.c_double)]
+
+
+# enum sr_haarpsi_convention (include/sr_hip.h)
+HAARPSI_MATLAB, HAARPSI_PYTHON = 0, 1
+HAARPSI_CONVENTIONS = {"matlab": HAARPSI_MATLAB, "python": HAARPSI_PYTHON}
 # enum sr_delta_e_formula (include/sr_hip.h)
 DELTA_E_2000, DELTA_E_76 = 0, 1
 DELTA_E_FORMULAS = {"ciede2000": DELTA_E_2000, "cie76": DELTA_E_76}
@@ -318,6 +332,12 @@ SIGNATURES = {
     "sr_delta_e_rms": (_dbl, [C.POINTER(DeltaESums)]),
     "sr_delta_e_percentile": (_dbl, [C.POINTER(DeltaESums), _dbl]),
     "sr_delta_e_fraction_at_least": (_i, [C.POINTER(DeltaESums), _dbl, C.POINTER(_dbl)]),
+    "sr_haarpsi_plan": (_i, [_i, _i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), _pi, C.POINTER(_sz)]),
+    "sr_haarpsi_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(HaarPsiSums)]),
+    "sr_haarpsi_cells_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _pi, _i, _pi, _i, C.POINTER(HaarPsiCell)]),
+    "sr_haarpsi_value": (_dbl, [C.POINTER(HaarPsiSums)]),
+    "sr_haarpsi_cell_value": (_dbl, [_dbl, _dbl]),
+    "sr_haarpsi_host_u8": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(HaarPsiSums)]),
     "sr_niqe_plan": (_i, [_i, _i, _i, _i, _pi, _pi, _pi, _pi, C.POINTER(_sz)]),
     "sr_niqe_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sr_niqe_half_plane": (_i, [_vp, _vp]),
@@ -908,6 +928,80 @@ def delta_e_fraction(sums: dict, t: float) -> float:
     out = C.c_double(0.0)
     check(load().sr_delta_e_fraction_at_least(C.byref(rec), float(t), C.byref(out)))
     return float(out.value)
+
+
+def haarpsi_convention(convention) -> int:
+    """'matlab' / 'python' (or the enum value) -> enum sr_haarpsi_convention.  ValueError for another name; another number
+    goes through to the library, which refuses it."""
+    if isinstance(convention, str):
+        if convention not in HAARPSI_CONVENTIONS:
+            raise ValueError(f"HaarPSI: unknown convention {convention!r}: {sorted(HAARPSI_CONVENTIONS)} are built")
+        return HAARPSI_CONVENTIONS[convention]
+    return _whole(convention, "convention")
+
+
+def _haarpsi_switches(crop_border, subsample, convention) -> Tuple[int, int, int]:
+    if not isinstance(subsample, (bool, np.bool_)):
+        subsample = _whole(subsample, "subsample")
+    return _whole(crop_border, "crop_border"), int(subsample), haarpsi_convention(convention)
+
+
+def haarpsi_plan(h: int, w: int, cn: int, crop_border: int = 0, subsample=True, convention=HAARPSI_MATLAB) -> dict:
+    """Host only (sr_haarpsi_plan): the sample map, its count, the blocks of the launch and the bytes of context scratch of a
+    HaarPSI call.  ValueError for cn not 1, 3 or 4, a negative crop_border, h or w < 1, another subsample or convention;
+    SrShapeError (a ValueError) naming the minimum for a side below 2 after the crop."""
+    h, w, cn = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn")))
+    crop_border, subsample, convention = _haarpsi_switches(crop_border, subsample, convention)
+    mh, mw, cnt, blocks, nbytes = C.c_int(0), C.c_int(0), C.c_uint64(0), C.c_int(0), C.c_size_t(0)
+    check(load().sr_haarpsi_plan(h, w, cn, crop_border, subsample, convention, C.byref(mh), C.byref(mw), C.byref(cnt),
+                                 C.byref(blocks), C.byref(nbytes)))
+    return {"size": (mh.value, mw.value), "count": int(cnt.value), "blocks": blocks.value, "scratch_bytes": int(nbytes.value)}
+
+
+def _haarpsi_dict(rec: "HaarPsiSums") -> dict:
+    n = int(rec.channels)
+    return {"num": np.array(rec.num[:n], np.float64), "den": np.array(rec.den[:n], np.float64), "channels": n,
+            "count": int(rec.count)}
+
+
+def haarpsi_value(sums: dict) -> float:
+    """Host only (sr_haarpsi_value): (ln(x / (1 - x)) / 4.2)^2 with x = sum num / sum den of a haarpsi record; NaN when every
+    weight is 0 (a black pair).  ValueError for a record of other than 2 or 3 channels."""
+    num, den = (np.asarray(sums[k], np.float64).ravel() for k in ("num", "den"))
+    if num.size != den.size or num.size not in (2, 3):
+        raise ValueError("haarpsi_value: need a record of 2 or 3 channels")
+    rec = HaarPsiSums()
+    for k in range(num.size):
+        rec.num[k], rec.den[k] = float(num[k]), float(den[k])
+    rec.channels, rec.count = int(num.size), int(sums.get("count", 0))
+    return float(load().sr_haarpsi_value(C.byref(rec)))
+
+
+def haarpsi_cell_value(num: float, den: float) -> float:
+    """Host only (sr_haarpsi_cell_value): the value of one cell's sums; NaN for den == 0."""
+    return float(load().sr_haarpsi_cell_value(float(num), float(den)))
+
+
+def haarpsi_host(a: np.ndarray, b: np.ndarray, crop_border: int = 0, subsample=True, convention=HAARPSI_MATLAB) -> dict:
+    """Host only (sr_haarpsi_host_u8): the float64 restatement of HaarPSI on two u8 host arrays (H x W, or H x W x 1 / 3 / 4;
+    any row stride, channels dense) -> {'num', 'den', 'channels', 'count'}.  ValueError as haarpsi_plan and for shapes that
+    differ."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("haarpsi_host: need u8 images")
+    if a.shape != b.shape or a.ndim not in (2, 3):
+        raise ValueError(f"haarpsi_host: need two H x W or H x W x C images of one shape, got {a.shape} vs {b.shape}")
+    cn = a.shape[2] if a.ndim == 3 else 1
+    arrs = []
+    for v in (a, b):
+        dense = v.strides[-1] == 1 and (v.ndim == 2 or v.strides[1] == cn) and v.strides[0] >= v.shape[1] * cn
+        arrs.append(v if dense else np.ascontiguousarray(v))
+    crop_border, subsample, convention = _haarpsi_switches(crop_border, subsample, convention)
+    rec = HaarPsiSums()
+    check(load().sr_haarpsi_host_u8(C.c_void_p(arrs[0].ctypes.data), int(arrs[0].strides[0]), C.c_void_p(arrs[1].ctypes.data),
+                                    int(arrs[1].strides[0]), int(a.shape[0]), int(a.shape[1]), int(cn), crop_border, subsample,
+                                    convention, C.byref(rec)))
+    return _haarpsi_dict(rec)
 
 
 def imresize_size(n: int, scale: float) -> int:
@@ -1502,6 +1596,34 @@ class Context:
                                            int(w), int(cn), crop_border, formula, xe, gw, ye, gh, recs))
         arr = np.frombuffer(recs, dtype=np.dtype([("sum", "<f8"), ("max", "<f8")])).reshape(gh, gw)
         return {k: np.ascontiguousarray(arr[k]) for k in ("sum", "max")}
+
+    def haarpsi(self, d_a, stride_a, d_b, stride_b, h, w, cn, crop_border=0, subsample=True, convention=HAARPSI_MATLAB) -> dict:
+        """sr_haarpsi_u8 -> {'num', 'den' (float64 [channels]: V, H and, for colour, chroma), 'channels', 'count'} of the two
+        images cropped by crop_border (finish with haarpsi_value).  Every argument is checked before the device is touched:
+        ValueError, or its subclass SrShapeError for a short stride or a crop that leaves a side below 2."""
+        crop_border, subsample, convention = _haarpsi_switches(crop_border, subsample, convention)
+        if not d_a or not d_b:
+            raise ValueError("haarpsi: null image pointer")
+        out = HaarPsiSums()
+        check(self.lib.sr_haarpsi_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
+                                     int(cn), crop_border, subsample, convention, C.byref(out)))
+        return _haarpsi_dict(out)
+
+    def haarpsi_cells(self, d_a, stride_a, d_b, stride_b, h, w, cn, x_edges, y_edges, crop_border=0, subsample=True,
+                      convention=HAARPSI_MATLAB) -> dict:
+        """sr_haarpsi_cells_u8: HaarPSI's sums per cell of the separable grid x_edges x y_edges (pixels of the CROPPED
+        rectangle) -> (gh, gw) float64 arrays 'num' and 'den', summed over the channels (a cell without a sample has den 0).
+        Every argument is checked before the device is touched (ValueError)."""
+        crop_border, subsample, convention = _haarpsi_switches(crop_border, subsample, convention)
+        if not d_a or not d_b:
+            raise ValueError("haarpsi_cells: null image pointer")
+        xe, gw = _edge_array(x_edges, "x_edges")
+        ye, gh = _edge_array(y_edges, "y_edges")
+        recs = (HaarPsiCell * (gh * gw))()
+        check(self.lib.sr_haarpsi_cells_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h),
+                                           int(w), int(cn), crop_border, subsample, convention, xe, gw, ye, gh, recs))
+        arr = np.frombuffer(recs, dtype=np.dtype([("num", "<f8"), ("den", "<f8")])).reshape(gh, gw)
+        return {k: np.ascontiguousarray(arr[k]) for k in ("num", "den")}
 
     def niqe_u8(self, d_img, stride, h, w, cn, crop_border=0) -> np.ndarray:
         """sr_niqe_u8 -> records[2, nby * nbx] (NIQE_RECORD, scale-major) of the image cropped by crop_border (finish with

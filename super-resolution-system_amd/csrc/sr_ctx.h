@@ -111,11 +111,12 @@ struct sr_ctx {
     double fsim_consts[12] = {0};                       // ... and EM_n, S2, Sij of its four orientations
     DevBuf deltae_ws;                                   // colour difference: the linearisation table, histogram, partials, cell slabs
     bool deltae_table = false;                          // the table is in place (false again whenever the buffer is regrown)
+    DevBuf haarpsi_ws;                                  // HaarPSI: per-block partials; the per-cell form adds the sample map, edges, records
     CachedTable imresize_tab;                           // imresize: both axes' weights, indices and starts of the last geometry
     // Frees every device buffer above; sr_ctx_destroy calls it with the stream drained and the device current.
     void release_device()
     {
-        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws, &brisque_ws, &vif_ws, &gmsd_ws, &fsim_ws, &deltae_ws, &imresize_tab.buf})
+        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws, &brisque_ws, &vif_ws, &gmsd_ws, &fsim_ws, &deltae_ws, &haarpsi_ws, &imresize_tab.buf})
             b->release();
     }
 };

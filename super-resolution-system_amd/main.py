@@ -78,6 +78,8 @@ class PipelineConfig:
     qa_fsim: bool = False      # (with enable_qa): ... and the phase-congruency feature similarity of the same pair ('fsim', 'fsimc')
     qa_delta_e: bool = False   # (with enable_qa): stage 4 also reports the per-pixel CIEDE2000 colour difference of the canvas against the
                                # INTER_CUBIC resize of the source ('delta_e'; with qa_map_cell > 0 also 'delta_e_map' over the same cells)
+    qa_haarpsi: bool = False   # (with enable_qa): stage 4 also reports HaarPSI of the canvas against the INTER_CUBIC resize of the source
+                               # ('haarpsi'; with qa_map_cell > 0 also 'haarpsi_map' over the same cells)
     qa_niqe_params: str = ""   # (with enable_qa): path of NIQE's pristine parameters (.npz with BasicSR's keys, or .mat): stage 4 also
                                # reports the NIQE of the canvas ('niqe_model'; the 'niqe' key keeps the reference's stand-in heuristic)
     qa_brisque_model: str = "" # (with enable_qa): path of a BRISQUE regressor (.npz: sv, sv_coef, gamma, rho, feature_min, feature_max): stage 4
@@ -340,6 +342,41 @@ class SuperResolutionPipeline:
         finally:
             ctx.sync()
             ref.free()
+
+    def _haarpsi(self, ctx, report: Dict[str, Any], d_src: int, src_shape, d_canvas: int, canvas_shape) -> None:
+        """Stage 4's optional 'haarpsi' entry (qa_haarpsi): HaarPSI (calculate_haarpsi's defaults, no crop) of the canvas
+        against the INTER_CUBIC resize of the source to the canvas size, the reference, both in HBM -- and, with
+        qa_map_cell > 0, 'haarpsi_map': its value over the uniform cells of report['quality_map'] (None for a cell without
+        weight).  A refusal or a NaN (a black pair) gives None and 'haarpsi_note' says why (the run does not fail).  Takes no
+        part in overall_score.  One helper for the device-resident, the host-array and the sharded path."""
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        ih, iw = int(src_shape[0]), int(src_shape[1])
+        cell = int(self.config.qa_map_cell)
+        report['haarpsi'] = None
+        if cell > 0:
+            report['haarpsi_map'] = None
+        q = self.quality_module
+        ref = None
+        try:
+            q._haarpsi_args("calculate_haarpsi", (H, W, cn), (H, W, cn), 0, True, 'matlab', None, None)
+            ref = ctx.alloc(H * W * cn)
+            ctx.resize_cubic_u8(d_src, iw * cn, ih, iw, cn, ref.ptr, W * cn, H, W)
+            v = q.calculate_haarpsi_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn))
+            if v != v:
+                report['haarpsi_note'] = "HaarPSI is undefined for this pair: every weight is 0 (both images are black)"
+            else:
+                report['haarpsi'] = float(v)
+            if cell > 0:
+                m = q.evaluate_haarpsi_map_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn), cell=cell)
+                report['haarpsi_map'] = {"cell": cell, "grid": [int(n) for n in m["haarpsi"].shape], "x_edges": m["x_edges"],
+                                         "y_edges": m["y_edges"],
+                                         "haarpsi": [[None if x != x else float(x) for x in r] for r in m["haarpsi"]]}
+        except ValueError as exc:
+            report['haarpsi_note'] = str(exc)
+        finally:
+            if ref is not None:
+                ctx.sync()
+                ref.free()
 
     def _delta_e(self, ctx, report: Dict[str, Any], d_src: int, src_shape, d_canvas: int, canvas_shape) -> None:
         """Stage 4's optional 'delta_e' entry (qa_delta_e): the per-pixel CIEDE2000 colour difference of the canvas against
@@ -609,6 +646,8 @@ class SuperResolutionPipeline:
                     self._vif_gmsd(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_delta_e:
                     self._delta_e(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
+                if self.config.qa_haarpsi:
+                    self._haarpsi(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_fsim:
                     self._fsim(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_niqe_params:
@@ -721,6 +760,8 @@ class SuperResolutionPipeline:
                         self._vif_gmsd(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_delta_e:
                         self._delta_e(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
+                    if self.config.qa_haarpsi:
+                        self._haarpsi(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_fsim:
                         self._fsim(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_niqe_params:
@@ -837,6 +878,13 @@ class SuperResolutionPipeline:
                         self._delta_e(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
                     finally:
                         d_src.free(); d_fused.free()
+                if self.config.qa_haarpsi:
+                    qctx = self.quality_module._ctx()
+                    d_src, d_fused = qctx.upload(original), qctx.upload(fused)
+                    try:
+                        self._haarpsi(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
+                    finally:
+                        d_src.free(); d_fused.free()
                 if self.config.qa_fsim:
                     qctx = self.quality_module._ctx()
                     d_src, d_fused = qctx.upload(original), qctx.upload(fused)
@@ -922,6 +970,9 @@ async def main() -> int:
     ap.add_argument("--qa-delta-e", action="store_true",
                     help="stage 4 also reports the per-pixel CIEDE2000 colour difference of the result against the bicubic resize "
                          "of the input (report key delta_e; with --qa-map-cell also delta_e_map over the same cells)")
+    ap.add_argument("--qa-haarpsi", action="store_true",
+                    help="stage 4 also reports HaarPSI (Haar wavelet perceptual similarity) of the result against the bicubic resize "
+                         "of the input (report key haarpsi; with --qa-map-cell also haarpsi_map over the same cells)")
     ap.add_argument("--qa-map-cell", type=int, default=0, metavar="N",
                     help="N > 0: stage 4 also writes the per-cell PSNR / SSIM map over uniform cells of N pixels (report key "
                          "quality_map, PipelineConfig.qa_map_cell); 0 = off")
@@ -962,7 +1013,7 @@ async def main() -> int:
         return 2
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act, sr_ensemble=args.sr_ensemble,
-                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark, qa_vif=args.qa_vif, qa_gmsd=args.qa_gmsd, qa_delta_e=args.qa_delta_e, qa_map_cell=args.qa_map_cell, qa_fsim=args.qa_fsim,
+                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark, qa_vif=args.qa_vif, qa_gmsd=args.qa_gmsd, qa_delta_e=args.qa_delta_e, qa_haarpsi=args.qa_haarpsi, qa_map_cell=args.qa_map_cell, qa_fsim=args.qa_fsim,
                          qa_niqe_params=args.qa_niqe_params, qa_brisque_model=args.qa_brisque_model, qa_dists_weights=args.qa_dists_weights,
                          benchmark_degrade=args.benchmark_degrade)
     if args.plan_only:

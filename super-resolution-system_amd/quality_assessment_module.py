@@ -819,6 +819,110 @@ class QualityAssessmentModule:
             raise ValueError("evaluate_delta_e_map: null device pointer")
         return self._delta_e_map_dev(self._ctx(), int(d_img1), int(d_img2), args, xe, ye)
 
+    # -- HaarPSI (no reference counterpart: Reisenhofer, Bosse, Kutyniok, Wiegand 2018) ---------------------------------------
+    @staticmethod
+    def _haarpsi_args(what: str, shape1, shape2, crop_border, subsample, convention, stride1, stride2):
+        """Every refusal of the HaarPSI methods, on the host: ValueError (SrShapeError for a crop that leaves a side below 2 or
+        a short stride).  -> (h, w, cn, crop_border, subsample, convention, stride1, stride2, plan)."""
+        shape1, shape2 = tuple(int(v) for v in shape1), tuple(int(v) for v in shape2)
+        if shape1 != shape2:
+            raise ValueError(f"{what}: images must have the same shape, got {shape1} vs {shape2} "
+                             "(nothing is cropped to a common rectangle)")
+        if len(shape1) not in (2, 3):
+            raise ValueError(f"{what}: need an H x W or H x W x C image, got shape {shape1}")
+        cn = shape1[2] if len(shape1) == 3 else 1
+        if cn not in (1, 3, 4):
+            raise ValueError(f"{what}: need a gray, RGB or RGBA image (1, 3 or 4 channels), got {cn}")
+        conv = _native.haarpsi_convention(convention)
+        if conv not in (_native.HAARPSI_MATLAB, _native.HAARPSI_PYTHON):
+            raise ValueError(f"{what}: unknown convention {convention!r}")
+        if not isinstance(subsample, (bool, np.bool_)):
+            raise ValueError(f"{what}: subsample must be True or False, got {subsample!r}")
+        plan = _native.haarpsi_plan(shape1[0], shape1[1], cn, crop_border, bool(subsample), conv)
+        row = shape1[1] * cn
+        s1, s2 = (row if s is None else int(s) for s in (stride1, stride2))
+        if s1 < row or s2 < row:
+            raise _native.SrShapeError(f"{what}: stride smaller than a row")
+        return shape1[0], shape1[1], cn, int(crop_border), bool(subsample), conv, s1, s2, plan
+
+    @staticmethod
+    def _haarpsi_dev(ctx, d1: int, d2: int, args, return_parts: bool):
+        h, w, cn, cb, sub, conv, s1, s2, _ = args
+        rec = ctx.haarpsi(d1, s1, d2, s2, h, w, cn, crop_border=cb, subsample=sub, convention=conv)
+        v = _native.haarpsi_value(rec)
+        if not return_parts:
+            return v
+        return {"haarpsi": v, "num": rec["num"], "den": rec["den"], "channels": rec["channels"], "count": rec["count"],
+                "subsample": sub, "convention": "python" if conv == _native.HAARPSI_PYTHON else "matlab"}
+
+    def calculate_haarpsi(self, reference: np.ndarray, distorted: np.ndarray, crop_border: int = 0, subsample: bool = True,
+                          convention: str = 'matlab', return_parts: bool = False):
+        """HaarPSI, the Haar wavelet perceptual similarity index of two u8 images of equal shape (gray, RGB or RGBA with alpha
+        ignored), as include/sr_hip.h defines it: C = 30, alpha = 4.2, three scales, over the image cropped by crop_border
+        (both sides at least 2 afterwards).  Larger is better; 1 (within 1e-12) for identical images; symmetric; NaN for a
+        black pair (every weight 0).  convention: 'matlab' (conv2 'same', the default) or 'python' (scipy convolve2d
+        'same', whose window sits one sample earlier) -- the two official scripts differ by 1e-3 .. 1e-2 on small images.
+        subsample = False skips the 2 x 2 pooling.  Returns the value, or with return_parts a dict with the value
+        ('haarpsi'), the per-channel sums 'num' and 'den', 'channels', 'count', 'subsample' and 'convention'.  A shape
+        mismatch is a ValueError (nothing is cropped to a common rectangle); float and 16-bit inputs are not built."""
+        a = self._require_u8(np.asarray(reference), "calculate_haarpsi")
+        b = self._require_u8(np.asarray(distorted), "calculate_haarpsi")
+        args = self._haarpsi_args("calculate_haarpsi", a.shape, b.shape, crop_border, subsample, convention, None, None)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._haarpsi_dev(ctx, da.ptr, db.ptr, args, return_parts)
+        finally:
+            da.free(); db.free()
+
+    def calculate_haarpsi_device(self, d_reference: int, shape1, d_distorted: int, shape2, crop_border: int = 0,
+                                 subsample: bool = True, convention: str = 'matlab', return_parts: bool = False,
+                                 stride1: Optional[int] = None, stride2: Optional[int] = None):
+        """calculate_haarpsi on two u8 images that already live in HBM (device addresses + shapes; strides in bytes, dense when
+        None)."""
+        args = self._haarpsi_args("calculate_haarpsi", shape1, shape2, crop_border, subsample, convention, stride1, stride2)
+        if not d_reference or not d_distorted:
+            raise ValueError("calculate_haarpsi: null device pointer")
+        return self._haarpsi_dev(self._ctx(), int(d_reference), int(d_distorted), args, return_parts)
+
+    @staticmethod
+    def _haarpsi_map_dev(ctx, d1: int, d2: int, args, xe: List[int], ye: List[int]) -> Dict[str, Any]:
+        h, w, cn, cb, sub, conv, s1, s2, _ = args
+        r = ctx.haarpsi_cells(d1, s1, d2, s2, h, w, cn, xe, ye, crop_border=cb, subsample=sub, convention=conv)
+        val = np.array([[_native.haarpsi_cell_value(n, d) for n, d in zip(rn, rd)] for rn, rd in zip(r["num"], r["den"])],
+                       np.float64).reshape(r["num"].shape)
+        return {"haarpsi": val, "num": r["num"], "den": r["den"], "x_edges": list(xe), "y_edges": list(ye)}
+
+    def evaluate_haarpsi_map(self, img1: np.ndarray, img2: np.ndarray, cell: Optional[int] = None, x_edges=None, y_edges=None,
+                             subsample: bool = True, convention: str = 'matlab') -> Dict[str, Any]:
+        """Where the similarity drops: HaarPSI (calculate_haarpsi's, no crop) per cell of a separable grid, with the argument
+        rules of evaluate_quality_map: uniform cells of `cell` pixels (default 256) or the edge lists x_edges (0 .. W) /
+        y_edges (0 .. H).  Returns (gh, gw) arrays 'haarpsi' (the value of the cell's own sums; NaN for a cell without weight),
+        'num' and 'den' (summed over the channels) and the two edge lists.  A sample belongs to the cell that holds pixel
+        (2 i, 2 j) (or (i, j) without subsampling): the cells' sums add up to the global ones.  Images of different shapes are
+        a ValueError."""
+        a = self._require_u8(np.asarray(img1), "evaluate_haarpsi_map")
+        b = self._require_u8(np.asarray(img2), "evaluate_haarpsi_map")
+        args = self._haarpsi_args("evaluate_haarpsi_map", a.shape, b.shape, 0, subsample, convention, None, None)
+        xe, ye = self._map_edges(args[0], args[1], cell, x_edges, y_edges)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._haarpsi_map_dev(ctx, da.ptr, db.ptr, args, xe, ye)
+        finally:
+            da.free(); db.free()
+
+    def evaluate_haarpsi_map_device(self, d_img1: int, shape1, d_img2: int, shape2, cell: Optional[int] = None, x_edges=None,
+                                    y_edges=None, subsample: bool = True, convention: str = 'matlab',
+                                    stride1: Optional[int] = None, stride2: Optional[int] = None) -> Dict[str, Any]:
+        """evaluate_haarpsi_map on two u8 images that already live in HBM (device addresses + shapes; strides in bytes, dense
+        when None)."""
+        args = self._haarpsi_args("evaluate_haarpsi_map", shape1, shape2, 0, subsample, convention, stride1, stride2)
+        xe, ye = self._map_edges(args[0], args[1], cell, x_edges, y_edges)
+        if not d_img1 or not d_img2:
+            raise ValueError("evaluate_haarpsi_map: null device pointer")
+        return self._haarpsi_map_dev(self._ctx(), int(d_img1), int(d_img2), args, xe, ye)
+
     # -- NIQE, the model (no reference counterpart in code: the reference delegates to pyiqa.create_metric('niqe')) ----------
     @staticmethod
     def _niqe_args(shape, crop_border) -> Tuple[int, int, int, int]:
