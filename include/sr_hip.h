@@ -331,7 +331,9 @@ SR_API int sr_feather_merge_dt(sr_ctx *ctx, int dtype, const sr_merge_tile *h_ti
  * Per channel the float32 Sobel of each tile (reflect-101 at the TILE's borders) times its cosine weight map
  * (feather width min(h, w) // 8) is accumulated in list order, divided by max(sum of weights, 1e-6f), summed along rows
  * (np.cumsum, axis=1) and along columns (axis=0) as sequential fp32 chains, halved, clipped to [0, 255] and truncated into
- * the u8 canvas.  d_work: canvas_h * canvas_w * cn floats of device workspace (the row sums).  Asynchronous. */
+ * the u8 canvas.  d_work: canvas_h * canvas_w * cn floats of device workspace.  On return d_work holds the row prefix sums
+ * (np.cumsum(grad_x / max(W, 1e-6f), axis=1), canvas layout, fp32); tests/test_gpu_gradient_lists.py compares them bit for
+ * bit, because the u8 canvas hides most fp32 differences.  Asynchronous. */
 SR_API int sr_gradient_fusion(sr_ctx *ctx, int dtype, void *const *h_d_tiles, const int64_t *h_strides,
                               const sr_tile_rect *h_rects, int n, int cn, int canvas_h, int canvas_w, uint8_t *d_canvas,
                               int64_t canvas_stride, float *d_work);

@@ -41,8 +41,8 @@ def _tile_gradients(tile: np.ndarray):
     return gx, gy
 
 
-def gradient_domain_fusion(tiles, positions, output_shape) -> np.ndarray:
-    """The reference's sequence of float32 array operations, vectorised as it is there."""
+def _normalised_gradients(tiles, positions, output_shape):
+    """The weighted, list-ordered float32 accumulation of gradient_domain_fusion -> (grad_x / W, grad_y / W)."""
     H, W = output_shape
     cn = tiles[0].shape[2] if tiles[0].ndim == 3 else 1
     shape = (H, W) if cn == 1 else (H, W, cn)
@@ -63,10 +63,23 @@ def gradient_domain_fusion(tiles, positions, output_shape) -> np.ndarray:
     wb = wacc[..., None] if cn > 1 else wacc
     grad_x /= wb
     grad_y /= wb
+    return grad_x, grad_y
+
+
+def gradient_domain_fusion(tiles, positions, output_shape) -> np.ndarray:
+    """The reference's sequence of float32 array operations, vectorised as it is there."""
+    grad_x, grad_y = _normalised_gradients(tiles, positions, output_shape)
     r = np.cumsum(grad_x, axis=1)
     r += np.cumsum(grad_y, axis=0)
     r /= 2
     return np.clip(r, 0, 255).astype(np.uint8)
+
+
+def row_prefix_plane(tiles, positions, output_shape) -> np.ndarray:
+    """np.cumsum(grad_x / max(wacc, 1e-6), axis=1) in float32: the first half of gradient_domain_fusion, the plane
+    sr_gradient_fusion leaves in its workspace.  The u8 canvas hides most fp32 differences; this plane does not."""
+    grad_x, _ = _normalised_gradients(tiles, positions, output_shape)
+    return np.cumsum(grad_x, axis=1)
 
 
 def gradient_domain_fusion_loops(tiles, positions, output_shape) -> np.ndarray:
