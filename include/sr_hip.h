@@ -777,6 +777,88 @@ SR_API int sr_fsim_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const u
 SR_API int sr_fsim_value(const sr_fsim_sums *sums, double *fsim, double *fsimc);
 /* Host only: Re((s_i s_q)^0.03), the chroma weight of one sample as the score kernel forms it. */
 SR_API double sr_fsim_chroma_weight(double s_i, double s_q);
+/* ---- VSI, the visual saliency-induced index with SDSP saliency (csrc/sr_vsi.hip, csrc/sr_vsi_host.cpp, csrc/sr_vsi.h) ---------
+ * Zhang, Shen and Li, TIP 2014, in the form of the authors' VSI.m with SDSP.m (Zhang, Gu and Li, ICIP 2013).  No reference
+ * counterpart.  PARITY UNPINNED: MATLAB, piq and pyiqa are not available offline; the definition below is recalled from the
+ * published scripts (the constants agree with piq's defaults) and pinned by the NumPy restatement tests/_vsi_ref.py alone.
+ * Known distances, rounding-level: L, M, N and the pooling mean are exact integers until one division; the pooled saliency is
+ * formed from the 256 x 256 map by composite per-axis tables (below) instead of from a stored full-resolution map; the
+ * up-resize applies its horizontal pass first whatever the scales.  Where max VS = min VS MATLAB's mat2gray returns the
+ * clamped map; here the value is NaN.
+ * Inputs: two u8 images of equal shape h x w x cn, cn = 3 (RGB) or 4 (alpha ignored), strides in bytes.  Both sides must be at
+ * least 16 (SR_ERR_SHAPE); cn = 1 is SR_ERR_UNSUPPORTED (VSI is defined for colour images: with R = G = B the a and b ranges
+ * are rounding residue of the XYZ matrix); F above 256 is SR_ERR_UNSUPPORTED.  Nothing is cropped.  The metric is symmetric.
+ *   resize   imresize(., 'bilinear') by the contribution rule of the imresize section above with the triangle t(x) = max(0,
+ *            1 - |x|) in place of the cubic and support 2 in place of 4: scale = n_out / n_in; kw = 2 / scale and weights
+ *            scale t(scale d) when scale < 1, else kw = 2; P = ceil(kw) + 2 taps, u = (i + 1) / scale + 0.5 (1 - 1 / scale),
+ *            left = floor(u - kw / 2); weights normalised by their sum; symmetric reflection at the border; any scale; nothing
+ *            is rounded between the passes; the axis with the smaller scale first, a tie vertical first.
+ *   SDSP     of each image on a fixed 256 x 256 grid, float64.  R, G, B as double resized to 256 x 256.  Lab by the script's
+ *            own RGB2Lab: v = x / 255, v <= 0.04045 ? v / 12.92 : ((v + 0.055) / 1.055)^2.4; X = 0.4124564 R + 0.3575761 G +
+ *            0.1804375 B, Y = 0.2126729 R + 0.7151522 G + 0.0721750 B, Z = 0.0193339 R + 0.1191920 G + 0.9503041 B; X / 0.950456,
+ *            Z / 1.088754; f(t) = cbrt(t) above 0.008856, else 7.787 t + 16 / 116; L = 116 f_Y - 16, a = 500 (f_X - f_Y), b =
+ *            200 (f_Y - f_Z).  (Not sr_delta_e's Lab: another matrix and white point.)  Log-Gabor: u1 = (c - 128) / 256, u2 =
+ *            (r - 128) / 256 for 0-based r, c, both 0 where u1^2 + u2^2 > 0.25, ifftshifted; radius = sqrt(u1^2 + u2^2),
+ *            radius[0,0] = 1; LG = exp(-ln(radius / 0.021)^2 / (2 1.34^2)), 0 where the radius is 0; LG[0,0] = 0.
+ *            SF = sqrt(sum_{p in L,a,b} real(ifft2(fft2(p) LG))^2); SD = exp(-((r + 1 - 128)^2 + (c + 1 - 128)^2) / 145^2);
+ *            SC = 1 - exp(-(a_n^2 + b_n^2) / 0.001^2), a_n = (a - min a) / (max a - min a) over the grid, b_n likewise (a flat
+ *            a or b is 0 / 0: the value is NaN); VS256 = SF SD SC.  The transform is FSIM's dense float64 DFT (the plane's
+ *            first sample subtracted first: LG is 0 at DC).
+ *   VS       imresize(VS256, [h w], 'bilinear') by the same rule (a side below 256 is a shrink with its wider kernel), then
+ *            mat2gray: (VS - min VS) / (max VS - min VS) over all h w samples; max = min gives NaN.
+ *   planes   carried exactly as integers: L 100 = 6 R + 63 G + 27 B, M 100 = 30 R + 4 G - 35 B, N 100 = 34 R - 60 G + 17 B.
+ *   pooling  FSIM's: F = max(1, floor(min(h, w) / 256 + 0.5)), the F x F mean as conv2(., 'same') with a zero border sampled
+ *            at 0, F, 2F, ...; L, M, N as int64 window sums divided once by 100 F^2; VS with zeros outside the image and the
+ *            divisor F^2.  Resize, mat2gray and the mean are linear and separable, so the pooled VS is (C_y VS256 C_x' - min VS
+ *            cover) / (max VS - min VS) / F^2, where row i of C_y adds the up-resize rows of the in-image part of window i and
+ *            cover counts the in-image samples of a window; only min VS and max VS visit every sample.
+ *   score    G = Scharr (FSIM's dx, dy) on the pooled L; sim(u, v, k) = (2 u v + k) / (u^2 + v^2 + k); S_vs = sim(VS1, VS2,
+ *            1.27), S_g = sim(G1, G2, 386), S_c = sim(M1, M2, 130) sim(N1, N2, 130), VSm = max(VS1, VS2);
+ *            VSI = sum(S_g^0.4 S_vs Re(S_c^0.02) VSm) / sum VSm, a negative S_c = z contributing |z|^0.02 cos(0.02 pi).
+ *            Identical images give 1 to 1e-12. */
+typedef struct sr_vsi_sums {
+    double sum_s;           /* sum S_g^0.4 S_vs Re(S_c^0.02) VSm */
+    double sum_w;           /* sum VSm */
+    uint64_t count;         /* rows * cols */
+    int32_t F, rows, cols, reserved;
+    double a_range[2][2];   /* per image: min, max of a on the 256 x 256 grid */
+    double b_range[2][2];   /* ... of b */
+    double vs_range[2][2];  /* ... of the full-resolution VS before mat2gray */
+} sr_vsi_sums;
+/* Host only, no context: F, the pooled size and the bytes of context workspace a call will hold (each output may be NULL).
+ * Carries every refusal that depends on the shape: SR_ERR_INVALID_ARG for cn not 1, 3 or 4 or h, w < 1; SR_ERR_UNSUPPORTED
+ * for cn = 1 and, naming the cap, for F above 256 or more pooled rows than one launch covers; SR_ERR_SHAPE for a side below 16. */
+SR_API int sr_vsi_plan(int h, int w, int cn, int *F, int *rows, int *cols, size_t *workspace_bytes);
+/* Host only, for inspection: LG (as the transform indexes it, DC first) and SD, 65536 values each; either may be NULL. */
+SR_API int sr_vsi_filter(double *lg, double *sd);
+/* Host only, for inspection: one axis of the triangle resize n_in -> n_out.  *taps takes the tap count; when w and idx are
+ * given (both or neither) they take w[n_out][taps] and the reflected 0-based idx[n_out][taps], cap being the taps there is
+ * room for.  SR_ERR_INVALID_ARG for sides below 1, a null taps, one of w and idx alone, or too small a cap. */
+SR_API int sr_vsi_resize_weights(int n_in, int n_out, int cap, int *taps, double *w, int32_t *idx);
+/* Inspection entry of the pooling with an EXPLICIT F in 1 .. 256 and no minimum side: h_out[2][3][rows * cols] takes the
+ * int64 window sums of L 100, M 100, N 100 of a, then of b.  One pass: every source byte is read at most once.  Synchronous.
+ * Refused before any device call: null pointers, cn not 1, 3 or 4, h or w < 1, F outside 1 .. 256 (SR_ERR_INVALID_ARG), cn = 1
+ * (SR_ERR_UNSUPPORTED), a stride shorter than a row (SR_ERR_SHAPE). */
+SR_API int sr_vsi_pool_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
+                          int cn, int F, int64_t *h_out);
+/* Inspection entry of the saliency of ONE image: h_lab[3][65536] (L, a, b on the grid), h_vs256[65536] and h_range[4] (min a,
+ * max a, min b, max b); each output may be NULL.  Synchronous.  Refusals as sr_vsi_u8. */
+SR_API int sr_vsi_saliency_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, int cn, double *h_lab,
+                              double *h_vs256, double *h_range);
+/* The record of the pair.  Strides are arbitrary (at least a row); pixels are read byte by byte.  Every sum, minimum and maximum
+ * goes through a fixed tree, no floating-point atomics: equal inputs give equal bits.  Synchronous; the workspace belongs to
+ * the context and grows on demand.  Refused before any device call: null pointers, everything sr_vsi_plan refuses, a stride
+ * shorter than a row (SR_ERR_SHAPE). */
+SR_API int sr_vsi_u8(sr_ctx *ctx, const uint8_t *d_a, int64_t stride_a, const uint8_t *d_b, int64_t stride_b, int h, int w,
+                     int cn, sr_vsi_sums *h_out);
+/* Host only: sum_s / sum_w; NaN for 0 / 0, when a sum is NaN, and (with sr_last_error) for a null record. */
+SR_API double sr_vsi_value(const sr_vsi_sums *sums);
+/* Host only: Re(s_c^0.02), the chroma weight of one sample as the score kernel forms it. */
+SR_API double sr_vsi_chroma_weight(double s_c);
+/* Host only, no context: the same record from host memory, every stage in the kernels' formulation (sequential sums where the
+ * device adds through trees).  Same refusals as sr_vsi_u8. */
+SR_API int sr_vsi_host_u8(const uint8_t *a, int64_t stride_a, const uint8_t *b, int64_t stride_b, int h, int w, int cn,
+                          sr_vsi_sums *out);
 /* ---- colour difference: CIEDE2000 and CIE76 per pixel (csrc/sr_deltae.hip, csrc/sr_deltae_host.cpp, csrc/sr_deltae.h) ---------
  * A full-reference, per-pixel colour difference of two images, in the arithmetic of scikit-image 0.18.3 (rgb2lab of a uint8
  * image, deltaE_ciede2000 / deltaE_cie76, float64).  PARITY PINNED: tests/golden/deltae_skimage.npz holds scikit-image's own

@@ -89,6 +89,14 @@ class FsimSums(C.Structure):
                 ("F", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32)]
 
 
+class VsiSums(C.Structure):
+    """sr_vsi_sums (include/sr_hip.h)."""
+    _fields_ = [("sum_s", C.c_double), ("sum_w", C.c_double), ("count", C.c_uint64),
+                ("F", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32),
+                ("a_range", C.c_double * 2 * 2), ("b_range", C.c_double * 2 * 2), ("vs_range", C.c_double * 2 * 2)]
+
+
+VSI_GRID = 256
 DELTA_E_BINS = 2048
 
 
@@ -322,6 +330,15 @@ SIGNATURES = {
     "sr_fsim_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, C.POINTER(FsimSums)]),
     "sr_fsim_value": (_i, [C.POINTER(FsimSums), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "sr_fsim_chroma_weight": (_dbl, [_dbl, _dbl]),
+    "sr_vsi_plan": (_i, [_i, _i, _i, _pi, _pi, _pi, C.POINTER(_sz)]),
+    "sr_vsi_filter": (_i, [C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "sr_vsi_resize_weights": (_i, [_i, _i, _i, _pi, C.POINTER(_dbl), C.POINTER(C.c_int32)]),
+    "sr_vsi_pool_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "sr_vsi_saliency_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "sr_vsi_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, C.POINTER(VsiSums)]),
+    "sr_vsi_value": (_dbl, [C.POINTER(VsiSums)]),
+    "sr_vsi_chroma_weight": (_dbl, [_dbl]),
+    "sr_vsi_host_u8": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, C.POINTER(VsiSums)]),
     "sr_delta_e_plan": (_i, [_i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), _pi, C.POINTER(_sz)]),
     "sr_delta_e_table": (_i, [C.POINTER(_dbl)]),
     "sr_delta_e_lab_u8": (_i, [_i, _i, _i, C.POINTER(_dbl)]),
@@ -846,6 +863,73 @@ def fsim_value(sums: dict) -> Tuple[float, float]:
 def fsim_chroma_weight(s_i: float, s_q: float) -> float:
     """Host only (sr_fsim_chroma_weight): Re((s_i s_q)^0.03) as the score kernel forms it."""
     return float(load().sr_fsim_chroma_weight(float(s_i), float(s_q)))
+
+
+def vsi_plan(h: int, w: int, cn: int) -> dict:
+    """Host only (sr_vsi_plan): F, the pooled size and the bytes of context workspace of a VSI call.  ValueError for cn not 1,
+    3 or 4; SrShapeError (a ValueError) naming the minimum for a side below 16; SrNativeError for cn = 1 (VSI is defined for
+    colour images) and, naming the cap, for F above 256."""
+    h, w, cn = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn")))
+    f, rows, cols, nbytes = C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    check(load().sr_vsi_plan(h, w, cn, C.byref(f), C.byref(rows), C.byref(cols), C.byref(nbytes)))
+    return {"F": f.value, "size": (rows.value, cols.value), "workspace_bytes": int(nbytes.value)}
+
+
+def vsi_filter() -> dict:
+    """Host only (sr_vsi_filter): {'lg': [256, 256] (DC first), 'sd': [256, 256]} of the SDSP grid."""
+    lg, sd = np.zeros((VSI_GRID, VSI_GRID), np.float64), np.zeros((VSI_GRID, VSI_GRID), np.float64)
+    dp = C.POINTER(C.c_double)
+    check(load().sr_vsi_filter(lg.ctypes.data_as(dp), sd.ctypes.data_as(dp)))
+    return {"lg": lg, "sd": sd}
+
+
+def vsi_resize_weights(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Host only (sr_vsi_resize_weights): (w [n_out, taps] float64, idx [n_out, taps] int32, reflected and 0-based) of one
+    axis of the triangle resize n_in -> n_out (imresize 'bilinear', antialiased when it shrinks)."""
+    n_in, n_out = _whole(n_in, "n_in"), _whole(n_out, "n_out")
+    taps = C.c_int(0)
+    check(load().sr_vsi_resize_weights(n_in, n_out, 0, C.byref(taps), None, None))
+    w, idx = np.zeros((n_out, taps.value), np.float64), np.zeros((n_out, taps.value), np.int32)
+    check(load().sr_vsi_resize_weights(n_in, n_out, taps.value, C.byref(taps), w.ctypes.data_as(C.POINTER(C.c_double)),
+                                       idx.ctypes.data_as(C.POINTER(C.c_int32))))
+    return w, idx
+
+
+def _vsi_dict(rec: "VsiSums") -> dict:
+    rng = lambda f: np.array([[f[0][0], f[0][1]], [f[1][0], f[1][1]]], np.float64)
+    return {"sum_s": rec.sum_s, "sum_w": rec.sum_w, "count": int(rec.count), "F": int(rec.F), "size": (int(rec.rows), int(rec.cols)),
+            "a_range": rng(rec.a_range), "b_range": rng(rec.b_range), "vs_range": rng(rec.vs_range)}
+
+
+def vsi_value(sums: dict) -> float:
+    """Host only (sr_vsi_value): sum_s / sum_w of a vsi record; NaN for 0 / 0 or a NaN sum."""
+    rec = VsiSums()
+    rec.sum_s, rec.sum_w = float(sums["sum_s"]), float(sums["sum_w"])
+    return float(load().sr_vsi_value(C.byref(rec)))
+
+
+def vsi_chroma_weight(s_c: float) -> float:
+    """Host only (sr_vsi_chroma_weight): Re(s_c^0.02) as the score kernel forms it."""
+    return float(load().sr_vsi_chroma_weight(float(s_c)))
+
+
+def vsi_host(a: np.ndarray, b: np.ndarray) -> dict:
+    """Host only (sr_vsi_host_u8): the float64 restatement of VSI on two u8 host arrays (H x W x 3 / 4; any row stride,
+    channels dense) -> the record of Context.vsi.  ValueError as vsi_plan and for shapes that differ."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("vsi_host: need u8 images")
+    if a.shape != b.shape or a.ndim not in (2, 3):
+        raise ValueError(f"vsi_host: need two H x W x C images of one shape, got {a.shape} vs {b.shape}")
+    cn = a.shape[2] if a.ndim == 3 else 1
+    arrs = []
+    for v in (a, b):
+        dense = v.strides[-1] == 1 and (v.ndim == 2 or v.strides[1] == cn) and v.strides[0] >= v.shape[1] * cn
+        arrs.append(v if dense else np.ascontiguousarray(v))
+    rec = VsiSums()
+    check(load().sr_vsi_host_u8(C.c_void_p(arrs[0].ctypes.data), int(arrs[0].strides[0]), C.c_void_p(arrs[1].ctypes.data),
+                                int(arrs[1].strides[0]), int(a.shape[0]), int(a.shape[1]), int(cn), C.byref(rec)))
+    return _vsi_dict(rec)
 
 
 def delta_e_formula(formula) -> int:
@@ -1562,6 +1646,41 @@ class Context:
                                   int(cn), C.byref(out)))
         return {"sum_s": out.sum_s, "sum_sc": out.sum_sc, "sum_pcm": out.sum_pcm, "count": int(out.count), "F": int(out.F),
                 "size": (int(out.rows), int(out.cols))}
+
+    def vsi_pool_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, F) -> np.ndarray:
+        """sr_vsi_pool_u8 -> int64 [2 images, 3 (L, M, N times 100), rows, cols]: the window sums of VSI's pooling with an
+        explicit F (1 .. 256), rows x cols = ceil(h / F) x ceil(w / F).  Every argument is checked before the device is touched."""
+        h, w, cn, F = (_whole(v, n) for v, n in ((h, "h"), (w, "w"), (cn, "cn"), (F, "F")))
+        if not d_a or not d_b:
+            raise ValueError("vsi_pool_u8: null image pointer")
+        if h < 1 or w < 1 or F < 1:
+            raise ValueError("vsi_pool_u8: need h, w, F >= 1")
+        out = np.zeros((2, 3, (h + F - 1) // F, (w + F - 1) // F), np.int64)
+        check(self.lib.sr_vsi_pool_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), h, w, cn, F,
+                                      out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def vsi_saliency(self, d_img, stride, h, w, cn) -> dict:
+        """sr_vsi_saliency_u8 -> {'lab': [3, 256, 256], 'vs256': [256, 256], 'range': [min a, max a, min b, max b]} of ONE image:
+        the SDSP saliency on its fixed grid, for inspection.  Refusals as vsi."""
+        if not d_img:
+            raise ValueError("vsi_saliency: null image pointer")
+        lab, vs, rng = np.zeros((3, VSI_GRID, VSI_GRID), np.float64), np.zeros((VSI_GRID, VSI_GRID), np.float64), np.zeros(4, np.float64)
+        dp = C.POINTER(C.c_double)
+        check(self.lib.sr_vsi_saliency_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w), int(cn), lab.ctypes.data_as(dp),
+                                          vs.ctypes.data_as(dp), rng.ctypes.data_as(dp)))
+        return {"lab": lab, "vs256": vs, "range": rng}
+
+    def vsi(self, d_a, stride_a, d_b, stride_b, h, w, cn) -> dict:
+        """sr_vsi_u8 -> {'sum_s', 'sum_w', 'count', 'F', 'size', 'a_range', 'b_range', 'vs_range' ([2 images, (min, max)])} of the
+        pair (finish with vsi_value).  Every argument is checked before the device is touched: ValueError, its subclass
+        SrShapeError for a short stride or a side below 16, SrNativeError for a gray image or F above 256."""
+        if not d_a or not d_b:
+            raise ValueError("vsi: null image pointer")
+        out = VsiSums()
+        check(self.lib.sr_vsi_u8(self.handle, C.c_void_p(d_a), int(stride_a), C.c_void_p(d_b), int(stride_b), int(h), int(w),
+                                 int(cn), C.byref(out)))
+        return _vsi_dict(out)
 
     def delta_e_u8(self, d_a, stride_a, d_b, stride_b, h, w, cn, crop_border=0, formula=DELTA_E_2000, d_map=0,
                    map_stride=0) -> dict:

@@ -109,6 +109,8 @@ struct sr_ctx {
     DevBuf fsim_ws;                                     // FSIM: pooled sums, filters, twiddles, transform planes, partials
     int fsim_rows = 0, fsim_cols = 0;                   // the pooled size whose filters and twiddles the scratch holds (0: none)
     double fsim_consts[12] = {0};                       // ... and EM_n, S2, Sij of its four orientations
+    DevBuf vsi_ws;                                      // VSI: pooled sums, LG / SD / twiddles, the axis tables, the SDSP planes, partials
+    int vsi_h = 0, vsi_w = 0;                           // the image size whose tables the scratch holds (0: none)
     DevBuf deltae_ws;                                   // colour difference: the linearisation table, histogram, partials, cell slabs
     bool deltae_table = false;                          // the table is in place (false again whenever the buffer is regrown)
     DevBuf haarpsi_ws;                                  // HaarPSI: per-block partials; the per-cell form adds the sample map, edges, records
@@ -116,7 +118,7 @@ struct sr_ctx {
     // Frees every device buffer above; sr_ctx_destroy calls it with the stream drained and the device current.
     void release_device()
     {
-        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws, &brisque_ws, &vif_ws, &gmsd_ws, &fsim_ws, &deltae_ws, &haarpsi_ws, &imresize_tab.buf})
+        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws, &brisque_ws, &vif_ws, &gmsd_ws, &fsim_ws, &vsi_ws, &deltae_ws, &haarpsi_ws, &imresize_tab.buf})
             b->release();
     }
 };

@@ -41,6 +41,11 @@ inline int imr_reflect(long long u, int n)
 
 // Every refusal of one axis, then its tables.  scope names the caller in the message.
 int imr_axis(const char *scope, int n_in, int n_out, double scale, int antialias, ImrAxis *a);
+// The same contribution rule with the kernel named and no [1/16, 16] range on the scale: the cubic (support 4: what imr_axis
+// builds) or the triangle t(x) = max(0, 1 - |x|) (support 2: imresize's 'bilinear', which VSI resizes by; sr_vsi_host.cpp).
+// trim drops the taps that are zero for every output at both ends (imr_axis does); without it all P = ceil(kw) + 2 stay.
+enum ImrKernel { IMR_CUBIC = 0, IMR_TRIANGLE = 1 };
+int imr_axis_kernel(const char *scope, int n_in, int n_out, double scale, int antialias, ImrKernel kernel, bool trim, ImrAxis *a);
 // Every shape refusal of a call, both axes' tables and the geometry.
 int imr_plan(const char *scope, int h, int w, int cn, double scale_y, double scale_x, int dh, int dw, int antialias, ImrAxis *ay,
              ImrAxis *ax, ImrPlan *p);

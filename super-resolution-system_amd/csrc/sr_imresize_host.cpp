@@ -22,6 +22,12 @@ double cubic(double x)
     return 0.0;
 }
 
+double triangle(double x)
+{
+    x = std::fabs(x);
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
 int check_scale(const char *scope, const char *axis, double scale)
 {
     if (!(scale >= SCALE_MIN && scale <= SCALE_MAX))
@@ -36,11 +42,20 @@ int imr_axis(const char *scope, int n_in, int n_out, double scale, int antialias
     if (n_in < 1 || n_out < 1) return sr_set_error(SR_ERR_INVALID_ARG, "%s: sides must be >= 1 (got %d -> %d)", scope, n_in, n_out);
     const int rc = check_scale(scope, "axis", scale);
     if (rc) return rc;
+    return imr_axis_kernel(scope, n_in, n_out, scale, antialias, IMR_CUBIC, true, a);
+}
+
+int imr_axis_kernel(const char *scope, int n_in, int n_out, double scale, int antialias, ImrKernel kernel, bool trim, ImrAxis *a)
+{
+    if (n_in < 1 || n_out < 1) return sr_set_error(SR_ERR_INVALID_ARG, "%s: sides must be >= 1 (got %d -> %d)", scope, n_in, n_out);
+    if (!(scale > 0.0)) return sr_set_error(SR_ERR_INVALID_ARG, "%s: the scale must be positive (got %.17g)", scope, scale);
+    const bool tri = kernel == IMR_TRIANGLE;
+    const double support = tri ? 2.0 : 4.0;
     if (std::ceil((double)n_in * scale) != (double)n_out && scale != (double)n_out / (double)n_in)
         return sr_set_error(SR_ERR_INVALID_ARG, "%s: %d -> %d is neither ceil(n * scale) nor scale = m / n for scale %.17g", scope, n_in,
                             n_out, scale);
     const bool shrink = antialias && scale < 1.0;
-    const double kw = shrink ? 4.0 / scale : 4.0;
+    const double kw = shrink ? support / scale : support;
     const int P = (int)std::ceil(kw) + 2;
     std::vector<double> w((size_t)n_out * P);
     std::vector<long long> left(n_out);
@@ -52,7 +67,8 @@ int imr_axis(const char *scope, int n_in, int n_out, double scale, int antialias
         double sum = 0.0;
         for (int k = 0; k < P; ++k) {
             const double d = u - lf - (double)k;
-            row[k] = shrink ? scale * cubic(scale * d) : cubic(d);
+            if (tri) row[k] = shrink ? scale * triangle(scale * d) : triangle(d);
+            else row[k] = shrink ? scale * cubic(scale * d) : cubic(d);
             sum += row[k];
         }
         for (int k = 0; k < P; ++k) row[k] /= sum;
@@ -64,8 +80,8 @@ int imr_axis(const char *scope, int n_in, int n_out, double scale, int antialias
             if (w[(size_t)i * P + k] != 0.0) return false;
         return true;
     };
-    while (c0 < c1 && all_zero(c0)) ++c0;
-    while (c1 > c0 && all_zero(c1)) --c1;
+    while (trim && c0 < c1 && all_zero(c0)) ++c0;
+    while (trim && c1 > c0 && all_zero(c1)) --c1;
     const int taps = c1 - c0 + 1;
     a->n_in = n_in;
     a->n_out = n_out;

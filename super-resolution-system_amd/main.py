@@ -76,6 +76,7 @@ class PipelineConfig:
                                # resize of the source (the reference), on the exact luma ('vifp', 'vifp_scales')
     qa_gmsd: bool = False      # (with enable_qa): ... and the gradient magnitude similarity deviation of the same pair ('gmsd')
     qa_fsim: bool = False      # (with enable_qa): ... and the phase-congruency feature similarity of the same pair ('fsim', 'fsimc')
+    qa_vsi: bool = False       # (with enable_qa): ... and the visual saliency-induced index (SDSP saliency) of the same pair ('vsi')
     qa_delta_e: bool = False   # (with enable_qa): stage 4 also reports the per-pixel CIEDE2000 colour difference of the canvas against the
                                # INTER_CUBIC resize of the source ('delta_e'; with qa_map_cell > 0 also 'delta_e_map' over the same cells)
     qa_haarpsi: bool = False   # (with enable_qa): stage 4 also reports HaarPSI of the canvas against the INTER_CUBIC resize of the source
@@ -339,6 +340,32 @@ class SuperResolutionPipeline:
                 report['fsim'], report['fsimc'] = float(v['fsim']), float(v['fsimc'])
             else:
                 report['fsim_note'] = "the pair is flat: FSIM is 0 / 0"
+        finally:
+            ctx.sync()
+            ref.free()
+
+    def _vsi(self, ctx, report: Dict[str, Any], d_src: int, src_shape, d_canvas: int, canvas_shape) -> None:
+        """Stage 4's optional 'vsi' entry (qa_vsi): VSI of the canvas against the INTER_CUBIC resize of the source to the canvas
+        size, both in HBM.  A refusal of the plan (a side below 16, a gray image, F above 256) or a NaN value (a flat a or b
+        plane, a constant saliency map) gives None and 'vsi_note' says why (the run does not fail).  The value does not enter
+        overall_score.  One helper for the device-resident, the host-array and the sharded path."""
+        import _native
+        H, W, cn = int(canvas_shape[0]), int(canvas_shape[1]), int(canvas_shape[2])
+        ih, iw = int(src_shape[0]), int(src_shape[1])
+        report['vsi'] = None
+        try:
+            _native.vsi_plan(H, W, cn)
+        except (ValueError, _native.SrNativeError) as exc:
+            report['vsi_note'] = str(exc)
+            return
+        ref = ctx.alloc(H * W * cn)
+        try:
+            ctx.resize_cubic_u8(d_src, iw * cn, ih, iw, cn, ref.ptr, W * cn, H, W)
+            v = self.quality_module.calculate_vsi_device(ref.ptr, (H, W, cn), d_canvas, (H, W, cn))['vsi']
+            if v == v:
+                report['vsi'] = float(v)
+            else:
+                report['vsi_note'] = "the pair is flat in a, b or saliency: VSI is 0 / 0"
         finally:
             ctx.sync()
             ref.free()
@@ -650,6 +677,8 @@ class SuperResolutionPipeline:
                     self._haarpsi(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_fsim:
                     self._fsim(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
+                if self.config.qa_vsi:
+                    self._vsi(ctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.ptr, (H, W, 3))
                 if self.config.qa_niqe_params:
                     self._niqe_model(ctx, report, canvas.ptr, (H, W, 3))
                 if self.config.qa_brisque_model:
@@ -764,6 +793,8 @@ class SuperResolutionPipeline:
                         self._haarpsi(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_fsim:
                         self._fsim(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
+                    if self.config.qa_vsi:
+                        self._vsi(qctx, report, ts.d_img.ptr, (ih, iw, 3), canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_niqe_params:
                         self._niqe_model(qctx, report, canvas.data_ptr(), (H, W, 3))
                     if self.config.qa_brisque_model:
@@ -892,6 +923,13 @@ class SuperResolutionPipeline:
                         self._fsim(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
                     finally:
                         d_src.free(); d_fused.free()
+                if self.config.qa_vsi:
+                    qctx = self.quality_module._ctx()
+                    d_src, d_fused = qctx.upload(original), qctx.upload(fused)
+                    try:
+                        self._vsi(qctx, report, d_src.ptr, original.shape, d_fused.ptr, fused.shape)
+                    finally:
+                        d_src.free(); d_fused.free()
                 if self.config.qa_niqe_params:
                     qctx = self.quality_module._ctx()
                     d_fused = qctx.upload(fused)
@@ -967,6 +1005,9 @@ async def main() -> int:
     ap.add_argument("--qa-gmsd", action="store_true",
                     help="stage 4 also reports the gradient magnitude similarity deviation of the result against the bicubic "
                          "resize of the input (report key gmsd)")
+    ap.add_argument("--qa-vsi", action="store_true",
+                    help="stage 4 also reports VSI (visual saliency-induced index, SDSP saliency) of the result against the "
+                         "bicubic resize of the input (report key vsi)")
     ap.add_argument("--qa-delta-e", action="store_true",
                     help="stage 4 also reports the per-pixel CIEDE2000 colour difference of the result against the bicubic resize "
                          "of the input (report key delta_e; with --qa-map-cell also delta_e_map over the same cells)")
@@ -1013,7 +1054,7 @@ async def main() -> int:
         return 2
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     cfg = PipelineConfig(block_size=args.block_size, sr_scale=args.sr_scale, sr_weights=args.sr_weights, sr_act=args.sr_act, sr_ensemble=args.sr_ensemble,
-                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark, qa_vif=args.qa_vif, qa_gmsd=args.qa_gmsd, qa_delta_e=args.qa_delta_e, qa_haarpsi=args.qa_haarpsi, qa_map_cell=args.qa_map_cell, qa_fsim=args.qa_fsim,
+                         qa_ms_ssim=args.qa_ms_ssim, qa_benchmark=args.qa_benchmark, qa_vif=args.qa_vif, qa_gmsd=args.qa_gmsd, qa_delta_e=args.qa_delta_e, qa_haarpsi=args.qa_haarpsi, qa_map_cell=args.qa_map_cell, qa_fsim=args.qa_fsim, qa_vsi=args.qa_vsi,
                          qa_niqe_params=args.qa_niqe_params, qa_brisque_model=args.qa_brisque_model, qa_dists_weights=args.qa_dists_weights,
                          benchmark_degrade=args.benchmark_degrade)
     if args.plan_only:

@@ -697,6 +697,58 @@ class QualityAssessmentModule:
             raise ValueError("calculate_fsim: null device pointer")
         return self._fsim_dev(self._ctx(), int(d_img1), int(d_img2), args, return_parts)
 
+    # -- VSI (no reference counterpart: the authors' VSI.m with SDSP.m) ---------------------------------------------------------
+    @staticmethod
+    def _vsi_args(shape1, shape2, stride1, stride2) -> Tuple[int, int, int, int, int]:
+        """Every refusal of the VSI methods, on the host: ValueError (SrShapeError for a side below 16 or a short stride),
+        SrNativeError for a gray image or F above 256.  -> (h, w, cn, stride1, stride2)."""
+        shape1, shape2 = tuple(int(v) for v in shape1), tuple(int(v) for v in shape2)
+        if shape1 != shape2:
+            raise ValueError(f"calculate_vsi: images must have the same shape, got {shape1} vs {shape2} "
+                             "(nothing is cropped to a common rectangle)")
+        if len(shape1) not in (2, 3):
+            raise ValueError(f"calculate_vsi: need an H x W x C image, got shape {shape1}")
+        cn = shape1[2] if len(shape1) == 3 else 1
+        _native.vsi_plan(shape1[0], shape1[1], cn)
+        row = shape1[1] * cn
+        s1, s2 = (row if s is None else int(s) for s in (stride1, stride2))
+        if s1 < row or s2 < row:
+            raise _native.SrShapeError("calculate_vsi: stride smaller than a row")
+        return shape1[0], shape1[1], cn, s1, s2
+
+    @staticmethod
+    def _vsi_dev(ctx, d1: int, d2: int, args, return_parts: bool) -> Dict[str, Any]:
+        h, w, cn, s1, s2 = args
+        parts = ctx.vsi(d1, s1, d2, s2, h, w, cn)
+        out = {'vsi': _native.vsi_value(parts)}
+        if return_parts:
+            out['parts'] = parts
+        return out
+
+    def calculate_vsi(self, img1: np.ndarray, img2: np.ndarray, return_parts: bool = False) -> Dict[str, Any]:
+        """VSI (Zhang, Shen and Li 2014, the authors' VSI.m with SDSP saliency), as include/sr_hip.h defines it -> {'vsi'}: u8
+        images of equal shape with 3 (RGB) or 4 channels (alpha ignored), both sides at least 16.  Symmetric; 1 for
+        identical images, NaN for a pair with a flat a or b plane.  return_parts adds 'parts', the record of the two sums
+        with F, the pooled size and the ranges of a, b and the saliency map."""
+        a = self._require_u8(np.asarray(img1), "calculate_vsi")
+        b = self._require_u8(np.asarray(img2), "calculate_vsi")
+        args = self._vsi_args(a.shape, b.shape, None, None)
+        ctx = self._ctx()
+        da, db = _DevImage(ctx, a), _DevImage(ctx, b)
+        try:
+            return self._vsi_dev(ctx, da.ptr, db.ptr, args, return_parts)
+        finally:
+            da.free(); db.free()
+
+    def calculate_vsi_device(self, d_img1: int, shape1, d_img2: int, shape2, return_parts: bool = False,
+                             stride1: Optional[int] = None, stride2: Optional[int] = None) -> Dict[str, Any]:
+        """calculate_vsi on two u8 images that already live in HBM (device addresses + shapes; strides in bytes, dense when
+        None)."""
+        args = self._vsi_args(shape1, shape2, stride1, stride2)
+        if not d_img1 or not d_img2:
+            raise ValueError("calculate_vsi: null device pointer")
+        return self._vsi_dev(self._ctx(), int(d_img1), int(d_img2), args, return_parts)
+
     # -- colour difference (no reference counterpart: scikit-image's rgb2lab and deltaE_ciede2000 / deltaE_cie76) ------------
     @staticmethod
     def _delta_e_args(what: str, shape1, shape2, crop_border, formula, stride1, stride2):
