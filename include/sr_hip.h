@@ -408,6 +408,75 @@ SR_API int sr_forbidden_map(sr_ctx *ctx, const uint8_t *d_sal, int h, int w, int
 SR_API int sr_rect_counts_u8(sr_ctx *ctx, const uint8_t *d_map, int64_t stride, int h, int w, const sr_tile_rect *h_rects,
                              int n, uint64_t *h_counts);
 
+/* ---- MSER text regions (ContentAnalyzer.detect_text_regions, tiling_module.py:214-237, 358-362; csrc/sr_mser.hip) -------
+ * PARITY UNPINNED: cv2 is not available to this repository's tests, so agreement with cv2.MSER_create() is not claimed and
+ * not tested.  What is built is Matas' maximally stable extremal regions in component-tree form, with OpenCV's default
+ * parameter values and OpenCV's 4-neighbourhood, pinned by a Python restatement, by a brute-force tree through
+ * scipy.ndimage.label and by sr_mser_host_u8; every comparison is exact (all records are integers).  Not built: colour
+ * MSER (MSCR), 8-connectivity, the regions' pixel lists.
+ *
+ * Input: a u8 image, cn 1 / 3 / 4 (alpha ignored), row stride in bytes; g = the gray plane of the content section above
+ * (cv2.COLOR_BGR2GRAY applied to the RGB data, 15-bit rule; cn 1: the value itself).
+ * Polarity: dark regions use g (polarity 0), bright regions 255 - g (polarity 1); each has its own tree.  polarity_mask:
+ * bit 0 dark, bit 1 bright; the default of the Python mirror is both, dark first.
+ * Component tree: for t = 0 .. 255 take the 4-connected components of {p : g(p) <= t}.  A node is a pair (component C,
+ * level t) where C holds at least one pixel with g = t.  The parent of a node is the node of the smallest level t' > t
+ * whose component contains C; the component of level max g is the root.  A node carries level, area = |C|, the inclusive
+ * box x0, y0, x1, y1 and seed = the smallest row-major pixel index in C; (level, seed) identifies it.
+ * Variation: S(n) = the area of the ancestor-or-self of n with the largest level <= level(n) + delta (the walk stops at
+ * the root); var(n) = (S(n) - area(n)) / area(n).  Two variations are compared by cross-multiplication in int64,
+ * (S_a - A_a) A_b against (S_b - A_b) A_a: nothing rounds.
+ * Maximally stable: n is stable iff var(n) <= var(parent(n)) (when it has a parent) and var(n) <= var(c) for every child
+ * c.  Ties knock out nobody; the root takes part like any other node.
+ * Filters, on stable nodes only: min_area <= area <= max_area, and in float64 (double)(S - area) < max_variation *
+ * (double)area (one multiplication, not contracted).
+ * Diversity: for a node n that passed the filters let a be its nearest ancestor that also passed them; n is dropped iff, in
+ * float64, (double)(area(a) - area(n)) < min_diversity * (double)area(a).  The ancestor's own fate under this rule does not
+ * matter.
+ * Defaults: delta 5, min_area 60, max_area 14400, max_variation 0.25, min_diversity 0.2.
+ * Output order: polarity (dark first), then level, then seed.  Equal inputs give equal bytes.
+ * SR_ERR_UNSUPPORTED: more than 2^24 pixels (4096 x 4096: indices stay int32 and the workspace, 53 bytes per pixel + 12 KiB,
+ * stays below 1 GiB), delta outside 1 .. 255, min_area < 1, max_area < min_area, a negative or NaN max_variation /
+ * min_diversity. */
+typedef struct sr_mser_params {
+    int delta, min_area, max_area;
+    double max_variation, min_diversity;
+} sr_mser_params;
+typedef struct sr_mser_region {
+    int polarity, level, area, x0, y0, x1, y1, seed, S;
+} sr_mser_region;
+typedef struct sr_mser_node {
+    int level, area, x0, y0, x1, y1, seed, parent_level, parent_seed; /* parent_*: -1 for the root */
+} sr_mser_node;
+SR_API int sr_mser_default_params(sr_mser_params *out);
+/* Host only: every refusal above, the bytes of context workspace of one call and the capacity of its node table (either
+ * output may be NULL). */
+SR_API int sr_mser_plan(int h, int w, const sr_mser_params *params, size_t *workspace_bytes, int64_t *node_cap);
+/* The regions of the image in HBM -> h_regions (the first cap of them in output order); *count is the true total even when it
+ * exceeds cap.  Level-synchronous union-find; the workspace comes from the context and is never read before it is written.
+ * Synchronous. */
+SR_API int sr_mser_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, int cn, const sr_mser_params *params,
+                      int polarity_mask, sr_mser_region *h_regions, int64_t cap, int64_t *count);
+/* For inspection: the whole node table of one polarity (0 dark, 1 bright) in (level, seed) order.  *count is the number of
+ * nodes; when it exceeds cap nothing else is written.  Synchronous. */
+SR_API int sr_mser_tree_u8(sr_ctx *ctx, const uint8_t *d_img, int64_t stride, int h, int w, int cn, int polarity,
+                           sr_mser_node *h_nodes, int64_t cap, int64_t *count);
+/* The records of the last sr_mser_u8 call on this context, kept on the host in output order: the first cap of them ->
+ * h_regions, *count the total.  No device work: a caller whose buffer was short fetches the rest here instead of running the
+ * detection again.  Empty before the first call and after a call that failed. */
+SR_API int sr_mser_last_regions(sr_ctx *ctx, sr_mser_region *h_regions, int64_t cap, int64_t *count);
+/* For tests: the context's MSER workspace (NULL and 0 before the first call).  A call never reads what it held before. */
+SR_API int sr_mser_workspace(sr_ctx *ctx, void **d_ptr, size_t *bytes);
+/* The host twins: the same definition on host pointers (sorted-pixel sequential union-find), the restatement the device is
+ * held to. */
+SR_API int sr_mser_host_u8(const uint8_t *img, int64_t stride, int h, int w, int cn, const sr_mser_params *params,
+                           int polarity_mask, sr_mser_region *regions, int64_t cap, int64_t *count);
+SR_API int sr_mser_tree_host_u8(const uint8_t *img, int64_t stride, int h, int w, int cn, int polarity, sr_mser_node *nodes,
+                                int64_t cap, int64_t *count);
+/* Host only: the text boxes of tiling_module.py:231-235 in region order, duplicates kept: (x, y, w, h) = (x0, y0,
+ * x1 - x0 + 1, y1 - y0 + 1), kept iff w > 20 and h > 10 and (double)w < image_w * 0.5.  rects needs room for n. */
+SR_API int sr_mser_text_boxes(const sr_mser_region *regions, int64_t n, int image_w, sr_tile_rect *rects, int64_t *m);
+
 /* ---- BlendingModule.poisson_fusion / repair_seams (blending_module.py:563-659, 1148-1240; csrc/sr_poisson.hip) ---------------
  * PARITY UNPINNED: cv2 is not available to this repository's tests, so the OpenCV behaviour below is restated from memory
  * (Cloning::normalClone of photo/src/seamless_cloning_impl.cpp, GaussianBlur's 8-bit fixed-point path) and tested against this

@@ -122,6 +122,20 @@ class HaarPsiCell(C.Structure):
     _fields_ = [("num", C.c_double), ("den", C.c_double)]
 
 
+class MserParams(C.Structure):
+    """sr_mser_params (include/sr_hip.h)."""
+    _fields_ = [("delta", C.c_int), ("min_area", C.c_int), ("max_area", C.c_int), ("max_variation", C.c_double),
+                ("min_diversity", C.c_double)]
+
+
+MSER_REGION_FIELDS = ("polarity", "level", "area", "x0", "y0", "x1", "y1", "seed", "S")
+MSER_NODE_FIELDS = ("level", "area", "x0", "y0", "x1", "y1", "seed", "parent_level", "parent_seed")
+# sr_mser_region / sr_mser_node (include/sr_hip.h) as structured dtypes: nine int32 each
+MSER_REGION_DTYPE = np.dtype([(f, np.int32) for f in MSER_REGION_FIELDS])
+MSER_NODE_DTYPE = np.dtype([(f, np.int32) for f in MSER_NODE_FIELDS])
+MSER_DARK, MSER_BRIGHT, MSER_BOTH = 1, 2, 3               # polarity_mask bits
+
+
 # enum sr_haarpsi_convention (include/sr_hip.h)
 HAARPSI_MATLAB, HAARPSI_PYTHON = 0, 1
 HAARPSI_CONVENTIONS = {"matlab": HAARPSI_MATLAB, "python": HAARPSI_PYTHON}
@@ -349,6 +363,15 @@ SIGNATURES = {
     "sr_delta_e_rms": (_dbl, [C.POINTER(DeltaESums)]),
     "sr_delta_e_percentile": (_dbl, [C.POINTER(DeltaESums), _dbl]),
     "sr_delta_e_fraction_at_least": (_i, [C.POINTER(DeltaESums), _dbl, C.POINTER(_dbl)]),
+    "sr_mser_default_params": (_i, [C.POINTER(MserParams)]),
+    "sr_mser_plan": (_i, [_i, _i, C.POINTER(MserParams), C.POINTER(_sz), C.POINTER(_i64)]),
+    "sr_mser_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(MserParams), _i, _vp, _i64, C.POINTER(_i64)]),
+    "sr_mser_tree_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i64, C.POINTER(_i64)]),
+    "sr_mser_last_regions": (_i, [_vp, _vp, _i64, C.POINTER(_i64)]),
+    "sr_mser_workspace": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    "sr_mser_host_u8": (_i, [_vp, _i64, _i, _i, _i, C.POINTER(MserParams), _i, _vp, _i64, C.POINTER(_i64)]),
+    "sr_mser_tree_host_u8": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, C.POINTER(_i64)]),
+    "sr_mser_text_boxes": (_i, [_vp, _i64, _i, C.POINTER(TileRect), C.POINTER(_i64)]),
     "sr_haarpsi_plan": (_i, [_i, _i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), _pi, C.POINTER(_sz)]),
     "sr_haarpsi_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(HaarPsiSums)]),
     "sr_haarpsi_cells_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _pi, _i, _pi, _i, C.POINTER(HaarPsiCell)]),
@@ -1086,6 +1109,100 @@ def haarpsi_host(a: np.ndarray, b: np.ndarray, crop_border: int = 0, subsample=T
                                     int(arrs[1].strides[0]), int(a.shape[0]), int(a.shape[1]), int(cn), crop_border, subsample,
                                     convention, C.byref(rec)))
     return _haarpsi_dict(rec)
+
+
+def mser_params(delta=None, min_area=None, max_area=None, max_variation=None, min_diversity=None) -> "MserParams":
+    """sr_mser_default_params with the given fields replaced (None: the default).  ValueError for a count that is not a whole
+    number; the ranges are the library's to refuse (NotImplementedError from mser_plan and every call)."""
+    p = MserParams()
+    check(load().sr_mser_default_params(C.byref(p)))
+    for name, v in (("delta", delta), ("min_area", min_area), ("max_area", max_area)):
+        if v is not None:
+            if isinstance(v, bool) or int(v) != v or not (-2 ** 31 <= int(v) < 2 ** 31):
+                raise ValueError(f"mser: {name} must be a whole number, got {v!r}")
+            setattr(p, name, int(v))
+    if max_variation is not None:
+        p.max_variation = float(max_variation)
+    if min_diversity is not None:
+        p.min_diversity = float(min_diversity)
+    return p
+
+
+def _mser_polarity_mask(polarity_mask) -> int:
+    if isinstance(polarity_mask, bool) or polarity_mask not in (MSER_DARK, MSER_BRIGHT, MSER_BOTH):
+        raise ValueError(f"mser: polarity_mask must be 1 (dark), 2 (bright) or 3 (both), got {polarity_mask!r}")
+    return int(polarity_mask)
+
+
+def mser_plan(h: int, w: int, params: Optional["MserParams"] = None) -> dict:
+    """Host only (sr_mser_plan) -> {'workspace_bytes', 'node_cap'}.  ValueError for h or w < 1; NotImplementedError for every
+    refusal of the definition (more than 2^24 pixels, delta outside 1..255, min_area < 1, max_area < min_area, a negative or
+    NaN max_variation / min_diversity)."""
+    params = params if params is not None else mser_params()
+    ws, cap = _sz(0), _i64(0)
+    _check_unsupported(load().sr_mser_plan(int(h), int(w), C.byref(params), C.byref(ws), C.byref(cap)))
+    return {"workspace_bytes": int(ws.value), "node_cap": int(cap.value)}
+
+
+def _mser_host_image(img, what: str):
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3, 4)) or img.size == 0:
+        raise ValueError(f"{what}: need a u8 H x W or H x W x 1 / 3 / 4 image")
+    cn = img.shape[2] if img.ndim == 3 else 1
+    dense = img.strides[-1] == 1 and (img.ndim == 2 or img.strides[1] == cn) and img.strides[0] >= img.shape[1] * cn
+    return (img if dense else np.ascontiguousarray(img)), cn
+
+
+MSER_FIRST_CAP = 65536            # records of a first buffer: 2.3 MB; text pages stay far below it
+
+
+def _mser_fetch(call, dtype, cap: int, again=None) -> np.ndarray:
+    """call(buffer, cap, count) once with room for cap records; when the count is larger, again(buffer, count, count) (default:
+    the same call, which computes everything a second time) fills a buffer of the whole count."""
+    out = np.zeros(max(int(cap), 1), dtype=dtype)
+    n = _i64(0)
+    _check_unsupported(call(C.c_void_p(out.ctypes.data), int(out.shape[0]), C.byref(n)))
+    if n.value > out.shape[0]:
+        out = np.zeros(int(n.value), dtype=dtype)
+        _check_unsupported((again or call)(C.c_void_p(out.ctypes.data), int(out.shape[0]), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def mser_host(img: np.ndarray, params: Optional["MserParams"] = None, polarity_mask: int = MSER_BOTH) -> np.ndarray:
+    """Host only (sr_mser_host_u8): the restatement of the MSER definition on a u8 host array -> the regions as a structured
+    array (MSER_REGION_DTYPE) in output order.  One run for up to MSER_FIRST_CAP regions; above that the restatement (which
+    keeps nothing between calls) runs a second time with room for all of them."""
+    img, cn = _mser_host_image(img, "mser_host")
+    params = params if params is not None else mser_params()
+    mask = _mser_polarity_mask(polarity_mask)
+    lib = load()
+    return _mser_fetch(lambda buf, cap, n: lib.sr_mser_host_u8(C.c_void_p(img.ctypes.data), int(img.strides[0]), int(img.shape[0]),
+                                                               int(img.shape[1]), cn, C.byref(params), mask, buf, cap, n),
+                       MSER_REGION_DTYPE, MSER_FIRST_CAP)
+
+
+def mser_tree_host(img: np.ndarray, polarity: int = 0) -> np.ndarray:
+    """Host only (sr_mser_tree_host_u8): the whole node table of one polarity (0 dark, 1 bright) in (level, seed) order
+    (MSER_NODE_DTYPE).  The first buffer holds a node per pixel up to 2^20 nodes (one run); a larger table takes a second run
+    with the count the first one reported."""
+    img, cn = _mser_host_image(img, "mser_tree_host")
+    if polarity not in (0, 1):
+        raise ValueError(f"mser_tree_host: polarity must be 0 or 1, got {polarity!r}")
+    lib = load()
+    return _mser_fetch(lambda buf, cap, n: lib.sr_mser_tree_host_u8(C.c_void_p(img.ctypes.data), int(img.strides[0]),
+                                                                    int(img.shape[0]), int(img.shape[1]), cn, int(polarity), buf,
+                                                                    cap, n),
+                       MSER_NODE_DTYPE, min(int(img.shape[0]) * int(img.shape[1]), 1 << 20))
+
+
+def mser_text_boxes(regions: np.ndarray, image_w: int) -> List[Tuple[int, int, int, int]]:
+    """Host only (sr_mser_text_boxes): the (x, y, w, h) boxes of tiling_module.py:231-235 in region order, duplicates kept."""
+    regions = np.ascontiguousarray(regions, dtype=MSER_REGION_DTYPE)
+    n = int(regions.shape[0])
+    rects = (TileRect * max(n, 1))()
+    m = _i64(0)
+    check(load().sr_mser_text_boxes(C.c_void_p(regions.ctypes.data), n, int(image_w), rects, C.byref(m)))
+    return [(rects[i].x, rects[i].y, rects[i].w, rects[i].h) for i in range(m.value)]
 
 
 def imresize_size(n: int, scale: float) -> int:
@@ -1914,6 +2031,42 @@ class Context:
         rects = (TileRect * max(n, 1))(*[TileRect(int(x), int(y), int(rw), int(rh)) for (x, y, rw, rh) in rects_xywh])
         check(self.lib.sr_rect_counts_u8(self.handle, C.c_void_p(d_map), int(stride), int(h), int(w), rects, n, out))
         return [int(out[i]) for i in range(n)]
+
+    # MSER text regions (sr_mser.hip) ----------------------------------------------------------
+    def mser(self, d_img: int, stride: int, h: int, w: int, cn: int, params: Optional["MserParams"] = None,
+             polarity_mask: int = MSER_BOTH) -> np.ndarray:
+        """sr_mser_u8: the MSER regions of the u8 image in HBM as a structured array (MSER_REGION_DTYPE) in output order
+        (polarity, level, seed).  Every refusal is raised before the device is touched (mser_plan).  The detection runs ONCE
+        whatever the count: records beyond the first MSER_FIRST_CAP are fetched from the copy the context keeps
+        (sr_mser_last_regions), without device work.  Synchronous."""
+        params = params if params is not None else mser_params()
+        mask = _mser_polarity_mask(polarity_mask)
+        if not d_img:
+            raise ValueError("mser: null image pointer")
+        mser_plan(h, w, params)
+        return _mser_fetch(lambda buf, cap, n: self.lib.sr_mser_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w),
+                                                                   int(cn), C.byref(params), mask, buf, cap, n),
+                           MSER_REGION_DTYPE, MSER_FIRST_CAP,
+                           again=lambda buf, cap, n: self.lib.sr_mser_last_regions(self.handle, buf, cap, n))
+
+    def mser_workspace(self) -> Tuple[int, int]:
+        """sr_mser_workspace -> (device address, bytes) of the context's MSER workspace; (0, 0) before the first call."""
+        p, n = _vp(None), _sz(0)
+        check(self.lib.sr_mser_workspace(self.handle, C.byref(p), C.byref(n)))
+        return int(p.value or 0), int(n.value)
+
+    def mser_tree(self, d_img: int, stride: int, h: int, w: int, cn: int, polarity: int = 0) -> np.ndarray:
+        """sr_mser_tree_u8: the whole node table of one polarity (0 dark, 1 bright) in (level, seed) order (MSER_NODE_DTYPE).
+        Synchronous."""
+        if polarity not in (0, 1):
+            raise ValueError(f"mser_tree: polarity must be 0 or 1, got {polarity!r}")
+        if not d_img:
+            raise ValueError("mser_tree: null image pointer")
+        plan = mser_plan(h, w)
+        # a node per pixel up to 2^20 nodes in one run; a larger table takes a second run with the reported count
+        return _mser_fetch(lambda buf, cap, n: self.lib.sr_mser_tree_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w),
+                                                                        int(cn), int(polarity), buf, cap, n),
+                           MSER_NODE_DTYPE, min(plan["node_cap"], 1 << 20))
 
     # Poisson fusion and seam repair (sr_poisson.hip) ------------------------------------------
     def poisson_clone_u8(self, d_dest: int, dest_stride: int, d_patch: int, patch_stride: int, d_mask: int, mask_stride: int,

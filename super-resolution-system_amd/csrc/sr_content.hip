@@ -1,7 +1,7 @@
 // sr_content.hip -- ContentAnalyzer (tiling_module.py:174-370 of the reference) on gfx950: the spectral-residual saliency
 // map (:261-289), the local entropy map (:291-321), the forbidden-zone map (:323-370) and the per-tile counts behind
-// metadata.roi_flags (:752-757).  Haar faces and MSER text are host callables of the Python mirror; their boxes arrive
-// here as rectangles.
+// metadata.roi_flags (:752-757).  Haar faces are a host callable of the Python mirror; MSER text regions come from
+// sr_mser.hip (or from a host callable); the boxes of both arrive here as rectangles.
 //
 //   k_ct_pack        gray plane (cv2.COLOR_BGR2GRAY applied to the RGB data: channel 0 takes the blue weight) as complex
 //                    lines

@@ -12,10 +12,18 @@ takes without cv2's contrib saliency module), the local entropy map, the forbidd
 either (positions are always the uniform grid): the flags are an annotation.  An analyzer is opt-in
 (``TilingModule(content_analyzer=ContentAnalyzer())``); without one nothing is launched and ``roi_flags`` stays ``{}``.
 
-Not on this path: the Haar face cascade and MSER text detection (OpenCV models and internals that cannot be restated) --
-``ContentAnalyzer`` takes them as optional host callables; without a face detector ``detect_faces`` returns ``[]`` (what
-the reference does when the cascade file is missing), without a text detector ``detect_text_regions`` raises
-NotImplementedError.  The ``cv2.saliency`` fine-grained branch is not rebuilt.  The L1/L2 tile caches and the JSON
+MSER text regions (tiling_module.py:214-237, 358-362): ``MserTextDetector`` runs the component tree and the selection
+rules on the GPU (csrc/sr_mser.hip; the definition is in include/sr_hip.h, "MSER").  PARITY UNPINNED: cv2 is not available
+to this repository's tests; the detector is Matas' MSER in component-tree form with OpenCV's default parameter values and
+4-neighbourhood, held exactly to a restatement and a brute-force check, not to ``cv2.MSER_create()``.  It is opt-in:
+``ContentAnalyzer(text_detector='mser')`` (or any host callable); with the default ``text_detector=None``
+``detect_text_regions`` raises NotImplementedError as before.  With the GPU detector the ``*_device`` forms take the text
+boxes from the image already in HBM and need no ``host_image``.  Not built: colour MSER (MSCR), 8-connectivity, the
+regions' pixel lists.
+
+Not on this path: the Haar face cascade (an OpenCV model that cannot be restated) -- ``ContentAnalyzer`` takes an optional
+host callable; without one ``detect_faces`` returns ``[]`` (what the reference does when the cascade file is missing).
+The ``cv2.saliency`` fine-grained branch is not rebuilt.  The L1/L2 tile caches and the JSON
 checkpoint are host-side persistence outside the tile -> blend -> assess path and are NOT rebuilt; only
 the constructor's cache-directory side effect and the ``restore_from_cache`` probe of main.py:299-304 exist.
 
@@ -150,11 +158,55 @@ class DeviceForbiddenMap:
 Box = Tuple[int, int, int, int]
 
 
+class MserTextDetector:
+    """MSER text regions on the GPU (csrc/sr_mser.hip; definition and PARITY UNPINNED note in include/sr_hip.h, "MSER"):
+    a valid ``text_detector=`` of ContentAnalyzer.  The parameters are OpenCV's defaults; every refusal of the definition
+    (NotImplementedError) is raised by the constructor.  Images are uint8 HxW or HxWx{1,3,4} (alpha ignored)."""
+
+    def __init__(self, delta: int = 5, min_area: int = 60, max_area: int = 14400, max_variation: float = 0.25,
+                 min_diversity: float = 0.2, device: int = 0):
+        self.params = _native.mser_params(delta, min_area, max_area, max_variation, min_diversity)
+        _native.mser_plan(1, 1, self.params)
+        self.device = device
+
+    def _ctx(self) -> "_native.Context":
+        return _native.default_context(self.device)
+
+    def regions_device(self, d_image: int, shape, stride: Optional[int] = None) -> np.ndarray:
+        """The regions (structured array, ``_native.MSER_REGION_DTYPE``, in polarity / level / seed order) of a u8 image
+        already in HBM; ``stride``: its row stride in bytes (default: dense)."""
+        h, w, cn = ContentAnalyzer._check_shape(shape, "MserTextDetector")
+        _native.mser_plan(h, w, self.params)
+        return self._ctx().mser(d_image, w * cn if stride is None else int(stride), h, w, cn, self.params)
+
+    def detect_device(self, d_image: int, shape, stride: Optional[int] = None) -> List[Box]:
+        """The text boxes ``(x, y, w, h)`` of tiling_module.py:231-235 (w > 20, h > 10, w < W * 0.5) in region order."""
+        return _native.mser_text_boxes(self.regions_device(d_image, shape, stride), int(shape[1]))
+
+    def _on_device(self, image, fn):
+        img = ContentAnalyzer._check_image(image, "MserTextDetector")
+        _native.mser_plan(img.shape[0], img.shape[1], self.params)
+        ctx = self._ctx()
+        d_img = ctx.upload(img)
+        try:
+            return fn(d_img.ptr, img.shape)
+        finally:
+            d_img.free()
+
+    def regions(self, image: np.ndarray) -> np.ndarray:
+        return self._on_device(image, self.regions_device)
+
+    def __call__(self, image: np.ndarray) -> List[Box]:
+        return self._on_device(image, self.detect_device)
+
+
 class ContentAnalyzer:
     """Key-region analysis for content-aware tiling (tiling_module.py:174-370) on the GPU.
 
     ``face_detector`` / ``text_detector``: optional host callables ``image -> [(x, y, w, h)]`` standing in for the
-    reference's Haar cascade and MSER (not restated).  Images are uint8 HxW or HxWx{1,3,4} (alpha ignored); every check
+    reference's Haar cascade and MSER; ``text_detector='mser'`` is shorthand for ``MserTextDetector(device=device)``, the
+    GPU detector, whose boxes the ``*_device`` forms take from the image in HBM.  Images are uint8 HxW or HxWx{1,3,4}
+    (alpha ignored); every check
     runs before device work.  The ``*_device`` forms take the address of a dense u8 image already in HBM and leave their
     result there."""
 
@@ -162,6 +214,10 @@ class ContentAnalyzer:
                  text_detector: Optional[Callable[[np.ndarray], Sequence[Box]]] = None):
         self.device = device
         self.face_detector = face_detector
+        if isinstance(text_detector, str):
+            if text_detector != 'mser':
+                raise ValueError(f"ContentAnalyzer: unknown text detector {text_detector!r}: 'mser' is built")
+            text_detector = MserTextDetector(device=device)
         self.text_detector = text_detector
         self.face_cascade = None              # the reference's attribute; no cascade is ever loaded here
         self._face_note_logged = False
@@ -262,11 +318,15 @@ class ContentAnalyzer:
             d_img.free()
 
     # -- forbidden zones (tiling_module.py:323-370) --------------------------------------------------------------
-    def _zone_rects(self, host_image: Optional[np.ndarray], protect_faces: bool, protect_text: bool) -> List[Box]:
-        """Face boxes grown by int(max(w, h) * 0.2) and text boxes as given; clipping is the map kernel's."""
+    def _zone_rects(self, host_image: Optional[np.ndarray], protect_faces: bool, protect_text: bool,
+                    d_image: Optional[int] = None, shape=None) -> List[Box]:
+        """Face boxes grown by int(max(w, h) * 0.2) and text boxes as given; clipping is the map kernel's.  A GPU text
+        detector on this analyzer's device reads the image at ``d_image`` and needs no host copy."""
         if protect_text and self.text_detector is None:
             self.detect_text_regions(host_image)          # raises NotImplementedError
-        need_host = (protect_faces and self.face_detector is not None) or protect_text
+        text_on_device = (isinstance(self.text_detector, MserTextDetector) and d_image is not None
+                          and self.text_detector.device == self.device)
+        need_host = (protect_faces and self.face_detector is not None) or (protect_text and not text_on_device)
         if need_host and host_image is None:
             raise ValueError("create_forbidden_zone_map: the face / text detectors are host callables and need host_image=")
         rects: List[Box] = []
@@ -276,7 +336,8 @@ class ContentAnalyzer:
                 x1, y1 = max(0, x - margin), max(0, y - margin)
                 rects.append((x1, y1, max(0, x + w + margin - x1), max(0, y + h + margin - y1)))
         if protect_text:
-            for x, y, w, h in self.detect_text_regions(host_image):
+            boxes = self.text_detector.detect_device(d_image, shape) if text_on_device else self.detect_text_regions(host_image)
+            for x, y, w, h in boxes:
                 # numpy's [y:y+h, x:x+w]: a negative start counts from the far edge there; detectors return boxes with
                 # x, y >= 0, anything else is refused rather than wrapped
                 if x < 0 or y < 0:
@@ -288,9 +349,10 @@ class ContentAnalyzer:
                                          protect_salient: bool = True, saliency_threshold: float = 0.7,
                                          host_image: Optional[np.ndarray] = None) -> DeviceForbiddenMap:
         """create_forbidden_zone_map on a dense u8 image already in HBM: the map (and the saliency plane) stay there.
-        ``host_image``: the same image on the host, needed only when a detector callable has to run."""
+        ``host_image``: the same image on the host, needed only when a host detector callable has to run (the GPU text
+        detector reads ``d_image``)."""
         h, w, cn = self._check_shape(shape, "create_forbidden_zone_map")
-        rects = self._zone_rects(host_image, protect_faces, protect_text)
+        rects = self._zone_rects(host_image, protect_faces, protect_text, d_image, shape)
         if protect_salient:
             self._check_fft(h, w, "create_forbidden_zone_map")
         threshold = int(255 * saliency_threshold)
