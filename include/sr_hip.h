@@ -477,6 +477,125 @@ SR_API int sr_mser_tree_host_u8(const uint8_t *img, int64_t stride, int h, int w
  * x1 - x0 + 1, y1 - y0 + 1), kept iff w > 20 and h > 10 and (double)w < image_w * 0.5.  rects needs room for n. */
 SR_API int sr_mser_text_boxes(const sr_mser_region *regions, int64_t n, int image_w, sr_tile_rect *rects, int64_t *m);
 
+/* ---- Cascade: Viola-Jones cascade detection (ContentAnalyzer.detect_faces, tiling_module.py:195-212, 346-357;
+ * cv2.CascadeClassifier(path).detectMultiScale(gray, 1.1, 4); csrc/sr_cascade.hip) ----------------------------------------
+ * PARITY UNPINNED WITH cv2: cv2 is not available to this repository's tests; the OpenCV steps below are recalled from
+ * objdetect/src/cascadedetect.cpp and could not be checked.  PARITY PINNED WITH scikit-image 0.18.3 for the LBP stage
+ * evaluation: with the OpenCV-trained model scikit-image ships (lbpcascade_frontalface_opencv.xml) the windows that pass
+ * every stage on three recorded planes equal those of skimage.feature.Cascade (tests/golden/cascade_skimage.npz).
+ * The HAAR path is built and tested on constructed cascades only: the reference's haarcascade_frontalface_default.xml is
+ * not available to this repository.  The trained model is the caller's file; the engine is this library.
+ *
+ * Input: a u8 image, cn 1 / 3 / 4 (alpha ignored), row stride in bytes; g = the gray plane of the content section above
+ * (cv2.COLOR_BGR2GRAY applied to the RGB data, 15-bit rule; cn 1: the value itself), the plane MSER uses.
+ * Model: a window W0 x H0 and a feature type (SR_CASCADE_LBP / SR_CASCADE_HAAR); stages, each a float32 threshold and a
+ * list of depth-1 stumps.  An LBP stump: feature index, eight 32-bit subset words, two float32 leaves.  A HAAR stump:
+ * feature index, float32 threshold, two leaves.  An LBP feature: a rectangle (x, y, bw, bh), the top-left block of a 3 x 3
+ * grid of bw x bh blocks.  A HAAR feature: 2 or 3 upright rectangles, each with a float32 weight.
+ * LBP code: block sums b0 .. b8 in row-major order, centre c = b4; bits 7 .. 0 are b0>=c, b1>=c, b2>=c, b5>=c, b8>=c, b7>=c,
+ * b6>=c, b3>=c.  The stump adds leaf[0] when subset[code >> 5] & (1 << (code & 31)) is set, leaf[1] otherwise.  Integers only.
+ * HAAR value: val = sum weight_i * boxsum_i in float64, left to right, every product and every sum rounded (no
+ * contraction).  With A, s, q the area, sum and sum of squares of the rectangle (1, 1, W0 - 2, H0 - 2) of the window:
+ * nf = sqrt((double)(A q - s^2)) when that integer is positive, 1 otherwise.  The stump adds leaf[0] when
+ * val < (double)thr * nf, leaf[1] otherwise.
+ * Stage: the leaves are added in float32 in stump order, starting from 0 (additions only); the window fails the stage when
+ * sum < stageThreshold.  A window is a detection when it passes every stage.
+ * Scales: f_0 = 1, f_{k+1} = f_k * scale_factor in double; rnd = round half to even in double;
+ * win_k = (rnd(W0 f_k), rnd(H0 f_k)); the scaled plane has sw = rnd(w / f_k), sh = rnd(h / f_k).  The list ends when win_k
+ * exceeds max_size on either side (default: the image) or when sw < W0 or sh < H0; scales whose win_k is below min_size on
+ * either side are skipped (they still count as steps of the list).
+ * Scaled plane: an exact-integer bilinear resize with pixel centres and a replicated border (THIS PROJECT'S CHOICE).  Per
+ * axis the position of output sample x is the rational ((2 x + 1) w - sw) / (2 sw); the taps are its floor and floor + 1,
+ * both clamped to [0, w - 1]; the weights are the numerators over the common denominator; the value is
+ * (sum weight products * pixels + D / 2) // D with D = 4 sw sh, in int64.  f = 1 is the identity.
+ * Windows: on scale k every position (x, y) with x = y = 0 modulo step, x <= sw - W0, y <= sh - H0; step = 2 when
+ * f_k <= 2, 1 otherwise.  A detection gives the candidate (rnd(x f_k), rnd(y f_k), win_k.w, win_k.h).  Canonical order
+ * of candidates: scale, then y, then x.
+ * Known distances to OpenCV, no size claimed: (1) OpenCV resizes with INTER_LINEAR_EXACT, whose fixed-point weights are
+ * not restated; (2) OpenCV's working size drops the last row and column of positions; (3) OpenCV skips the position after a
+ * window that fails stage 0 (a CPU shortcut that depends on scan order).
+ * Grouping (host only; groupRectangles(cands, min_neighbors, 0.2)): min_neighbors = 0 returns the candidates as they are.
+ * Otherwise classes are the transitive closure of "similar": |dx|, |dy|, |d(x + w)|, |d(y + h)| all <=
+ * 0.2 * (min(w1, w2) + min(h1, h2)) * 0.5, evaluated in double in that order.  Classes are ordered by their first member in
+ * canonical order.  A class of n members becomes, per field x, y, w, h: the integer sum of the members' fields (held in
+ * 64 bits) converted to float32, multiplied in float32 by the float32 quotient 1.f / n, rounded half to even to int.  A
+ * class is dropped when
+ * n <= min_neighbors; a class r1 is dropped when some other class r2 with n2 > min_neighbors contains it within
+ * dx = rnd(r2.w * 0.2), dy = rnd(r2.h * 0.2) (double products) -- r1.x >= r2.x - dx, r1.y >= r2.y - dy,
+ * r1.x + r1.w <= r2.x + r2.w + dx, r1.y + r1.h <= r2.y + r2.h + dy -- and (n2 > max(3, n1) or n1 < 3).
+ * SR_ERR_UNSUPPORTED, by name, before any device call: the old opencv-haar-classifier XML layout; a stageType other than
+ * BOOST; trees deeper than one node; tilted Haar rectangles; more than 3 (or fewer than 2) rectangles per Haar feature; an
+ * LBP maxCatCount other than 256; a window side outside 3 .. 255 (3: the LBP grid and the normalisation rectangle need it;
+ * 255: coordinates pack into bytes and every box sum of squares stays below 2^32); zero stages; more than 4096 stages or
+ * 65536 stumps; a feature index out of range; a rectangle outside the window or empty; NaN thresholds, leaves or weights;
+ * scale_factor <= 1 or NaN; more than SR_CASCADE_MAX_SCALES (128) steps of the scale list; a negative min_neighbors; an
+ * image above 2^24 pixels; a pyramid whose table elements (the sum of (sw + 1)(sh + 1) over the scales; its samples and
+ * window positions are fewer) exceed 2^31 - 1: every index of the kernels is an int32.  The pyramid holds about 5.8 times
+ * the image at factor 1.1, far below that; the two caps alone do not bound it (128 scales of nearly 2^24 samples each at
+ * a factor close to 1), so the pyramid is measured and refused by name.
+ * Not built: tilted features, deep trees, the old XML layout, HOG cascades, detectMultiScale3's weights, a multi-GPU split
+ * of one call. */
+#define SR_CASCADE_LBP 0
+#define SR_CASCADE_HAAR 1
+#define SR_CASCADE_MAX_SCALES 128
+typedef struct sr_cascade sr_cascade;
+typedef struct sr_cascade_info {
+    int feature_type, win_w, win_h, n_stages, n_stumps, n_features;
+    /* what the file declared, for the refusals: 1 = the old opencv-haar-classifier layout; 0 = BOOST; the deepest tree in
+     * nodes; 1 = some Haar rectangle is tilted; the largest rectangle count of a Haar feature (0 for LBP); LBP maxCatCount */
+    int old_layout, stage_type, max_tree_nodes, tilted, max_rects, max_cat_count;
+} sr_cascade_info;
+typedef struct sr_cascade_params {
+    double scale_factor;                   /* 1.1 */
+    int min_neighbors;                     /* 4; used by the callers of sr_cascade_group */
+    int min_w, min_h, max_w, max_h;        /* 0: no minimum / the image */
+} sr_cascade_params;
+typedef struct sr_cascade_scale {
+    double f;
+    int win_w, win_h, sw, sh, step, nx, ny; /* nx x ny window positions */
+} sr_cascade_scale;
+/* Host only: checks and packs a model.  stage_thr[n_stages], stage_count[n_stages] (stumps per stage, in order);
+ * stump_feature[n_stumps], stump_leaves[2 n_stumps]; LBP: stump_subsets[8 n_stumps], feat_rects[4 n_features] (x, y, bw, bh);
+ * HAAR: stump_thr[n_stumps], feat_nrects[n_features], feat_rects[12 n_features] (three x, y, w, h slots),
+ * feat_weights[3 n_features].  Arrays of the other type may be NULL.  Every model refusal above happens here. */
+SR_API int sr_cascade_create(const sr_cascade_info *info, const float *stage_thr, const int *stage_count,
+                             const int *stump_feature, const float *stump_thr, const float *stump_leaves,
+                             const int32_t *stump_subsets, const int *feat_nrects, const int *feat_rects,
+                             const float *feat_weights, sr_cascade **out);
+SR_API int sr_cascade_destroy(sr_cascade *model);
+SR_API int sr_cascade_desc(const sr_cascade *model, sr_cascade_info *out);
+SR_API int sr_cascade_default_params(sr_cascade_params *out);
+/* Host only: every refusal of the arguments, the scale list (the first cap entries -> scales, *n_scales the total; 0 for an
+ * image smaller than the window), the bytes of context workspace of one call and the number of window positions. */
+SR_API int sr_cascade_plan(const sr_cascade *model, int h, int w, const sr_cascade_params *params, sr_cascade_scale *scales,
+                           int cap, int *n_scales, size_t *workspace_bytes, int64_t *positions);
+/* The raw candidates (x, y, w, h) of the image in HBM in canonical order -> h_cands (the first cap of them); *count is the
+ * true total.  A fixed number of launches whatever the number of scales; nothing is launched when there is no scale.  The
+ * workspace comes from the context and is never read before it is written.  Synchronous. */
+SR_API int sr_cascade_u8(sr_ctx *ctx, const sr_cascade *model, const uint8_t *d_img, int64_t stride, int h, int w, int cn,
+                         const sr_cascade_params *params, sr_tile_rect *h_cands, int64_t cap, int64_t *count);
+/* The candidates of the last sr_cascade_u8 call on this context, kept on the host: no device work.  Empty before the first
+ * call and after a call that failed. */
+SR_API int sr_cascade_last_candidates(sr_ctx *ctx, sr_tile_rect *h_cands, int64_t cap, int64_t *count);
+/* Host only: the grouping above.  rects needs room for n; *m receives the number of boxes. */
+SR_API int sr_cascade_group(const sr_tile_rect *cands, int64_t n, int min_neighbors, sr_tile_rect *rects, int64_t *m);
+/* For inspection and tests: the scaled plane of scale k of the plan (sw * sh bytes, dense) -> h_plane. */
+SR_API int sr_cascade_plane_u8(sr_ctx *ctx, const sr_cascade *model, const uint8_t *d_img, int64_t stride, int h, int w, int cn,
+                               const sr_cascade_params *params, int k, uint8_t *h_plane);
+/* For inspection and tests: on the scale-0 plane (the gray plane itself) and the given step (1 or 2), per position in
+ * row-major order the number of stages passed -> h_map; *count = nx * ny (nothing else is written when it exceeds cap). */
+SR_API int sr_cascade_stage_map_u8(sr_ctx *ctx, const sr_cascade *model, const uint8_t *d_img, int64_t stride, int h, int w,
+                                   int cn, int step, int32_t *h_map, int64_t cap, int64_t *count);
+/* For tests: the context's cascade workspace (NULL and 0 before the first call). */
+SR_API int sr_cascade_workspace(sr_ctx *ctx, void **d_ptr, size_t *bytes);
+/* The host twins: the same definition on host pointers, the restatement the device is held to. */
+SR_API int sr_cascade_host_u8(const sr_cascade *model, const uint8_t *img, int64_t stride, int h, int w, int cn,
+                              const sr_cascade_params *params, sr_tile_rect *cands, int64_t cap, int64_t *count);
+SR_API int sr_cascade_plane_host_u8(const sr_cascade *model, const uint8_t *img, int64_t stride, int h, int w, int cn,
+                                    const sr_cascade_params *params, int k, uint8_t *plane);
+SR_API int sr_cascade_stage_map_host_u8(const sr_cascade *model, const uint8_t *img, int64_t stride, int h, int w, int cn,
+                                        int step, int32_t *map, int64_t cap, int64_t *count);
+
 /* ---- BlendingModule.poisson_fusion / repair_seams (blending_module.py:563-659, 1148-1240; csrc/sr_poisson.hip) ---------------
  * PARITY UNPINNED: cv2 is not available to this repository's tests, so the OpenCV behaviour below is restated from memory
  * (Cloning::normalClone of photo/src/seamless_cloning_impl.cpp, GaussianBlur's 8-bit fixed-point path) and tested against this

@@ -18,10 +18,10 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libsrhip.so")
 OBJ_DIR = os.path.join(_HERE, "build")
 SOURCES = [os.path.join(CSRC, n) for n in ("sr_engine.hip", "sr_runtime.hip", "sr_tiles.hip", "sr_assess.hip", "sr_lpips.hip", "sr_adjust.hip", "sr_gradient.hip", "sr_commercial.hip",
-                                           "sr_content.hip", "sr_poisson.hip", "sr_qmap.hip", "sr_msssim.hip", "sr_srbench.hip", "sr_srnet.hip", "sr_resnet.hip", "sr_rrdb.hip", "sr_rcan.hip", "sr_swinir.hip", "sr_hat.hip", "sr_swin2sr.hip", "sr_ensemble.hip", "sr_niqe.hip", "sr_dists.hip", "sr_brisque.hip", "sr_imresize.hip", "sr_vif.hip", "sr_gmsd.hip", "sr_fsim.hip", "sr_vsi.hip", "sr_deltae.hip", "sr_haarpsi.hip", "sr_mser.hip",
-                                           "sr_encode.cpp", "sr_comm.cpp", "sr_blend_plan.cpp", "sr_niqe_host.cpp", "sr_dists_host.cpp", "sr_brisque_host.cpp", "sr_swinir_host.cpp", "sr_hat_host.cpp", "sr_swin2sr_host.cpp", "sr_imresize_host.cpp", "sr_vif_host.cpp", "sr_fsim_host.cpp", "sr_vsi_host.cpp", "sr_deltae_host.cpp", "sr_haarpsi_host.cpp", "sr_mser_host.cpp", "sr_host.cpp")]
+                                           "sr_content.hip", "sr_poisson.hip", "sr_qmap.hip", "sr_msssim.hip", "sr_srbench.hip", "sr_srnet.hip", "sr_resnet.hip", "sr_rrdb.hip", "sr_rcan.hip", "sr_swinir.hip", "sr_hat.hip", "sr_swin2sr.hip", "sr_ensemble.hip", "sr_niqe.hip", "sr_dists.hip", "sr_brisque.hip", "sr_imresize.hip", "sr_vif.hip", "sr_gmsd.hip", "sr_fsim.hip", "sr_vsi.hip", "sr_deltae.hip", "sr_haarpsi.hip", "sr_mser.hip", "sr_cascade.hip",
+                                           "sr_encode.cpp", "sr_comm.cpp", "sr_blend_plan.cpp", "sr_niqe_host.cpp", "sr_dists_host.cpp", "sr_brisque_host.cpp", "sr_swinir_host.cpp", "sr_hat_host.cpp", "sr_swin2sr_host.cpp", "sr_imresize_host.cpp", "sr_vif_host.cpp", "sr_fsim_host.cpp", "sr_vsi_host.cpp", "sr_deltae_host.cpp", "sr_haarpsi_host.cpp", "sr_mser_host.cpp", "sr_cascade_host.cpp", "sr_host.cpp")]
 HEADERS = [os.path.join(CSRC, "sr_internal.h"), os.path.join(CSRC, "sr_blend_tables.h"), os.path.join(CSRC, "sr_ctx.h"), os.path.join(CSRC, "sr_device.h"), os.path.join(CSRC, "sr_march.inc"), os.path.join(CSRC, "sr_down2.inc"),
-           os.path.join(CSRC, "sr_linear.h"), os.path.join(CSRC, "sr_fft.h"), os.path.join(CSRC, "sr_conv_mfma.h"), os.path.join(CSRC, "sr_net_common.h"), os.path.join(CSRC, "sr_ssim11.h"), os.path.join(CSRC, "sr_mscn.h"), os.path.join(CSRC, "sr_vgg_stream.h"), os.path.join(CSRC, "sr_vgg_ranges.h"), os.path.join(CSRC, "sr_swinir.h"), os.path.join(CSRC, "sr_swin_common.h"), os.path.join(CSRC, "sr_chan_attn.h"), os.path.join(CSRC, "sr_hat.h"), os.path.join(CSRC, "sr_swin2sr.h"), os.path.join(CSRC, "sr_imresize.h"), os.path.join(CSRC, "sr_vif.h"), os.path.join(CSRC, "sr_fsim.h"), os.path.join(CSRC, "sr_vsi.h"), os.path.join(CSRC, "sr_deltae.h"), os.path.join(CSRC, "sr_haarpsi.h"), os.path.join(CSRC, "sr_mser.h"),
+           os.path.join(CSRC, "sr_linear.h"), os.path.join(CSRC, "sr_fft.h"), os.path.join(CSRC, "sr_conv_mfma.h"), os.path.join(CSRC, "sr_net_common.h"), os.path.join(CSRC, "sr_ssim11.h"), os.path.join(CSRC, "sr_mscn.h"), os.path.join(CSRC, "sr_vgg_stream.h"), os.path.join(CSRC, "sr_vgg_ranges.h"), os.path.join(CSRC, "sr_swinir.h"), os.path.join(CSRC, "sr_swin_common.h"), os.path.join(CSRC, "sr_chan_attn.h"), os.path.join(CSRC, "sr_hat.h"), os.path.join(CSRC, "sr_swin2sr.h"), os.path.join(CSRC, "sr_imresize.h"), os.path.join(CSRC, "sr_vif.h"), os.path.join(CSRC, "sr_fsim.h"), os.path.join(CSRC, "sr_vsi.h"), os.path.join(CSRC, "sr_deltae.h"), os.path.join(CSRC, "sr_haarpsi.h"), os.path.join(CSRC, "sr_mser.h"), os.path.join(CSRC, "sr_cascade.h"),
            os.path.join(_ROOT, "include", "sr_hip.h")]
 
 

@@ -136,6 +136,27 @@ MSER_NODE_DTYPE = np.dtype([(f, np.int32) for f in MSER_NODE_FIELDS])
 MSER_DARK, MSER_BRIGHT, MSER_BOTH = 1, 2, 3               # polarity_mask bits
 
 
+class CascadeInfo(C.Structure):
+    """sr_cascade_info (include/sr_hip.h)."""
+    _fields_ = [(k, C.c_int) for k in ("feature_type", "win_w", "win_h", "n_stages", "n_stumps", "n_features", "old_layout",
+                                      "stage_type", "max_tree_nodes", "tilted", "max_rects", "max_cat_count")]
+
+
+class CascadeParams(C.Structure):
+    """sr_cascade_params (include/sr_hip.h)."""
+    _fields_ = [("scale_factor", C.c_double), ("min_neighbors", C.c_int), ("min_w", C.c_int), ("min_h", C.c_int),
+                ("max_w", C.c_int), ("max_h", C.c_int)]
+
+
+class CascadeScale(C.Structure):
+    """sr_cascade_scale (include/sr_hip.h)."""
+    _fields_ = [("f", C.c_double)] + [(k, C.c_int) for k in ("win_w", "win_h", "sw", "sh", "step", "nx", "ny")]
+
+
+SR_CASCADE_MAX_SCALES = 128
+CASCADE_RECT_DTYPE = np.dtype([(f, np.int32) for f in ("x", "y", "w", "h")])      # sr_tile_rect
+
+
 # enum sr_haarpsi_convention (include/sr_hip.h)
 HAARPSI_MATLAB, HAARPSI_PYTHON = 0, 1
 HAARPSI_CONVENTIONS = {"matlab": HAARPSI_MATLAB, "python": HAARPSI_PYTHON}
@@ -372,6 +393,21 @@ SIGNATURES = {
     "sr_mser_host_u8": (_i, [_vp, _i64, _i, _i, _i, C.POINTER(MserParams), _i, _vp, _i64, C.POINTER(_i64)]),
     "sr_mser_tree_host_u8": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, C.POINTER(_i64)]),
     "sr_mser_text_boxes": (_i, [_vp, _i64, _i, C.POINTER(TileRect), C.POINTER(_i64)]),
+    "sr_cascade_create": (_i, [C.POINTER(CascadeInfo)] + [_vp] * 9 + [C.POINTER(_vp)]),
+    "sr_cascade_destroy": (_i, [_vp]),
+    "sr_cascade_desc": (_i, [_vp, C.POINTER(CascadeInfo)]),
+    "sr_cascade_default_params": (_i, [C.POINTER(CascadeParams)]),
+    "sr_cascade_plan": (_i, [_vp, _i, _i, C.POINTER(CascadeParams), C.POINTER(CascadeScale), _i, C.POINTER(_i), C.POINTER(_sz),
+                             C.POINTER(_i64)]),
+    "sr_cascade_u8": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, C.POINTER(CascadeParams), _vp, _i64, C.POINTER(_i64)]),
+    "sr_cascade_last_candidates": (_i, [_vp, _vp, _i64, C.POINTER(_i64)]),
+    "sr_cascade_group": (_i, [_vp, _i64, _i, _vp, C.POINTER(_i64)]),
+    "sr_cascade_plane_u8": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, C.POINTER(CascadeParams), _i, _vp]),
+    "sr_cascade_stage_map_u8": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _i64, C.POINTER(_i64)]),
+    "sr_cascade_workspace": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    "sr_cascade_host_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(CascadeParams), _vp, _i64, C.POINTER(_i64)]),
+    "sr_cascade_plane_host_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(CascadeParams), _i, _vp]),
+    "sr_cascade_stage_map_host_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i64, C.POINTER(_i64)]),
     "sr_haarpsi_plan": (_i, [_i, _i, _i, _i, _i, _i, _pi, _pi, C.POINTER(C.c_uint64), _pi, C.POINTER(_sz)]),
     "sr_haarpsi_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(HaarPsiSums)]),
     "sr_haarpsi_cells_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _pi, _i, _pi, _i, C.POINTER(HaarPsiCell)]),
@@ -1203,6 +1239,148 @@ def mser_text_boxes(regions: np.ndarray, image_w: int) -> List[Tuple[int, int, i
     m = _i64(0)
     check(load().sr_mser_text_boxes(C.c_void_p(regions.ctypes.data), n, int(image_w), rects, C.byref(m)))
     return [(rects[i].x, rects[i].y, rects[i].w, rects[i].h) for i in range(m.value)]
+
+
+def cascade_params(scale_factor=None, min_neighbors=None, min_size=None, max_size=None) -> "CascadeParams":
+    """sr_cascade_default_params (1.1, 4, no minimum, the image) with the given fields replaced; sizes are (w, h) as in
+    cv2.  ValueError for a count that is not a whole number; the ranges are the library's to refuse."""
+    p = CascadeParams()
+    check(load().sr_cascade_default_params(C.byref(p)))
+    if scale_factor is not None:
+        p.scale_factor = float(scale_factor)
+    ints = [("min_neighbors", min_neighbors)]
+    for name, size in (("min", min_size), ("max", max_size)):
+        if size is not None:
+            if len(size) != 2:
+                raise ValueError(f"cascade: {name}_size must be (w, h), got {size!r}")
+            ints += [(f"{name}_w", size[0]), (f"{name}_h", size[1])]
+    for name, v in ints:
+        if v is not None:
+            if isinstance(v, bool) or int(v) != v or not (-2 ** 31 <= int(v) < 2 ** 31):
+                raise ValueError(f"cascade: {name} must be a whole number, got {v!r}")
+            setattr(p, name, int(v))
+    return p
+
+
+def _cascade_rects(buf: np.ndarray) -> np.ndarray:
+    return buf.view(np.int32).reshape(-1, 4)
+
+
+def cascade_group(cands, min_neighbors: int = 4) -> np.ndarray:
+    """Host only (sr_cascade_group): OpenCV's groupRectangles(cands, min_neighbors, 0.2) as the definition states it ->
+    int32 [m, 4] boxes (x, y, w, h).  NotImplementedError for a negative min_neighbors."""
+    c = np.ascontiguousarray(np.asarray(cands, dtype=np.int32).reshape(-1, 4))
+    out = np.zeros((max(len(c), 1), 4), np.int32)
+    m = _i64(0)
+    _check_unsupported(load().sr_cascade_group(C.c_void_p(c.ctypes.data), len(c), int(min_neighbors), C.c_void_p(out.ctypes.data),
+                                               C.byref(m)))
+    return out[:m.value].copy()
+
+
+CASCADE_FIRST_CAP = 65536         # candidates of a first buffer (1 MB); a face image stays far below it
+
+
+class CascadeModel:
+    """sr_cascade: a checked and packed cascade (host only; the tables go to the GPU with every call).  ``tables`` is what
+    tiling_module.load_cascade returns.  Every model refusal of the definition (include/sr_hip.h, "Cascade") is raised here
+    as NotImplementedError."""
+
+    def __init__(self, tables: dict):
+        t = tables
+        haar = t["feature_type"] == "HAAR"
+        if t["feature_type"] not in ("LBP", "HAAR"):
+            raise NotImplementedError(f"cascade: feature type {t['feature_type']!r} is neither LBP nor HAAR (HOG cascades are not built)")
+        f32 = lambda k: np.ascontiguousarray(t[k], dtype=np.float32) if t.get(k) is not None else None   # noqa: E731
+        i32 = lambda k: np.ascontiguousarray(t[k], dtype=np.int32) if t.get(k) is not None else None     # noqa: E731
+        arrs = [f32("stage_thresholds"), i32("stage_counts"), i32("stump_feature"), f32("stump_threshold"), f32("stump_leaves"),
+                i32("stump_subsets"), i32("feature_nrects"), i32("feature_rects"), f32("feature_weights")]
+        n_stages, n_stumps = len(arrs[0]), len(arrs[2])
+        n_feat = 0 if arrs[7] is None else arrs[7].size // (12 if haar else 4)
+        want = [n_stages, n_stages, n_stumps, n_stumps if haar else None, 2 * n_stumps, None if haar else 8 * n_stumps,
+                n_feat if haar else None, (12 if haar else 4) * n_feat, 3 * n_feat if haar else None]
+        for a, n, name in zip(arrs, want, ("stage_thresholds", "stage_counts", "stump_feature", "stump_threshold", "stump_leaves",
+                                          "stump_subsets", "feature_nrects", "feature_rects", "feature_weights")):
+            if n is not None and (0 if a is None else a.size) != n:
+                raise ValueError(f"cascade: table {name} has {0 if a is None else a.size} entries, expected {n}")
+        info = CascadeInfo(1 if haar else 0, int(t["window"][0]), int(t["window"][1]), n_stages, n_stumps, n_feat,
+                           int(t.get("old_layout", 0)), int(t.get("stage_type", 0)), int(t.get("max_tree_nodes", 1)),
+                           int(t.get("tilted", 0)), int(t.get("max_rects", 0)), int(t.get("max_cat_count", 256)))
+        self._keep = arrs
+        h = C.c_void_p()
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None                   # noqa: E731
+        _check_unsupported(load().sr_cascade_create(C.byref(info), *[ptr(a) for a in arrs], C.byref(h)))
+        self.handle = h
+        self.feature_type, self.window = t["feature_type"], (info.win_w, info.win_h)
+        self.n_stages, self.n_stumps, self.n_features = n_stages, n_stumps, n_feat
+
+    def info(self) -> dict:
+        d = CascadeInfo()
+        check(load().sr_cascade_desc(self.handle, C.byref(d)))
+        return {k: getattr(d, k) for k, _ in CascadeInfo._fields_}
+
+    def plan(self, h: int, w: int, params: Optional["CascadeParams"] = None) -> dict:
+        """Host only (sr_cascade_plan) -> {'scales': [dict per scale], 'workspace_bytes', 'positions'}.  NotImplementedError
+        for every refusal of the arguments."""
+        params = params if params is not None else cascade_params()
+        sc = (CascadeScale * SR_CASCADE_MAX_SCALES)()
+        n, ws, pos = _i(0), _sz(0), _i64(0)
+        _check_unsupported(load().sr_cascade_plan(self.handle, int(h), int(w), C.byref(params), sc, SR_CASCADE_MAX_SCALES, C.byref(n),
+                                                  C.byref(ws), C.byref(pos)))
+        return {"scales": [{k: getattr(sc[i], k) for k, _ in CascadeScale._fields_} for i in range(n.value)],
+                "workspace_bytes": int(ws.value), "positions": int(pos.value)}
+
+    def host(self, img: np.ndarray, params: Optional["CascadeParams"] = None) -> np.ndarray:
+        """Host only (sr_cascade_host_u8): the raw candidates int32 [n, 4] (x, y, w, h) in canonical order."""
+        img, cn = _mser_host_image(img, "cascade_host")
+        params = params if params is not None else cascade_params()
+        lib = load()
+        return _cascade_rects(_mser_fetch(lambda buf, cap, n: lib.sr_cascade_host_u8(
+            self.handle, C.c_void_p(img.ctypes.data), int(img.strides[0]), int(img.shape[0]), int(img.shape[1]), cn, C.byref(params),
+            buf, cap, n), CASCADE_RECT_DTYPE, CASCADE_FIRST_CAP))
+
+    def plane_host(self, img: np.ndarray, k: int, params: Optional["CascadeParams"] = None) -> np.ndarray:
+        """Host only (sr_cascade_plane_host_u8): the scaled plane of scale k of the plan."""
+        img, cn = _mser_host_image(img, "cascade_plane_host")
+        params = params if params is not None else cascade_params()
+        scales = self.plan(img.shape[0], img.shape[1], params)["scales"]
+        if not 0 <= int(k) < len(scales):
+            raise ValueError(f"cascade_plane_host: scale {k} of {len(scales)}")
+        out = np.zeros((scales[k]["sh"], scales[k]["sw"]), np.uint8)
+        _check_unsupported(load().sr_cascade_plane_host_u8(self.handle, C.c_void_p(img.ctypes.data), int(img.strides[0]),
+                                                           int(img.shape[0]), int(img.shape[1]), cn, C.byref(params), int(k),
+                                                           C.c_void_p(out.ctypes.data)))
+        return out
+
+    def map_shape(self, h: int, w: int, step: int) -> Tuple[int, int]:
+        if step not in (1, 2):
+            raise ValueError(f"cascade: step must be 1 or 2, got {step!r}")
+        if w < self.window[0] or h < self.window[1]:
+            return 0, 0
+        return (h - self.window[1]) // step + 1, (w - self.window[0]) // step + 1
+
+    def stage_map_host(self, img: np.ndarray, step: int = 1) -> np.ndarray:
+        """Host only (sr_cascade_stage_map_host_u8): int32 [ny, nx], the number of stages each window of the gray plane
+        itself passes."""
+        img, cn = _mser_host_image(img, "cascade_stage_map_host")
+        ny, nx = self.map_shape(img.shape[0], img.shape[1], step)
+        out = np.zeros(max(ny * nx, 1), np.int32)
+        n = _i64(0)
+        _check_unsupported(load().sr_cascade_stage_map_host_u8(self.handle, C.c_void_p(img.ctypes.data), int(img.strides[0]),
+                                                               int(img.shape[0]), int(img.shape[1]), cn, int(step),
+                                                               C.c_void_p(out.ctypes.data), ny * nx, C.byref(n)))
+        assert n.value == ny * nx
+        return out[:ny * nx].reshape(ny, nx)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            load().sr_cascade_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
 
 
 def imresize_size(n: int, scale: float) -> int:
@@ -2067,6 +2245,56 @@ class Context:
         return _mser_fetch(lambda buf, cap, n: self.lib.sr_mser_tree_u8(self.handle, C.c_void_p(d_img), int(stride), int(h), int(w),
                                                                         int(cn), int(polarity), buf, cap, n),
                            MSER_NODE_DTYPE, min(plan["node_cap"], 1 << 20))
+
+    # Cascade detection (sr_cascade.hip) ---------------------------------------------------------
+    def cascade(self, model: "CascadeModel", d_img: int, stride: int, h: int, w: int, cn: int,
+                params: Optional["CascadeParams"] = None) -> np.ndarray:
+        """sr_cascade_u8: the raw candidates of the u8 image in HBM, int32 [n, 4] (x, y, w, h) in canonical order (scale, y,
+        x).  Every refusal is raised before the device is touched (CascadeModel.plan).  The detection runs ONCE whatever the
+        count: candidates beyond the first CASCADE_FIRST_CAP come from the copy the context keeps
+        (sr_cascade_last_candidates).  Synchronous."""
+        params = params if params is not None else cascade_params()
+        if not d_img:
+            raise ValueError("cascade: null image pointer")
+        model.plan(h, w, params)
+        return _cascade_rects(_mser_fetch(
+            lambda buf, cap, n: self.lib.sr_cascade_u8(self.handle, model.handle, C.c_void_p(d_img), int(stride), int(h), int(w),
+                                                       int(cn), C.byref(params), buf, cap, n),
+            CASCADE_RECT_DTYPE, CASCADE_FIRST_CAP,
+            again=lambda buf, cap, n: self.lib.sr_cascade_last_candidates(self.handle, buf, cap, n)))
+
+    def cascade_plane(self, model: "CascadeModel", d_img: int, stride: int, h: int, w: int, cn: int, k: int,
+                      params: Optional["CascadeParams"] = None) -> np.ndarray:
+        """sr_cascade_plane_u8: the scaled plane of scale k of the plan as the kernels made it (inspection)."""
+        params = params if params is not None else cascade_params()
+        scales = model.plan(h, w, params)["scales"]
+        if not d_img or not 0 <= int(k) < len(scales):
+            raise ValueError(f"cascade_plane: null image pointer or scale {k} of {len(scales)}")
+        out = np.zeros((scales[k]["sh"], scales[k]["sw"]), np.uint8)
+        _check_unsupported(self.lib.sr_cascade_plane_u8(self.handle, model.handle, C.c_void_p(d_img), int(stride), int(h), int(w),
+                                                        int(cn), C.byref(params), int(k), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def cascade_stage_map(self, model: "CascadeModel", d_img: int, stride: int, h: int, w: int, cn: int,
+                          step: int = 1) -> np.ndarray:
+        """sr_cascade_stage_map_u8: int32 [ny, nx], the number of stages each window of the gray plane itself passes
+        (inspection; every stage on every window, no compaction)."""
+        ny, nx = model.map_shape(h, w, step)
+        if not d_img:
+            raise ValueError("cascade_stage_map: null image pointer")
+        out = np.zeros(max(ny * nx, 1), np.int32)
+        n = _i64(0)
+        _check_unsupported(self.lib.sr_cascade_stage_map_u8(self.handle, model.handle, C.c_void_p(d_img), int(stride), int(h),
+                                                            int(w), int(cn), int(step), C.c_void_p(out.ctypes.data), ny * nx,
+                                                            C.byref(n)))
+        assert n.value == ny * nx
+        return out[:ny * nx].reshape(ny, nx)
+
+    def cascade_workspace(self) -> Tuple[int, int]:
+        """sr_cascade_workspace -> (device address, bytes) of the context's cascade workspace; (0, 0) before the first call."""
+        p, n = C.c_void_p(), _sz(0)
+        check(self.lib.sr_cascade_workspace(self.handle, C.byref(p), C.byref(n)))
+        return int(p.value or 0), int(n.value)
 
     # Poisson fusion and seam repair (sr_poisson.hip) ------------------------------------------
     def poisson_clone_u8(self, d_dest: int, dest_stride: int, d_patch: int, patch_stride: int, d_mask: int, mask_stride: int,

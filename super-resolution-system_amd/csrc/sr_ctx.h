@@ -116,11 +116,13 @@ struct sr_ctx {
     DevBuf haarpsi_ws;                                  // HaarPSI: per-block partials; the per-cell form adds the sample map, edges, records
     DevBuf mser_ws;                                     // MSER: gray plane, sorted pixels, union-find, node table (sr_mser.h)
     std::vector<sr_mser_region> mser_last;              // the sorted records of the last sr_mser_u8 (sr_mser_last_regions)
+    DevBuf cascade_ws;                                  // cascade: gray plane, scaled planes, summed-area tables, model, lists (sr_cascade.h)
+    std::vector<sr_tile_rect> cascade_last;             // the candidates of the last sr_cascade_u8 (sr_cascade_last_candidates)
     CachedTable imresize_tab;                           // imresize: both axes' weights, indices and starts of the last geometry
     // Frees every device buffer above; sr_ctx_destroy calls it with the stream drained and the device current.
     void release_device()
     {
-        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws, &brisque_ws, &vif_ws, &gmsd_ws, &fsim_ws, &vsi_ws, &deltae_ws, &haarpsi_ws, &mser_ws, &imresize_tab.buf})
+        for (DevBuf *b : {&scratch, &extract_tab.buf, &resize_tab.buf, &cubic_tab.buf, &gray_planes, &cm_ws, &msssim_ws, &bench_ws, &niqe_ws, &brisque_ws, &vif_ws, &gmsd_ws, &fsim_ws, &vsi_ws, &deltae_ws, &haarpsi_ws, &mser_ws, &cascade_ws, &imresize_tab.buf})
             b->release();
     }
 };

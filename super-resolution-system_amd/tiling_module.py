@@ -21,8 +21,17 @@ to this repository's tests; the detector is Matas' MSER in component-tree form w
 boxes from the image already in HBM and need no ``host_image``.  Not built: colour MSER (MSCR), 8-connectivity, the
 regions' pixel lists.
 
-Not on this path: the Haar face cascade (an OpenCV model that cannot be restated) -- ``ContentAnalyzer`` takes an optional
-host callable; without one ``detect_faces`` returns ``[]`` (what the reference does when the cascade file is missing).
+Cascade face detection (tiling_module.py:195-212, 346-357): ``CascadeFaceDetector`` runs
+``cv2.CascadeClassifier(path).detectMultiScale(gray, 1.1, 4)`` on the GPU (csrc/sr_cascade.hip; the definition is in
+include/sr_hip.h, "Cascade"): window evaluation over an image pyramid, then groupRectangles on the host.  Only the trained
+model cannot be restated, so the caller supplies the file (``load_cascade`` reads OpenCV's ``opencv-cascade-classifier`` XML
+without cv2) and the engine is built here.  PARITY UNPINNED with cv2; the LBP stage evaluation is pinned to scikit-image
+0.18.3 on the OpenCV-trained LBP model it ships; the HAAR path is built and tested on constructed cascades only, because
+``haarcascade_frontalface_default.xml`` is not available to this repository.  Opt-in:
+``ContentAnalyzer(face_cascade='path.xml')`` or ``face_detector=CascadeFaceDetector(...)`` (or any host callable); with the
+default ``face_detector=None`` ``detect_faces`` returns ``[]`` (what the reference does when the cascade file is missing).
+Not built: tilted features, deep trees, the old XML layout, HOG cascades, ``detectMultiScale3`` weights, a multi-GPU split
+of one call; main.py has no content-analyzer hook, so there is no switch there.
 The ``cv2.saliency`` fine-grained branch is not rebuilt.  The L1/L2 tile caches and the JSON
 checkpoint are host-side persistence outside the tile -> blend -> assess path and are NOT rebuilt; only
 the constructor's cache-directory side effect and the ``restore_from_cache`` probe of main.py:299-304 exist.
@@ -200,26 +209,136 @@ class MserTextDetector:
         return self._on_device(image, self.detect_device)
 
 
+def load_cascade(path: str) -> dict:
+    """An OpenCV cascade file in the ``opencv-cascade-classifier`` XML layout -> plain arrays (host only, ``xml.etree``; no
+    cv2): what ``_native.CascadeModel`` takes.  LBP subset words are masked to 32 bits (the file writes them signed).  The
+    file's declarations the engine refuses (old layout, stageType, tree depth, tilted rectangles, rectangle counts,
+    maxCatCount) are recorded, not judged: ``CascadeModel`` raises NotImplementedError by name."""
+    import xml.etree.ElementTree as ET
+    root = ET.parse(path).getroot()
+    casc = next((e for e in root if e.get("type_id") == "opencv-cascade-classifier"), None)
+    if casc is None:
+        if any(e.get("type_id") == "opencv-haar-classifier" for e in root):
+            # nothing of the old layout is read: the engine refuses it by name
+            return {"feature_type": "HAAR", "window": (0, 0), "old_layout": 1, "stage_thresholds": [], "stage_counts": [],
+                    "stump_feature": [], "stump_threshold": [], "stump_leaves": [], "feature_nrects": [], "feature_rects": [],
+                    "feature_weights": []}
+        raise ValueError(f"load_cascade: {path} holds no opencv-cascade-classifier")
+    text = lambda e, tag: e.findtext(tag).strip()                                                       # noqa: E731
+    ftype = text(casc, "featureType")
+    t = {"feature_type": ftype, "window": (int(text(casc, "width")), int(text(casc, "height"))), "old_layout": 0,
+         "stage_type": 0 if text(casc, "stageType") == "BOOST" else 1,
+         "max_cat_count": int(next(casc.iter("maxCatCount")).text) if any(True for _ in casc.iter("maxCatCount")) else 0}
+    haar = ftype == "HAAR"
+    thr, counts, feat, sthr, leaves, subsets, nodes_max = [], [], [], [], [], [], 1
+    for stage in casc.find("stages"):
+        weak = list(stage.find("weakClassifiers"))
+        thr.append(float(text(stage, "stageThreshold")))
+        counts.append(len(weak))
+        for tree in weak:
+            node = text(tree, "internalNodes").split()
+            per = 4 if haar else 11
+            nodes_max = max(nodes_max, len(node) // per)
+            feat.append(int(node[2]))
+            if haar:
+                sthr.append(float(node[3]))
+            else:
+                subsets.append([int(v) & 0xFFFFFFFF for v in node[3:11]])
+            leaves.append([float(v) for v in text(tree, "leafValues").split()][:2])
+    t.update(stage_thresholds=np.array(thr, np.float32), stage_counts=np.array(counts, np.int32),
+             stump_feature=np.array(feat, np.int32), stump_leaves=np.array(leaves, np.float32).reshape(-1, 2),
+             max_tree_nodes=nodes_max)
+    feats = list(casc.find("features"))
+    if haar:
+        rects, weights, nrects, tilted = np.zeros((len(feats), 3, 4), np.int32), np.zeros((len(feats), 3), np.float32), [], 0
+        for i, f in enumerate(feats):
+            rs = [r.text.split() for r in f.find("rects")]
+            nrects.append(len(rs))
+            tilted |= int((f.findtext("tilted") or "0").strip() != "0")
+            for j, r in enumerate(rs[:3]):
+                rects[i, j] = [int(v) for v in r[:4]]
+                weights[i, j] = float(r[4])
+        t.update(stump_threshold=np.array(sthr, np.float32), feature_rects=rects, feature_weights=weights,
+                 feature_nrects=np.array(nrects, np.int32), tilted=tilted, max_rects=max(nrects, default=0))
+    else:
+        t.update(stump_subsets=np.array(subsets, np.uint32).view(np.int32).reshape(-1, 8),
+                 feature_rects=np.array([[int(v) for v in text(f, "rect").split()] for f in feats], np.int32).reshape(-1, 4))
+    return t
+
+
+class CascadeFaceDetector:
+    """Viola-Jones cascade detection on the GPU (csrc/sr_cascade.hip; definition in include/sr_hip.h, "Cascade"):
+    ``cv2.CascadeClassifier(path).detectMultiScale(gray, scale_factor, min_neighbors)``, a valid ``face_detector=`` of
+    ContentAnalyzer.  PARITY UNPINNED with cv2; the LBP stage evaluation is pinned to scikit-image 0.18.3; the HAAR path is
+    tested on constructed cascades only.  ``cascade``: a path (``load_cascade``), the tables it returns, or a
+    ``_native.CascadeModel``; the trained model is the caller's file.  Every refusal of the definition
+    (NotImplementedError) is raised by the constructor.  Sizes are ``(w, h)``; images uint8 HxW or HxWx{1,3,4}."""
+
+    def __init__(self, cascade, scale_factor: float = 1.1, min_neighbors: int = 4, min_size=None, max_size=None, device: int = 0):
+        if isinstance(cascade, (str, os.PathLike)):
+            cascade = load_cascade(os.fspath(cascade))
+        self.model = cascade if isinstance(cascade, _native.CascadeModel) else _native.CascadeModel(cascade)
+        self.params = _native.cascade_params(scale_factor, min_neighbors, min_size, max_size)
+        self.model.plan(1, 1, self.params)
+        self.device = device
+
+    def _ctx(self) -> "_native.Context":
+        return _native.default_context(self.device)
+
+    def candidates_device(self, d_image: int, shape, stride: Optional[int] = None) -> np.ndarray:
+        """The raw candidates, int32 [n, 4] (x, y, w, h) in canonical order (scale, y, x), of a u8 image already in HBM."""
+        h, w, cn = ContentAnalyzer._check_shape(shape, "CascadeFaceDetector")
+        self.model.plan(h, w, self.params)
+        return self._ctx().cascade(self.model, d_image, w * cn if stride is None else int(stride), h, w, cn, self.params)
+
+    def detect_device(self, d_image: int, shape, stride: Optional[int] = None) -> List[Box]:
+        """The grouped boxes ``(x, y, w, h)``: groupRectangles(candidates, min_neighbors, 0.2)."""
+        boxes = _native.cascade_group(self.candidates_device(d_image, shape, stride), self.params.min_neighbors)
+        return [tuple(int(v) for v in b) for b in boxes]
+
+    def _on_device(self, image, fn):
+        img = ContentAnalyzer._check_image(image, "CascadeFaceDetector")
+        self.model.plan(img.shape[0], img.shape[1], self.params)
+        ctx = self._ctx()
+        d_img = ctx.upload(img)
+        try:
+            return fn(d_img.ptr, img.shape)
+        finally:
+            d_img.free()
+
+    def candidates(self, image: np.ndarray) -> np.ndarray:
+        return self._on_device(image, self.candidates_device)
+
+    def __call__(self, image: np.ndarray) -> List[Box]:
+        return self._on_device(image, self.detect_device)
+
+
 class ContentAnalyzer:
     """Key-region analysis for content-aware tiling (tiling_module.py:174-370) on the GPU.
 
     ``face_detector`` / ``text_detector``: optional host callables ``image -> [(x, y, w, h)]`` standing in for the
-    reference's Haar cascade and MSER; ``text_detector='mser'`` is shorthand for ``MserTextDetector(device=device)``, the
-    GPU detector, whose boxes the ``*_device`` forms take from the image in HBM.  Images are uint8 HxW or HxWx{1,3,4}
+    reference's Haar cascade and MSER; ``text_detector='mser'`` is shorthand for ``MserTextDetector(device=device)`` and
+    ``face_cascade='path.xml'`` for ``face_detector=CascadeFaceDetector('path.xml', device=device)``, the GPU detectors,
+    whose boxes the ``*_device`` forms take from the image in HBM.  Images are uint8 HxW or HxWx{1,3,4}
     (alpha ignored); every check
     runs before device work.  The ``*_device`` forms take the address of a dense u8 image already in HBM and leave their
     result there."""
 
     def __init__(self, device: int = 0, face_detector: Optional[Callable[[np.ndarray], Sequence[Box]]] = None,
-                 text_detector: Optional[Callable[[np.ndarray], Sequence[Box]]] = None):
+                 text_detector: Optional[Callable[[np.ndarray], Sequence[Box]]] = None, face_cascade=None):
         self.device = device
+        if face_cascade is not None:
+            if face_detector is not None:
+                raise ValueError("ContentAnalyzer: give face_detector= or face_cascade=, not both")
+            face_detector = CascadeFaceDetector(face_cascade, device=device)
         self.face_detector = face_detector
         if isinstance(text_detector, str):
             if text_detector != 'mser':
                 raise ValueError(f"ContentAnalyzer: unknown text detector {text_detector!r}: 'mser' is built")
             text_detector = MserTextDetector(device=device)
         self.text_detector = text_detector
-        self.face_cascade = None              # the reference's attribute; no cascade is ever loaded here
+        # the reference's attribute: the loaded model of a GPU cascade detector, None otherwise
+        self.face_cascade = face_detector.model if isinstance(face_detector, CascadeFaceDetector) else None
         self._face_note_logged = False
 
     def _ctx(self) -> "_native.Context":
@@ -320,18 +439,22 @@ class ContentAnalyzer:
     # -- forbidden zones (tiling_module.py:323-370) --------------------------------------------------------------
     def _zone_rects(self, host_image: Optional[np.ndarray], protect_faces: bool, protect_text: bool,
                     d_image: Optional[int] = None, shape=None) -> List[Box]:
-        """Face boxes grown by int(max(w, h) * 0.2) and text boxes as given; clipping is the map kernel's.  A GPU text
-        detector on this analyzer's device reads the image at ``d_image`` and needs no host copy."""
+        """Face boxes grown by int(max(w, h) * 0.2) and text boxes as given; clipping is the map kernel's.  A GPU face or
+        text detector on this analyzer's device reads the image at ``d_image`` and needs no host copy."""
         if protect_text and self.text_detector is None:
             self.detect_text_regions(host_image)          # raises NotImplementedError
         text_on_device = (isinstance(self.text_detector, MserTextDetector) and d_image is not None
                           and self.text_detector.device == self.device)
-        need_host = (protect_faces and self.face_detector is not None) or (protect_text and not text_on_device)
+        faces_on_device = (isinstance(self.face_detector, CascadeFaceDetector) and d_image is not None
+                           and self.face_detector.device == self.device)
+        need_host = (protect_faces and self.face_detector is not None and not faces_on_device) or \
+                    (protect_text and not text_on_device)
         if need_host and host_image is None:
             raise ValueError("create_forbidden_zone_map: the face / text detectors are host callables and need host_image=")
         rects: List[Box] = []
         if protect_faces:
-            for x, y, w, h in self.detect_faces(host_image):
+            faces = self.face_detector.detect_device(d_image, shape) if faces_on_device else self.detect_faces(host_image)
+            for x, y, w, h in faces:
                 margin = int(max(w, h) * 0.2)
                 x1, y1 = max(0, x - margin), max(0, y - margin)
                 rects.append((x1, y1, max(0, x + w + margin - x1), max(0, y + h + margin - y1)))
@@ -349,8 +472,8 @@ class ContentAnalyzer:
                                          protect_salient: bool = True, saliency_threshold: float = 0.7,
                                          host_image: Optional[np.ndarray] = None) -> DeviceForbiddenMap:
         """create_forbidden_zone_map on a dense u8 image already in HBM: the map (and the saliency plane) stay there.
-        ``host_image``: the same image on the host, needed only when a host detector callable has to run (the GPU text
-        detector reads ``d_image``)."""
+        ``host_image``: the same image on the host, needed only when a host detector callable has to run (the GPU face and
+        text detectors read ``d_image``)."""
         h, w, cn = self._check_shape(shape, "create_forbidden_zone_map")
         rects = self._zone_rects(host_image, protect_faces, protect_text, d_image, shape)
         if protect_salient:
